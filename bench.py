@@ -7,7 +7,13 @@ scene (radiativetransfer.jl_amd/scenes.py).  One "step" = the whole of rt_run.jl
 resident scene: every layer's elemental -> doubling -> interaction, the surface, post-processing,
 and (N > 1) the ONE RCCL all-gather of the R/T spectra.  Inputs are in HBM before the timed region.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `config`).
+`--dump-outputs DIR` writes the spectra of the last timed step as DIR/<name>.npy (float64; R and T, for C5 the seven arrays of
+rt_run(::RRS)); the scenes are seeded, so the same arguments give the same inputs in every run.  Everything else the benchmark
+measures or checks runs only with `--full`: the CPU baselines, `roofline` / `stages_ms` (for C2 / C3 from three serialized steps
+after the timed region), the C5 finiteness check and, in the default run, `extra` (Voigt, C1 / C4 / C5, Float32, Dual).
 
 N > 1: one process per GPU.  The driver's launcher (`python -m torch.distributed.run ... bench.py --gpus N`)
 sets WORLD_SIZE/RANK/LOCAL_RANK; started WITHOUT it, `--gpus N` spawns that launcher as a child process before
@@ -21,8 +27,8 @@ Other workloads (`--workload`): C1 (scalar, N = 4: lane-per-point kernel), C3 (B
 29 944 points; `--scaling strong` splits that FIXED axis over the ranks), C4 (IQUV, 64 streams, N = 256), C5 (rotational
 Raman, N = 15, 6 837 points x 178 Raman lines: HBM-bound pair kernels).  Prints ONE JSON line on rank 0 (contract in
 the task description).  Weak scaling (default): every rank owns `--points` spectral points of a global axis of
-N x points; ndoubl / interface codes are computed on the global axis.  The default run (C2, one GPU) also carries
-`extra.workloads.{C1,C4,C5}` -- each with its own `roofline` and `cpu_baseline` -- and `extra.f32`, so that the other
+N x points; ndoubl / interface codes are computed on the global axis.  The default run (C2, one GPU) with `--full` also
+carries `extra.workloads.{C1,C4,C5}` -- each with its own `roofline` and `cpu_baseline` -- and `extra.f32`, so that the other
 regimes are driver-timed too (`--no-extras` skips them).
 """
 import argparse
@@ -43,6 +49,26 @@ PEAK_FP64_MFMA_TFLOPS = 78.6  # AMD MI355X FP64 matrix spec; v_mfma_f64_16x16x4 
 PEAK_HBM_GBS = 8000.0         # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achievable)
 PEAK_FP32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: FP32 matrix
 DEFAULT_POINTS = {"C2": 10_000, "C1": 200_000, "C3": 29_944, "C4": 2_000, "C5": 6_837}
+DUMP_BYTES_MAX = 60_000_000   # --dump-outputs: below 64 MB in all, the .npy headers included
+RRS_OUTPUTS = ("R", "T", "ieR", "ieT", "hdr", "bhr_uw", "bhr_dw")   # the return tuple of rt_run(::RRS)
+
+
+def save_outputs(a, names, arrays):
+    """The spectra of the last timed step, every array with the spectral axis last.  --dump-spectra: the first five (those of
+    shape [nVza, nStokes, S]) stacked in one file; --dump-outputs: each as DIR/<name>.npy in float64.  Above DUMP_BYTES_MAX in
+    all, the same fixed seeded sample of spectral points is taken from every array."""
+    if a.dump_spectra:
+        np.save(a.dump_spectra, np.stack(arrays[:5]))
+    if not a.dump_outputs:
+        return
+    total = sum(x.nbytes for x in arrays)
+    if total > DUMP_BYTES_MAX:
+        S = arrays[0].shape[-1]
+        keep = np.sort(np.random.default_rng(0).choice(S, S * DUMP_BYTES_MAX // total, replace=False))
+        arrays = [x[..., keep] for x in arrays]
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    for name, x in zip(names, arrays):
+        np.save(os.path.join(a.dump_outputs, f"{name}.npy"), np.ascontiguousarray(x, dtype=np.float64))
 
 
 def cpu_baseline(model, workload, budget_s=12.0):
@@ -222,13 +248,33 @@ def elastic_leg(a, workload, S_loc, steps, warmup, world, rank, dev, dist, with_
         mine = np.concatenate([np.transpose(R_loc, (2, 1, 0)).reshape(-1), np.transpose(T_loc, (2, 1, 0)).reshape(-1)])
         got = (Gh if backend == "gloo" else G.cpu()).numpy().reshape(world, 2 * nout)
         assert np.array_equal(got[rank], mine) and np.all(np.isfinite(got)), "all-gather returned wrong data"
-        if a.dump_spectra and rank == 0:     # [world][R|T][S_loc, nStokes, nVza] -> R, T [nVza, nStokes, S_tot]
+        if (a.dump_spectra or a.dump_outputs) and rank == 0:     # [world][R|T][S_loc, nStokes, nVza] -> R, T [nVza, nStokes, S_tot]
             g5 = got.reshape(world, 2, S_loc, shard.nStokes, len(shard.node))
             RT_full = np.transpose(g5, (1, 4, 3, 0, 2)).reshape(2, len(shard.node), shard.nStokes, S_tot)
-            np.save(a.dump_spectra, RT_full)
-    elif a.dump_spectra:
-        R_loc, T_loc = h.get_RT()
-        np.save(a.dump_spectra, np.stack([R_loc, T_loc]))
+            save_outputs(a, ("R", "T"), list(RT_full))
+    elif a.dump_spectra or a.dump_outputs:
+        save_outputs(a, ("R", "T"), list(h.get_RT()))
+    out = None
+    if rank == 0:
+        N, M = scene.N, scene.M
+        nd = scene.ndoubl.astype(np.float64)
+        names = {"C2": "O2-A band IQU scene", "C3": "OCO-2-style 3-band IQU scene (BASELINE configs[2])"}
+        out = {
+            "metric": f"spectral points/sec (whole node), {names.get(workload, workload + ' scene')}",
+            "value": S_tot / (el / steps),
+            "unit": "spectral points/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+            "ms_per_step": el / steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"{workload}: N={N} ({N // scene.nStokes} streams x {scene.nStokes} Stokes), Nz={scene.Nz}, "
+                                   f"M={M}, S={S_loc}/GPU ({S_tot} in total), sum(ndoubl)={int(nd.sum())}, Lambertian surface, "
+                                   f"{len(scene.node)} VZA",
+                       "sharding": f"spectral axis, {world} x {S_loc} points, one all-gather of R||T" if world > 1 else "none",
+                       "collective": collective,
+                       "devices": "all ranks on GPU 0 (--share-device)" if a.share_device else "one GPU per rank"},
+        }
+    if not a.full:
+        h.close()
+        return out
     tm = h.timers()  # of the last step, HIP events on the library's stream
     kernel_timing = "HIP events of the last timed step on the library's stream"
     if tm["reduced_launches"] > 0 and tm["full_launches"] > 0 and "9=0" not in a.opt:
@@ -250,10 +296,7 @@ def elastic_leg(a, workload, S_loc, steps, warmup, world, rank, dev, dist, with_
         kernel_timing = ("HIP events of 3 steps with MOM_OPT_OVERLAP = 0 run directly after the timed region (in the timed steps the "
                          f"two problem sizes run concurrently on two streams: layer sweep of the last timed step {tm_ov['layers_ms']:.2f} ms "
                          f"against {tm['layers_ms']:.2f} ms serialized)")
-    out = None
     if rank == 0:
-        N, M = scene.N, scene.M
-        nd = scene.ndoubl.astype(np.float64)
         # ALGORITHMIC flop of the layer kernels per spectral point and Fourier moment (the surface
         # interaction runs in k_surface): GEMM = 2N^3, inverse = 2N^3, matvec = 2N^2 -- the reference's op list
         # on the FULL N x N operators, whatever the kernels do internally (Neumann series, m = 0 sub-problem)
@@ -318,24 +361,10 @@ def elastic_leg(a, workload, S_loc, steps, warmup, world, rank, dev, dist, with_
                     "pmc_source": ("profiles/traffic.json: " + prof.get("source", prof.get("round", "?"))) if prof else None,
                     "traffic_all_launches_of_the_pmc_pass": prof.get("hbm_bytes_all_launches_of_the_pass"),
                     "kernel_timing": kernel_timing}
-        names = {"C2": "O2-A band IQU scene", "C3": "OCO-2-style 3-band IQU scene (BASELINE configs[2])"}
-        out = {
-            "metric": f"spectral points/sec (whole node), {names.get(workload, workload + ' scene')}",
-            "value": S_tot / (el / steps),
-            "unit": "spectral points/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-            "ms_per_step": el / steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"{workload}: N={N} ({N // scene.nStokes} streams x {scene.nStokes} Stokes), Nz={scene.Nz}, "
-                                   f"M={M}, S={S_loc}/GPU ({S_tot} in total), sum(ndoubl)={int(nd.sum())}, Lambertian surface, "
-                                   f"{len(scene.node)} VZA",
-                       "sharding": f"spectral axis, {world} x {S_loc} points, one all-gather of R||T" if world > 1 else "none",
-                       "collective": collective,
-                       "devices": "all ranks on GPU 0 (--share-device)" if a.share_device else "one GPU per rank"},
-            "roofline": roof,
-            "stages_ms": {k: tm[k] for k in ("layers_ms", "full_layers_ms", "reduced_layers_ms", "surface_ms",
-                                             "postprocess_ms", "total_ms")},
-            "stages_timing": kernel_timing,
-        }
+        out["roofline"] = roof
+        out["stages_ms"] = {k: tm[k] for k in ("layers_ms", "full_layers_ms", "reduced_layers_ms", "surface_ms",
+                                               "postprocess_ms", "total_ms")}
+        out["stages_timing"] = kernel_timing
         if world == 1 and with_cpu:
             out["cpu_baseline"] = cpu_baseline(model, workload, budget_s=cpu_budget)
     h.close()
@@ -419,14 +448,29 @@ def c5_leg(a, S, steps, warmup, dev, with_cpu=True, world=1, rank=0, dist=None):
         res = h.get_RT_rrs()[:4] + h.get_hdr_rrs()
         own = [np.ascontiguousarray(r[..., lo - wlo:hi - wlo].T).reshape(-1) for r in res]   # ABI order: spectral index slowest
         assert np.array_equal(got[rank], np.concatenate(own)) and np.all(np.isfinite(got)), "all-gather returned wrong data"
-        if a.dump_spectra and rank == 0:
-            np.save(a.dump_spectra, np.stack(rtamd.sharding.unpack_rrs_spectra(got, len(sc.node), sc.nStokes, per)[:5]))
-    elif a.dump_spectra:
-        np.save(a.dump_spectra, np.stack(h.get_RT_rrs()[:4] + h.get_hdr_rrs()[:1]))
+        if (a.dump_spectra or a.dump_outputs) and rank == 0:
+            save_outputs(a, RRS_OUTPUTS, rtamd.sharding.unpack_rrs_spectra(got, len(sc.node), sc.nStokes, per))
+    elif a.dump_spectra or a.dump_outputs:
+        save_outputs(a, RRS_OUTPUTS, h.get_RT_rrs()[:4] + h.get_hdr_rrs())
+    N, nR = sc.N, RS.n_Raman
+    out = None
+    if rank == 0:
+        out = {"metric": "spectral points/sec (whole node), C5 rotational-Raman scene", "value": S_tot / (el / steps),
+               "unit": "spectral points/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": el / steps * 1e3,
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+               "config": {"workload": f"C5: RRS, N={N} (5 streams x 3 Stokes), Nz={sc.Nz}, M={sc.M}, S={S}/GPU ({S_tot} in total), "
+                                      f"nRaman={nR}, sum(ndoubl)={int(sc.ndoubl.sum())}, "
+                                      f"rrs_strict_reference={int(RS.rrs_strict_reference)}, Lambertian surface, 1 VZA",
+                          "sharding": "none" if world == 1 else
+                          f"contiguous spectral slices + recomputed halo of max|i_l1l0| = {int(np.abs(RS.i_λ1λ0).max())} points "
+                          f"(rank 0 window: {whi - wlo} points)",
+                          "collective": collective}}
+    if not a.full:
+        h.close()
+        return out
     tk = h.rrs_timers()
     res = h.get_RT_rrs()
     assert np.all(np.isfinite(res[2][..., lo - wlo:hi - wlo])) and np.abs(res[2]).max() > 0
-    N, nR = sc.N, RS.n_Raman
     pairs = int(sum(max(0, min(hi, S_tot - int(o)) - max(lo, -int(o))) for o in RS.i_λ1λ0))  # owned n1 with n1 + offset on the grid
     bytes_pair = (4 * N * N + 4 * N) * 8
     ms, nl = tk["dbl_pair"]
@@ -440,22 +484,12 @@ def c5_leg(a, S, steps, warmup, dev, with_cpu=True, world=1, rank=0, dist=None):
     ms_i, nl_i = tk["int_pair"]
     avg_i = ms_i / max(nl_i, 1)
     gbs_i = pairs * bytes_pair_int / (avg_i * 1e-3) / 1e9 if nl_i else 0.0
-    out = None
     if rank == 0:
         prof = {}
         tf = ROOT / "profiles" / "traffic.json"
         if tf.exists():
             prof = json.loads(tf.read_text()).get("C5", {})
-        out = {"metric": "spectral points/sec (whole node), C5 rotational-Raman scene", "value": S_tot / (el / steps),
-               "unit": "spectral points/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": el / steps * 1e3,
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-               "config": {"workload": f"C5: RRS, N={N} (5 streams x 3 Stokes), Nz={sc.Nz}, M={sc.M}, S={S}/GPU ({S_tot} in total), "
-                                      f"nRaman={nR}, sum(ndoubl)={int(sc.ndoubl.sum())}, "
-                                      f"rrs_strict_reference={int(RS.rrs_strict_reference)}, Lambertian surface, 1 VZA",
-                          "sharding": "none" if world == 1 else
-                          f"contiguous spectral slices + recomputed halo of max|i_l1l0| = {int(np.abs(RS.i_λ1λ0).max())} points "
-                          f"(rank 0 window: {whi - wlo} points)",
-                          "collective": collective},
+        out.update({
                "roofline": {"bound": "hbm", "achieved": gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBS,
                             "traffic": prof.get("hbm_bytes_per_launch"), "kernel": "momr::k_dbl_pair1<FUSE, MODE> (one-tile doubling pair kernel)",
                             "pmc_source": ("profiles/traffic.json: " + prof.get("source", prof.get("round", "?"))) if prof else None,
@@ -466,7 +500,7 @@ def c5_leg(a, S, steps, warmup, dev, with_cpu=True, world=1, rank=0, dist=None):
                                      "avg_launch_ms": avg_i, "launches_per_step": nl_i, "pairs_per_launch": pairs,
                                      "algorithmic_bytes_per_pair": bytes_pair_int},
                "stages_ms": {"dbl_pair_ms": tk["dbl_pair"][0], "int_pair_ms": tk["int_pair"][0],
-                             "ie_elemental_ms": tk["ie_elemental"][0], "total_ms": tk["total"][0]}}
+                             "ie_elemental_ms": tk["ie_elemental"][0], "total_ms": tk["total"][0]}})
     h.close()
     if with_cpu and rank == 0 and world == 1:
         out["cpu_baseline"] = c5_cpu_baseline(S)
@@ -636,10 +670,16 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip extra.workloads / extra.f32 of the default run")
     ap.add_argument("--dump-spectra", default="", metavar="FILE.npy",
                     help="rank 0 saves the gathered spectra of the last step (parity of an N-rank run against the 1-rank run)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 saves the spectra of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, roofline / stage figures, checks and (default run) the extra legs")
     ap.add_argument("--opt", action="append", default=[], metavar="ID=VALUE", help="mom_set_option(ID, VALUE) before the scene is set (kernel A/B runs)")
     a = ap.parse_args()
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.share_device and a.backend != "gloo":
         ap.error("--share-device needs --backend gloo (RCCL refuses two ranks on one GPU)")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -674,14 +714,16 @@ def main():
                 dist.init_process_group("gloo")
 
     S_loc = a.points or DEFAULT_POINTS[a.workload]
+    with_cpu = a.full and not a.no_cpu_baseline
     if a.workload == "C5":
-        out = c5_leg(a, S_loc, a.steps, a.warmup, dev, with_cpu=not a.no_cpu_baseline, world=world, rank=rank, dist=dist)
+        out = c5_leg(a, S_loc, a.steps, a.warmup, dev, with_cpu=with_cpu, world=world, rank=rank, dist=dist)
     else:
-        out = elastic_leg(a, a.workload, S_loc, a.steps, a.warmup, world, rank, dev, dist, with_cpu=not a.no_cpu_baseline)
+        out = elastic_leg(a, a.workload, S_loc, a.steps, a.warmup, world, rank, dev, dist, with_cpu=with_cpu)
     if rank == 0:
         default_run = a.workload == "C2" and world == 1 and not a.points
-        if world == 1 and a.workload == "C2":
+        if world == 1 and a.workload == "C2" and a.full:
             extra = {}
+            a = argparse.Namespace(**{**vars(a), "dump_spectra": "", "dump_outputs": ""})   # the legs below keep the headline's files
             if not a.no_voigt:
                 try:
                     extra["voigt"] = voigt_leg()
@@ -691,11 +733,11 @@ def main():
                 legs = {}
                 for wl, pts, st in (("C1", DEFAULT_POINTS["C1"], 3), ("C4", 256, 1)):
                     try:
-                        legs[wl] = elastic_leg(a, wl, pts, st, 1, 1, 0, dev, None, with_cpu=not a.no_cpu_baseline, cpu_budget=6.0)
+                        legs[wl] = elastic_leg(a, wl, pts, st, 1, 1, 0, dev, None, with_cpu=with_cpu, cpu_budget=6.0)
                     except Exception as e:
                         legs[wl] = {"error": repr(e)}
                 try:
-                    legs["C5"] = c5_leg(a, DEFAULT_POINTS["C5"], 2, 1, dev, with_cpu=not a.no_cpu_baseline)
+                    legs["C5"] = c5_leg(a, DEFAULT_POINTS["C5"], 2, 1, dev, with_cpu=with_cpu)
                 except Exception as e:
                     legs["C5"] = {"error": repr(e)}
                 extra["workloads"] = legs
@@ -704,7 +746,7 @@ def main():
                 except Exception as e:
                     extra["f32"] = {"error": repr(e)}
                 try:
-                    extra["dual"] = dual_leg(dev, with_cpu=not a.no_cpu_baseline)
+                    extra["dual"] = dual_leg(dev, with_cpu=with_cpu)
                 except Exception as e:
                     extra["dual"] = {"error": repr(e)}
             if extra:

@@ -119,7 +119,7 @@ def test_bench_C5_two_ranks():
     """`python bench.py --workload C5 --gpus 2`: the RRS leg shards with halos and reports the whole-job rate."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "C5", "--gpus", "2", "--backend", "gloo", "--share-device",
-                          "--points", "600", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
+                          "--points", "600", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     j = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -193,3 +193,16 @@ def test_bench_C5_two_ranks_gathered_spectra_bitwise(tmp_path):
     assert a.shape == b.shape == (5,) + a.shape[1:] and a.shape[-1] == 1200
     assert np.abs(a[2]).max() > 0
     assert np.array_equal(a, b)
+
+
+def test_bench_dump_outputs_are_the_rt_run_spectra(tmp_path, rtamd):
+    """`bench.py --dump-outputs DIR` (plain one-GPU run): R and T of the last timed step as DIR/R.npy, DIR/T.npy in float64,
+    the spectra rt_run returns for the same seeded scene; the line reports the timed steps it ran."""
+    import helpers
+    j = _bench(["--points", "512", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["dtype"] == "f64" and "roofline" not in j
+    R, T = np.load(tmp_path / "R.npy"), np.load(tmp_path / "T.npy")
+    assert R.dtype == T.dtype == np.float64 and R.shape == (3, 3, 512)
+    Rr, Tr = rtamd.rt_run(rtamd.scenes.scene_C2(S=512))[:2]
+    helpers.assert_stokes_close(R, Rr, what="dumped R")
+    helpers.assert_stokes_close(T, Tr, what="dumped T")
