@@ -477,11 +477,16 @@ int mom_timers(mom_t *h, double *ms, int n, int *kernel_launches);
  *                         (r5 read these from environment variables, once per process.)
  *   MOM_OPT_DUAL_WORKSPACE_MB   operator workspace of mom_rt_run_dual in MiB (0, default: 60 % of the free HBM when the run
  *                         starts); a scene that needs more is processed in chunks of spectral points.
+ *   MOM_OPT_STRIP2        operators of edge 52 / 56 / 60 (Float64, layer-sweep mode, ScatteringInterface_11 after the first layer,
+ *                         stream-pair tables that fit the front of one operator buffer): 1 (default) = the TWO-BUFFER 4-wave strip
+ *                         image runs them first, two workgroups per CU (csrc/mom_strip2.hpp), and the 8-wave image finishes
+ *                         whatever it left (series beyond 12 terms) -- two launches per sweep, both counted in mom_timers'
+ *                         kernel_launches; results are bitwise those of the 8-wave image.  0 = the 8-wave image only.
  */
 int mom_set_option(mom_t *h, int option, int value);
 enum { MOM_OPT_INVERSE = 0, MOM_OPT_FORCE_GENERIC = 1, MOM_OPT_M0_REDUCTION = 2, MOM_OPT_SMALL_WG = 3, MOM_OPT_STAGGER = 4,
        MOM_OPT_SMALL_N = 5, MOM_OPT_LAYER_SWEEP = 6, MOM_OPT_STRIP_PAD = 7, MOM_OPT_LEAN = 8, MOM_OPT_OVERLAP = 9,
-       MOM_OPT_RRS_KERNELS = 10, MOM_OPT_DUAL_WORKSPACE_MB = 11 };
+       MOM_OPT_RRS_KERNELS = 10, MOM_OPT_DUAL_WORKSPACE_MB = 11, MOM_OPT_STRIP2 = 12 };
 
 /* ---- Voigt line-by-line cross section --------------------------------------------------
  * compute_absorption_cross_section(model::HitranModel, grid, p, T)

@@ -38,6 +38,7 @@ MOM_OPT_LEAN = 8
 MOM_OPT_OVERLAP = 9
 MOM_OPT_RRS_KERNELS = 10   # mask: 1 WG pairs, 2 ... for 16 < N <= 32, 4 WG points, 8 tile elemental, 16 / 32 fused elemental always / never
 MOM_OPT_DUAL_WORKSPACE_MB = 11   # operator workspace of mom_rt_run_dual (0: 60 % of the free HBM)
+MOM_OPT_STRIP2 = 12              # N = 52, 56, 60 on the two-buffer 4-wave image first (1, default), 0 = the 8-wave image only
 
 
 class MomError(RuntimeError):

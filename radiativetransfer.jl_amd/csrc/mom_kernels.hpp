@@ -1095,8 +1095,11 @@ __device__ __forceinline__ void wg_prologue(Ctx &c, const DevStreams &q, real *s
 // ---------------------------------------------------------------------------------------
 // elemental! into c.r (r-+), c.t (t++), c.jp, c.jm.  Zpp(i,j), Zmp(i,j): phase-matrix
 // element functors for this spectral point.  Ends with a barrier.
+// HOLDT (two-buffer strip image, mom_strip2.hpp: the tables live at the front of t's buffer): the t entries of the first batch
+// of eight slots stay in registers until the tables are no longer read; every later entry lies behind the tables (the host
+// checks it, s2_applies) and is stored at once.
 // ---------------------------------------------------------------------------------------
-template <class FZP, class FZM>
+template <bool HOLDT = false, class FZP, class FZM>
 __device__ __forceinline__ void elemental_build(const Ctx &c, const DevStreams &q, int m, int nd, real tau_sum,
                                                 real dtau, real varpi, FZP Zpp, FZM Zmp) {
   const int N = c.N, ld = c.ld, n = q.nS;
@@ -1123,6 +1126,8 @@ __device__ __forceinline__ void elemental_build(const Ctx &c, const DevStreams &
   // loads stay coalesced (consecutive lanes = consecutive rows of one column).  Slot s -> (row block, column slot).
   // (4-wave build: the operators there have N <= 48, most lanes of a row block would idle -- plain linear order.)
   constexpr bool kRowLanes = kWaves >= 8;
+  static_assert(!HOLDT || (!kRowLanes && kWaves > 1), "HOLDT: linear element order, eight slots held");
+  real th[8];
   const int lane_e = wg_lane(), wave_e = wg_wave(), tid_e = wg_tid();
   const int CS = (N + kWaves - 1) / kWaves;
   const int slots = kRowLanes ? ((N + 63) >> 6) * CS : (N * N + kThreads - 1) / kThreads;
@@ -1273,7 +1278,8 @@ __device__ __forceinline__ void elemental_build(const Ctx &c, const DevStreams &
           }
           if (nd >= 1) rr *= c.sg[i];  // apply_D_elemental!, elemental.jl:265-269
           c.r[i + j * ld] = rr;
-          c.t[i + j * ld] = tt;
+          if (HOLDT && s0 == 0) th[u] = tt;
+          else c.t[i + j * ld] = tt;
         }
       }
     };
@@ -1308,6 +1314,13 @@ __device__ __forceinline__ void elemental_build(const Ctx &c, const DevStreams &
     c.jm[i] = jm;
   }
   __syncthreads();
+  if constexpr (HOLDT) {  // the tables are read: the held t entries go home
+    coords(0);
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (ok[u]) c.t[ii[u] + jj[u] * ld] = th[u];
+    __syncthreads();
+  }
   MOM_STAMP(48);
   // P and Q served as table space (linear: the sun-block Z columns land in P's padding rows): their K padding must read
   // as zero again -- always in the Float32 build, whose strip chains run every k-step of the last row tile (r4: without

@@ -1,0 +1,420 @@
+// mom_strip2.hpp -- the TWO-BUFFER 4-wave strip image (r7): Float64, N = 52, 56, 60 (KS = 13 .. 15), TWO workgroups per CU.
+//
+// Why (profiles/r05_phase_stamps_n60.txt): the 8-wave N = 60 image holds r, t, P, Q (4 x 32.7 KB) + vectors + the
+// stream-pair tables, 149 KB: one workgroup per CU.  72 % of its time is inside the strip chains, where one wave per SIMD keeps
+// the matrix pipe saturated; the other 28 % (elemental layer, composite loads, the B product, write-backs, barriers) leave the
+// pipe idle, and in the doubling steps (56 % of the kernel) waves 4 .. 7 only wait at the barriers.  Only a second independent
+// unit on the CU can fill those gaps.  This image:
+//   * buffers r and t only (2 x 32.7 KB at N = 60) + vectors with `part` cut to its 16 norm slots + a 128-real layer tail:
+//     74.8 KB, two workgroups per CU;
+//   * four waves, one column strip each (N = 52 .. 60: four 16-row tiles);
+//   * elemental layer: its tables (E, F1, F2 and the sun-block columns) in t's buffer; elemental_build<true> keeps the t entries
+//     of its first batch -- the only ones whose addresses can meet the tables -- in registers and stores them after the tables
+//     are done (s2_applies checks that the tables end below the first directly stored entry);
+//   * doubling: P = r r overwrites t's buffer (each wave its own strip, whose t^T strip it holds in registers for the Horner loop
+//     anyway); after the series and (A r)^T, t is restored from those registers (two barriers more per step);
+//   * interaction (interface 11): R+- staged in r's buffer (r's strip held in registers), B over it, the two Horner chains, r
+//     restored, the products with r and t, then T++ staged in t's buffer for the last two products;
+//   * anything else -- a series beyond kStripMaxP terms, a forced pivoted inverse -- is not computed here: the workgroup records
+//     the layer in resume[unit] and leaves the unit; nothing of that layer has reached the composite state in global memory, so
+//     the 8-wave image's launch behind it (LayerArgs::resume) redoes the layer and carries the unit to the end.
+// Every product is the one of the 8-wave image's strip path (mom_strip.hpp) on the same operands in the same order: the results
+// are bitwise those of the 8-wave image.
+// Scope: Float64, 4-wave build, sweep mode, single composite (no multi-target), interface 11 on every layer after the first.
+#pragma once
+#include "mom_entry.hpp"
+
+namespace MOM_NS {
+
+constexpr int kS2Lay = 128;  // reals of the layer-scalar tail
+__host__ __device__ inline size_t s2_vec_reals(int N) { return part_offset_doubles(N) + 16; }
+__host__ __device__ inline size_t s2_lds_bytes(int N) { return (2 * mat_elems(N) + s2_vec_reals(N) + kS2Lay) * sizeof(real); }
+// the elemental layer's table space at the front of t's buffer: E | F1 | F2 per stream pair (when they fit a buffer, as in
+// elemental_build) and the sun-block columns, 2 nS columns of N
+__host__ __device__ inline int s2_table_reals(int N, int ns, int nS) {
+  const int Nq = N / (ns > 0 ? ns : 1);
+  const bool tab = 3 * Nq * Nq <= (int)mat_elems(N);
+  return (tab ? 3 * Nq * Nq : 0) + 2 * nS * N;
+}
+// t-buffer offset of the first element that elemental_build<true> stores directly: element 8 kThreads (slot 8 of the linear order)
+__host__ __device__ inline int s2_direct_offset(int N) {
+  const int e = 8 * kThreads;
+  return (e % N) + (e / N) * ld_for(N);
+}
+// does the image apply to operators of edge N with ns Stokes components per stream (nS per stream-pair table row)?
+__host__ __device__ inline bool s2_applies(int N, int ns, int nS) {
+  return kF64 && kWaves == 4 && (N == 52 || N == 56 || N == 60) && N * N > 8 * kThreads &&
+         s2_table_reals(N, ns, nS) <= s2_direct_offset(N) && 2 * (s2_lds_bytes(N) + 1024) <= kLdsPerCU;
+}
+
+__device__ __forceinline__ void make_ctx_s2(Ctx &c, int N, int inv_mode, int ns, real *smem) {
+  c.N = N;
+  c.Np = np_for(N);
+  c.nc = cols_for(N);
+  c.ld = ld_for(N);
+  c.ldv = c.Np;
+  c.fd.init(N);
+  c.inv_mode = inv_mode;
+  c.qpre = 0;
+  c.slot = 0;
+  c.ptab = nullptr;
+  const size_t msz = mat_elems(N);
+  c.r = smem; c.t = smem + msz; c.P = nullptr; c.Q = nullptr; c.X = nullptr;
+  real *p = smem + 2 * msz;
+  const int lv = c.ldv;
+  c.jp = p; c.jm = p + lv; c.j1p = p + 2 * lv; c.j1m = p + 3 * lv; c.v1 = p + 4 * lv; c.v2 = p + 5 * lv;
+  c.Jp = p + 6 * lv; c.Jm = p + 7 * lv; c.prow = p + 8 * lv; c.pcol = p + 9 * lv; c.rowk = p + 10 * lv;
+  c.ei = p + 11 * lv; c.mu = p + 12 * lv; c.wt = p + 13 * lv; c.sg = p + 14 * lv;
+  c.thr = p + 15 * lv;
+  int *ip = reinterpret_cast<int *>(c.thr + 32);
+  c.ipiv = ip; c.sh = ip + lv; c.bad = ip + lv + 1;
+  c.part = p + part_offset_doubles(N);
+  const int Nq = N / (ns > 0 ? ns : 1);
+  c.tabE = c.t;
+  c.tabZS = c.t + ((3 * Nq * Nq <= (int)msz) ? 3 * Nq * Nq : 0);
+}
+
+// One doubling step (doubling.jl:44-67) in two buffers; returns false, before anything of the step is stored, if it needs the
+// general path.  In: c.r (riding columns N, N + 1 = j0+, j0-), c.t, c.jp, c.jm; out: the same, as doubling_step_strip.
+template <int KS>
+__device__ __forceinline__ bool doubling_step_s2(Ctx &c, real expk) {
+  using G = StripGeom<KS>;
+  constexpr int N = G::N, NT = G::NT, LD = G::LD;
+  static_assert(NT == kWaves, "two-buffer image: one column strip per wave");
+  const int lane = wg_lane(), wave = wg_wave(), lr = lane & 15, lq = lane >> 4;
+  const int c0 = 16 * wave, col = c0 + lr;
+  const bool colok = col < N;
+  real *r = c.r, *t = c.t;
+  real *P = c.t;  // P = r r lives in t's buffer until t is restored
+  r4 T0[NT];
+  strip_load_lds<KS>(t, lr, lq, c0, T0);
+  // ---- P = r r (+ riding columns r j0+, r j0-) and ||r r||_F^2 (doubling_rr_strip); this wave's strip of P goes to exactly
+  // the addresses its T0 load has just read, and the riding columns N, N + 1 of t are read by no product that is stored
+  real ss = 0.0;
+  {
+    r4 W[NT], B[NT];
+    strip_load_lds<KS>(r, lr, lq, c0, W);
+    strip_zero(B);
+    strip_mul<KS>(r, lr, lq, W, B);
+    strip_store_lds<KS>(P, lr, lq, c0, colok, B);
+    if (colok) {
+      if (lq == G::LQ0) P[col + N * LD] = B[G::RT][G::RR0];        // (r j0+)[col]
+      if (lq == G::LQ1) P[col + (N + 1) * LD] = B[G::RT][G::RR1];  // (r j0-)[col]
+#pragma unroll
+      for (int rt = 0; rt < NT; ++rt)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr)
+          if (strip_rowok<KS>(rt, rr, lq)) ss += B[rt][rr] * B[rt][rr];
+    }
+  }
+  wg_sumsq_put(c, ss);
+  __syncthreads();
+  const real beta2 = wg_sumsq_get(c);
+  const int p = __builtin_amdgcn_readfirstlane(neumann_terms_12(beta2));
+  if (p > kStripMaxP || c.inv_mode != 0) return false;
+  // riding rows of the multiplier r^T: w1 = j1- + r j0+, w2 = j0+ + r j1-  (doubling.jl:51-60); every wave writes the same values
+  if (lane < N) {
+    r[lane + N * LD] = c.jm[lane] * expk + P[lane + N * LD];
+    r[lane + (N + 1) * LD] = c.jp[lane] + expk * P[lane + (N + 1) * LD];
+  }
+  r4 Y[NT];
+  strip_copy(Y, T0);
+  // Y = A^T = (t (I - r r)^-1)^T by Horner: Y <- t^T + (r r)^T Y
+#pragma nounroll
+  for (int k = 1; k < p; ++k) {
+    r4 acc[NT];
+    strip_copy(acc, T0);
+    strip_mul<KS>(P, lr, lq, Y, acc);
+    strip_copy(Y, acc);
+  }
+  r4 Zt[NT];
+  strip_zero(Zt);
+  strip_mul<KS>(r, lr, lq, Y, Zt);  // (A r)^T ; rows N, N+1: (A w1)^T, (A w2)^T
+  const real aw = Zt[G::RT][G::RR0], aw2 = Zt[G::RT][G::RR1];
+  __syncthreads();  // every wave is done with P
+  strip_store_lds<KS>(t, lr, lq, c0, colok, T0);  // t back
+  __syncthreads();
+  r4 Rn[NT], Tn[NT];
+  strip_load_lds<KS>(r, lr, lq, c0, Rn);
+  strip_mul<KS>(t, lr, lq, Zt, Rn);  // r^T + t^T (A r)^T      (:64)
+  strip_zero(Tn);
+  strip_mul<KS>(t, lr, lq, Y, Tn);   // t^T A^T                (:67)
+  __syncthreads();  // every wave is done reading r and t of this step
+  strip_store_lds<KS>(r, lr, lq, c0, colok, Rn);
+  strip_store_lds<KS>(t, lr, lq, c0, colok, Tn);
+  if (colok && lq == G::LQ0) {  // j0- += A w1 (:57)
+    const real jm = c.jm[col] + aw;
+    c.jm[col] = jm;
+    r[col + (N + 1) * LD] = jm;
+  }
+  if (colok && lq == G::LQ1) {  // j0+ = j1+ + A w2 (:60)
+    const real jp = c.jp[col] * expk + aw2;
+    c.jp[col] = jp;
+    r[col + N * LD] = jp;
+  }
+  __syncthreads();
+  return true;
+}
+
+// nd doubling steps; bail = true (nothing of the layer has left the workgroup) if a step needs the general path
+template <int KS>
+__device__ __forceinline__ real doubling_run_s2(Ctx &c, int nd, real expk, bool &bail) {
+  const int N = c.N, ld = c.ld;
+  bail = false;
+  if (nd == 0) return expk;
+  for (int i = wg_tid(); i < N; i += kThreads) {
+    c.r[i + N * ld] = c.jp[i];
+    c.r[i + (N + 1) * ld] = c.jm[i];
+  }
+  __syncthreads();
+  for (int it = 0; it < nd; ++it) {
+    if (!doubling_step_s2<KS>(c, expk)) {
+      bail = true;
+      return expk;
+    }
+    expk = expk * expk;
+  }
+  // apply_D! (doubling.jl:93-110) and apply_D_SFI! (:112-118): r-+ rows and j0- scaled by sg
+  real *r = c.r;
+  for (int e = wg_tid(); e < N * N; e += kThreads) {
+    int i, j;
+    c.fd.split(e, i, j);
+    r[i + j * ld] *= c.sg[i];
+  }
+  for (int i = wg_tid(); i < N; i += kThreads) {
+    c.jm[i] *= c.sg[i];
+    r[i + N * ld] = 0.0; r[i + (N + 1) * ld] = 0.0;
+  }
+  __syncthreads();
+  return expk;
+}
+
+// ScatteringInterface_11 in two buffers (see interaction_strip for the algebra; same products, same order).  Returns false,
+// nothing stored, if the series is too long.  Ends with a barrier.
+template <int KS>
+__device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) {
+  using G = StripGeom<KS>;
+  constexpr int N = G::N, NT = G::NT, LD = G::LD, NN = N * N, U = (NN + kThreads - 1) / kThreads;
+  static_assert(NT == kWaves, "two-buffer image: one column strip per wave");
+  const int lane = wg_lane(), wave = wg_wave(), lr = lane & 15, lq = lane >> 4;
+  const int c0 = 16 * wave, col = c0 + lr;
+  const bool colok = col < N;
+  real *r = c.r, *t = c.t;
+  // ---- (a) r's strip into registers, R+- into r's buffer; B = r-+ R+- and W0 = R+-^T t++^T on strips
+  r4 rT[NT];
+  {
+    real vr[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int e = wg_tid() + u * kThreads;
+      if (e < NN) {
+        int i, j;
+        c.fd.split(e, i, j);
+        vr[u] = MOM_NT_LOAD(g.R_pm + i + j * G::CP);
+      }
+    }
+    strip_load_lds<KS>(r, lr, lq, c0, rT);
+    __syncthreads();  // every wave holds its strip of r
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int e = wg_tid() + u * kThreads;
+      if (e < NN) {
+        int i, j;
+        c.fd.split(e, i, j);
+        r[i + j * LD] = vr[u];
+      }
+    }
+  }
+  __syncthreads();
+  const real *Rpm = r;
+  r4 Bs[NT], W0[NT];
+  real ss = 0.0;
+  strip_zero(Bs);
+  strip_mul<KS>(Rpm, lr, lq, rT, Bs);
+  if (colok) {
+#pragma unroll
+    for (int rt = 0; rt < NT; ++rt)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr)
+        if (strip_rowok<KS>(rt, rr, lq)) ss += Bs[rt][rr] * Bs[rt][rr];
+  }
+  {
+    r4 tT[NT];
+    strip_load_lds<KS>(t, lr, lq, c0, tT);
+    strip_zero(W0);
+    strip_mul<KS>(Rpm, lr, lq, tT, W0);
+  }
+  __syncthreads();  // every wave is done with R+-
+  real *B = r;      // B replaces R+-
+  strip_store_lds<KS>(B, lr, lq, c0, colok, Bs);
+  wg_sumsq_put(c, ss);
+  __syncthreads();
+  const real beta2 = wg_sumsq_get(c);
+  const int p = __builtin_amdgcn_readfirstlane(neumann_terms_12(beta2));
+  if (p > kStripMaxP) return false;
+  const unsigned mask = strip_sign_mask(c.sg, lq, N);
+  // ---- (b) the two Horner loops, multiplier B^T
+  r4 Y1[NT], Y2[NT];
+  strip_copy(Y2, W0);
+#pragma nounroll
+  for (int k = 1; k < p; ++k) {  // Y2 <- W0 + B^T Y2 : X^T
+    r4 acc[NT];
+    strip_copy(acc, W0);
+    strip_mul<KS>(B, lr, lq, Y2, acc);
+    strip_copy(Y2, acc);
+  }
+  {
+    r4 T1[NT];
+    strip_load_glb<KS>(g.T_mm, lr, lq, c0, colok, T1);
+    strip_copy(Y1, T1);
+#pragma nounroll
+    for (int k = 1; k < p; ++k) {  // Y1 <- T--^T + B^T Y1 : T01^T
+      r4 acc[NT];
+      strip_copy(acc, T1);
+      strip_mul<KS>(B, lr, lq, Y1, acc);
+      strip_copy(Y1, acc);
+    }
+  }
+  __syncthreads();  // every wave is done with B
+  // ---- (c) r back (riding column N = j0-); the products with r and t
+  strip_store_lds<KS>(r, lr, lq, c0, colok, rT);
+  for (int i = wg_tid(); i < N; i += kThreads) r[i + N * LD] = c.jm[i];
+  __syncthreads();
+  {  // T-- = T01 t--  ->  (t--)^T T01^T = D t^T D Y1                                   (:96)
+    r4 Yf[NT], o[NT];
+    strip_copy(Yf, Y1);
+    strip_flip(Yf, mask);
+    strip_zero(o);
+    strip_mul<KS>(t, lr, lq, Yf, o);
+    strip_flip(o, mask);
+    strip_store_glb<KS>(g.T_mm, lr, lq, c0, colok, o);
+  }
+  // V = (T01 r-+)^T = r-+^T Y1 ; row N: (T01 j0-)^T
+  r4 V[NT];
+  strip_zero(V);
+  strip_mul<KS>(r, lr, lq, Y1, V);
+  // T21^T = t++^T + r-+^T X^T ; row N: (X j0-)^T
+  r4 T21[NT];
+  strip_load_lds<KS>(t, lr, lq, c0, T21);
+  strip_mul<KS>(r, lr, lq, Y2, T21);
+  {  // R+- = r+- + X t--  ->  D (D r+-^T + t^T D X^T), D r+-^T[row][col] = sg[col] r-+[col][row]   (:116)
+    r4 acc[NT];
+    const real sc = colok ? c.sg[col] : 1.0;
+#pragma unroll
+    for (int rt = 0; rt < NT; ++rt) acc[rt] = rT[rt] * sc;
+    strip_flip(Y2, mask);
+    strip_mul<KS>(t, lr, lq, Y2, acc);
+    strip_flip(acc, mask);
+    strip_store_glb<KS>(g.R_pm, lr, lq, c0, colok, acc);
+  }
+  // ---- (d) T++ (+ J0+ as its riding column N) into t's buffer; the products with T++
+  r4 Radd[NT];
+  strip_load_glb<KS>(g.R_mp, lr, lq, c0, colok, Radd);
+  const real j0m = (colok && lq == G::LQ0) ? g.J0m[col] : 0.0;
+  {
+    real vt[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int e = wg_tid() + u * kThreads;
+      if (e < NN) {
+        int i, j;
+        c.fd.split(e, i, j);
+        vt[u] = MOM_NT_LOAD(g.T_pp + i + j * G::CP);
+      }
+    }
+    const real vj = (wg_tid() < N) ? g.J0p[wg_tid()] : 0.0;
+    __syncthreads();  // every wave is done with t
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int e = wg_tid() + u * kThreads;
+      if (e < NN) {
+        int i, j;
+        c.fd.split(e, i, j);
+        t[i + j * LD] = vt[u];
+      }
+    }
+    if (wg_tid() < N) t[wg_tid() + N * LD] = vj;
+  }
+  __syncthreads();
+  const real *Tpp = t;
+  // R-+ = R-+ + (T01 r-+) T++  ->  R-+^T + T++^T V ; row N: (T01 r-+ J0+)^T        (:93)
+  strip_mul<KS>(Tpp, lr, lq, V, Radd);
+  strip_store_glb<KS>(g.R_mp, lr, lq, c0, colok, Radd);
+  // J0- = J0- + T01 (r-+ J0+ + j0-)                                                (:90)
+  if (colok && lq == G::LQ0) g.J0m[col] = j0m + (Radd[G::RT][G::RR0] + V[G::RT][G::RR0]);
+  // T++ = T21 T++  ->  T++^T T21^T ; row N: (T21 J0+)^T                            (:113)
+  {
+    r4 o[NT];
+    strip_zero(o);
+    strip_mul<KS>(Tpp, lr, lq, T21, o);
+    strip_store_glb<KS>(g.T_pp, lr, lq, c0, colok, o);
+    // J0+ = j0+ + T21 (J0+ + R+- j0-)                                                (:110)
+    if (colok && lq == G::LQ0) g.J0p[col] = c.jp[col] + (o[G::RT][G::RR0] + T21[G::RT][G::RR0]);
+  }
+  __syncthreads();
+  return true;
+}
+
+// One launch walks all layers of every unit (sweep mode only); see the header of this file for what it does not do.
+template <int KS>
+__global__ void __launch_bounds__(kThreads, 2) k_layer_s2(const LayerArgs a) {
+  // (the argument block is never written: see k_layer_lean)
+  constexpr int N = 4 * KS;
+  const size_t total = (size_t)a.S * a.M;
+  Ctx c;
+  make_ctx_s2(c, N, a.q.inv_mode, a.q.regular ? a.q.nS : 1, mom_smem);
+  zero_padding<true>(c);
+  __syncthreads();
+  load_streams(c, a.q);
+  __syncthreads();
+  real *lay = mom_smem + 2 * mat_elems(N) + s2_vec_reals(N);
+  const int nz = a.Nz_sweep;
+  const int LW = 3 + a.K, LZ = kS2Lay / LW;
+  for (size_t pt = blockIdx.x; pt < total; pt += gridDim.x) {
+    const int n = (int)(pt % a.S), mrel = (int)(pt / a.S), m = a.m_first + mrel;
+    const size_t NNs = (size_t)N * N;
+    CompPtrs g = comp_ptrs(a.comp, N, comp_pitch(N), pt);
+    int done = nz;
+    for (int z = 0; z < nz; ++z) {
+      const int zl = z % LZ;
+      if (zl == 0) {
+        const int cnt = ((nz - z < LZ) ? nz - z : LZ) * LW;
+        for (int i = wg_tid(); i < cnt; i += kThreads) {
+          const int zz = i / LW, k = i - zz * LW;
+          const size_t o = (size_t)n + (size_t)a.S * (z + zz);
+          lay[i] = (k == 0) ? as_global(a.tau)[o] : (k == 1) ? as_global(a.varpi)[o] : (k == 2) ? as_global(a.tau_sum)[o]
+                                                                                                : as_global(a.zw)[(size_t)a.K * o + (k - 3)];
+        }
+        __syncthreads();
+      }
+      const int nd = a.nd_z[z];
+      const bool first = (z == 0) && (a.first != 0);
+      const real *ls = lay + zl * LW;
+      const real tau = ls[0], varpi = ls[1], tau_sum = ls[2];
+      const real dtau = ldexp(tau, -nd);         // τ ./ 2^ndoubl   (rt_kernel.jl:244)
+      real expk = exp(-dtau / a.q.mu0);          // init_layer      (rt_kernel.jl:273)
+      ZMix zpp{as_global(a.Zpp) + NNs * a.K * mrel, ls + 3, a.K, N};
+      ZMix zmp{as_global(a.Zmp) + NNs * a.K * mrel, ls + 3, a.K, N};
+      elemental_build<true>(c, a.q, m, nd, tau_sum, dtau, varpi, zpp, zmp);
+      bool bail;
+      expk = doubling_run_s2<KS>(c, nd, expk, bail);
+      if (!bail) {
+        if (first) {
+          store_added_as_composite(c, g);
+          __syncthreads();
+        } else {
+          bail = !interaction_strip_s2<KS>(c, g);
+        }
+      }
+      if (bail) {  // workgroup-uniform: the 8-wave image redoes this layer and finishes the unit
+        done = z;
+        __syncthreads();
+        break;
+      }
+    }
+    if (wg_tid() == 0) a.resume[pt] = done;
+  }
+  if (wg_tid() == 0 && *c.bad) atomicMax(a.info, *c.bad);
+}
+
+}  // namespace MOM_NS

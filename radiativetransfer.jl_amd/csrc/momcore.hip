@@ -307,6 +307,12 @@ hipError_t mom6_lean9_launch(const void *layer_args, int grid, hipStream_t st); 
 hipError_t mom6_lean10_launch(const void *layer_args, int grid, hipStream_t st);
 size_t mom6_lean9_lds_bytes(int ns);
 size_t mom6_lean10_lds_bytes(int ns);
+hipError_t mom2_strip13_launch(const void *layer_args, int grid, hipStream_t st);  // momcore_strip2.hip: the two-buffer 4-wave image
+hipError_t mom2_strip14_launch(const void *layer_args, int grid, hipStream_t st);
+hipError_t mom2_strip15_launch(const void *layer_args, int grid, hipStream_t st);
+size_t mom2_strip13_lds_bytes(int ns, int nS);
+size_t mom2_strip14_lds_bytes(int ns, int nS);
+size_t mom2_strip15_lds_bytes(int ns, int nS);
 // the quad-block image (momcore_q4.hip, mom_q4.hpp): one wavefront per unit, v_mfma_f64_4x4x4 products, four units per CU
 #define MOM_Q4_DECL(KS)                                                                  \
   hipError_t momq_q4_##KS##_launch(const void *layer_args, int grid, hipStream_t st);     \
@@ -454,6 +460,9 @@ struct mom_handle {
                            // resume launch; 0 = the full image only
   int *d_resume = nullptr; // resume[unit] of the lean image (mom_lean.hpp)
   size_t resume_cap = 0;
+  int opt_strip2 = 1;       // MOM_OPT_STRIP2: N = 52, 56, 60 on the two-buffer 4-wave image first (mom_strip2.hpp), the 8-wave image resumes
+  int *d_resume2 = nullptr; // its resume[unit] (a table of its own: the m = 0 sub-problem's lean launch may run at the same time)
+  size_t resume2_cap = 0;
   int Nk = 0;              // operator edge the scene-level kernels of the full problem run with (>= N)
   DevStreams qk{};         // q with N = Nk
   int opt_small = 1;       // N <= 4: lane-per-point sweep kernel (mom_small.hip)
@@ -683,7 +692,7 @@ extern "C" int mom_destroy(mom_t *h) {
   fr(h->d_tau); fr(h->d_varpi); fr(h->d_zw); fr(h->d_Zpp); fr(h->d_Zmp); fr(h->d_tau_sum); fr(h->d_cos); fr(h->d_sin);
   fr(h->d_mu0); fr(h->d_wt0); fr(h->d_sg0); fr(h->d_Zpp0); fr(h->d_Zmp0); fr(h->d_hdrJ0); fr(h->d_scratch0);
   for (int k = 0; k < 6; ++k) fr(h->comp0[k]);
-  fr(h->d_R); fr(h->d_hdr); fr(h->d_post[0]); fr(h->d_gather); fr(h->d_rrs_send); fr(h->d_Rsurf); fr(h->d_Rsurf0); fr(h->d_albedo_spec); fr(h->d_hdrJm); fr(h->d_smtab); fr(h->d_smpart); if (h->d_resume) (void)hipFree(h->d_resume); if (h->d_ndif) (void)hipFree(h->d_ndif); fr(h->d_tau_abs); fr(h->d_grid); fr(h->d_lines); fr(h->d_prof); fr(h->d_tau_rayl);
+  fr(h->d_R); fr(h->d_hdr); fr(h->d_post[0]); fr(h->d_gather); fr(h->d_rrs_send); fr(h->d_Rsurf); fr(h->d_Rsurf0); fr(h->d_albedo_spec); fr(h->d_hdrJm); fr(h->d_smtab); fr(h->d_smpart); if (h->d_resume) (void)hipFree(h->d_resume); if (h->d_resume2) (void)hipFree(h->d_resume2); if (h->d_ndif) (void)hipFree(h->d_ndif); fr(h->d_tau_abs); fr(h->d_grid); fr(h->d_lines); fr(h->d_prof); fr(h->d_tau_rayl);
   fr(h->d_layer_max); fr(h->d_aer); if (h->d_aer_mode) (void)hipFree(h->d_aer_mode); fr(h->d_hdrJ); fr(h->d_bhr_uw); fr(h->d_bhr_dw); fr(h->d_node); fr(h->d_scratch); fr(h->d_info);
   for (int k = 0; k < 4; ++k) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
   for (int k = 0; k < 2; ++k) if (h->ev_voigt[k]) (void)hipEventDestroy(h->ev_voigt[k]);
@@ -722,6 +731,7 @@ extern "C" int mom_set_option(mom_t *h, int option, int value) {
   else if (option == MOM_OPT_STRIP_PAD) { h->opt_pad = value; h->scene_set = false; }
   else if (option == MOM_OPT_LEAN) { h->opt_lean = value; h->scene_set = false; }  // the padded edge of the m = 0 sub-problem depends on it
   else if (option == MOM_OPT_OVERLAP) h->opt_overlap = value;
+  else if (option == MOM_OPT_STRIP2) h->opt_strip2 = value;
   else if (option == MOM_OPT_DUAL_WORKSPACE_MB) {
     if (value < 0) return fail(h, MOM_EINVAL, "mom_set_option: MOM_OPT_DUAL_WORKSPACE_MB takes megabytes >= 0 (0 = 60 % of the free HBM)");
     h->opt_dual_budget = (size_t)value << 20;
@@ -1568,9 +1578,29 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, double *const c
     size_t sm = lds_bytes(q.N, lds);
     if (lds && (q.N == 44 || q.N == 52 || q.N == 56 || q.N == 60)) {  // strip-chained kernels (momcore_strip.hip), one image per N
       sm = strip_lds_bytes(q.N, ns_tab);  // + the persistent stream-pair tables
+      // N = 52, 56, 60: the two-buffer 4-wave image first (two workgroups per CU; mom_strip2.hpp), then this image resumes what it
+      // left (C2: nothing -- its launch reads the resume table and ends)
+      size_t (*const s2_lds)(int, int) = q.N == 60 ? mom2_strip15_lds_bytes : q.N == 56 ? mom2_strip14_lds_bytes
+                                       : q.N == 52 ? mom2_strip13_lds_bytes : nullptr;
+      bool s2 = h->opt_strip2 && sweep && !tg && q.inv_mode == 0 && s2_lds && s2_lds(ns_tab, q.nS) > 0;
+      for (int k = 1; k < nzr && s2; ++k) s2 = (a.iface_z[k] == 3);
+      if (s2 && !a.first) s2 = (a.iface_z[0] == 3);
+      if (s2) {
+        const size_t units = S * (size_t)Mcount;
+        if (units > h->resume2_cap) {  // grow-only
+          if (h->d_resume2) { HIPCHK(h, hipStreamSynchronize(cur)); (void)hipFree(h->d_resume2); h->d_resume2 = nullptr; h->resume2_cap = 0; }
+          HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_resume2), units * sizeof(int)));
+          h->resume2_cap = units;
+        }
+        a.resume = h->d_resume2;
+        const int grid2 = (int)std::min<size_t>(units, (size_t)2 * h->num_cu);  // persistent, two per CU
+        HIPCHK(h, (q.N == 60 ? mom2_strip15_launch : q.N == 56 ? mom2_strip14_launch : mom2_strip13_launch)(&a, grid2, cur));
+        h->launches++;
+      }
       // persistent workgroups, one per CU (only one 135 KB LDS image fits a CU): the prologue is paid once;
       // their start is staggered over about one unit time (~ (44 + 17 nd) us at N = 60)
-      if (S * Mcount >= 8 * (size_t)h->num_cu && h->opt_stagger) {
+      // (not behind the two-buffer image: its units are done, a staggered start would only delay the empty resume launch)
+      if (S * Mcount >= 8 * (size_t)h->num_cu && h->opt_stagger && a.resume == nullptr) {
         const double f = (double)q.N / 60.0, unit_us = f * f * f * (44.0 + 17.0 * a.nd);
         a.stagger = (int)(unit_us * 100.0 / 32.0);
       }
@@ -1594,7 +1624,10 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, double *const c
   // round.  The images cannot share a CU (149 + 48.5 KB of LDS), so nothing else overlaps.
   // ... and only then: where the two kernels CAN share a CU they contend for its matrix pipes and LDS bandwidth and the sweep
   // takes longer than the two launches in sequence (profiles/r06_C2_ab.txt (b'): N = 36 .. 44 with the m = 0 problem on the
-  // wave-per-point kernel 28 -> 45 ms, C4 -5 %), so the overlap is reserved for the persistent one-per-CU strip images
+  // wave-per-point kernel 28 -> 45 ms, C4 -5 %), so the overlap is reserved for the persistent one-per-CU strip images.
+  // r7: in front of those images the two-buffer image (75 KB, two per CU) now runs the units, and a quad-block workgroup of the
+  // sub-problem can share a CU with it; measured, the overlap still pays there (C2 330.1 against 332.1 ms without it,
+  // profiles/r07_C2_ab.txt), so the gate stays as it is
   const bool two = red0 && can_sweep && h->opt_overlap && M > 1 && !tg && h->stream2 && !h->opt_force_generic &&
                    (Nk == 52 || Nk == 56 || Nk == 60);
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
