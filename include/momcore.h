@@ -482,11 +482,22 @@ int mom_timers(mom_t *h, double *ms, int n, int *kernel_launches);
  *                         image runs them first, two workgroups per CU (csrc/mom_strip2.hpp), and the 8-wave image finishes
  *                         whatever it left (series beyond 12 terms) -- two launches per sweep, both counted in mom_timers'
  *                         kernel_launches; results are bitwise those of the 8-wave image.  0 = the 8-wave image only.
+ *   MOM_OPT_STRIP2_SCHED  how the two workgroups of a CU share it in the two-buffer image, a mask (default 1): 1 = the units come from
+ *                         a shared queue (an atomic ticket per unit; the counter is zeroed on the stream before the launch)
+ *                         instead of a fixed stride per workgroup, 2 = the workgroup that arrives second on its CU runs its strip
+ *                         chains at raised wave priority (an experiment: the two units do not run in lock-step to begin with, and the
+ *                         priority measured 1.6 ms slower on C2 on top of the queue, profiles/r08_C2_ab.txt).  0 = neither (the
+ *                         scheduling before this option existed).  Results do not depend on it: units are independent.
  */
 int mom_set_option(mom_t *h, int option, int value);
+
+/* The two-buffer strip image's last launch on this handle (MOM_OPT_STRIP2): *units = the units it was given, *left = how many of
+ * them it handed to the 8-wave image through the resume table (a series beyond 12 terms).  0, 0 if it never ran.  Synchronises.
+ * A test observable: results do not depend on it. */
+int mom_strip2_resumed(mom_t *h, int *units, int *left);
 enum { MOM_OPT_INVERSE = 0, MOM_OPT_FORCE_GENERIC = 1, MOM_OPT_M0_REDUCTION = 2, MOM_OPT_SMALL_WG = 3, MOM_OPT_STAGGER = 4,
        MOM_OPT_SMALL_N = 5, MOM_OPT_LAYER_SWEEP = 6, MOM_OPT_STRIP_PAD = 7, MOM_OPT_LEAN = 8, MOM_OPT_OVERLAP = 9,
-       MOM_OPT_RRS_KERNELS = 10, MOM_OPT_DUAL_WORKSPACE_MB = 11, MOM_OPT_STRIP2 = 12 };
+       MOM_OPT_RRS_KERNELS = 10, MOM_OPT_DUAL_WORKSPACE_MB = 11, MOM_OPT_STRIP2 = 12, MOM_OPT_STRIP2_SCHED = 13 };
 
 /* ---- Voigt line-by-line cross section --------------------------------------------------
  * compute_absorption_cross_section(model::HitranModel, grid, p, T)

@@ -39,6 +39,7 @@ MOM_OPT_OVERLAP = 9
 MOM_OPT_RRS_KERNELS = 10   # mask: 1 WG pairs, 2 ... for 16 < N <= 32, 4 WG points, 8 tile elemental, 16 / 32 fused elemental always / never
 MOM_OPT_DUAL_WORKSPACE_MB = 11   # operator workspace of mom_rt_run_dual (0: 60 % of the free HBM)
 MOM_OPT_STRIP2 = 12              # N = 52, 56, 60 on the two-buffer 4-wave image first (1, default), 0 = the 8-wave image only
+MOM_OPT_STRIP2_SCHED = 13        # its scheduling, a mask (1, default): 1 = shared unit queue, 2 = asymmetric chain priority (off: measured slower); 0 = neither
 
 
 class MomError(RuntimeError):
@@ -118,6 +119,7 @@ SIGNATURES = {
     "mom_allgather_RT": (C.c_int, [c_h, c_dp, c_dp]),
     "mom_timers": (C.c_int, [c_h, c_dp, C.c_int, c_ip]),
     "mom_set_option": (C.c_int, [c_h, C.c_int, C.c_int]),
+    "mom_strip2_resumed": (C.c_int, [c_h, c_ip, c_ip]),
     "mom_voigt_xsec": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip, C.c_int, c_dp, c_dp]),
     "mom_voigt_last_kernel_ms": (C.c_double, []),
 }
@@ -548,6 +550,12 @@ class Handle:
         self.check(self.lib.mom_allgather_RT(self._h, dp(R), dp(T)))
         shp = (self.S * self.comm_size, self.nS, self.nVza)
         return np.transpose(R.reshape(shp), (2, 1, 0)).copy(), np.transpose(T.reshape(shp), (2, 1, 0)).copy()
+
+    def strip2_resumed(self):
+        """(units of the two-buffer strip image's last launch, units it left to the 8-wave image through the resume table)"""
+        u, l = C.c_int(0), C.c_int(0)
+        self.check(self.lib.mom_strip2_resumed(self._h, C.byref(u), C.byref(l)))
+        return u.value, l.value
 
     def timers(self):
         ms = np.zeros(8)

@@ -41,6 +41,11 @@ struct LayerArgs {
   // The lean kernel writes it; the full image, launched afterwards with the same pointer, starts every unit at that layer
   // (its composite state in global memory is the one after layer resume - 1) and skips the finished ones.  nullptr: all layers.
   int *resume;
+  // two-buffer strip image (mom_strip2.hpp), MOM_OPT_STRIP2_SCHED: sched[0] = the shared unit queue's ticket counter, sched[1 + cu]
+  // = arrival tickets per CU; zeroed on the stream before the launch.  sched_mode: bit 0 = units from the queue (else static
+  // striding), bit 1 = the second workgroup to arrive on a CU runs its strip chains at raised wave priority.
+  int *sched;
+  int sched_mode;
 };
 
 struct ZMix {

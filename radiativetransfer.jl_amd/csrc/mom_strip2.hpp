@@ -22,9 +22,55 @@
 // are bitwise those of the 8-wave image.
 // Scope: Float64, 4-wave build, sweep mode, single composite (no multi-target), interface 11 on every layer after the first.
 #pragma once
+#include "mom_diag.hpp"
 #include "mom_entry.hpp"
 
 namespace MOM_NS {
+
+// MOM_OPT_STRIP2_SCHED (LayerArgs::sched, sched_mode): how the workgroups share the units and the two of a CU its matrix pipe.
+//   * Bit 0 (default on), a shared unit queue: the units are handed out by an atomic ticket instead of pt += gridDim.x, so no
+//     workgroup idles through a partial last round; resume[] stays indexed by unit.  Units are independent: the order does not
+//     change a result.  C2: full layers 272.7 -> 263.0 ms, N = 52 / 56 -2 % (profiles/r08_C2_ab.txt).
+//   * Bit 1 (default off), asymmetric chain priority: the workgroup that arrives SECOND on its CU (a ticket per CU, keyed by the
+//     XCC / SE / SH / CU ids of the hardware registers -- blockIdx says nothing about residency) runs every strip chain at wave
+//     priority 1 and everything else at 0.  Meant against two units running in lock-step; the timelines
+//     (profiles/r08_phase_stamps_s2.txt) show that they do not (both outside a chain: 5 % of the time), and the priority only moves
+//     time from the favoured unit's chains to its non-chain sections: 1.5 ms gained alone, 1.6 ms lost on top of the queue.
+// The kernel is instantiated per value of the mask (k_layer_s2<KS, MODE>): 0 is the kernel as it was before the option, and the
+// default carries nothing of the priority.
+constexpr int kS2CuKeys = 2048;     // XCC id (3 bits) x HW_ID bits 15:8 (CU, SH, SE)
+constexpr int kS2SchedInts = 1 + kS2CuKeys;
+#define MOM_S2_GETREG(id, off, size) ((((size)-1) << 11) | ((off) << 6) | (id))
+__device__ __forceinline__ int s2_cu_key() {
+  const unsigned cu = __builtin_amdgcn_s_getreg(MOM_S2_GETREG(4, 8, 8));    // HW_REG_HW_ID: cu_id 11:8, sh_id 12, se_id 15:13
+  const unsigned xcc = __builtin_amdgcn_s_getreg(MOM_S2_GETREG(20, 0, 4));  // HW_REG_XCC_ID
+  return (int)(((xcc & 7u) << 8) | cu);
+}
+#ifndef MOM_S2_PRIO
+#define MOM_S2_PRIO 1
+#endif
+// the boundary of a strip chain: the favoured workgroup raises / drops its priority (the flag is kept in the LDS int c.ipiv[1], not
+// in a scalar register: the kernel has none to spare); sec = the timeline id (diagnostic builds) of the section that ends here
+// PRIO = false (every instantiation without bit 1 of the mode): nothing is emitted
+__device__ __forceinline__ int s2_favoured(const Ctx &c) { return __builtin_amdgcn_readfirstlane(c.ipiv[1]) & 1; }
+template <bool ON, bool PRIO>
+__device__ __forceinline__ void s2_chain(const Ctx &c, int sec, int fav) {
+#ifndef MOM_DIAG_TIMELINE
+  if constexpr (PRIO)
+#endif
+  {
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (PRIO)
+      if (fav) __builtin_amdgcn_s_setprio(ON ? MOM_S2_PRIO : 0);
+    MOM_TL(c, sec);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+// the unit a QUEUE workgroup is on: its ticket, from LDS into a scalar register
+#define S2_UNIT(c) ((size_t)(unsigned)__builtin_amdgcn_readfirstlane((c).ipiv[0]))
+// timeline sections (diagnostic builds): what a workgroup was in until the event
+enum { S2_SEC_TOP = 0, S2_SEC_ELEM = 1, S2_SEC_DBL = 2, S2_SEC_DEND = 3, S2_SEC_ICOPY = 4, S2_SEC_ICH1 = 5, S2_SEC_ICOPY2 = 6,
+       S2_SEC_ICH2 = 7, S2_SEC_IEND = 8, S2_SEC_FIRST = 9 };
 
 constexpr int kS2Lay = 128;  // reals of the layer-scalar tail
 __host__ __device__ inline size_t s2_vec_reals(int N) { return part_offset_doubles(N) + 16; }
@@ -157,7 +203,7 @@ __device__ __forceinline__ bool doubling_step_s2(Ctx &c, real expk) {
 }
 
 // nd doubling steps; bail = true (nothing of the layer has left the workgroup) if a step needs the general path
-template <int KS>
+template <int KS, bool PRIO>
 __device__ __forceinline__ real doubling_run_s2(Ctx &c, int nd, real expk, bool &bail) {
   const int N = c.N, ld = c.ld;
   bail = false;
@@ -167,13 +213,17 @@ __device__ __forceinline__ real doubling_run_s2(Ctx &c, int nd, real expk, bool 
     c.r[i + (N + 1) * ld] = c.jm[i];
   }
   __syncthreads();
+  const int fav = PRIO ? s2_favoured(c) : 0;
+  s2_chain<true, PRIO>(c, S2_SEC_ELEM, fav);  // a doubling step is products and barriers throughout
   for (int it = 0; it < nd; ++it) {
     if (!doubling_step_s2<KS>(c, expk)) {
+      s2_chain<false, PRIO>(c, S2_SEC_DBL, fav);
       bail = true;
       return expk;
     }
     expk = expk * expk;
   }
+  s2_chain<false, PRIO>(c, S2_SEC_DBL, fav);
   // apply_D! (doubling.jl:93-110) and apply_D_SFI! (:112-118): r-+ rows and j0- scaled by sg
   real *r = c.r;
   for (int e = wg_tid(); e < N * N; e += kThreads) {
@@ -186,12 +236,13 @@ __device__ __forceinline__ real doubling_run_s2(Ctx &c, int nd, real expk, bool 
     r[i + N * ld] = 0.0; r[i + (N + 1) * ld] = 0.0;
   }
   __syncthreads();
+  MOM_TL(c, S2_SEC_DEND);
   return expk;
 }
 
 // ScatteringInterface_11 in two buffers (see interaction_strip for the algebra; same products, same order).  Returns false,
 // nothing stored, if the series is too long.  Ends with a barrier.
-template <int KS>
+template <int KS, bool PRIO>
 __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) {
   using G = StripGeom<KS>;
   constexpr int N = G::N, NT = G::NT, LD = G::LD, NN = N * N, U = (NN + kThreads - 1) / kThreads;
@@ -226,6 +277,8 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
     }
   }
   __syncthreads();
+  const int fav = PRIO ? s2_favoured(c) : 0;  // (read once per interaction: the later boundaries have no vector register to spare)
+  s2_chain<true, PRIO>(c, S2_SEC_ICOPY, fav);
   const real *Rpm = r;
   r4 Bs[NT], W0[NT];
   real ss = 0.0;
@@ -251,7 +304,10 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
   __syncthreads();
   const real beta2 = wg_sumsq_get(c);
   const int p = __builtin_amdgcn_readfirstlane(neumann_terms_12(beta2));
-  if (p > kStripMaxP) return false;
+  if (p > kStripMaxP) {
+    s2_chain<false, PRIO>(c, S2_SEC_ICH1, fav);
+    return false;
+  }
   const unsigned mask = strip_sign_mask(c.sg, lq, N);
   // ---- (b) the two Horner loops, multiplier B^T
   r4 Y1[NT], Y2[NT];
@@ -307,6 +363,7 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
     strip_flip(acc, mask);
     strip_store_glb<KS>(g.R_pm, lr, lq, c0, colok, acc);
   }
+  s2_chain<false, PRIO>(c, S2_SEC_ICH1, fav);
   // ---- (d) T++ (+ J0+ as its riding column N) into t's buffer; the products with T++
   r4 Radd[NT];
   strip_load_glb<KS>(g.R_mp, lr, lq, c0, colok, Radd);
@@ -336,6 +393,7 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
     if (wg_tid() < N) t[wg_tid() + N * LD] = vj;
   }
   __syncthreads();
+  s2_chain<true, PRIO>(c, S2_SEC_ICOPY2, fav);
   const real *Tpp = t;
   // R-+ = R-+ + (T01 r-+) T++  ->  R-+^T + T++^T V ; row N: (T01 r-+ J0+)^T        (:93)
   strip_mul<KS>(Tpp, lr, lq, V, Radd);
@@ -351,15 +409,20 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
     // J0+ = j0+ + T21 (J0+ + R+- j0-)                                                (:110)
     if (colok && lq == G::LQ0) g.J0p[col] = c.jp[col] + (o[G::RT][G::RR0] + T21[G::RT][G::RR0]);
   }
+  s2_chain<false, PRIO>(c, S2_SEC_ICH2, fav);
   __syncthreads();
+  MOM_TL(c, S2_SEC_IEND);
   return true;
 }
 
 // One launch walks all layers of every unit (sweep mode only); see the header of this file for what it does not do.
-template <int KS>
+// MODE = the bits of LayerArgs::sched_mode, one instantiation each: without bit 0 the unit loop is the fixed stride, without bit 1
+// no chain boundary emits anything, so MODE 0 is the kernel as it was before the option existed.
+template <int KS, int MODE>
 __global__ void __launch_bounds__(kThreads, 2) k_layer_s2(const LayerArgs a) {
   // (the argument block is never written: see k_layer_lean)
   constexpr int N = 4 * KS;
+  constexpr bool QUEUE = (MODE & 1) != 0, PRIO = (MODE & 2) != 0;
   const size_t total = (size_t)a.S * a.M;
   Ctx c;
   make_ctx_s2(c, N, a.q.inv_mode, a.q.regular ? a.q.nS : 1, mom_smem);
@@ -370,12 +433,33 @@ __global__ void __launch_bounds__(kThreads, 2) k_layer_s2(const LayerArgs a) {
   real *lay = mom_smem + 2 * mat_elems(N) + s2_vec_reals(N);
   const int nz = a.Nz_sweep;
   const int LW = 3 + a.K, LZ = kS2Lay / LW;
-  for (size_t pt = blockIdx.x; pt < total; pt += gridDim.x) {
-    const int n = (int)(pt % a.S), mrel = (int)(pt / a.S), m = a.m_first + mrel;
+  // (c.ipiv, c.sh serve the pivoted inverse, which this image never runs: c.ipiv[0], [1] carry the tickets to the other waves)
+  if (PRIO && wg_tid() == 0) c.ipiv[1] = atomicAdd(a.sched + 1 + s2_cu_key(), 1);  // odd: the favoured workgroup
+#ifdef MOM_DIAG_TIMELINE
+  if (!PRIO && wg_tid() == 0) c.ipiv[1] = 0;
+  if (wg_tid() == 0) c.ipiv[2] = -1;
+  int tl_units = 0;
+#endif
+  for (size_t pt = blockIdx.x;; pt += gridDim.x) {
+    if constexpr (QUEUE) {  // the next unit nobody has taken: thread 0 draws the ticket and hands it to the other waves through LDS
+      if (wg_tid() == 0) c.ipiv[0] = atomicAdd(a.sched, 1);
+      __syncthreads();
+      pt = S2_UNIT(c);
+    }
+    if (pt >= total) break;
+#ifdef MOM_DIAG_TIMELINE
+    if (wg_tid() == 0 && tl_units == 1) c.ipiv[2] = 0;
+    ++tl_units;
+    MOM_TL(c, S2_SEC_TOP);
+#endif
     const size_t NNs = (size_t)N * N;
-    CompPtrs g = comp_ptrs(a.comp, N, comp_pitch(N), pt);
     int done = nz;
     for (int z = 0; z < nz; ++z) {
+      // QUEUE: the unit index is read from LDS again wherever a layer needs it.  Held in scalar registers across the layer loop,
+      // it and what derives from it (n, the moment, six composite pointers) cost the register allocator the room it needs to
+      // keep the kernel free of scratch; the fixed stride does not, there the compiler re-derives them from blockIdx.
+      if constexpr (QUEUE) pt = S2_UNIT(c);
+      const int n = (int)(pt % a.S), mrel = (int)(pt / a.S), m = a.m_first + mrel;
       const int zl = z % LZ;
       if (zl == 0) {
         const int cnt = ((nz - z < LZ) ? nz - z : LZ) * LW;
@@ -397,13 +481,16 @@ __global__ void __launch_bounds__(kThreads, 2) k_layer_s2(const LayerArgs a) {
       ZMix zmp{as_global(a.Zmp) + NNs * a.K * mrel, ls + 3, a.K, N};
       elemental_build<true>(c, a.q, m, nd, tau_sum, dtau, varpi, zpp, zmp);
       bool bail;
-      expk = doubling_run_s2<KS>(c, nd, expk, bail);
+      expk = doubling_run_s2<KS, PRIO>(c, nd, expk, bail);
       if (!bail) {
+        if constexpr (QUEUE) pt = S2_UNIT(c);
+        const CompPtrs g = comp_ptrs(a.comp, N, comp_pitch(N), pt);
         if (first) {
           store_added_as_composite(c, g);
           __syncthreads();
+          MOM_TL(c, S2_SEC_FIRST);
         } else {
-          bail = !interaction_strip_s2<KS>(c, g);
+          bail = !interaction_strip_s2<KS, PRIO>(c, g);
         }
       }
       if (bail) {  // workgroup-uniform: the 8-wave image redoes this layer and finishes the unit
@@ -412,9 +499,20 @@ __global__ void __launch_bounds__(kThreads, 2) k_layer_s2(const LayerArgs a) {
         break;
       }
     }
+    if constexpr (QUEUE) pt = S2_UNIT(c);
     if (wg_tid() == 0) a.resume[pt] = done;
+    if constexpr (QUEUE) __syncthreads();  // every wave has read this unit's ticket before thread 0 draws the next one
   }
   if (wg_tid() == 0 && *c.bad) atomicMax(a.info, *c.bad);
+#ifdef MOM_DIAG_TIMELINE
+  if (wg_tid() == 0 && blockIdx.x < kTlWgs) {
+    unsigned *hd = mom_tl_hdr + 4 * blockIdx.x;
+    hd[0] = (unsigned)s2_cu_key();
+    hd[1] = (unsigned)c.ipiv[1];
+    hd[2] = (unsigned)(c.ipiv[1] & 1);
+    hd[3] = (unsigned)(c.ipiv[2] < 0 ? 0 : c.ipiv[2]);
+  }
+#endif
 }
 
 }  // namespace MOM_NS

@@ -313,6 +313,7 @@ hipError_t mom2_strip15_launch(const void *layer_args, int grid, hipStream_t st)
 size_t mom2_strip13_lds_bytes(int ns, int nS);
 size_t mom2_strip14_lds_bytes(int ns, int nS);
 size_t mom2_strip15_lds_bytes(int ns, int nS);
+size_t mom2_strip13_sched_ints();  // ints of LayerArgs::sched (the same for every size)
 // the quad-block image (momcore_q4.hip, mom_q4.hpp): one wavefront per unit, v_mfma_f64_4x4x4 products, four units per CU
 #define MOM_Q4_DECL(KS)                                                                  \
   hipError_t momq_q4_##KS##_launch(const void *layer_args, int grid, hipStream_t st);     \
@@ -463,6 +464,11 @@ struct mom_handle {
   int opt_strip2 = 1;       // MOM_OPT_STRIP2: N = 52, 56, 60 on the two-buffer 4-wave image first (mom_strip2.hpp), the 8-wave image resumes
   int *d_resume2 = nullptr; // its resume[unit] (a table of its own: the m = 0 sub-problem's lean launch may run at the same time)
   size_t resume2_cap = 0;
+  size_t resume2_units = 0;  // units and layers of the image's last launch (mom_strip2_resumed)
+  int resume2_nz = 0;
+  int opt_strip2_sched = 1;  // MOM_OPT_STRIP2_SCHED: bit 0 = shared unit queue, bit 1 = asymmetric chain priority (mom_strip2.hpp; one
+                             // kernel per value); the priority measured slower on top of the queue (profiles/r08_C2_ab.txt): off
+  int *d_sched2 = nullptr;   // LayerArgs::sched of the two-buffer image: zeroed on the stream before each of its launches
   int Nk = 0;              // operator edge the scene-level kernels of the full problem run with (>= N)
   DevStreams qk{};         // q with N = Nk
   int opt_small = 1;       // N <= 4: lane-per-point sweep kernel (mom_small.hip)
@@ -692,7 +698,7 @@ extern "C" int mom_destroy(mom_t *h) {
   fr(h->d_tau); fr(h->d_varpi); fr(h->d_zw); fr(h->d_Zpp); fr(h->d_Zmp); fr(h->d_tau_sum); fr(h->d_cos); fr(h->d_sin);
   fr(h->d_mu0); fr(h->d_wt0); fr(h->d_sg0); fr(h->d_Zpp0); fr(h->d_Zmp0); fr(h->d_hdrJ0); fr(h->d_scratch0);
   for (int k = 0; k < 6; ++k) fr(h->comp0[k]);
-  fr(h->d_R); fr(h->d_hdr); fr(h->d_post[0]); fr(h->d_gather); fr(h->d_rrs_send); fr(h->d_Rsurf); fr(h->d_Rsurf0); fr(h->d_albedo_spec); fr(h->d_hdrJm); fr(h->d_smtab); fr(h->d_smpart); if (h->d_resume) (void)hipFree(h->d_resume); if (h->d_resume2) (void)hipFree(h->d_resume2); if (h->d_ndif) (void)hipFree(h->d_ndif); fr(h->d_tau_abs); fr(h->d_grid); fr(h->d_lines); fr(h->d_prof); fr(h->d_tau_rayl);
+  fr(h->d_R); fr(h->d_hdr); fr(h->d_post[0]); fr(h->d_gather); fr(h->d_rrs_send); fr(h->d_Rsurf); fr(h->d_Rsurf0); fr(h->d_albedo_spec); fr(h->d_hdrJm); fr(h->d_smtab); fr(h->d_smpart); if (h->d_resume) (void)hipFree(h->d_resume); if (h->d_resume2) (void)hipFree(h->d_resume2); if (h->d_sched2) (void)hipFree(h->d_sched2); if (h->d_ndif) (void)hipFree(h->d_ndif); fr(h->d_tau_abs); fr(h->d_grid); fr(h->d_lines); fr(h->d_prof); fr(h->d_tau_rayl);
   fr(h->d_layer_max); fr(h->d_aer); if (h->d_aer_mode) (void)hipFree(h->d_aer_mode); fr(h->d_hdrJ); fr(h->d_bhr_uw); fr(h->d_bhr_dw); fr(h->d_node); fr(h->d_scratch); fr(h->d_info);
   for (int k = 0; k < 4; ++k) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
   for (int k = 0; k < 2; ++k) if (h->ev_voigt[k]) (void)hipEventDestroy(h->ev_voigt[k]);
@@ -714,6 +720,18 @@ extern "C" int mom_sync(mom_t *h) {
   return MOM_OK;
 }
 
+extern "C" int mom_strip2_resumed(mom_t *h, int *units, int *left) {
+  if (!h || !units || !left) return fail(h, MOM_EINVAL, "mom_strip2_resumed: null argument");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  *units = (int)h->resume2_units; *left = 0;
+  if (!h->d_resume2 || h->resume2_units == 0) { *units = 0; return MOM_OK; }
+  std::vector<int> r(h->resume2_units);
+  HIPCHK(h, hipMemcpy(r.data(), h->d_resume2, r.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (int v : r) *left += (v < h->resume2_nz);
+  return MOM_OK;
+}
+
 extern "C" int mom_check(mom_t *h) {
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
   HIPCHK(h, hipSetDevice(h->device));
@@ -732,6 +750,10 @@ extern "C" int mom_set_option(mom_t *h, int option, int value) {
   else if (option == MOM_OPT_LEAN) { h->opt_lean = value; h->scene_set = false; }  // the padded edge of the m = 0 sub-problem depends on it
   else if (option == MOM_OPT_OVERLAP) h->opt_overlap = value;
   else if (option == MOM_OPT_STRIP2) h->opt_strip2 = value;
+  else if (option == MOM_OPT_STRIP2_SCHED) {
+    if (value < 0 || value > 3) return fail(h, MOM_EINVAL, "mom_set_option: MOM_OPT_STRIP2_SCHED takes a mask of bits 0 and 1");
+    h->opt_strip2_sched = value;
+  }
   else if (option == MOM_OPT_DUAL_WORKSPACE_MB) {
     if (value < 0) return fail(h, MOM_EINVAL, "mom_set_option: MOM_OPT_DUAL_WORKSPACE_MB takes megabytes >= 0 (0 = 60 % of the free HBM)");
     h->opt_dual_budget = (size_t)value << 20;
@@ -1593,6 +1615,15 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, double *const c
           h->resume2_cap = units;
         }
         a.resume = h->d_resume2;
+        h->resume2_units = units; h->resume2_nz = nzr;
+        if (h->opt_strip2_sched) {  // the queue counter (and, for the chain priority, the per-CU tickets) start at zero: a memset ON
+                                    // THE STREAM, so that an asynchronous step (or a captured one) resets them in order with its launches
+          const size_t ints = mom2_strip13_sched_ints();
+          if (!h->d_sched2) HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_sched2), ints * sizeof(int)));
+          HIPCHK(h, hipMemsetAsync(h->d_sched2, 0, ((h->opt_strip2_sched & 2) ? ints : 1) * sizeof(int), cur));
+          a.sched = h->d_sched2;
+          a.sched_mode = h->opt_strip2_sched;
+        }
         const int grid2 = (int)std::min<size_t>(units, (size_t)2 * h->num_cu);  // persistent, two per CU
         HIPCHK(h, (q.N == 60 ? mom2_strip15_launch : q.N == 56 ? mom2_strip14_launch : mom2_strip13_launch)(&a, grid2, cur));
         h->launches++;
@@ -1617,17 +1648,18 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, double *const c
     return MOM_OK;
   };
   // MOM_OPT_OVERLAP: the two launches of a sweep -- moments 1..M-1 on the full problem, moment 0 on the (I,Q) sub-problem --
-  // are independent, and each ends in a partial round of its persistent workgroups (C2: 20 000 units on 256 workgroups = 78.1
-  // rounds, 10 000 on 768 = 13.02).  The sub-problem (with its surface interaction) goes first, on the handle's second,
-  // high-priority stream; the full problem's workgroups take the CUs as the sub-problem's last round frees them, and the
-  // workgroups that start late are those with the highest indices -- the ones WITHOUT a unit in the full problem's own partial
-  // round.  The images cannot share a CU (149 + 48.5 KB of LDS), so nothing else overlaps.
-  // ... and only then: where the two kernels CAN share a CU they contend for its matrix pipes and LDS bandwidth and the sweep
-  // takes longer than the two launches in sequence (profiles/r06_C2_ab.txt (b'): N = 36 .. 44 with the m = 0 problem on the
-  // wave-per-point kernel 28 -> 45 ms, C4 -5 %), so the overlap is reserved for the persistent one-per-CU strip images.
-  // r7: in front of those images the two-buffer image (75 KB, two per CU) now runs the units, and a quad-block workgroup of the
-  // sub-problem can share a CU with it; measured, the overlap still pays there (C2 330.1 against 332.1 ms without it,
-  // profiles/r07_C2_ab.txt), so the gate stays as it is
+  // are independent.  What runs at the edges 52 / 56 / 60 (C2: N = 60, sub-problem N = 40): the sub-problem on the quad-block image
+  // (one wavefront per unit, four per CU, 10 000 units), the full problem on the two-buffer strip image (two 4-wave workgroups per
+  // CU, persistent, 20 000 units handed out by its shared queue, MOM_OPT_STRIP2_SCHED) and behind it the 8-wave image's resume
+  // launch, which finds nothing left in C2.  The sub-problem (with its surface interaction) goes first, on the handle's second,
+  // high-priority stream; the full problem's workgroups take the CUs as the sub-problem's tail frees them, and a quad-block
+  // workgroup can share a CU with ONE two-buffer workgroup (75 + 2 x 40 KB of LDS), not with two.
+  // Where two such kernels share CUs for long they contend for the matrix pipes and LDS bandwidth and the sweep takes longer
+  // than the two launches in sequence (profiles/r06_C2_ab.txt (b'): N = 36 .. 44 with the m = 0 problem on the wave-per-point
+  // kernel 28 -> 45 ms, C4 -5 %), so the overlap is reserved for the edges below, where only the tails meet; measured there it
+  // gained about 2 ms of 330 (profiles/r07_C2_ab.txt).  With the shared unit queue the full problem has no partial last round left
+  // to fill: re-measured at the default, 322.6 ms with the overlap and 322.7 without (profiles/r08_C2_ab.txt).  It costs nothing,
+  // so the gate stays
   const bool two = red0 && can_sweep && h->opt_overlap && M > 1 && !tg && h->stream2 && !h->opt_force_generic &&
                    (Nk == 52 || Nk == 56 || Nk == 60);
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));

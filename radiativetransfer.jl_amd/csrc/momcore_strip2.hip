@@ -17,14 +17,35 @@ using namespace MOM_NS;
 
 // mom2_strip<KS>_launch(args, grid, stream): the sweep kernel; mom2_strip<KS>_lds_bytes(ns, nS): its LDS bytes, 0 if the image
 // does not apply to ns Stokes components per stream (nS per stream entry of the scene)
-hipError_t MOM_CAT(MOM_CAT(mom2_strip, MOM_STRIP_KS), _launch)(const void *layer_args, int grid, hipStream_t st) {
-  const LayerArgs a = *reinterpret_cast<const LayerArgs *>(layer_args);
+template <int MODE>
+static hipError_t launch_s2(const LayerArgs &a, int grid, hipStream_t st) {
   const size_t smem = s2_lds_bytes(4 * MOM_STRIP_KS);
-  hipError_t e = mom_allow_lds(reinterpret_cast<const void *>(k_layer_s2<MOM_STRIP_KS>), smem);
+  hipError_t e = mom_allow_lds(reinterpret_cast<const void *>(k_layer_s2<MOM_STRIP_KS, MODE>), smem);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_layer_s2<MOM_STRIP_KS>), dim3(grid), dim3(kThreads), smem, st, a);
+  hipLaunchKernelGGL((k_layer_s2<MOM_STRIP_KS, MODE>), dim3(grid), dim3(kThreads), smem, st, a);
   return hipGetLastError();
 }
+hipError_t MOM_CAT(MOM_CAT(mom2_strip, MOM_STRIP_KS), _launch)(const void *layer_args, int grid, hipStream_t st) {
+  const LayerArgs a = *reinterpret_cast<const LayerArgs *>(layer_args);
+  switch (a.sched_mode & 3) {  // one kernel per scheduling mode (mom_strip2.hpp)
+    case 1: return launch_s2<1>(a, grid, st);
+    case 2: return launch_s2<2>(a, grid, st);
+    case 3: return launch_s2<3>(a, grid, st);
+    default: return launch_s2<0>(a, grid, st);
+  }
+}
+// ints of LayerArgs::sched (the unit queue's counter + the arrival tickets per CU), zeroed on the stream before every launch
+size_t MOM_CAT(MOM_CAT(mom2_strip, MOM_STRIP_KS), _sched_ints)() { return kS2SchedInts; }
+#ifdef MOM_DIAG_TIMELINE
+// diagnostic builds (tools/phase_stamps_s2.py): the timelines of the last launch; ev[kTlWgs * kTlCap], hdr[4 * kTlWgs]
+extern "C" int MOM_CAT(MOM_CAT(mom2_strip, MOM_STRIP_KS), _timeline_read)(unsigned long long *ev, unsigned *hdr, int *wgs, int *cap) {
+  *wgs = kTlWgs; *cap = kTlCap;
+  if (!ev) return 0;
+  if (hipMemcpyFromSymbol(ev, HIP_SYMBOL(mom_tl_ev), sizeof(unsigned long long) * kTlWgs * kTlCap) != hipSuccess) return 1;
+  if (hipMemcpyFromSymbol(hdr, HIP_SYMBOL(mom_tl_hdr), sizeof(unsigned) * 4 * kTlWgs) != hipSuccess) return 1;
+  return 0;
+}
+#endif
 size_t MOM_CAT(MOM_CAT(mom2_strip, MOM_STRIP_KS), _lds_bytes)(int ns, int nS) {
   return s2_applies(4 * MOM_STRIP_KS, ns, nS) ? s2_lds_bytes(4 * MOM_STRIP_KS) : 0;
 }
