@@ -19,6 +19,29 @@ inline hipError_t mom_allow_lds(const void *fn, size_t bytes) {
   return e;
 }
 
+// One launch of a kernel templated on LDSM (operators in LDS / in per-workgroup global slabs): `k_lds` and `k_gen` are its two
+// instantiations, MOM_LDSM(KERN, further template arguments...) names them
+template <class Args>
+inline hipError_t mom_launch_ldsm(void (*k_lds)(Args), void (*k_gen)(Args), bool lds, int grid, int threads, size_t smem,
+                                  hipStream_t st, const Args &a) {
+  void (*const k)(Args) = lds ? k_lds : k_gen;
+  const hipError_t e = mom_allow_lds(reinterpret_cast<const void *>(k), smem);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(threads), smem, st, a);
+  return hipGetLastError();
+}
+#define MOM_LDSM(KERN, ...) KERN<true, ##__VA_ARGS__>, KERN<false, ##__VA_ARGS__>
+
+// The interface code is a template argument of the layer kernels (see interaction_core): STMT(IF) for IF = iface, codes
+// outside 0..2 taking the image of code 3
+#define MOM_IFACE_SWITCH(iface, STMT) \
+  switch (iface) {                    \
+    case 0: STMT(0); break;           \
+    case 1: STMT(1); break;           \
+    case 2: STMT(2); break;           \
+    default: STMT(3); break;          \
+  }
+
 // text for mom_last_global_error() (the thread's library-level error string, momcore.hip)
 void mom_set_global_error(const char *msg);
 

@@ -19,6 +19,7 @@
 #include "mom_entry.hpp"
 #include "mom_ops.hpp"
 #include "mom_host.hpp"
+#include "mom_images.hpp"
 #include "mom_rrs.hpp"
 
 using namespace mom;
@@ -292,58 +293,10 @@ __global__ void __launch_bounds__(kThreads) k_batch_inv_dual(DualArgs a) {
 // momcore_w4.hip: the same kernels built for 4-wave workgroups (2 workgroups per CU when the operators are
 // small enough for two LDS images: the m = 0 (I,Q) sub-problem of N = 60 is N0 = 40 -> 77 KB).
 size_t mom4_lds_bytes(int N, bool lds_mats);
-size_t mom4_strip_lds_bytes(int N, int ns);
 hipError_t mom4_launch_layer(const void *layer_args, int iface, bool lds, int grid, size_t smem, hipStream_t st);
 // momcore_gen.hip: the general layer kernels k_layer<LDSM, IFACE> of the 8-wave build
 hipError_t mom_gen_launch_layer(const void *layer_args, int iface, bool lds, int grid, size_t smem, hipStream_t st);
-// momcore_strip.hip, one object per operator size N = 4 KS
-hipError_t mom_strip9_launch_layer(const void *layer_args, int iface, int grid, size_t smem, hipStream_t st);
-hipError_t mom_strip10_launch_layer(const void *layer_args, int iface, int grid, size_t smem, hipStream_t st);
-hipError_t mom_strip9_launch_lean(const void *layer_args, int grid, hipStream_t st);   // momcore_strip.hip with mom_lean.hpp
-hipError_t mom_strip10_launch_lean(const void *layer_args, int grid, hipStream_t st);
-size_t mom_strip9_lean_lds_bytes(int ns);
-size_t mom_strip10_lean_lds_bytes(int ns);
-hipError_t mom6_lean9_launch(const void *layer_args, int grid, hipStream_t st);        // momcore_lean6.hip: the six-wave lean image
-hipError_t mom6_lean10_launch(const void *layer_args, int grid, hipStream_t st);
-size_t mom6_lean9_lds_bytes(int ns);
-size_t mom6_lean10_lds_bytes(int ns);
-hipError_t mom2_strip13_launch(const void *layer_args, int grid, hipStream_t st);  // momcore_strip2.hip: the two-buffer 4-wave image
-hipError_t mom2_strip14_launch(const void *layer_args, int grid, hipStream_t st);
-hipError_t mom2_strip15_launch(const void *layer_args, int grid, hipStream_t st);
-size_t mom2_strip13_lds_bytes(int ns, int nS);
-size_t mom2_strip14_lds_bytes(int ns, int nS);
-size_t mom2_strip15_lds_bytes(int ns, int nS);
-size_t mom2_strip13_sched_ints();  // ints of LayerArgs::sched (the same for every size)
-// the quad-block image (momcore_q4.hip, mom_q4.hpp): one wavefront per unit, v_mfma_f64_4x4x4 products, four units per CU
-#define MOM_Q4_DECL(KS)                                                                  \
-  hipError_t momq_q4_##KS##_launch(const void *layer_args, int grid, hipStream_t st);     \
-  size_t momq_q4_##KS##_lds_bytes(int ns, int K);                                         \
-  int momq_q4_##KS##_per_cu();
-MOM_Q4_DECL(5) MOM_Q4_DECL(6) MOM_Q4_DECL(7) MOM_Q4_DECL(8) MOM_Q4_DECL(9) MOM_Q4_DECL(10)
-#undef MOM_Q4_DECL
-// the image of operator edge N = 4 KS: LDS bytes (0: does not apply), launch, workgroups per CU
-static size_t q4_image_lds(int N, int ns, int K) {
-  switch (N) {
-    case 20: return momq_q4_5_lds_bytes(ns, K); case 24: return momq_q4_6_lds_bytes(ns, K); case 28: return momq_q4_7_lds_bytes(ns, K);
-    case 32: return momq_q4_8_lds_bytes(ns, K); case 36: return momq_q4_9_lds_bytes(ns, K); case 40: return momq_q4_10_lds_bytes(ns, K);
-    default: return 0;
-  }
-}
-static hipError_t q4_image_launch(int N, const void *args, int num_cu, size_t units, hipStream_t st) {
-  static int per_cu[6] = {0, 0, 0, 0, 0, 0};   // (per process: the occupancy of an image does not depend on the handle)
-  const int k = N / 4 - 5;
-  if (per_cu[k] == 0)
-    per_cu[k] = (N == 20 ? momq_q4_5_per_cu : N == 24 ? momq_q4_6_per_cu : N == 28 ? momq_q4_7_per_cu : N == 32 ? momq_q4_8_per_cu
-                 : N == 36 ? momq_q4_9_per_cu : momq_q4_10_per_cu)();
-  const int grid = (int)std::min<size_t>(units, (size_t)per_cu[k] * num_cu);
-  return (N == 20 ? momq_q4_5_launch : N == 24 ? momq_q4_6_launch : N == 28 ? momq_q4_7_launch : N == 32 ? momq_q4_8_launch
-          : N == 36 ? momq_q4_9_launch : momq_q4_10_launch)(args, grid, st);
-}
-hipError_t mom_strip11_launch_layer(const void *layer_args, int iface, int grid, size_t smem, hipStream_t st);
-hipError_t mom4_strip11_launch_layer(const void *layer_args, int iface, int grid, size_t smem, hipStream_t st);  // 4-wave build of N = 44
-hipError_t mom_strip13_launch_layer(const void *layer_args, int iface, int grid, size_t smem, hipStream_t st);
-hipError_t mom_strip14_launch_layer(const void *layer_args, int iface, int grid, size_t smem, hipStream_t st);
-hipError_t mom_strip15_launch_layer(const void *layer_args, int iface, int grid, size_t smem, hipStream_t st);
+// the per-size images (strip-chained, lean, two-buffer, quad-block): mom_images.hpp
 hipError_t mom4_launch_surface(const void *surf_args, bool lds, int grid, size_t smem, hipStream_t st);
 int mom4_generic_bufs_elems(int N);
 // momcore_f32.hip: the Float32 build of the scene-level path (dtype = 1)
@@ -499,7 +452,7 @@ struct mom_handle {
   double rrs_ms = 0.0;
   // grow-only device workspace of the operator-level batched entry points (no hipMalloc / hipFree per call, no leak on an
   // error return): slot k holds ws_cap[k] bytes
-  void *ws[4] = {};
+  char *ws[4] = {};
   size_t ws_cap[4] = {};
   // resident HITRAN table + TIPS splines of one absorber (mom_absorption_set_lines)
   MomLineTable lt{};
@@ -537,22 +490,29 @@ static hipError_t dmalloc(T **p, size_t count) {
   return hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T));
 }
 
+// grow-only device buffer: at least `count` elements behind *p, whose capacity *cap counts elements.  No allocation in steady
+// state; before a buffer that is too small is freed, the stream it was last used on (`st`) is drained
+template <class T>
+static hipError_t grow(T **p, size_t *cap, size_t count, hipStream_t st) {
+  if (count <= *cap) return hipSuccess;
+  if (*p) {
+    const hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return e;
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+  }
+  const hipError_t e = dmalloc(p, count);
+  if (e == hipSuccess) *cap = count;
+  return e;
+}
+
 // slot of the handle's grow-only workspace, at least `count` elements of T
 template <class T>
 static hipError_t ws_get(mom_t *h, int slot, T **p, size_t count) {
-  const size_t bytes = count * sizeof(T);
-  if (bytes > h->ws_cap[slot]) {
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return e;
-    (void)hipFree(h->ws[slot]);
-    h->ws[slot] = nullptr;
-    h->ws_cap[slot] = 0;
-    e = hipMalloc(&h->ws[slot], bytes);
-    if (e != hipSuccess) return e;
-    h->ws_cap[slot] = bytes;
-  }
+  const hipError_t e = grow(&h->ws[slot], &h->ws_cap[slot], count * sizeof(T), h->stream);
   *p = reinterpret_cast<T *>(h->ws[slot]);
-  return hipSuccess;
+  return e;
 }
 
 static size_t smem_bytes(const mom_t *h) { return lds_bytes(h->N, h->lds_mode); }
@@ -564,7 +524,8 @@ static size_t smem_bytes(const mom_t *h) { return lds_bytes(h->N, h->lds_mode); 
 // its column is zero in r and off-diagonal in t (zero weight, elemental.jl:198-205), its row is zero because its Z row
 // is, so every product, series and pivoted inverse leaves the real rows and columns with the same terms plus exact zeros.
 constexpr int kPadMax = 4;
-static bool strip_size(int N) { return N == 36 || N == 40 || N == 44 || N == 52 || N == 56 || N == 60; }
+// (the edges that have a strip-chained finisher, of the 4-wave or the 8-wave build: the image table, mom_images.hpp)
+static bool strip_size(int N) { return mom_find_image(MOM_IMG_STRIP4, N) || mom_find_image(MOM_IMG_STRIP8, N); }
 static int strip_pad(int N) {
   if (strip_size(N)) return N;
   for (int p = N + 1; p <= N + kPadMax; ++p)
@@ -578,11 +539,6 @@ static std::vector<double> pad_blocks(const double *src, int N, int Nk, size_t B
     for (int j = 0; j < N; ++j)
       for (int i = 0; i < N; ++i) out[i + (size_t)Nk * (j + (size_t)Nk * b)] = src[i + (size_t)N * (j + (size_t)N * b)];
   return out;
-}
-
-template <class K>
-static hipError_t allow_lds(K kernel, size_t bytes) {
-  return mom_allow_lds(reinterpret_cast<const void *>(kernel), bytes);
 }
 
 void mom_set_global_error(const char *msg) { g_err = msg ? msg : ""; }
@@ -828,31 +784,11 @@ static int check_info(mom_t *h) {
   return MOM_OK;
 }
 
-#define LAUNCH(h, KERN, grid, args)                                                       \
-  do {                                                                                    \
-    const size_t sm__ = smem_bytes(h);                                                    \
-    if ((h)->lds_mode) {                                                                  \
-      HIPCHK(h, allow_lds(KERN<true>, sm__));                                             \
-      hipLaunchKernelGGL(KERN<true>, dim3(grid), dim3(kThreads), sm__, (h)->stream, args); \
-    } else {                                                                              \
-      HIPCHK(h, allow_lds(KERN<false>, sm__));                                            \
-      hipLaunchKernelGGL(KERN<false>, dim3(grid), dim3(kThreads), sm__, (h)->stream, args); \
-    }                                                                                     \
-    HIPCHK(h, hipGetLastError());                                                         \
-  } while (0)
-
-#define LAUNCH2(h, KERN, TARG, grid, args)                                                        \
-  do {                                                                                            \
-    const size_t sm__ = smem_bytes(h);                                                            \
-    if ((h)->lds_mode) {                                                                          \
-      HIPCHK(h, allow_lds(KERN<true, TARG>, sm__));                                               \
-      hipLaunchKernelGGL((KERN<true, TARG>), dim3(grid), dim3(kThreads), sm__, (h)->stream, args); \
-    } else {                                                                                      \
-      HIPCHK(h, allow_lds(KERN<false, TARG>, sm__));                                              \
-      hipLaunchKernelGGL((KERN<false, TARG>), dim3(grid), dim3(kThreads), sm__, (h)->stream, args); \
-    }                                                                                             \
-    HIPCHK(h, hipGetLastError());                                                                 \
-  } while (0)
+// operator-level entry points: KERN<LDSM> (LAUNCH2: KERN<LDSM, TARG>) on the handle's stream with the handle's LDS image
+#define LAUNCH(h, KERN, grid, args) \
+  HIPCHK(h, mom_launch_ldsm(MOM_LDSM(KERN), (h)->lds_mode, grid, kThreads, smem_bytes(h), (h)->stream, args))
+#define LAUNCH2(h, KERN, TARG, grid, args) \
+  HIPCHK(h, mom_launch_ldsm(MOM_LDSM(KERN, TARG), (h)->lds_mode, grid, kThreads, smem_bytes(h), (h)->stream, args))
 
 extern "C" int mom_elemental(mom_t *h, int m, int ndoubl, const double *tau_sum, const double *dtau, const double *varpi,
                              const double *Zpp, const double *Zmp, int z_batch) {
@@ -1054,13 +990,10 @@ static int blas_common(mom_t *h, int n, int batch, const double *A, const double
   BlasArgs a{n, batch, dA, dB, dC, scr, h->d_info};
   const size_t sm = lds_bytes(n, lds);
   if (inv) {
-    if (lds) { HIPCHK(h, allow_lds(k_batch_inv<true>, sm)); hipLaunchKernelGGL(k_batch_inv<true>, dim3(grid), dim3(kThreads), sm, h->stream, a); }
-    else { HIPCHK(h, allow_lds(k_batch_inv<false>, sm)); hipLaunchKernelGGL(k_batch_inv<false>, dim3(grid), dim3(kThreads), sm, h->stream, a); }
+    HIPCHK(h, mom_launch_ldsm(MOM_LDSM(k_batch_inv), lds, grid, kThreads, sm, h->stream, a));
   } else {
-    if (lds) { HIPCHK(h, allow_lds(k_batched_mul<true>, sm)); hipLaunchKernelGGL(k_batched_mul<true>, dim3(grid), dim3(kThreads), sm, h->stream, a); }
-    else { HIPCHK(h, allow_lds(k_batched_mul<false>, sm)); hipLaunchKernelGGL(k_batched_mul<false>, dim3(grid), dim3(kThreads), sm, h->stream, a); }
+    HIPCHK(h, mom_launch_ldsm(MOM_LDSM(k_batched_mul), lds, grid, kThreads, sm, h->stream, a));
   }
-  HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(C, dC, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return inv ? check_info(h) : MOM_OK;
@@ -1144,13 +1077,10 @@ static int dual_common(mom_t *h, int n, int batch, int P, const double *A, const
   DualArgs a{n, batch, P, buf, dA_, buf + cnt, dB_, buf + 2 * cnt, dC_, scr, h->d_info};
   const size_t sm = lds_bytes(n, lds);
   if (inv) {
-    if (lds) { HIPCHK(h, allow_lds(k_batch_inv_dual<true>, sm)); hipLaunchKernelGGL(k_batch_inv_dual<true>, dim3(grid), dim3(kThreads), sm, h->stream, a); }
-    else { HIPCHK(h, allow_lds(k_batch_inv_dual<false>, sm)); hipLaunchKernelGGL(k_batch_inv_dual<false>, dim3(grid), dim3(kThreads), sm, h->stream, a); }
+    HIPCHK(h, mom_launch_ldsm(MOM_LDSM(k_batch_inv_dual), lds, grid, kThreads, sm, h->stream, a));
   } else {
-    if (lds) { HIPCHK(h, allow_lds(k_batched_mul_dual<true>, sm)); hipLaunchKernelGGL(k_batched_mul_dual<true>, dim3(grid), dim3(kThreads), sm, h->stream, a); }
-    else { HIPCHK(h, allow_lds(k_batched_mul_dual<false>, sm)); hipLaunchKernelGGL(k_batched_mul_dual<false>, dim3(grid), dim3(kThreads), sm, h->stream, a); }
+    HIPCHK(h, mom_launch_ldsm(MOM_LDSM(k_batched_mul_dual), lds, grid, kThreads, sm, h->stream, a));
   }
-  HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(C, buf + 2 * cnt, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (P) HIPCHK(h, hipMemcpyAsync(dC, dC_, cntP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1370,6 +1300,21 @@ extern "C" int mom_scene_set_surface(mom_t *h, int kind, int M, const double *Rs
 
 using SmallSweepArgs = MomSmallSweepArgs;  // mom_host.hpp
 
+// The runs that are ONE launch (rt_run_small, rt_run_wave) between the handle's timing events: the launch is the whole "full
+// layers" stage, the surface and post-processing stages are empty
+static int single_launch_begin(mom_t *h) {
+  while (h->ev_full.size() < 2) { hipEvent_t e; HIPCHK(h, hipEventCreate(&e)); h->ev_full.push_back(e); }
+  HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+  HIPCHK(h, hipEventRecord(h->ev_full[0], h->stream));
+  return MOM_OK;
+}
+static int single_launch_end(mom_t *h) {
+  HIPCHK(h, hipEventRecord(h->ev_full[1], h->stream));
+  for (int k = 1; k < 4; ++k) HIPCHK(h, hipEventRecord(h->ev[k], h->stream));
+  h->launches = 1; h->launches_full = 1; h->launches_red = 0;
+  return MOM_OK;
+}
+
 // N <= 4: one spectral point per lane, all moments / layers / surface / post-processing in ONE launch
 static int rt_run_small(mom_t *h) {
   const int N = h->N, Nz = h->Nz;
@@ -1386,11 +1331,7 @@ static int rt_run_small(mom_t *h) {
     HIPCHK(h, hipMemcpyAsync(h->d_smtab, tab, sizeof tab, hipMemcpyHostToDevice, h->stream));
   }
   {
-    if (h->ndif_cap < 2 * (size_t)Nz) {  // no allocation in steady state
-      if (h->d_ndif) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->d_ndif); h->d_ndif = nullptr; }
-      HIPCHK(h, dmalloc(&h->d_ndif, 2 * (size_t)Nz));
-      h->ndif_cap = 2 * (size_t)Nz;
-    }
+    HIPCHK(h, grow(&h->d_ndif, &h->ndif_cap, 2 * (size_t)Nz, h->stream));
     std::vector<int> v(h->nd);
     v.insert(v.end(), h->iface.begin(), h->iface.end());
     HIPCHK(h, hipMemcpyAsync(h->d_ndif, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -1410,23 +1351,13 @@ static int rt_run_small(mom_t *h) {
   if (h->K > 4) return fail(h, MOM_EINVAL, "mom_rt_run: the N <= 4 sweep kernel handles at most 4 phase-matrix bases");
   if (a.M > 1 && h->opt_small != 2) {  // one (point, moment) per lane (mom_small.hip SPLIT); MOM_OPT_SMALL_N = 2: one point per lane
     const size_t need = (size_t)a.M * 2 * a.nVza * a.nS * a.S;
-    if (need > h->smpart_cap) {  // grow-only: no allocation in steady state
-      if (h->d_smpart) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->d_smpart); h->d_smpart = nullptr; h->smpart_cap = 0; }
-      HIPCHK(h, dmalloc(&h->d_smpart, need));
-      h->smpart_cap = need;
-    }
+    HIPCHK(h, grow(&h->d_smpart, &h->smpart_cap, need, h->stream));
     a.part = h->d_smpart;
   }
-  while (h->ev_full.size() < 2) { hipEvent_t e; HIPCHK(h, hipEventCreate(&e)); h->ev_full.push_back(e); }
-  HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-  HIPCHK(h, hipEventRecord(h->ev_full[0], h->stream));
+  int rc = single_launch_begin(h);
+  if (rc) return rc;
   HIPCHK(h, momsm_launch_sweep(&a, N, h->stream));
-  HIPCHK(h, hipEventRecord(h->ev_full[1], h->stream));
-  HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-  HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-  HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
-  h->launches = 1; h->launches_full = 1; h->launches_red = 0;
-  return MOM_OK;
+  return single_launch_end(h);
 }
 
 using WaveSweepArgs = MomWaveSweepArgs;  // mom_host.hpp
@@ -1442,14 +1373,8 @@ static bool wave_sweep_applies(const mom_t *h) {
 // 4 < N <= 32: one spectral point per wavefront, operators in MFMA-layout registers, ONE launch
 static int rt_run_wave(mom_t *h) {
   const int Nz = h->Nz;
-  {
-    if (h->ndif_cap < 2 * (size_t)Nz) {  // no allocation in steady state
-      if (h->d_ndif) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->d_ndif); h->d_ndif = nullptr; }
-      HIPCHK(h, dmalloc(&h->d_ndif, 2 * (size_t)Nz));
-      h->ndif_cap = 2 * (size_t)Nz;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->d_ndif, h->nd.data(), (size_t)Nz * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  }
+  HIPCHK(h, grow(&h->d_ndif, &h->ndif_cap, 2 * (size_t)Nz, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_ndif, h->nd.data(), (size_t)Nz * sizeof(int), hipMemcpyHostToDevice, h->stream));
   WaveSweepArgs a{};
   a.N = h->N; a.S = h->S; a.M = h->scene_M; a.K = h->K; a.Nz = Nz; a.nVza = h->nVza; a.nS = h->nS; a.imu0 = h->q.imu0;
   a.inv_mode = h->opt_inverse;
@@ -1464,16 +1389,123 @@ static int rt_run_wave(mom_t *h) {
   a.R = h->d_R; a.T = h->d_T; a.hdr = h->d_hdr; a.bhr_uw = h->d_bhr_uw; a.bhr_dw = h->d_bhr_dw;
   a.info = h->d_info;
   a.surf_kind = h->surf_kind; a.Rsurf = h->d_Rsurf; a.albedo_spec = h->d_albedo_spec;
-  while (h->ev_full.size() < 2) { hipEvent_t e; HIPCHK(h, hipEventCreate(&e)); h->ev_full.push_back(e); }
-  HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-  HIPCHK(h, hipEventRecord(h->ev_full[0], h->stream));
+  int rc = single_launch_begin(h);
+  if (rc) return rc;
   HIPCHK(h, momw_launch_sweep(&a, h->stream));
-  HIPCHK(h, hipEventRecord(h->ev_full[1], h->stream));
-  HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-  HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-  HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
+  if ((rc = single_launch_end(h))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));  // h->nd may be rewritten by the next scene_set
-  h->launches = 1; h->launches_full = 1; h->launches_red = 0;
+  return MOM_OK;
+}
+
+// ---- one layer launch (rt_run_core's launch_layer) as a policy over the image table (mom_images.hpp) ----------------------
+// the kernel that runs every layer no first-stage image has completed
+enum Finisher { kFinStrip4, kFinStrip8, kFinGen4, kFinGen8 };  // strip-chained image / general k_layer, 4-wave / 8-wave build
+
+static Finisher choose_finisher(const mom_t *h, const DevStreams &q, int ns_tab, bool lds) {
+  // small operators: 4-wave workgroups, two per CU (momcore_w4.hip; the strip-chained images of that build where the edge has
+  // one), when two LDS images fit
+  const MomLayerImage *s4 = mom_find_image(MOM_IMG_STRIP4, q.N);
+  if (lds && h->opt_w4 && np_for(q.N) <= 48 &&
+      2 * (s4 ? s4->lds_bytes(ns_tab, q.nS, h->K) : mom4_lds_bytes(q.N, true)) + 2048 <= 160 * 1024)
+    return s4 ? kFinStrip4 : kFinGen4;
+  return (lds && mom_find_image(MOM_IMG_STRIP8, q.N)) ? kFinStrip8 : kFinGen8;
+}
+
+// At most one first-stage image in front of the finisher, or {nullptr}.  Behind each of them the finisher resumes what it left:
+//   * general 4-wave image (operator edges 20 .. 32, multiples of 4): the quad-block image (mom_q4.hpp), MOM_OPT_LEAN >= 3;
+//   * 4-wave strip image: MOM_OPT_LEAN = 3 the quad-block image, 2 the six-wave lean image, 1 (and wherever the chosen one does
+//     not apply) the lean image (three workgroups per CU; mom_lean.hpp) -- the route exists only where the lean image applies;
+//   * 8-wave strip image: the two-buffer 4-wave image (two workgroups per CU; mom_strip2.hpp), MOM_OPT_STRIP2 (C2: it leaves
+//     nothing -- the finisher's launch reads the resume table and ends).
+struct FirstStage {
+  const MomLayerImage *image;
+  MomImageFamily family;
+};
+static FirstStage choose_first_stage(const mom_t *h, Finisher fin, const DevStreams &q, int ns_tab) {
+  auto applying = [&](MomImageFamily f) {
+    const MomLayerImage *im = mom_find_image(f, q.N);
+    return FirstStage{(im && im->lds_bytes(ns_tab, q.nS, h->K) > 0) ? im : nullptr, f};
+  };
+  if (fin == kFinGen4 && h->opt_lean >= 3) return applying(MOM_IMG_QUAD);
+  if (fin == kFinStrip8 && h->opt_strip2) return applying(MOM_IMG_STRIP2);
+  if (fin == kFinStrip4 && h->opt_lean) {
+    const FirstStage lean = applying(MOM_IMG_LEAN);
+    if (lean.image && h->opt_lean >= 2) {
+      const FirstStage alt = applying(h->opt_lean >= 3 ? MOM_IMG_QUAD : MOM_IMG_LEAN6);
+      if (alt.image) return alt;
+    }
+    return lean;
+  }
+  return FirstStage{nullptr, MOM_IMG_LEAN};
+}
+
+// The first-stage launch of `fs` for the sweep described by `a`, if it applies: a whole-slab sweep of a single-target run, no
+// forced pivoted inverse, interface code 3 on every layer that interacts (the images handle no other).  On return a.resume (and
+// a.sched) are set for the finisher as well.
+static int launch_first_stage(mom_t *h, const FirstStage &fs, LayerArgs &a, bool multi_target, hipStream_t st) {
+  const int nzr = a.Nz_sweep;  // 0: a per-layer launch
+  bool ok = fs.image && nzr > 0 && !multi_target && a.q.inv_mode == 0;
+  for (int k = 1; k < nzr && ok; ++k) ok = (a.iface_z[k] == 3);
+  if (ok && !a.first) ok = (a.iface_z[0] == 3);
+  if (!ok) return MOM_OK;
+  const size_t units = (size_t)a.S * a.M;
+  // resume[unit]: the two-buffer image has a table of its own -- under MOM_OPT_OVERLAP the m = 0 sub-problem's first stage and
+  // the full problem's two-buffer launch can be in flight at once
+  const bool two_buffer = (fs.family == MOM_IMG_STRIP2);
+  int **table = two_buffer ? &h->d_resume2 : &h->d_resume;
+  HIPCHK(h, grow(table, two_buffer ? &h->resume2_cap : &h->resume_cap, units, st));
+  a.resume = *table;
+  int per_cu = fs.image->per_cu();
+  if (two_buffer) {
+    h->resume2_units = units; h->resume2_nz = nzr;  // (mom_strip2_resumed)
+    if (h->opt_strip2_sched) {  // the queue counter (and, for the chain priority, the per-CU tickets) start at zero: a memset ON
+                                // THE STREAM, so that an asynchronous step (or a captured one) resets them in order with its launches
+      const size_t ints = kMomStrip2SchedInts;
+      if (!h->d_sched2) HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_sched2), ints * sizeof(int)));
+      HIPCHK(h, hipMemsetAsync(h->d_sched2, 0, ((h->opt_strip2_sched & 2) ? ints : 1) * sizeof(int), st));
+      a.sched = h->d_sched2;
+      a.sched_mode = h->opt_strip2_sched;
+    }
+  }
+#ifdef MOM_EXPERIMENTS
+  if (fs.family == MOM_IMG_LEAN || fs.family == MOM_IMG_LEAN6) {
+    static const int lean_per_cu = getenv("MOM_LEAN_PER_CU") ? atoi(getenv("MOM_LEAN_PER_CU")) : 0;
+    if (lean_per_cu > 0) per_cu = lean_per_cu;
+  }
+#endif
+  const int grid = (int)std::min<size_t>(units, (size_t)per_cu * h->num_cu);  // persistent workgroups
+  HIPCHK(h, fs.image->launch(&a, a.iface, grid, st));
+  h->launches++;
+  return MOM_OK;
+}
+
+// One k_layer launch (plus the first-stage launch in front of it, if any) of the argument block `a` on stream `st`
+static int launch_layer_images(mom_t *h, LayerArgs &a, bool multi_target, hipStream_t st) {
+  const DevStreams &q = a.q;
+  const size_t units = (size_t)a.S * a.M;
+  const bool lds = (q.N <= 64) && !h->opt_force_generic;
+  const int ns_tab = q.regular ? q.nS : 1;  // Stokes components per stream of the elemental layer's stream-pair tables
+  const Finisher fin = choose_finisher(h, q, ns_tab, lds);
+  const int rc = launch_first_stage(h, choose_first_stage(h, fin, q, ns_tab), a, multi_target, st);
+  if (rc) return rc;
+  if (fin == kFinStrip4 || fin == kFinStrip8) {  // strip-chained kernels (momcore_strip.hip), one image per N
+    const MomLayerImage *im = mom_find_image(fin == kFinStrip4 ? MOM_IMG_STRIP4 : MOM_IMG_STRIP8, q.N);
+    // 8-wave build: persistent workgroups, one per CU (only one 135 KB LDS image fits a CU): the prologue is paid once;
+    // their start is staggered over about one unit time (~ (44 + 17 nd) us at N = 60)
+    // (not behind the two-buffer image: its units are done, a staggered start would only delay the empty resume launch)
+    if (fin == kFinStrip8 && units >= 8 * (size_t)h->num_cu && h->opt_stagger && a.resume == nullptr) {
+      const double f = (double)q.N / 60.0, unit_us = f * f * f * (44.0 + 17.0 * a.nd);
+      a.stagger = (int)(unit_us * 100.0 / 32.0);
+    }
+    const int grid = (int)std::min<size_t>(units, (size_t)im->per_cu() * h->num_cu);  // persistent: two per CU (4-wave), one (8-wave)
+    HIPCHK(h, im->launch(&a, a.iface, grid, st));
+  } else if (fin == kFinGen4) {
+    HIPCHK(h, mom4_launch_layer(&a, a.iface, true, (int)((a.S >= 2048) ? a.S : units), mom4_lds_bytes(q.N, true), st));
+  } else {
+    const int grid = lds ? (int)((a.S >= 2048) ? a.S : units) : (int)std::min<size_t>(units, (size_t)h->G);
+    HIPCHK(h, mom_gen_launch_layer(&a, a.iface, lds, grid, lds_bytes(q.N, lds), st));
+  }
+  h->launches++;
   return MOM_OK;
 }
 
@@ -1534,118 +1566,7 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, double *const c
         for (int t = 0; t < kMaxTargets; ++t) a.act_z[r][t] = tg->act[(size_t)(r0 + r) * kMaxTargets + t];
     }
     a.scratch = scratch; a.info = h->d_info;
-    const bool lds = (q.N <= 64) && !h->opt_force_generic;
-    // small operators: 4-wave workgroups, two per CU (momcore_w4.hip), when two LDS images fit
-    const int ns_tab = q.regular ? q.nS : 1;  // Stokes components per stream of the elemental layer's stream-pair tables
-    const bool strip4 = (q.N == 36 || q.N == 40 || q.N == 44);
-    if (lds && h->opt_w4 && np_for(q.N) <= 48 &&
-        2 * (strip4 ? mom4_strip_lds_bytes(q.N, ns_tab) : mom4_lds_bytes(q.N, true)) + 2048 <= 160 * 1024) {
-      const int grid4 = (int)((S >= 2048) ? S : S * Mcount);
-      // operator edges 20 .. 32 (multiples of 4) on the quad-block image first (mom_q4.hpp), the general 4-wave image finishes what
-      // it left; the edges 36 / 40 take the same route below, with the strip image as the finisher
-      if (!strip4 && h->opt_lean >= 3 && sweep && !tg && q.inv_mode == 0 && q4_image_lds(q.N, ns_tab, h->K) > 0) {
-        bool quad = true;
-        for (int k = 1; k < nzr && quad; ++k) quad = (a.iface_z[k] == 3);
-        if (quad && !a.first) quad = (a.iface_z[0] == 3);
-        if (quad) {
-          const size_t units = S * (size_t)Mcount;
-          if (units > h->resume_cap) {  // grow-only
-            if (h->d_resume) { HIPCHK(h, hipStreamSynchronize(cur)); (void)hipFree(h->d_resume); h->d_resume = nullptr; h->resume_cap = 0; }
-            HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_resume), units * sizeof(int)));
-            h->resume_cap = units;
-          }
-          a.resume = h->d_resume;
-          HIPCHK(h, q4_image_launch(q.N, &a, h->num_cu, units, cur));
-          h->launches++;
-        }
-      }
-      if (strip4) {  // strip-chained kernels of the 4-wave build (momcore_strip.hip)
-        const int gridp = (int)std::min<size_t>(S * Mcount, (size_t)2 * h->num_cu);  // persistent, two per CU
-        // N = 36, 40: the lean image first (three workgroups per CU; mom_lean.hpp), then the full image resumes what it left
-        bool lean = h->opt_lean && sweep && !tg && q.inv_mode == 0 && (q.N == 36 || q.N == 40) &&
-                    (q.N == 40 ? mom_strip10_lean_lds_bytes(ns_tab) : mom_strip9_lean_lds_bytes(ns_tab)) > 0;
-        for (int k = 1; k < nzr && lean; ++k) lean = (a.iface_z[k] == 3);
-        if (lean && !a.first) lean = (a.iface_z[0] == 3);
-        if (lean) {
-          const size_t units = S * (size_t)Mcount;
-          if (units > h->resume_cap) {  // grow-only
-            if (h->d_resume) { HIPCHK(h, hipStreamSynchronize(cur)); (void)hipFree(h->d_resume); h->d_resume = nullptr; h->resume_cap = 0; }
-            HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_resume), units * sizeof(int)));
-            h->resume_cap = units;
-          }
-          a.resume = h->d_resume;
-          const bool quad = h->opt_lean >= 3 && q4_image_lds(q.N, ns_tab, h->K) > 0;
-          const bool six = !quad && h->opt_lean == 2 && (q.N == 40 ? mom6_lean10_lds_bytes(ns_tab) : mom6_lean9_lds_bytes(ns_tab)) > 0;
-#ifdef MOM_EXPERIMENTS
-          static const int lean_per_cu = getenv("MOM_LEAN_PER_CU") ? atoi(getenv("MOM_LEAN_PER_CU")) : 0;
-#else
-          const int lean_per_cu = 0;
-#endif
-          const int per_cu = lean_per_cu > 0 ? lean_per_cu : (six ? 2 : 3);
-          const int gridl = (int)std::min<size_t>(units, (size_t)per_cu * h->num_cu);
-          if (quad) HIPCHK(h, q4_image_launch(q.N, &a, h->num_cu, units, cur));
-          else if (six) HIPCHK(h, (q.N == 40 ? mom6_lean10_launch : mom6_lean9_launch)(&a, gridl, cur));
-          else HIPCHK(h, (q.N == 40 ? mom_strip10_launch_lean : mom_strip9_launch_lean)(&a, gridl, cur));
-          h->launches++;
-        }
-        HIPCHK(h, (q.N == 44 ? mom4_strip11_launch_layer : q.N == 40 ? mom_strip10_launch_layer : mom_strip9_launch_layer)(
-                      &a, a.iface, gridp, mom4_strip_lds_bytes(q.N, ns_tab), cur));
-        h->launches++;
-        return MOM_OK;
-      }
-      HIPCHK(h, mom4_launch_layer(&a, a.iface, true, grid4, mom4_lds_bytes(q.N, true), cur));
-      h->launches++;
-      return MOM_OK;
-    }
-    size_t sm = lds_bytes(q.N, lds);
-    if (lds && (q.N == 44 || q.N == 52 || q.N == 56 || q.N == 60)) {  // strip-chained kernels (momcore_strip.hip), one image per N
-      sm = strip_lds_bytes(q.N, ns_tab);  // + the persistent stream-pair tables
-      // N = 52, 56, 60: the two-buffer 4-wave image first (two workgroups per CU; mom_strip2.hpp), then this image resumes what it
-      // left (C2: nothing -- its launch reads the resume table and ends)
-      size_t (*const s2_lds)(int, int) = q.N == 60 ? mom2_strip15_lds_bytes : q.N == 56 ? mom2_strip14_lds_bytes
-                                       : q.N == 52 ? mom2_strip13_lds_bytes : nullptr;
-      bool s2 = h->opt_strip2 && sweep && !tg && q.inv_mode == 0 && s2_lds && s2_lds(ns_tab, q.nS) > 0;
-      for (int k = 1; k < nzr && s2; ++k) s2 = (a.iface_z[k] == 3);
-      if (s2 && !a.first) s2 = (a.iface_z[0] == 3);
-      if (s2) {
-        const size_t units = S * (size_t)Mcount;
-        if (units > h->resume2_cap) {  // grow-only
-          if (h->d_resume2) { HIPCHK(h, hipStreamSynchronize(cur)); (void)hipFree(h->d_resume2); h->d_resume2 = nullptr; h->resume2_cap = 0; }
-          HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_resume2), units * sizeof(int)));
-          h->resume2_cap = units;
-        }
-        a.resume = h->d_resume2;
-        h->resume2_units = units; h->resume2_nz = nzr;
-        if (h->opt_strip2_sched) {  // the queue counter (and, for the chain priority, the per-CU tickets) start at zero: a memset ON
-                                    // THE STREAM, so that an asynchronous step (or a captured one) resets them in order with its launches
-          const size_t ints = mom2_strip13_sched_ints();
-          if (!h->d_sched2) HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_sched2), ints * sizeof(int)));
-          HIPCHK(h, hipMemsetAsync(h->d_sched2, 0, ((h->opt_strip2_sched & 2) ? ints : 1) * sizeof(int), cur));
-          a.sched = h->d_sched2;
-          a.sched_mode = h->opt_strip2_sched;
-        }
-        const int grid2 = (int)std::min<size_t>(units, (size_t)2 * h->num_cu);  // persistent, two per CU
-        HIPCHK(h, (q.N == 60 ? mom2_strip15_launch : q.N == 56 ? mom2_strip14_launch : mom2_strip13_launch)(&a, grid2, cur));
-        h->launches++;
-      }
-      // persistent workgroups, one per CU (only one 135 KB LDS image fits a CU): the prologue is paid once;
-      // their start is staggered over about one unit time (~ (44 + 17 nd) us at N = 60)
-      // (not behind the two-buffer image: its units are done, a staggered start would only delay the empty resume launch)
-      if (S * Mcount >= 8 * (size_t)h->num_cu && h->opt_stagger && a.resume == nullptr) {
-        const double f = (double)q.N / 60.0, unit_us = f * f * f * (44.0 + 17.0 * a.nd);
-        a.stagger = (int)(unit_us * 100.0 / 32.0);
-      }
-      const int grid = (int)std::min<size_t>(S * Mcount, (size_t)h->num_cu);
-      HIPCHK(h, (q.N == 60 ? mom_strip15_launch_layer : q.N == 56 ? mom_strip14_launch_layer : q.N == 52 ? mom_strip13_launch_layer : mom_strip11_launch_layer)(
-                    &a, a.iface, grid, sm, cur));
-      h->launches++;
-      return MOM_OK;
-    }
-    const int grid = lds ? (int)((S >= 2048) ? S : S * Mcount) : (int)std::min<size_t>(S * Mcount, (size_t)h->G);
-    HIPCHK(h, mom_gen_launch_layer(&a, a.iface, lds, grid, sm, cur));
-    HIPCHK(h, hipGetLastError());
-    h->launches++;
-    return MOM_OK;
+    return launch_layer_images(h, a, tg != nullptr, cur);
   };
   // MOM_OPT_OVERLAP: the two launches of a sweep -- moments 1..M-1 on the full problem, moment 0 on the (I,Q) sub-problem --
   // are independent.  What runs at the edges 52 / 56 / 60 (C2: N = 60, sub-problem N = 40): the sub-problem on the quad-block image
@@ -1661,7 +1582,7 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, double *const c
   // to fill: re-measured at the default, 322.6 ms with the overlap and 322.7 without (profiles/r08_C2_ab.txt).  It costs nothing,
   // so the gate stays
   const bool two = red0 && can_sweep && h->opt_overlap && M > 1 && !tg && h->stream2 && !h->opt_force_generic &&
-                   (Nk == 52 || Nk == 56 || Nk == 60);
+                   mom_find_image(MOM_IMG_STRIP2, Nk) != nullptr;  // ("the edges below": those of the two-buffer image)
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
   for (int z = (can_sweep ? -1 : za); z < (can_sweep ? 0 : zb); ++z) {
     int rc;
@@ -1723,14 +1644,9 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, double *const c
     const hipStream_t sst = (two && red) ? h->stream2 : h->stream;  // the sub-problem's surface follows its layers
     if (lds && h->opt_w4 && np_for(q.N) <= 48 && 2 * mom4_lds_bytes(q.N, true) + 2048 <= 160 * 1024) {
       HIPCHK(h, mom4_launch_surface(&a, true, (int)S, mom4_lds_bytes(q.N, true), sst));
-    } else if (lds) {
-      HIPCHK(h, allow_lds(k_surface<true>, sm));
-      hipLaunchKernelGGL(k_surface<true>, dim3(grid), dim3(kThreads), sm, sst, a);
     } else {
-      HIPCHK(h, allow_lds(k_surface<false>, sm));
-      hipLaunchKernelGGL(k_surface<false>, dim3(grid), dim3(kThreads), sm, sst, a);
+      HIPCHK(h, mom_launch_ldsm(MOM_LDSM(k_surface), lds, grid, kThreads, sm, sst, a));
     }
-    HIPCHK(h, hipGetLastError());
   }
   if (two) {  // join: everything below (post-processing, the caller's downloads) is ordered behind both streams
     HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));
@@ -1800,11 +1716,7 @@ extern "C" int mom_rt_run_multisensor(mom_t *h, int nSensors, const int *sensor_
     }
     for (int k = 0; k < 2; ++k) HIPCHK(h, dmalloc(&h->d_msJ[k], (size_t)Na * S * h->M));
   }
-  if (h->ms_out_cap < 2 * out1 * nSensors) {
-    if (h->d_ms_out) { (void)hipFree(h->d_ms_out); h->d_ms_out = nullptr; }
-    HIPCHK(h, dmalloc(&h->d_ms_out, 2 * out1 * nSensors));
-    h->ms_out_cap = 2 * out1 * nSensors;
-  }
+  HIPCHK(h, grow(&h->d_ms_out, &h->ms_out_cap, 2 * out1 * nSensors, h->stream));
   double *d_uw = h->d_ms_out, *d_dw = h->d_ms_out + out1 * nSensors;
   // rt_kernel_multisensor! (rt_kernel_multisensor.jl:51-112): ONE sweep over the layers builds every layer's added operators
   // once and feeds all composites -- the running slab above the sensors (target 0, frozen into a per-sensor snapshot when
@@ -1874,14 +1786,8 @@ extern "C" int mom_rt_run_multisensor(mom_t *h, int nSensors, const int *sensor_
       const bool lds = (Nk <= 64) && !h->opt_force_generic;
       const size_t sm = lds_bytes(Nk, lds);
       const size_t units = S * M;
-      if (lds) {
-        HIPCHK(h, allow_lds(k_combine<true>, sm));
-        hipLaunchKernelGGL(k_combine<true>, dim3((unsigned)units), dim3(kThreads), sm, h->stream, a);
-      } else {
-        HIPCHK(h, allow_lds(k_combine<false>, sm));
-        hipLaunchKernelGGL(k_combine<false>, dim3((unsigned)std::min<size_t>(units, (size_t)h->G)), dim3(kThreads), sm, h->stream, a);
-      }
-      HIPCHK(h, hipGetLastError());
+      const int grid = (int)(lds ? units : std::min<size_t>(units, (size_t)h->G));
+      HIPCHK(h, mom_launch_ldsm(MOM_LDSM(k_combine), lds, grid, kThreads, sm, h->stream, a));
     }
     for (int i = 0; i < nc; ++i) {
       const int ims = ord[i], L = sensor_levels[ims];
@@ -1898,14 +1804,8 @@ extern "C" int mom_rt_run_multisensor(mom_t *h, int nSensors, const int *sensor_
         const bool lds = (Nk <= 64) && !h->opt_force_generic;
         const size_t sm = lds_bytes(Nk, lds);
         const size_t units = S * M;
-        if (lds) {
-          HIPCHK(h, allow_lds(k_interlayer<true>, sm));
-          hipLaunchKernelGGL(k_interlayer<true>, dim3((unsigned)units), dim3(kThreads), sm, h->stream, a);
-        } else {
-          HIPCHK(h, allow_lds(k_interlayer<false>, sm));
-          hipLaunchKernelGGL(k_interlayer<false>, dim3((unsigned)std::min<size_t>(units, (size_t)h->G)), dim3(kThreads), sm, h->stream, a);
-        }
-        HIPCHK(h, hipGetLastError());
+        const int grid = (int)(lds ? units : std::min<size_t>(units, (size_t)h->G));
+        HIPCHK(h, mom_launch_ldsm(MOM_LDSM(k_interlayer), lds, grid, kThreads, sm, h->stream, a));
         PostArgs pa{};
         pa.N = Nk; pa.nS = h->nS; pa.S = h->S; pa.M = M; pa.nVza = h->nVza; pa.red0 = 0;
         pa.node = h->d_node; pa.cos_mphi = h->d_cos; pa.sin_mphi = h->d_sin;
@@ -2158,12 +2058,7 @@ extern "C" int mom_postprocess(mom_t *h, int m, int nVza, const int *node_1based
   HIPCHK(h, hipSetDevice(h->device));
   { const int rc_ = op_composite_ready(h, "mom_postprocess"); if (rc_) return rc_; }
   const size_t total = (size_t)nVza * h->nS * h->S;
-  if (total > h->post_cap) {
-    if (h->d_post[0]) (void)hipFree(h->d_post[0]);
-    h->d_post[0] = nullptr; h->post_cap = 0;
-    HIPCHK(h, dmalloc(&h->d_post[0], 2 * total));
-    h->post_cap = total;
-  }
+  HIPCHK(h, grow(&h->d_post[0], &h->post_cap, 2 * total, h->stream));
   h->d_post[1] = h->d_post[0] + total;
   // bigCS = weight * Diagonal([cos(m φ), cos(m φ), sin(m φ), sin(m φ)][1:n])   (postprocessing_vza.jl:32-33)
   auto cosd = [](double x) { return mom_cosd(x); };
@@ -2312,12 +2207,7 @@ extern "C" int mom_allgather_RT(mom_t *h, double *R_SFI_global, double *T_SFI_gl
   if (!h->comm) return fail(h, MOM_ESTATE, "mom_allgather_RT: call mom_comm_init first");
   HIPCHK(h, hipSetDevice(h->device));
   const size_t nout = (size_t)h->nVza * h->nS * h->S, need = 2 * nout * h->comm_size;
-  if (need > h->gather_cap) {
-    if (h->d_gather) (void)hipFree(h->d_gather);
-    h->d_gather = nullptr; h->gather_cap = 0;
-    HIPCHK(h, dmalloc(&h->d_gather, need));
-    h->gather_cap = need;
-  }
+  HIPCHK(h, grow(&h->d_gather, &h->gather_cap, need, h->stream));
   int rc = mom_allgather_RT_device(h, h->d_gather);
   if (rc) return rc;
   // [rank][R|T][nVza, nStokes, S_loc] -> R_SFI, T_SFI [nVza, nStokes, nranks * S_loc] (rank-major spectral axis)
@@ -2529,11 +2419,7 @@ extern "C" int mom_voigt_tau_abs_profile(mom_t *h, int Nz, const double *pressur
   const size_t cap = h->lines_cap;
   // per-layer scalars [p | T | cgd | factor][Nz] and the Nz sortedness flags
   const size_t prm_doubles = 4 * (size_t)Nz + ((size_t)Nz + 1) / 2;
-  if (prm_doubles > h->prof_cap) {
-    if (h->d_prof) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->d_prof); h->d_prof = nullptr; h->prof_cap = 0; }
-    HIPCHK(h, dmalloc(&h->d_prof, prm_doubles));
-    h->prof_cap = prm_doubles;
-  }
+  HIPCHK(h, grow(&h->d_prof, &h->prof_cap, prm_doubles, h->stream));
   std::vector<double> prm(4 * (size_t)Nz);
   for (int z = 0; z < Nz; ++z) {
     prm[z] = pressure[z];
@@ -3050,12 +2936,7 @@ extern "C" int mom_allgather_rrs_device(mom_t *h, int per, void *d_global) {
   if (!h->comm) return fail(h, MOM_ESTATE, "mom_allgather_rrs_device: call mom_comm_init first");
   if (!d_global) return fail(h, MOM_EINVAL, "mom_allgather_rrs_device: null buffer");
   const size_t cnt = mom_rrs_spectra_count(h, per);
-  if (cnt > h->rrs_send_cap) {
-    if (h->d_rrs_send) (void)hipFree(h->d_rrs_send);
-    h->d_rrs_send = nullptr; h->rrs_send_cap = 0;
-    HIPCHK(h, dmalloc(&h->d_rrs_send, cnt));
-    h->rrs_send_cap = cnt;
-  }
+  HIPCHK(h, grow(&h->d_rrs_send, &h->rrs_send_cap, cnt, h->stream));
   if ((rc = rrs_pack_owned(h, per, h->d_rrs_send))) return rc;
   return mom_allgather(h, h->d_rrs_send, d_global, cnt);
 }

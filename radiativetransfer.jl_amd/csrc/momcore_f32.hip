@@ -7,7 +7,7 @@
 // the f64 rate), LDS images half the size.  What runs: the fused per-layer kernels of the general path (LDS-resident
 // for N <= 64, generic mode above), layer-sweep mode, the surface layer (all three surface kinds) with HDRF/BHR, and
 // post-processing; r4: the strip-chained images of the 8-wave build (N = 44, 52, 56, 60: momcore_strip.hip compiled for
-// float, momf_strip<KS>_launch_layer), the (I,Q) reduction of moment 0 (a nested sub-scene: momf_scene::sub) and the padding of
+// float, families F32_STRIP8 / F32_STRIP4 of mom_images.hpp), the (I,Q) reduction of moment 0 (a nested sub-scene: momf_scene::sub) and the padding of
 // other edges to the strip sizes (strip_pad_f), and the operator-level API on dtype = 1 handles (mom_ops.hpp compiled for float:
 // mom_elemental ... mom_download).  Not built for f32: multi-sensor, RRS, the device-side optics route.
 //
@@ -29,6 +29,7 @@
 #include "mom_entry.hpp"
 #include "mom_ops.hpp"
 #include "mom_host.hpp"
+#include "mom_images.hpp"
 
 using namespace momf;
 
@@ -489,21 +490,8 @@ int momf_scene_set_surface(momf_scene *s, int kind, int M, const double *Rsurf, 
   return MOM_OK;
 }
 
-template <class K>
-static hipError_t allow(K kernel, size_t bytes) { return mom_allow_lds(reinterpret_cast<const void *>(kernel), bytes); }
-
 hipError_t momwf_launch_sweep(const void *args, hipStream_t st);  // mom_wave.hip built with -DMOMW_FLOAT
-// momcore_strip.hip built for float (Makefile: momcore_fs<KS>.o)
-hipError_t momf_strip11_launch_layer(const void *layer_args, int iface, int grid, size_t smem, hipStream_t st);
-hipError_t momf_strip13_launch_layer(const void *layer_args, int iface, int grid, size_t smem, hipStream_t st);
-hipError_t momf_strip14_launch_layer(const void *layer_args, int iface, int grid, size_t smem, hipStream_t st);
-hipError_t momf_strip15_launch_layer(const void *layer_args, int iface, int grid, size_t smem, hipStream_t st);
-// ... and their 4-wave builds (momcore_f4s<KS>.o, namespace momf4): two workgroups per CU
-#define MOMF4_DECL(KS)                                                                                          \
-  hipError_t momf4_strip##KS##_launch_layer(const void *layer_args, int iface, int grid, size_t smem, hipStream_t st); \
-  size_t momf4_strip##KS##_lds_bytes();
-MOMF4_DECL(9) MOMF4_DECL(10) MOMF4_DECL(11) MOMF4_DECL(13) MOMF4_DECL(14) MOMF4_DECL(15)
-#undef MOMF4_DECL
+// momcore_strip.hip built for float (Makefile: momcore_fs<KS>.o, 8 waves; momcore_f4s<KS>.o, 4 waves): mom_images.hpp
 
 // 4 < N <= 32: one spectral point per wavefront, operators in MFMA-layout registers, the whole run in ONE launch -- the
 // Float32 build of momw::k_wsweep (the Float64 path: rt_run_wave in momcore.hip).  Covers ScatteringInterface_11 on every
@@ -625,52 +613,19 @@ int momf_rt_run(momf_scene *s) {
     for (int k = 0; k < 6; ++k) a.comp[k] = s->comp[k];
     a.scratch = s->d_scratch; a.info = s->d_info;
     const int grid = lds ? (int)((S >= 2048) ? S : S * M) : (int)std::min<size_t>(S * M, (size_t)s->G);
-#define F32_LAUNCH(IF)                                                                            \
-  if (lds) {                                                                                      \
-    FCHK(s, allow(k_layer<true, IF>, sm));                                                        \
-    hipLaunchKernelGGL((k_layer<true, IF>), dim3(grid), dim3(kThreads), sm, s->stream, a);         \
-  } else {                                                                                        \
-    FCHK(s, allow(k_layer<false, IF>, sm));                                                       \
-    hipLaunchKernelGGL((k_layer<false, IF>), dim3(grid), dim3(kThreads), sm, s->stream, a);        \
-  }
     // strip-chained images (Float32 builds of mom_strip.hpp's chains) for the edges that have one; MOM_OPT_INVERSE != 0 keeps
     // the general path inside the same image, MOM_OPT_STRIPS_F32 = 0 (s->strips) the general image
-    const int ks4 = (N % 4 == 0) ? N / 4 : 0;
-    if (lds && s->strips && s->w4 && (ks4 == 9 || ks4 == 10 || ks4 == 11 || ks4 == 13 || ks4 == 14 || ks4 == 15)) {
-      // 4-wave images (N = 36, 40 have no other): two workgroups per CU
-      hipError_t e = hipSuccess;
-      switch (ks4) {
-        case 9: e = momf4_strip9_launch_layer(&a, a.iface, grid, momf4_strip9_lds_bytes(), s->stream); break;
-        case 10: e = momf4_strip10_launch_layer(&a, a.iface, grid, momf4_strip10_lds_bytes(), s->stream); break;
-        case 11: e = momf4_strip11_launch_layer(&a, a.iface, grid, momf4_strip11_lds_bytes(), s->stream); break;
-        case 13: e = momf4_strip13_launch_layer(&a, a.iface, grid, momf4_strip13_lds_bytes(), s->stream); break;
-        case 14: e = momf4_strip14_launch_layer(&a, a.iface, grid, momf4_strip14_lds_bytes(), s->stream); break;
-        default: e = momf4_strip15_launch_layer(&a, a.iface, grid, momf4_strip15_lds_bytes(), s->stream); break;
-      }
-      FCHK(s, e);
+    // 4-wave images (N = 36, 40 have no other): two workgroups per CU
+    const MomLayerImage *im = (lds && s->strips && s->w4) ? mom_find_image(MOM_IMG_F32_STRIP4, N) : nullptr;
+    if (!im && lds && s->strips) im = mom_find_image(MOM_IMG_F32_STRIP8, N);
+    if (im) {
+      FCHK(s, im->launch(&a, a.iface, grid, s->stream));
       s->launches++;
       continue;
     }
-    if (lds && s->strips && (ks4 == 11 || ks4 == 13 || ks4 == 14 || ks4 == 15)) {
-      hipError_t e = hipSuccess;
-      switch (ks4) {
-        case 11: e = momf_strip11_launch_layer(&a, a.iface, grid, sm, s->stream); break;
-        case 13: e = momf_strip13_launch_layer(&a, a.iface, grid, sm, s->stream); break;
-        case 14: e = momf_strip14_launch_layer(&a, a.iface, grid, sm, s->stream); break;
-        default: e = momf_strip15_launch_layer(&a, a.iface, grid, sm, s->stream); break;
-      }
-      FCHK(s, e);
-      s->launches++;
-      continue;
-    }
-    switch (a.iface) {
-      case 0: F32_LAUNCH(0) break;
-      case 1: F32_LAUNCH(1) break;
-      case 2: F32_LAUNCH(2) break;
-      default: F32_LAUNCH(3) break;
-    }
+#define F32_LAUNCH(IF) FCHK(s, mom_launch_ldsm(MOM_LDSM(k_layer, IF), lds, grid, kThreads, sm, s->stream, a))
+    MOM_IFACE_SWITCH(a.iface, F32_LAUNCH)
 #undef F32_LAUNCH
-    FCHK(s, hipGetLastError());
     s->launches++;
   }
   FCHK(s, hipEventRecord(s->ev[1], s->stream));
@@ -687,14 +642,7 @@ int momf_rt_run(momf_scene *s) {
     a.bhr_uw = s->d_bhr_uw; a.bhr_dw = s->d_bhr_dw; a.nS_out = s->nS;
     a.scratch = s->d_scratch; a.info = s->d_info;
     const int grid = lds ? (int)S : (int)std::min<size_t>(S, (size_t)s->G);
-    if (lds) {
-      FCHK(s, allow(k_surface<true>, sm));
-      hipLaunchKernelGGL(k_surface<true>, dim3(grid), dim3(kThreads), sm, s->stream, a);
-    } else {
-      FCHK(s, allow(k_surface<false>, sm));
-      hipLaunchKernelGGL(k_surface<false>, dim3(grid), dim3(kThreads), sm, s->stream, a);
-    }
-    FCHK(s, hipGetLastError());
+    FCHK(s, mom_launch_ldsm(MOM_LDSM(k_surface), lds, grid, kThreads, sm, s->stream, a));
   }
   FCHK(s, hipEventRecord(s->ev[2], s->stream));
   {
@@ -789,13 +737,10 @@ int momf_blas(momf_scene *s, int n, int batch, const double *A, const double *B,
   BlasArgsF a{n, batch, dA, dB, dC, scr, s->d_info};
   const size_t sm = lds_bytes(n, lds);
   if (inv) {
-    if (lds) { FCHK(s, allow(k_batch_inv_f32<true>, sm)); hipLaunchKernelGGL(k_batch_inv_f32<true>, dim3(grid), dim3(kThreads), sm, s->stream, a); }
-    else { FCHK(s, allow(k_batch_inv_f32<false>, sm)); hipLaunchKernelGGL(k_batch_inv_f32<false>, dim3(grid), dim3(kThreads), sm, s->stream, a); }
+    FCHK(s, mom_launch_ldsm(MOM_LDSM(k_batch_inv_f32), lds, grid, kThreads, sm, s->stream, a));
   } else {
-    if (lds) { FCHK(s, allow(k_batched_mul_f32<true>, sm)); hipLaunchKernelGGL(k_batched_mul_f32<true>, dim3(grid), dim3(kThreads), sm, s->stream, a); }
-    else { FCHK(s, allow(k_batched_mul_f32<false>, sm)); hipLaunchKernelGGL(k_batched_mul_f32<false>, dim3(grid), dim3(kThreads), sm, s->stream, a); }
+    FCHK(s, mom_launch_ldsm(MOM_LDSM(k_batched_mul_f32), lds, grid, kThreads, sm, s->stream, a));
   }
-  FCHK(s, hipGetLastError());
   return download_f(s, C, dC, cnt);
 }
 
@@ -837,18 +782,10 @@ static int up_vec(momf_scene *s, float *dst, const double *src, size_t n) {
   FCHK(s, hipStreamSynchronize(s->stream));
   return MOM_OK;
 }
-#define OP_LAUNCH(s, KERN, grid, args)                                                            \
-  do {                                                                                            \
-    const bool l__ = (s)->Nu <= 64 && !(s)->force_generic;                                        \
-    const size_t sm__ = lds_bytes((s)->Nu, l__);                                                  \
-    if (l__) {                                                                                    \
-      FCHK(s, allow(KERN<true>, sm__));                                                           \
-      hipLaunchKernelGGL(KERN<true>, dim3(grid), dim3(kThreads), sm__, (s)->stream, args);        \
-    } else {                                                                                      \
-      FCHK(s, allow(KERN<false>, sm__));                                                          \
-      hipLaunchKernelGGL(KERN<false>, dim3(grid), dim3(kThreads), sm__, (s)->stream, args);       \
-    }                                                                                             \
-    FCHK(s, hipGetLastError());                                                                   \
+#define OP_LAUNCH(s, KERN, grid, args)                                                                       \
+  do {                                                                                                       \
+    const bool l__ = (s)->Nu <= 64 && !(s)->force_generic;                                                   \
+    FCHK(s, mom_launch_ldsm(MOM_LDSM(KERN), l__, grid, kThreads, lds_bytes((s)->Nu, l__), (s)->stream, args)); \
   } while (0)
 static int op_grid(const momf_scene *s) {
   return (s->Nu <= 64 && !s->force_generic) ? s->S : (int)std::min<size_t>((size_t)s->S, (size_t)s->G);

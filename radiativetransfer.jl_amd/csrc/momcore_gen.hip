@@ -11,33 +11,11 @@ using namespace MOM_NS;
 
 hipError_t mom_gen_launch_layer(const void *layer_args, int iface, bool lds, int grid, size_t smem, hipStream_t st) {
   const LayerArgs a = *reinterpret_cast<const LayerArgs *>(layer_args);
-  hipError_t e = hipSuccess;
-#define GEN_LAUNCH(IF)                                                                                         \
-  if (lds) {                                                                                                   \
-    if ((e = mom_allow_lds(reinterpret_cast<const void *>(k_layer<true, IF>), smem)) != hipSuccess) return e;  \
-    hipLaunchKernelGGL((k_layer<true, IF>), dim3(grid), dim3(kThreads), smem, st, a);                          \
-  } else {                                                                                                     \
-    if ((e = mom_allow_lds(reinterpret_cast<const void *>(k_layer<false, IF>), smem)) != hipSuccess) return e; \
-    hipLaunchKernelGGL((k_layer<false, IF>), dim3(grid), dim3(kThreads), smem, st, a);                         \
-  }
-  if (a.ntgt > 0) {  // multi-target form: one image per LDS mode, interface code dispatched at run time (IFACE = -1)
-    if (lds) {
-      if ((e = mom_allow_lds(reinterpret_cast<const void *>(k_layer<true, -1, 0, true>), smem)) != hipSuccess) return e;
-      hipLaunchKernelGGL((k_layer<true, -1, 0, true>), dim3(grid), dim3(kThreads), smem, st, a);
-    } else {
-      if ((e = mom_allow_lds(reinterpret_cast<const void *>(k_layer<false, -1, 0, true>), smem)) != hipSuccess) return e;
-      hipLaunchKernelGGL((k_layer<false, -1, 0, true>), dim3(grid), dim3(kThreads), smem, st, a);
-    }
-    return hipGetLastError();
-  }
-  switch (iface) {  // the interface code is a template argument: see interaction_core
-    case 0: GEN_LAUNCH(0) break;
-    case 1: GEN_LAUNCH(1) break;
-    case 2: GEN_LAUNCH(2) break;
-    default: GEN_LAUNCH(3) break;
-  }
+  // multi-target form: one image per LDS mode, interface code dispatched at run time (IFACE = -1)
+  if (a.ntgt > 0) return mom_launch_ldsm(MOM_LDSM(k_layer, -1, 0, true), lds, grid, kThreads, smem, st, a);
+#define GEN_LAUNCH(IF) return mom_launch_ldsm(MOM_LDSM(k_layer, IF), lds, grid, kThreads, smem, st, a)
+  MOM_IFACE_SWITCH(iface, GEN_LAUNCH)
 #undef GEN_LAUNCH
-  return hipGetLastError();
 }
 
 #ifdef MOM_DIAG_STAMPS

@@ -10,6 +10,7 @@
 #include "mom_diag.hpp"
 #include "mom_entry.hpp"
 #include "mom_host.hpp"
+#include "mom_images.hpp"
 // the lean image (three operator buffers, three workgroups per CU): Float64, 4-wave build, N = 36, 40
 #if defined(MOM_WAVES) && MOM_WAVES == 4 && !defined(MOM_REAL_IS_FLOAT) && (MOM_STRIP_KS == 9 || MOM_STRIP_KS == 10)
 #define MOM_HAVE_LEAN 1
@@ -18,45 +19,48 @@
 
 using namespace MOM_NS;
 
-#define MOM_CAT2(a, b) a##b
-#define MOM_CAT(a, b) MOM_CAT2(a, b)
-// entry-point prefix: mom_strip (Float64 builds) or momf_strip (the Float32 build of the same images: -DMOM_REAL=float
-// -DMOM_REAL_IS_FLOAT=1 -DMOM_NS=momf -DMOM_STRIP_PREFIX=momf_strip)
-#ifndef MOM_STRIP_PREFIX
-#define MOM_STRIP_PREFIX mom_strip
+// family of this build in the image table (mom_images.hpp), from its workgroup shape and precision
+#if defined(MOM_REAL_IS_FLOAT)
+#if defined(MOM_WAVES) && MOM_WAVES == 4
+#define MOM_IMAGE_FAMILY F32_STRIP4
+#else
+#define MOM_IMAGE_FAMILY F32_STRIP8
+#endif
+#elif defined(MOM_WAVES) && MOM_WAVES == 4
+#define MOM_IMAGE_FAMILY STRIP4
+#else
+#define MOM_IMAGE_FAMILY STRIP8
 #endif
 
-// host entry used by momcore.hip: mom_strip<KS>_launch_layer(args, iface, grid, smem, stream)
-hipError_t MOM_CAT(MOM_CAT(MOM_STRIP_PREFIX, MOM_STRIP_KS), _launch_layer)(const void *layer_args, int iface, int grid, size_t smem,
-                                                                     hipStream_t st) {
+// LDS bytes of one workgroup of this image: the vector area depends on the workgroup shape of the build, the Float64 builds
+// add the persistent stream-pair tables for ns Stokes components per stream
+static size_t image_lds_bytes(int ns, int, int) { return strip_lds_bytes(4 * MOM_STRIP_KS, ns); }
+static int image_per_cu() { return kWaves == 4 ? 2 : 1; }  // 4-wave builds: two LDS images fit a CU (mom_kernels.hpp ld_for)
+
+static hipError_t image_launch(const void *layer_args, int iface, int grid, hipStream_t st) {
   const LayerArgs a = *reinterpret_cast<const LayerArgs *>(layer_args);
+  const size_t smem = image_lds_bytes(a.q.regular ? a.q.nS : 1, 0, 0);
   hipError_t e = hipSuccess;
 #define STRIP_LAUNCH(IF)                                                                                            \
   if ((e = mom_allow_lds(reinterpret_cast<const void *>(k_layer<true, IF, MOM_STRIP_KS>), smem)) != hipSuccess)     \
     return e;                                                                                                       \
-  hipLaunchKernelGGL((k_layer<true, IF, MOM_STRIP_KS>), dim3(grid), dim3(kThreads), smem, st, a);
+  hipLaunchKernelGGL((k_layer<true, IF, MOM_STRIP_KS>), dim3(grid), dim3(kThreads), smem, st, a)
   if (a.ntgt > 0) {  // multi-target form (interface code dispatched at run time)
     if ((e = mom_allow_lds(reinterpret_cast<const void *>(k_layer<true, -1, MOM_STRIP_KS, true>), smem)) != hipSuccess) return e;
     hipLaunchKernelGGL((k_layer<true, -1, MOM_STRIP_KS, true>), dim3(grid), dim3(kThreads), smem, st, a);
     return hipGetLastError();
   }
-  switch (iface) {
-    case 0: STRIP_LAUNCH(0) break;
-    case 1: STRIP_LAUNCH(1) break;
-    case 2: STRIP_LAUNCH(2) break;
-    default: STRIP_LAUNCH(3) break;
-  }
+  MOM_IFACE_SWITCH(iface, STRIP_LAUNCH)
 #undef STRIP_LAUNCH
   return hipGetLastError();
 }
-
-// LDS bytes of one workgroup of this image (the vector area depends on the workgroup shape of the build)
-size_t MOM_CAT(MOM_CAT(MOM_STRIP_PREFIX, MOM_STRIP_KS), _lds_bytes)() { return lds_bytes(4 * MOM_STRIP_KS, true); }
+MOM_DEFINE_IMAGE(MOM_IMAGE_FAMILY, MOM_STRIP_KS, image_launch, image_lds_bytes, image_per_cu)
 
 #ifdef MOM_HAVE_LEAN
-// mom_strip<KS>_launch_lean(args, grid, stream): the lean sweep kernel; mom_strip<KS>_lean_lds_bytes(ns): its LDS bytes, 0 if the
-// image does not apply to ns Stokes components per stream
-hipError_t MOM_CAT(MOM_CAT(MOM_STRIP_PREFIX, MOM_STRIP_KS), _launch_lean)(const void *layer_args, int grid, hipStream_t st) {
+// the lean sweep kernel of the same build: LDS bytes 0 if it does not apply to ns Stokes components per stream
+static size_t lean_image_lds_bytes(int ns, int, int) { return lean_applies(4 * MOM_STRIP_KS, ns) ? lean_lds_bytes(4 * MOM_STRIP_KS) : 0; }
+static int lean_image_per_cu() { return 3; }
+static hipError_t lean_image_launch(const void *layer_args, int, int grid, hipStream_t st) {
   const LayerArgs a = *reinterpret_cast<const LayerArgs *>(layer_args);
   const size_t smem = lean_lds_bytes(4 * MOM_STRIP_KS);
   hipError_t e = mom_allow_lds(reinterpret_cast<const void *>(k_layer_lean<MOM_STRIP_KS>), smem);
@@ -64,12 +68,16 @@ hipError_t MOM_CAT(MOM_CAT(MOM_STRIP_PREFIX, MOM_STRIP_KS), _launch_lean)(const 
   hipLaunchKernelGGL((k_layer_lean<MOM_STRIP_KS>), dim3(grid), dim3(kThreads), smem, st, a);
   return hipGetLastError();
 }
-size_t MOM_CAT(MOM_CAT(MOM_STRIP_PREFIX, MOM_STRIP_KS), _lean_lds_bytes)(int ns) {
-  return lean_applies(4 * MOM_STRIP_KS, ns) ? lean_lds_bytes(4 * MOM_STRIP_KS) : 0;
-}
+MOM_DEFINE_IMAGE(LEAN, MOM_STRIP_KS, lean_image_launch, lean_image_lds_bytes, lean_image_per_cu)
 #endif
 
 #ifdef MOM_DIAG_STAMPS
+// diagnostic builds (tools/phase_stamps*.py load it by name): mom_strip_diag_read<KS>, or with the prefix of the build's rule
+#define MOM_CAT2(a, b) a##b
+#define MOM_CAT(a, b) MOM_CAT2(a, b)
+#ifndef MOM_STRIP_PREFIX
+#define MOM_STRIP_PREFIX mom_strip
+#endif
 extern "C" int MOM_CAT(MOM_CAT(MOM_STRIP_PREFIX, _diag_read), MOM_STRIP_KS)(unsigned long long *out, int reset) {
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mom_diag_acc), 128 * sizeof(unsigned long long)) != hipSuccess) return 1;
   if (reset) {

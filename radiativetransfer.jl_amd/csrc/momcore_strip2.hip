@@ -8,15 +8,14 @@
 
 #include "mom_diag.hpp"
 #include "mom_host.hpp"
+#include "mom_images.hpp"
 #include "mom_strip2.hpp"
 
 using namespace MOM_NS;
 
-#define MOM_CAT2(a, b) a##b
-#define MOM_CAT(a, b) MOM_CAT2(a, b)
+static_assert(kMomStrip2SchedInts == (size_t)kS2SchedInts, "mom_images.hpp: size of LayerArgs::sched");
 
-// mom2_strip<KS>_launch(args, grid, stream): the sweep kernel; mom2_strip<KS>_lds_bytes(ns, nS): its LDS bytes, 0 if the image
-// does not apply to ns Stokes components per stream (nS per stream entry of the scene)
+// the sweep kernel, one per scheduling mode (mom_strip2.hpp)
 template <int MODE>
 static hipError_t launch_s2(const LayerArgs &a, int grid, hipStream_t st) {
   const size_t smem = s2_lds_bytes(4 * MOM_STRIP_KS);
@@ -25,19 +24,24 @@ static hipError_t launch_s2(const LayerArgs &a, int grid, hipStream_t st) {
   hipLaunchKernelGGL((k_layer_s2<MOM_STRIP_KS, MODE>), dim3(grid), dim3(kThreads), smem, st, a);
   return hipGetLastError();
 }
-hipError_t MOM_CAT(MOM_CAT(mom2_strip, MOM_STRIP_KS), _launch)(const void *layer_args, int grid, hipStream_t st) {
+static hipError_t image_launch(const void *layer_args, int, int grid, hipStream_t st) {
   const LayerArgs a = *reinterpret_cast<const LayerArgs *>(layer_args);
-  switch (a.sched_mode & 3) {  // one kernel per scheduling mode (mom_strip2.hpp)
+  switch (a.sched_mode & 3) {
     case 1: return launch_s2<1>(a, grid, st);
     case 2: return launch_s2<2>(a, grid, st);
     case 3: return launch_s2<3>(a, grid, st);
     default: return launch_s2<0>(a, grid, st);
   }
 }
-// ints of LayerArgs::sched (the unit queue's counter + the arrival tickets per CU), zeroed on the stream before every launch
-size_t MOM_CAT(MOM_CAT(mom2_strip, MOM_STRIP_KS), _sched_ints)() { return kS2SchedInts; }
+// LDS bytes, 0 if the image does not apply to ns Stokes components per stream (nS per stream entry of the scene)
+static size_t image_lds_bytes(int ns, int nS, int) { return s2_applies(4 * MOM_STRIP_KS, ns, nS) ? s2_lds_bytes(4 * MOM_STRIP_KS) : 0; }
+static int image_per_cu() { return 2; }
+MOM_DEFINE_IMAGE(STRIP2, MOM_STRIP_KS, image_launch, image_lds_bytes, image_per_cu)
+
 #ifdef MOM_DIAG_TIMELINE
 // diagnostic builds (tools/phase_stamps_s2.py): the timelines of the last launch; ev[kTlWgs * kTlCap], hdr[4 * kTlWgs]
+#define MOM_CAT2(a, b) a##b
+#define MOM_CAT(a, b) MOM_CAT2(a, b)
 extern "C" int MOM_CAT(MOM_CAT(mom2_strip, MOM_STRIP_KS), _timeline_read)(unsigned long long *ev, unsigned *hdr, int *wgs, int *cap) {
   *wgs = kTlWgs; *cap = kTlCap;
   if (!ev) return 0;
@@ -46,6 +50,3 @@ extern "C" int MOM_CAT(MOM_CAT(mom2_strip, MOM_STRIP_KS), _timeline_read)(unsign
   return 0;
 }
 #endif
-size_t MOM_CAT(MOM_CAT(mom2_strip, MOM_STRIP_KS), _lds_bytes)(int ns, int nS) {
-  return s2_applies(4 * MOM_STRIP_KS, ns, nS) ? s2_lds_bytes(4 * MOM_STRIP_KS) : 0;
-}
