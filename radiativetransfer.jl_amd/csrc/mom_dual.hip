@@ -1138,13 +1138,7 @@ int momd_run(const MomDualScene &sc, std::string *err) {
   const size_t per_unit = momd_bytes_per_unit(N, P);
   size_t Uc = std::min<size_t>(std::min<size_t>((size_t)sc.S, 65535), std::max<size_t>(1, sc.work_budget / per_unit));  // grid.y <= 65535
   const size_t need = Uc * per_unit + 256;
-  if (*sc.work_cap < need) {
-    if (*sc.work) DCHK(hipFree(*sc.work));
-    *sc.work = nullptr;
-    *sc.work_cap = 0;
-    DCHK(hipMalloc(sc.work, need));
-    *sc.work_cap = need;
-  }
+  if (sc.work->capacity() < need) DCHK(sc.work->renew(need));
   double *dts = nullptr;  // d tau_sum [S, Nz+1, P]
   if (P > 0 && sc.dtau) {
     dts = sc.dtau_sum_buf;
@@ -1159,7 +1153,7 @@ int momd_run(const MomDualScene &sc, std::string *err) {
   for (size_t u0 = 0; u0 < (size_t)sc.S; u0 += Uc) {
     const int U = (int)std::min<size_t>(Uc, (size_t)sc.S - u0);
     const size_t MS = (size_t)(P + 1) * U * NN, VS = (size_t)(P + 1) * U * N;
-    double *base = (double *)*sc.work;
+    double *base = reinterpret_cast<double *>(sc.work->get());
     auto mat = [&]() { double *p = base; base += MS; return p; };
     auto vec = [&]() { double *p = base; base += VS; return p; };
     Layer ad{mat(), mat(), mat(), mat(), vec(), vec()};

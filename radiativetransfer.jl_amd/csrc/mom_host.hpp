@@ -2,9 +2,95 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <map>
 #include <string>
 #include <utility>
+#include <vector>
+
+// The one owner of a device allocation of the handles (mom_handle, momf_scene): pointer + capacity in elements of T, freed by
+// the destructor.  A member that is not a MomDevBuf (an alias into one, a pointer borrowed from another handle) is never freed.
+// After a failed call the buffer is empty, so an error return between two allocations leaves each buffer valid or empty.
+template <class T>
+class MomDevBuf {
+ public:
+  MomDevBuf() = default;
+  MomDevBuf(const MomDevBuf &) = delete;
+  MomDevBuf &operator=(const MomDevBuf &) = delete;
+  MomDevBuf(MomDevBuf &&o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+  MomDevBuf &operator=(MomDevBuf &&o) noexcept {
+    if (this != &o) { reset(); p_ = o.p_; cap_ = o.cap_; o.p_ = nullptr; o.cap_ = 0; }
+    return *this;
+  }
+  ~MomDevBuf() { reset(); }
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr;
+    cap_ = 0;
+  }
+  // exactly max(count, 1) elements, fresh: what is held is freed first (the caller knows no work in flight uses it)
+  hipError_t renew(size_t count) {
+    reset();
+    count = std::max<size_t>(count, 1);
+    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p_), count * sizeof(T));
+    if (e == hipSuccess) cap_ = count;
+    else p_ = nullptr;
+    return e;
+  }
+  // grow-only, at least `count` elements: no call into the runtime in steady state; before a buffer that is too small is
+  // freed, the stream it was last used on (`st`) is drained
+  hipError_t reserve(size_t count, hipStream_t st) {
+    if (count <= cap_) return hipSuccess;
+    const hipError_t e = p_ ? hipStreamSynchronize(st) : hipSuccess;
+    reset();
+    return e != hipSuccess ? e : renew(count);
+  }
+  T *get() const { return p_; }
+  operator T *() const { return p_; }
+  size_t capacity() const { return cap_; }
+
+ private:
+  T *p_ = nullptr;
+  size_t cap_ = 0;
+};
+
+// host array -> a buffer of exactly `count` elements; the copy is asynchronous on `st` (src must outlive it)
+template <class T>
+inline hipError_t mom_upload(MomDevBuf<T> &dst, const T *src, size_t count, hipStream_t st) {
+  const hipError_t e = dst.renew(count);
+  return e != hipSuccess ? e : hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, st);
+}
+// the same through a staging vector of T (double -> float, int -> int); `st` is drained before the vector dies
+template <class T, class U>
+inline hipError_t mom_upload_as(MomDevBuf<T> &dst, const U *src, size_t count, hipStream_t st) {
+  std::vector<T> v(count);
+  for (size_t i = 0; i < count; ++i) v[i] = (T)src[i];
+  const hipError_t e = mom_upload(dst, v.data(), count, st), e2 = hipStreamSynchronize(st);
+  return e != hipSuccess ? e : e2;
+}
+
+// Scene-level path: an operator edge N for which no strip-chained kernel image exists is padded with up to 4 DUMMY
+// STREAM ENTRIES (mu = 1, weight 0, zero rows and columns in every phase-matrix basis and BRDF matrix) when that
+// reaches a size one exists for: most IQU stream counts (N = 3 k is a multiple of 4 only for every fourth k), and
+// N = 32, 48 (measured: N = 48 as 52 runs 1.3x faster than the general path at 48).  A dummy entry is decoupled exactly:
+// its column is zero in r and off-diagonal in t (zero weight, elemental.jl:198-205), its row is zero because its Z row
+// is, so every product, series and pivoted inverse leaves the real rows and columns with the same terms plus exact zeros.
+// `strip_size`: the edges that have a strip-chained finisher in the driver's precision (the image table, mom_images.hpp)
+constexpr int kMomPadMax = 4;
+inline int mom_strip_pad(bool (*strip_size)(int), int N) {
+  if (strip_size(N)) return N;
+  for (int p = N + 1; p <= N + kMomPadMax; ++p)
+    if (strip_size(p)) return p;
+  return N;
+}
+// [N,N,B] -> [Nk,Nk,B], zero padded
+inline std::vector<double> mom_pad_blocks(const double *src, int N, int Nk, size_t B) {
+  std::vector<double> out((size_t)Nk * Nk * B, 0.0);
+  for (size_t b = 0; b < B; ++b)
+    for (int j = 0; j < N; ++j)
+      for (int i = 0; i < N; ++i) out[i + (size_t)Nk * (j + (size_t)Nk * b)] = src[i + (size_t)N * (j + (size_t)N * b)];
+  return out;
+}
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is set once per (device, kernel image) and raised only when a
 // larger LDS image is requested -- not on every launch.
@@ -86,8 +172,7 @@ struct MomDualScene {
   double *dtau_sum_buf;                                    // [S,Nz+1,P] scratch
   int *info;
   hipStream_t stream;
-  void **work;                                             // workspace owned by the handle (grown on demand)
-  size_t *work_cap;
+  MomDevBuf<char> *work;                                   // workspace owned by the handle (grown on demand)
   size_t work_budget;                                      // bytes the operator workspace may take (units are chunked to fit)
 };
 size_t momd_bytes_per_unit(int N, int P);

@@ -342,42 +342,35 @@ struct mom_handle {
   bool lds_mode = true;
   int opt_inverse = 0, opt_force_generic = 0;
   hipStream_t stream = nullptr;
-  double *d_mu = nullptr, *d_wt = nullptr, *d_sg = nullptr;
+  MomDevBuf<double> d_mu, d_wt, d_sg;
   DevStreams q{};
   bool streams_set = false;
   std::vector<double> h_mu, h_wt;
   int strict = 1;
-  double *added[6] = {}, *surf[6] = {}, *comp[6] = {};
+  MomDevBuf<double> added[6], surf[6], comp[6];
   bool op_layers = false;     // added / surface layers of the operator-level API: allocated on first use
   bool comp_pitched = false;  // composite matrix blocks hold scene-level (row-pitched) state
   bool comp_on_chip = false;  // the last mom_rt_run kept the composite layer in registers (lane / wave kernels)
-  double *d_post[2] = {};     // operator-level mom_postprocess: gathered J0-/J0+ rows [nVza*nS*S] x 2
-  size_t post_cap = 0;
+  MomDevBuf<double> d_post;   // operator-level mom_postprocess: gathered J0- | J0+ rows [2][nVza*nS*S]
   // RCCL communicator (mom_comm_init); the library is dlopen'ed on first use
   void *comm = nullptr;
   int comm_rank = 0, comm_size = 1;
-  double *d_gather = nullptr;
-  size_t gather_cap = 0;
-  double *d_rrs_send = nullptr;  // packed owned spectra of the RRS run: send buffer of mom_allgather_rrs_device
-  size_t rrs_send_cap = 0;
+  MomDevBuf<double> d_gather;
+  MomDevBuf<double> d_rrs_send;  // packed owned spectra of the RRS run: send buffer of mom_allgather_rrs_device
   // device-side layer optics (mom_absorption_* / mom_voigt_tau_abs / mom_scene_set_optics)
-  double *d_tau_abs = nullptr, *d_grid = nullptr, *d_lines = nullptr, *d_tau_rayl = nullptr, *d_layer_max = nullptr,
-         *d_aer = nullptr;
-  int *d_aer_mode = nullptr;
+  MomDevBuf<double> d_tau_abs, d_grid, d_lines, d_tau_rayl, d_layer_max, d_aer;
+  MomDevBuf<int> d_aer_mode;
   int abs_Nz = 0;
-  size_t lines_cap = 0;   // line capacity of ONE layer's block of d_lines
-  int lines_nz = 1;       // layers held in d_lines: arrays [nu | gamma_d | y | S][lines_nz][lines_cap], then the two window arrays as ints
-  double *d_prof = nullptr;  // per-layer scalars of mom_voigt_tau_abs_profile
-  size_t prof_cap = 0;
-  double *d_vec[4] = {};  // S-length temporaries (tau_sum, dtau, varpi, expk)
-  double *d_Zop[2] = {};
-  size_t Zop_cap = 0;
+  size_t lines_per = 0;   // lines ONE layer's block of d_lines has room for (the stride of its arrays, not the size of the allocation)
+  int lines_nz = 1;       // layers held in d_lines: arrays [nu | gamma_d | y | S][lines_nz][lines_per], then the two window arrays as ints
+  MomDevBuf<double> d_prof;  // per-layer scalars of mom_voigt_tau_abs_profile
+  MomDevBuf<double> d_vec[4];  // S-length temporaries (tau_sum, dtau, varpi, expk)
+  MomDevBuf<double> d_Zop[2];
   // scene
   int Nz = 0, K = 0, nVza = 0, scene_M = 0;
-  double *d_tau = nullptr, *d_varpi = nullptr, *d_zw = nullptr, *d_Zpp = nullptr, *d_Zmp = nullptr,
-         *d_tau_sum = nullptr, *d_cos = nullptr, *d_sin = nullptr, *d_R = nullptr, *d_T = nullptr, *d_hdr = nullptr,
-         *d_hdrJ = nullptr, *d_bhr_uw = nullptr, *d_bhr_dw = nullptr;
-  int *d_node = nullptr;
+  MomDevBuf<double> d_tau, d_varpi, d_zw, d_Zpp, d_Zmp, d_tau_sum, d_cos, d_sin, d_R, d_hdr, d_hdrJ, d_bhr_uw, d_bhr_dw;
+  double *d_T = nullptr;  // d_R + nVza nS S: R_SFI || T_SFI are ONE buffer (the all-gather's send buffer as it stands)
+  MomDevBuf<int> d_node;
   std::vector<int> nd, iface;
   double albedo = 0.0;
   bool scene_set = false;
@@ -393,71 +386,61 @@ struct mom_handle {
   // ForwardDiff.Dual run (mom_dual.hip): partials of the scene's inputs and of the outputs, the operator workspace
   int dual_P = 0;
   bool dual_ran = false;
-  bool dual_last = false;   // the last run of the resident scene was mom_rt_run_dual: hdr / bhr hold nothing of it
-  double *d_dual_in[8] = {};  // dtau, dvarpi, dzw, dZpp, dZmp, dalbedo, dRsurf, dalbedo_spec
-  double *d_dual_out = nullptr, *d_dual_ts = nullptr;  // dR | dT [nVza,nS,S,P] x 2; d tau_sum [S,Nz+1,P]
-  void *dual_work = nullptr;
-  size_t dual_work_cap = 0;
+  MomDevBuf<double> d_dual_in[8];  // dtau, dvarpi, dzw, dZpp, dZmp, dalbedo, dRsurf, dalbedo_spec
+  MomDevBuf<double> d_dual_out, d_dual_ts;  // dR | dT [nVza,nS,S,P] x 2; d tau_sum [S,Nz+1,P]
+  MomDevBuf<char> dual_work;
   size_t opt_dual_budget = 0;  // MOM_OPT_DUAL_WORKSPACE_MB (0: 60 % of the free HBM at the time of the run)
-  double *d_Rsurf = nullptr, *d_Rsurf0 = nullptr, *d_albedo_spec = nullptr, *d_hdrJm = nullptr;
+  MomDevBuf<double> d_Rsurf, d_Rsurf0, d_albedo_spec, d_hdrJm;
   int opt_sweep = 1;       // one launch walks all layers of a unit (LayerArgs::Nz_sweep)
-  double *comp_top[6] = {};  // mom_rt_run_multisensor: composite state of the slab above a sensor
-  double *d_msJ[2] = {};     // interface fields dwJ, uwJ [Nk,S,M]
-  std::vector<double *> ms_comp;  // multi-sensor: 6 arrays per composite set (snapshot of the top slab + bottom slab per sensor)
-  size_t ms_sets = 0;
-  double *d_ms_out = nullptr;  // [2][nVza*nS*S*nSensors]
-  size_t ms_out_cap = 0;
+  MomDevBuf<double> comp_top[6];  // mom_rt_run_multisensor: composite state of the slab above a sensor
+  MomDevBuf<double> d_msJ[2];     // interface fields dwJ, uwJ [Nk,S,M]
+  std::vector<MomDevBuf<double>> ms_comp;  // multi-sensor: 6 arrays per composite set (snapshot of the top slab + bottom slab per sensor)
+  MomDevBuf<double> d_ms_out;  // [2][nVza*nS*S*nSensors]
   int opt_pad = 1;         // scene-level path: pad the operator edge to the next strip-chained kernel size (strip_pad)
   int opt_lean = 3;        // N = 36, 40: 3 = the quad-block image (one wavefront per unit, 4 x 4 x 4 MFMA blocks, four units per CU;
                            // mom_q4.hpp), 1 = the four-wave lean strip image (three workgroups per CU), 2 = the six-wave one (half-strip
                            // doubling chains, two per CU: measured slower, profiles/r05_mid_ab.txt), each followed by the full image's
                            // resume launch; 0 = the full image only
-  int *d_resume = nullptr; // resume[unit] of the lean image (mom_lean.hpp)
-  size_t resume_cap = 0;
+  MomDevBuf<int> d_resume; // resume[unit] of the lean image (mom_lean.hpp)
   int opt_strip2 = 1;       // MOM_OPT_STRIP2: N = 52, 56, 60 on the two-buffer 4-wave image first (mom_strip2.hpp), the 8-wave image resumes
-  int *d_resume2 = nullptr; // its resume[unit] (a table of its own: the m = 0 sub-problem's lean launch may run at the same time)
-  size_t resume2_cap = 0;
+  MomDevBuf<int> d_resume2; // its resume[unit] (a table of its own: the m = 0 sub-problem's lean launch may run at the same time)
   size_t resume2_units = 0;  // units and layers of the image's last launch (mom_strip2_resumed)
   int resume2_nz = 0;
   int opt_strip2_sched = 1;  // MOM_OPT_STRIP2_SCHED: bit 0 = shared unit queue, bit 1 = asymmetric chain priority (mom_strip2.hpp; one
                              // kernel per value); the priority measured slower on top of the queue (profiles/r08_C2_ab.txt): off
-  int *d_sched2 = nullptr;   // LayerArgs::sched of the two-buffer image: zeroed on the stream before each of its launches
+  MomDevBuf<int> d_sched2;   // LayerArgs::sched of the two-buffer image: zeroed on the stream before each of its launches
   int Nk = 0;              // operator edge the scene-level kernels of the full problem run with (>= N)
   DevStreams qk{};         // q with N = Nk
   int opt_small = 1;       // N <= 4: lane-per-point sweep kernel (mom_small.hip)
-  double *d_smtab = nullptr;  // F1 | F2 | SI tables [3][N,N]
-  double *d_smpart = nullptr; // N <= 4, one (point, moment) per lane: the per-moment terms of R_SFI / T_SFI [M][2][nVza,nS,S]
-  size_t smpart_cap = 0;
-  int *d_ndif = nullptr;      // ndoubl | iface [2][Nz]
-  size_t ndif_cap = 0;
+  MomDevBuf<double> d_smtab;  // F1 | F2 | SI tables [3][N,N]
+  MomDevBuf<double> d_smpart; // N <= 4, one (point, moment) per lane: the per-moment terms of R_SFI / T_SFI [M][2][nVza,nS,S]
+  MomDevBuf<int> d_ndif;      // ndoubl | iface [2][Nz]
   bool red0 = false;
   int N0 = 0, nS0 = 0;
   DevStreams q0{};
-  double *d_mu0 = nullptr, *d_wt0 = nullptr, *d_sg0 = nullptr, *d_Zpp0 = nullptr, *d_Zmp0 = nullptr, *d_hdrJ0 = nullptr,
-         *d_scratch0 = nullptr;
-  double *comp0[6] = {};
-  double *d_scratch = nullptr;
+  MomDevBuf<double> d_mu0, d_wt0, d_sg0, d_Zpp0, d_Zmp0, d_hdrJ0, d_scratch0;
+  MomDevBuf<double> comp0[6];
+  MomDevBuf<double> d_scratch;
   int G = 0;  // workgroups in generic mode
   int num_cu = 256;
-  int *d_info = nullptr;
+  MomDevBuf<int> d_info;
   hipEvent_t ev[4] = {};
   hipEvent_t ev_voigt[2] = {};  // mom_voigt_tau_abs_profile's timing pair (created on first use, owned by the handle)
   std::vector<hipEvent_t> ev_full, ev_red;  // start/stop pairs around each full-problem / reduced layer launch
   int launches = 0, launches_full = 0, launches_red = 0;
   // rotational-Raman path (mom_rrs.hip): the persistent AddedLayerRS / CompositeLayerRS state and the scene's Raman inputs
   momr::State *rrs = nullptr;
-  double *d_fscatt = nullptr, *d_Zr[2] = {};  // fScattRayleigh [S,Nz]; Raman phase matrices [N,N,M] x2
-  double *d_rrs_op[8] = {};                   // operator-level inputs: tau_sum, dtau, varpi, fscatt [S]; Z x4 [N,N]
+  MomDevBuf<double> d_fscatt, d_Zr[2];  // fScattRayleigh [S,Nz]; Raman phase matrices [N,N,M] x2
+  MomDevBuf<double> d_rrs_op[8];        // operator-level inputs: tau_sum, dtau, varpi, fscatt [S]; Z x4 [N,N]
   bool rrs_scene = false;
   double rrs_ms = 0.0;
-  // grow-only device workspace of the operator-level batched entry points (no hipMalloc / hipFree per call, no leak on an
-  // error return): slot k holds ws_cap[k] bytes
-  char *ws[4] = {};
-  size_t ws_cap[4] = {};
+  // grow-only device workspace of the operator-level batched entry points (no allocation per call, no leak on an error
+  // return): bytes, viewed as the element type each call needs
+  MomDevBuf<char> ws[4];
   // resident HITRAN table + TIPS splines of one absorber (mom_absorption_set_lines)
   MomLineTable lt{};
-  double *d_lt = nullptr;   // one allocation behind lt's double arrays
-  int *d_lt_i = nullptr;    // iso index [nLines] | knots per isotopologue [nIso] | unsorted flag [1]
+  MomDevBuf<double> d_lt;   // one allocation behind lt's double arrays
+  MomDevBuf<int> d_lt_i;    // iso index [nLines] | knots per isotopologue [nIso] | unsorted flag [1]
   double lt_Tmin = 0.0, lt_Tmax = 0.0;
   std::string err;
 };
@@ -485,61 +468,11 @@ static int fail(mom_t *h, int code, const char *msg) {
   return code;
 }
 
-template <class T>
-static hipError_t dmalloc(T **p, size_t count) {
-  return hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T));
-}
-
-// grow-only device buffer: at least `count` elements behind *p, whose capacity *cap counts elements.  No allocation in steady
-// state; before a buffer that is too small is freed, the stream it was last used on (`st`) is drained
-template <class T>
-static hipError_t grow(T **p, size_t *cap, size_t count, hipStream_t st) {
-  if (count <= *cap) return hipSuccess;
-  if (*p) {
-    const hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return e;
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-  }
-  const hipError_t e = dmalloc(p, count);
-  if (e == hipSuccess) *cap = count;
-  return e;
-}
-
-// slot of the handle's grow-only workspace, at least `count` elements of T
-template <class T>
-static hipError_t ws_get(mom_t *h, int slot, T **p, size_t count) {
-  const hipError_t e = grow(&h->ws[slot], &h->ws_cap[slot], count * sizeof(T), h->stream);
-  *p = reinterpret_cast<T *>(h->ws[slot]);
-  return e;
-}
-
 static size_t smem_bytes(const mom_t *h) { return lds_bytes(h->N, h->lds_mode); }
 
-// Scene-level path: an operator edge N for which no strip-chained kernel image exists is padded with up to 4 DUMMY
-// STREAM ENTRIES (mu = 1, weight 0, zero rows and columns in every phase-matrix basis and BRDF matrix) when that
-// reaches a size one exists for: most IQU stream counts (N = 3 k is a multiple of 4 only for every fourth k), and
-// N = 32, 48 (measured: N = 48 as 52 runs 1.3x faster than the general path at 48).  A dummy entry is decoupled exactly:
-// its column is zero in r and off-diagonal in t (zero weight, elemental.jl:198-205), its row is zero because its Z row
-// is, so every product, series and pivoted inverse leaves the real rows and columns with the same terms plus exact zeros.
-constexpr int kPadMax = 4;
-// (the edges that have a strip-chained finisher, of the 4-wave or the 8-wave build: the image table, mom_images.hpp)
+// the edges that have a strip-chained finisher, of the 4-wave or the 8-wave build (the pad rule: mom_host.hpp)
 static bool strip_size(int N) { return mom_find_image(MOM_IMG_STRIP4, N) || mom_find_image(MOM_IMG_STRIP8, N); }
-static int strip_pad(int N) {
-  if (strip_size(N)) return N;
-  for (int p = N + 1; p <= N + kPadMax; ++p)
-    if (strip_size(p)) return p;
-  return N;
-}
-// [N,N,B] -> [Nk,Nk,B], zero padded
-static std::vector<double> pad_blocks(const double *src, int N, int Nk, size_t B) {
-  std::vector<double> out((size_t)Nk * Nk * B, 0.0);
-  for (size_t b = 0; b < B; ++b)
-    for (int j = 0; j < N; ++j)
-      for (int i = 0; i < N; ++i) out[i + (size_t)Nk * (j + (size_t)Nk * b)] = src[i + (size_t)N * (j + (size_t)N * b)];
-  return out;
-}
+static int strip_pad(int N) { return mom_strip_pad(strip_size, N); }
 
 void mom_set_global_error(const char *msg) { g_err = msg ? msg : ""; }
 extern "C" const char *mom_last_global_error(void) { return g_err.c_str(); }
@@ -551,8 +484,8 @@ static int ensure_op_layers(mom_t *h) {
   const size_t NN = (size_t)h->N * h->N;
   for (int k = 0; k < 6; ++k) {
     const size_t per = ((k < 4) ? NN : (size_t)h->N) * h->S;
-    HIPCHK(h, dmalloc(&h->added[k], per));
-    HIPCHK(h, dmalloc(&h->surf[k], per));
+    HIPCHK(h, h->added[k].renew(per));
+    HIPCHK(h, h->surf[k].renew(per));
     HIPCHK(h, hipMemsetAsync(h->added[k], 0, per * sizeof(double), h->stream));
     HIPCHK(h, hipMemsetAsync(h->surf[k], 0, per * sizeof(double), h->stream));
   }
@@ -594,21 +527,21 @@ extern "C" int mom_create(mom_t **out, int device, int N, int nStokes, int S, in
     HIPCHK(h, hipEventCreateWithFlags(&h->ev_go, hipEventDisableTiming));
   }
   const size_t NN = (size_t)N * N;
-  const int Na = N + kPadMax;  // room for the dummy entries of strip_pad
-  HIPCHK(h, dmalloc(&h->d_mu, Na));
-  HIPCHK(h, dmalloc(&h->d_wt, Na));
-  HIPCHK(h, dmalloc(&h->d_sg, Na));
+  const int Na = N + kMomPadMax;  // room for the dummy entries of strip_pad
+  HIPCHK(h, h->d_mu.renew(Na));
+  HIPCHK(h, h->d_wt.renew(Na));
+  HIPCHK(h, h->d_sg.renew(Na));
   (void)NN;
   for (int k = 0; k < 6 && dtype == 0; ++k) {
     // composite blocks: room for the scene-level row pitch (comp_pitch); the operator-level API uses the natural one.
     // The added / surface layers of the operator-level API (12 N^2 S doubles) are allocated on its first use
     // (ensure_op_layers): the scene-level path keeps the added layer in LDS and never needs them.
     const size_t perc = (k < 4) ? (size_t)comp_pitch(Na) * Na : (size_t)Na;
-    HIPCHK(h, dmalloc(&h->comp[k], perc * S * max_m));
+    HIPCHK(h, h->comp[k].renew(perc * S * max_m));
     HIPCHK(h, hipMemsetAsync(h->comp[k], 0, perc * S * max_m * sizeof(double), h->stream));
   }
-  for (int k = 0; k < 4; ++k) HIPCHK(h, dmalloc(&h->d_vec[k], S));
-  HIPCHK(h, dmalloc(&h->d_info, 1));
+  for (int k = 0; k < 4; ++k) HIPCHK(h, h->d_vec[k].renew(S));
+  HIPCHK(h, h->d_info.renew(1));
   HIPCHK(h, hipMemsetAsync(h->d_info, 0, sizeof(int), h->stream));
   h->G = 1024;
   {
@@ -624,7 +557,7 @@ extern "C" int mom_create(mom_t **out, int device, int N, int nStokes, int S, in
     return MOM_OK;
   }
   // + one padded matrix of slack: B-operand reads of the last column tile run past the stored columns
-  HIPCHK(h, dmalloc(&h->d_scratch, (size_t)h->G * kGenericBufs * mat_elems(N) + (size_t)ld_for(N) * np_for(N)));
+  HIPCHK(h, h->d_scratch.renew((size_t)h->G * kGenericBufs * mat_elems(N) + (size_t)ld_for(N) * np_for(N)));
   HIPCHK(h, hipMemsetAsync(h->d_scratch, 0, ((size_t)h->G * kGenericBufs * mat_elems(N) + (size_t)ld_for(N) * np_for(N)) * sizeof(double), h->stream));
   for (int k = 0; k < 4; ++k) HIPCHK(h, hipEventCreate(&h->ev[k]));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -637,25 +570,7 @@ extern "C" int mom_destroy(mom_t *h) {
   (void)hipStreamSynchronize(h->stream);
   if (h->f32) momf_destroy(h->f32);
   momr::destroy(h->rrs);
-  (void)hipFree(h->d_lt); (void)hipFree(h->d_lt_i);
-  for (int k = 0; k < 4; ++k) (void)hipFree(h->ws[k]);
-  (void)hipFree(h->d_fscatt); (void)hipFree(h->d_Zr[0]); (void)hipFree(h->d_Zr[1]);
-  for (int k = 0; k < 8; ++k) (void)hipFree(h->d_rrs_op[k]);
   if (h->comm && g_rccl_destroy) g_rccl_destroy(h->comm);
-  auto fr = [](void *p) { if (p) (void)hipFree(p); };
-  fr(h->d_mu); fr(h->d_wt); fr(h->d_sg);
-  for (int k = 0; k < 8; ++k) fr(h->d_dual_in[k]);
-  fr(h->d_dual_out); fr(h->d_dual_ts); fr(h->dual_work);
-  for (int k = 0; k < 6; ++k) { fr(h->added[k]); fr(h->surf[k]); fr(h->comp[k]); fr(h->comp_top[k]); }
-  fr(h->d_msJ[0]); fr(h->d_msJ[1]); fr(h->d_ms_out);
-  for (auto p : h->ms_comp) fr(p);
-  for (int k = 0; k < 4; ++k) fr(h->d_vec[k]);
-  fr(h->d_Zop[0]); fr(h->d_Zop[1]);
-  fr(h->d_tau); fr(h->d_varpi); fr(h->d_zw); fr(h->d_Zpp); fr(h->d_Zmp); fr(h->d_tau_sum); fr(h->d_cos); fr(h->d_sin);
-  fr(h->d_mu0); fr(h->d_wt0); fr(h->d_sg0); fr(h->d_Zpp0); fr(h->d_Zmp0); fr(h->d_hdrJ0); fr(h->d_scratch0);
-  for (int k = 0; k < 6; ++k) fr(h->comp0[k]);
-  fr(h->d_R); fr(h->d_hdr); fr(h->d_post[0]); fr(h->d_gather); fr(h->d_rrs_send); fr(h->d_Rsurf); fr(h->d_Rsurf0); fr(h->d_albedo_spec); fr(h->d_hdrJm); fr(h->d_smtab); fr(h->d_smpart); if (h->d_resume) (void)hipFree(h->d_resume); if (h->d_resume2) (void)hipFree(h->d_resume2); if (h->d_sched2) (void)hipFree(h->d_sched2); if (h->d_ndif) (void)hipFree(h->d_ndif); fr(h->d_tau_abs); fr(h->d_grid); fr(h->d_lines); fr(h->d_prof); fr(h->d_tau_rayl);
-  fr(h->d_layer_max); fr(h->d_aer); if (h->d_aer_mode) (void)hipFree(h->d_aer_mode); fr(h->d_hdrJ); fr(h->d_bhr_uw); fr(h->d_bhr_dw); fr(h->d_node); fr(h->d_scratch); fr(h->d_info);
   for (int k = 0; k < 4; ++k) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
   for (int k = 0; k < 2; ++k) if (h->ev_voigt[k]) (void)hipEventDestroy(h->ev_voigt[k]);
   for (auto e : h->ev_full) (void)hipEventDestroy(e);
@@ -665,7 +580,7 @@ extern "C" int mom_destroy(mom_t *h) {
   if (h->ev_go) (void)hipEventDestroy(h->ev_go);
   if (h->stream2) (void)hipStreamDestroy(h->stream2);
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;  // frees every device buffer of the handle (MomDevBuf members)
   return MOM_OK;
 }
 
@@ -744,7 +659,7 @@ extern "C" int mom_set_streams(mom_t *h, const double *qp_muN, const double *wt_
   }
   {
     std::vector<double> mu(qp_muN, qp_muN + N), wt(wt_muN, wt_muN + N);
-    mu.resize(N + kPadMax, 1.0); wt.resize(N + kPadMax, 0.0); sg.resize(N + kPadMax, 1.0);  // dummy entries (strip_pad)
+    mu.resize(N + kMomPadMax, 1.0); wt.resize(N + kMomPadMax, 0.0); sg.resize(N + kMomPadMax, 1.0);  // dummy entries (strip_pad)
     HIPCHK(h, hipMemcpyAsync(h->d_mu, mu.data(), mu.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_wt, wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_sg, sg.data(), sg.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -803,12 +718,7 @@ extern "C" int mom_elemental(mom_t *h, int m, int ndoubl, const double *tau_sum,
   HIPCHK(h, hipSetDevice(h->device));
   { const int rc_ = ensure_op_layers(h); if (rc_) return rc_; }
   const size_t NN = (size_t)h->N * h->N, zc = NN * z_batch;
-  if (zc > h->Zop_cap) {
-    if (h->d_Zop[0]) { (void)hipFree(h->d_Zop[0]); (void)hipFree(h->d_Zop[1]); }
-    HIPCHK(h, dmalloc(&h->d_Zop[0], zc));
-    HIPCHK(h, dmalloc(&h->d_Zop[1], zc));
-    h->Zop_cap = zc;
-  }
+  for (int k = 0; k < 2; ++k) HIPCHK(h, h->d_Zop[k].reserve(zc, h->stream));
   const size_t sb = (size_t)h->S * sizeof(double);
   HIPCHK(h, hipMemcpyAsync(h->d_vec[0], tau_sum, sb, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->d_vec[1], dtau, sb, hipMemcpyHostToDevice, h->stream));
@@ -973,18 +883,22 @@ static int blas_common(mom_t *h, int n, int batch, const double *A, const double
   }
   const size_t cnt = (size_t)n * n * batch;
   double *dA = nullptr, *dB = nullptr, *dC = nullptr, *scr = nullptr;
-  HIPCHK(h, ws_get(h, 0, &dA, cnt));
-  HIPCHK(h, ws_get(h, 1, &dC, cnt));
+  HIPCHK(h, h->ws[0].reserve(cnt * sizeof(double), h->stream));
+  dA = reinterpret_cast<double *>(h->ws[0].get());
+  HIPCHK(h, h->ws[1].reserve(cnt * sizeof(double), h->stream));
+  dC = reinterpret_cast<double *>(h->ws[1].get());
   HIPCHK(h, hipMemcpyAsync(dA, A, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
   if (!inv) {
-    HIPCHK(h, ws_get(h, 2, &dB, cnt));
+    HIPCHK(h, h->ws[2].reserve(cnt * sizeof(double), h->stream));
+    dB = reinterpret_cast<double *>(h->ws[2].get());
     HIPCHK(h, hipMemcpyAsync(dB, B, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
   }
   const bool lds = n <= 64 && !h->opt_force_generic;
   const int grid = lds ? batch : std::min(batch, 1024);
   if (!lds) {
     const size_t scn = (size_t)grid * kGenericBufs * mat_elems(n) + (size_t)ld_for(n) * np_for(n);
-    HIPCHK(h, ws_get(h, 3, &scr, scn));
+    HIPCHK(h, h->ws[3].reserve(scn * sizeof(double), h->stream));
+    scr = reinterpret_cast<double *>(h->ws[3].get());
     HIPCHK(h, hipMemsetAsync(scr, 0, scn * sizeof(double), h->stream));
   }
   BlasArgs a{n, batch, dA, dB, dC, scr, h->d_info};
@@ -1022,8 +936,10 @@ extern "C" int mom_elemental_inelastic_rrs(mom_t *h, int m, int ndoubl, int nRam
   const size_t S = h->S, NN = (size_t)N * N, big = NN * S * nRaman, vec = (size_t)N * S * nRaman;
   double *buf = nullptr;
   int *dI = nullptr;
-  HIPCHK(h, ws_get(h, 0, &buf, 4 * big + 2 * vec + nRaman + 4 * S + 2 * NN));
-  HIPCHK(h, ws_get(h, 1, &dI, (size_t)nRaman));
+  HIPCHK(h, h->ws[0].reserve((4 * big + 2 * vec + nRaman + 4 * S + 2 * NN) * sizeof(double), h->stream));
+  buf = reinterpret_cast<double *>(h->ws[0].get());
+  HIPCHK(h, h->ws[1].reserve((size_t)nRaman * sizeof(int), h->stream));
+  dI = reinterpret_cast<int *>(h->ws[1].get());
   double *d_out = buf, *d_vp = buf + 4 * big + 2 * vec, *d_fs = d_vp + nRaman, *d_ts = d_fs + S, *d_dt = d_ts + S,
          *d_w = d_dt + S, *d_zp = d_w + S, *d_zm = d_zp + NN;
   HIPCHK(h, hipMemcpyAsync(dI, i_l1l0, nRaman * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -1059,7 +975,8 @@ static int dual_common(mom_t *h, int n, int batch, int P, const double *A, const
   const size_t cnt = (size_t)n * n * batch, cntP = cnt * P;
   double *buf = nullptr, *scr = nullptr;
   // one allocation: A, B, C [cnt] and dA, dB, dC [cntP]
-  HIPCHK(h, ws_get(h, 0, &buf, 3 * cnt + 3 * cntP + 1));
+  HIPCHK(h, h->ws[0].reserve((3 * cnt + 3 * cntP + 1) * sizeof(double), h->stream));
+  buf = reinterpret_cast<double *>(h->ws[0].get());
   double *dA_ = buf + 3 * cnt, *dB_ = dA_ + cntP, *dC_ = dB_ + cntP;
   HIPCHK(h, hipMemcpyAsync(buf, A, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
   if (P) HIPCHK(h, hipMemcpyAsync(dA_, dA, cntP * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1071,7 +988,8 @@ static int dual_common(mom_t *h, int n, int batch, int P, const double *A, const
   const int grid = lds ? batch : std::min(batch, 1024);
   if (!lds) {
     const size_t scn = (size_t)grid * kGenericBufs * mat_elems(n) + (size_t)ld_for(n) * np_for(n);
-    HIPCHK(h, ws_get(h, 3, &scr, scn));
+    HIPCHK(h, h->ws[3].reserve(scn * sizeof(double), h->stream));
+    scr = reinterpret_cast<double *>(h->ws[3].get());
     HIPCHK(h, hipMemsetAsync(scr, 0, scn * sizeof(double), h->stream));
   }
   DualArgs a{n, batch, P, buf, dA_, buf + cnt, dB_, buf + 2 * cnt, dC_, scr, h->d_info};
@@ -1097,14 +1015,6 @@ extern "C" int mom_batched_mul_dual(mom_t *h, int n, int batch, int P, const dou
 }
 
 // ---------------------------------------------------------------- scene-level
-
-template <class T>
-static int upload_new(mom_t *h, T **dst, const T *src, size_t count) {
-  if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
-  HIPCHK(h, dmalloc(dst, count));
-  HIPCHK(h, hipMemcpyAsync(*dst, src, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
-  return MOM_OK;
-}
 
 // everything of a scene that does not depend on how the layer optics reach the device: phase-matrix bases, view
 // geometry, output buffers, the m = 0 reduction
@@ -1140,10 +1050,10 @@ extern "C" int mom_scene_set(mom_t *h, int Nz, int K, int M, const double *tau, 
     h->scene_set = true;
     return MOM_OK;
   }
-  if ((rc = upload_new(h, &h->d_tau, tau, S * Nz))) return rc;
-  if ((rc = upload_new(h, &h->d_varpi, varpi, S * Nz))) return rc;
-  if ((rc = upload_new(h, &h->d_zw, zw, (size_t)K * S * Nz))) return rc;
-  if ((rc = upload_new(h, &h->d_tau_sum, tau_sum, S * (Nz + 1)))) return rc;
+  HIPCHK(h, mom_upload(h->d_tau, tau, S * Nz, h->stream));
+  HIPCHK(h, mom_upload(h->d_varpi, varpi, S * Nz, h->stream));
+  HIPCHK(h, mom_upload(h->d_zw, zw, (size_t)K * S * Nz, h->stream));
+  HIPCHK(h, mom_upload(h->d_tau_sum, tau_sum, S * (Nz + 1), h->stream));
   if ((rc = scene_common(h, Nz, K, M, Zpp, Zmp, albedo, nVza, node_1based, cos_mphi, sin_mphi))) return rc;
   h->nd.assign(ndoubl, ndoubl + Nz);
   h->iface.assign(iface, iface + Nz);
@@ -1156,37 +1066,35 @@ static int scene_common(mom_t *h, int Nz, int K, int M, const double *Zpp, const
   for (int v = 0; v < nVza; ++v)
     if (node_1based[v] < 1 || node_1based[v] * h->nS > h->N) return fail(h, MOM_EINVAL, "mom_scene_set: bad view node");
   const size_t S = h->S, NN = (size_t)h->N * h->N;
-  int rc;
   // a new scene: the partials of the previous one (mom_scene_set_partials) do not belong to it
-  for (int k = 0; k < 8; ++k)
-    if (h->d_dual_in[k]) { (void)hipFree(h->d_dual_in[k]); h->d_dual_in[k] = nullptr; }
-  h->dual_P = 0; h->dual_ran = false; h->dual_last = false;
+  for (auto &b : h->d_dual_in) b.reset();
+  h->dual_P = 0; h->dual_ran = false;
   // (edges up to 32 belong to the wave-per-point kernel, which takes the operators as they are)
   const int Nk = (h->opt_pad && !(h->N <= 32 && h->opt_small)) ? strip_pad(h->N) : h->N;
   h->Nk = Nk;
   h->qk = h->q;
   h->qk.N = Nk;
   if (Nk == h->N) {
-    if ((rc = upload_new(h, &h->d_Zpp, Zpp, NN * K * M))) return rc;
-    if ((rc = upload_new(h, &h->d_Zmp, Zmp, NN * K * M))) return rc;
+    HIPCHK(h, mom_upload(h->d_Zpp, Zpp, NN * K * M, h->stream));
+    HIPCHK(h, mom_upload(h->d_Zmp, Zmp, NN * K * M, h->stream));
   } else {
-    const std::vector<double> zp = pad_blocks(Zpp, h->N, Nk, (size_t)K * M), zm = pad_blocks(Zmp, h->N, Nk, (size_t)K * M);
-    if ((rc = upload_new(h, &h->d_Zpp, zp.data(), zp.size()))) return rc;
-    if ((rc = upload_new(h, &h->d_Zmp, zm.data(), zm.size()))) return rc;
+    const std::vector<double> zp = mom_pad_blocks(Zpp, h->N, Nk, (size_t)K * M), zm = mom_pad_blocks(Zmp, h->N, Nk, (size_t)K * M);
+    HIPCHK(h, mom_upload(h->d_Zpp, zp.data(), zp.size(), h->stream));
+    HIPCHK(h, mom_upload(h->d_Zmp, zm.data(), zm.size(), h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));  // the padded host copies go out of scope
   }
-  if ((rc = upload_new(h, &h->d_node, node_1based, (size_t)nVza))) return rc;
-  if ((rc = upload_new(h, &h->d_cos, cos_mphi, (size_t)nVza * M))) return rc;
-  if ((rc = upload_new(h, &h->d_sin, sin_mphi, (size_t)nVza * M))) return rc;
-  if (h->d_R) { (void)hipFree(h->d_R); (void)hipFree(h->d_hdr); h->d_R = h->d_T = h->d_hdr = nullptr; }
+  HIPCHK(h, mom_upload(h->d_node, node_1based, (size_t)nVza, h->stream));
+  HIPCHK(h, mom_upload(h->d_cos, cos_mphi, (size_t)nVza * M, h->stream));
+  HIPCHK(h, mom_upload(h->d_sin, sin_mphi, (size_t)nVza * M, h->stream));
+  h->d_R.reset(); h->d_hdr.reset(); h->d_T = nullptr;
   // R_SFI || T_SFI in ONE buffer: it is the send buffer of the all-gather (mom_allgather_RT) as it stands
-  HIPCHK(h, dmalloc(&h->d_R, 2 * (size_t)nVza * h->nS * S));
+  HIPCHK(h, h->d_R.renew(2 * (size_t)nVza * h->nS * S));
   h->d_T = h->d_R + (size_t)nVza * h->nS * S;
-  HIPCHK(h, dmalloc(&h->d_hdr, (size_t)nVza * h->nS * S));
+  HIPCHK(h, h->d_hdr.renew((size_t)nVza * h->nS * S));
   if (!h->d_hdrJ) {
-    HIPCHK(h, dmalloc(&h->d_hdrJ, (size_t)(h->N + kPadMax) * S));
-    HIPCHK(h, dmalloc(&h->d_bhr_uw, (size_t)h->nS * S));
-    HIPCHK(h, dmalloc(&h->d_bhr_dw, (size_t)h->nS * S));
+    HIPCHK(h, h->d_hdrJ.renew((size_t)(h->N + kMomPadMax) * S));
+    HIPCHK(h, h->d_bhr_uw.renew((size_t)h->nS * S));
+    HIPCHK(h, h->d_bhr_dw.renew((size_t)h->nS * S));
   }
   // ---- m = 0 reduction (include/momcore.h): conditions checked on the data, bitwise
   {
@@ -1200,9 +1108,8 @@ static int scene_common(mom_t *h, int Nz, int K, int M, const double *Zpp, const
           const size_t o = i + (size_t)N * (j + (size_t)N * kb);  // moment 0 block
           if (Zpp[o] != 0.0 || Zmp[o] != 0.0) { ok = false; break; }
         }
-    auto fr = [](double *&p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    fr(h->d_mu0); fr(h->d_wt0); fr(h->d_sg0); fr(h->d_Zpp0); fr(h->d_Zmp0); fr(h->d_hdrJ0); fr(h->d_scratch0);
-    for (int k = 0; k < 6; ++k) fr(h->comp0[k]);
+    for (MomDevBuf<double> *b : {&h->d_mu0, &h->d_wt0, &h->d_sg0, &h->d_Zpp0, &h->d_Zmp0, &h->d_hdrJ0, &h->d_scratch0}) b->reset();
+    for (auto &b : h->comp0) b.reset();
     h->red0 = ok;
     if (ok) {
       // N0r real entries; the kernels run on N0 >= N0r (dummy entries of strip_pad at the end: mu = 1, weight 0, Z = 0)
@@ -1222,19 +1129,19 @@ static int scene_common(mom_t *h, int Nz, int K, int M, const double *Zpp, const
             zp[i + (size_t)N0 * (j + (size_t)N0 * kb)] = Zpp[src];
             zm[i + (size_t)N0 * (j + (size_t)N0 * kb)] = Zmp[src];
           }
-      if ((rc = upload_new(h, &h->d_mu0, mu0v.data(), (size_t)N0))) return rc;
-      if ((rc = upload_new(h, &h->d_wt0, wt0v.data(), (size_t)N0))) return rc;
-      if ((rc = upload_new(h, &h->d_sg0, sg0v.data(), (size_t)N0))) return rc;
-      if ((rc = upload_new(h, &h->d_Zpp0, zp.data(), zp.size()))) return rc;
-      if ((rc = upload_new(h, &h->d_Zmp0, zm.data(), zm.size()))) return rc;
+      HIPCHK(h, mom_upload(h->d_mu0, mu0v.data(), (size_t)N0, h->stream));
+      HIPCHK(h, mom_upload(h->d_wt0, wt0v.data(), (size_t)N0, h->stream));
+      HIPCHK(h, mom_upload(h->d_sg0, sg0v.data(), (size_t)N0, h->stream));
+      HIPCHK(h, mom_upload(h->d_Zpp0, zp.data(), zp.size(), h->stream));
+      HIPCHK(h, mom_upload(h->d_Zmp0, zm.data(), zm.size(), h->stream));
       for (int k = 0; k < 6; ++k) {
         const size_t cnt = ((k < 4) ? (size_t)comp_pitch(N0) * N0 : (size_t)N0) * S;
-        HIPCHK(h, dmalloc(&h->comp0[k], cnt));
+        HIPCHK(h, h->comp0[k].renew(cnt));
         HIPCHK(h, hipMemsetAsync(h->comp0[k], 0, cnt * sizeof(double), h->stream));
       }
-      HIPCHK(h, dmalloc(&h->d_hdrJ0, (size_t)N0 * S));
+      HIPCHK(h, h->d_hdrJ0.renew((size_t)N0 * S));
       const size_t scr = (size_t)h->G * kGenericBufs * mat_elems(N0) + (size_t)ld_for(N0) * np_for(N0);
-      HIPCHK(h, dmalloc(&h->d_scratch0, scr));
+      HIPCHK(h, h->d_scratch0.renew(scr));
       HIPCHK(h, hipMemsetAsync(h->d_scratch0, 0, scr * sizeof(double), h->stream));
       HIPCHK(h, hipMemsetAsync(h->d_bhr_uw, 0, (size_t)h->nS * S * sizeof(double), h->stream));
       HIPCHK(h, hipMemsetAsync(h->d_bhr_dw, 0, (size_t)h->nS * S * sizeof(double), h->stream));
@@ -1267,14 +1174,13 @@ extern "C" int mom_scene_set_surface(mom_t *h, int kind, int M, const double *Rs
   }
   if (kind == 1) {
     if (h->Nk == N) {
-      if ((rc = upload_new(h, &h->d_Rsurf, Rsurf, NN * M))) return rc;
+      HIPCHK(h, mom_upload(h->d_Rsurf, Rsurf, NN * M, h->stream));
     } else {
-      const std::vector<double> rp = pad_blocks(Rsurf, N, h->Nk, (size_t)M);
-      if ((rc = upload_new(h, &h->d_Rsurf, rp.data(), rp.size()))) return rc;
+      const std::vector<double> rp = mom_pad_blocks(Rsurf, N, h->Nk, (size_t)M);
+      HIPCHK(h, mom_upload(h->d_Rsurf, rp.data(), rp.size(), h->stream));
       HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    if (h->d_hdrJm) { (void)hipFree(h->d_hdrJm); h->d_hdrJm = nullptr; }
-    HIPCHK(h, dmalloc(&h->d_hdrJm, (size_t)h->Nk * S * M));
+    HIPCHK(h, h->d_hdrJm.renew((size_t)h->Nk * S * M));
     if (h->red0) {
       // moment 0 runs on the (I,Q) sub-problem: its surface matrix must not couple (I,Q) with (U,V) either
       const int nS0 = h->nS0, N0 = h->N0;
@@ -1288,10 +1194,10 @@ extern "C" int mom_scene_set_surface(mom_t *h, int kind, int M, const double *Rs
                                        "MOM_OPT_M0_REDUCTION = 0 before mom_scene_set for this surface");
           if (iq_i && iq_j) r0[(i / nS) * nS0 + (i % nS) + (size_t)N0 * ((j / nS) * nS0 + (j % nS))] = v;
         }
-      if ((rc = upload_new(h, &h->d_Rsurf0, r0.data(), r0.size()))) return rc;
+      HIPCHK(h, mom_upload(h->d_Rsurf0, r0.data(), r0.size(), h->stream));
     }
   } else if (kind == 2) {
-    if ((rc = upload_new(h, &h->d_albedo_spec, albedo_spec, S))) return rc;
+    HIPCHK(h, mom_upload(h->d_albedo_spec, albedo_spec, S, h->stream));
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->surf_kind = kind;
@@ -1318,7 +1224,7 @@ static int single_launch_end(mom_t *h) {
 // N <= 4: one spectral point per lane, all moments / layers / surface / post-processing in ONE launch
 static int rt_run_small(mom_t *h) {
   const int N = h->N, Nz = h->Nz;
-  if (!h->d_smtab) HIPCHK(h, dmalloc(&h->d_smtab, 3 * 16));
+  if (!h->d_smtab) HIPCHK(h, h->d_smtab.renew(3 * 16));
   {  // mu_j/(mu_i + mu_j), mu_j/(mu_i - mu_j), (1/mu_i) + (1/mu_j): the expressions of elemental.jl:176-186, evaluated once
     double tab[48] = {0};
     for (int j = 0; j < N; ++j)
@@ -1331,7 +1237,7 @@ static int rt_run_small(mom_t *h) {
     HIPCHK(h, hipMemcpyAsync(h->d_smtab, tab, sizeof tab, hipMemcpyHostToDevice, h->stream));
   }
   {
-    HIPCHK(h, grow(&h->d_ndif, &h->ndif_cap, 2 * (size_t)Nz, h->stream));
+    HIPCHK(h, h->d_ndif.reserve(2 * (size_t)Nz, h->stream));
     std::vector<int> v(h->nd);
     v.insert(v.end(), h->iface.begin(), h->iface.end());
     HIPCHK(h, hipMemcpyAsync(h->d_ndif, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -1351,7 +1257,7 @@ static int rt_run_small(mom_t *h) {
   if (h->K > 4) return fail(h, MOM_EINVAL, "mom_rt_run: the N <= 4 sweep kernel handles at most 4 phase-matrix bases");
   if (a.M > 1 && h->opt_small != 2) {  // one (point, moment) per lane (mom_small.hip SPLIT); MOM_OPT_SMALL_N = 2: one point per lane
     const size_t need = (size_t)a.M * 2 * a.nVza * a.nS * a.S;
-    HIPCHK(h, grow(&h->d_smpart, &h->smpart_cap, need, h->stream));
+    HIPCHK(h, h->d_smpart.reserve(need, h->stream));
     a.part = h->d_smpart;
   }
   int rc = single_launch_begin(h);
@@ -1373,7 +1279,7 @@ static bool wave_sweep_applies(const mom_t *h) {
 // 4 < N <= 32: one spectral point per wavefront, operators in MFMA-layout registers, ONE launch
 static int rt_run_wave(mom_t *h) {
   const int Nz = h->Nz;
-  HIPCHK(h, grow(&h->d_ndif, &h->ndif_cap, 2 * (size_t)Nz, h->stream));
+  HIPCHK(h, h->d_ndif.reserve(2 * (size_t)Nz, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->d_ndif, h->nd.data(), (size_t)Nz * sizeof(int), hipMemcpyHostToDevice, h->stream));
   WaveSweepArgs a{};
   a.N = h->N; a.S = h->S; a.M = h->scene_M; a.K = h->K; a.Nz = Nz; a.nVza = h->nVza; a.nS = h->nS; a.imu0 = h->q.imu0;
@@ -1452,16 +1358,16 @@ static int launch_first_stage(mom_t *h, const FirstStage &fs, LayerArgs &a, bool
   // resume[unit]: the two-buffer image has a table of its own -- under MOM_OPT_OVERLAP the m = 0 sub-problem's first stage and
   // the full problem's two-buffer launch can be in flight at once
   const bool two_buffer = (fs.family == MOM_IMG_STRIP2);
-  int **table = two_buffer ? &h->d_resume2 : &h->d_resume;
-  HIPCHK(h, grow(table, two_buffer ? &h->resume2_cap : &h->resume_cap, units, st));
-  a.resume = *table;
+  MomDevBuf<int> &table = two_buffer ? h->d_resume2 : h->d_resume;
+  HIPCHK(h, table.reserve(units, st));
+  a.resume = table;
   int per_cu = fs.image->per_cu();
   if (two_buffer) {
     h->resume2_units = units; h->resume2_nz = nzr;  // (mom_strip2_resumed)
     if (h->opt_strip2_sched) {  // the queue counter (and, for the chain priority, the per-CU tickets) start at zero: a memset ON
                                 // THE STREAM, so that an asynchronous step (or a captured one) resets them in order with its launches
       const size_t ints = kMomStrip2SchedInts;
-      if (!h->d_sched2) HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&h->d_sched2), ints * sizeof(int)));
+      if (!h->d_sched2) HIPCHK(h, h->d_sched2.renew(ints));
       HIPCHK(h, hipMemsetAsync(h->d_sched2, 0, ((h->opt_strip2_sched & 2) ? ints : 1) * sizeof(int), st));
       a.sched = h->d_sched2;
       a.sched_mode = h->opt_strip2_sched;
@@ -1520,7 +1426,8 @@ struct TargetSpec {
   std::vector<signed char> act;  // [zb - za][kMaxTargets]
 };
 
-static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, double *const compF[6], bool do_surface, bool do_post,
+template <class Comp6>  // compF[6]: the handle's buffers or raw pointers
+static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, const Comp6 &compF, bool do_surface, bool do_post,
                        bool cont = false, const TargetSpec *tg = nullptr) {
   const size_t S = h->S;
   const int M = h->scene_M;
@@ -1540,7 +1447,7 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, double *const c
   for (int z = za; z < zb && can_sweep; ++z) can_sweep = (h->nd[z] <= 127);
   hipStream_t cur = h->stream;  // the stream launch_layer issues to (MOM_OPT_OVERLAP switches it for the m = 0 sub-problem)
   auto launch_layer = [&](int z, const DevStreams &q, int m_first, int Mcount, const double *Zpp, const double *Zmp,
-                          double *const comp[6], double *scratch) -> int {
+                          const auto &comp, double *scratch) -> int {  // comp[6]: buffers or raw pointers
     LayerArgs a{};
     a.q = q; a.S = h->S; a.M = Mcount; a.K = h->K; a.m_first = m_first;
     const bool sweep = z < 0;
@@ -1681,7 +1588,6 @@ extern "C" int mom_rt_run(mom_t *h) {
   h->launches = 0; h->launches_full = 0; h->launches_red = 0;
   h->comp_pitched = true;
   h->comp_on_chip = true;
-  h->dual_last = false;
   if (h->N <= 4 && h->opt_small && !h->opt_force_generic && h->nVza <= 4 && h->surf_kind == 0 && h->K <= 4) return rt_run_small(h);
   if (wave_sweep_applies(h)) return rt_run_wave(h);
   h->comp_on_chip = false;
@@ -1709,38 +1615,29 @@ extern "C" int mom_rt_run_multisensor(mom_t *h, int nSensors, const int *sensor_
   h->comp_pitched = true;
   h->comp_on_chip = false;
   if (!h->comp_top[0]) {
-    const int Na = h->N + kPadMax;
+    const int Na = h->N + kMomPadMax;
     for (int k = 0; k < 6; ++k) {
       const size_t perc = (k < 4) ? (size_t)comp_pitch(Na) * Na : (size_t)Na;
-      HIPCHK(h, dmalloc(&h->comp_top[k], perc * S * h->M));
+      HIPCHK(h, h->comp_top[k].renew(perc * S * h->M));
     }
-    for (int k = 0; k < 2; ++k) HIPCHK(h, dmalloc(&h->d_msJ[k], (size_t)Na * S * h->M));
+    for (int k = 0; k < 2; ++k) HIPCHK(h, h->d_msJ[k].renew((size_t)Na * S * h->M));
   }
-  HIPCHK(h, grow(&h->d_ms_out, &h->ms_out_cap, 2 * out1 * nSensors, h->stream));
+  HIPCHK(h, h->d_ms_out.reserve(2 * out1 * nSensors, h->stream));
   double *d_uw = h->d_ms_out, *d_dw = h->d_ms_out + out1 * nSensors;
   // rt_kernel_multisensor! (rt_kernel_multisensor.jl:51-112): ONE sweep over the layers builds every layer's added operators
   // once and feeds all composites -- the running slab above the sensors (target 0, frozen into a per-sensor snapshot when
   // the sweep passes the sensor's level) and the slab below each sensor -- then per sensor the surface interaction, the
   // interface solve and the post-processing.  Sensors are processed in chunks of what one kernel's target table holds.
-  const int Na = h->N + kPadMax;
+  const int Na = h->N + kMomPadMax;
   const size_t blk[6] = {(size_t)comp_pitch(Na) * Na, (size_t)comp_pitch(Na) * Na, (size_t)comp_pitch(Na) * Na,
                          (size_t)comp_pitch(Na) * Na, (size_t)Na, (size_t)Na};
   const int per_chunk = (kMaxTargets - 1) / 2;  // top + (snapshot + bottom) per sensor
   for (int c0 = 0; c0 < nSensors; c0 += per_chunk) {
     const int nc = std::min(per_chunk, nSensors - c0);
     const size_t need = (size_t)2 * nc;  // composite sets beyond h->comp_top: nc snapshots + nc bottoms
-    if (h->ms_sets < need) {
-      for (auto p : h->ms_comp) (void)hipFree(p);
-      h->ms_comp.clear();
-      h->ms_sets = 0;
-      for (size_t sidx = 0; sidx < need; ++sidx)
-        for (int k = 0; k < 6; ++k) {
-          double *p = nullptr;
-          HIPCHK(h, dmalloc(&p, blk[k] * S * h->M));
-          h->ms_comp.push_back(p);
-        }
-      h->ms_sets = need;
-    }
+    if (h->ms_comp.size() < 6 * need) h->ms_comp.resize(6 * need);
+    for (size_t sidx = 0; sidx < need; ++sidx)
+      for (int k = 0; k < 6; ++k) HIPCHK(h, h->ms_comp[6 * sidx + k].reserve(blk[k] * S * h->M, h->stream));
     // sensors of this chunk in order of depth: the slab below sensor i is the SEGMENT of layers [L_i, L_i+1) -- built in the
     // shared sweep, so every layer feeds the running top slab and exactly one segment whatever the number of sensors --
     // joined afterwards to the slab below sensor i + 1 (k_combine); the deepest sensor's segment runs to the last layer
@@ -1836,38 +1733,35 @@ extern "C" int mom_scene_set_partials(mom_t *h, int P, const double *dtau, const
   if (P < 0 || P > 64 || ((dZpp == nullptr) != (dZmp == nullptr)))
     return fail(h, MOM_EINVAL, "mom_scene_set_partials: 0 <= P <= 64; dZpp and dZmp come together");
   HIPCHK(h, hipSetDevice(h->device));
-  for (int k = 0; k < 8; ++k)
-    if (h->d_dual_in[k]) { (void)hipFree(h->d_dual_in[k]); h->d_dual_in[k] = nullptr; }
-  if (h->d_dual_out) { (void)hipFree(h->d_dual_out); h->d_dual_out = nullptr; }
-  if (h->d_dual_ts) { (void)hipFree(h->d_dual_ts); h->d_dual_ts = nullptr; }
+  for (auto &b : h->d_dual_in) b.reset();
+  h->d_dual_out.reset(); h->d_dual_ts.reset();
   h->dual_P = P;
   h->dual_ran = false;
   if (P == 0) return MOM_OK;
   const size_t S = h->S, Nz = h->Nz, K = h->K, M = h->scene_M, N = h->N, Nk = h->Nk;
-  int rc;
-  if (dtau && (rc = upload_new(h, &h->d_dual_in[0], dtau, S * Nz * P))) return rc;
-  if (dvarpi && (rc = upload_new(h, &h->d_dual_in[1], dvarpi, S * Nz * P))) return rc;
-  if (dzw && (rc = upload_new(h, &h->d_dual_in[2], dzw, K * S * Nz * P))) return rc;
+  if (dtau) HIPCHK(h, mom_upload(h->d_dual_in[0], dtau, S * Nz * P, h->stream));
+  if (dvarpi) HIPCHK(h, mom_upload(h->d_dual_in[1], dvarpi, S * Nz * P, h->stream));
+  if (dzw) HIPCHK(h, mom_upload(h->d_dual_in[2], dzw, K * S * Nz * P, h->stream));
   if (dZpp) {
     if (Nk == N) {
-      if ((rc = upload_new(h, &h->d_dual_in[3], dZpp, N * N * K * M * P))) return rc;
-      if ((rc = upload_new(h, &h->d_dual_in[4], dZmp, N * N * K * M * P))) return rc;
+      HIPCHK(h, mom_upload(h->d_dual_in[3], dZpp, N * N * K * M * P, h->stream));
+      HIPCHK(h, mom_upload(h->d_dual_in[4], dZmp, N * N * K * M * P, h->stream));
     } else {  // the scene's operators carry strip_pad's dummy entries (Z = 0): so do the partials
-      const std::vector<double> zp = pad_blocks(dZpp, (int)N, (int)Nk, K * M * P), zm = pad_blocks(dZmp, (int)N, (int)Nk, K * M * P);
-      if ((rc = upload_new(h, &h->d_dual_in[3], zp.data(), zp.size()))) return rc;
-      if ((rc = upload_new(h, &h->d_dual_in[4], zm.data(), zm.size()))) return rc;
+      const std::vector<double> zp = mom_pad_blocks(dZpp, (int)N, (int)Nk, K * M * P), zm = mom_pad_blocks(dZmp, (int)N, (int)Nk, K * M * P);
+      HIPCHK(h, mom_upload(h->d_dual_in[3], zp.data(), zp.size(), h->stream));
+      HIPCHK(h, mom_upload(h->d_dual_in[4], zm.data(), zm.size(), h->stream));
       HIPCHK(h, hipStreamSynchronize(h->stream));
     }
   }
-  if (dalbedo && (rc = upload_new(h, &h->d_dual_in[5], dalbedo, (size_t)P))) return rc;
+  if (dalbedo) HIPCHK(h, mom_upload(h->d_dual_in[5], dalbedo, (size_t)P, h->stream));
   if (dRsurf && h->surf_kind == 1) {
-    const std::vector<double> rp = pad_blocks(dRsurf, (int)N, (int)Nk, M * P);
-    if ((rc = upload_new(h, &h->d_dual_in[6], rp.data(), rp.size()))) return rc;
+    const std::vector<double> rp = mom_pad_blocks(dRsurf, (int)N, (int)Nk, M * P);
+    HIPCHK(h, mom_upload(h->d_dual_in[6], rp.data(), rp.size(), h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
-  if (dalbedo_spec && h->surf_kind == 2 && (rc = upload_new(h, &h->d_dual_in[7], dalbedo_spec, S * P))) return rc;
-  HIPCHK(h, dmalloc(&h->d_dual_out, (3 * (size_t)h->nVza + 2) * h->nS * S * P));   // dR | dT | dhdr | dbhr_uw | dbhr_dw
-  HIPCHK(h, dmalloc(&h->d_dual_ts, S * (Nz + 1) * P));
+  if (dalbedo_spec && h->surf_kind == 2) HIPCHK(h, mom_upload(h->d_dual_in[7], dalbedo_spec, S * P, h->stream));
+  HIPCHK(h, h->d_dual_out.renew((3 * (size_t)h->nVza + 2) * h->nS * S * P));   // dR | dT | dhdr | dbhr_uw | dbhr_dw
+  HIPCHK(h, h->d_dual_ts.renew(S * (Nz + 1) * P));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MOM_OK;
 }
@@ -1896,12 +1790,12 @@ extern "C" int mom_rt_run_dual(mom_t *h) {
   sc.dbhr_uw = h->d_dual_out ? h->d_dual_out + 3 * out * h->dual_P : nullptr;
   sc.dbhr_dw = sc.dbhr_uw ? sc.dbhr_uw + (size_t)h->nS * h->S * h->dual_P : nullptr;
   sc.dtau_sum_buf = h->d_dual_ts; sc.info = h->d_info; sc.stream = h->stream;
-  sc.work = &h->dual_work; sc.work_cap = &h->dual_work_cap;
+  sc.work = &h->dual_work;
   size_t budget = h->opt_dual_budget;
   if (!budget) {
     size_t fr = 0, tot = 0;
     HIPCHK(h, hipMemGetInfo(&fr, &tot));
-    budget = (size_t)(0.6 * (double)(fr + h->dual_work_cap));
+    budget = (size_t)(0.6 * (double)(fr + h->dual_work.capacity()));
   }
   sc.work_budget = budget;
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
@@ -1913,7 +1807,6 @@ extern "C" int mom_rt_run_dual(mom_t *h) {
   HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
   HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
   h->dual_ran = true;
-  h->dual_last = true;
   h->comp_on_chip = true;  // no composite layer of this run is left in the handle's operator-level state
   return MOM_OK;
 }
@@ -2058,8 +1951,8 @@ extern "C" int mom_postprocess(mom_t *h, int m, int nVza, const int *node_1based
   HIPCHK(h, hipSetDevice(h->device));
   { const int rc_ = op_composite_ready(h, "mom_postprocess"); if (rc_) return rc_; }
   const size_t total = (size_t)nVza * h->nS * h->S;
-  HIPCHK(h, grow(&h->d_post[0], &h->post_cap, 2 * total, h->stream));
-  h->d_post[1] = h->d_post[0] + total;
+  HIPCHK(h, h->d_post.reserve(2 * total, h->stream));
+  double *const d_post[2] = {h->d_post, h->d_post + total};
   // bigCS = weight * Diagonal([cos(m φ), cos(m φ), sin(m φ), sin(m φ)][1:n])   (postprocessing_vza.jl:32-33)
   auto cosd = [](double x) { return mom_cosd(x); };
   auto sind = [](double x) { return mom_sind(x); };
@@ -2068,16 +1961,18 @@ extern "C" int mom_postprocess(mom_t *h, int m, int nVza, const int *node_1based
     for (int v = 0; v < nVza; ++v) cs[v + (size_t)nVza * k] = weight * ((k < 2) ? cosd(m * vaz_deg[v]) : sind(m * vaz_deg[v]));
   int *d_node = nullptr;
   double *d_cs = nullptr;
-  HIPCHK(h, ws_get(h, 2, &d_node, (size_t)nVza));   // grow-only workspace of the handle: no allocation per call, nothing to leak
-  HIPCHK(h, ws_get(h, 3, &d_cs, cs.size()));
+  HIPCHK(h, h->ws[2].reserve((size_t)nVza * sizeof(int), h->stream));   // grow-only workspace of the handle: no allocation per call, nothing to leak
+  d_node = reinterpret_cast<int *>(h->ws[2].get());
+  HIPCHK(h, h->ws[3].reserve(cs.size() * sizeof(double), h->stream));
+  d_cs = reinterpret_cast<double *>(h->ws[3].get());
   HIPCHK(h, hipMemcpyAsync(d_node, node_1based, (size_t)nVza * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(d_cs, cs.data(), cs.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_op_postprocess, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->N, h->nS, h->S, nVza,
-                     d_node, d_cs, h->comp[4], h->comp[5], h->d_post[0], h->d_post[1]);
+                     d_node, d_cs, h->comp[4].get(), h->comp[5].get(), d_post[0], d_post[1]);
   HIPCHK(h, hipGetLastError());
   std::vector<double> hr(total), ht(total);
-  HIPCHK(h, hipMemcpyAsync(hr.data(), h->d_post[0], total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(ht.data(), h->d_post[1], total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(hr.data(), d_post[0], total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(ht.data(), d_post[1], total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (size_t i = 0; i < total; ++i) { R_SFI[i] += hr[i]; T_SFI[i] += ht[i]; }  // `+=` like :48-49
   return MOM_OK;
@@ -2207,7 +2102,7 @@ extern "C" int mom_allgather_RT(mom_t *h, double *R_SFI_global, double *T_SFI_gl
   if (!h->comm) return fail(h, MOM_ESTATE, "mom_allgather_RT: call mom_comm_init first");
   HIPCHK(h, hipSetDevice(h->device));
   const size_t nout = (size_t)h->nVza * h->nS * h->S, need = 2 * nout * h->comm_size;
-  HIPCHK(h, grow(&h->d_gather, &h->gather_cap, need, h->stream));
+  HIPCHK(h, h->d_gather.reserve(need, h->stream));
   int rc = mom_allgather_RT_device(h, h->d_gather);
   if (rc) return rc;
   // [rank][R|T][nVza, nStokes, S_loc] -> R_SFI, T_SFI [nVza, nStokes, nranks * S_loc] (rank-major spectral axis)
@@ -2225,13 +2120,11 @@ extern "C" int mom_absorption_begin(mom_t *h, int Nz, const double *grid) {
   if (Nz <= 0) return fail(h, MOM_EINVAL, "mom_absorption_begin: bad argument");
   HIPCHK(h, hipSetDevice(h->device));
   const size_t S = h->S;
-  if (h->d_tau_abs) { (void)hipFree(h->d_tau_abs); h->d_tau_abs = nullptr; }
-  HIPCHK(h, dmalloc(&h->d_tau_abs, S * Nz));
+  HIPCHK(h, h->d_tau_abs.renew(S * Nz));
   HIPCHK(h, hipMemsetAsync(h->d_tau_abs, 0, S * Nz * sizeof(double), h->stream));  // τ_abs = zeros (model_from_parameters.jl:48)
   h->abs_Nz = Nz;
   if (grid) {
-    int rc = upload_new(h, &h->d_grid, grid, S);
-    if (rc) return rc;
+    HIPCHK(h, mom_upload(h->d_grid, grid, S, h->stream));
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MOM_OK;
@@ -2276,14 +2169,14 @@ extern "C" int mom_voigt_tau_abs(mom_t *h, int iz_1based, int nLines, const doub
     if (ind_start_1based[j] < ind_start_1based[j - 1] || ind_stop_1based[j] < ind_stop_1based[j - 1]) { sorted = 0; break; }
   HIPCHK(h, hipSetDevice(h->device));
   const size_t lb = (size_t)nLines;
-  if (lb > h->lines_cap || h->lines_nz != 1) {  // 4 double + 2 int arrays per line, grown geometrically: no allocation in steady state
+  if (lb > h->lines_per || h->lines_nz != 1) {  // 4 double + 2 int arrays per line, grown geometrically: no allocation in steady state
     h->lines_nz = 1;
-    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->d_lines); h->d_lines = nullptr; h->lines_cap = 0; }
+    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
     const size_t cap = std::max<size_t>(lb, 1024) * 2;
-    HIPCHK(h, dmalloc(&h->d_lines, 5 * cap));
-    h->lines_cap = cap;
+    HIPCHK(h, h->d_lines.renew(5 * cap));
+    h->lines_per = cap;
   }
-  const size_t cap = h->lines_cap;
+  const size_t cap = h->lines_per;
   double *dl = h->d_lines;
   int *dw = reinterpret_cast<int *>(dl + 4 * cap);
   const double *src[4] = {nu, gamma_d, y, S};
@@ -2315,12 +2208,11 @@ extern "C" int mom_absorption_set_lines(mom_t *h, int nLines, const double *nu0,
     if (nT[k] < 2 || nT[k] > nTmax) return fail(h, MOM_EINVAL, "mom_absorption_set_lines: bad knot count");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  (void)hipFree(h->d_lt); (void)hipFree(h->d_lt_i);
-  h->d_lt = nullptr; h->d_lt_i = nullptr;
+  h->d_lt.reset(); h->d_lt_i.reset();
   h->lt = MomLineTable{};
   const size_t L = (size_t)std::max(nLines, 1), Tn = (size_t)std::max(nIso, 1) * std::max(nTmax, 1);
-  HIPCHK(h, dmalloc(&h->d_lt, 8 * L + 3 * Tn));
-  HIPCHK(h, dmalloc(&h->d_lt_i, L + std::max(nIso, 1) + 1));
+  HIPCHK(h, h->d_lt.renew(8 * L + 3 * Tn));
+  HIPCHK(h, h->d_lt_i.renew(L + std::max(nIso, 1) + 1));
   const double *cols[8] = {nu0, S0, gamma_air, gamma_self, E_lower, n_air, delta_air, sqrt_mol_weight};
   for (int k = 0; k < 8 && nLines > 0; ++k) HIPCHK(h, hipMemcpy(h->d_lt + k * L, cols[k], (size_t)nLines * sizeof(double), hipMemcpyHostToDevice));
   const double *tabs[3] = {tips_T, tips_Q, tips_z};
@@ -2360,14 +2252,14 @@ extern "C" int mom_voigt_tau_abs_layer(mom_t *h, int iz_1based, double pressure,
   if (nLines == 0) return MOM_OK;
   HIPCHK(h, hipSetDevice(h->device));
   const size_t lb = (size_t)nLines;
-  if (lb > h->lines_cap || h->lines_nz != 1) {
+  if (lb > h->lines_per || h->lines_nz != 1) {
     h->lines_nz = 1;
-    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->d_lines); h->d_lines = nullptr; h->lines_cap = 0; }
+    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
     const size_t cap = std::max<size_t>(lb, 1024) * 2;
-    HIPCHK(h, dmalloc(&h->d_lines, 5 * cap));
-    h->lines_cap = cap;
+    HIPCHK(h, h->d_lines.renew(5 * cap));
+    h->lines_per = cap;
   }
-  const size_t cap = h->lines_cap;
+  const size_t cap = h->lines_per;
   double *dl = h->d_lines;
   int *dw = reinterpret_cast<int *>(dl + 4 * cap);
   int *flag = h->d_lt_i + (size_t)std::max(nLines, 1) + std::max(h->lt.nIso, 1);
@@ -2410,16 +2302,16 @@ extern "C" int mom_voigt_tau_abs_profile(mom_t *h, int Nz, const double *pressur
   HIPCHK(h, hipSetDevice(h->device));
   const size_t per = std::max<size_t>((size_t)nLines, 1024) * 2;       // line capacity of one layer's block
   const size_t need = per * (size_t)Nz;
-  if (need > h->lines_cap * (size_t)std::max(h->lines_nz, 1) || h->lines_nz != Nz) {
-    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->d_lines); h->d_lines = nullptr; h->lines_cap = 0; }
-    HIPCHK(h, dmalloc(&h->d_lines, 5 * need));
-    h->lines_cap = per;
+  if (need > h->lines_per * (size_t)std::max(h->lines_nz, 1) || h->lines_nz != Nz) {
+    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
+    HIPCHK(h, h->d_lines.renew(5 * need));
+    h->lines_per = per;
     h->lines_nz = Nz;
   }
-  const size_t cap = h->lines_cap;
+  const size_t cap = h->lines_per;
   // per-layer scalars [p | T | cgd | factor][Nz] and the Nz sortedness flags
   const size_t prm_doubles = 4 * (size_t)Nz + ((size_t)Nz + 1) / 2;
-  HIPCHK(h, grow(&h->d_prof, &h->prof_cap, prm_doubles, h->stream));
+  HIPCHK(h, h->d_prof.reserve(prm_doubles, h->stream));
   std::vector<double> prm(4 * (size_t)Nz);
   for (int z = 0; z < Nz; ++z) {
     prm[z] = pressure[z];
@@ -2453,9 +2345,9 @@ extern "C" int mom_voigt_tau_abs_profile(mom_t *h, int Nz, const double *pressur
 extern "C" int mom_absorption_get_prefactors(mom_t *h, int n, double *nu, double *gamma_d, double *y, double *S, int *ind_start_1based,
                                              int *ind_stop_1based) {
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
-  if (!h->d_lines || n < 0 || (size_t)n > h->lines_cap) return fail(h, MOM_ESTATE, "mom_absorption_get_prefactors: no prefactors resident");
+  if (!h->d_lines || n < 0 || (size_t)n > h->lines_per) return fail(h, MOM_ESTATE, "mom_absorption_get_prefactors: no prefactors resident");
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t cap = h->lines_cap, nz = (size_t)std::max(h->lines_nz, 1), last = (nz - 1) * cap;  // the LAST layer of a profile call
+  const size_t cap = h->lines_per, nz = (size_t)std::max(h->lines_nz, 1), last = (nz - 1) * cap;  // the LAST layer of a profile call
   double *dst[4] = {nu, gamma_d, y, S};
   for (int k = 0; k < 4; ++k)
     if (dst[k]) HIPCHK(h, hipMemcpy(dst[k], h->d_lines + k * nz * cap + last, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
@@ -2554,7 +2446,7 @@ extern "C" int mom_scene_set_optics(mom_t *h, int Nz, int nAer, int M, const dou
   const size_t S = h->S;
   const int K = 1 + nAer;
   int rc;
-  if ((rc = upload_new(h, &h->d_tau_rayl, tau_rayl, S * Nz))) return rc;
+  HIPCHK(h, mom_upload(h->d_tau_rayl, tau_rayl, S * Nz, h->stream));
   // createAero (compEffectiveLayerProperties.jl:80-85): τ' = (1 - fᵗ ω̃) τ_aer, ϖ' = (1 - fᵗ) ω̃ / (1 - fᵗ ω̃); the
   // all-zero tests of types.jl:641-661 are decided here on the host (they are properties of whole spectral columns)
   std::vector<double> aer((size_t)2 * std::max(nAer, 1) * Nz, 0.0);
@@ -2574,14 +2466,13 @@ extern "C" int mom_scene_set_optics(mom_t *h, int Nz, int nAer, int M, const dou
       x_zero = x_zero && (wy == 0.0);
     }
   }
-  if ((rc = upload_new(h, &h->d_aer, aer.data(), aer.size()))) return rc;
-  if ((rc = upload_new(h, &h->d_aer_mode, mode.data(), mode.size()))) return rc;
-  auto renew = [&](double **p, size_t cnt) -> hipError_t { if (*p) { (void)hipFree(*p); *p = nullptr; } return dmalloc(p, cnt); };
-  HIPCHK(h, renew(&h->d_tau, S * Nz));
-  HIPCHK(h, renew(&h->d_varpi, S * Nz));
-  HIPCHK(h, renew(&h->d_zw, (size_t)K * S * Nz));
-  HIPCHK(h, renew(&h->d_tau_sum, S * (Nz + 1)));
-  HIPCHK(h, renew(&h->d_layer_max, (size_t)Nz));
+  HIPCHK(h, mom_upload(h->d_aer, aer.data(), aer.size(), h->stream));
+  HIPCHK(h, mom_upload(h->d_aer_mode, mode.data(), mode.size(), h->stream));
+  HIPCHK(h, h->d_tau.renew(S * Nz));
+  HIPCHK(h, h->d_varpi.renew(S * Nz));
+  HIPCHK(h, h->d_zw.renew((size_t)K * S * Nz));
+  HIPCHK(h, h->d_tau_sum.renew(S * (Nz + 1)));
+  HIPCHK(h, h->d_layer_max.renew((size_t)Nz));
   HIPCHK(h, hipMemsetAsync(h->d_layer_max, 0, (size_t)Nz * sizeof(double), h->stream));
   OpticsArgs a{};
   a.S = h->S; a.Nz = Nz; a.nAer = nAer; a.varpi_rayl = varpi_rayl;
@@ -2784,10 +2675,10 @@ extern "C" int mom_rrs_elemental(mom_t *h, int m, int ndoubl, const double *tau_
   const double *src[8] = {tau_sum, dtau, varpi, fscattRayl, Zpp, Zmp, Zpp_l1l0, Zmp_l1l0};
   for (int k = 0; k < 8; ++k) {
     const size_t cnt = (k < 4) ? S : NN;
-    if (!h->d_rrs_op[k]) HIPCHK(h, dmalloc(&h->d_rrs_op[k], cnt));
+    if (!h->d_rrs_op[k]) HIPCHK(h, h->d_rrs_op[k].renew(cnt));
     HIPCHK(h, hipMemcpyAsync(h->d_rrs_op[k], src[k], cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
   }
-  double *const *d = h->d_rrs_op;
+  const MomDevBuf<double> *d = h->d_rrs_op;
   RRSCHK(h, momr::elemental(h->rrs, rrs_streams(h), m, ndoubl, 0, d[0], d[1], d[2], d[4], d[5], 1, nullptr, d[3], d[6], d[7], true, true));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MOM_OK;
@@ -2841,9 +2732,9 @@ extern "C" int mom_scene_set_rrs(mom_t *h, const double *fscattRayl, const doubl
   if (!fscattRayl || !Zpp_l1l0 || !Zmp_l1l0) return fail(h, MOM_EINVAL, "mom_scene_set_rrs: bad argument");
   if (h->Nk != h->N) return fail(h, MOM_ESTATE, "mom_scene_set_rrs: the scene was set with a padded operator edge (MOM_OPT_STRIP_PAD)");
   const size_t NN = (size_t)h->N * h->N;
-  if ((rc = upload_new(h, &h->d_fscatt, fscattRayl, (size_t)h->S * h->Nz))) return rc;
-  if ((rc = upload_new(h, &h->d_Zr[0], Zpp_l1l0, NN * h->scene_M))) return rc;
-  if ((rc = upload_new(h, &h->d_Zr[1], Zmp_l1l0, NN * h->scene_M))) return rc;
+  HIPCHK(h, mom_upload(h->d_fscatt, fscattRayl, (size_t)h->S * h->Nz, h->stream));
+  HIPCHK(h, mom_upload(h->d_Zr[0], Zpp_l1l0, NN * h->scene_M, h->stream));
+  HIPCHK(h, mom_upload(h->d_Zr[1], Zmp_l1l0, NN * h->scene_M, h->stream));
   h->rrs_scene = true;
   return MOM_OK;
 }
@@ -2936,7 +2827,7 @@ extern "C" int mom_allgather_rrs_device(mom_t *h, int per, void *d_global) {
   if (!h->comm) return fail(h, MOM_ESTATE, "mom_allgather_rrs_device: call mom_comm_init first");
   if (!d_global) return fail(h, MOM_EINVAL, "mom_allgather_rrs_device: null buffer");
   const size_t cnt = mom_rrs_spectra_count(h, per);
-  HIPCHK(h, grow(&h->d_rrs_send, &h->rrs_send_cap, cnt, h->stream));
+  HIPCHK(h, h->d_rrs_send.reserve(cnt, h->stream));
   if ((rc = rrs_pack_owned(h, per, h->d_rrs_send))) return rc;
   return mom_allgather(h, h->d_rrs_send, d_global, cnt);
 }

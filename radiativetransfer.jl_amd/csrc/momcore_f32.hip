@@ -96,8 +96,6 @@ __global__ void k_combine_m0_f32(CombineArgsF a) {
   }
 }
 
-template <class T>
-hipError_t dmallocf(T **p, size_t count) { return hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T)); }
 
 // batch_inv! / batched_mul for Float32 arrays (gpu_batched.jl:45-58, 90-97: cuBLAS Sgetrf/Sgetri, Sgemm)
 struct BlasArgsF {
@@ -155,24 +153,10 @@ std::vector<float> tof(const double *src, size_t n) {
 
 }  // namespace
 
-// Edges with a Float32 strip-chained image; other edges are padded with up to 4 dummy stream entries (mu = 1, weight 0, zero
-// rows and columns in every phase-matrix basis and BRDF matrix: decoupled exactly, see strip_pad in momcore.hip) to reach one
-constexpr int kPadMaxF = 4;
-static bool strip_size_f(int N) { return N == 36 || N == 40 || N == 44 || N == 52 || N == 56 || N == 60; }
-static int strip_pad_f(int N) {
-  if (strip_size_f(N)) return N;
-  for (int p = N + 1; p <= N + kPadMaxF; ++p)
-    if (strip_size_f(p)) return p;
-  return N;
-}
-// [N,N,B] -> [Nk,Nk,B], zero padded
-static std::vector<double> pad_blocks_f(const double *src, int N, int Nk, size_t B) {
-  std::vector<double> out((size_t)Nk * Nk * B, 0.0);
-  for (size_t b = 0; b < B; ++b)
-    for (int j = 0; j < N; ++j)
-      for (int i = 0; i < N; ++i) out[i + (size_t)Nk * (j + (size_t)Nk * b)] = src[i + (size_t)N * (j + (size_t)N * b)];
-  return out;
-}
+// Edges with a Float32 strip-chained image (the image table, mom_images.hpp); other edges are padded with dummy stream entries
+// to reach one (the pad rule: mom_host.hpp)
+static bool strip_size_f(int N) { return mom_find_image(MOM_IMG_F32_STRIP4, N) || mom_find_image(MOM_IMG_F32_STRIP8, N); }
+static int strip_pad_f(int N) { return mom_strip_pad(strip_size_f, N); }
 
 struct momf_scene {
   int device = 0, N = 0, nS = 0, S = 0, Mmax = 0;
@@ -183,25 +167,23 @@ struct momf_scene {
   int m_first = 0;
   bool opt_m0 = true, opt_pad = true;
   // operator-level API (mom_ops.hpp): added / surface / composite layers in the reference's [N,N,S] layout, allocated on first use
-  float *op_added[6] = {}, *op_surf[6] = {}, *op_comp[6] = {}, *op_vec[4] = {}, *op_Z[2] = {};
-  size_t op_Zcap = 0;
-  float *blas_buf[4] = {};  // mom_batch_inv / mom_batched_mul: A, B, C, generic-mode scratch (grow-only)
-  size_t blas_cap[4] = {};
+  MomDevBuf<float> op_added[6], op_surf[6], op_comp[6], op_vec[4], op_Z[2];
+  MomDevBuf<float> blas_buf[4];  // mom_batch_inv / mom_batched_mul: A, B, C, generic-mode scratch (grow-only)
   bool op_ready = false, op_comp_set = false;
   std::vector<double> hd_mu, hd_wt, hd_sg;  // the caller's Float64 streams (the sub-scene is cut from them)
   double hd_I0[4] = {}, hd_D[4] = {}, hd_mu0 = 0;
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;  // borrowed from the Float64 handle (the sub-scene shares it), like d_info: never destroyed here
+  int *d_info = nullptr;
   DevStreams q{};
-  float *d_mu = nullptr, *d_wt = nullptr, *d_sg = nullptr;
-  float *comp[6] = {};
-  float *d_tau = nullptr, *d_varpi = nullptr, *d_zw = nullptr, *d_tau_sum = nullptr, *d_Zpp = nullptr, *d_Zmp = nullptr;
-  float *d_R = nullptr, *d_T = nullptr, *d_hdr = nullptr, *d_hdrJ = nullptr, *d_hdrJm = nullptr, *d_bhr_uw = nullptr,
-        *d_bhr_dw = nullptr, *d_scratch = nullptr, *d_Rsurf = nullptr, *d_albedo_spec = nullptr;
-  double *d_cos = nullptr, *d_sin = nullptr;
-  float *d_smtab = nullptr;               // N <= 4: the three stream-pair tables of the lane-per-point kernel
-  float *d_smpart = nullptr;              // ... and the per-moment terms of R_SFI / T_SFI of its (point, moment) form
-  size_t smpart_cap = 0;
-  int *d_node = nullptr, *d_info = nullptr, *d_nd = nullptr;  // d_nd: ndoubl per layer for the wave-per-point kernel
+  MomDevBuf<float> d_mu, d_wt, d_sg;
+  MomDevBuf<float> comp[6];
+  MomDevBuf<float> d_tau, d_varpi, d_zw, d_tau_sum, d_Zpp, d_Zmp;
+  MomDevBuf<float> d_R, d_hdr, d_hdrJ, d_hdrJm, d_bhr_uw, d_bhr_dw, d_scratch, d_Rsurf, d_albedo_spec;
+  float *d_T = nullptr;                   // d_R + nVza nS S (one buffer)
+  MomDevBuf<double> d_cos, d_sin;
+  MomDevBuf<float> d_smtab;               // N <= 4: the three stream-pair tables of the lane-per-point kernel
+  MomDevBuf<float> d_smpart;              // ... and the per-moment terms of R_SFI / T_SFI of its (point, moment) form
+  MomDevBuf<int> d_node, d_nd;            // d_nd: ndoubl per layer for the wave-per-point kernel
   bool pack = true;                       // MOM_OPT_SMALL_N = 1 (2: one point per wavefront)
   bool small_n = true;                    // MOM_OPT_SMALL_N: 4 < N <= 32 on the wave-per-point kernels (mom_wave.hip, Float32 build)
   int Nz = 0, K = 0, M = 0, nVza = 0, surf_kind = 0, G = 1024;
@@ -234,16 +216,16 @@ int momf_create(momf_scene **out, int device, hipStream_t stream, int N, int nS,
   const int Nm = s->Nmax = strip_pad_f(N);
   s->lds = N <= 64;
   FCHK(s, hipSetDevice(device));
-  FCHK(s, dmallocf(&s->d_mu, Nm));
-  FCHK(s, dmallocf(&s->d_wt, Nm));
-  FCHK(s, dmallocf(&s->d_sg, Nm));
+  FCHK(s, s->d_mu.renew(Nm));
+  FCHK(s, s->d_wt.renew(Nm));
+  FCHK(s, s->d_sg.renew(Nm));
   for (int k = 0; k < 6; ++k) {
     const size_t per = (k < 4) ? (size_t)comp_pitch(Nm) * Nm : (size_t)Nm;
-    FCHK(s, dmallocf(&s->comp[k], per * S * max_m));
+    FCHK(s, s->comp[k].renew(per * S * max_m));
     FCHK(s, hipMemsetAsync(s->comp[k], 0, per * S * max_m * sizeof(float), stream));
   }
   const size_t scr = (size_t)s->G * kGenericBufs * mat_elems(Nm) + (size_t)ld_for(Nm) * np_for(Nm);
-  FCHK(s, dmallocf(&s->d_scratch, scr));
+  FCHK(s, s->d_scratch.renew(scr));
   FCHK(s, hipMemsetAsync(s->d_scratch, 0, scr * sizeof(float), stream));
   for (int k = 0; k < 4; ++k) FCHK(s, hipEventCreate(&s->ev[k]));
   FCHK(s, hipStreamSynchronize(stream));
@@ -253,18 +235,8 @@ int momf_create(momf_scene **out, int device, hipStream_t stream, int N, int nS,
 void momf_destroy(momf_scene *s) {
   if (!s) return;
   momf_destroy(s->sub);
-  auto fr = [](void *p) { if (p) (void)hipFree(p); };
-  fr(s->d_mu); fr(s->d_wt); fr(s->d_sg);
-  for (int k = 0; k < 6; ++k) fr(s->comp[k]);
-  fr(s->d_tau); fr(s->d_varpi); fr(s->d_zw); fr(s->d_tau_sum); fr(s->d_Zpp); fr(s->d_Zmp); fr(s->d_R); fr(s->d_hdr);
-  fr(s->d_hdrJ); fr(s->d_hdrJm); fr(s->d_bhr_uw); fr(s->d_bhr_dw); fr(s->d_scratch); fr(s->d_Rsurf); fr(s->d_albedo_spec);
-  fr(s->d_cos); fr(s->d_sin); fr(s->d_node); fr(s->d_nd); fr(s->d_smtab); fr(s->d_smpart);
-  for (int k = 0; k < 6; ++k) { fr(s->op_added[k]); fr(s->op_surf[k]); fr(s->op_comp[k]); }
-  for (int k = 0; k < 4; ++k) fr(s->op_vec[k]);
-  fr(s->op_Z[0]); fr(s->op_Z[1]);
-  for (int k = 0; k < 4; ++k) fr(s->blas_buf[k]);
   for (int k = 0; k < 4; ++k) if (s->ev[k]) (void)hipEventDestroy(s->ev[k]);
-  delete s;
+  delete s;  // frees the scene's device buffers (MomDevBuf members)
 }
 
 void momf_set_options(momf_scene *s, int inv_mode, int force_generic, int sweep, int small_n, int m0, int pad, int w4) {
@@ -313,26 +285,14 @@ static int apply_streams(momf_scene *s) {
   return MOM_OK;
 }
 
-template <class T, class U>
-static int upload_f(momf_scene *s, T **dst, const U *src, size_t n) {
-  if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
-  FCHK(s, dmallocf(dst, n));
-  std::vector<T> v(n);
-  for (size_t i = 0; i < n; ++i) v[i] = (T)src[i];
-  FCHK(s, hipMemcpyAsync(*dst, v.data(), n * sizeof(T), hipMemcpyHostToDevice, s->stream));
-  FCHK(s, hipStreamSynchronize(s->stream));
-  return MOM_OK;
-}
-
 // the layer optics assembled on the device in Float64 (mom_scene_set_optics): rounded to the scene's Float32 there
 __global__ void k_cvt_d2f(const double *src, float *dst, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] = (float)src[i];
 }
-static int convert_f(momf_scene *s, float **dst, const double *d_src, size_t n) {
-  if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
-  FCHK(s, dmallocf(dst, n));
-  hipLaunchKernelGGL(k_cvt_d2f, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, d_src, *dst, n);
+static int convert_f(momf_scene *s, MomDevBuf<float> &dst, const double *d_src, size_t n) {
+  FCHK(s, dst.renew(n));
+  hipLaunchKernelGGL(k_cvt_d2f, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, d_src, dst.get(), n);
   FCHK(s, hipGetLastError());
   return MOM_OK;
 }
@@ -364,35 +324,34 @@ static int scene_set_impl(momf_scene *s, int Nz, int K, int M, const double *tau
   const int N = s->N, Nu = s->Nu, nS = s->nS;
   const size_t S = s->S, NN = (size_t)N * N;
   if (dev_layers) {
-    if ((rc = convert_f(s, &s->d_tau, tau, S * Nz))) return rc;
-    if ((rc = convert_f(s, &s->d_varpi, varpi, S * Nz))) return rc;
-    if ((rc = convert_f(s, &s->d_zw, zw, (size_t)K * S * Nz))) return rc;
-    if ((rc = convert_f(s, &s->d_tau_sum, tau_sum, S * (Nz + 1)))) return rc;
+    if ((rc = convert_f(s, s->d_tau, tau, S * Nz))) return rc;
+    if ((rc = convert_f(s, s->d_varpi, varpi, S * Nz))) return rc;
+    if ((rc = convert_f(s, s->d_zw, zw, (size_t)K * S * Nz))) return rc;
+    if ((rc = convert_f(s, s->d_tau_sum, tau_sum, S * (Nz + 1)))) return rc;
   } else {
-    if ((rc = upload_f(s, &s->d_tau, tau, S * Nz))) return rc;
-    if ((rc = upload_f(s, &s->d_varpi, varpi, S * Nz))) return rc;
-    if ((rc = upload_f(s, &s->d_zw, zw, (size_t)K * S * Nz))) return rc;
-    if ((rc = upload_f(s, &s->d_tau_sum, tau_sum, S * (Nz + 1)))) return rc;
+    FCHK(s, mom_upload_as(s->d_tau, tau, S * Nz, s->stream));
+    FCHK(s, mom_upload_as(s->d_varpi, varpi, S * Nz, s->stream));
+    FCHK(s, mom_upload_as(s->d_zw, zw, (size_t)K * S * Nz, s->stream));
+    FCHK(s, mom_upload_as(s->d_tau_sum, tau_sum, S * (Nz + 1), s->stream));
   }
   if (N == Nu) {
-    if ((rc = upload_f(s, &s->d_Zpp, Zpp, NN * K * M))) return rc;
-    if ((rc = upload_f(s, &s->d_Zmp, Zmp, NN * K * M))) return rc;
+    FCHK(s, mom_upload_as(s->d_Zpp, Zpp, NN * K * M, s->stream));
+    FCHK(s, mom_upload_as(s->d_Zmp, Zmp, NN * K * M, s->stream));
   } else {
-    const std::vector<double> zp = pad_blocks_f(Zpp, Nu, N, (size_t)K * M), zm = pad_blocks_f(Zmp, Nu, N, (size_t)K * M);
-    if ((rc = upload_f(s, &s->d_Zpp, zp.data(), zp.size()))) return rc;
-    if ((rc = upload_f(s, &s->d_Zmp, zm.data(), zm.size()))) return rc;
+    const std::vector<double> zp = mom_pad_blocks(Zpp, Nu, N, (size_t)K * M), zm = mom_pad_blocks(Zmp, Nu, N, (size_t)K * M);
+    FCHK(s, mom_upload_as(s->d_Zpp, zp.data(), zp.size(), s->stream));
+    FCHK(s, mom_upload_as(s->d_Zmp, zm.data(), zm.size(), s->stream));
   }
-  if ((rc = upload_f(s, &s->d_node, node, (size_t)nVza))) return rc;
-  if ((rc = upload_f(s, &s->d_cos, cos_mphi, (size_t)nVza * M))) return rc;
-  if ((rc = upload_f(s, &s->d_sin, sin_mphi, (size_t)nVza * M))) return rc;
-  auto renew = [&](float **p, size_t n) -> hipError_t { if (*p) { (void)hipFree(*p); *p = nullptr; } return dmallocf(p, n); };
+  FCHK(s, mom_upload_as(s->d_node, node, (size_t)nVza, s->stream));
+  FCHK(s, mom_upload_as(s->d_cos, cos_mphi, (size_t)nVza * M, s->stream));
+  FCHK(s, mom_upload_as(s->d_sin, sin_mphi, (size_t)nVza * M, s->stream));
   const size_t nout = (size_t)nVza * nS * S;
-  FCHK(s, renew(&s->d_R, 2 * nout));
+  FCHK(s, s->d_R.renew(2 * nout));
   s->d_T = s->d_R + nout;
-  FCHK(s, renew(&s->d_hdr, nout));
-  FCHK(s, renew(&s->d_hdrJ, (size_t)N * S));
-  FCHK(s, renew(&s->d_bhr_uw, (size_t)nS * S));
-  FCHK(s, renew(&s->d_bhr_dw, (size_t)nS * S));
+  FCHK(s, s->d_hdr.renew(nout));
+  FCHK(s, s->d_hdrJ.renew((size_t)N * S));
+  FCHK(s, s->d_bhr_uw.renew((size_t)nS * S));
+  FCHK(s, s->d_bhr_dw.renew((size_t)nS * S));
   s->Nz = Nz; s->K = K; s->M = M; s->nVza = nVza; s->albedo = (float)albedo; s->surf_kind = 0;
   s->nd.assign(ndoubl, ndoubl + Nz);
   s->iface.assign(iface, iface + Nz);
@@ -456,13 +415,12 @@ int momf_scene_set_surface(momf_scene *s, int kind, int M, const double *Rsurf, 
   int rc;
   if (kind == 1) {
     if (N == Nu) {
-      if ((rc = upload_f(s, &s->d_Rsurf, Rsurf, (size_t)N * N * M))) return rc;
+      FCHK(s, mom_upload_as(s->d_Rsurf, Rsurf, (size_t)N * N * M, s->stream));
     } else {
-      const std::vector<double> rp = pad_blocks_f(Rsurf, Nu, N, (size_t)M);
-      if ((rc = upload_f(s, &s->d_Rsurf, rp.data(), rp.size()))) return rc;
+      const std::vector<double> rp = mom_pad_blocks(Rsurf, Nu, N, (size_t)M);
+      FCHK(s, mom_upload_as(s->d_Rsurf, rp.data(), rp.size(), s->stream));
     }
-    if (s->d_hdrJm) { (void)hipFree(s->d_hdrJm); s->d_hdrJm = nullptr; }
-    FCHK(s, dmallocf(&s->d_hdrJm, (size_t)N * s->S * M));
+    FCHK(s, s->d_hdrJm.renew((size_t)N * s->S * M));
     if (s->m_first) {
       // moment 0 runs on the (I,Q) sub-scene: its surface matrix must not couple (I,Q) with (U,V) either
       const int nS0 = s->sub->nS, N0 = s->sub->Nu;
@@ -481,7 +439,7 @@ int momf_scene_set_surface(momf_scene *s, int kind, int M, const double *Rsurf, 
       if ((rc = momf_scene_set_surface(s->sub, 1, 1, r0.data(), nullptr))) { s->err = s->sub->err; return rc; }
     }
   } else if (kind == 2) {
-    if ((rc = upload_f(s, &s->d_albedo_spec, albedo_spec, (size_t)s->S))) return rc;
+    FCHK(s, mom_upload_as(s->d_albedo_spec, albedo_spec, (size_t)s->S, s->stream));
     if (s->m_first && (rc = momf_scene_set_surface(s->sub, 2, 1, nullptr, albedo_spec))) { s->err = s->sub->err; return rc; }
   } else if (s->m_first) {
     s->sub->surf_kind = 0;
@@ -503,7 +461,7 @@ static bool wave_applies_f32(const momf_scene *s) {
   return s->iface[s->Nz - 1] == 3;
 }
 static int rt_run_wave_f32(momf_scene *s) {
-  if (!s->d_nd) FCHK(s, hipMalloc((void **)&s->d_nd, sizeof(int) * kMaxSweepLayers * 4));
+  if (!s->d_nd) FCHK(s, s->d_nd.renew(kMaxSweepLayers * 4));
   if (s->Nz > kMaxSweepLayers * 4) { s->err = "Float32 wave sweep: too many layers"; return MOM_EINVAL; }
   FCHK(s, hipMemcpyAsync(s->d_nd, s->nd.data(), sizeof(int) * s->Nz, hipMemcpyHostToDevice, s->stream));
   MomWaveSweepArgsF a{};
@@ -532,8 +490,8 @@ hipError_t momsmf_launch_sweep(const void *args, int N, hipStream_t st);  // mom
 // N <= 4: one spectral point per lane, the whole run in ONE launch (the Float64 path: rt_run_small in momcore.hip)
 static int rt_run_small_f32(momf_scene *s) {
   const int N = s->N, Nz = s->Nz;
-  if (!s->d_smtab) FCHK(s, hipMalloc((void **)&s->d_smtab, sizeof(float) * 48));
-  if (!s->d_nd) FCHK(s, hipMalloc((void **)&s->d_nd, sizeof(int) * kMaxSweepLayers * 4));
+  if (!s->d_smtab) FCHK(s, s->d_smtab.renew(48));
+  if (!s->d_nd) FCHK(s, s->d_nd.renew(kMaxSweepLayers * 4));
   if (2 * Nz > kMaxSweepLayers * 4) { s->err = "Float32 lane sweep: too many layers"; return MOM_EINVAL; }
   float tab[48] = {0};
   for (int j = 0; j < N; ++j)
@@ -561,11 +519,7 @@ static int rt_run_small_f32(momf_scene *s) {
   a.info = s->d_info;
   if (a.M > 1 && s->pack) {  // one (point, moment) per lane; MOM_OPT_SMALL_N = 2: one point per lane
     const size_t need = (size_t)a.M * 2 * a.nVza * a.nS * a.S;
-    if (need > s->smpart_cap) {
-      if (s->d_smpart) { FCHK(s, hipStreamSynchronize(s->stream)); (void)hipFree(s->d_smpart); s->d_smpart = nullptr; s->smpart_cap = 0; }
-      FCHK(s, hipMalloc((void **)&s->d_smpart, need * sizeof(float)));
-      s->smpart_cap = need;
-    }
+    FCHK(s, s->d_smpart.reserve(need, s->stream));
     a.part = s->d_smpart;
   }
   FCHK(s, hipEventRecord(s->ev[0], s->stream));
@@ -706,35 +660,28 @@ int momf_timers(momf_scene *s, double *ms, int *launches) {
 }
 
 // batch_inv!(X, A) / A ⊠ B on a Float32 handle: Float64 host arrays at the ABI, f32 on the device; the device buffers are a
-// grow-only workspace of the handle (no hipMalloc / hipFree per call, nothing to leak on an early return)
+// grow-only workspace of the handle (no allocation per call, nothing to leak on an early return)
 static int up_vec(momf_scene *s, float *dst, const double *src, size_t n);
-static int blas_ws(momf_scene *s, int slot, size_t count, float **out) {
-  if (s->blas_cap[slot] < count) {
-    if (s->blas_buf[slot]) { FCHK(s, hipStreamSynchronize(s->stream)); (void)hipFree(s->blas_buf[slot]); s->blas_buf[slot] = nullptr; s->blas_cap[slot] = 0; }
-    FCHK(s, dmallocf(&s->blas_buf[slot], count));
-    s->blas_cap[slot] = count;
-  }
-  *out = s->blas_buf[slot];
-  return MOM_OK;
-}
 int momf_blas(momf_scene *s, int n, int batch, const double *A, const double *B, double *C, bool inv) {
   FCHK(s, hipSetDevice(s->device));
   const size_t cnt = (size_t)n * n * batch;
-  float *dA = nullptr, *dB = nullptr, *dC = nullptr, *scr = nullptr;
+  MomDevBuf<float> &dA = s->blas_buf[0], &dB = s->blas_buf[1], &dC = s->blas_buf[2], &scr = s->blas_buf[3];
   int rc;
-  if ((rc = blas_ws(s, 0, cnt, &dA)) || (rc = blas_ws(s, 2, cnt, &dC))) return rc;
+  FCHK(s, dA.reserve(cnt, s->stream));
+  FCHK(s, dC.reserve(cnt, s->stream));
   if ((rc = up_vec(s, dA, A, cnt))) return rc;
   if (!inv) {
-    if ((rc = blas_ws(s, 1, cnt, &dB)) || (rc = up_vec(s, dB, B, cnt))) return rc;
+    FCHK(s, dB.reserve(cnt, s->stream));
+    if ((rc = up_vec(s, dB, B, cnt))) return rc;
   }
   const bool lds = n <= 64 && !s->force_generic;
   const int grid = lds ? batch : std::min(batch, 1024);
   if (!lds) {
     const size_t scn = (size_t)grid * kGenericBufs * mat_elems(n) + (size_t)ld_for(n) * np_for(n);
-    if ((rc = blas_ws(s, 3, scn, &scr))) return rc;
+    FCHK(s, scr.reserve(scn, s->stream));
     FCHK(s, hipMemsetAsync(scr, 0, scn * sizeof(float), s->stream));
   }
-  BlasArgsF a{n, batch, dA, dB, dC, scr, s->d_info};
+  BlasArgsF a{n, batch, dA, inv ? nullptr : dB.get(), dC, lds ? nullptr : scr.get(), s->d_info};
   const size_t sm = lds_bytes(n, lds);
   if (inv) {
     FCHK(s, mom_launch_ldsm(MOM_LDSM(k_batch_inv_f32), lds, grid, kThreads, sm, s->stream, a));
@@ -756,14 +703,14 @@ static int op_begin(momf_scene *s, DevStreams *q) {
     const size_t NN = (size_t)N * N;
     for (int k = 0; k < 6; ++k) {
       const size_t per = ((k < 4) ? NN : (size_t)N) * s->S;
-      FCHK(s, dmallocf(&s->op_added[k], per));
-      FCHK(s, dmallocf(&s->op_surf[k], per));
-      FCHK(s, dmallocf(&s->op_comp[k], per));
+      FCHK(s, s->op_added[k].renew(per));
+      FCHK(s, s->op_surf[k].renew(per));
+      FCHK(s, s->op_comp[k].renew(per));
       FCHK(s, hipMemsetAsync(s->op_added[k], 0, per * sizeof(float), s->stream));
       FCHK(s, hipMemsetAsync(s->op_surf[k], 0, per * sizeof(float), s->stream));
       FCHK(s, hipMemsetAsync(s->op_comp[k], 0, per * sizeof(float), s->stream));
     }
-    for (int k = 0; k < 4; ++k) FCHK(s, dmallocf(&s->op_vec[k], (size_t)s->S));
+    for (int k = 0; k < 4; ++k) FCHK(s, s->op_vec[k].renew((size_t)s->S));
     s->op_ready = true;
   }
   // the caller's streams (a scene on this handle may have padded the device copies BEHIND entry Nu - 1; rewritten here anyway)
@@ -797,12 +744,7 @@ int momf_op_elemental(momf_scene *s, int m, int nd, const double *tau_sum, const
   int rc;
   if ((rc = op_begin(s, &a.q))) return rc;
   const size_t zc = (size_t)s->Nu * s->Nu * z_batch;
-  if (zc > s->op_Zcap) {
-    if (s->op_Z[0]) { (void)hipFree(s->op_Z[0]); (void)hipFree(s->op_Z[1]); s->op_Z[0] = s->op_Z[1] = nullptr; }
-    FCHK(s, dmallocf(&s->op_Z[0], zc));
-    FCHK(s, dmallocf(&s->op_Z[1], zc));
-    s->op_Zcap = zc;
-  }
+  for (int k = 0; k < 2; ++k) FCHK(s, s->op_Z[k].reserve(zc, s->stream));
   if ((rc = up_vec(s, s->op_vec[0], tau_sum, s->S)) || (rc = up_vec(s, s->op_vec[1], dtau, s->S)) ||
       (rc = up_vec(s, s->op_vec[2], varpi, s->S)) || (rc = up_vec(s, s->op_Z[0], Zpp, zc)) || (rc = up_vec(s, s->op_Z[1], Zmp, zc)))
     return rc;
