@@ -20,7 +20,7 @@
 #include <type_traits>
 
 // The whole device library is compiled once per workgroup shape: MOM_WAVES wavefronts per workgroup inside
-// namespace MOM_NS (momcore.hip: 8 waves, namespace mom; momcore_w4.hip: 4 waves, namespace mom4).
+// namespace MOM_NS (momcore.hip, mom_scene.hip: 8 waves, namespace mom; momcore_w4.hip: 4 waves, namespace mom4).
 #ifndef MOM_NS
 #define MOM_NS mom
 #endif

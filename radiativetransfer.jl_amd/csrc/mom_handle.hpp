@@ -1,0 +1,158 @@
+// mom_handle.hpp -- the handle behind mom_t and what more than one unit of the host driver needs of it (momcore.hip,
+// mom_scene.hip, mom_optics.hip, mom_rrs_api.hip, mom_comm.hip).  Float64 driver only: include it with the default MOM_NS.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "momcore.h"
+
+#include "mom_diag.hpp"
+#include "mom_entry.hpp"
+#include "mom_host.hpp"
+
+namespace momr { struct State; }  // mom_rrs.hpp
+
+struct mom_handle {
+  int device = 0, N = 0, nS = 0, S = 0, M = 0;
+  int dtype = 0;              // 0 = Float64, 1 = Float32 (scene-level path only, momcore_f32.hip)
+  momf_scene *f32 = nullptr;
+  bool lds_mode = true;
+  int opt_inverse = 0, opt_force_generic = 0;
+  hipStream_t stream = nullptr;
+  MomDevBuf<double> d_mu, d_wt, d_sg;
+  mom::DevStreams q{};
+  bool streams_set = false;
+  std::vector<double> h_mu, h_wt;
+  int strict = 1;
+  MomDevBuf<double> added[6], surf[6], comp[6];
+  bool op_layers = false;     // added / surface layers of the operator-level API: allocated on first use
+  bool comp_pitched = false;  // composite matrix blocks hold scene-level (row-pitched) state
+  bool comp_on_chip = false;  // the last mom_rt_run kept the composite layer in registers (lane / wave kernels)
+  MomDevBuf<double> d_post;   // operator-level mom_postprocess: gathered J0- | J0+ rows [2][nVza*nS*S]
+  // RCCL communicator (mom_comm_init); the library is dlopen'ed on first use
+  void *comm = nullptr;
+  int comm_rank = 0, comm_size = 1;
+  MomDevBuf<double> d_gather;
+  MomDevBuf<double> d_rrs_send;  // packed owned spectra of the RRS run: send buffer of mom_allgather_rrs_device
+  // device-side layer optics (mom_absorption_* / mom_voigt_tau_abs / mom_scene_set_optics)
+  MomDevBuf<double> d_tau_abs, d_grid, d_lines, d_tau_rayl, d_layer_max, d_aer;
+  MomDevBuf<int> d_aer_mode;
+  int abs_Nz = 0;
+  size_t lines_per = 0;   // lines ONE layer's block of d_lines has room for (the stride of its arrays, not the size of the allocation)
+  int lines_nz = 1;       // layers held in d_lines: arrays [nu | gamma_d | y | S][lines_nz][lines_per], then the two window arrays as ints
+  MomDevBuf<double> d_prof;  // per-layer scalars of mom_voigt_tau_abs_profile
+  MomDevBuf<double> d_vec[4];  // S-length temporaries (tau_sum, dtau, varpi, expk)
+  MomDevBuf<double> d_Zop[2];
+  // scene
+  int Nz = 0, K = 0, nVza = 0, scene_M = 0;
+  MomDevBuf<double> d_tau, d_varpi, d_zw, d_Zpp, d_Zmp, d_tau_sum, d_cos, d_sin, d_R, d_hdr, d_hdrJ, d_bhr_uw, d_bhr_dw;
+  double *d_T = nullptr;  // d_R + nVza nS S: R_SFI || T_SFI are ONE buffer (the all-gather's send buffer as it stands)
+  MomDevBuf<int> d_node;
+  std::vector<int> nd, iface;
+  double albedo = 0.0;
+  bool scene_set = false;
+  // m = 0 reduction (see mom_scene_set)
+  int opt_m0 = 1;
+  int opt_w4 = 1;
+  int opt_stagger = 1;
+  int opt_rrs_kernels = -1;  // MOM_OPT_RRS_KERNELS (-1: momr::KOPT_DEFAULT)
+  int opt_overlap = 1;       // MOM_OPT_OVERLAP: the m = 0 sub-problem on a second (high-priority) stream of the handle
+  hipStream_t stream2 = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_go = nullptr;
+  int surf_kind = 0;         // 0 Lambertian scalar, 1 BRDF matrices, 2 Lambertian Legendre (mom_scene_set_surface)
+  // ForwardDiff.Dual run (mom_dual.hip): partials of the scene's inputs and of the outputs, the operator workspace
+  int dual_P = 0;
+  bool dual_ran = false;
+  MomDevBuf<double> d_dual_in[8];  // dtau, dvarpi, dzw, dZpp, dZmp, dalbedo, dRsurf, dalbedo_spec
+  MomDevBuf<double> d_dual_out, d_dual_ts;  // dR | dT [nVza,nS,S,P] x 2; d tau_sum [S,Nz+1,P]
+  MomDevBuf<char> dual_work;
+  size_t opt_dual_budget = 0;  // MOM_OPT_DUAL_WORKSPACE_MB (0: 60 % of the free HBM at the time of the run)
+  MomDevBuf<double> d_Rsurf, d_Rsurf0, d_albedo_spec, d_hdrJm;
+  int opt_sweep = 1;       // one launch walks all layers of a unit (LayerArgs::Nz_sweep)
+  MomDevBuf<double> comp_top[6];  // mom_rt_run_multisensor: composite state of the slab above a sensor
+  MomDevBuf<double> d_msJ[2];     // interface fields dwJ, uwJ [Nk,S,M]
+  std::vector<MomDevBuf<double>> ms_comp;  // multi-sensor: 6 arrays per composite set (snapshot of the top slab + bottom slab per sensor)
+  MomDevBuf<double> d_ms_out;  // [2][nVza*nS*S*nSensors]
+  int opt_pad = 1;         // scene-level path: pad the operator edge to the next strip-chained kernel size (strip_pad)
+  int opt_lean = 3;        // N = 36, 40: 3 = the quad-block image (one wavefront per unit, 4 x 4 x 4 MFMA blocks, four units per CU;
+                           // mom_q4.hpp), 1 = the four-wave lean strip image (three workgroups per CU), 2 = the six-wave one (half-strip
+                           // doubling chains, two per CU: measured slower, profiles/r05_mid_ab.txt), each followed by the full image's
+                           // resume launch; 0 = the full image only
+  MomDevBuf<int> d_resume; // resume[unit] of the lean image (mom_lean.hpp)
+  int opt_strip2 = 1;       // MOM_OPT_STRIP2: N = 52, 56, 60 on the two-buffer 4-wave image first (mom_strip2.hpp), the 8-wave image resumes
+  MomDevBuf<int> d_resume2; // its resume[unit] (a table of its own: the m = 0 sub-problem's lean launch may run at the same time)
+  size_t resume2_units = 0;  // units and layers of the image's last launch (mom_strip2_resumed)
+  int resume2_nz = 0;
+  int opt_strip2_sched = 1;  // MOM_OPT_STRIP2_SCHED: bit 0 = shared unit queue, bit 1 = asymmetric chain priority (mom_strip2.hpp; one
+                             // kernel per value); the priority measured slower on top of the queue (profiles/r08_C2_ab.txt): off
+  MomDevBuf<int> d_sched2;   // LayerArgs::sched of the two-buffer image: zeroed on the stream before each of its launches
+  int Nk = 0;              // operator edge the scene-level kernels of the full problem run with (>= N)
+  mom::DevStreams qk{};         // q with N = Nk
+  int opt_small = 1;       // N <= 4: lane-per-point sweep kernel (mom_small.hip)
+  MomDevBuf<double> d_smtab;  // F1 | F2 | SI tables [3][N,N]
+  MomDevBuf<double> d_smpart; // N <= 4, one (point, moment) per lane: the per-moment terms of R_SFI / T_SFI [M][2][nVza,nS,S]
+  MomDevBuf<int> d_ndif;      // ndoubl | iface [2][Nz]
+  bool red0 = false;
+  int N0 = 0, nS0 = 0;
+  mom::DevStreams q0{};
+  MomDevBuf<double> d_mu0, d_wt0, d_sg0, d_Zpp0, d_Zmp0, d_hdrJ0, d_scratch0;
+  MomDevBuf<double> comp0[6];
+  MomDevBuf<double> d_scratch;
+  int G = 0;  // workgroups in generic mode
+  int num_cu = 256;
+  MomDevBuf<int> d_info;
+  hipEvent_t ev[4] = {};
+  hipEvent_t ev_voigt[2] = {};  // mom_voigt_tau_abs_profile's timing pair (created on first use, owned by the handle)
+  std::vector<hipEvent_t> ev_full, ev_red;  // start/stop pairs around each full-problem / reduced layer launch
+  int launches = 0, launches_full = 0, launches_red = 0;
+  // rotational-Raman path (mom_rrs.hip): the persistent AddedLayerRS / CompositeLayerRS state and the scene's Raman inputs
+  momr::State *rrs = nullptr;
+  MomDevBuf<double> d_fscatt, d_Zr[2];  // fScattRayleigh [S,Nz]; Raman phase matrices [N,N,M] x2
+  MomDevBuf<double> d_rrs_op[8];        // operator-level inputs: tau_sum, dtau, varpi, fscatt [S]; Z x4 [N,N]
+  bool rrs_scene = false;
+  double rrs_ms = 0.0;
+  // grow-only device workspace of the operator-level batched entry points (no allocation per call, no leak on an error
+  // return): bytes, viewed as the element type each call needs
+  MomDevBuf<char> ws[4];
+  // resident HITRAN table + TIPS splines of one absorber (mom_absorption_set_lines)
+  MomLineTable lt{};
+  MomDevBuf<double> d_lt;   // one allocation behind lt's double arrays
+  MomDevBuf<int> d_lt_i;    // iso index [nLines] | knots per isotopologue [nIso] | unsorted flag [1]
+  double lt_Tmin = 0.0, lt_Tmax = 0.0;
+  std::string err;
+};
+
+// what the units share besides the handle; internal to libmomcore.so, not part of the C ABI
+#pragma GCC visibility push(hidden)
+int fail(mom_t *h, int code, const char *msg);  // momcore.hip: error text -> the handle (if any) and the thread's string; returns code
+int check_info(mom_t *h);                       // momcore.hip: the zero-pivot report of the handle's kernels (synchronises)
+// momcore.hip: one launch of k_combine<lds> for mom_rt_run_multisensor (why not from mom_scene.hip: see its definition)
+hipError_t mom_launch_combine(const mom::InterArgs &a, bool lds, int grid, size_t smem, hipStream_t st);
+// mom_scene.hip: everything of a scene that does not depend on how the layer optics reach the device: phase-matrix bases, view
+// geometry, output buffers, the m = 0 reduction
+int scene_common(mom_t *h, int Nz, int K, int M, const double *Zpp, const double *Zmp, double albedo, int nVza,
+                 const int *node_1based, const double *cos_mphi, const double *sin_mphi);
+// mom_comm.hip: set once RCCL is loaded (mom_comm_init); the maximum over the ranks of `count` doubles on the device, in place
+extern void (*g_rccl_destroy)(void *);
+int mom_comm_allreduce_max(mom_t *h, double *d_buf, size_t count);
+#pragma GCC visibility pop
+
+#define HIPCHK(h, call)                                                                            \
+  do {                                                                                             \
+    hipError_t e__ = (call);                                                                       \
+    if (e__ != hipSuccess) {                                                                       \
+      char buf__[512];                                                                             \
+      snprintf(buf__, sizeof buf__, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
+      return fail(h, MOM_EHIP, buf__);                                                             \
+    }                                                                                              \
+  } while (0)
+
+#define F64_ONLY(h, name)                                                                                 \
+  if ((h) && (h)->dtype != 0)                                                                             \
+  return fail(h, MOM_EINVAL, name ": not available on a Float32 (dtype = 1) handle (scene-level path only)")

@@ -178,7 +178,7 @@ struct MomDualScene {
 size_t momd_bytes_per_unit(int N, int P);
 int momd_run(const MomDualScene &sc, std::string *err);   // 0 ok, 1 unsupported, 2 HIP error (text in *err)
 
-// argument blocks of the single-launch sweep kernels, shared by the launching translation unit (momcore.hip) and the
+// argument blocks of the single-launch sweep kernels, shared by the launching translation unit (mom_scene.hip) and the
 // kernels' own (mom_small.hip: momsm::k_sweep; mom_wave.hip: momw::k_wsweep)
 template <class Real>
 struct MomSmallSweepArgsT {
@@ -223,3 +223,53 @@ struct MomWaveSweepArgsT {
 };
 using MomWaveSweepArgs = MomWaveSweepArgsT<double>;   // Float64 wave-per-point sweep (mom_wave.hip)
 using MomWaveSweepArgsF = MomWaveSweepArgsT<float>;   // Float32 build of the same kernels (mom_wave.hip with -DMOMW_FLOAT)
+
+// ---- entry points between the translation units: declarations only (no device code, nothing that depends on MOM_NS / MOM_REAL).
+// Every unit that defines one of them includes this header, so a definition is checked against what its callers see.
+// momcore_w4.hip: the same kernels built for 4-wave workgroups (2 workgroups per CU when the operators are
+// small enough for two LDS images: the m = 0 (I,Q) sub-problem of N = 60 is N0 = 40 -> 77 KB).
+size_t mom4_lds_bytes(int N, bool lds_mats);
+hipError_t mom4_launch_layer(const void *layer_args, int iface, bool lds, int grid, size_t smem, hipStream_t st);
+// momcore_gen.hip: the general layer kernels k_layer<LDSM, IFACE> of the 8-wave build
+hipError_t mom_gen_launch_layer(const void *layer_args, int iface, bool lds, int grid, size_t smem, hipStream_t st);
+// the per-size images (strip-chained, lean, two-buffer, quad-block): mom_images.hpp
+hipError_t mom4_launch_surface(const void *surf_args, bool lds, int grid, size_t smem, hipStream_t st);
+int mom4_generic_bufs_elems(int N);
+// momcore_f32.hip: the Float32 build of the scene-level path (dtype = 1)
+struct momf_scene;
+int momf_create(momf_scene **out, int device, hipStream_t stream, int N, int nS, int S, int max_m, int *d_info);
+void momf_destroy(momf_scene *s);
+const char *momf_error(const momf_scene *s);
+void momf_set_options(momf_scene *s, int inv_mode, int force_generic, int sweep, int small_n, int m0, int pad, int w4);
+int momf_set_streams(momf_scene *s, const double *mu, const double *wt, const double *sg, int imu0, double mu0, const double *I0,
+                     const double *D, int regular);
+int momf_scene_set(momf_scene *s, int Nz, int K, int M, const double *tau, const double *varpi, const double *zw,
+                   const double *Zpp, const double *Zmp, const int *ndoubl, const int *iface, const double *tau_sum,
+                   double albedo, int nVza, const int *node, const double *cos_mphi, const double *sin_mphi);
+int momf_scene_set_dev(momf_scene *s, int Nz, int K, int M, const double *d_tau, const double *d_varpi, const double *d_zw,
+                       const double *Zpp, const double *Zmp, const int *ndoubl, const int *iface, const double *d_tau_sum,
+                       double albedo, int nVza, const int *node, const double *cos_mphi, const double *sin_mphi);
+int momf_scene_set_surface(momf_scene *s, int kind, int M, const double *Rsurf, const double *albedo_spec);
+int momf_rt_run(momf_scene *s);
+int momf_get_RT(momf_scene *s, double *R, double *T);
+int momf_get_hdr(momf_scene *s, double *hdr, double *up, double *dw);
+int momf_timers(momf_scene *s, double *ms, int *launches);
+int momf_blas(momf_scene *s, int n, int batch, const double *A, const double *B, double *C, bool inv);
+int momf_op_elemental(momf_scene *s, int m, int nd, const double *tau_sum, const double *dtau, const double *varpi,
+                      const double *Zpp, const double *Zmp, int z_batch);
+int momf_op_doubling(momf_scene *s, int nd, double *expk);
+int momf_op_interaction(momf_scene *s, int iface, int with_surface_layer);
+int momf_op_copy_added_to_composite(momf_scene *s);
+int momf_op_surface_lambertian(momf_scene *s, int m, double albedo, const double *tau_tot);
+int momf_op_upload(momf_scene *s, int which, const double *src);
+int momf_op_download(momf_scene *s, int which, double *dst);
+// mom_small.hip: N <= 4, one spectral point per lane, the whole sweep in one launch
+hipError_t momsm_launch_sweep(const void *args, int N, hipStream_t st);
+hipError_t momsmf_launch_sweep(const void *args, int N, hipStream_t st);  // mom_small.hip built with -DMOMS_FLOAT
+// mom_wave.hip: 4 < N <= 32, one spectral point per wavefront; k_wsweep<2, 8> is an object of its own (mom_wave8.o, -DMOMW_ONLY_KS8)
+hipError_t momw_launch_sweep(const void *args, hipStream_t st);
+hipError_t momw_launch_sweep8(const void *args, hipStream_t st);
+hipError_t momwf_launch_sweep(const void *args, hipStream_t st);  // mom_wave.hip built with -DMOMW_FLOAT
+hipError_t momwf_launch_sweep8(const void *args, hipStream_t st);
+// mom_rrs.hip built with -DMOMR_BIG_TU: the one launcher of the 3 x 3- and 4 x 4-tile RRS images (32 < N <= 64)
+hipError_t momr_big_launch(int which, int nt, int v0, int v1, unsigned grid, void *stream, const void *args, int iface);

@@ -1,7 +1,7 @@
 // mom_ops.hpp -- the operator-level kernels (include/momcore.h: mom_elemental, mom_doubling, mom_interaction,
-// mom_surface_lambertian): one reference operator per launch on [N,N,S] arrays in the reference's own layout, for per-op
-// parity tests and for a host that keeps its layer loop.  Compiled once per real type: namespace mom (Float64, momcore.hip)
-// and momf (Float32, momcore_f32.hip -- the reference's float_type = Float32 runs through every operator,
+// mom_surface_lambertian, mom_batch_inv, mom_batched_mul): one reference operator per launch on [N,N,S] arrays in the reference's
+// own layout, for per-op parity tests and for a host that keeps its layer loop.  Compiled once per real type: namespace mom
+// (Float64, momcore.hip) and momf (Float32, momcore_f32.hip -- the reference's float_type = Float32 runs through every operator,
 // parameters_from_yaml.jl:160, gpu_batched.jl:45-58).
 #pragma once
 #include "mom_entry.hpp"
@@ -123,6 +123,54 @@ __global__ void k_op_surface_fill(DevStreams q, int S, int m, real albedo, const
     const bool in_sun = (i >= i_start) && (i < i_end);
     j0p[(size_t)N * pt + i] = (m == 0) ? (in_sun ? q.I0[i - i_start] : 0.0) * att : 0.0;
     j0m[(size_t)N * pt + i] = (m == 0 && (i % n == 0)) ? (q.mu0 * (rho * q.I0[0])) * att : 0.0;
+  }
+}
+
+// batch_inv! / batched_mul on [N,N,S] arrays (gpu_batched.jl:45-58, 90-97: cuBLAS getrf/getri, gemm; mom_batch_inv / mom_batched_mul)
+struct BlasArgs {
+  int N, S;
+  const real *A, *B;
+  real *C;
+  real *scratch;
+  int *info;
+};
+
+template <bool LDSM>
+__global__ void __launch_bounds__(kThreads) k_batch_inv(BlasArgs a) {
+  const int N = a.N;
+  Ctx c;
+  make_ctx<LDSM>(c, N, 1, mom_smem, LDSM ? nullptr : a.scratch + (size_t)blockIdx.x * kGenericBufs * mat_elems(N));
+  zero_padding<LDSM>(c);
+  if (threadIdx.x == 0) *c.bad = 0;
+  __syncthreads();
+  const size_t NN = (size_t)N * N;
+  for (size_t pt = blockIdx.x; pt < (size_t)a.S; pt += gridDim.x) {
+    wg_copy_mat(N, c.fd, a.A + NN * pt, N, c.P, c.ld);
+    __syncthreads();
+    if (N <= 64) wg_inverse_reg(N, c.P, c.ld, c.part, c.prow, c.ipiv, c.bad);
+    else wg_inverse(N, c.fd, c.P, c.ld, c.prow, c.pcol, c.rowk, c.ipiv, c.sh, c.bad);
+    wg_copy_mat(N, c.fd, c.P, c.ld, a.C + NN * pt, N);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && *c.bad) atomicMax(a.info, *c.bad);
+}
+
+template <bool LDSM>
+__global__ void __launch_bounds__(kThreads) k_batched_mul(BlasArgs a) {
+  const int N = a.N;
+  Ctx c;
+  make_ctx<LDSM>(c, N, 1, mom_smem, LDSM ? nullptr : a.scratch + (size_t)blockIdx.x * kGenericBufs * mat_elems(N));
+  zero_padding<LDSM>(c);
+  __syncthreads();
+  const size_t NN = (size_t)N * N;
+  const int ld = c.ld;
+  for (size_t pt = blockIdx.x; pt < (size_t)a.S; pt += gridDim.x) {
+    wg_copy_mat(N, c.fd, a.A + NN * pt, N, c.P, ld);
+    wg_copy_mat(N, c.fd, a.B + NN * pt, N, c.Q, ld);
+    __syncthreads();
+    real *C = a.C + NN * pt;
+    wg_gemm<false>(N, ElP{c.P, ld}, ElP{c.Q, ld}, [=](int i, int j, real v) { C[i + (size_t)j * N] = v; });
+    __syncthreads();
   }
 }
 

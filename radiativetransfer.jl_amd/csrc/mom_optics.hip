@@ -1,0 +1,417 @@
+// mom_optics.hip -- the device-side layer optics of the C ABI (include/momcore.h): the resident absorption table
+// and the Voigt entry points (kernels: voigt.hip), k_optics and mom_scene_set_optics, mom_scene_get_layers.
+#include "mom_handle.hpp"
+
+extern "C" int mom_absorption_begin(mom_t *h, int Nz, const double *grid) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (Nz <= 0) return fail(h, MOM_EINVAL, "mom_absorption_begin: bad argument");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t S = h->S;
+  HIPCHK(h, h->d_tau_abs.renew(S * Nz));
+  HIPCHK(h, hipMemsetAsync(h->d_tau_abs, 0, S * Nz * sizeof(double), h->stream));  // τ_abs = zeros (model_from_parameters.jl:48)
+  h->abs_Nz = Nz;
+  if (grid) {
+    HIPCHK(h, mom_upload(h->d_grid, grid, S, h->stream));
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MOM_OK;
+}
+
+extern "C" int mom_absorption_set(mom_t *h, int Nz, const double *tau_abs) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (Nz <= 0 || !tau_abs) return fail(h, MOM_EINVAL, "mom_absorption_set: bad argument");
+  int rc = mom_absorption_begin(h, Nz, nullptr);
+  if (rc) return rc;
+  HIPCHK(h, hipMemcpyAsync(h->d_tau_abs, tau_abs, (size_t)h->S * Nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MOM_OK;
+}
+
+extern "C" int mom_absorption_get(mom_t *h, double *tau_abs) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (!h->d_tau_abs || !tau_abs) return fail(h, MOM_ESTATE, "mom_absorption_get: no resident tau_abs table / null output");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(tau_abs, h->d_tau_abs, (size_t)h->S * h->abs_Nz * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MOM_OK;
+}
+
+extern "C" int mom_voigt_tau_abs(mom_t *h, int iz_1based, int nLines, const double *nu, const double *gamma_d, const double *y,
+                                 const double *S, const int *ind_start_1based, const int *ind_stop_1based, double factor) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (!h->d_tau_abs || !h->d_grid) return fail(h, MOM_ESTATE, "mom_voigt_tau_abs: call mom_absorption_begin with the spectral grid first");
+  if (iz_1based < 1 || iz_1based > h->abs_Nz || nLines < 0 ||
+      (nLines > 0 && (!nu || !gamma_d || !y || !S || !ind_start_1based || !ind_stop_1based)))
+    return fail(h, MOM_EINVAL, "mom_voigt_tau_abs: bad argument");
+  for (int j = 0; j < nLines; ++j)
+    if (ind_start_1based[j] < 1 || ind_stop_1based[j] > h->S) {
+      char buf[160];
+      snprintf(buf, sizeof buf, "mom_voigt_tau_abs: line %d: window [%d, %d] outside the grid 1..%d", j + 1, ind_start_1based[j],
+               ind_stop_1based[j], h->S);
+      return fail(h, MOM_EINVAL, buf);
+    }
+  if (nLines == 0) return MOM_OK;
+  int sorted = 1;
+  for (int j = 1; j < nLines; ++j)
+    if (ind_start_1based[j] < ind_start_1based[j - 1] || ind_stop_1based[j] < ind_stop_1based[j - 1]) { sorted = 0; break; }
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t lb = (size_t)nLines;
+  if (lb > h->lines_per || h->lines_nz != 1) {  // 4 double + 2 int arrays per line, grown geometrically: no allocation in steady state
+    h->lines_nz = 1;
+    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
+    const size_t cap = std::max<size_t>(lb, 1024) * 2;
+    HIPCHK(h, h->d_lines.renew(5 * cap));
+    h->lines_per = cap;
+  }
+  const size_t cap = h->lines_per;
+  double *dl = h->d_lines;
+  int *dw = reinterpret_cast<int *>(dl + 4 * cap);
+  const double *src[4] = {nu, gamma_d, y, S};
+  // the host arrays are borrowed for the call only: the copies must have left them before we return
+  for (int k = 0; k < 4; ++k) HIPCHK(h, hipMemcpyAsync(dl + k * cap, src[k], lb * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(dw, ind_start_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(dw + cap, ind_stop_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, mom_voigt_launch(h->stream, nLines, dl, dl + cap, dl + 2 * cap, dl + 3 * cap, dw, dw + cap, h->S, h->d_grid,
+                             h->d_tau_abs + (size_t)h->S * (iz_1based - 1), factor, 1, sorted));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MOM_OK;
+}
+
+// Resident line table of one absorber: the HITRAN columns of the lines inside the padded grid (the host selects them once,
+// compute_absorption_cross_section.jl:54-72) and the TIPS-2017 spline tables of their isotopologues (qoft! :197-214: knots,
+// values and the second derivatives of DataInterpolations.CubicSpline, computed once by the host in the tables' Float32).
+extern "C" int mom_absorption_set_lines(mom_t *h, int nLines, const double *nu0, const double *S0, const double *gamma_air,
+                                        const double *gamma_self, const double *E_lower, const double *n_air,
+                                        const double *delta_air, const double *sqrt_mol_weight, const int *iso_index, int nIso,
+                                        int nTmax, const int *nT, const double *tips_T, const double *tips_Q, const double *tips_z) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (nLines < 0 || nIso < 0 || nTmax < 0 || (nLines > 0 && (!nu0 || !S0 || !gamma_air || !gamma_self || !E_lower || !n_air ||
+      !delta_air || !sqrt_mol_weight || !iso_index)) || (nIso > 0 && (nTmax < 2 || !nT || !tips_T || !tips_Q || !tips_z)))
+    return fail(h, MOM_EINVAL, "mom_absorption_set_lines: bad argument");
+  for (int j = 0; j < nLines; ++j)
+    if (E_lower[j] != -1.0 && (iso_index[j] < 0 || iso_index[j] >= nIso))
+      return fail(h, MOM_EINVAL, "mom_absorption_set_lines: iso_index out of range");
+  for (int k = 0; k < nIso; ++k)
+    if (nT[k] < 2 || nT[k] > nTmax) return fail(h, MOM_EINVAL, "mom_absorption_set_lines: bad knot count");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->d_lt.reset(); h->d_lt_i.reset();
+  h->lt = MomLineTable{};
+  const size_t L = (size_t)std::max(nLines, 1), Tn = (size_t)std::max(nIso, 1) * std::max(nTmax, 1);
+  HIPCHK(h, h->d_lt.renew(8 * L + 3 * Tn));
+  HIPCHK(h, h->d_lt_i.renew(L + std::max(nIso, 1) + 1));
+  const double *cols[8] = {nu0, S0, gamma_air, gamma_self, E_lower, n_air, delta_air, sqrt_mol_weight};
+  for (int k = 0; k < 8 && nLines > 0; ++k) HIPCHK(h, hipMemcpy(h->d_lt + k * L, cols[k], (size_t)nLines * sizeof(double), hipMemcpyHostToDevice));
+  const double *tabs[3] = {tips_T, tips_Q, tips_z};
+  for (int k = 0; k < 3 && nIso > 0; ++k) HIPCHK(h, hipMemcpy(h->d_lt + 8 * L + k * Tn, tabs[k], (size_t)nIso * nTmax * sizeof(double), hipMemcpyHostToDevice));
+  if (nLines > 0) HIPCHK(h, hipMemcpy(h->d_lt_i, iso_index, (size_t)nLines * sizeof(int), hipMemcpyHostToDevice));
+  if (nIso > 0) HIPCHK(h, hipMemcpy(h->d_lt_i + L, nT, (size_t)nIso * sizeof(int), hipMemcpyHostToDevice));
+  MomLineTable &t = h->lt;
+  t.nLines = nLines; t.nIso = nIso; t.nTmax = nTmax;
+  t.nu0 = h->d_lt; t.S0 = h->d_lt + L; t.g_air = h->d_lt + 2 * L; t.g_self = h->d_lt + 3 * L; t.E = h->d_lt + 4 * L;
+  t.n_air = h->d_lt + 5 * L; t.d_air = h->d_lt + 6 * L; t.sqw = h->d_lt + 7 * L;
+  t.tT = h->d_lt + 8 * L; t.tQ = t.tT + Tn; t.tZ = t.tQ + Tn;
+  t.iso = h->d_lt_i; t.nT = h->d_lt_i + L;
+  // the common validity range of the TIPS tables in use (qoft! asserts Tmin < T < Tmax, :204)
+  h->lt_Tmin = -1e300; h->lt_Tmax = 1e300;
+  for (int k = 0; k < nIso; ++k) {
+    double lo = 1e300, hi = -1e300;
+    for (int i = 0; i < nT[k]; ++i) { lo = std::min(lo, tips_T[(size_t)k * nTmax + i]); hi = std::max(hi, tips_T[(size_t)k * nTmax + i]); }
+    h->lt_Tmin = std::max(h->lt_Tmin, lo); h->lt_Tmax = std::min(h->lt_Tmax, hi);
+  }
+  return MOM_OK;
+}
+
+// compute_absorption_profile! for ONE layer (atmo_prof.jl:427-449) with the per-line prefactors formed ON THE DEVICE from the
+// resident table: only (p, T, vmr, wing_cutoff, factor) cross the bus.
+extern "C" int mom_voigt_tau_abs_layer(mom_t *h, int iz_1based, double pressure, double temperature, double vmr,
+                                       double wing_cutoff, double factor) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (!h->d_tau_abs || !h->d_grid) return fail(h, MOM_ESTATE, "mom_voigt_tau_abs_layer: call mom_absorption_begin with the spectral grid first");
+  if (!h->d_lt) return fail(h, MOM_ESTATE, "mom_voigt_tau_abs_layer: call mom_absorption_set_lines first");
+  if (iz_1based < 1 || iz_1based > h->abs_Nz || !(temperature > 0.0)) return fail(h, MOM_EINVAL, "mom_voigt_tau_abs_layer: bad argument");
+  if (h->lt.nIso > 0 && !(h->lt_Tmin < temperature && temperature < h->lt_Tmax)) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "TIPS2017: T (%g) must be between %g K and %g K.", temperature, h->lt_Tmin, h->lt_Tmax);
+    return fail(h, MOM_EINVAL, buf);
+  }
+  const int nLines = h->lt.nLines;
+  if (nLines == 0) return MOM_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t lb = (size_t)nLines;
+  if (lb > h->lines_per || h->lines_nz != 1) {
+    h->lines_nz = 1;
+    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
+    const size_t cap = std::max<size_t>(lb, 1024) * 2;
+    HIPCHK(h, h->d_lines.renew(5 * cap));
+    h->lines_per = cap;
+  }
+  const size_t cap = h->lines_per;
+  double *dl = h->d_lines;
+  int *dw = reinterpret_cast<int *>(dl + 4 * cap);
+  int *flag = h->d_lt_i + (size_t)std::max(nLines, 1) + std::max(h->lt.nIso, 1);
+  HIPCHK(h, hipMemsetAsync(flag, 0, sizeof(int), h->stream));
+  // γ_d = (cSqrt2Ln2 / cc_) sqrt(cBolts_ / cMassMol) sqrt(T) ν₀ / sqrt(mol_weight)   (:87-88): the scalar part once
+  const double cgd = (1.1774100225 / 2.99792458e8) * std::sqrt(1.3806503e-23 / 1.66053873e-27) * std::sqrt(temperature);
+  HIPCHK(h, mom_line_prefactors_launch(h->stream, h->lt, h->S, h->d_grid, pressure, temperature, vmr, wing_cutoff, cgd, dl, dl + cap,
+                                       dl + 2 * cap, dl + 3 * cap, dw, dw + cap, flag));
+  int unsorted = 0;
+  HIPCHK(h, hipMemcpyAsync(&unsorted, flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, mom_voigt_launch(h->stream, nLines, dl, dl + cap, dl + 2 * cap, dl + 3 * cap, dw, dw + cap, h->S, h->d_grid,
+                             h->d_tau_abs + (size_t)h->S * (iz_1based - 1), factor, 1, unsorted ? 0 : 1));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MOM_OK;
+}
+
+// compute_absorption_profile! for ALL layers of a profile (atmo_prof.jl:427-449) in two launches: the reference walks the
+// layers on the host and, per layer, launches one line-shape kernel per line; at its operating point (O2 A-band at
+// 0.015 cm^-1, wing cut-off 40 cm^-1, 40 layers) a per-layer launch covers 90 workgroups -- a third of the GPU -- and the
+// host round trips between the layers cost more than the arithmetic.  Here blockIdx.y = layer.  gpu_ms (optional): HIP-event
+// time of the two kernels.
+extern "C" int mom_voigt_tau_abs_profile(mom_t *h, int Nz, const double *pressure, const double *temperature, double vmr,
+                                         double wing_cutoff, const double *factor, double *gpu_ms) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (!h->d_tau_abs || !h->d_grid) return fail(h, MOM_ESTATE, "mom_voigt_tau_abs_profile: call mom_absorption_begin with the spectral grid first");
+  if (!h->d_lt) return fail(h, MOM_ESTATE, "mom_voigt_tau_abs_profile: call mom_absorption_set_lines first");
+  if (Nz < 1 || Nz > h->abs_Nz || !pressure || !temperature || !factor) return fail(h, MOM_EINVAL, "mom_voigt_tau_abs_profile: bad argument");
+  for (int z = 0; z < Nz; ++z) {
+    if (!(temperature[z] > 0.0)) return fail(h, MOM_EINVAL, "mom_voigt_tau_abs_profile: bad argument");
+    if (h->lt.nIso > 0 && !(h->lt_Tmin < temperature[z] && temperature[z] < h->lt_Tmax)) {
+      char buf[160];
+      snprintf(buf, sizeof buf, "TIPS2017: T (%g) must be between %g K and %g K.", temperature[z], h->lt_Tmin, h->lt_Tmax);
+      return fail(h, MOM_EINVAL, buf);
+    }
+  }
+  if (gpu_ms) *gpu_ms = 0.0;
+  const int nLines = h->lt.nLines;
+  if (nLines == 0) return MOM_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t per = std::max<size_t>((size_t)nLines, 1024) * 2;       // line capacity of one layer's block
+  const size_t need = per * (size_t)Nz;
+  if (need > h->lines_per * (size_t)std::max(h->lines_nz, 1) || h->lines_nz != Nz) {
+    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
+    HIPCHK(h, h->d_lines.renew(5 * need));
+    h->lines_per = per;
+    h->lines_nz = Nz;
+  }
+  const size_t cap = h->lines_per;
+  // per-layer scalars [p | T | cgd | factor][Nz] and the Nz sortedness flags
+  const size_t prm_doubles = 4 * (size_t)Nz + ((size_t)Nz + 1) / 2;
+  HIPCHK(h, h->d_prof.reserve(prm_doubles, h->stream));
+  std::vector<double> prm(4 * (size_t)Nz);
+  for (int z = 0; z < Nz; ++z) {
+    prm[z] = pressure[z];
+    prm[Nz + z] = temperature[z];
+    // γ_d = (cSqrt2Ln2 / cc_) sqrt(cBolts_ / cMassMol) sqrt(T) ν₀ / sqrt(mol_weight)   (:87-88): the scalar part
+    prm[2 * (size_t)Nz + z] = (1.1774100225 / 2.99792458e8) * std::sqrt(1.3806503e-23 / 1.66053873e-27) * std::sqrt(temperature[z]);
+    prm[3 * (size_t)Nz + z] = factor[z];
+  }
+  HIPCHK(h, hipMemcpyAsync(h->d_prof, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  int *flags = reinterpret_cast<int *>(h->d_prof + 4 * (size_t)Nz);
+  HIPCHK(h, hipMemsetAsync(flags, 0, sizeof(int) * (size_t)Nz, h->stream));
+  double *pf = h->d_lines;
+  int *win = reinterpret_cast<int *>(pf + 4 * cap * (size_t)Nz);
+  if (gpu_ms) {
+    for (int k = 0; k < 2; ++k)
+      if (!h->ev_voigt[k]) HIPCHK(h, hipEventCreate(&h->ev_voigt[k]));
+    HIPCHK(h, hipEventRecord(h->ev_voigt[0], h->stream));
+  }
+  HIPCHK(h, mom_voigt_profile_launch(h->stream, h->lt, Nz, cap, h->S, h->d_grid, h->d_prof, vmr, wing_cutoff, pf, win, flags,
+                                     h->d_tau_abs, h->d_prof + 3 * (size_t)Nz));
+  if (gpu_ms) HIPCHK(h, hipEventRecord(h->ev_voigt[1], h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // prm is a host temporary
+  if (gpu_ms) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, h->ev_voigt[0], h->ev_voigt[1]) == hipSuccess) *gpu_ms = ms;
+  }
+  return MOM_OK;
+}
+
+// the prefactors of the last mom_voigt_tau_abs / mom_voigt_tau_abs_layer call (test access); n = its number of lines
+extern "C" int mom_absorption_get_prefactors(mom_t *h, int n, double *nu, double *gamma_d, double *y, double *S, int *ind_start_1based,
+                                             int *ind_stop_1based) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (!h->d_lines || n < 0 || (size_t)n > h->lines_per) return fail(h, MOM_ESTATE, "mom_absorption_get_prefactors: no prefactors resident");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t cap = h->lines_per, nz = (size_t)std::max(h->lines_nz, 1), last = (nz - 1) * cap;  // the LAST layer of a profile call
+  double *dst[4] = {nu, gamma_d, y, S};
+  for (int k = 0; k < 4; ++k)
+    if (dst[k]) HIPCHK(h, hipMemcpy(dst[k], h->d_lines + k * nz * cap + last, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  const int *dw = reinterpret_cast<const int *>(h->d_lines + 4 * nz * cap);
+  if (ind_start_1based) HIPCHK(h, hipMemcpy(ind_start_1based, dw + last, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  if (ind_stop_1based) HIPCHK(h, hipMemcpy(ind_stop_1based, dw + nz * cap + last, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  return MOM_OK;
+}
+
+// constructCoreOpticalProperties (compEffectiveLayerProperties.jl:1-78) with the `+` of types.jl:632-678, createAero
+// (:80-85), the gas term (:672-678) and the cumulative τ_sum of extractEffectiveProps (:108), one thread per spectral
+// point walking the layers; per-layer max(τ ϖ) for get_dtau_ndoubl / `scatter` by atomic max on the bit pattern
+// (non-negative doubles order like their unsigned bit patterns).  Contraction off: the same IEEE operations as the
+// host (numpy / Julia) path, so both routes give bitwise equal τ, ϖ, weights.
+struct OpticsArgs {
+  int S, Nz, nAer;
+  double varpi_rayl;
+  const double *tau_rayl, *tau_abs;  // [S,Nz]
+  const double *aer;                 // [2,nAer,Nz]: τ_y, w_y = τ_y ϖ_y per aerosol type and layer (spectrally flat)
+  const int *aer_mode;               // [nAer,Nz]: 0 = Rayleigh side all zero, 1 = mix, 2 = aerosol side all zero
+  double *tau, *varpi, *zw, *tau_sum, *layer_max;
+};
+#pragma clang fp contract(off)
+__global__ void k_optics(OpticsArgs a) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  const int K = 1 + a.nAer;
+  double tsum = 0.0;
+  const bool live = n < a.S;
+  if (live) a.tau_sum[n] = 0.0;
+  for (int z = 0; z < a.Nz; ++z) {
+    double tw = 0.0;
+    if (live) {
+      const size_t o = n + (size_t)a.S * z;
+      double tau = a.tau_rayl[o], varpi = a.varpi_rayl;
+      double w[8];
+      w[0] = 1.0;
+      for (int k = 1; k < K; ++k) w[k] = 0.0;
+      for (int x = 0; x < a.nAer; ++x) {
+        const double ty = a.aer[x + (size_t)a.nAer * z], wy = a.aer[a.nAer * a.Nz + x + (size_t)a.nAer * z];
+        const int mode = a.aer_mode[x + (size_t)a.nAer * z];
+        const double wx = tau * varpi, tot = wx + wy, tn = tau + ty;
+        if (mode == 0) {
+          for (int k = 0; k < K; ++k) w[k] = 0.0;
+          w[x + 1] = 1.0;
+        } else if (mode == 1) {
+          const double fx = wx / tot;
+          for (int k = 0; k < K; ++k) w[k] *= fx;
+          w[x + 1] = wy / tot;
+        }
+        varpi = tot / tn;
+        tau = tn;
+      }
+      const double tn = tau + a.tau_abs[o];
+      varpi = (tau * varpi) / tn;
+      tau = tn;
+      a.tau[o] = tau;
+      a.varpi[o] = varpi;
+      for (int k = 0; k < K; ++k) a.zw[k + (size_t)K * o] = w[k];
+      tsum = tsum + 1.0 * tau;
+      a.tau_sum[o + a.S] = tsum;
+      tw = tau * varpi;
+    }
+    // NaN (0/0 in an empty layer) must not win silently: fmax drops it like Julia's maximum would propagate it --
+    // the host path would fail on such a scene as well; keep it visible as +inf
+    if (tw != tw) tw = __longlong_as_double(0x7ff0000000000000ll);
+    double m = tw;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off));
+    if ((threadIdx.x & 63) == 0 && m > 0.0)
+      atomicMax(reinterpret_cast<unsigned long long *>(a.layer_max + z), (unsigned long long)__double_as_longlong(m));
+  }
+}
+
+// doubling_number (rt_helper_functions.jl:31-57): log10 arithmetic and the eps test as in the reference
+static int doubling_number_host(double dtau_max, double tau_end) {
+  if (tau_end <= dtau_max) return 0;
+  const double q1 = std::log10(2.0), q2 = std::log10(dtau_max), q3 = std::log10(tau_end);
+  const double tlimit = (q3 - q2) / q1, nlimit = std::floor(tlimit);
+  if (tlimit - nlimit < 2.220446049250313e-16) return (int)nlimit;
+  return (int)nlimit + 1;
+}
+
+extern "C" int mom_scene_set_optics(mom_t *h, int Nz, int nAer, int M, const double *tau_rayl, double varpi_rayl,
+                                    const double *tau_aer, const double *omega_aer, const double *ft_aer,
+                                    const double *Zpp, const double *Zmp, double albedo, int nVza, const int *node_1based,
+                                    const double *cos_mphi, const double *sin_mphi) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (!h->streams_set) return fail(h, MOM_ESTATE, "mom_scene_set_optics: call mom_set_streams first");
+  if (Nz <= 0 || nAer < 0 || nAer > 7 || M <= 0 || M > h->M || nVza <= 0 || !tau_rayl || !Zpp || !Zmp || !node_1based ||
+      !cos_mphi || !sin_mphi || (nAer > 0 && (!tau_aer || !omega_aer || !ft_aer)))
+    return fail(h, MOM_EINVAL, "mom_scene_set_optics: bad argument");
+  if (!h->d_tau_abs || h->abs_Nz != Nz)
+    return fail(h, MOM_ESTATE, "mom_scene_set_optics: no resident tau_abs table of this Nz (mom_absorption_begin / _set)");
+  HIPCHK(h, hipSetDevice(h->device));
+  h->scene_set = false;
+  const size_t S = h->S;
+  const int K = 1 + nAer;
+  int rc;
+  HIPCHK(h, mom_upload(h->d_tau_rayl, tau_rayl, S * Nz, h->stream));
+  // createAero (compEffectiveLayerProperties.jl:80-85): τ' = (1 - fᵗ ω̃) τ_aer, ϖ' = (1 - fᵗ) ω̃ / (1 - fᵗ ω̃); the
+  // all-zero tests of types.jl:641-661 are decided here on the host (they are properties of whole spectral columns)
+  std::vector<double> aer((size_t)2 * std::max(nAer, 1) * Nz, 0.0);
+  std::vector<int> mode((size_t)std::max(nAer, 1) * Nz, 2);
+  for (int z = 0; z < Nz; ++z) {
+    bool x_zero = true;  // all(τ ϖ == 0) of the accumulated left operand
+    if (varpi_rayl != 0.0)
+      for (size_t n = 0; n < S; ++n)
+        if (tau_rayl[n + S * z] != 0.0) { x_zero = false; break; }
+    for (int x = 0; x < nAer; ++x) {
+      const double ty = (1 - ft_aer[x] * omega_aer[x]) * tau_aer[x + (size_t)nAer * z];
+      const double vy = (1 - ft_aer[x]) * omega_aer[x] / (1 - ft_aer[x] * omega_aer[x]);
+      const double wy = ty * vy;
+      aer[x + (size_t)nAer * z] = ty;
+      aer[(size_t)nAer * Nz + x + (size_t)nAer * z] = wy;
+      mode[x + (size_t)nAer * z] = x_zero ? 0 : (wy != 0.0 ? 1 : 2);
+      x_zero = x_zero && (wy == 0.0);
+    }
+  }
+  HIPCHK(h, mom_upload(h->d_aer, aer.data(), aer.size(), h->stream));
+  HIPCHK(h, mom_upload(h->d_aer_mode, mode.data(), mode.size(), h->stream));
+  HIPCHK(h, h->d_tau.renew(S * Nz));
+  HIPCHK(h, h->d_varpi.renew(S * Nz));
+  HIPCHK(h, h->d_zw.renew((size_t)K * S * Nz));
+  HIPCHK(h, h->d_tau_sum.renew(S * (Nz + 1)));
+  HIPCHK(h, h->d_layer_max.renew((size_t)Nz));
+  HIPCHK(h, hipMemsetAsync(h->d_layer_max, 0, (size_t)Nz * sizeof(double), h->stream));
+  OpticsArgs a{};
+  a.S = h->S; a.Nz = Nz; a.nAer = nAer; a.varpi_rayl = varpi_rayl;
+  a.tau_rayl = h->d_tau_rayl; a.tau_abs = h->d_tau_abs; a.aer = h->d_aer; a.aer_mode = h->d_aer_mode;
+  a.tau = h->d_tau; a.varpi = h->d_varpi; a.zw = h->d_zw; a.tau_sum = h->d_tau_sum; a.layer_max = h->d_layer_max;
+  hipLaunchKernelGGL(k_optics, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  // get_dtau_ndoubl takes maximum(τ .* ϖ) over the WHOLE spectral axis (rt_kernel.jl:241-242): across the ranks of a
+  // sharded run the per-layer maxima are combined first (one tiny all-reduce at set-up time, not in the sweep)
+  if (h->comm && (rc = mom_comm_allreduce_max(h, h->d_layer_max, (size_t)Nz))) return rc;
+  std::vector<double> mx((size_t)Nz);
+  HIPCHK(h, hipMemcpyAsync(mx.data(), h->d_layer_max, (size_t)Nz * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  double mu_min = h->h_mu[0];
+  for (double v : h->h_mu) mu_min = std::min(mu_min, v);
+  h->nd.assign((size_t)Nz, 0);
+  h->iface.assign((size_t)Nz, 0);
+  int prev = 0;
+  for (int z = 0; z < Nz; ++z) {
+    if (!std::isfinite(mx[z])) return fail(h, MOM_EINVAL, "mom_scene_set_optics: a layer has non-finite τ ϖ (empty layer: τ = 0?)");
+    h->nd[z] = doubling_number_host(std::min(mx[z], 0.001 * mu_min), mx[z]);
+    if (h->nd[z] > 60) return fail(h, MOM_EINVAL, "mom_scene_set_optics: ndoubl out of range");
+    const bool scatter = mx[z] > 2 * 2.220446049250313e-16;  // compEffectiveLayerProperties.jl:104
+    prev = (z == 0) ? (scatter ? 3 : 0) : (prev == 0 ? (scatter ? 1 : 0) : (scatter ? 3 : 2));  // rt_helper_functions.jl:8-27
+    h->iface[z] = prev;
+  }
+  if (h->f32) {  // Float32 handle: the Float64 assembly above is rounded to Float32 on the device (no host hop of tau_abs either)
+    h->Nz = Nz; h->K = K; h->scene_M = M; h->nVza = nVza; h->albedo = albedo; h->surf_kind = 0;
+    if ((rc = momf_scene_set_dev(h->f32, Nz, K, M, h->d_tau, h->d_varpi, h->d_zw, Zpp, Zmp, h->nd.data(), h->iface.data(), h->d_tau_sum,
+                                 albedo, nVza, node_1based, cos_mphi, sin_mphi)))
+      return fail(h, rc, momf_error(h->f32));
+    h->scene_set = true;
+    return MOM_OK;
+  }
+  if ((rc = scene_common(h, Nz, K, M, Zpp, Zmp, albedo, nVza, node_1based, cos_mphi, sin_mphi))) return rc;
+  h->scene_set = true;
+  return MOM_OK;
+}
+
+extern "C" int mom_scene_get_layers(mom_t *h, int *ndoubl, int *iface, double *tau, double *varpi, double *zw, double *tau_sum) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (!h->scene_set) return fail(h, MOM_ESTATE, "mom_scene_get_layers: no scene");
+  if (h->f32 && (tau || varpi || zw || tau_sum) && !h->d_tau)
+    return fail(h, MOM_ESTATE, "mom_scene_get_layers: a Float32 handle keeps the Float64 layer arrays only after mom_scene_set_optics");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t S = h->S, Nz = h->Nz;
+  if (ndoubl) std::copy(h->nd.begin(), h->nd.end(), ndoubl);
+  if (iface) std::copy(h->iface.begin(), h->iface.end(), iface);
+  if (tau) HIPCHK(h, hipMemcpyAsync(tau, h->d_tau, S * Nz * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (varpi) HIPCHK(h, hipMemcpyAsync(varpi, h->d_varpi, S * Nz * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (zw) HIPCHK(h, hipMemcpyAsync(zw, h->d_zw, (size_t)h->K * S * Nz * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (tau_sum) HIPCHK(h, hipMemcpyAsync(tau_sum, h->d_tau_sum, S * (Nz + 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MOM_OK;
+}

@@ -32,9 +32,8 @@
 #include <utility>
 #include <vector>
 
+#include "mom_host.hpp"
 #include "mom_tile.hpp"
-
-hipError_t momr_big_launch(int which, int nt, int v0, int v1, unsigned grid, void *stream, const void *args, int iface);
 
 // The 3 x 3- and 4 x 4-tile images (32 < N <= 64) are built as a second object from this source (-DMOMR_BIG_TU, namespace
 // momr_big, without -amdgpu-mfma-vgpr-form, which crashes the compiler on them): device code + ONE launcher, momr_big_launch

@@ -1,4 +1,4 @@
-// mom_rrs.hpp -- host interface of the rotational-Raman (RRS) kernels (mom_rrs.hip) towards momcore.hip.
+// mom_rrs.hpp -- host interface of the rotational-Raman (RRS) kernels (mom_rrs.hip) towards mom_rrs_api.hip.
 //
 // State of the inelastic path of rt_run(::RRS) (src/CoreRT/rt_run.jl:41-230): the reference's AddedLayerRS / CompositeLayerRS
 // (types.jl:145-205) as persistent HBM arrays in the reference's own memory order -- elastic operators [N,N,S], sources

@@ -199,7 +199,7 @@ __device__ __forceinline__ int solve_right(Mat<N> &X, const Mat<N> &B, const Mat
   return bad;
 }
 
-using SweepArgs = ::MomSmallSweepArgsT<real>;  // mom_host.hpp: the one definition shared with momcore.hip / momcore_f32.hip
+using SweepArgs = ::MomSmallSweepArgsT<real>;  // mom_host.hpp: the one definition shared with mom_scene.hip / momcore_f32.hip
 
 // Register budget (r5).  Up to r4 the N = 3, 4 images were built for two waves per SIMD (256 VGPRs) and SPILLED: k_sweep<4> 522
 // VGPRs, 996 B of scratch per lane -- 6.5 GB of scratch traffic per 1.7 ms launch against 88 MB of algorithmic bytes (74 x; the
@@ -612,7 +612,7 @@ __global__ void k_sum(SweepArgs a) {
 
 }  // namespace MOMS_NS
 
-// host entry used by momcore.hip (argument block = MOMS_NS::SweepArgs, passed as bytes)
+// host entry used by mom_scene.hip (argument block = MOMS_NS::SweepArgs, passed as bytes)
 #ifndef MOMS_FLOAT
 size_t momsm_args_bytes() { return sizeof(MOMS_NS::SweepArgs); }
 #endif

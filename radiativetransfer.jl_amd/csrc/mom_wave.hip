@@ -205,7 +205,7 @@ __device__ __forceinline__ int series_terms(real beta2, real thr) {
   return 1 + __popc(m & 0x7fffffffu);
 }
 
-using WArgs = ::MomWaveSweepArgsT<real>;  // mom_host.hpp: the one definition shared with momcore.hip / momcore_f32.hip
+using WArgs = ::MomWaveSweepArgsT<real>;  // mom_host.hpp: the one definition shared with mom_scene.hip / momcore_f32.hip
 
 // per-lane coordinates; row / column quantities are read from the block's LDS table tab = mu[32] | wt[32] | sg[32]
 // (padding entries: mu = 1, wt = 0, sg = 1)
@@ -755,7 +755,6 @@ __global__ void __launch_bounds__(256, (NT == 1 ? MOMW_OCC1 : 1)) k_wsweep(WArgs
 #define MOMW_LAUNCH momw_launch_sweep
 #define MOMW_LAUNCH8 momw_launch_sweep8
 #endif
-hipError_t MOMW_LAUNCH8(const void *args, hipStream_t st);
 #ifdef MOMW_ONLY_KS8
 hipError_t MOMW_LAUNCH8(const void *args, hipStream_t st) {
   const MOMW_NS::WArgs a = *reinterpret_cast<const MOMW_NS::WArgs *>(args);

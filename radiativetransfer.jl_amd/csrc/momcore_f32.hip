@@ -96,55 +96,6 @@ __global__ void k_combine_m0_f32(CombineArgsF a) {
   }
 }
 
-
-// batch_inv! / batched_mul for Float32 arrays (gpu_batched.jl:45-58, 90-97: cuBLAS Sgetrf/Sgetri, Sgemm)
-struct BlasArgsF {
-  int N, S;
-  const float *A, *B;
-  float *C;
-  float *scratch;
-  int *info;
-};
-
-template <bool LDSM>
-__global__ void __launch_bounds__(kThreads) k_batch_inv_f32(BlasArgsF a) {
-  const int N = a.N;
-  Ctx c;
-  make_ctx<LDSM>(c, N, 1, mom_smem, LDSM ? nullptr : a.scratch + (size_t)blockIdx.x * kGenericBufs * mat_elems(N));
-  zero_padding<LDSM>(c);
-  if (threadIdx.x == 0) *c.bad = 0;
-  __syncthreads();
-  const size_t NN = (size_t)N * N;
-  for (size_t pt = blockIdx.x; pt < (size_t)a.S; pt += gridDim.x) {
-    wg_copy_mat(N, c.fd, a.A + NN * pt, N, c.P, c.ld);
-    __syncthreads();
-    if (N <= 64) wg_inverse_reg(N, c.P, c.ld, c.part, c.prow, c.ipiv, c.bad);
-    else wg_inverse(N, c.fd, c.P, c.ld, c.prow, c.pcol, c.rowk, c.ipiv, c.sh, c.bad);
-    wg_copy_mat(N, c.fd, c.P, c.ld, a.C + NN * pt, N);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && *c.bad) atomicMax(a.info, *c.bad);
-}
-
-template <bool LDSM>
-__global__ void __launch_bounds__(kThreads) k_batched_mul_f32(BlasArgsF a) {
-  const int N = a.N;
-  Ctx c;
-  make_ctx<LDSM>(c, N, 1, mom_smem, LDSM ? nullptr : a.scratch + (size_t)blockIdx.x * kGenericBufs * mat_elems(N));
-  zero_padding<LDSM>(c);
-  __syncthreads();
-  const size_t NN = (size_t)N * N;
-  const int ld = c.ld;
-  for (size_t pt = blockIdx.x; pt < (size_t)a.S; pt += gridDim.x) {
-    wg_copy_mat(N, c.fd, a.A + NN * pt, N, c.P, ld);
-    wg_copy_mat(N, c.fd, a.B + NN * pt, N, c.Q, ld);
-    __syncthreads();
-    float *C = a.C + NN * pt;
-    wg_gemm<false>(N, ElP{c.P, ld}, ElP{c.Q, ld}, [=](int i, int j, float v) { C[i + (size_t)j * N] = v; });
-    __syncthreads();
-  }
-}
-
 std::vector<float> tof(const double *src, size_t n) {
   std::vector<float> v(n);
   for (size_t i = 0; i < n; ++i) v[i] = (float)src[i];
@@ -448,11 +399,10 @@ int momf_scene_set_surface(momf_scene *s, int kind, int M, const double *Rsurf, 
   return MOM_OK;
 }
 
-hipError_t momwf_launch_sweep(const void *args, hipStream_t st);  // mom_wave.hip built with -DMOMW_FLOAT
 // momcore_strip.hip built for float (Makefile: momcore_fs<KS>.o, 8 waves; momcore_f4s<KS>.o, 4 waves): mom_images.hpp
 
 // 4 < N <= 32: one spectral point per wavefront, operators in MFMA-layout registers, the whole run in ONE launch -- the
-// Float32 build of momw::k_wsweep (the Float64 path: rt_run_wave in momcore.hip).  Covers ScatteringInterface_11 on every
+// Float32 build of momw::k_wsweep (the Float64 path: rt_run_wave in mom_scene.hip).  Covers ScatteringInterface_11 on every
 // layer after the first and at the surface.
 static bool wave_applies_f32(const momf_scene *s) {
   if (!(s->N > 4 && s->N <= 32 && s->small_n && !s->force_generic && s->nVza * s->nS <= 256)) return false;
@@ -485,9 +435,7 @@ static int rt_run_wave_f32(momf_scene *s) {
   return MOM_OK;
 }
 
-hipError_t momsmf_launch_sweep(const void *args, int N, hipStream_t st);  // mom_small.hip built with -DMOMS_FLOAT
-
-// N <= 4: one spectral point per lane, the whole run in ONE launch (the Float64 path: rt_run_small in momcore.hip)
+// N <= 4: one spectral point per lane, the whole run in ONE launch (the Float64 path: rt_run_small in mom_scene.hip)
 static int rt_run_small_f32(momf_scene *s) {
   const int N = s->N, Nz = s->Nz;
   if (!s->d_smtab) FCHK(s, s->d_smtab.renew(48));
@@ -681,12 +629,12 @@ int momf_blas(momf_scene *s, int n, int batch, const double *A, const double *B,
     FCHK(s, scr.reserve(scn, s->stream));
     FCHK(s, hipMemsetAsync(scr, 0, scn * sizeof(float), s->stream));
   }
-  BlasArgsF a{n, batch, dA, inv ? nullptr : dB.get(), dC, lds ? nullptr : scr.get(), s->d_info};
+  BlasArgs a{n, batch, dA, inv ? nullptr : dB.get(), dC, lds ? nullptr : scr.get(), s->d_info};
   const size_t sm = lds_bytes(n, lds);
   if (inv) {
-    FCHK(s, mom_launch_ldsm(MOM_LDSM(k_batch_inv_f32), lds, grid, kThreads, sm, s->stream, a));
+    FCHK(s, mom_launch_ldsm(MOM_LDSM(k_batch_inv), lds, grid, kThreads, sm, s->stream, a));
   } else {
-    FCHK(s, mom_launch_ldsm(MOM_LDSM(k_batched_mul_f32), lds, grid, kThreads, sm, s->stream, a));
+    FCHK(s, mom_launch_ldsm(MOM_LDSM(k_batched_mul), lds, grid, kThreads, sm, s->stream, a));
   }
   return download_f(s, C, dC, cnt);
 }

@@ -1,6 +1,6 @@
 // momcore_gen.hip -- the general (non strip-chained) layer kernels of the 8-wave build, k_layer<LDSM, IFACE>, in a
 // translation unit of their own: they are the largest kernel images of the library (eight of them), and compiling them
-// next to the rest of momcore.hip serialised the build.  Host entry point used by momcore.hip.
+// next to the rest of momcore.hip serialised the build.  Host entry point used by mom_scene.hip.
 #include <hip/hip_runtime.h>
 
 #include "mom_diag.hpp"

@@ -1,7 +1,7 @@
 // momcore_w4.hip -- the fused kernels instantiated for 4-wave (256-thread) workgroups, namespace mom4.
 // Two such workgroups share a CU when 4 operators + vectors fit 80 KB of LDS (N <= 40); their phases then
 // overlap each other's barriers and LDS latencies.  Host entry points are plain C++ functions used by
-// momcore.hip; the argument blocks are layout-identical to mom::LayerArgs / mom::SurfArgs.
+// mom_scene.hip; the argument blocks are layout-identical to mom::LayerArgs / mom::SurfArgs.
 #define MOM_WAVES 4
 #define MOM_TJ 3
 #define MOM_NO_STRAIGHT  // operators of this build have at most 12 MFMA k-steps

@@ -219,7 +219,7 @@ thread_local double v_last_ms = 0.0;
 }  // namespace
 
 // one launch for all lines on `st` (device pointers); used by mom_voigt_xsec below and by the handle-level
-// mom_voigt_tau_abs (momcore.hip), which accumulates straight into the resident tau_abs table
+// mom_voigt_tau_abs (mom_optics.hip), which accumulates straight into the resident tau_abs table
 // ---------------------------------------------------------------------------------------------------------------------
 // Per-line prefactors of compute_absorption_cross_section (compute_absorption_cross_section.jl:73-107) on the device, from
 // ONE resident HITRAN table per absorber: pressure shift (:79), Lorentz half width (:82-84), Doppler half width (:87-88),
