@@ -488,6 +488,13 @@ int mom_timers(mom_t *h, double *ms, int n, int *kernel_launches);
  *                         chains at raised wave priority (an experiment: the two units do not run in lock-step to begin with, and the
  *                         priority measured 1.6 ms slower on C2 on top of the queue, profiles/r08_C2_ab.txt).  0 = neither (the
  *                         scheduling before this option existed).  Results do not depend on it: units are independent.
+ *   MOM_OPT_ZERO_SKIP     the quad-block image (operator edges 20 .. 40, csrc/mom_q4.hpp): 1 (default) = its products leave out the
+ *                         blocks that are exact zeros because of the zero-weight streams at the end of the stream set (the view
+ *                         angles, the Sun, dummy entries): the driver counts the trailing weights that are exactly 0.0, the first
+ *                         nbw = ceil((N - count) / 4) blocks of four entries hold the weighted ones, and a launch takes the kernel
+ *                         compiled for that many (or the next larger number it has: 0, 1, 2 or 4 blocks left out).  0 = the kernel
+ *                         that multiplies every block.  The terms left out are exact zeros: stored values, series lengths and
+ *                         resume decisions do not depend on the option (at most the sign of a zero does).
  */
 int mom_set_option(mom_t *h, int option, int value);
 
@@ -497,7 +504,8 @@ int mom_set_option(mom_t *h, int option, int value);
 int mom_strip2_resumed(mom_t *h, int *units, int *left);
 enum { MOM_OPT_INVERSE = 0, MOM_OPT_FORCE_GENERIC = 1, MOM_OPT_M0_REDUCTION = 2, MOM_OPT_SMALL_WG = 3, MOM_OPT_STAGGER = 4,
        MOM_OPT_SMALL_N = 5, MOM_OPT_LAYER_SWEEP = 6, MOM_OPT_STRIP_PAD = 7, MOM_OPT_LEAN = 8, MOM_OPT_OVERLAP = 9,
-       MOM_OPT_RRS_KERNELS = 10, MOM_OPT_DUAL_WORKSPACE_MB = 11, MOM_OPT_STRIP2 = 12, MOM_OPT_STRIP2_SCHED = 13 };
+       MOM_OPT_RRS_KERNELS = 10, MOM_OPT_DUAL_WORKSPACE_MB = 11, MOM_OPT_STRIP2 = 12, MOM_OPT_STRIP2_SCHED = 13,
+       MOM_OPT_ZERO_SKIP = 14 };
 
 /* ---- Voigt line-by-line cross section --------------------------------------------------
  * compute_absorption_cross_section(model::HitranModel, grid, p, T)

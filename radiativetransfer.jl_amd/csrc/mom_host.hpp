@@ -83,6 +83,16 @@ inline int mom_strip_pad(bool (*strip_size)(int), int N) {
     if (strip_size(p)) return p;
   return N;
 }
+// Zero-weight streams come last in a stream set: the view angles and the Sun behind the Gauss nodes, the dummy entries behind
+// them.  mom_weighted_edge: the entries in front of the trailing run of weights that are EXACTLY 0.0 (a zero between weighted
+// entries ends the run); mom_q4_nbw: the blocks of four entries that hold one of them, at least 1 -- from block nbw on every entry is
+// a zero-weight stream, whose column the elemental layer writes as r = 0, t = its diagonal entry (mom_kernels.hpp: weight <= 1e-8)
+inline int mom_weighted_edge(const double *wt, int N) {
+  int n = N;
+  while (n > 0 && wt[n - 1] == 0.0) --n;
+  return n;
+}
+inline int mom_q4_nbw(const double *wt, int N) { return std::max(1, (mom_weighted_edge(wt, N) + 3) / 4); }
 // [N,N,B] -> [Nk,Nk,B], zero padded
 inline std::vector<double> mom_pad_blocks(const double *src, int N, int Nk, size_t B) {
   std::vector<double> out((size_t)Nk * Nk * B, 0.0);

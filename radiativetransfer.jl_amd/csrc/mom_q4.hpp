@@ -122,33 +122,54 @@ __device__ __forceinline__ void q4_store_glb_T(gdouble *__restrict__ X, const Q4
 // NV > 0: the riding block row -- accR(Jg) += sum_K V(K) X(K, Jg) with V(K)[i][k] = ride[i * N + 4 K + k] for i < NV (vector i at
 // ride + i N), zero rows above: row i of accR is v_i^T X.
 // q4_mul_c: out = C0 + M^T X (the MFMA's C operand of the first k-block is C0: no copy of the initial value); q4_mul: acc += M^T X.
-template <int KS, int NV = 0, bool ZERO = false>
+//
+// NBW < NB (MOM_OPT_ZERO_SKIP): the entries >= 4 NBW of the problem are zero-weight streams (view angles, the Sun, dummy entries;
+// the host counts them, mom_host.hpp mom_q4_nbw).  elemental_build gives such a stream j the column r[:, j] = 0, t[:, j] = e_j t_jj,
+// so every operator of the sweep is [A 0; C D] with D diagonal or zero, and so is every product, series and sign flip of them.
+// In the layout of this product two operands are then exact zeros and their MFMAs (and fragment reads) are not issued:
+//   * the left fragment A(I, K) for I >= NBW unless K == I    (column block I of the multiplier M),
+//   * the right operand X(K, Jg) for K >= NBW unless Jg == K >> 2   (row block K of the transposed operator).
+// Block rows I < NBW keep the request pipeline below (pairs of rows, the riding row behind the last of them); a block row I >= NBW is
+// ONE product, A(I, I) X(I, I >> 2), its fragment requested with the first pair's and used behind the last.  Every accumulator without
+// a product receives its initial value.  NBW = NB is the instruction stream without the rule.
+template <int KS, int NV = 0, bool ZERO = false, int NBW = Q4Geom<KS>::NB>
 __device__ __forceinline__ void q4_mul_c(const real *M, const real (&X)[Q4Geom<KS>::NB][Q4Geom<KS>::NJ],
                                          const real (&C0)[Q4Geom<KS>::NB][Q4Geom<KS>::NJ],
                                          real (&acc)[Q4Geom<KS>::NB][Q4Geom<KS>::NJ], const real *ride = nullptr,
                                          real (*accR)[Q4Geom<KS>::NJ] = nullptr) {
   using G = Q4Geom<KS>;
+  static_assert(NBW >= 1 && NBW <= G::NB, "q4_mul_c: 1 <= NBW <= NB");
+  constexpr int NZ = G::NB - NBW;   // block rows of zero-weight entries only
   int l = wg_lane();
   asm volatile("" : "+v"(l));   // keep the address arithmetic inside (mom_device.hpp item_straight)
   const int k = l >> 4, i = l & 3;
   const real *base = M + k + i * G::LD;
+#define Q4_XLIVE(K, J) ((K) < NBW || (J) == ((K) >> 2))   // X(K, J) can be non-zero
 #if Q4_MUL_VARIANT == 2
   // the plain triple loop, scheduled by the compiler (tools/q4_probe.hip's form)
 #pragma unroll
-  for (int I = 0; I < G::NB; ++I)
+  for (int I = 0; I < G::NB; ++I) {
+    if (I >= NBW) {
+#pragma unroll
+      for (int J = 0; J < G::NJ; ++J) acc[I][J] = ZERO ? (real)0 : C0[I][J];
+    }
 #pragma unroll
     for (int K = 0; K < G::NB; ++K) {
+      if (I >= NBW && K != I) continue;
       const real a = base[4 * K + 4 * I * G::LD];
 #pragma unroll
-      for (int J = 0; J < G::NJ; ++J) acc[I][J] = mma4(a, X[K][J], K == 0 ? (ZERO ? (real)0 : C0[I][J]) : acc[I][J]);
+      for (int J = 0; J < G::NJ; ++J)
+        if (Q4_XLIVE(K, J)) acc[I][J] = mma4(a, X[K][J], (I < NBW && K == 0) ? (ZERO ? (real)0 : C0[I][J]) : acc[I][J]);
     }
+  }
   if constexpr (NV > 0) {
     const real *rb = ride + k + i * G::N;
 #pragma unroll
     for (int K = 0; K < G::NB; ++K) {
       const real a = (i < NV) ? rb[4 * K] : 0.0;
 #pragma unroll
-      for (int J = 0; J < G::NJ; ++J) (*accR)[J] = mma4(a, X[K][J], (*accR)[J]);
+      for (int J = 0; J < G::NJ; ++J)
+        if (Q4_XLIVE(K, J)) (*accR)[J] = mma4(a, X[K][J], (*accR)[J]);
     }
   }
   return;
@@ -157,16 +178,24 @@ __device__ __forceinline__ void q4_mul_c(const real *M, const real (&X)[Q4Geom<K
   // one (left to itself the compiler reads each fragment right in front of its MFMAs and waits for it: one exposed LDS latency per
   // six MFMAs -- the first version of this image ran its products at 9 .. 11 k cycles instead of 5.3 k); two rows at a time give six
   // independent accumulators per k-block (three leave the pipe waiting for its own result: s_nop between the groups)
-  constexpr int NP = (G::NB + 1) / 2;          // row pairs (the last one may be a single row)
+  constexpr int NP = (NBW + 1) / 2;          // row pairs (the last one may be a single row)
   real an[2][G::NB];
+  const real *rb = NV > 0 ? ride + k + i * G::N : nullptr;
 #pragma unroll
   for (int h = 0; h < 2; ++h)
 #pragma unroll
-    for (int K = 0; K < G::NB; ++K) an[h][K] = (h < G::NB) ? base[4 * K + 4 * h * G::LD] : 0.0;
+    for (int K = 0; K < G::NB; ++K) {
+      if (h < NBW) an[h][K] = base[4 * K + 4 * h * G::LD];
+      else if (NV > 0 && h == NBW) an[h][K] = (i < NV) ? rb[4 * K] : 0.0;   // (NBW = 1: the riding row pairs with row 0)
+      else an[h][K] = 0.0;
+    }
+  real ad[NZ > 0 ? NZ : 1];   // the diagonal fragments A(I, I) of the block rows I >= NBW
+#pragma unroll
+  for (int d = 0; d < NZ; ++d) ad[d] = base[4 * (NBW + d) + 4 * (NBW + d) * G::LD];
 #pragma unroll
   for (int Pp = 0; Pp < NP; ++Pp) {
     const int I0 = 2 * Pp;
-    const bool two = I0 + 1 < G::NB;
+    const bool two = I0 + 1 < NBW;
     real ac[2][G::NB];
 #pragma unroll
     for (int h = 0; h < 2; ++h)
@@ -175,11 +204,10 @@ __device__ __forceinline__ void q4_mul_c(const real *M, const real (&X)[Q4Geom<K
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int In = I0 + 2 + h;
-      if (In < G::NB) {
+      if (In < NBW) {
 #pragma unroll
         for (int K = 0; K < G::NB; ++K) an[h][K] = base[4 * K + 4 * In * G::LD];
-      } else if (NV > 0 && In == G::NB) {   // the riding block row follows the last operator row
-        const real *rb = ride + k + i * G::N;
+      } else if (NV > 0 && In == NBW) {   // the riding block row follows the last weighted operator row
 #pragma unroll
         for (int K = 0; K < G::NB; ++K) an[h][K] = (i < NV) ? rb[4 * K] : 0.0;
       }
@@ -190,40 +218,54 @@ __device__ __forceinline__ void q4_mul_c(const real *M, const real (&X)[Q4Geom<K
 #pragma unroll
     for (int K = 0; K < G::NB; ++K) {
 #pragma unroll
-      for (int J = 0; J < G::NJ; ++J) acc[I0][J] = mma4(ac[0][K], X[K][J], K == 0 ? (ZERO ? (real)0 : C0[I0][J]) : acc[I0][J]);
+      for (int J = 0; J < G::NJ; ++J)
+        if (Q4_XLIVE(K, J)) acc[I0][J] = mma4(ac[0][K], X[K][J], K == 0 ? (ZERO ? (real)0 : C0[I0][J]) : acc[I0][J]);
       if (two) {
 #pragma unroll
-        for (int J = 0; J < G::NJ; ++J) acc[I0 + 1][J] = mma4(ac[1][K], X[K][J], K == 0 ? (ZERO ? (real)0 : C0[I0 + 1][J]) : acc[I0 + 1][J]);
-      } else if (NV > 0) {   // odd NB: the riding row pairs with the last operator row
+        for (int J = 0; J < G::NJ; ++J)
+          if (Q4_XLIVE(K, J)) acc[I0 + 1][J] = mma4(ac[1][K], X[K][J], K == 0 ? (ZERO ? (real)0 : C0[I0 + 1][J]) : acc[I0 + 1][J]);
+      } else if (NV > 0) {   // odd NBW: the riding row pairs with the last weighted operator row
 #pragma unroll
-        for (int J = 0; J < G::NJ; ++J) (*accR)[J] = mma4(ac[1][K], X[K][J], (*accR)[J]);
+        for (int J = 0; J < G::NJ; ++J)
+          if (Q4_XLIVE(K, J)) (*accR)[J] = mma4(ac[1][K], X[K][J], (*accR)[J]);
       }
     }
 #if Q4_MUL_VARIANT != 1
     __builtin_amdgcn_sched_barrier(0);
 #endif
   }
-  if constexpr (NV > 0 && (G::NB % 2) == 0) {   // even NB: the riding row is requested into an[0] by the last pair
+  if constexpr (NV > 0 && (NBW % 2) == 0) {   // even NBW: the riding row is requested into an[0] by the last pair
 #pragma unroll
     for (int K = 0; K < G::NB; ++K) {
 #pragma unroll
-      for (int J = 0; J < G::NJ; ++J) (*accR)[J] = mma4(an[0][K], X[K][J], (*accR)[J]);
+      for (int J = 0; J < G::NJ; ++J)
+        if (Q4_XLIVE(K, J)) (*accR)[J] = mma4(an[0][K], X[K][J], (*accR)[J]);
     }
   }
+#pragma unroll
+  for (int d = 0; d < NZ; ++d) {   // block rows of zero-weight entries: the diagonal block's product, initial values elsewhere
+    const int I = NBW + d;
+#pragma unroll
+    for (int J = 0; J < G::NJ; ++J) {
+      const real c0 = ZERO ? (real)0 : C0[I][J];
+      acc[I][J] = (J == (I >> 2)) ? mma4(ad[d], X[I][J], c0) : c0;
+    }
+  }
+#undef Q4_XLIVE
 }
 
-template <int KS, int NV = 0>
+template <int KS, int NV = 0, int NBW = Q4Geom<KS>::NB>
 __device__ __forceinline__ void q4_mul(const real *M, const real (&X)[Q4Geom<KS>::NB][Q4Geom<KS>::NJ],
                                        real (&acc)[Q4Geom<KS>::NB][Q4Geom<KS>::NJ], const real *ride = nullptr,
                                        real (*accR)[Q4Geom<KS>::NJ] = nullptr) {
-  q4_mul_c<KS, NV>(M, X, acc, acc, ride, accR);
+  q4_mul_c<KS, NV, false, NBW>(M, X, acc, acc, ride, accR);
 }
 // acc = M^T X (the first k-block's C operand is the constant zero: no zeroing of the accumulators)
-template <int KS, int NV = 0>
+template <int KS, int NV = 0, int NBW = Q4Geom<KS>::NB>
 __device__ __forceinline__ void q4_mul_z(const real *M, const real (&X)[Q4Geom<KS>::NB][Q4Geom<KS>::NJ],
                                          real (&acc)[Q4Geom<KS>::NB][Q4Geom<KS>::NJ], const real *ride = nullptr,
                                          real (*accR)[Q4Geom<KS>::NJ] = nullptr) {
-  q4_mul_c<KS, NV, true>(M, X, acc, acc, ride, accR);
+  q4_mul_c<KS, NV, true, NBW>(M, X, acc, acc, ride, accR);
 }
 
 // Y = sum_{k < p} (M^T)^k C0 by Horner, Y <- C0 + M^T Y starting from Y = C0: p - 1 products at ONE product site (a second site
@@ -232,7 +274,7 @@ __device__ __forceinline__ void q4_mul_z(const real *M, const real (&X)[Q4Geom<K
 #ifndef Q4_HORNER_SITES
 #define Q4_HORNER_SITES 1
 #endif
-template <int KS>
+template <int KS, int NBW = Q4Geom<KS>::NB>
 __device__ __forceinline__ void q4_horner(const real *M, const real (&C0)[Q4Geom<KS>::NB][Q4Geom<KS>::NJ], int p,
                                           real (&Y)[Q4Geom<KS>::NB][Q4Geom<KS>::NJ]) {
   q4_copy<KS>(Y, C0);
@@ -243,12 +285,12 @@ __device__ __forceinline__ void q4_horner(const real *M, const real (&C0)[Q4Geom
 #pragma nounroll
   for (; n >= 2; n -= 2) {
     real Z[Q4Geom<KS>::NB][Q4Geom<KS>::NJ];
-    q4_mul_c<KS>(M, Y, C0, Z);
-    q4_mul_c<KS>(M, Z, C0, Y);
+    q4_mul_c<KS, 0, false, NBW>(M, Y, C0, Z);
+    q4_mul_c<KS, 0, false, NBW>(M, Z, C0, Y);
   }
   if (n == 1) {
     real acc[Q4Geom<KS>::NB][Q4Geom<KS>::NJ];
-    q4_mul_c<KS>(M, Y, C0, acc);
+    q4_mul_c<KS, 0, false, NBW>(M, Y, C0, acc);
     q4_copy<KS>(Y, acc);
   }
 #else
@@ -256,7 +298,7 @@ __device__ __forceinline__ void q4_horner(const real *M, const real (&C0)[Q4Geom
   for (int kk = 1; kk < p; ++kk) {
     real acc[Q4Geom<KS>::NB][Q4Geom<KS>::NJ];
     MOM_STAMP(74);
-    q4_mul_c<KS>(M, Y, C0, acc);
+    q4_mul_c<KS, 0, false, NBW>(M, Y, C0, acc);
 #ifdef MOM_DIAG_STAMPS
     if (kk == 1) { MOM_STAMP(75); } else { MOM_STAMP(77); }   // first round of a series (code fetched from L2?) against the later ones
     if (threadIdx.x == 0 && blockIdx.x == (gridDim.x >> 1)) mom_diag_acc[kk == 1 ? 78 : 79] += 1;
@@ -334,7 +376,7 @@ __device__ __forceinline__ void make_ctx_q4(Ctx &c, int N, int inv_mode, real *s
 // nd doubling steps (doubling.jl:43-68) on the quad-block layout; bail = true, nothing of the layer has left the wave, if a step
 // needs the general path.  In / out: c.r, c.t (plain, pitch N), c.jp, c.jm.  After the elemental layer c.ei, c.v1, c.v2 are free:
 // c.ei / c.v1 hold the riding vectors of the step (w1, w2 of doubling_step_strip).
-template <int KS>
+template <int KS, int NBW = Q4Geom<KS>::NB>
 __device__ __forceinline__ real doubling_run_q4(Ctx &c, int nd, real expk, bool &bail) {
   using G = Q4Geom<KS>;
   constexpr int N = G::N, NB = G::NB, NJ = G::NJ;
@@ -354,7 +396,7 @@ __device__ __forceinline__ real doubling_run_q4(Ctx &c, int nd, real expk, bool 
 #pragma unroll
       for (int J = 0; J < NJ; ++J) rj[J] = 0.0;
       // the vectors j0+, j0- sit in c.jp, c.jm = consecutive vectors (make_ctx_q4): ride base c.jp, vector 0 = j0+, 1 = j0-
-      q4_mul_z<KS, 2>(r, Rn, B, c.jp, &rj);
+      q4_mul_z<KS, 2, NBW>(r, Rn, B, c.jp, &rj);
 #pragma unroll
       for (int K = 0; K < NB; ++K)
 #pragma unroll
@@ -382,7 +424,7 @@ __device__ __forceinline__ real doubling_run_q4(Ctx &c, int nd, real expk, bool 
     MOM_STAMP(81);
     real Y[NB][NJ];
     // Y = A^T = (t (I - r r)^-1)^T by Horner: Y <- t^T + (r r)^T Y, p - 1 times starting from t^T (p >= 2 unless r r = 0)
-    q4_horner<KS>(P, T0, p, Y);
+    q4_horner<KS, NBW>(P, T0, p, Y);
     MOM_STAMP(71);
     real aw[NJ];   // lanes k == 0: (A w1)[col]; k == 1: (A w2)[col]
     real Tn[NB][NJ];
@@ -390,10 +432,10 @@ __device__ __forceinline__ real doubling_run_q4(Ctx &c, int nd, real expk, bool 
       real Zt[NB][NJ];
 #pragma unroll
       for (int J = 0; J < NJ; ++J) aw[J] = 0.0;
-      q4_mul_z<KS, 2>(r, Y, Zt, c.ei, &aw);    // (A r)^T ; riding rows (A w1)^T, (A w2)^T
-      q4_mul<KS>(t, Zt, Rn);                    // r^T + t^T (A r)^T      (:64)
+      q4_mul_z<KS, 2, NBW>(r, Y, Zt, c.ei, &aw);    // (A r)^T ; riding rows (A w1)^T, (A w2)^T
+      q4_mul<KS, 0, NBW>(t, Zt, Rn);                    // r^T + t^T (A r)^T      (:64)
     }
-    q4_mul_z<KS>(t, Y, Tn);                       // t^T A^T                (:67)
+    q4_mul_z<KS, 0, NBW>(t, Y, Tn);                       // t^T A^T                (:67)
     // last step: apply_D! (doubling.jl:93-110) and apply_D_SFI! (:112-118) ride on the write-back -- the rows of r-+ (columns of
     // its transpose held here) and j0- are scaled by sg
     const bool last = (it == nd - 1);
@@ -421,7 +463,7 @@ __device__ __forceinline__ real doubling_run_q4(Ctx &c, int nd, real expk, bool 
 // ScatteringInterface_11 (interaction.jl:69-117) in the algebra of interaction_strip / interaction_strip_lean.  Returns false,
 // nothing stored, if the series is too long.  Riding vectors: c.jm rides with r (column "N" of r = j0-); the composite J0+ is
 // fetched into c.v1 and rides with P = T++.
-template <int KS>
+template <int KS, int NBW = Q4Geom<KS>::NB>
 __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
   using G = Q4Geom<KS>;
   constexpr int N = G::N, NB = G::NB, NJ = G::NJ, NN = N * N;
@@ -457,7 +499,7 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
     {
       real rT[NB][NJ];
       q4_load_T<KS>(r, q, rT);
-      q4_mul_z<KS>(P, rT, Bs);
+      q4_mul_z<KS, 0, NBW>(P, rT, Bs);
     }
 #pragma unroll
     for (int K = 0; K < NB; ++K)
@@ -466,7 +508,7 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
     {
       real tT[NB][NJ];
       q4_load_T<KS>(t, q, tT);
-      q4_mul_z<KS>(P, tT, W0);
+      q4_mul_z<KS, 0, NBW>(P, tT, W0);
     }
     q4_fence();
     q4_store_T<KS>(P, q, Bs);   // P = B = r-+ R+-
@@ -486,7 +528,7 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
     real T1[NB][NJ];
     q4_load_glb_T<KS>(g.T_mm, q, T1);
     __builtin_amdgcn_sched_barrier(0);
-    q4_horner<KS>(P, W0, p, Y2);       // Y2 <- W0 + B^T Y2 : X^T, X = t++ R+- (I - B)^-1
+    q4_horner<KS, NBW>(P, W0, p, Y2);       // Y2 <- W0 + B^T Y2 : X^T, X = t++ R+- (I - B)^-1
 #pragma unroll
     for (int u = 0; u < UT; ++u) {
       const int e = lane + 64 * u;
@@ -498,7 +540,7 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
     }
     vj = (lane < N) ? g.J0p[lane] : 0.0;
     __builtin_amdgcn_sched_barrier(0);
-    q4_horner<KS>(P, T1, p, Y1);       // Y1 <- T--^T + B^T Y1 : T01^T
+    q4_horner<KS, NBW>(P, T1, p, Y1);       // Y1 <- T--^T + B^T Y1 : T01^T
   }
   q4_fence();
   MOM_STAMP(55);
@@ -519,15 +561,15 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
       real Yf[NB][NJ], o[NB][NJ];
       q4_copy<KS>(Yf, Y1);
       q4_flip<KS>(Yf, mask);
-      q4_mul_z<KS>(t, Yf, o);
+      q4_mul_z<KS, 0, NBW>(t, Yf, o);
       q4_flip<KS>(o, mask);
       q4_store_glb_T<KS>(g.T_mm, q, o);
     }
     real V[NB][NJ], Vr[NJ], Rr[NJ];
 #pragma unroll
     for (int J = 0; J < NJ; ++J) { Vr[J] = 0.0; Rr[J] = 0.0; }
-    q4_mul_z<KS, 1>(r, Y1, V, c.jm, &Vr);                 // (T01 r-+)^T ; riding row: (T01 j0-)^T
-    q4_mul<KS, 1>(P, V, Radd, c.v1, &Rr);               // R-+^T + T++^T (T01 r)^T ; riding row: (T01 r J0+)^T
+    q4_mul_z<KS, 1, NBW>(r, Y1, V, c.jm, &Vr);                 // (T01 r-+)^T ; riding row: (T01 j0-)^T
+    q4_mul<KS, 1, NBW>(P, V, Radd, c.v1, &Rr);               // R-+^T + T++^T (T01 r)^T ; riding row: (T01 r J0+)^T
     q4_store_glb_T<KS>(g.R_mp, q, Radd);
 #pragma unroll
     for (int J = 0; J < NJ; ++J) {
@@ -542,10 +584,10 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
     q4_load_T<KS>(t, q, T21);
 #pragma unroll
     for (int J = 0; J < NJ; ++J) { Tr[J] = 0.0; Or[J] = 0.0; }
-    q4_mul<KS, 1>(r, Y2, T21, c.jm, &Tr);               // riding row: (X j0-)^T = (T21 R+- j0-)^T
+    q4_mul<KS, 1, NBW>(r, Y2, T21, c.jm, &Tr);               // riding row: (X j0-)^T = (T21 R+- j0-)^T
     {
       real o[NB][NJ];
-      q4_mul_z<KS, 1>(P, T21, o, c.v1, &Or);              // (T21 T++)^T ; riding row: (T21 J0+)^T
+      q4_mul_z<KS, 1, NBW>(P, T21, o, c.v1, &Or);              // (T21 T++)^T ; riding row: (T21 J0+)^T
       q4_store_glb_T<KS>(g.T_pp, q, o);
     }
 #pragma unroll
@@ -563,7 +605,7 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
       for (int K = 0; K < NB; ++K) acc[K][J] = acc[K][J] * sc;
     }
     q4_flip<KS>(Y2, mask);
-    q4_mul<KS>(t, Y2, acc);
+    q4_mul<KS, 0, NBW>(t, Y2, acc);
     q4_flip<KS>(acc, mask);
     q4_store_glb_T<KS>(g.R_pm, q, acc);
   }
@@ -580,7 +622,7 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
 #else
 #define MOM_Q4_ATTR
 #endif
-template <int KS>
+template <int KS, int NBW = Q4Geom<KS>::NB>
 __global__ void __launch_bounds__(64) MOM_Q4_ATTR k_layer_q4(const LayerArgs a) {
   using G = Q4Geom<KS>;
   constexpr int N = G::N;
@@ -622,14 +664,14 @@ __global__ void __launch_bounds__(64) MOM_Q4_ATTR k_layer_q4(const LayerArgs a) 
       elemental_build(c, a.q, m, nd, tau_sum, dtau, varpi, zpp, zmp);
       MOM_STAMP(41);
       bool bail;
-      expk = doubling_run_q4<KS>(c, nd, expk, bail);
+      expk = doubling_run_q4<KS, NBW>(c, nd, expk, bail);
       if (!bail) {
         if (first) {
           store_added_as_composite(c, g);
           q4_fence();
           MOM_STAMP(42);
         } else {
-          bail = !interaction_q4<KS>(c, g);
+          bail = !interaction_q4<KS, NBW>(c, g);
         }
       }
       if (bail) {  // the full image redoes this layer and finishes the unit

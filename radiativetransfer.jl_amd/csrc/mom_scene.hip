@@ -110,6 +110,7 @@ int scene_common(mom_t *h, int Nz, int K, int M, const double *Zpp, const double
   h->Nk = Nk;
   h->qk = h->q;
   h->qk.N = Nk;
+  h->nbw_0 = 0;
   if (Nk == h->N) {
     HIPCHK(h, mom_upload(h->d_Zpp, Zpp, NN * K * M, h->stream));
     HIPCHK(h, mom_upload(h->d_Zmp, Zmp, NN * K * M, h->stream));
@@ -165,6 +166,7 @@ int scene_common(mom_t *h, int Nz, int K, int M, const double *Zpp, const double
             zp[i + (size_t)N0 * (j + (size_t)N0 * kb)] = Zpp[src];
             zm[i + (size_t)N0 * (j + (size_t)N0 * kb)] = Zmp[src];
           }
+      h->nbw_0 = mom_q4_nbw(wt0v.data(), N0);  // after the reduction to (I,Q) and the padding
       HIPCHK(h, mom_upload(h->d_mu0, mu0v.data(), (size_t)N0, h->stream));
       HIPCHK(h, mom_upload(h->d_wt0, wt0v.data(), (size_t)N0, h->stream));
       HIPCHK(h, mom_upload(h->d_sg0, sg0v.data(), (size_t)N0, h->stream));
@@ -482,10 +484,14 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, const Comp6 &co
   if (cont && can_sweep) can_sweep = (h->iface[za] == h->iface[za + 1]);
   for (int z = za; z < zb && can_sweep; ++z) can_sweep = (h->nd[z] <= 127);
   hipStream_t cur = h->stream;  // the stream launch_layer issues to (MOM_OPT_OVERLAP switches it for the m = 0 sub-problem)
-  auto launch_layer = [&](int z, const DevStreams &q, int m_first, int Mcount, const double *Zpp, const double *Zmp,
+  // nbw: LayerArgs::nbw of the stream set q (MOM_OPT_ZERO_SKIP = 0: none).  Full problem: from the weights mom_set_streams
+  // uploaded (the dummy entries behind the N real ones only lengthen the run of zero weights); sub-problem: scene_common's count
+  const int nbw_k = mom_q4_nbw(h->h_wt.data(), h->N);
+  auto launch_layer = [&](int z, const DevStreams &q, int nbw, int m_first, int Mcount, const double *Zpp, const double *Zmp,
                           const auto &comp, double *scratch) -> int {  // comp[6]: buffers or raw pointers
     LayerArgs a{};
     a.q = q; a.S = h->S; a.M = Mcount; a.K = h->K; a.m_first = m_first;
+    a.nbw = h->opt_zero_skip ? nbw : 0;
     const bool sweep = z < 0;
     if (sweep) {
       z = za;
@@ -540,7 +546,7 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, const Comp6 &co
         HIPCHK(h, hipEventRecord(h->ev_go, cur));
         HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_go, 0));
         HIPCHK(h, hipEventRecord(h->ev_red[2 * e], cur));
-        if ((rc = launch_layer(z, h->q0, 0, 1, h->d_Zpp0, h->d_Zmp0, h->comp0, h->d_scratch0))) return rc;
+        if ((rc = launch_layer(z, h->q0, h->nbw_0, 0, 1, h->d_Zpp0, h->d_Zmp0, h->comp0, h->d_scratch0))) return rc;
         HIPCHK(h, hipEventRecord(h->ev_red[2 * e + 1], cur));
         h->launches_red++;
         cur = h->stream;
@@ -549,19 +555,19 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, const Comp6 &co
         double *comp1[6];
         for (int k = 0; k < 6; ++k) comp1[k] = compF[k] + ((k < 4) ? (size_t)comp_pitch(Nk) * Nk : (size_t)Nk) * S;
         HIPCHK(h, hipEventRecord(h->ev_full[2 * e], h->stream));
-        if ((rc = launch_layer(z, h->qk, 1, M - 1, h->d_Zpp + NN * h->K, h->d_Zmp + NN * h->K, comp1, h->d_scratch))) return rc;
+        if ((rc = launch_layer(z, h->qk, nbw_k, 1, M - 1, h->d_Zpp + NN * h->K, h->d_Zmp + NN * h->K, comp1, h->d_scratch))) return rc;
         HIPCHK(h, hipEventRecord(h->ev_full[2 * e + 1], h->stream));
         h->launches_full++;
       }
       if (!two) {
         HIPCHK(h, hipEventRecord(h->ev_red[2 * e], h->stream));
-        if ((rc = launch_layer(z, h->q0, 0, 1, h->d_Zpp0, h->d_Zmp0, h->comp0, h->d_scratch0))) return rc;
+        if ((rc = launch_layer(z, h->q0, h->nbw_0, 0, 1, h->d_Zpp0, h->d_Zmp0, h->comp0, h->d_scratch0))) return rc;
         HIPCHK(h, hipEventRecord(h->ev_red[2 * e + 1], h->stream));
         h->launches_red++;
       }
     } else {
       HIPCHK(h, hipEventRecord(h->ev_full[2 * e], h->stream));
-      if ((rc = launch_layer(z, h->qk, 0, M, h->d_Zpp, h->d_Zmp, compF, h->d_scratch))) return rc;
+      if ((rc = launch_layer(z, h->qk, nbw_k, 0, M, h->d_Zpp, h->d_Zmp, compF, h->d_scratch))) return rc;
       HIPCHK(h, hipEventRecord(h->ev_full[2 * e + 1], h->stream));
       h->launches_full++;
     }

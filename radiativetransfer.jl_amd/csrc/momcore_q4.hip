@@ -1,6 +1,7 @@
 // momcore_q4.hip -- the quad-block image (mom_q4.hpp): one wavefront per (spectral point, moment) unit of an N = 36 / 40 problem,
 // v_mfma_f64_4x4x4_4b products, four units per CU.  One object per operator size N = 4 * MOM_STRIP_KS (KS = 9, 10), compiled with
-// -DMOM_WAVES=1 -DMOM_NS=momq.  Its entry in the image table: mom_images.hpp.
+// -DMOM_WAVES=1 -DMOM_NS=momq.  Its entry in the image table: mom_images.hpp.  An object holds the kernel once per instantiated
+// number of weighted block rows (MOM_OPT_ZERO_SKIP, LayerArgs::nbw): the image's launch function picks among them.
 #ifndef MOM_STRIP_KS
 #error "compile with -DMOM_STRIP_KS=<N/4>"
 #endif
@@ -13,21 +14,50 @@
 
 using namespace MOM_NS;
 
-static hipError_t image_launch(const void *layer_args, int, int grid, hipStream_t st) {
-  const LayerArgs a = *reinterpret_cast<const LayerArgs *>(layer_args);
+// The instantiations of the zero-skip rule (mom_q4.hpp q4_mul_c): NBW = NB - kSkip[v] block rows of weighted entries.  A rule for
+// FEWER zero blocks than the problem has is still exact, so a launch takes the smallest instantiated NBW >= LayerArgs::nbw:
+// one to four zero-weight streams of two to four components (the view angles, the Sun, a dummy stream) are 0, 1, 2 .. 4 blocks
+constexpr int kNB = MOM_STRIP_KS;
+constexpr int kSkip[] = {0, 1, 2, 4};
+static_assert(kNB > 4, "momcore_q4.hip: NB - 4 >= 1");
+template <int V>
+static const void *variant_fn() { return reinterpret_cast<const void *>(k_layer_q4<MOM_STRIP_KS, kNB - kSkip[V]>); }
+static int variant_for(int nbw) {
+  if (nbw < 1 || nbw > kNB) return 0;
+  int v = 0;
+  for (int c = 1; c < (int)(sizeof kSkip / sizeof kSkip[0]); ++c)
+    if (kNB - kSkip[c] >= nbw) v = c;
+  return v;
+}
+template <int V>
+static hipError_t launch_variant(const LayerArgs &a, int grid, hipStream_t st) {
   const size_t smem = q4_lds_bytes(4 * MOM_STRIP_KS);
-  hipError_t e = mom_allow_lds(reinterpret_cast<const void *>(k_layer_q4<MOM_STRIP_KS>), smem);
+  hipError_t e = mom_allow_lds(variant_fn<V>(), smem);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_layer_q4<MOM_STRIP_KS>), dim3(grid), dim3(64), smem, st, a);
+  hipLaunchKernelGGL((k_layer_q4<MOM_STRIP_KS, kNB - kSkip[V]>), dim3(grid), dim3(64), smem, st, a);
   return hipGetLastError();
 }
-// workgroups of this image a CU holds: by LDS and by the registers the compiler gave the kernel (occupancy API)
-static int query_per_cu() {
+static hipError_t image_launch(const void *layer_args, int, int grid, hipStream_t st) {
+  const LayerArgs a = *reinterpret_cast<const LayerArgs *>(layer_args);
+  switch (variant_for(a.nbw)) {
+    case 1: return launch_variant<1>(a, grid, st);
+    case 2: return launch_variant<2>(a, grid, st);
+    case 3: return launch_variant<3>(a, grid, st);
+    default: return launch_variant<0>(a, grid, st);
+  }
+}
+// workgroups of this image a CU holds: by LDS and by the registers the compiler gave the kernel (occupancy API); the least of the
+// instantiations, so that the persistent grid fits whichever of them a launch takes
+template <int V>
+static int query_variant_per_cu() {
   int nb = 0;
   const size_t smem = q4_lds_bytes(4 * MOM_STRIP_KS);
-  if (mom_allow_lds(reinterpret_cast<const void *>(k_layer_q4<MOM_STRIP_KS>), smem) != hipSuccess) return 4;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_layer_q4<MOM_STRIP_KS>, 64, smem) != hipSuccess || nb < 1) return 4;
+  if (mom_allow_lds(variant_fn<V>(), smem) != hipSuccess) return 4;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_layer_q4<MOM_STRIP_KS, kNB - kSkip[V]>, 64, smem) != hipSuccess || nb < 1) return 4;
   return nb;
+}
+static int query_per_cu() {
+  return std::min(std::min(query_variant_per_cu<0>(), query_variant_per_cu<1>()), std::min(query_variant_per_cu<2>(), query_variant_per_cu<3>()));
 }
 static int image_per_cu() {
   static const int per_cu = query_per_cu();  // (per process: the occupancy of an image does not depend on the handle)
