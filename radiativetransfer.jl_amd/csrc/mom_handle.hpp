@@ -18,14 +18,15 @@
 
 namespace momr { struct State; }  // mom_rrs.hpp
 
-struct mom_handle {
+// The resident scene's arrays and counts (d_mu ... d_scratch, Nz, K, nVza, scene_M, surf_kind, albedo, nd, iface) are the base:
+// MomSceneBufs, mom_host.hpp -- the declaration the Float32 scene shares
+struct mom_handle : MomSceneBufs<double> {
   int device = 0, N = 0, nS = 0, S = 0, M = 0;
   int dtype = 0;              // 0 = Float64, 1 = Float32 (scene-level path only, momcore_f32.hip)
   momf_scene *f32 = nullptr;
   bool lds_mode = true;
   int opt_inverse = 0, opt_force_generic = 0;
   hipStream_t stream = nullptr;
-  MomDevBuf<double> d_mu, d_wt, d_sg;
   mom::DevStreams q{};
   bool streams_set = false;
   std::vector<double> h_mu, h_wt;
@@ -50,12 +51,6 @@ struct mom_handle {
   MomDevBuf<double> d_vec[4];  // S-length temporaries (tau_sum, dtau, varpi, expk)
   MomDevBuf<double> d_Zop[2];
   // scene
-  int Nz = 0, K = 0, nVza = 0, scene_M = 0;
-  MomDevBuf<double> d_tau, d_varpi, d_zw, d_Zpp, d_Zmp, d_tau_sum, d_cos, d_sin, d_R, d_hdr, d_hdrJ, d_bhr_uw, d_bhr_dw;
-  double *d_T = nullptr;  // d_R + nVza nS S: R_SFI || T_SFI are ONE buffer (the all-gather's send buffer as it stands)
-  MomDevBuf<int> d_node;
-  std::vector<int> nd, iface;
-  double albedo = 0.0;
   bool scene_set = false;
   // m = 0 reduction (see mom_scene_set)
   int opt_m0 = 1;
@@ -65,7 +60,6 @@ struct mom_handle {
   int opt_overlap = 1;       // MOM_OPT_OVERLAP: the m = 0 sub-problem on a second (high-priority) stream of the handle
   hipStream_t stream2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_go = nullptr;
-  int surf_kind = 0;         // 0 Lambertian scalar, 1 BRDF matrices, 2 Lambertian Legendre (mom_scene_set_surface)
   // ForwardDiff.Dual run (mom_dual.hip): partials of the scene's inputs and of the outputs, the operator workspace
   int dual_P = 0;
   bool dual_ran = false;
@@ -73,7 +67,7 @@ struct mom_handle {
   MomDevBuf<double> d_dual_out, d_dual_ts;  // dR | dT [nVza,nS,S,P] x 2; d tau_sum [S,Nz+1,P]
   MomDevBuf<char> dual_work;
   size_t opt_dual_budget = 0;  // MOM_OPT_DUAL_WORKSPACE_MB (0: 60 % of the free HBM at the time of the run)
-  MomDevBuf<double> d_Rsurf, d_Rsurf0, d_albedo_spec, d_hdrJm;
+  MomDevBuf<double> d_Rsurf0;
   int opt_sweep = 1;       // one launch walks all layers of a unit (LayerArgs::Nz_sweep)
   MomDevBuf<double> comp_top[6];  // mom_rt_run_multisensor: composite state of the slab above a sensor
   MomDevBuf<double> d_msJ[2];     // interface fields dwJ, uwJ [Nk,S,M]
@@ -97,15 +91,11 @@ struct mom_handle {
   int Nk = 0;              // operator edge the scene-level kernels of the full problem run with (>= N)
   mom::DevStreams qk{};         // q with N = Nk
   int opt_small = 1;       // N <= 4: lane-per-point sweep kernel (mom_small.hip)
-  MomDevBuf<double> d_smtab;  // F1 | F2 | SI tables [3][N,N]
-  MomDevBuf<double> d_smpart; // N <= 4, one (point, moment) per lane: the per-moment terms of R_SFI / T_SFI [M][2][nVza,nS,S]
-  MomDevBuf<int> d_ndif;      // ndoubl | iface [2][Nz]
   bool red0 = false;
   int N0 = 0, nS0 = 0;
   mom::DevStreams q0{};
   MomDevBuf<double> d_mu0, d_wt0, d_sg0, d_Zpp0, d_Zmp0, d_hdrJ0, d_scratch0;
   MomDevBuf<double> comp0[6];
-  MomDevBuf<double> d_scratch;
   int G = 0;  // workgroups in generic mode
   int num_cu = 256;
   MomDevBuf<int> d_info;

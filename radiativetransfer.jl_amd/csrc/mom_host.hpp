@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -68,6 +69,79 @@ inline hipError_t mom_upload_as(MomDevBuf<T> &dst, const U *src, size_t count, h
   const hipError_t e = mom_upload(dst, v.data(), count, st), e2 = hipStreamSynchronize(st);
   return e != hipSuccess ? e : e2;
 }
+#pragma GCC visibility push(hidden)  // what follows is internal to libmomcore.so: the exports of the library are the C ABI's
+// The C ABI's Float64 host arrays <-> device memory of the handle's precision, into memory that exists.  double: the copy itself,
+// asynchronous on `st`.  float: rounded / widened through a staging vector, `st` drained before it dies.
+template <class Real>
+inline hipError_t mom_to_device(Real *dst, const double *src, size_t n, hipStream_t st) {
+  if constexpr (std::is_same<Real, double>::value) {
+    return hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, st);
+  } else {
+    const std::vector<Real> v(src, src + n);
+    const hipError_t e = hipMemcpyAsync(dst, v.data(), n * sizeof(Real), hipMemcpyHostToDevice, st), e2 = hipStreamSynchronize(st);
+    return e != hipSuccess ? e : e2;
+  }
+}
+template <class Real>
+inline hipError_t mom_to_host(double *dst, const Real *src, size_t n, hipStream_t st) {
+  if constexpr (std::is_same<Real, double>::value) {
+    return hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, st);
+  } else {
+    std::vector<Real> v(n);
+    const hipError_t e = hipMemcpyAsync(v.data(), src, n * sizeof(Real), hipMemcpyDeviceToHost, st), e2 = hipStreamSynchronize(st);
+    std::copy(v.begin(), v.end(), dst);
+    return e != hipSuccess ? e : e2;
+  }
+}
+
+// The resident scene of a handle, ONE declaration for both precisions: mom_handle derives from MomSceneBufs<double>, momf_scene from
+// MomSceneBufs<float>, and what both drivers do with a scene (the single-launch runs' argument blocks, the getters: below) reads
+// these names.  The azimuthal weights stay Float64 in both (the reference's host-side `bigCS`).
+template <class Real>
+struct MomSceneBufs {
+  int Nz = 0, K = 0, nVza = 0, scene_M = 0;  // scene_M: Fourier moments of the resident scene (<= the handle's M)
+  int surf_kind = 0;                         // 0 Lambertian scalar, 1 BRDF matrices, 2 Lambertian Legendre (mom_scene_set_surface)
+  Real albedo = 0;
+  std::vector<int> nd, iface;
+  MomDevBuf<Real> d_mu, d_wt, d_sg;
+  MomDevBuf<Real> d_tau, d_varpi, d_zw, d_tau_sum, d_Zpp, d_Zmp;
+  MomDevBuf<double> d_cos, d_sin;
+  MomDevBuf<int> d_node;
+  MomDevBuf<Real> d_R, d_hdr, d_hdrJ, d_hdrJm, d_bhr_uw, d_bhr_dw;
+  Real *d_T = nullptr;  // d_R + nVza nS S: R_SFI || T_SFI are ONE buffer (the all-gather's send buffer as it stands)
+  MomDevBuf<Real> d_Rsurf, d_albedo_spec;
+  MomDevBuf<Real> d_smtab;   // N <= 4: F1 | F2 | SI tables [3][N,N] of the lane-per-point kernel
+  MomDevBuf<Real> d_smpart;  // ... one (point, moment) per lane: the per-moment terms of R_SFI / T_SFI [M][2][nVza,nS,S]
+  MomDevBuf<int> d_ndif;     // ndoubl | iface [2][Nz] of the single-launch runs
+  MomDevBuf<Real> d_scratch;
+};
+
+// R / T and hdr / BHR of the resident scene into the caller's Float64 arrays (S spectral points, nS Stokes components)
+template <class Real>
+inline hipError_t mom_download_RT(const MomSceneBufs<Real> &b, int nS, int S, double *R, double *T, hipStream_t st) {
+  const size_t nout = (size_t)b.nVza * nS * S;
+  const hipError_t e = mom_to_host(R, b.d_R.get(), nout, st);
+  return e != hipSuccess ? e : mom_to_host(T, b.d_T, nout, st);
+}
+template <class Real>
+inline hipError_t mom_download_hdr(const MomSceneBufs<Real> &b, int nS, int S, double *hdr, double *up, double *dw, hipStream_t st) {
+  hipError_t e = mom_to_host(hdr, b.d_hdr.get(), (size_t)b.nVza * nS * S, st);
+  if (e == hipSuccess) e = mom_to_host(up, b.d_bhr_uw.get(), (size_t)nS * S, st);
+  return e != hipSuccess ? e : mom_to_host(dw, b.d_bhr_dw.get(), (size_t)nS * S, st);
+}
+
+// the four stage times of a run from its events ev[0..3]: layers, surface, post-processing, total (ms)
+inline hipError_t mom_stage_times(const hipEvent_t *ev, double *ms) {
+  hipError_t e = hipEventSynchronize(ev[3]);
+  const int from[4] = {0, 1, 2, 0}, to[4] = {1, 2, 3, 3};
+  for (int k = 0; k < 4 && e == hipSuccess; ++k) {
+    float t = 0.f;
+    e = hipEventElapsedTime(&t, ev[from[k]], ev[to[k]]);
+    ms[k] = t;
+  }
+  return e;
+}
+#pragma GCC visibility pop
 
 // Scene-level path: an operator edge N for which no strip-chained kernel image exists is padded with up to 4 DUMMY
 // STREAM ENTRIES (mu = 1, weight 0, zero rows and columns in every phase-matrix basis and BRDF matrix) when that
@@ -233,6 +307,68 @@ struct MomWaveSweepArgsT {
 };
 using MomWaveSweepArgs = MomWaveSweepArgsT<double>;   // Float64 wave-per-point sweep (mom_wave.hip)
 using MomWaveSweepArgsF = MomWaveSweepArgsT<float>;   // Float32 build of the same kernels (mom_wave.hip with -DMOMW_FLOAT)
+
+#pragma GCC visibility push(hidden)
+// ---- The single-launch runs up to their launch, written once for both drivers over MomSceneBufs<Real>.  `Streams` is the driver's
+// DevStreams (mom:: or momf::, mom_kernels.hpp), with N the edge the scene runs on.  The nd | iface upload, the launch (momsm_ /
+// momsmf_, momw_ / momwf_launch_sweep) and the timing events around it stay with each driver.
+// What the two argument blocks have in common
+template <class Args, class Real, class Streams>
+inline void mom_fill_sweep_scene(Args &a, const MomSceneBufs<Real> &b, const Streams &q, int S, int *info) {
+  a.S = S; a.M = b.scene_M; a.K = b.K; a.Nz = b.Nz; a.nVza = b.nVza; a.nS = q.nS; a.imu0 = q.imu0;
+  a.mu0 = q.mu0; a.albedo = b.albedo;
+  for (int k = 0; k < 4; ++k) { a.I0[k] = q.I0[k]; a.D[k] = q.D[k]; }
+  a.mu = b.d_mu; a.wt = b.d_wt; a.sg = b.d_sg;
+  a.Zpp = b.d_Zpp; a.Zmp = b.d_Zmp;
+  a.nd = b.d_ndif; a.node = b.d_node; a.cos_mphi = b.d_cos; a.sin_mphi = b.d_sin;
+  a.tau = b.d_tau; a.varpi = b.d_varpi; a.zw = b.d_zw; a.tau_sum = b.d_tau_sum;
+  a.R = b.d_R; a.T = b.d_T; a.hdr = b.d_hdr; a.bhr_uw = b.d_bhr_uw; a.bhr_dw = b.d_bhr_dw;
+  a.info = info;
+}
+// N <= 4, one spectral point per lane.  F1 | F2 | SI [3][16] from the host copy of the streams: mu_j/(mu_i + mu_j),
+// mu_j/(mu_i - mu_j), (1/mu_i) + (1/mu_j) -- the expressions of elemental.jl:176-186 in Real, evaluated once
+template <class Real>
+inline void mom_small_tables(const Real *mu, int N, Real *tab /* [48] */) {
+  std::fill(tab, tab + 48, Real(0));
+  for (int j = 0; j < N; ++j)
+    for (int i = 0; i < N; ++i) {
+      const Real mui = mu[i], muj = mu[j];
+      tab[i + N * j] = muj / (mui + muj);
+      tab[16 + i + N * j] = muj / (mui - muj);
+      tab[32 + i + N * j] = (1 / mui) + (1 / muj);
+    }
+}
+// its argument block: tables in d_smtab, nd | iface in d_ndif.  `split` (MOM_OPT_SMALL_N = 1) and more than one moment: one
+// (point, moment) per lane (mom_small.hip SPLIT), which needs the grow-only part buffer
+template <class Real, class Streams>
+inline hipError_t mom_fill_small_args(MomSmallSweepArgsT<Real> &a, MomSceneBufs<Real> &b, const Streams &q, int S, int *info, bool split,
+                                      hipStream_t st) {
+  mom_fill_sweep_scene(a, b, q, S, info);
+  a.F1 = b.d_smtab; a.F2 = b.d_smtab + 16; a.SI = b.d_smtab + 32;
+  a.iface = b.d_ndif + b.Nz;
+  if (!(a.M > 1 && split)) return hipSuccess;
+  const hipError_t e = b.d_smpart.reserve((size_t)a.M * 2 * a.nVza * a.nS * a.S, st);
+  a.part = b.d_smpart;
+  return e;
+}
+// 4 < N <= 32, one spectral point per wavefront.  The kernel covers ScatteringInterface_11 (code 3) on every layer after the first
+// and at the surface; `small_n` / `force_generic`: MOM_OPT_SMALL_N, MOM_OPT_FORCE_GENERIC
+template <class Real>
+inline bool mom_wave_sweep_applies(const MomSceneBufs<Real> &b, int N, int nS, bool small_n, bool force_generic) {
+  if (!(N > 4 && N <= 32 && small_n && !force_generic && b.nVza * nS <= 256)) return false;
+  for (int z = 1; z < b.Nz; ++z)
+    if (b.iface[z] != 3) return false;
+  return b.iface[b.Nz - 1] == 3;
+}
+// points per wavefront (mom_wave.hip, block-diagonal packing; k_wsweep's PK); `pack`: MOM_OPT_SMALL_N = 1 (2 keeps one point per wave)
+inline int mom_wave_points(int N, bool pack) { return pack ? (N == 5 ? 3 : (N >= 6 && N <= 8 ? 2 : 1)) : 1; }
+template <class Real, class Streams>
+inline void mom_fill_wave_args(MomWaveSweepArgsT<Real> &a, const MomSceneBufs<Real> &b, const Streams &q, int S, int *info, bool pack) {
+  mom_fill_sweep_scene(a, b, q, S, info);
+  a.N = q.N; a.inv_mode = q.inv_mode; a.pad = mom_wave_points(q.N, pack);
+  a.surf_kind = b.surf_kind; a.Rsurf = b.d_Rsurf; a.albedo_spec = b.d_albedo_spec;
+}
+#pragma GCC visibility pop
 
 // ---- entry points between the translation units: declarations only (no device code, nothing that depends on MOM_NS / MOM_REAL).
 // Every unit that defines one of them includes this header, so a definition is checked against what its callers see.

@@ -5,6 +5,7 @@
 // parameters_from_yaml.jl:160, gpu_batched.jl:45-58).
 #pragma once
 #include "mom_entry.hpp"
+#include "mom_host.hpp"
 
 namespace MOM_NS {
 
@@ -173,5 +174,38 @@ __global__ void __launch_bounds__(kThreads) k_batched_mul(BlasArgs a) {
     __syncthreads();
   }
 }
+
+#pragma GCC visibility push(hidden)
+// Host side of mom_batch_inv / mom_batched_mul, one text for both builds like the kernels above: the C ABI's Float64 arrays go
+// through the grow-only workspace ws[0..3] (A, C, B, generic-mode scratch; elements of W: the Float64 handle's byte buffers, the
+// Float32 scene's float buffers) in this build's `real`; operators in
+// LDS up to n = 64 unless MOM_OPT_FORCE_GENERIC, else at most 1024 workgroups on global slabs (zeroed: zero_padding reads them)
+template <class W>
+inline hipError_t batched_run(hipStream_t st, MomDevBuf<W> *ws, int *d_info, bool force_generic, int n, int batch, const double *A,
+                              const double *B, double *C, bool inv) {
+  const size_t cnt = (size_t)n * n * batch;
+  const auto workspace = [&](int k, size_t elems, real *&p) {
+    const hipError_t e = ws[k].reserve(elems * sizeof(real) / sizeof(W), st);
+    p = reinterpret_cast<real *>(ws[k].get());
+    return e;
+  };
+  real *dA = nullptr, *dB = nullptr, *dC = nullptr, *scr = nullptr;
+  hipError_t e;
+  if ((e = workspace(0, cnt, dA)) != hipSuccess || (e = workspace(1, cnt, dC)) != hipSuccess) return e;
+  if ((e = mom_to_device(dA, A, cnt, st)) != hipSuccess) return e;
+  if (!inv && ((e = workspace(2, cnt, dB)) != hipSuccess || (e = mom_to_device(dB, B, cnt, st)) != hipSuccess)) return e;
+  const bool lds = n <= 64 && !force_generic;
+  const int grid = lds ? batch : std::min(batch, 1024);
+  if (!lds) {
+    const size_t scn = (size_t)grid * kGenericBufs * mat_elems(n) + (size_t)ld_for(n) * np_for(n);
+    if ((e = workspace(3, scn, scr)) != hipSuccess || (e = hipMemsetAsync(scr, 0, scn * sizeof(real), st)) != hipSuccess) return e;
+  }
+  BlasArgs a{n, batch, dA, dB, dC, scr, d_info};
+  const size_t sm = lds_bytes(n, lds);
+  e = inv ? mom_launch_ldsm(MOM_LDSM(k_batch_inv), lds, grid, kThreads, sm, st, a)
+          : mom_launch_ldsm(MOM_LDSM(k_batched_mul), lds, grid, kThreads, sm, st, a);
+  return e != hipSuccess ? e : mom_to_host(C, dC, cnt, st);
+}
+#pragma GCC visibility pop
 
 }  // namespace MOM_NS

@@ -3,6 +3,7 @@
 // points, the getters.  Handle and shared helpers: mom_handle.hpp.
 #include "mom_handle.hpp"
 #include "mom_images.hpp"
+#include "mom_reduce.hpp"
 
 using namespace mom;
 
@@ -135,43 +136,27 @@ int scene_common(mom_t *h, int Nz, int K, int M, const double *Zpp, const double
   }
   // ---- m = 0 reduction (include/momcore.h): conditions checked on the data, bitwise
   {
-    const int N = h->N, nS = h->nS, Nq = N / nS;
-    bool ok = h->opt_m0 && nS >= 3 && h->q.regular && !(N <= 4 && h->opt_small && nVza <= 4 && K <= 4);
-    for (int k = 2; k < nS && ok; ++k) ok = (h->q.I0[k] == 0.0);
-    for (int kb = 0; kb < K && ok; ++kb)
-      for (int j = 0; j < N && ok; ++j)
-        for (int i = 0; i < N; ++i) {
-          if (((i % nS) < 2) == ((j % nS) < 2)) continue;
-          const size_t o = i + (size_t)N * (j + (size_t)N * kb);  // moment 0 block
-          if (Zpp[o] != 0.0 || Zmp[o] != 0.0) { ok = false; break; }
-        }
+    const int N = h->N, nS = h->nS;
+    const bool ok = h->opt_m0 && nS >= 3 && h->q.regular && !(N <= 4 && h->opt_small && nVza <= 4 && K <= 4) &&
+                    mom_m0_reducible(h->q.I0, N, nS, K, Zpp, Zmp);
     for (MomDevBuf<double> *b : {&h->d_mu0, &h->d_wt0, &h->d_sg0, &h->d_Zpp0, &h->d_Zmp0, &h->d_hdrJ0, &h->d_scratch0}) b->reset();
     for (auto &b : h->comp0) b.reset();
     h->red0 = ok;
     if (ok) {
       // N0r real entries; the kernels run on N0 >= N0r (dummy entries of strip_pad at the end: mu = 1, weight 0, Z = 0)
-      const int nS0 = 2, N0r = nS0 * Nq;
+      const int nS0 = kMomM0Stokes, N0r = mom_m0_edge(N, nS);
       int N0 = h->opt_pad ? strip_pad(N0r) : N0r;
       // r6: sub-problems of edge 18 .. 30 that are not a multiple of 4 take ONE dummy stream (two entries) to reach a quad-block
       // size (20, 24, 28, 32: mom_q4.hpp; IQUV scenes of 9 .. 15 streams)
       if (h->opt_pad && h->opt_lean >= 3 && N0 == N0r && N0r > 16 && N0r < 32 && (N0r % 4) != 0) N0 = N0r + 2;
       h->N0 = N0; h->nS0 = nS0;
-      std::vector<double> mu0v(N0, 1.0), wt0v(N0, 0.0), sg0v(N0, 1.0), zp((size_t)N0 * N0 * K, 0.0), zm((size_t)N0 * N0 * K, 0.0);
-      auto full = [&](int i0) { return (i0 / nS0) * nS + (i0 % nS0); };
-      for (int i = 0; i < N0r; ++i) { mu0v[i] = h->h_mu[full(i)]; wt0v[i] = h->h_wt[full(i)]; }
-      for (int kb = 0; kb < K; ++kb)
-        for (int j = 0; j < N0r; ++j)
-          for (int i = 0; i < N0r; ++i) {
-            const size_t src = full(i) + (size_t)N * (full(j) + (size_t)N * kb);
-            zp[i + (size_t)N0 * (j + (size_t)N0 * kb)] = Zpp[src];
-            zm[i + (size_t)N0 * (j + (size_t)N0 * kb)] = Zmp[src];
-          }
-      h->nbw_0 = mom_q4_nbw(wt0v.data(), N0);  // after the reduction to (I,Q) and the padding
-      HIPCHK(h, mom_upload(h->d_mu0, mu0v.data(), (size_t)N0, h->stream));
-      HIPCHK(h, mom_upload(h->d_wt0, wt0v.data(), (size_t)N0, h->stream));
-      HIPCHK(h, mom_upload(h->d_sg0, sg0v.data(), (size_t)N0, h->stream));
-      HIPCHK(h, mom_upload(h->d_Zpp0, zp.data(), zp.size(), h->stream));
-      HIPCHK(h, mom_upload(h->d_Zmp0, zm.data(), zm.size(), h->stream));
+      const MomM0Cut cut = mom_m0_cut(h->h_mu.data(), h->h_wt.data(), N, nS, K, N0, Zpp, Zmp);
+      h->nbw_0 = mom_q4_nbw(cut.wt.data(), N0);  // after the reduction to (I,Q) and the padding
+      HIPCHK(h, mom_upload(h->d_mu0, cut.mu.data(), (size_t)N0, h->stream));
+      HIPCHK(h, mom_upload(h->d_wt0, cut.wt.data(), (size_t)N0, h->stream));
+      HIPCHK(h, mom_upload(h->d_sg0, cut.sg.data(), (size_t)N0, h->stream));
+      HIPCHK(h, mom_upload(h->d_Zpp0, cut.Zpp.data(), cut.Zpp.size(), h->stream));
+      HIPCHK(h, mom_upload(h->d_Zmp0, cut.Zmp.data(), cut.Zmp.size(), h->stream));
       for (int k = 0; k < 6; ++k) {
         const size_t cnt = ((k < 4) ? (size_t)comp_pitch(N0) * N0 : (size_t)N0) * S;
         HIPCHK(h, h->comp0[k].renew(cnt));
@@ -221,17 +206,8 @@ extern "C" int mom_scene_set_surface(mom_t *h, int kind, int M, const double *Rs
     HIPCHK(h, h->d_hdrJm.renew((size_t)h->Nk * S * M));
     if (h->red0) {
       // moment 0 runs on the (I,Q) sub-problem: its surface matrix must not couple (I,Q) with (U,V) either
-      const int nS0 = h->nS0, N0 = h->N0;
-      std::vector<double> r0((size_t)N0 * N0);
-      for (int j = 0; j < N; ++j)
-        for (int i = 0; i < N; ++i) {
-          const bool iq_i = (i % nS) < nS0, iq_j = (j % nS) < nS0;
-          const double v = Rsurf[i + (size_t)N * j];
-          if (iq_i != iq_j && v != 0.0)
-            return fail(h, MOM_EINVAL, "mom_scene_set_surface: the m = 0 BRDF matrix couples (I,Q) with (U,V); set "
-                                       "MOM_OPT_M0_REDUCTION = 0 before mom_scene_set for this surface");
-          if (iq_i && iq_j) r0[(i / nS) * nS0 + (i % nS) + (size_t)N0 * ((j / nS) * nS0 + (j % nS))] = v;
-        }
+      std::vector<double> r0;
+      if (!mom_m0_cut_brdf(Rsurf, N, nS, h->N0, r0)) return fail(h, MOM_EINVAL, kMomM0BrdfCouples);
       HIPCHK(h, mom_upload(h->d_Rsurf0, r0.data(), r0.size(), h->stream));
     }
   } else if (kind == 2) {
@@ -241,8 +217,6 @@ extern "C" int mom_scene_set_surface(mom_t *h, int kind, int M, const double *Rs
   h->surf_kind = kind;
   return MOM_OK;
 }
-
-using SmallSweepArgs = MomSmallSweepArgs;  // mom_host.hpp
 
 // The runs that are ONE launch (rt_run_small, rt_run_wave) between the handle's timing events: the launch is the whole "full
 // layers" stage, the surface and post-processing stages are empty
@@ -259,80 +233,37 @@ static int single_launch_end(mom_t *h) {
   return MOM_OK;
 }
 
-// N <= 4: one spectral point per lane, all moments / layers / surface / post-processing in ONE launch
+// N <= 4: one spectral point per lane, all moments / layers / surface / post-processing in ONE launch (arguments: mom_host.hpp)
 static int rt_run_small(mom_t *h) {
-  const int N = h->N, Nz = h->Nz;
+  const int Nz = h->Nz;
   if (!h->d_smtab) HIPCHK(h, h->d_smtab.renew(3 * 16));
-  {  // mu_j/(mu_i + mu_j), mu_j/(mu_i - mu_j), (1/mu_i) + (1/mu_j): the expressions of elemental.jl:176-186, evaluated once
-    double tab[48] = {0};
-    for (int j = 0; j < N; ++j)
-      for (int i = 0; i < N; ++i) {
-        const double mui = h->h_mu[i], muj = h->h_mu[j];
-        tab[i + N * j] = muj / (mui + muj);
-        tab[16 + i + N * j] = muj / (mui - muj);
-        tab[32 + i + N * j] = (1 / mui) + (1 / muj);
-      }
-    HIPCHK(h, hipMemcpyAsync(h->d_smtab, tab, sizeof tab, hipMemcpyHostToDevice, h->stream));
-  }
+  double tab[48];
+  mom_small_tables(h->h_mu.data(), h->N, tab);
+  HIPCHK(h, hipMemcpyAsync(h->d_smtab, tab, sizeof tab, hipMemcpyHostToDevice, h->stream));
   {
     HIPCHK(h, h->d_ndif.reserve(2 * (size_t)Nz, h->stream));
     std::vector<int> v(h->nd);
     v.insert(v.end(), h->iface.begin(), h->iface.end());
     HIPCHK(h, hipMemcpyAsync(h->d_ndif, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));  // the host vectors above go out of scope
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // the host arrays above go out of scope
   }
-  SmallSweepArgs a{};
-  a.S = h->S; a.M = h->scene_M; a.K = h->K; a.Nz = Nz; a.nVza = h->nVza; a.nS = h->nS; a.imu0 = h->q.imu0;
-  a.mu0 = h->q.mu0; a.albedo = h->albedo;
-  for (int k = 0; k < 4; ++k) { a.I0[k] = h->q.I0[k]; a.D[k] = h->q.D[k]; }
-  a.mu = h->d_mu; a.wt = h->d_wt; a.sg = h->d_sg;
-  a.F1 = h->d_smtab; a.F2 = h->d_smtab + 16; a.SI = h->d_smtab + 32;
-  a.Zpp = h->d_Zpp; a.Zmp = h->d_Zmp;
-  a.nd = h->d_ndif; a.iface = h->d_ndif + Nz; a.node = h->d_node; a.cos_mphi = h->d_cos; a.sin_mphi = h->d_sin;
-  a.tau = h->d_tau; a.varpi = h->d_varpi; a.zw = h->d_zw; a.tau_sum = h->d_tau_sum;
-  a.R = h->d_R; a.T = h->d_T; a.hdr = h->d_hdr; a.bhr_uw = h->d_bhr_uw; a.bhr_dw = h->d_bhr_dw;
-  a.info = h->d_info;
   if (h->K > 4) return fail(h, MOM_EINVAL, "mom_rt_run: the N <= 4 sweep kernel handles at most 4 phase-matrix bases");
-  if (a.M > 1 && h->opt_small != 2) {  // one (point, moment) per lane (mom_small.hip SPLIT); MOM_OPT_SMALL_N = 2: one point per lane
-    const size_t need = (size_t)a.M * 2 * a.nVza * a.nS * a.S;
-    HIPCHK(h, h->d_smpart.reserve(need, h->stream));
-    a.part = h->d_smpart;
-  }
+  MomSmallSweepArgs a{};
+  HIPCHK(h, mom_fill_small_args(a, *h, h->q, h->S, h->d_info, h->opt_small != 2, h->stream));
   int rc = single_launch_begin(h);
   if (rc) return rc;
-  HIPCHK(h, momsm_launch_sweep(&a, N, h->stream));
+  HIPCHK(h, momsm_launch_sweep(&a, h->N, h->stream));
   return single_launch_end(h);
 }
 
-using WaveSweepArgs = MomWaveSweepArgs;  // mom_host.hpp
-
-// the wave-per-point kernel covers ScatteringInterface_11 on every layer after the first and at the surface
-static bool wave_sweep_applies(const mom_t *h) {
-  if (!(h->N > 4 && h->N <= 32 && h->opt_small && !h->opt_force_generic && h->nVza * h->nS <= 256)) return false;
-  for (int z = 1; z < h->Nz; ++z)
-    if (h->iface[z] != 3) return false;
-  return h->iface[h->Nz - 1] == 3;
-}
-
 // 4 < N <= 32: one spectral point per wavefront, operators in MFMA-layout registers, ONE launch
+static bool wave_sweep_applies(const mom_t *h) { return mom_wave_sweep_applies(*h, h->N, h->nS, h->opt_small, h->opt_force_generic); }
 static int rt_run_wave(mom_t *h) {
   const int Nz = h->Nz;
   HIPCHK(h, h->d_ndif.reserve(2 * (size_t)Nz, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->d_ndif, h->nd.data(), (size_t)Nz * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  WaveSweepArgs a{};
-  a.N = h->N; a.S = h->S; a.M = h->scene_M; a.K = h->K; a.Nz = Nz; a.nVza = h->nVza; a.nS = h->nS; a.imu0 = h->q.imu0;
-  a.inv_mode = h->opt_inverse;
-  // points per wavefront (mom_wave.hip, block-diagonal packing): MOM_OPT_SMALL_N = 2 keeps one point per wave
-  a.pad = (h->opt_small == 1) ? (h->N == 5 ? 3 : (h->N >= 6 && h->N <= 8 ? 2 : 1)) : 1;
-  a.mu0 = h->q.mu0; a.albedo = h->albedo;
-  for (int k = 0; k < 4; ++k) { a.I0[k] = h->q.I0[k]; a.D[k] = h->q.D[k]; }
-  a.mu = h->d_mu; a.wt = h->d_wt; a.sg = h->d_sg;
-  a.Zpp = h->d_Zpp; a.Zmp = h->d_Zmp;
-  a.nd = h->d_ndif; a.node = h->d_node; a.cos_mphi = h->d_cos; a.sin_mphi = h->d_sin;
-  a.tau = h->d_tau; a.varpi = h->d_varpi; a.zw = h->d_zw; a.tau_sum = h->d_tau_sum;
-  a.R = h->d_R; a.T = h->d_T; a.hdr = h->d_hdr; a.bhr_uw = h->d_bhr_uw; a.bhr_dw = h->d_bhr_dw;
-  a.info = h->d_info;
-  a.surf_kind = h->surf_kind; a.Rsurf = h->d_Rsurf; a.albedo_spec = h->d_albedo_spec;
+  MomWaveSweepArgs a{};
+  mom_fill_wave_args(a, *h, h->q, h->S, h->d_info, h->opt_small == 1);
   int rc = single_launch_begin(h);
   if (rc) return rc;
   HIPCHK(h, momw_launch_sweep(&a, h->stream));
@@ -884,9 +815,7 @@ extern "C" int mom_get_RT(mom_t *h, double *R_SFI, double *T_SFI) {
     const int rc = momf_get_RT(h->f32, R_SFI, T_SFI);
     return rc ? fail(h, rc, momf_error(h->f32)) : check_info(h);
   }
-  const size_t bytes = (size_t)h->nVza * h->nS * h->S * sizeof(double);
-  HIPCHK(h, hipMemcpyAsync(R_SFI, h->d_R, bytes, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(T_SFI, h->d_T, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, mom_download_RT(*h, h->nS, h->S, R_SFI, T_SFI, h->stream));
   return check_info(h);
 }
 
@@ -898,9 +827,7 @@ extern "C" int mom_get_hdr(mom_t *h, double *hdr, double *bhr_uw, double *bhr_dw
     const int rc = momf_get_hdr(h->f32, hdr, bhr_uw, bhr_dw);
     return rc ? fail(h, rc, momf_error(h->f32)) : check_info(h);
   }
-  HIPCHK(h, hipMemcpyAsync(hdr, h->d_hdr, (size_t)h->nVza * h->nS * h->S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(bhr_uw, h->d_bhr_uw, (size_t)h->nS * h->S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(bhr_dw, h->d_bhr_dw, (size_t)h->nS * h->S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, mom_download_hdr(*h, h->nS, h->S, hdr, bhr_uw, bhr_dw, h->stream));
   return check_info(h);
 }
 

@@ -518,34 +518,7 @@ static int blas_common(mom_t *h, int n, int batch, const double *A, const double
     if (rc) return fail(h, rc, momf_error(h->f32));
     return inv ? check_info(h) : MOM_OK;
   }
-  const size_t cnt = (size_t)n * n * batch;
-  double *dA = nullptr, *dB = nullptr, *dC = nullptr, *scr = nullptr;
-  HIPCHK(h, h->ws[0].reserve(cnt * sizeof(double), h->stream));
-  dA = reinterpret_cast<double *>(h->ws[0].get());
-  HIPCHK(h, h->ws[1].reserve(cnt * sizeof(double), h->stream));
-  dC = reinterpret_cast<double *>(h->ws[1].get());
-  HIPCHK(h, hipMemcpyAsync(dA, A, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (!inv) {
-    HIPCHK(h, h->ws[2].reserve(cnt * sizeof(double), h->stream));
-    dB = reinterpret_cast<double *>(h->ws[2].get());
-    HIPCHK(h, hipMemcpyAsync(dB, B, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  }
-  const bool lds = n <= 64 && !h->opt_force_generic;
-  const int grid = lds ? batch : std::min(batch, 1024);
-  if (!lds) {
-    const size_t scn = (size_t)grid * kGenericBufs * mat_elems(n) + (size_t)ld_for(n) * np_for(n);
-    HIPCHK(h, h->ws[3].reserve(scn * sizeof(double), h->stream));
-    scr = reinterpret_cast<double *>(h->ws[3].get());
-    HIPCHK(h, hipMemsetAsync(scr, 0, scn * sizeof(double), h->stream));
-  }
-  BlasArgs a{n, batch, dA, dB, dC, scr, h->d_info};
-  const size_t sm = lds_bytes(n, lds);
-  if (inv) {
-    HIPCHK(h, mom_launch_ldsm(MOM_LDSM(k_batch_inv), lds, grid, kThreads, sm, h->stream, a));
-  } else {
-    HIPCHK(h, mom_launch_ldsm(MOM_LDSM(k_batched_mul), lds, grid, kThreads, sm, h->stream, a));
-  }
-  HIPCHK(h, hipMemcpyAsync(C, dC, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, batched_run(h->stream, h->ws, h->d_info, h->opt_force_generic != 0, n, batch, A, B, C, inv));  // mom_ops.hpp
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return inv ? check_info(h) : MOM_OK;
 }
@@ -735,13 +708,7 @@ extern "C" int mom_timers(mom_t *h, double *ms, int n, int *kernel_launches) {
     if (kernel_launches) *kernel_launches = nl;
     return MOM_OK;
   }
-  HIPCHK(h, hipEventSynchronize(h->ev[3]));
-  float t01, t12, t23, t03;
-  HIPCHK(h, hipEventElapsedTime(&t01, h->ev[0], h->ev[1]));
-  HIPCHK(h, hipEventElapsedTime(&t12, h->ev[1], h->ev[2]));
-  HIPCHK(h, hipEventElapsedTime(&t23, h->ev[2], h->ev[3]));
-  HIPCHK(h, hipEventElapsedTime(&t03, h->ev[0], h->ev[3]));
-  ms[0] = t01; ms[1] = t12; ms[2] = t23; ms[3] = t03;
+  HIPCHK(h, mom_stage_times(h->ev, ms));
   if (n >= 8) {  // per-kernel sums: full-problem layer launches, reduced (m = 0) layer launches
     double full = 0.0, red = 0.0;
     float t;

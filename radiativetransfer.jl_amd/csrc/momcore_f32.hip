@@ -9,7 +9,10 @@
 // post-processing; r4: the strip-chained images of the 8-wave build (N = 44, 52, 56, 60: momcore_strip.hip compiled for
 // float, families F32_STRIP8 / F32_STRIP4 of mom_images.hpp), the (I,Q) reduction of moment 0 (a nested sub-scene: momf_scene::sub) and the padding of
 // other edges to the strip sizes (strip_pad_f), and the operator-level API on dtype = 1 handles (mom_ops.hpp compiled for float:
-// mom_elemental ... mom_download).  Not built for f32: multi-sensor, RRS, the device-side optics route.
+// mom_elemental ... mom_download); r6: the device-side optics route (momf_scene_set_dev: the layer optics assembled in Float64 on the
+// device, rounded there).  Not built for f32: multi-sensor, RRS, the Dual run.
+//
+// What this driver shares with the Float64 one, and what stays apart on purpose: DESIGN.md, section 3.
 //
 // The C ABI keeps Float64 host arrays for both dtypes (a Float32 Julia host passes Float64.(x) and converts back):
 // inputs are rounded to f32 on upload, outputs widened on download.
@@ -30,6 +33,7 @@
 #include "mom_ops.hpp"
 #include "mom_host.hpp"
 #include "mom_images.hpp"
+#include "mom_reduce.hpp"
 
 using namespace momf;
 
@@ -96,12 +100,6 @@ __global__ void k_combine_m0_f32(CombineArgsF a) {
   }
 }
 
-std::vector<float> tof(const double *src, size_t n) {
-  std::vector<float> v(n);
-  for (size_t i = 0; i < n; ++i) v[i] = (float)src[i];
-  return v;
-}
-
 }  // namespace
 
 // Edges with a Float32 strip-chained image (the image table, mom_images.hpp); other edges are padded with dummy stream entries
@@ -109,8 +107,9 @@ std::vector<float> tof(const double *src, size_t n) {
 static bool strip_size_f(int N) { return mom_find_image(MOM_IMG_F32_STRIP4, N) || mom_find_image(MOM_IMG_F32_STRIP8, N); }
 static int strip_pad_f(int N) { return mom_strip_pad(strip_size_f, N); }
 
-struct momf_scene {
-  int device = 0, N = 0, nS = 0, S = 0, Mmax = 0;
+// (the resident scene's arrays and counts: MomSceneBufs, mom_host.hpp)
+struct momf_scene : MomSceneBufs<float> {
+  int device = 0, N = 0, nS = 0, S = 0, M = 0;  // M: moments allocated (the resident scene's: scene_M)
   int Nu = 0, Nmax = 0;  // Nu: the caller's operator edge; N: the kernels' (strip_pad_f, decided in momf_set_streams); Nmax: allocated
   // m = 0 reduction (include/momcore.h, MOM_OPT_M0_REDUCTION): moment 0 runs as its own scene `sub` on the (I,Q) streams,
   // this scene's launches start at Fourier index m_first = 1
@@ -119,33 +118,26 @@ struct momf_scene {
   bool opt_m0 = true, opt_pad = true;
   // operator-level API (mom_ops.hpp): added / surface / composite layers in the reference's [N,N,S] layout, allocated on first use
   MomDevBuf<float> op_added[6], op_surf[6], op_comp[6], op_vec[4], op_Z[2];
-  MomDevBuf<float> blas_buf[4];  // mom_batch_inv / mom_batched_mul: A, B, C, generic-mode scratch (grow-only)
+  MomDevBuf<float> blas_buf[4];  // mom_batch_inv / mom_batched_mul: A, C, B, generic-mode scratch (grow-only: batched_run)
   bool op_ready = false, op_comp_set = false;
   std::vector<double> hd_mu, hd_wt, hd_sg;  // the caller's Float64 streams (the sub-scene is cut from them)
   double hd_I0[4] = {}, hd_D[4] = {}, hd_mu0 = 0;
   hipStream_t stream = nullptr;  // borrowed from the Float64 handle (the sub-scene shares it), like d_info: never destroyed here
   int *d_info = nullptr;
   DevStreams q{};
-  MomDevBuf<float> d_mu, d_wt, d_sg;
   MomDevBuf<float> comp[6];
-  MomDevBuf<float> d_tau, d_varpi, d_zw, d_tau_sum, d_Zpp, d_Zmp;
-  MomDevBuf<float> d_R, d_hdr, d_hdrJ, d_hdrJm, d_bhr_uw, d_bhr_dw, d_scratch, d_Rsurf, d_albedo_spec;
-  float *d_T = nullptr;                   // d_R + nVza nS S (one buffer)
-  MomDevBuf<double> d_cos, d_sin;
-  MomDevBuf<float> d_smtab;               // N <= 4: the three stream-pair tables of the lane-per-point kernel
-  MomDevBuf<float> d_smpart;              // ... and the per-moment terms of R_SFI / T_SFI of its (point, moment) form
-  MomDevBuf<int> d_node, d_nd;            // d_nd: ndoubl per layer for the wave-per-point kernel
   bool pack = true;                       // MOM_OPT_SMALL_N = 1 (2: one point per wavefront)
   bool small_n = true;                    // MOM_OPT_SMALL_N: 4 < N <= 32 on the wave-per-point kernels (mom_wave.hip, Float32 build)
-  int Nz = 0, K = 0, M = 0, nVza = 0, surf_kind = 0, G = 1024;
-  float albedo = 0.f;
-  std::vector<int> nd, iface;
+  int G = 1024;
   std::vector<float> h_mu;
   bool lds = true, force_generic = false, sweep = true, strips = true, w4 = true;  // w4: MOM_OPT_SMALL_WG
   hipEvent_t ev[4] = {};
   int launches = 0;
   std::string err;
 };
+
+// (every call of it is inlined now; the out-of-line copy stays in the library's dynamic symbol table, which does not change)
+template hipError_t MomDevBuf<float>::reserve(size_t, hipStream_t);
 
 #define FCHK(s, call)                                                                                         \
   do {                                                                                                        \
@@ -163,7 +155,7 @@ const char *momf_error(const momf_scene *s) { return s->err.c_str(); }
 int momf_create(momf_scene **out, int device, hipStream_t stream, int N, int nS, int S, int max_m, int *d_info) {
   momf_scene *s = new momf_scene();
   *out = s;
-  s->device = device; s->N = s->Nu = N; s->nS = nS; s->S = S; s->Mmax = max_m; s->stream = stream; s->d_info = d_info;
+  s->device = device; s->N = s->Nu = N; s->nS = nS; s->S = S; s->M = max_m; s->stream = stream; s->d_info = d_info;
   const int Nm = s->Nmax = strip_pad_f(N);
   s->lds = N <= 64;
   FCHK(s, hipSetDevice(device));
@@ -225,7 +217,7 @@ static int apply_streams(momf_scene *s) {
   if ((int)s->hd_mu.size() != Nu) { s->err = "Float32 scene: streams not set"; return MOM_ESTATE; }
   const int N = s->N = (s->opt_pad && !s->force_generic && !(Nu <= 32 && s->small_n)) ? strip_pad_f(Nu) : Nu;
   s->lds = (N <= 64) && !s->force_generic;
-  std::vector<float> fm = tof(s->hd_mu.data(), Nu), fw = tof(s->hd_wt.data(), Nu), fs = tof(s->hd_sg.data(), Nu);
+  std::vector<float> fm(s->hd_mu.begin(), s->hd_mu.end()), fw(s->hd_wt.begin(), s->hd_wt.end()), fs(s->hd_sg.begin(), s->hd_sg.end());
   fm.resize(N, 1.f); fw.resize(N, 0.f); fs.resize(N, 1.f);  // dummy entries
   s->h_mu = fm;
   FCHK(s, hipMemcpyAsync(s->d_mu, fm.data(), N * sizeof(float), hipMemcpyHostToDevice, s->stream));
@@ -303,29 +295,21 @@ static int scene_set_impl(momf_scene *s, int Nz, int K, int M, const double *tau
   FCHK(s, s->d_hdrJ.renew((size_t)N * S));
   FCHK(s, s->d_bhr_uw.renew((size_t)nS * S));
   FCHK(s, s->d_bhr_dw.renew((size_t)nS * S));
-  s->Nz = Nz; s->K = K; s->M = M; s->nVza = nVza; s->albedo = (float)albedo; s->surf_kind = 0;
+  s->Nz = Nz; s->K = K; s->scene_M = M; s->nVza = nVza; s->albedo = (float)albedo; s->surf_kind = 0;
   s->nd.assign(ndoubl, ndoubl + Nz);
   s->iface.assign(iface, iface + Nz);
-  // ---- m = 0 reduction (include/momcore.h): the same conditions as the Float64 driver, checked on the data, bitwise.
+  // ---- m = 0 reduction (include/momcore.h): the data test and the cut are the Float64 driver's (mom_reduce.hpp).
   // Scenes that run on the lane- or wave-per-point kernels (all moments in one launch) keep moment 0 there.
   s->m_first = 0;
-  const int Nq = Nu / nS;
-  bool ok = s->opt_m0 && nS >= 3 && s->q.regular && !(Nu <= 4 && s->small_n) && !wave_applies_f32(s);
-  for (int k = 2; k < nS && ok; ++k) ok = (s->hd_I0[k] == 0.0);
-  for (int kb = 0; kb < K && ok; ++kb)
-    for (int j = 0; j < Nu && ok; ++j)
-      for (int i = 0; i < Nu; ++i) {
-        if (((i % nS) < 2) == ((j % nS) < 2)) continue;
-        const size_t o = i + (size_t)Nu * (j + (size_t)Nu * kb);  // moment 0 block
-        if (Zpp[o] != 0.0 || Zmp[o] != 0.0) { ok = false; break; }
-      }
+  const bool ok = s->opt_m0 && nS >= 3 && s->q.regular && !(Nu <= 4 && s->small_n) && !wave_applies_f32(s) &&
+                  mom_m0_reducible(s->hd_I0, Nu, nS, K, Zpp, Zmp);
   if (!ok) {
     momf_destroy(s->sub);
     s->sub = nullptr;
     return MOM_OK;
   }
   // N0r real entries; the kernels run on N0 >= N0r (dummy entries at the end) unless the wave-per-point kernel takes the scene
-  const int nS0 = 2, N0r = nS0 * Nq;
+  const int nS0 = kMomM0Stokes, N0r = mom_m0_edge(Nu, nS);
   const int N0 = (s->opt_pad && !s->force_generic && !(N0r <= 32 && s->small_n)) ? strip_pad_f(N0r) : N0r;
   if (s->sub && !(s->sub->Nu == N0 && s->sub->S == s->S)) { momf_destroy(s->sub); s->sub = nullptr; }
   if (!s->sub) {
@@ -339,21 +323,12 @@ static int scene_set_impl(momf_scene *s, int Nz, int K, int M, const double *tau
   momf_scene *u = s->sub;
   momf_set_options(u, s->q.inv_mode, s->force_generic, s->sweep, s->small_n, 0, 0, s->w4);
   u->strips = s->strips;
-  std::vector<double> mu0v(N0, 1.0), wt0v(N0, 0.0), sg0v(N0, 1.0), zp((size_t)N0 * N0 * K, 0.0), zm((size_t)N0 * N0 * K, 0.0);
-  auto full = [&](int i0) { return (i0 / nS0) * nS + (i0 % nS0); };
-  for (int i = 0; i < N0r; ++i) { mu0v[i] = s->hd_mu[full(i)]; wt0v[i] = s->hd_wt[full(i)]; }
-  for (int kb = 0; kb < K; ++kb)
-    for (int j = 0; j < N0r; ++j)
-      for (int i = 0; i < N0r; ++i) {
-        const size_t src = full(i) + (size_t)Nu * (full(j) + (size_t)Nu * kb);
-        zp[i + (size_t)N0 * (j + (size_t)N0 * kb)] = Zpp[src];
-        zm[i + (size_t)N0 * (j + (size_t)N0 * kb)] = Zmp[src];
-      }
+  const MomM0Cut cut = mom_m0_cut(s->hd_mu.data(), s->hd_wt.data(), Nu, nS, K, N0, Zpp, Zmp);
   const double one[4] = {1.0, 1.0, 1.0, 1.0};
   auto sub_fail = [&](int code) { s->err = u->err; return code; };
-  if ((rc = momf_set_streams(u, mu0v.data(), wt0v.data(), sg0v.data(), s->q.imu0, s->hd_mu0, s->hd_I0, one, s->q.regular)))
+  if ((rc = momf_set_streams(u, cut.mu.data(), cut.wt.data(), cut.sg.data(), s->q.imu0, s->hd_mu0, s->hd_I0, one, s->q.regular)))
     return sub_fail(rc);
-  if ((rc = scene_set_impl(u, Nz, K, 1, tau, varpi, zw, zp.data(), zm.data(), ndoubl, iface, tau_sum, albedo, nVza, node, cos_mphi,
+  if ((rc = scene_set_impl(u, Nz, K, 1, tau, varpi, zw, cut.Zpp.data(), cut.Zmp.data(), ndoubl, iface, tau_sum, albedo, nVza, node, cos_mphi,
                            sin_mphi, dev_layers)))
     return sub_fail(rc);
   s->m_first = 1;
@@ -374,19 +349,8 @@ int momf_scene_set_surface(momf_scene *s, int kind, int M, const double *Rsurf, 
     FCHK(s, s->d_hdrJm.renew((size_t)N * s->S * M));
     if (s->m_first) {
       // moment 0 runs on the (I,Q) sub-scene: its surface matrix must not couple (I,Q) with (U,V) either
-      const int nS0 = s->sub->nS, N0 = s->sub->Nu;
-      std::vector<double> r0((size_t)N0 * N0, 0.0);
-      for (int j = 0; j < Nu; ++j)
-        for (int i = 0; i < Nu; ++i) {
-          const bool iq_i = (i % nS) < nS0, iq_j = (j % nS) < nS0;
-          const double v = Rsurf[i + (size_t)Nu * j];
-          if (iq_i != iq_j && v != 0.0) {
-            s->err = "mom_scene_set_surface: the m = 0 BRDF matrix couples (I,Q) with (U,V); set MOM_OPT_M0_REDUCTION = 0 before "
-                     "mom_scene_set for this surface";
-            return MOM_EINVAL;
-          }
-          if (iq_i && iq_j) r0[(i / nS) * nS0 + (i % nS) + (size_t)N0 * ((j / nS) * nS0 + (j % nS))] = v;
-        }
+      std::vector<double> r0;
+      if (!mom_m0_cut_brdf(Rsurf, Nu, nS, s->sub->Nu, r0)) { s->err = kMomM0BrdfCouples; return MOM_EINVAL; }
       if ((rc = momf_scene_set_surface(s->sub, 1, 1, r0.data(), nullptr))) { s->err = s->sub->err; return rc; }
     }
   } else if (kind == 2) {
@@ -402,31 +366,15 @@ int momf_scene_set_surface(momf_scene *s, int kind, int M, const double *Rsurf, 
 // momcore_strip.hip built for float (Makefile: momcore_fs<KS>.o, 8 waves; momcore_f4s<KS>.o, 4 waves): mom_images.hpp
 
 // 4 < N <= 32: one spectral point per wavefront, operators in MFMA-layout registers, the whole run in ONE launch -- the
-// Float32 build of momw::k_wsweep (the Float64 path: rt_run_wave in mom_scene.hip).  Covers ScatteringInterface_11 on every
-// layer after the first and at the surface.
-static bool wave_applies_f32(const momf_scene *s) {
-  if (!(s->N > 4 && s->N <= 32 && s->small_n && !s->force_generic && s->nVza * s->nS <= 256)) return false;
-  for (int z = 1; z < s->Nz; ++z)
-    if (s->iface[z] != 3) return false;
-  return s->iface[s->Nz - 1] == 3;
-}
+// Float32 build of momw::k_wsweep (the Float64 path: rt_run_wave in mom_scene.hip; what the two share: mom_host.hpp).  The
+// "too many layers" refusals of the two runs: an artefact of d_ndif's fixed allocation here, kept as it is
+static bool wave_applies_f32(const momf_scene *s) { return mom_wave_sweep_applies(*s, s->N, s->nS, s->small_n, s->force_generic); }
 static int rt_run_wave_f32(momf_scene *s) {
-  if (!s->d_nd) FCHK(s, s->d_nd.renew(kMaxSweepLayers * 4));
+  if (!s->d_ndif) FCHK(s, s->d_ndif.renew(kMaxSweepLayers * 4));
   if (s->Nz > kMaxSweepLayers * 4) { s->err = "Float32 wave sweep: too many layers"; return MOM_EINVAL; }
-  FCHK(s, hipMemcpyAsync(s->d_nd, s->nd.data(), sizeof(int) * s->Nz, hipMemcpyHostToDevice, s->stream));
+  FCHK(s, hipMemcpyAsync(s->d_ndif, s->nd.data(), sizeof(int) * s->Nz, hipMemcpyHostToDevice, s->stream));
   MomWaveSweepArgsF a{};
-  a.N = s->N; a.S = s->S; a.M = s->M; a.K = s->K; a.Nz = s->Nz; a.nVza = s->nVza; a.nS = s->nS; a.imu0 = s->q.imu0;
-  a.inv_mode = s->q.inv_mode;
-  a.pad = s->pack ? (s->N == 5 ? 3 : (s->N >= 6 && s->N <= 8 ? 2 : 1)) : 1;  // points per wavefront (k_wsweep's PK)
-  a.mu0 = s->q.mu0; a.albedo = s->albedo;
-  for (int k = 0; k < 4; ++k) { a.I0[k] = s->q.I0[k]; a.D[k] = s->q.D[k]; }
-  a.mu = s->d_mu; a.wt = s->d_wt; a.sg = s->d_sg;
-  a.Zpp = s->d_Zpp; a.Zmp = s->d_Zmp;
-  a.nd = s->d_nd; a.node = s->d_node; a.cos_mphi = s->d_cos; a.sin_mphi = s->d_sin;
-  a.tau = s->d_tau; a.varpi = s->d_varpi; a.zw = s->d_zw; a.tau_sum = s->d_tau_sum;
-  a.R = s->d_R; a.T = s->d_T; a.hdr = s->d_hdr; a.bhr_uw = s->d_bhr_uw; a.bhr_dw = s->d_bhr_dw;
-  a.info = s->d_info;
-  a.surf_kind = s->surf_kind; a.Rsurf = s->d_Rsurf; a.albedo_spec = s->d_albedo_spec;
+  mom_fill_wave_args(a, *s, s->q, s->S, s->d_info, s->pack);
   FCHK(s, hipEventRecord(s->ev[0], s->stream));
   FCHK(s, momwf_launch_sweep(&a, s->stream));
   for (int k = 1; k < 4; ++k) FCHK(s, hipEventRecord(s->ev[k], s->stream));
@@ -437,41 +385,21 @@ static int rt_run_wave_f32(momf_scene *s) {
 
 // N <= 4: one spectral point per lane, the whole run in ONE launch (the Float64 path: rt_run_small in mom_scene.hip)
 static int rt_run_small_f32(momf_scene *s) {
-  const int N = s->N, Nz = s->Nz;
+  const int Nz = s->Nz;
   if (!s->d_smtab) FCHK(s, s->d_smtab.renew(48));
-  if (!s->d_nd) FCHK(s, s->d_nd.renew(kMaxSweepLayers * 4));
+  if (!s->d_ndif) FCHK(s, s->d_ndif.renew(kMaxSweepLayers * 4));
   if (2 * Nz > kMaxSweepLayers * 4) { s->err = "Float32 lane sweep: too many layers"; return MOM_EINVAL; }
-  float tab[48] = {0};
-  for (int j = 0; j < N; ++j)
-    for (int i = 0; i < N; ++i) {  // the expressions of elemental.jl:176-186 in Float32, evaluated once
-      const float mui = s->h_mu[i], muj = s->h_mu[j];
-      tab[i + N * j] = muj / (mui + muj);
-      tab[16 + i + N * j] = muj / (mui - muj);
-      tab[32 + i + N * j] = (1 / mui) + (1 / muj);
-    }
+  float tab[48];
+  mom_small_tables(s->h_mu.data(), s->N, tab);
   FCHK(s, hipMemcpyAsync(s->d_smtab, tab, sizeof tab, hipMemcpyHostToDevice, s->stream));
   std::vector<int> v(s->nd);
   v.insert(v.end(), s->iface.begin(), s->iface.end());
-  FCHK(s, hipMemcpyAsync(s->d_nd, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
+  FCHK(s, hipMemcpyAsync(s->d_ndif, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
   FCHK(s, hipStreamSynchronize(s->stream));
   MomSmallSweepArgsF a{};
-  a.S = s->S; a.M = s->M; a.K = s->K; a.Nz = Nz; a.nVza = s->nVza; a.nS = s->nS; a.imu0 = s->q.imu0;
-  a.mu0 = s->q.mu0; a.albedo = s->albedo;
-  for (int k = 0; k < 4; ++k) { a.I0[k] = s->q.I0[k]; a.D[k] = s->q.D[k]; }
-  a.mu = s->d_mu; a.wt = s->d_wt; a.sg = s->d_sg;
-  a.F1 = s->d_smtab; a.F2 = s->d_smtab + 16; a.SI = s->d_smtab + 32;
-  a.Zpp = s->d_Zpp; a.Zmp = s->d_Zmp;
-  a.nd = s->d_nd; a.iface = s->d_nd + Nz; a.node = s->d_node; a.cos_mphi = s->d_cos; a.sin_mphi = s->d_sin;
-  a.tau = s->d_tau; a.varpi = s->d_varpi; a.zw = s->d_zw; a.tau_sum = s->d_tau_sum;
-  a.R = s->d_R; a.T = s->d_T; a.hdr = s->d_hdr; a.bhr_uw = s->d_bhr_uw; a.bhr_dw = s->d_bhr_dw;
-  a.info = s->d_info;
-  if (a.M > 1 && s->pack) {  // one (point, moment) per lane; MOM_OPT_SMALL_N = 2: one point per lane
-    const size_t need = (size_t)a.M * 2 * a.nVza * a.nS * a.S;
-    FCHK(s, s->d_smpart.reserve(need, s->stream));
-    a.part = s->d_smpart;
-  }
+  FCHK(s, mom_fill_small_args(a, *s, s->q, s->S, s->d_info, s->pack, s->stream));
   FCHK(s, hipEventRecord(s->ev[0], s->stream));
-  FCHK(s, momsmf_launch_sweep(&a, N, s->stream));
+  FCHK(s, momsmf_launch_sweep(&a, s->N, s->stream));
   for (int k = 1; k < 4; ++k) FCHK(s, hipEventRecord(s->ev[k], s->stream));
   s->launches = 1;
   return MOM_OK;
@@ -483,7 +411,7 @@ int momf_rt_run(momf_scene *s) {
   if (wave_applies_f32(s)) return rt_run_wave_f32(s);
   const size_t S = s->S;
   const int N = s->N, Nz = s->Nz;
-  const int m_first = s->m_first, M = s->M - m_first;  // this scene's own moments: m_first ... s->M - 1
+  const int m_first = s->m_first, M = s->scene_M - m_first;  // this scene's own moments: m_first ... s->scene_M - 1
   const bool lds = s->lds;
   const size_t sm = lds_bytes(N, lds);
   s->launches = 0;
@@ -532,7 +460,7 @@ int momf_rt_run(momf_scene *s) {
   }
   FCHK(s, hipEventRecord(s->ev[1], s->stream));
   // surface: every moment of a BRDF surface, moment 0 only otherwise (m > 0: r = 0, t = I, j = 0 -- the interaction is the identity)
-  for (int m = m_first; m < ((s->surf_kind == 1) ? s->M : 1); ++m) {
+  for (int m = m_first; m < ((s->surf_kind == 1) ? s->scene_M : 1); ++m) {
     SurfArgs a{};
     a.q = s->q; a.S = s->S; a.iface = s->iface[Nz - 1];
     a.albedo = s->albedo; a.tau_tot = s->d_tau_sum + S * Nz;
@@ -570,73 +498,29 @@ int momf_rt_run(momf_scene *s) {
   return MOM_OK;
 }
 
-static int download_f(momf_scene *s, double *dst, const float *src, size_t n) {
-  std::vector<float> v(n);
-  FCHK(s, hipMemcpyAsync(v.data(), src, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-  FCHK(s, hipStreamSynchronize(s->stream));
-  for (size_t i = 0; i < n; ++i) dst[i] = (double)v[i];
-  return MOM_OK;
-}
-
 int momf_get_RT(momf_scene *s, double *R, double *T) {
   FCHK(s, hipSetDevice(s->device));
-  const size_t nout = (size_t)s->nVza * s->nS * s->S;
-  int rc = download_f(s, R, s->d_R, nout);
-  if (rc) return rc;
-  return download_f(s, T, s->d_T, nout);
+  FCHK(s, mom_download_RT(*s, s->nS, s->S, R, T, s->stream));
+  return MOM_OK;
 }
-
 int momf_get_hdr(momf_scene *s, double *hdr, double *up, double *dw) {
   FCHK(s, hipSetDevice(s->device));
-  int rc = download_f(s, hdr, s->d_hdr, (size_t)s->nVza * s->nS * s->S);
-  if (rc) return rc;
-  if ((rc = download_f(s, up, s->d_bhr_uw, (size_t)s->nS * s->S))) return rc;
-  return download_f(s, dw, s->d_bhr_dw, (size_t)s->nS * s->S);
+  FCHK(s, mom_download_hdr(*s, s->nS, s->S, hdr, up, dw, s->stream));
+  return MOM_OK;
 }
 
 int momf_timers(momf_scene *s, double *ms, int *launches) {
   FCHK(s, hipSetDevice(s->device));
-  FCHK(s, hipEventSynchronize(s->ev[3]));
-  float t01, t12, t23, t03;
-  FCHK(s, hipEventElapsedTime(&t01, s->ev[0], s->ev[1]));
-  FCHK(s, hipEventElapsedTime(&t12, s->ev[1], s->ev[2]));
-  FCHK(s, hipEventElapsedTime(&t23, s->ev[2], s->ev[3]));
-  FCHK(s, hipEventElapsedTime(&t03, s->ev[0], s->ev[3]));
-  ms[0] = t01; ms[1] = t12; ms[2] = t23; ms[3] = t03;
+  FCHK(s, mom_stage_times(s->ev, ms));
   *launches = s->launches;
   return MOM_OK;
 }
 
-// batch_inv!(X, A) / A ⊠ B on a Float32 handle: Float64 host arrays at the ABI, f32 on the device; the device buffers are a
-// grow-only workspace of the handle (no allocation per call, nothing to leak on an early return)
-static int up_vec(momf_scene *s, float *dst, const double *src, size_t n);
+// batch_inv!(X, A) / A ⊠ B on a Float32 handle: Float64 host arrays at the ABI, f32 on the device (batched_run, mom_ops.hpp)
 int momf_blas(momf_scene *s, int n, int batch, const double *A, const double *B, double *C, bool inv) {
   FCHK(s, hipSetDevice(s->device));
-  const size_t cnt = (size_t)n * n * batch;
-  MomDevBuf<float> &dA = s->blas_buf[0], &dB = s->blas_buf[1], &dC = s->blas_buf[2], &scr = s->blas_buf[3];
-  int rc;
-  FCHK(s, dA.reserve(cnt, s->stream));
-  FCHK(s, dC.reserve(cnt, s->stream));
-  if ((rc = up_vec(s, dA, A, cnt))) return rc;
-  if (!inv) {
-    FCHK(s, dB.reserve(cnt, s->stream));
-    if ((rc = up_vec(s, dB, B, cnt))) return rc;
-  }
-  const bool lds = n <= 64 && !s->force_generic;
-  const int grid = lds ? batch : std::min(batch, 1024);
-  if (!lds) {
-    const size_t scn = (size_t)grid * kGenericBufs * mat_elems(n) + (size_t)ld_for(n) * np_for(n);
-    FCHK(s, scr.reserve(scn, s->stream));
-    FCHK(s, hipMemsetAsync(scr, 0, scn * sizeof(float), s->stream));
-  }
-  BlasArgs a{n, batch, dA, inv ? nullptr : dB.get(), dC, lds ? nullptr : scr.get(), s->d_info};
-  const size_t sm = lds_bytes(n, lds);
-  if (inv) {
-    FCHK(s, mom_launch_ldsm(MOM_LDSM(k_batch_inv), lds, grid, kThreads, sm, s->stream, a));
-  } else {
-    FCHK(s, mom_launch_ldsm(MOM_LDSM(k_batched_mul), lds, grid, kThreads, sm, s->stream, a));
-  }
-  return download_f(s, C, dC, cnt);
+  FCHK(s, batched_run(s->stream, s->blas_buf, s->d_info, s->force_generic, n, batch, A, B, C, inv));
+  return MOM_OK;
 }
 
 // =========================================================================================
@@ -662,21 +546,15 @@ static int op_begin(momf_scene *s, DevStreams *q) {
     s->op_ready = true;
   }
   // the caller's streams (a scene on this handle may have padded the device copies BEHIND entry Nu - 1; rewritten here anyway)
-  const std::vector<float> fm = tof(s->hd_mu.data(), N), fw = tof(s->hd_wt.data(), N), fs = tof(s->hd_sg.data(), N);
-  FCHK(s, hipMemcpyAsync(s->d_mu, fm.data(), N * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  FCHK(s, hipMemcpyAsync(s->d_wt, fw.data(), N * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  FCHK(s, hipMemcpyAsync(s->d_sg, fs.data(), N * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  FCHK(s, hipStreamSynchronize(s->stream));
+  FCHK(s, mom_to_device<float>(s->d_mu, s->hd_mu.data(), N, s->stream));
+  FCHK(s, mom_to_device<float>(s->d_wt, s->hd_wt.data(), N, s->stream));
+  FCHK(s, mom_to_device<float>(s->d_sg, s->hd_sg.data(), N, s->stream));
   *q = s->q;
   q->mu = s->d_mu; q->wt = s->d_wt; q->sg = s->d_sg; q->N = N;
   return MOM_OK;
 }
-static int up_vec(momf_scene *s, float *dst, const double *src, size_t n) {
-  const std::vector<float> v = tof(src, n);
-  FCHK(s, hipMemcpyAsync(dst, v.data(), n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  FCHK(s, hipStreamSynchronize(s->stream));
-  return MOM_OK;
-}
+#define OP_UP(s, dst, src, n) FCHK(s, mom_to_device<float>(dst, src, n, (s)->stream))
+#define OP_DOWN(s, dst, src, n) FCHK(s, mom_to_host<float>(dst, src, n, (s)->stream))
 #define OP_LAUNCH(s, KERN, grid, args)                                                                       \
   do {                                                                                                       \
     const bool l__ = (s)->Nu <= 64 && !(s)->force_generic;                                                   \
@@ -693,9 +571,11 @@ int momf_op_elemental(momf_scene *s, int m, int nd, const double *tau_sum, const
   if ((rc = op_begin(s, &a.q))) return rc;
   const size_t zc = (size_t)s->Nu * s->Nu * z_batch;
   for (int k = 0; k < 2; ++k) FCHK(s, s->op_Z[k].reserve(zc, s->stream));
-  if ((rc = up_vec(s, s->op_vec[0], tau_sum, s->S)) || (rc = up_vec(s, s->op_vec[1], dtau, s->S)) ||
-      (rc = up_vec(s, s->op_vec[2], varpi, s->S)) || (rc = up_vec(s, s->op_Z[0], Zpp, zc)) || (rc = up_vec(s, s->op_Z[1], Zmp, zc)))
-    return rc;
+  OP_UP(s, s->op_vec[0], tau_sum, s->S);
+  OP_UP(s, s->op_vec[1], dtau, s->S);
+  OP_UP(s, s->op_vec[2], varpi, s->S);
+  OP_UP(s, s->op_Z[0], Zpp, zc);
+  OP_UP(s, s->op_Z[1], Zmp, zc);
   a.S = s->S; a.m = m; a.nd = nd; a.z_batch = z_batch;
   a.tau_sum = s->op_vec[0]; a.dtau = s->op_vec[1]; a.varpi = s->op_vec[2]; a.Zpp = s->op_Z[0]; a.Zmp = s->op_Z[1];
   for (int k = 0; k < 6; ++k) a.added[k] = s->op_added[k];
@@ -709,12 +589,13 @@ int momf_op_doubling(momf_scene *s, int nd, double *expk) {
   OpArgs a{};
   int rc;
   if ((rc = op_begin(s, &a.q))) return rc;
-  if ((rc = up_vec(s, s->op_vec[3], expk, s->S))) return rc;
+  OP_UP(s, s->op_vec[3], expk, s->S);
   a.S = s->S; a.nd = nd; a.expk = s->op_vec[3];
   for (int k = 0; k < 6; ++k) a.added[k] = s->op_added[k];
   a.scratch = s->d_scratch; a.info = s->d_info;
   if (nd > 0) OP_LAUNCH(s, k_op_doubling, op_grid(s), a);  // doubling.jl:28 returns early for 0
-  return download_f(s, expk, s->op_vec[3], s->S);
+  OP_DOWN(s, expk, s->op_vec[3], s->S);
+  return MOM_OK;
 }
 
 int momf_op_interaction(momf_scene *s, int iface, int with_surface_layer) {
@@ -752,7 +633,7 @@ int momf_op_surface_lambertian(momf_scene *s, int m, double albedo, const double
   DevStreams q;
   int rc;
   if ((rc = op_begin(s, &q))) return rc;
-  if ((rc = up_vec(s, s->op_vec[0], tau_tot, s->S))) return rc;
+  OP_UP(s, s->op_vec[0], tau_tot, s->S);
   hipLaunchKernelGGL(k_op_surface_fill, dim3(s->S), dim3(256), 0, s->stream, q, s->S, m, (float)albedo, s->op_vec[0], s->op_surf[0],
                      s->op_surf[1], s->op_surf[2], s->op_surf[3], s->op_surf[4], s->op_surf[5]);
   FCHK(s, hipGetLastError());
@@ -772,7 +653,8 @@ int momf_op_upload(momf_scene *s, int which, const double *src) {
   size_t count = 0;
   float *p = op_which(s, which, &count);
   if (which / 6 == 1) s->op_comp_set = true;
-  return up_vec(s, p, src, count);
+  OP_UP(s, p, src, count);
+  return MOM_OK;
 }
 int momf_op_download(momf_scene *s, int which, double *dst) {
   DevStreams q;
@@ -785,5 +667,6 @@ int momf_op_download(momf_scene *s, int which, double *dst) {
   }
   size_t count = 0;
   float *p = op_which(s, which, &count);
-  return download_f(s, dst, p, count);
+  OP_DOWN(s, dst, p, count);
+  return MOM_OK;
 }
