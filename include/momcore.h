@@ -328,6 +328,31 @@ int mom_voigt_tau_abs(mom_t *h, int iz_1based, int nLines, const double *nu, con
                       const double *S, const int *ind_start_1based, const int *ind_stop_1based, double factor);
 int mom_absorption_set(mom_t *h, int Nz, const double *tau_abs);
 int mom_absorption_get(mom_t *h, double *tau_abs);
+/* ---- The Dual run of the absorption path: tau_abs together with its partials with respect to each layer's pressure (k = 0)
+ * and temperature (k = 1) -- ForwardDiff.Dual numbers through compute_absorption_cross_section, as
+ * absorption_cross_section(model, grid, p, T; autodiff = true) runs it (autodiff_helper.jl:17-51).  The partials are those of
+ * the reference's statements as written (the two rational approximations of w(z), not the exact Faddeeva function); integer
+ * and boolean decisions (line selection, grid windows, the branch |x| + y >= 8 of w, E_lower != -1, the TIPS range) are taken
+ * on the values.  Float64 and Float32 handles alike: the absorption table is Float64 on both.
+ *   mom_voigt_tau_abs_dual          mom_voigt_tau_abs that also takes the partials of the four per-line prefactors, each
+ *                                   [nLines, 2] column-major (index j + nLines k; NULL = zeros), and adds d_k sigma * factor into
+ *                                   dtau_abs[:, iz, k] (factor = vcd_dry[iz] * vmr is a constant)
+ *   mom_voigt_tau_abs_profile_dual  mom_voigt_tau_abs_profile (same checks, two launches for all layers) whose prefactor kernel
+ *                                   also forms those partials on the device
+ *   mom_absorption_get_partials     dtau_abs [nSpec, Nz, 2] (partial index slowest).  The table is allocated and zeroed by the
+ *                                   first Dual call after mom_absorption_begin, zeroed by mom_absorption_begin, dropped by
+ *                                   mom_absorption_set (a host table has no partials); without it: MOM_ESTATE.  A value call
+ *                                   (mom_voigt_tau_abs, _layer, _profile) into the same table adds an absorber whose partials
+ *                                   count as zero.
+ *   mom_absorption_get_prefactor_partials   the partials of the prefactors of the last Dual call (last layer of a profile
+ *                                   call), each [n, 2] column-major, NULL to skip (test access). */
+int mom_voigt_tau_abs_dual(mom_t *h, int iz_1based, int nLines, const double *nu, const double *gamma_d, const double *y,
+                           const double *S, const double *dnu, const double *dgamma_d, const double *dy, const double *dS,
+                           const int *ind_start_1based, const int *ind_stop_1based, double factor);
+int mom_voigt_tau_abs_profile_dual(mom_t *h, int Nz, const double *pressure, const double *temperature, double vmr,
+                                   double wing_cutoff, const double *factor, double *gpu_ms);
+int mom_absorption_get_partials(mom_t *h, double *dtau_abs);
+int mom_absorption_get_prefactor_partials(mom_t *h, int n, double *dnu, double *dgamma_d, double *dy, double *dS);
 int mom_scene_set_optics(mom_t *h, int Nz, int nAer, int M, const double *tau_rayl, double varpi_rayl,
                          const double *tau_aer, const double *omega_aer, const double *ft_aer, const double *Zpp,
                          const double *Zmp, double albedo, int nVza, const int *node_1based, const double *cos_mphi,
@@ -519,7 +544,15 @@ int mom_voigt_xsec(int device, int nLines, const double *nu, const double *gamma
                    const double *S, const int *ind_start_1based, const int *ind_stop_1based, int nGrid,
                    const double *grid, double *sigma);
 
-/* GPU time (HIP events around the kernel, ms) of the last mom_voigt_xsec call of the calling thread. */
+/* The Dual run of mom_voigt_xsec: dnu, dgamma_d, dy, dS are the partials of the four prefactors with respect to pressure
+ * (k = 0) and temperature (k = 1), each [nLines, 2] column-major (index j + nLines k; NULL = zeros).  sigma[nGrid] as above,
+ * dsigma [nGrid, 2] column-major = the Jacobian absorption_cross_section(...; autodiff = true) returns as result.derivs[1]. */
+int mom_voigt_xsec_dual(int device, int nLines, const double *nu, const double *gamma_d, const double *y, const double *S,
+                        const double *dnu, const double *dgamma_d, const double *dy, const double *dS,
+                        const int *ind_start_1based, const int *ind_stop_1based, int nGrid, const double *grid,
+                        double *sigma, double *dsigma);
+
+/* GPU time (HIP events around the kernel, ms) of the last mom_voigt_xsec / mom_voigt_xsec_dual call of the calling thread. */
 double mom_voigt_last_kernel_ms(void);
 
 #ifdef __cplusplus

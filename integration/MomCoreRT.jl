@@ -289,9 +289,11 @@ end
 """
 compute_absorption_profile! (src/CoreRT/tools/atmo_prof.jl:427-449) for a HitranModel with Voigt broadening: one
 resident line table per absorber, then all layers of the profile in two launches (the reference: a loop over layers
-with one kernel launch per line, compute_absorption_cross_section.jl:118-124).
+with one kernel launch per line, compute_absorption_cross_section.jl:118-124).  `dual = true`: the same two launches on
+ForwardDiff.Dual numbers -- the partials of τ_abs with respect to each layer's pressure and temperature accumulate in the
+resident ∂τ_abs table (absorption_partials).
 """
-function compute_absorption_profile!(h::MomHandle, grid, hitran, tips, p_full, T, vmr, vcd_dry, wing_cutoff)
+function compute_absorption_profile!(h::MomHandle, grid, hitran, tips, p_full, T, vmr, vcd_dry, wing_cutoff; dual::Bool = false)
     Nz = length(p_full)
     MomCore.mom_absorption_begin!(h.ptr, Nz, collect(Float64, grid))
     keep = (minimum(grid) - wing_cutoff) .< hitran.νᵢ .< (maximum(grid) + wing_cutoff)      # compute_absorption_cross_section.jl:54-72
@@ -299,8 +301,19 @@ function compute_absorption_profile!(h::MomHandle, grid, hitran, tips, p_full, T
                                       hitran.E″[keep], hitran.n_air[keep], hitran.δ_air[keep], tips.sqrt_mol_weight[keep],
                                       tips.iso_index[keep], tips.nIso, tips.nTmax, tips.nT, tips.T, tips.Q, tips.z)
     ms = Ref{Cdouble}(0)
-    MomCore.mom_voigt_tau_abs_profile!(h.ptr, Nz, p_full, T, Float64(vmr), Float64(wing_cutoff), vcd_dry .* vmr, ms)
+    if dual
+        MomCore.mom_voigt_tau_abs_profile_dual!(h.ptr, Nz, p_full, T, Float64(vmr), Float64(wing_cutoff), vcd_dry .* vmr, ms)
+    else
+        MomCore.mom_voigt_tau_abs_profile!(h.ptr, Nz, p_full, T, Float64(vmr), Float64(wing_cutoff), vcd_dry .* vmr, ms)
+    end
     return ms[]      # τ_abs stays resident; mom_scene_set_optics assembles the layer optics from it
+end
+
+"""∂τ_abs [nSpec, Nz, 2] of the Dual calls since mom_absorption_begin: [:, :, 1] with respect to the layer's pressure, [:, :, 2] to its temperature."""
+function absorption_partials(h::MomHandle, nSpec, Nz)
+    dτ_abs = zeros(Float64, nSpec, Nz, 2)
+    MomCore.mom_absorption_get_partials!(h.ptr, dτ_abs)
+    return dτ_abs
 end
 
 """compute_absorption_cross_section(model::HitranModel, grid, p, T) with architecture isa MI355X: ONE call for all lines."""
@@ -309,5 +322,18 @@ function voigt_xsec(arch::MI355X, ν, γ_d, y, S, ind_start, ind_stop, grid)
     momcheck(MomCore.mom_voigt_xsec(arch.device, length(ν), ν, γ_d, y, S, Cint.(ind_start), Cint.(ind_stop), length(grid),
                                     collect(Float64, grid), result))
     return result
+end
+
+"""
+absorption_cross_section(model, grid, p, T; autodiff = true) (src/Absorption/autodiff_helper.jl:17-51) with architecture isa
+MI355X: (σ, J[nGrid, 2]) from ONE call.  dν, dγ_d, dy, dS: the partials of the prefactors with respect to [p, T], each
+[nLines, 2] (what ForwardDiff carries through compute_absorption_cross_section.jl:79-101).
+"""
+function voigt_xsec_dual(arch::MI355X, ν, γ_d, y, S, dν, dγ_d, dy, dS, ind_start, ind_stop, grid)
+    result = zeros(Float64, length(grid));  derivs = zeros(Float64, length(grid), 2)
+    momcheck(MomCore.mom_voigt_xsec_dual(arch.device, length(ν), ν, γ_d, y, S, collect(Float64, dν), collect(Float64, dγ_d),
+                                         collect(Float64, dy), collect(Float64, dS), Cint.(ind_start), Cint.(ind_stop), length(grid),
+                                         collect(Float64, grid), result, derivs))
+    return result, derivs
 end
 # <<< absorption

@@ -94,6 +94,10 @@ SIGNATURES = {
     "mom_voigt_tau_abs": (C.c_int, [c_h, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip, C.c_double]),
     "mom_absorption_set": (C.c_int, [c_h, C.c_int, c_dp]),
     "mom_absorption_get": (C.c_int, [c_h, c_dp]),
+    "mom_voigt_tau_abs_dual": (C.c_int, [c_h, C.c_int, C.c_int] + [c_dp] * 8 + [c_ip, c_ip, C.c_double]),
+    "mom_voigt_tau_abs_profile_dual": (C.c_int, [c_h, C.c_int, c_dp, c_dp, C.c_double, C.c_double, c_dp, c_dp]),
+    "mom_absorption_get_partials": (C.c_int, [c_h, c_dp]),
+    "mom_absorption_get_prefactor_partials": (C.c_int, [c_h, C.c_int, c_dp, c_dp, c_dp, c_dp]),
     "mom_scene_set_optics": (C.c_int, [c_h, C.c_int, C.c_int, C.c_int, c_dp, C.c_double, c_dp, c_dp, c_dp, c_dp, c_dp,
                                        C.c_double, C.c_int, c_ip, c_dp, c_dp]),
     "mom_scene_get_layers": (C.c_int, [c_h, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp]),
@@ -122,6 +126,7 @@ SIGNATURES = {
     "mom_set_option": (C.c_int, [c_h, C.c_int, C.c_int]),
     "mom_strip2_resumed": (C.c_int, [c_h, c_ip, c_ip]),
     "mom_voigt_xsec": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip, C.c_int, c_dp, c_dp]),
+    "mom_voigt_xsec_dual": (C.c_int, [C.c_int, C.c_int] + [c_dp] * 8 + [c_ip, c_ip, C.c_int, c_dp, c_dp, c_dp]),
     "mom_voigt_last_kernel_ms": (C.c_double, []),
 }
 
@@ -434,6 +439,38 @@ class Handle:
         self.check(self.lib.mom_absorption_get_prefactors(self._h, n, *[dp(x) for x in d], ip(i0), ip(i1)))
         return d + [i0, i1]
 
+    # -- the Dual run of the absorption path: partials with respect to (p, T) of each layer ------------------
+    def voigt_tau_abs_dual(self, iz_1based, nu, gamma_d, y, S, dnu, dgamma_d, dy, dS, ind_start, ind_stop, factor):
+        """mom_voigt_tau_abs_dual: the partials of the four prefactors as [nLines, 2] numpy (column 0: pressure, 1:
+        temperature) or None (zeros)."""
+        a = [f64(x) for x in (nu, gamma_d, y, S)]
+        d = [_partials(x, len(a[0])) for x in (dnu, dgamma_d, dy, dS)]
+        i0, i1 = i32(ind_start), i32(ind_stop)
+        self.check(self.lib.mom_voigt_tau_abs_dual(self._h, int(iz_1based), len(a[0]), *[dp(x) for x in a],
+                                                   *[None if x is None else dp(x) for x in d], ip(i0), ip(i1), float(factor)))
+
+    def voigt_tau_abs_profile_dual(self, p, T, vmr, wing_cutoff, factor) -> float:
+        """voigt_tau_abs_profile that also adds the partials into the resident dtau_abs table; returns the GPU time in ms."""
+        p, T, f = f64(p), f64(T), f64(factor)
+        assert p.size == T.size == f.size
+        ms = np.zeros(1)
+        self.check(self.lib.mom_voigt_tau_abs_profile_dual(self._h, int(p.size), dp(p), dp(T), float(vmr), float(wing_cutoff), dp(f),
+                                                           dp(ms)))
+        return float(ms[0])
+
+    def absorption_get_partials(self):
+        """dtau_abs as numpy [2, S, Nz]: [0] with respect to the layer's pressure, [1] to its temperature."""
+        out = np.empty(2 * self.S * self._absNz)
+        self.check(self.lib.mom_absorption_get_partials(self._h, dp(out)))
+        return np.transpose(out.reshape(2, self._absNz, self.S), (0, 2, 1)).copy()
+
+    def absorption_get_prefactor_partials(self, n=None):
+        """dnu, dgamma_d, dy, dS of the last Dual call, each [n, 2] numpy."""
+        n = self._nLines if n is None else int(n)
+        d = [np.empty(2 * n) for _ in range(4)]
+        self.check(self.lib.mom_absorption_get_prefactor_partials(self._h, n, *[dp(x) for x in d]))
+        return [x.reshape(2, n).T.copy() for x in d]
+
     def scene_set_optics(self, Nz, M, tau_rayl, varpi_rayl, tau_aer, omega_aer, ft_aer, Zpp, Zmp, albedo, node, cos_mphi,
                          sin_mphi):
         """tau_rayl [S, Nz], tau_aer [nAer, Nz] numpy (reference layouts); Zpp/Zmp already in ABI order."""
@@ -587,6 +624,30 @@ def voigt_xsec(nu, gamma_d, y, S, ind_start, ind_stop, grid, device: int = 0):
     if rc != MOM_OK:
         raise MomError(rc, lib.mom_last_global_error().decode())
     return sigma
+
+
+def _partials(x, n):
+    """[n, 2] numpy -> the ABI's column-major flat array (index j + n k); None stays None (zeros)"""
+    if x is None:
+        return None
+    x = np.asarray(x, dtype=np.float64)
+    assert x.shape == (n, 2), f"partials must be [nLines, 2], got {x.shape}"
+    return np.ascontiguousarray(x.T).reshape(-1)
+
+
+def voigt_xsec_dual(nu, gamma_d, y, S, dnu, dgamma_d, dy, dS, ind_start, ind_stop, grid, device: int = 0):
+    """mom_voigt_xsec_dual: sigma [nGrid] and dsigma [nGrid, 2] (column 0: d/dp, 1: d/dT).  The partials of the prefactors are
+    [nLines, 2] numpy or None (zeros)."""
+    lib = load()
+    a = [f64(x) for x in (nu, gamma_d, y, S)]
+    d = [_partials(x, len(a[0])) for x in (dnu, dgamma_d, dy, dS)]
+    i0, i1, g = i32(ind_start), i32(ind_stop), f64(grid)
+    sigma, dsigma = np.empty(len(g)), np.empty(2 * len(g))
+    rc = lib.mom_voigt_xsec_dual(device, len(a[0]), *[dp(x) for x in a], *[None if x is None else dp(x) for x in d], ip(i0), ip(i1),
+                                 len(g), dp(g), dp(sigma), dp(dsigma))
+    if rc != MOM_OK:
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return sigma, dsigma.reshape(2, len(g)).T.copy()
 
 
 def voigt_last_kernel_ms() -> float:

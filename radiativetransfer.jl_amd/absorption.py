@@ -160,6 +160,18 @@ class CubicSpline:
         D = (u[i] / h[i + 1] - z[i] * h[i + 1] / 6) * (t[i + 1] - x)
         return float(I + C + D)
 
+    def derivative(self, x: float) -> float:
+        """d/dx of the piece __call__ evaluates (the same interval): I + C + D differentiated term by term, as
+        ForwardDiff carries a Dual abscissa through the evaluation."""
+        t, u, h, z = self.t, self.u, self.h, self.z
+        i = int(np.searchsorted(t, x, side="right")) - 1
+        i = max(0, min(i, len(t) - 2))
+        x = np.float64(x)
+        dI = z[i + 1] * (3 * (x - t[i]) ** 2) / (6 * h[i + 1]) - z[i] * (3 * (t[i + 1] - x) ** 2) / (6 * h[i + 1])
+        dC = u[i + 1] / h[i + 1] - z[i + 1] * h[i + 1] / 6
+        dD = u[i] / h[i + 1] - z[i] * h[i + 1] / 6
+        return float(dI + np.float64(dC) - np.float64(dD))
+
 
 _SPLINES = {}
 
@@ -175,6 +187,14 @@ def qoft(mol: int, iso: int, T: float, T_ref: float = t_ref) -> float:
     if not (Tmin < T < Tmax):
         raise AssertionError(f"TIPS2017: T ({T}) must be between {Tmin} K and {Tmax} K.")
     return sp(T_ref) / sp(T)
+
+
+def qoft_dual(mol: int, iso: int, T: float, T_ref: float = t_ref):
+    """qoft! on a Dual temperature: (Q(T_ref)/Q(T), its derivative with respect to T = -Q(T_ref) Q'(T) / Q(T)^2)."""
+    rate = qoft(mol, iso, T, T_ref)     # range assertion and spline cache
+    sp = _SPLINES[(int(mol), int(iso))][0]
+    Qref, Q = sp(T_ref), sp(T)
+    return rate, -(Qref / (Q * Q)) * sp.derivative(T)
 
 
 def linear_rotor_qratio(T: float) -> float:
@@ -248,6 +268,88 @@ def line_prefactors(h: HitranTable, grid: np.ndarray, pressure: float, temperatu
     return LinePrefactors(ν, γ_d, y, S, i0, i1)
 
 
+def line_prefactors_dual(h: HitranTable, grid: np.ndarray, pressure: float, temperature: float, vmr: float = 0.0,
+                         wing_cutoff: float = 40.0, qratio=None, mol_weights: Optional[dict] = None):
+    """line_prefactors on ForwardDiff.Dual numbers with x = [p, T] (autodiff_helper.jl:17-51 through
+    compute_absorption_cross_section.jl:79-101): returns the LinePrefactors (the values, as line_prefactors forms them) and
+    dν, dγ_d, dy, dS, each [n, 2] with column 0 = d/dp and column 1 = d/dT -- the derivative of every statement as written,
+    by the rule ForwardDiff applies to it.  Line selection, windows and the E″ != -1 test are taken on the values.  A
+    `qratio` override has no known derivative and raises ValueError."""
+    if qratio is not None:
+        raise ValueError("line_prefactors_dual: the derivative of a qratio override is unknown; the Dual run uses the reference's qoft!")
+    pf = line_prefactors(h, grid, pressure, temperature, vmr, wing_cutoff, None, mol_weights)
+    grid = np.asarray(grid, dtype=np.float64)
+    T, p = float(temperature), float(pressure)
+    keep = (grid.min() - wing_cutoff < h.νᵢ) & (h.νᵢ < grid.max() + wing_cutoff)
+    ν0, S0, E, n_air = h.νᵢ[keep], h.Sᵢ[keep], h.E_lower[keep], h.n_air[keep]
+    mol, iso = h.mol[keep], h.iso[keep]
+    n = ν0.size
+    z = np.zeros(n)
+    dν = np.stack([(1 / p_ref) * h.δ_air[keep], z], axis=1)
+    # γ_l = lin(p) (t_ref / T)^n
+    lin = h.γ_air[keep] * (1 - vmr) * p / p_ref + h.γ_self[keep] * vmr * p / p_ref
+    dlin = h.γ_air[keep] * (1 - vmr) / p_ref + h.γ_self[keep] * vmr / p_ref
+    dγl_p = dlin * (t_ref / T) ** n_air
+    dγl_T = lin * (n_air * (t_ref / T) ** (n_air - 1) * (-(t_ref / (T * T))))
+    # γ_d = c sqrt(T) ν0 / sqrt(w): only the square root depends on T
+    cg = (cSqrt2Ln2 / cc_) * np.sqrt(cBolts_ / cMassMol)
+    sqw = _sqrt_weights(h, keep, mol_weights)
+    dγd_T = cg * (1 / (2 * np.sqrt(T))) * ν0 / sqw
+    dγd = np.stack([z, dγd_T], axis=1)
+    # y = sqrt(ln 2) γ_l / γ_d, quotient rule
+    ynum = np.sqrt(cLn2) * (lin * (t_ref / T) ** n_air)
+    g = pf.γ_d
+    dy = np.stack([np.sqrt(cLn2) * dγl_p * (1 / g), np.sqrt(cLn2) * dγl_T * (1 / g) + dγd_T * (-(ynum / (g * g)))], axis=1)
+    # S = S0 rate e1 e2 / e3 where E″ != -1
+    dS_T = np.zeros(n)
+    for (M, I) in sorted(set(zip(mol.tolist(), iso.tolist()))):
+        sel = (mol == M) & (iso == I) & (E != -1)
+        if not np.any(sel):
+            continue
+        rate, drate = qoft_dual(M, I, T, t_ref)
+        e1 = np.exp(c2 * E[sel] * (1 / t_ref - 1 / T))
+        ex2 = np.exp(-c2 * ν0[sel] / T)
+        e2, e3 = 1 - ex2, 1 - np.exp(-c2 * ν0[sel] / t_ref)
+        de1 = e1 * (c2 * E[sel] * (1 / (T * T)))
+        de2 = -(ex2 * (c2 * ν0[sel] / (T * T)))
+        r1, dr1 = rate * e1, drate * e1 + rate * de1
+        dS_T[sel] = S0[sel] * ((dr1 * e2 + r1 * de2) / e3)
+    dS = np.stack([z, dS_T], axis=1)
+    return pf, dν, dγd, dy, dS
+
+
+def _sqrt_weights(h: HitranTable, keep, mol_weights: Optional[dict] = None) -> np.ndarray:
+    """Float64(sqrt(mol_weight(mol, iso)::Float32)) of the kept lines (compute_absorption_cross_section.jl:88)"""
+    mol, iso = h.mol[keep], h.iso[keep]
+    sqw = np.empty(mol.size)
+    for (M, I) in sorted(set(zip(mol.tolist(), iso.tolist()))):
+        w = np.float32(mol_weights[(M, I)]) if mol_weights is not None and (M, I) in mol_weights else mol_weight(M, I)
+        sqw[(mol == M) & (iso == I)] = np.float64(np.sqrt(w))
+    return sqw
+
+
+def absorption_cross_section(h: HitranTable, grid, pressure: float, temperature: float, autodiff: bool = False, vmr: float = 0.0,
+                             wing_cutoff: float = 40.0, device: int = 0):
+    """absorption_cross_section(model, grid, p, T; autodiff) (autodiff_helper.jl:17-51): σ[nGrid], or with autodiff=True
+    (σ, J[nGrid, 2]) -- the Jacobian with respect to x = [p, T] that ForwardDiff.jacobian! returns as result.derivs[1],
+    from the Dual run of the Voigt kernel (mom_voigt_xsec_dual)."""
+    if not autodiff:
+        return compute_absorption_cross_section(h, grid, pressure, temperature, vmr, wing_cutoff, device=device)
+    pf, dν, dγd, dy, dS = line_prefactors_dual(h, grid, pressure, temperature, vmr, wing_cutoff)
+    return _lib.voigt_xsec_dual(pf.ν, pf.γ_d, pf.y, pf.S, dν, dγd, dy, dS, pf.ind_start, pf.ind_stop,
+                                np.asarray(grid, dtype=np.float64), device=device)
+
+
+def optics_partials(tau, varpi, dtau_abs_k):
+    """The partial of the layer optics with respect to one parameter that acts through the gas absorption only:
+    `+(::CoreScatteringOpticalProperties, ::CoreAbsorptionOpticalProperties)` (types.jl:672-678) is τ = τ_x + τ_abs,
+    ϖ = τ_x ϖ_x / τ, so dτ = dτ_abs and dϖ = -ϖ dτ_abs / τ (τ, ϖ: the sums, [nSpec, Nz], as the scene holds them); the
+    weights of the phase-matrix bases do not depend on τ_abs.  Returns the corert.ScenePartial that rt_run_dual takes."""
+    from .corert import ScenePartial
+    tau, varpi, d = (np.asarray(x, dtype=np.float64) for x in (tau, varpi, dtau_abs_k))
+    return ScenePartial(dτ=d.copy(), dϖ=-varpi * d / tau)
+
+
 def compute_absorption_cross_section(h: HitranTable, grid, pressure: float, temperature: float, vmr: float = 0.0,
                                      wing_cutoff: float = 40.0, qratio=None, device: int = 0) -> np.ndarray:
     """compute_absorption_cross_section(model::HitranModel, grid, p, T) with Voigt broadening and
@@ -288,7 +390,7 @@ def resident_line_table(h, table: HitranTable, grid, wing_cutoff: float = 40.0):
 
 def compute_absorption_profile(h, table: HitranTable, grid, p_full, T, vcd_dry, vmr, wing_cutoff: float = 40.0,
                                model_vmr: float = 0.0, qratio=None, begin: bool = True, device_prefactors: bool = False,
-                               layer_by_layer: bool = False):
+                               layer_by_layer: bool = False, dual: bool = False):
     """compute_absorption_profile!(τ_abs, absorption_model, grid, vmr, profile) (atmo_prof.jl:427-449) on the handle's
     resident τ_abs table: per layer the host builds the line prefactors (O(nLines)), the GPU adds
     σ(ν; p[iz], T[iz]) * vcd_dry[iz] * vmr[iz] into τ_abs[:, iz] (mom_voigt_tau_abs).  `vmr` scalar or per layer (the
@@ -296,7 +398,9 @@ def compute_absorption_profile(h, table: HitranTable, grid, p_full, T, vcd_dry, 
     begin=False adds another absorber to the same table (the reference's `+=` over molecules).  device_prefactors=True
     forms the per-line prefactors on the GPU from one resident line table (mom_absorption_set_lines) and runs ALL layers in
     two launches (mom_voigt_tau_abs_profile; returns their GPU time in ms); layer_by_layer=True keeps one
-    mom_voigt_tau_abs_layer call per layer (same arithmetic, bitwise)."""
+    mom_voigt_tau_abs_layer call per layer (same arithmetic, bitwise).  dual=True takes the Dual entry points on either route
+    (mom_voigt_tau_abs_dual fed by line_prefactors_dual, or mom_voigt_tau_abs_profile_dual): the partials of τ_abs with
+    respect to each layer's pressure and temperature accumulate in the handle's dtau_abs table (absorption_get_partials)."""
     p_full, T, vcd_dry = (np.asarray(x, dtype=np.float64) for x in (p_full, T, vcd_dry))
     Nz = p_full.size
     assert T.size == Nz and vcd_dry.size == Nz
@@ -308,12 +412,21 @@ def compute_absorption_profile(h, table: HitranTable, grid, p_full, T, vcd_dry, 
         if qratio is not None:
             raise ValueError("device_prefactors uses the reference's qoft! (TIPS-2017); qratio overrides are host-route only")
         resident_line_table(h, table, grid, wing_cutoff)
+        if dual:
+            if layer_by_layer:
+                raise ValueError("dual=True runs all layers in two launches; there is no layer-by-layer Dual entry point")
+            return h.voigt_tau_abs_profile_dual(p_full, T, model_vmr, wing_cutoff, vcd_dry * vmr_arr)
         if layer_by_layer:
             for iz in range(Nz):
                 h.voigt_tau_abs_layer(iz + 1, p_full[iz], T[iz], model_vmr, wing_cutoff, vcd_dry[iz] * vmr_arr[iz])
             return None
         return h.voigt_tau_abs_profile(p_full, T, model_vmr, wing_cutoff, vcd_dry * vmr_arr)   # all layers in two launches
     for iz in range(Nz):
+        if dual:
+            pf, dν, dγd, dy, dS = line_prefactors_dual(table, grid, p_full[iz], T[iz], vmr=model_vmr, wing_cutoff=wing_cutoff,
+                                                       qratio=qratio)
+            h.voigt_tau_abs_dual(iz + 1, pf.ν, pf.γ_d, pf.y, pf.S, dν, dγd, dy, dS, pf.ind_start, pf.ind_stop, vcd_dry[iz] * vmr_arr[iz])
+            continue
         pf = line_prefactors(table, grid, p_full[iz], T[iz], vmr=model_vmr, wing_cutoff=wing_cutoff, qratio=qratio)
         h.voigt_tau_abs(iz + 1, pf.ν, pf.γ_d, pf.y, pf.S, pf.ind_start, pf.ind_stop, vcd_dry[iz] * vmr_arr[iz])
 

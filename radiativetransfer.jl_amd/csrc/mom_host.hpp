@@ -220,6 +220,13 @@ hipError_t mom_voigt_launch(hipStream_t st, int nLines, const double *nu, const 
                             const double *S, const int *i0, const int *i1, int nGrid, const double *grid, double *out,
                             double factor, int accumulate, int sorted);
 
+// its Dual run: the partials of the prefactors (k = 0 pressure, 1 temperature; partial k of line j at p[j + ks k], null = zeros)
+// and dout[g + os k] = d_k acc  or  += factor * d_k acc
+hipError_t mom_voigt_dual_launch(hipStream_t st, int nLines, const double *nu, const double *gamma_d, const double *y,
+                                 const double *S, const int *i0, const int *i1, int nGrid, const double *grid, double *out,
+                                 double factor, int accumulate, int sorted, const double *dnu, const double *dgd, const double *dy,
+                                 const double *dS, size_t ks, double *dout, size_t os);
+
 // resident HITRAN table of one absorber + the TIPS spline tables of its isotopologues (device pointers)
 struct MomLineTable {
   int nLines, nIso, nTmax;
@@ -236,6 +243,11 @@ hipError_t mom_voigt_profile_launch(hipStream_t st, const MomLineTable &tb, int 
 hipError_t mom_line_prefactors_launch(hipStream_t st, const MomLineTable &tb, int nGrid, const double *grid, double p, double T,
                                       double vmr, double wing, double cgd, double *nu, double *gd, double *y, double *S, int *i0,
                                       int *i1, int *unsorted);
+// the Dual run of mom_voigt_profile_launch: prm = [p | T | cgd | factor | d cgd / dT][Nz], the prefactors' partials at
+// dpf[nu | gamma_d | y | S][k][Nz][cap], dtau_abs [nGrid, Nz, 2]
+hipError_t mom_voigt_profile_dual_launch(hipStream_t st, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
+                                         const double *prm, double vmr, double wing, double *pf, double *dpf, int *win, int *unsorted,
+                                         double *tau_abs, double *dtau_abs, const double *factor);
 
 // mom_dual.hip: rt_run on ForwardDiff.Dual numbers (values + P partials) for the resident scene.  Device pointers unless noted;
 // partial arrays have the layout of their value arrays with the partial index as the slowest axis, nullptr = zero partials.

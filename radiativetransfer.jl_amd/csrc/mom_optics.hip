@@ -9,6 +9,10 @@ extern "C" int mom_absorption_begin(mom_t *h, int Nz, const double *grid) {
   const size_t S = h->S;
   HIPCHK(h, h->d_tau_abs.renew(S * Nz));
   HIPCHK(h, hipMemsetAsync(h->d_tau_abs, 0, S * Nz * sizeof(double), h->stream));  // τ_abs = zeros (model_from_parameters.jl:48)
+  if (h->d_dtau_abs) {  // the partials restart with the table
+    if (Nz != h->abs_Nz) HIPCHK(h, h->d_dtau_abs.renew(2 * S * Nz));
+    HIPCHK(h, hipMemsetAsync(h->d_dtau_abs, 0, 2 * S * Nz * sizeof(double), h->stream));
+  }
   h->abs_Nz = Nz;
   if (grid) {
     HIPCHK(h, mom_upload(h->d_grid, grid, S, h->stream));
@@ -24,6 +28,7 @@ extern "C" int mom_absorption_set(mom_t *h, int Nz, const double *tau_abs) {
   if (rc) return rc;
   HIPCHK(h, hipMemcpyAsync(h->d_tau_abs, tau_abs, (size_t)h->S * Nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->d_dtau_abs.reset();  // a host table has no partials
   return MOM_OK;
 }
 
@@ -73,6 +78,90 @@ extern "C" int mom_voigt_tau_abs(mom_t *h, int iz_1based, int nLines, const doub
   HIPCHK(h, hipMemcpyAsync(dw + cap, ind_stop_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, mom_voigt_launch(h->stream, nLines, dl, dl + cap, dl + 2 * cap, dl + 3 * cap, dw, dw + cap, h->S, h->d_grid,
                              h->d_tau_abs + (size_t)h->S * (iz_1based - 1), factor, 1, sorted));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MOM_OK;
+}
+
+// ---- The Dual run of the absorption path: tau_abs and its partials with respect to the layer's pressure (k = 0) and temperature
+// (k = 1), ForwardDiff.Dual through compute_absorption_cross_section as absorption_cross_section(...; autodiff = true) runs it
+// (autodiff_helper.jl:17-51).  Works on Float64 and Float32 handles alike: the absorption table is Float64 on both.
+namespace {
+// dtau_abs [S, abs_Nz, 2], allocated and zeroed by the first Dual call after mom_absorption_begin
+int dual_table(mom_t *h) {
+  if (h->d_dtau_abs) return MOM_OK;
+  const size_t n = 2 * (size_t)h->S * h->abs_Nz;
+  HIPCHK(h, h->d_dtau_abs.renew(n));
+  HIPCHK(h, hipMemsetAsync(h->d_dtau_abs, 0, n * sizeof(double), h->stream));
+  return MOM_OK;
+}
+// d_lines with room for `nz` layers of `lb` lines (the value entry points' layout and growth) and d_dlines to match
+int dual_lines(mom_t *h, size_t lb, int nz) {
+  const size_t per = std::max<size_t>(lb, 1024) * 2;
+  if (lb > h->lines_per || h->lines_nz != nz || !h->d_lines) {
+    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
+    HIPCHK(h, h->d_lines.renew(5 * per * (size_t)nz));
+    h->lines_per = per;
+    h->lines_nz = nz;
+  }
+  HIPCHK(h, h->d_dlines.reserve(8 * h->lines_per * (size_t)nz, h->stream));
+  return MOM_OK;
+}
+}  // namespace
+
+extern "C" int mom_voigt_tau_abs_dual(mom_t *h, int iz_1based, int nLines, const double *nu, const double *gamma_d, const double *y,
+                                      const double *S, const double *dnu, const double *dgamma_d, const double *dy, const double *dS,
+                                      const int *ind_start_1based, const int *ind_stop_1based, double factor) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (!h->d_tau_abs || !h->d_grid) return fail(h, MOM_ESTATE, "mom_voigt_tau_abs_dual: call mom_absorption_begin with the spectral grid first");
+  if (iz_1based < 1 || iz_1based > h->abs_Nz || nLines < 0 ||
+      (nLines > 0 && (!nu || !gamma_d || !y || !S || !ind_start_1based || !ind_stop_1based)))
+    return fail(h, MOM_EINVAL, "mom_voigt_tau_abs_dual: bad argument");
+  for (int j = 0; j < nLines; ++j)
+    if (ind_start_1based[j] < 1 || ind_stop_1based[j] > h->S) {
+      char buf[160];
+      snprintf(buf, sizeof buf, "mom_voigt_tau_abs_dual: line %d: window [%d, %d] outside the grid 1..%d", j + 1, ind_start_1based[j],
+               ind_stop_1based[j], h->S);
+      return fail(h, MOM_EINVAL, buf);
+    }
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = dual_table(h);
+  if (rc) return rc;
+  if (nLines == 0) return MOM_OK;
+  int sorted = 1;
+  for (int j = 1; j < nLines; ++j)
+    if (ind_start_1based[j] < ind_start_1based[j - 1] || ind_stop_1based[j] < ind_stop_1based[j - 1]) { sorted = 0; break; }
+  const size_t lb = (size_t)nLines;
+  rc = dual_lines(h, lb, 1);
+  if (rc) return rc;
+  const size_t cap = h->lines_per;
+  double *dl = h->d_lines, *dd = h->d_dlines;
+  int *dw = reinterpret_cast<int *>(dl + 4 * cap);
+  const double *src[4] = {nu, gamma_d, y, S}, *dsrc[4] = {dnu, dgamma_d, dy, dS};
+  const double *dev[4];
+  // the host arrays are borrowed for the call only: the copies must have left them before we return
+  for (int k = 0; k < 4; ++k) HIPCHK(h, hipMemcpyAsync(dl + k * cap, src[k], lb * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  for (int q = 0; q < 4; ++q) {  // host [nLines, 2] column-major -> [q][k][cap]; a null array: zeros
+    dev[q] = dd + 2 * q * cap;
+    for (int k = 0; k < 2; ++k) {
+      if (dsrc[q]) HIPCHK(h, hipMemcpyAsync(dd + (2 * q + k) * cap, dsrc[q] + lb * k, lb * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      else HIPCHK(h, hipMemsetAsync(dd + (2 * q + k) * cap, 0, lb * sizeof(double), h->stream));
+    }
+  }
+  HIPCHK(h, hipMemcpyAsync(dw, ind_start_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(dw + cap, ind_stop_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  const size_t col = (size_t)h->S * (iz_1based - 1);
+  HIPCHK(h, mom_voigt_dual_launch(h->stream, nLines, dl, dl + cap, dl + 2 * cap, dl + 3 * cap, dw, dw + cap, h->S, h->d_grid,
+                                  h->d_tau_abs + col, factor, 1, sorted, dev[0], dev[1], dev[2], dev[3], cap,
+                                  h->d_dtau_abs + col, (size_t)h->S * h->abs_Nz));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MOM_OK;
+}
+
+extern "C" int mom_absorption_get_partials(mom_t *h, double *dtau_abs) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (!h->d_dtau_abs || !dtau_abs) return fail(h, MOM_ESTATE, "mom_absorption_get_partials: no resident dtau_abs table (no Dual call since the table was set) / null output");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(dtau_abs, h->d_dtau_abs, 2 * (size_t)h->S * h->abs_Nz * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MOM_OK;
 }
@@ -169,46 +258,67 @@ extern "C" int mom_voigt_tau_abs_layer(mom_t *h, int iz_1based, double pressure,
 // 0.015 cm^-1, wing cut-off 40 cm^-1, 40 layers) a per-layer launch covers 90 workgroups -- a third of the GPU -- and the
 // host round trips between the layers cost more than the arithmetic.  Here blockIdx.y = layer.  gpu_ms (optional): HIP-event
 // time of the two kernels.
-extern "C" int mom_voigt_tau_abs_profile(mom_t *h, int Nz, const double *pressure, const double *temperature, double vmr,
-                                         double wing_cutoff, const double *factor, double *gpu_ms) {
+namespace {
+// mom_voigt_tau_abs_profile and its Dual run; `fn` is the entry point's name in the error texts
+int voigt_profile_run(mom_t *h, const char *fn, bool dual, int Nz, const double *pressure, const double *temperature, double vmr,
+                      double wing_cutoff, const double *factor, double *gpu_ms) {
+  char buf[200];
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
-  if (!h->d_tau_abs || !h->d_grid) return fail(h, MOM_ESTATE, "mom_voigt_tau_abs_profile: call mom_absorption_begin with the spectral grid first");
-  if (!h->d_lt) return fail(h, MOM_ESTATE, "mom_voigt_tau_abs_profile: call mom_absorption_set_lines first");
-  if (Nz < 1 || Nz > h->abs_Nz || !pressure || !temperature || !factor) return fail(h, MOM_EINVAL, "mom_voigt_tau_abs_profile: bad argument");
+  if (!h->d_tau_abs || !h->d_grid) {
+    snprintf(buf, sizeof buf, "%s: call mom_absorption_begin with the spectral grid first", fn);
+    return fail(h, MOM_ESTATE, buf);
+  }
+  if (!h->d_lt) {
+    snprintf(buf, sizeof buf, "%s: call mom_absorption_set_lines first", fn);
+    return fail(h, MOM_ESTATE, buf);
+  }
+  snprintf(buf, sizeof buf, "%s: bad argument", fn);
+  if (Nz < 1 || Nz > h->abs_Nz || !pressure || !temperature || !factor) return fail(h, MOM_EINVAL, buf);
   for (int z = 0; z < Nz; ++z) {
-    if (!(temperature[z] > 0.0)) return fail(h, MOM_EINVAL, "mom_voigt_tau_abs_profile: bad argument");
+    if (!(temperature[z] > 0.0)) return fail(h, MOM_EINVAL, buf);
     if (h->lt.nIso > 0 && !(h->lt_Tmin < temperature[z] && temperature[z] < h->lt_Tmax)) {
-      char buf[160];
       snprintf(buf, sizeof buf, "TIPS2017: T (%g) must be between %g K and %g K.", temperature[z], h->lt_Tmin, h->lt_Tmax);
       return fail(h, MOM_EINVAL, buf);
     }
   }
   if (gpu_ms) *gpu_ms = 0.0;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (dual) {
+    const int rc = dual_table(h);
+    if (rc) return rc;
+  }
   const int nLines = h->lt.nLines;
   if (nLines == 0) return MOM_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t per = std::max<size_t>((size_t)nLines, 1024) * 2;       // line capacity of one layer's block
-  const size_t need = per * (size_t)Nz;
-  if (need > h->lines_per * (size_t)std::max(h->lines_nz, 1) || h->lines_nz != Nz) {
-    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
-    HIPCHK(h, h->d_lines.renew(5 * need));
-    h->lines_per = per;
-    h->lines_nz = Nz;
+  if (dual) {
+    const int rc = dual_lines(h, (size_t)nLines, Nz);
+    if (rc) return rc;
+  } else {
+    const size_t per = std::max<size_t>((size_t)nLines, 1024) * 2;       // line capacity of one layer's block
+    const size_t need = per * (size_t)Nz;
+    if (need > h->lines_per * (size_t)std::max(h->lines_nz, 1) || h->lines_nz != Nz) {
+      if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
+      HIPCHK(h, h->d_lines.renew(5 * need));
+      h->lines_per = per;
+      h->lines_nz = Nz;
+    }
   }
   const size_t cap = h->lines_per;
-  // per-layer scalars [p | T | cgd | factor][Nz] and the Nz sortedness flags
-  const size_t prm_doubles = 4 * (size_t)Nz + ((size_t)Nz + 1) / 2;
+  // per-layer scalars [p | T | cgd | factor][Nz] (Dual run: | d cgd / dT) and the Nz sortedness flags
+  const size_t nprm = dual ? 5 : 4;
+  const size_t prm_doubles = nprm * (size_t)Nz + ((size_t)Nz + 1) / 2;
   HIPCHK(h, h->d_prof.reserve(prm_doubles, h->stream));
-  std::vector<double> prm(4 * (size_t)Nz);
+  std::vector<double> prm(nprm * (size_t)Nz);
   for (int z = 0; z < Nz; ++z) {
     prm[z] = pressure[z];
     prm[Nz + z] = temperature[z];
     // γ_d = (cSqrt2Ln2 / cc_) sqrt(cBolts_ / cMassMol) sqrt(T) ν₀ / sqrt(mol_weight)   (:87-88): the scalar part
-    prm[2 * (size_t)Nz + z] = (1.1774100225 / 2.99792458e8) * std::sqrt(1.3806503e-23 / 1.66053873e-27) * std::sqrt(temperature[z]);
+    const double cg = (1.1774100225 / 2.99792458e8) * std::sqrt(1.3806503e-23 / 1.66053873e-27);
+    prm[2 * (size_t)Nz + z] = cg * std::sqrt(temperature[z]);
     prm[3 * (size_t)Nz + z] = factor[z];
+    if (dual) prm[4 * (size_t)Nz + z] = cg * (1.0 / (2.0 * std::sqrt(temperature[z])));   // d sqrt(T) = 1 / (2 sqrt(T))
   }
   HIPCHK(h, hipMemcpyAsync(h->d_prof, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  int *flags = reinterpret_cast<int *>(h->d_prof + 4 * (size_t)Nz);
+  int *flags = reinterpret_cast<int *>(h->d_prof + nprm * (size_t)Nz);
   HIPCHK(h, hipMemsetAsync(flags, 0, sizeof(int) * (size_t)Nz, h->stream));
   double *pf = h->d_lines;
   int *win = reinterpret_cast<int *>(pf + 4 * cap * (size_t)Nz);
@@ -217,14 +327,43 @@ extern "C" int mom_voigt_tau_abs_profile(mom_t *h, int Nz, const double *pressur
       if (!h->ev_voigt[k]) HIPCHK(h, hipEventCreate(&h->ev_voigt[k]));
     HIPCHK(h, hipEventRecord(h->ev_voigt[0], h->stream));
   }
-  HIPCHK(h, mom_voigt_profile_launch(h->stream, h->lt, Nz, cap, h->S, h->d_grid, h->d_prof, vmr, wing_cutoff, pf, win, flags,
-                                     h->d_tau_abs, h->d_prof + 3 * (size_t)Nz));
+  if (dual)
+    HIPCHK(h, mom_voigt_profile_dual_launch(h->stream, h->lt, Nz, cap, h->S, h->d_grid, h->d_prof, vmr, wing_cutoff, pf, h->d_dlines, win,
+                                            flags, h->d_tau_abs, h->d_dtau_abs, h->d_prof + 3 * (size_t)Nz));
+  else
+    HIPCHK(h, mom_voigt_profile_launch(h->stream, h->lt, Nz, cap, h->S, h->d_grid, h->d_prof, vmr, wing_cutoff, pf, win, flags,
+                                       h->d_tau_abs, h->d_prof + 3 * (size_t)Nz));
   if (gpu_ms) HIPCHK(h, hipEventRecord(h->ev_voigt[1], h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));   // prm is a host temporary
   if (gpu_ms) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, h->ev_voigt[0], h->ev_voigt[1]) == hipSuccess) *gpu_ms = ms;
   }
+  return MOM_OK;
+}
+}  // namespace
+
+extern "C" int mom_voigt_tau_abs_profile(mom_t *h, int Nz, const double *pressure, const double *temperature, double vmr,
+                                         double wing_cutoff, const double *factor, double *gpu_ms) {
+  return voigt_profile_run(h, "mom_voigt_tau_abs_profile", false, Nz, pressure, temperature, vmr, wing_cutoff, factor, gpu_ms);
+}
+// Its Dual run: the same two launches also form the prefactors' partials and add d_k sigma * factor into dtau_abs[:, iz, k]
+extern "C" int mom_voigt_tau_abs_profile_dual(mom_t *h, int Nz, const double *pressure, const double *temperature, double vmr,
+                                              double wing_cutoff, const double *factor, double *gpu_ms) {
+  return voigt_profile_run(h, "mom_voigt_tau_abs_profile_dual", true, Nz, pressure, temperature, vmr, wing_cutoff, factor, gpu_ms);
+}
+
+// the partials of the prefactors of the last Dual call (test access), each [n, 2] column-major
+extern "C" int mom_absorption_get_prefactor_partials(mom_t *h, int n, double *dnu, double *dgamma_d, double *dy, double *dS) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  const size_t cap = h->lines_per, nz = (size_t)std::max(h->lines_nz, 1), last = (nz - 1) * cap;  // the LAST layer of a profile call
+  if (!h->d_lines || !h->d_dlines || n < 0 || (size_t)n > cap || h->d_dlines.capacity() < 8 * nz * cap)
+    return fail(h, MOM_ESTATE, "mom_absorption_get_prefactor_partials: no prefactor partials resident");
+  HIPCHK(h, hipSetDevice(h->device));
+  double *dst[4] = {dnu, dgamma_d, dy, dS};
+  for (int q = 0; q < 4; ++q)
+    for (int k = 0; k < 2 && dst[q]; ++k)
+      HIPCHK(h, hipMemcpy(dst[q] + (size_t)n * k, h->d_dlines + (2 * q + k) * nz * cap + last, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   return MOM_OK;
 }
 

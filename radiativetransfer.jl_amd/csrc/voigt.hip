@@ -78,22 +78,89 @@ __device__ __forceinline__ double w_hw32sd_re(double x, double y) {
   return cmul(inner, rec).re;
 }
 
+// Dual run (ForwardDiff.Dual numbers through line_shape!(::Voigt)): Re w(z) as above and the complex derivative w'(z).  Both
+// approximations are rational in z, so one w' serves every partial: d_k Re w = Re(w'(z) (d_k x + i d_k y)).  The branch is
+// taken on the values, as ForwardDiff takes it.
+//   humlicek2:   t = y - i x, u = t^2, w = N / D with N = t (1.410474 + u / sqrt(pi)), D = 3/4 + u (3 + u);
+//                dw/dt = (N' - w D') / D with N' = 1.410474 + 3 u / sqrt(pi), D' = 2 t (3 + 2 u); dt/dz = -i
+//   weideman32a: r = 1 / (L - i z), Z = (L + i z) r, P = sum a_k Z^k (P' carried by the same Horner loop),
+//                w = (1 / sqrt(pi) + 2 P r) r;  r' = i r^2, Z' = i r (1 + Z),
+//                w' = (2 P' Z' r + 2 P r') r + (1 / sqrt(pi) + 2 P r) r'
+// The reciprocals take the refined form: |D|^2 > 1e5 and < 1e60, |L - i z|^2 in [22, 200] (see above).
+__device__ __forceinline__ double w_hw32sd_dual(double x, double y, cplx &dw) {
+  const double rsp = 0.5641895835477563;  // 1/sqrt(pi)
+  if (fabs(x) + y >= 8.0) {
+    const cplx t = {y, -x};
+    const cplx u = cmul(t, t);
+    const cplx num = cmul(t, cplx{1.410474 + u.re * rsp, u.im * rsp});
+    const cplx up3 = {3.0 + u.re, u.im};
+    cplx den = cmul(u, up3);
+    den.re += 0.75;
+    const double inv = rcp_refined(den.re * den.re + den.im * den.im);
+    const cplx rden = {den.re * inv, -den.im * inv};
+    const cplx w = cmul(num, rden);
+    const cplx dnum = {1.410474 + 3.0 * u.re * rsp, 3.0 * u.im * rsp};
+    const cplx dden = cmul(cplx{2.0 * t.re, 2.0 * t.im}, cplx{3.0 + 2.0 * u.re, 2.0 * u.im});
+    const cplx wd = cmul(w, dden);
+    const cplx q = cmul(cplx{dnum.re - wd.re, dnum.im - wd.im}, rden);  // dw/dt
+    dw = {q.im, -q.re};                                                  // times dt/dz = -i
+    return w.re;
+  }
+  const double L = 4.756828460010884;  // sqrt(32/sqrt(2))
+  const cplx lpiz = {L - y, x}, lmiz = {L + y, -x};
+  const double inv = rcp_refined(lmiz.re * lmiz.re + lmiz.im * lmiz.im);
+  const cplx rec = {lmiz.re * inv, -lmiz.im * inv};
+  const cplx Z = cmul(lpiz, rec);
+  cplx p = {kW32A[31], 0.0}, dp = {0.0, 0.0};
+#pragma unroll
+  for (int k = 30; k >= 0; --k) {
+    dp = cmul(dp, Z);
+    dp.re += p.re;
+    dp.im += p.im;
+    p = cmul(p, Z);
+    p.re += kW32A[k];
+  }
+  const cplx p2 = {2 * p.re, 2 * p.im};
+  cplx inner = cmul(p2, rec);
+  inner.re += rsp;
+  const cplx r2 = cmul(rec, rec);
+  const cplx dr = {-r2.im, r2.re};                                        // r' = i r^2
+  const cplx dZ = cmul(cplx{-rec.im, rec.re}, cplx{1.0 + Z.re, Z.im});    // Z' = i r (1 + Z)
+  const cplx a1 = cmul(cmul(cplx{2 * dp.re, 2 * dp.im}, dZ), rec), a2 = cmul(p2, dr);
+  const cplx b1 = cmul(cplx{a1.re + a2.re, a1.im + a2.im}, rec), b2 = cmul(inner, dr);
+  dw = {b1.re + b2.re, b1.im + b2.im};
+  return cmul(inner, rec).re;
+}
+
 #ifndef MOM_VOIGT_BLOCK
 #define MOM_VOIGT_BLOCK 256
 #endif
 constexpr int kBlock = MOM_VOIGT_BLOCK;  // grid points per workgroup
 
+// Dual run of voigt_block: the partials of the per-line prefactors with respect to (k = 0) pressure and (k = 1) temperature,
+// partial k of line j at p[j + ks k] (a null array counts as zeros), and the output partials dsigma[g + os k]
+struct VoigtDualArgs {
+  const double *dnu, *dgd, *dy, *dS;
+  size_t ks;
+  double *dsigma;
+  size_t os;
+};
+
+// DUAL = false is the value kernel; DUAL = true shares its candidate search and ordered compaction, stages d a, d b, d nu, d y
+// (two each) next to a, b, nu, y and sums the two partials of every grid point in the same ascending line order
+template <bool DUAL>
 __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict__ nu,
                                             const double *__restrict__ gamma_d, const double *__restrict__ y,
                                             const double *__restrict__ S, const int *__restrict__ i0,
                                             const int *__restrict__ i1, int nGrid,
                                             const double *__restrict__ grid, double *__restrict__ sigma,
-                                            double factor, int accumulate, int sorted) {
+                                            double factor, int accumulate, int sorted, const VoigtDualArgs dd) {
   // per-line constants of the candidates, staged once per workgroup: centre, S c/gamma_d, c'/gamma_d, y and the
   // 0-based window -- the two divisions by gamma_d are per LINE here, not per evaluation (same expressions, same values)
   __shared__ double c_nu[kBlock], c_a[kBlock], c_b[kBlock], c_y[kBlock];
   __shared__ int2 c_win[kBlock];  // {first point, last - first} of the window: ONE read and ONE unsigned compare per candidate
   __shared__ int wcount[kBlock / 64];
+  __shared__ double c_d[DUAL ? 8 * kBlock : 1];  // Dual run: [d a | d b | d nu | d y][k][candidate]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g0 = blockIdx.x * kBlock;             // 0-based first grid index of this block
   const int g1 = min(nGrid, g0 + kBlock) - 1;     // last
@@ -101,6 +168,7 @@ __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict
   const double gx = (gi < nGrid) ? grid[gi] : 0.0;
   const double cSqrtLn2divSqrtPi = 0.469718639319144059835, cSqrtLn2 = 0.8325546111577;
   double acc = 0.0;
+  [[maybe_unused]] double dacc[2] = {0.0, 0.0};
   // Range [jlo, jhi] of line indices whose window touches this block: one cheap strided pass (two loads and a compare
   // per line, no barrier) instead of running the ordered compaction below over the whole list -- line lists are
   // sorted by wavenumber, so the range is tight (an unsorted list still works, it only gets no benefit).  The sum
@@ -155,6 +223,18 @@ __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict
       c_b[pos] = cSqrtLn2 / gd;
       c_y[pos] = y[j];
       c_win[pos] = make_int2(lo, hi - lo);  // hi >= lo for a hit
+      if constexpr (DUAL) {  // a = S c / gamma_d, b = c' / gamma_d by the quotient rule, per LINE like the values
+        const double a = c_a[pos], b = c_b[pos];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          const size_t o = (size_t)j + dd.ks * k;
+          const double dg = dd.dgd ? dd.dgd[o] : 0.0, ds = dd.dS ? dd.dS[o] : 0.0;
+          c_d[k * kBlock + pos] = (ds * cSqrtLn2divSqrtPi - a * dg) / gd;
+          c_d[(2 + k) * kBlock + pos] = -(b * dg) / gd;
+          c_d[(4 + k) * kBlock + pos] = dd.dnu ? dd.dnu[o] : 0.0;
+          c_d[(6 + k) * kBlock + pos] = dd.dy ? dd.dy[o] : 0.0;
+        }
+      }
     }
     int nc = 0;
 #pragma unroll
@@ -174,8 +254,23 @@ __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict
       const double cn = c_nu[c], ca = c_a[c], cb = c_b[c], cy = c_y[c];
       const bool in = (unsigned)(gt - win.x) <= (unsigned)win.y;
       if (__builtin_amdgcn_ballot_w64(in) == 0) continue;
-      const double w = w_hw32sd_re(cb * (gx - cn), cy);
-      if (in) acc = fma(ca, w, acc);   // acc += a w, one rounding as before
+      if constexpr (DUAL) {
+        // x = b (g - nu): d_k x = d_k b (g - nu) - b d_k nu;  d_k sigma += d_k a Re w + a Re(w' (d_k x + i d_k y))
+        const double dist = gx - cn;
+        cplx dw;
+        const double w = w_hw32sd_dual(cb * dist, cy, dw);
+        if (in) {
+          acc = fma(ca, w, acc);
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            const double dx = c_d[(2 + k) * kBlock + c] * dist - cb * c_d[(4 + k) * kBlock + c];
+            dacc[k] += c_d[k * kBlock + c] * w + ca * (dw.re * dx - dw.im * c_d[(6 + k) * kBlock + c]);
+          }
+        }
+      } else {
+        const double w = w_hw32sd_re(cb * (gx - cn), cy);
+        if (in) acc = fma(ca, w, acc);   // acc += a w, one rounding as before
+      }
     }
 #else
     (void)gt;
@@ -189,6 +284,14 @@ __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict
 #pragma clang fp contract(off)
     const double scaled = acc * factor;
     sigma[gi] = accumulate ? sigma[gi] + scaled : acc;
+    if constexpr (DUAL) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        double *o = dd.dsigma + gi + dd.os * k;
+        const double dscaled = dacc[k] * factor;
+        *o = accumulate ? *o + dscaled : dacc[k];
+      }
+    }
   }
 }
 
@@ -198,7 +301,15 @@ __global__ void __launch_bounds__(kBlock) k_voigt(int nLines, const double *__re
                                                   const int *__restrict__ i1, int nGrid,
                                                   const double *__restrict__ grid, double *__restrict__ sigma,
                                                   double factor, int accumulate, int sorted) {
-  voigt_block(nLines, nu, gamma_d, y, S, i0, i1, nGrid, grid, sigma, factor, accumulate, sorted);
+  voigt_block<false>(nLines, nu, gamma_d, y, S, i0, i1, nGrid, grid, sigma, factor, accumulate, sorted, VoigtDualArgs{});
+}
+__global__ void __launch_bounds__(kBlock) k_voigt_dual(int nLines, const double *__restrict__ nu,
+                                                       const double *__restrict__ gamma_d, const double *__restrict__ y,
+                                                       const double *__restrict__ S, const int *__restrict__ i0,
+                                                       const int *__restrict__ i1, int nGrid,
+                                                       const double *__restrict__ grid, double *__restrict__ sigma,
+                                                       double factor, int accumulate, int sorted, VoigtDualArgs dd) {
+  voigt_block<true>(nLines, nu, gamma_d, y, S, i0, i1, nGrid, grid, sigma, factor, accumulate, sorted, dd);
 }
 
 // All layers of a profile in ONE launch (blockIdx.y = layer): the per-line prefactors of layer z sit at [k][z][cap]
@@ -210,8 +321,21 @@ __global__ void __launch_bounds__(kBlock) k_voigt_profile(int nLines, int Nz, si
                                                           const int *__restrict__ unsorted) {
   const int z = blockIdx.y;
   const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
-  voigt_block(nLines, pf + lz, pf + ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz, nGrid, grid,
-              tau_abs + (size_t)nGrid * z, factor[z], 1, unsorted[z] ? 0 : 1);
+  voigt_block<false>(nLines, pf + lz, pf + ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz, nGrid, grid,
+                     tau_abs + (size_t)nGrid * z, factor[z], 1, unsorted[z] ? 0 : 1, VoigtDualArgs{});
+}
+// ... and its Dual run: the partials of layer z's prefactors at dpf[q][k][z][cap] (q = nu, gamma_d, y, S), dtau_abs [nGrid, Nz, 2]
+__global__ void __launch_bounds__(kBlock) k_voigt_profile_dual(int nLines, int Nz, size_t cap, const double *__restrict__ pf,
+                                                               const double *__restrict__ dpf, const int *__restrict__ win, int nGrid,
+                                                               const double *__restrict__ grid, double *__restrict__ tau_abs,
+                                                               double *__restrict__ dtau_abs, const double *__restrict__ factor,
+                                                               const int *__restrict__ unsorted) {
+  const int z = blockIdx.y;
+  const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
+  const VoigtDualArgs dd = {dpf + lz, dpf + 2 * ks + lz, dpf + 4 * ks + lz, dpf + 6 * ks + lz, ks, dtau_abs + (size_t)nGrid * z,
+                            (size_t)nGrid * Nz};
+  voigt_block<true>(nLines, pf + lz, pf + ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz, nGrid, grid,
+                    tau_abs + (size_t)nGrid * z, factor[z], 1, unsorted[z] ? 0 : 1, dd);
 }
 
 thread_local double v_last_ms = 0.0;
@@ -258,7 +382,8 @@ __device__ __forceinline__ int locate_interval(const double *a, int n, double x,
   }
   return lo;
 }
-__device__ __forceinline__ double spline_eval(const double *t, const double *u, const double *z, int n1, double x) {
+// dq (optional): the derivative of the same piece with respect to x -- I + C + D differentiated term by term
+__device__ __forceinline__ double spline_eval(const double *t, const double *u, const double *z, int n1, double x, double *dq = nullptr) {
   // DataInterpolations.CubicSpline evaluation (restated in absorption.CubicSpline.__call__): interval by searchsortedlast
   const int i = min(max(locate_interval(t, n1 + 1, x, n1 >= 2 ? 1 : 0), 0), n1 - 1);  // knots t[0 .. n1]
   // the tables are Float32 (TIPS_2017.nc); products of two table entries are Float32 operations, as in the reference's
@@ -271,6 +396,7 @@ __device__ __forceinline__ double spline_eval(const double *t, const double *u, 
   const double I = z[i] * (a * a * a) / h6 + z[i + 1] * (b * b * b) / h6;
   const double C = (double)cu * b;
   const double D = (double)du * a;
+  if (dq) *dq = (z[i + 1] * (3.0 * (b * b)) / h6 - z[i] * (3.0 * (a * a)) / h6) + (double)cu - (double)du;
   return I + C + D;
 }
 __device__ __forceinline__ double interp_index(const double *grid, int n, double x, double fill) {
@@ -283,29 +409,67 @@ __device__ __forceinline__ double interp_index(const double *grid, int n, double
   const double slope = 1.0 / (grid[lo + 1] - grid[lo]);
   return slope * (x - grid[lo]) + (double)(lo + 1);
 }
+// Dual run: where the partials of nu, gamma_d, y, S of one layer go (partial k of line j at p[j + ks k]; k = 0 pressure,
+// 1 temperature) and d cgd / dT
+struct LineDualOut {
+  double *dnu, *dgd, *dy, *dS;
+  size_t ks;
+  double dcgd;
+};
+// DUAL: the same statements on ForwardDiff.Dual numbers -- every value below is formed exactly as in the value run, the
+// partials follow each statement by its rule; windows and the sortedness flag come from the values
+template <bool DUAL>
 __device__ __forceinline__ void line_prefactors_one(int j, const MomLineTable &tb, int nGrid, const double *grid, double p, double T,
                                                     double vmr, double wing, double cgd, double *nu, double *gd, double *yy, double *SS,
-                                                    int *i0, int *i1, int *unsorted) {
+                                                    int *i0, int *i1, int *unsorted, const LineDualOut dd) {
 #pragma clang fp contract(off)
   if (j >= tb.nLines) return;
   const double p_ref = 1013.25, t_ref = 296.0, c2 = 1.4387769, cLn2 = 0.6931471805599;
   const double nu0 = tb.nu0[j], E = tb.E[j];
   const double v = nu0 + p / p_ref * tb.d_air[j];
-  const double gl = (tb.g_air[j] * (1 - vmr) * p / p_ref + tb.g_self[j] * vmr * p / p_ref) * pow(t_ref / T, tb.n_air[j]);
+  const double tpow = pow(t_ref / T, tb.n_air[j]);
+  const double gl = (tb.g_air[j] * (1 - vmr) * p / p_ref + tb.g_self[j] * vmr * p / p_ref) * tpow;
   const double g = cgd * nu0 / tb.sqw[j];
   double S = tb.S0[j];
+  [[maybe_unused]] double dS_T = 0.0;
   if (E != -1.0) {
     const int is = tb.iso[j];
     const double *t = tb.tT + (size_t)is * tb.nTmax, *u = tb.tQ + (size_t)is * tb.nTmax, *z = tb.tZ + (size_t)is * tb.nTmax;
     const int n1 = tb.nT[is] - 1;
-    const double rate = spline_eval(t, u, z, n1, t_ref) / spline_eval(t, u, z, n1, T);
-    const double corr = rate * exp(c2 * E * (1 / t_ref - 1 / T)) * (1 - exp(-c2 * nu0 / T)) / (1 - exp(-c2 * nu0 / t_ref));
+    double dQ = 0.0;
+    const double Qref = spline_eval(t, u, z, n1, t_ref), Q = spline_eval(t, u, z, n1, T, DUAL ? &dQ : nullptr);
+    const double rate = Qref / Q;
+    const double e1 = exp(c2 * E * (1 / t_ref - 1 / T)), ex2 = exp(-c2 * nu0 / T), e2 = 1 - ex2, e3 = 1 - exp(-c2 * nu0 / t_ref);
+    const double corr = rate * e1 * e2 / e3;
+    if constexpr (DUAL) {  // S0 rate e1 e2 / e3: d rate = -Q(t_ref) Q'(T) / Q(T)^2, d e1 = e1 c2 E'' / T^2, d e2 = -exp(-c2 nu0 / T) c2 nu0 / T^2
+      const double drate = -(Qref / (Q * Q)) * dQ, de1 = e1 * (c2 * E * (1 / (T * T))), de2 = -(ex2 * (c2 * nu0 / (T * T)));
+      const double r1 = rate * e1, dr1 = drate * e1 + rate * de1;
+      dS_T = S * ((dr1 * e2 + r1 * de2) / e3);
+    }
     S = S * corr;
   }
   nu[j] = v;
   gd[j] = g;
-  yy[j] = sqrt(cLn2) * gl / g;
+  const double ynum = sqrt(cLn2) * gl;
+  yy[j] = ynum / g;
   SS[j] = S;
+  if constexpr (DUAL) {
+    // nu = nu0 + p / p_ref delta;  gamma_l = lin(p) (t_ref / T)^n: d/dp = the bracket times the power (no gamma_l / p),
+    // d/dT = lin n (t_ref / T)^(n - 1) (-t_ref / T^2);  gamma_d = cgd(T) nu0 / sqrt(w);  y = sqrt(ln 2) gamma_l / gamma_d
+    const double n = tb.n_air[j];
+    const double dgl_p = (tb.g_air[j] * (1 - vmr) / p_ref + tb.g_self[j] * vmr / p_ref) * tpow;
+    const double lin = tb.g_air[j] * (1 - vmr) * p / p_ref + tb.g_self[j] * vmr * p / p_ref;
+    const double dgl_T = lin * (n * pow(t_ref / T, n - 1) * (-(t_ref / (T * T))));
+    const double dg_T = dd.dcgd * nu0 / tb.sqw[j];
+    dd.dnu[j] = (1 / p_ref) * tb.d_air[j];
+    dd.dnu[j + dd.ks] = 0.0;
+    dd.dgd[j] = 0.0;
+    dd.dgd[j + dd.ks] = dg_T;
+    dd.dy[j] = sqrt(cLn2) * dgl_p * (1 / g);
+    dd.dy[j + dd.ks] = sqrt(cLn2) * dgl_T * (1 / g) + dg_T * (-(ynum / (g * g)));
+    dd.dS[j] = 0.0;
+    dd.dS[j + dd.ks] = dS_T;
+  }
   const int a = (int)rint(interp_index(grid, nGrid, v - wing, 1.0)), b = (int)rint(interp_index(grid, nGrid, v + wing, (double)nGrid));
   i0[j] = a;
   i1[j] = b;
@@ -317,15 +481,25 @@ __device__ __forceinline__ void line_prefactors_one(int j, const MomLineTable &t
 }
 __global__ void k_line_prefactors(MomLineTable tb, int nGrid, const double *grid, double p, double T, double vmr, double wing,
                                   double cgd, double *nu, double *gd, double *yy, double *SS, int *i0, int *i1, int *unsorted) {
-  line_prefactors_one(blockIdx.x * blockDim.x + threadIdx.x, tb, nGrid, grid, p, T, vmr, wing, cgd, nu, gd, yy, SS, i0, i1, unsorted);
+  line_prefactors_one<false>(blockIdx.x * blockDim.x + threadIdx.x, tb, nGrid, grid, p, T, vmr, wing, cgd, nu, gd, yy, SS, i0, i1, unsorted,
+                             LineDualOut{});
 }
 // blockIdx.y = layer; prm = [p | T | cgd][Nz]; outputs at [k][z][cap] (see k_voigt_profile)
 __global__ void k_line_prefactors_profile(MomLineTable tb, int Nz, size_t cap, int nGrid, const double *grid, const double *prm,
                                           double vmr, double wing, double *pf, int *win, int *unsorted) {
   const int z = blockIdx.y;
   const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
-  line_prefactors_one(blockIdx.x * blockDim.x + threadIdx.x, tb, nGrid, grid, prm[z], prm[Nz + z], vmr, wing, prm[2 * Nz + z], pf + lz,
-                      pf + ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz, unsorted + z);
+  line_prefactors_one<false>(blockIdx.x * blockDim.x + threadIdx.x, tb, nGrid, grid, prm[z], prm[Nz + z], vmr, wing, prm[2 * Nz + z], pf + lz,
+                             pf + ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz, unsorted + z, LineDualOut{});
+}
+// Dual run: prm = [p | T | cgd | factor | d cgd / dT][Nz]; partials at dpf[q][k][z][cap] (see k_voigt_profile_dual)
+__global__ void k_line_prefactors_profile_dual(MomLineTable tb, int Nz, size_t cap, int nGrid, const double *grid, const double *prm,
+                                               double vmr, double wing, double *pf, double *dpf, int *win, int *unsorted) {
+  const int z = blockIdx.y;
+  const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
+  const LineDualOut dd = {dpf + lz, dpf + 2 * ks + lz, dpf + 4 * ks + lz, dpf + 6 * ks + lz, ks, prm[4 * Nz + z]};
+  line_prefactors_one<true>(blockIdx.x * blockDim.x + threadIdx.x, tb, nGrid, grid, prm[z], prm[Nz + z], vmr, wing, prm[2 * Nz + z], pf + lz,
+                            pf + ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz, unsorted + z, dd);
 }
 hipError_t mom_voigt_profile_launch(hipStream_t st, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
                                     const double *prm, double vmr, double wing, double *pf, int *win, int *unsorted, double *tau_abs,
@@ -337,6 +511,18 @@ hipError_t mom_voigt_profile_launch(hipStream_t st, const MomLineTable &tb, int 
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_voigt_profile, dim3((nGrid + kBlock - 1) / kBlock, Nz), dim3(kBlock), 0, st, tb.nLines, Nz, cap, pf, win, nGrid,
                      grid, tau_abs, factor, unsorted);
+  return hipGetLastError();
+}
+hipError_t mom_voigt_profile_dual_launch(hipStream_t st, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
+                                         const double *prm, double vmr, double wing, double *pf, double *dpf, int *win, int *unsorted,
+                                         double *tau_abs, double *dtau_abs, const double *factor) {
+  if (tb.nLines <= 0 || Nz <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_line_prefactors_profile_dual, dim3((tb.nLines + 255) / 256, Nz), dim3(256), 0, st, tb, Nz, cap, nGrid, grid, prm,
+                     vmr, wing, pf, dpf, win, unsorted);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_voigt_profile_dual, dim3((nGrid + kBlock - 1) / kBlock, Nz), dim3(kBlock), 0, st, tb.nLines, Nz, cap, pf, dpf, win,
+                     nGrid, grid, tau_abs, dtau_abs, factor, unsorted);
   return hipGetLastError();
 }
 hipError_t mom_line_prefactors_launch(hipStream_t st, const MomLineTable &tb, int nGrid, const double *grid, double p, double T,
@@ -356,23 +542,38 @@ hipError_t mom_voigt_launch(hipStream_t st, int nLines, const double *nu, const 
   return hipGetLastError();
 }
 
+hipError_t mom_voigt_dual_launch(hipStream_t st, int nLines, const double *nu, const double *gamma_d, const double *y,
+                                 const double *S, const int *i0, const int *i1, int nGrid, const double *grid, double *out,
+                                 double factor, int accumulate, int sorted, const double *dnu, const double *dgd, const double *dy,
+                                 const double *dS, size_t ks, double *dout, size_t os) {
+  hipLaunchKernelGGL(k_voigt_dual, dim3((nGrid + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nLines, nu, gamma_d, y, S, i0, i1,
+                     nGrid, grid, out, factor, accumulate, sorted, VoigtDualArgs{dnu, dgd, dy, dS, ks, dout, os});
+  return hipGetLastError();
+}
+
 #define VCHK(call)                                                                                     \
   do {                                                                                                 \
     hipError_t e__ = (call);                                                                           \
     if (e__ != hipSuccess) {                                                                           \
       char buf__[384];                                                                                 \
-      snprintf(buf__, sizeof buf__, "mom_voigt_xsec: %s failed: %s", #call, hipGetErrorString(e__));   \
+      snprintf(buf__, sizeof buf__, "%s: %s failed: %s", fn, #call, hipGetErrorString(e__));           \
       mom_set_global_error(buf__);                                                                     \
       rc = MOM_EHIP;                                                                                   \
       goto done;                                                                                       \
     }                                                                                                  \
   } while (0)
 
-extern "C" int mom_voigt_xsec(int device, int nLines, const double *nu, const double *gamma_d, const double *y,
-                              const double *S, const int *ind_start, const int *ind_stop, int nGrid, const double *grid,
-                              double *sigma) {
+namespace {
+// mom_voigt_xsec (dsigma = nullptr: the value kernel) and mom_voigt_xsec_dual (dpart: dnu, dgamma_d, dy, dS, each [nLines, 2]
+// or null = zeros); `fn` is the entry point's name in the error texts
+int voigt_xsec_run(const char *fn, int device, int nLines, const double *nu, const double *gamma_d, const double *y, const double *S,
+                   const double *const *dpart, const int *ind_start, const int *ind_stop, int nGrid, const double *grid, double *sigma,
+                   double *dsigma) {
+  char buf[192];
+  const bool dual = dsigma != nullptr;
   if (nLines < 0 || nGrid <= 0 || !grid || !sigma || (nLines > 0 && (!nu || !gamma_d || !y || !S || !ind_start || !ind_stop))) {
-    mom_set_global_error("mom_voigt_xsec: bad argument (null pointer or non-positive size)");
+    snprintf(buf, sizeof buf, "%s: bad argument (null pointer or non-positive size)", fn);
+    mom_set_global_error(buf);
     return MOM_EINVAL;
   }
   int sorted = 1;  // window starts and stops non-decreasing: the kernel finds a block's lines by bisection
@@ -380,29 +581,38 @@ extern "C" int mom_voigt_xsec(int device, int nLines, const double *nu, const do
     if (ind_start[j] < ind_start[j - 1] || ind_stop[j] < ind_stop[j - 1]) { sorted = 0; break; }
   for (int j = 0; j < nLines; ++j)
     if (ind_start[j] < 1 || ind_stop[j] > nGrid) {  // empty windows (start > stop) are allowed
-      char buf[160];
-      snprintf(buf, sizeof buf, "mom_voigt_xsec: line %d: window [%d, %d] outside the grid 1..%d", j + 1, ind_start[j], ind_stop[j], nGrid);
+      snprintf(buf, sizeof buf, "%s: line %d: window [%d, %d] outside the grid 1..%d", fn, j + 1, ind_start[j], ind_stop[j], nGrid);
       mom_set_global_error(buf);
       return MOM_EINVAL;
     }
   int rc = MOM_OK;
-  // one device allocation (lines | windows | grid | sigma) and one pinned-free staging copy per array on a private
-  // stream; callers that evaluate many layers should use the handle-level mom_voigt_tau_abs, which keeps all of
-  // this resident
+  // one device allocation (lines | grid | sigma | windows; Dual run: the line partials and dsigma in front of the windows) and
+  // one pinned-free staging copy per array on a private stream; callers that evaluate many layers should use the
+  // handle-level mom_voigt_tau_abs, which keeps all of this resident
   const size_t lb = (size_t)(nLines > 0 ? nLines : 1);
-  const size_t bytes = (4 * lb + 2 * (size_t)nGrid) * sizeof(double) + 2 * lb * sizeof(int);
+  const size_t dual_doubles = dual ? 8 * lb + 2 * (size_t)nGrid : 0;
+  const size_t bytes = (4 * lb + 2 * (size_t)nGrid + dual_doubles) * sizeof(double) + 2 * lb * sizeof(int);
   char *base = nullptr;
   hipStream_t st = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { mom_set_global_error("mom_voigt_xsec: no HIP device available"); return MOM_EHIP; }
-  if (device < 0 || device >= ndev) { mom_set_global_error("mom_voigt_xsec: device index out of range"); return MOM_EINVAL; }
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    snprintf(buf, sizeof buf, "%s: no HIP device available", fn);
+    mom_set_global_error(buf);
+    return MOM_EHIP;
+  }
+  if (device < 0 || device >= ndev) {
+    snprintf(buf, sizeof buf, "%s: device index out of range", fn);
+    mom_set_global_error(buf);
+    return MOM_EINVAL;
+  }
   VCHK(hipSetDevice(device));
   VCHK(hipStreamCreate(&st));
   VCHK(hipMalloc((void **)&base, bytes));
   {
     double *d_line = (double *)base, *d_grid = d_line + 4 * lb, *d_sig = d_grid + nGrid;
-    int *d_win = (int *)(d_sig + nGrid);
+    double *d_dline = d_sig + nGrid, *d_dsig = d_dline + (dual ? 8 * lb : 0);   // Dual run only: [q][k][lb], [nGrid, 2]
+    int *d_win = (int *)(d_sig + nGrid + dual_doubles);
     const double *hsrc[4] = {nu, gamma_d, y, S};
     for (int k = 0; k < 4; ++k)
       if (nLines) VCHK(hipMemcpyAsync(d_line + k * lb, hsrc[k], (size_t)nLines * sizeof(double), hipMemcpyHostToDevice, st));
@@ -411,13 +621,26 @@ extern "C" int mom_voigt_xsec(int device, int nLines, const double *nu, const do
       VCHK(hipMemcpyAsync(d_win + lb, ind_stop, (size_t)nLines * sizeof(int), hipMemcpyHostToDevice, st));
     }
     VCHK(hipMemcpyAsync(d_grid, grid, (size_t)nGrid * sizeof(double), hipMemcpyHostToDevice, st));
+    const double *d_part[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int q = 0; q < 4 && dual && nLines; ++q) {
+      if (!dpart[q]) continue;
+      for (int k = 0; k < 2; ++k)   // host [nLines, 2] column-major -> [k][lb]
+        VCHK(hipMemcpyAsync(d_dline + (2 * q + k) * lb, dpart[q] + (size_t)nLines * k, (size_t)nLines * sizeof(double),
+                            hipMemcpyHostToDevice, st));
+      d_part[q] = d_dline + 2 * q * lb;
+    }
     VCHK(hipEventCreate(&e0));
     VCHK(hipEventCreate(&e1));
     VCHK(hipEventRecord(e0, st));
-    VCHK(mom_voigt_launch(st, nLines, d_line, d_line + lb, d_line + 2 * lb, d_line + 3 * lb, d_win, d_win + lb, nGrid, d_grid,
-                          d_sig, 1.0, 0, sorted));
+    if (dual)
+      VCHK(mom_voigt_dual_launch(st, nLines, d_line, d_line + lb, d_line + 2 * lb, d_line + 3 * lb, d_win, d_win + lb, nGrid, d_grid,
+                                 d_sig, 1.0, 0, sorted, d_part[0], d_part[1], d_part[2], d_part[3], lb, d_dsig, (size_t)nGrid));
+    else
+      VCHK(mom_voigt_launch(st, nLines, d_line, d_line + lb, d_line + 2 * lb, d_line + 3 * lb, d_win, d_win + lb, nGrid, d_grid,
+                            d_sig, 1.0, 0, sorted));
     VCHK(hipEventRecord(e1, st));
     VCHK(hipMemcpyAsync(sigma, d_sig, (size_t)nGrid * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (dual) VCHK(hipMemcpyAsync(dsigma, d_dsig, 2 * (size_t)nGrid * sizeof(double), hipMemcpyDeviceToHost, st));
     VCHK(hipStreamSynchronize(st));
     float ms = 0.f;
     VCHK(hipEventElapsedTime(&ms, e0, e1));
@@ -430,6 +653,25 @@ done:
   if (st) (void)hipStreamDestroy(st);
   return rc;
 }
+}  // namespace
 
-// GPU time of the k_voigt launch of the last mom_voigt_xsec call on this thread (HIP events), ms.
+extern "C" int mom_voigt_xsec(int device, int nLines, const double *nu, const double *gamma_d, const double *y,
+                              const double *S, const int *ind_start, const int *ind_stop, int nGrid, const double *grid,
+                              double *sigma) {
+  return voigt_xsec_run("mom_voigt_xsec", device, nLines, nu, gamma_d, y, S, nullptr, ind_start, ind_stop, nGrid, grid, sigma, nullptr);
+}
+
+extern "C" int mom_voigt_xsec_dual(int device, int nLines, const double *nu, const double *gamma_d, const double *y, const double *S,
+                                   const double *dnu, const double *dgamma_d, const double *dy, const double *dS,
+                                   const int *ind_start, const int *ind_stop, int nGrid, const double *grid, double *sigma,
+                                   double *dsigma) {
+  if (!dsigma) {
+    mom_set_global_error("mom_voigt_xsec_dual: bad argument (null pointer or non-positive size)");
+    return MOM_EINVAL;
+  }
+  const double *dpart[4] = {dnu, dgamma_d, dy, dS};
+  return voigt_xsec_run("mom_voigt_xsec_dual", device, nLines, nu, gamma_d, y, S, dpart, ind_start, ind_stop, nGrid, grid, sigma, dsigma);
+}
+
+// GPU time of the k_voigt / k_voigt_dual launch of the last mom_voigt_xsec / mom_voigt_xsec_dual call on this thread (HIP events), ms.
 extern "C" double mom_voigt_last_kernel_ms(void) { return v_last_ms; }
