@@ -46,8 +46,9 @@ struct LayerArgs {
   // striding), bit 1 = the second workgroup to arrive on a CU runs its strip chains at raised wave priority.
   int *sched;
   int sched_mode;
-  // quad-block image (mom_q4.hpp), MOM_OPT_ZERO_SKIP: block rows of four entries that hold a weighted stream entry -- the entries
-  // from 4 nbw on are zero-weight streams, whose exact-zero blocks the products leave out; 0 (or N / 4): no such rule
+  // quad-block image (mom_q4.hpp) and two-buffer strip image (mom_strip2.hpp), MOM_OPT_ZERO_SKIP: block rows of four entries that
+  // hold a weighted stream entry -- the entries from 4 nbw on are zero-weight streams, whose exact-zero blocks (k-steps) the
+  // products leave out; 0 (or N / 4): no such rule.  Set per first-stage launch: 0 where the image's bit of the option is off
   int nbw;
 };
 

@@ -331,6 +331,9 @@ static int launch_first_stage(mom_t *h, const FirstStage &fs, LayerArgs &a, bool
   HIPCHK(h, table.reserve(units, st));
   a.resume = table;
   int per_cu = fs.image->per_cu();
+  // MOM_OPT_ZERO_SKIP: bit 0 the quad-block image, bit 1 the two-buffer strip image; the other first-stage images have no such rule
+  const int skip_bit = (fs.family == MOM_IMG_QUAD) ? 1 : two_buffer ? 2 : 0;
+  if (!(h->opt_zero_skip & skip_bit)) a.nbw = 0;
   if (two_buffer) {
     h->resume2_units = units; h->resume2_nz = nzr;  // (mom_strip2_resumed)
     if (h->opt_strip2_sched) {  // the queue counter (and, for the chain priority, the per-CU tickets) start at zero: a memset ON
@@ -415,14 +418,15 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, const Comp6 &co
   if (cont && can_sweep) can_sweep = (h->iface[za] == h->iface[za + 1]);
   for (int z = za; z < zb && can_sweep; ++z) can_sweep = (h->nd[z] <= 127);
   hipStream_t cur = h->stream;  // the stream launch_layer issues to (MOM_OPT_OVERLAP switches it for the m = 0 sub-problem)
-  // nbw: LayerArgs::nbw of the stream set q (MOM_OPT_ZERO_SKIP = 0: none).  Full problem: from the weights mom_set_streams
+  // nbw: LayerArgs::nbw of the stream set q (launch_first_stage clears it where MOM_OPT_ZERO_SKIP has the image's bit off).  Full
+  // problem: from the weights mom_set_streams
   // uploaded (the dummy entries behind the N real ones only lengthen the run of zero weights); sub-problem: scene_common's count
   const int nbw_k = mom_q4_nbw(h->h_wt.data(), h->N);
   auto launch_layer = [&](int z, const DevStreams &q, int nbw, int m_first, int Mcount, const double *Zpp, const double *Zmp,
                           const auto &comp, double *scratch) -> int {  // comp[6]: buffers or raw pointers
     LayerArgs a{};
     a.q = q; a.S = h->S; a.M = Mcount; a.K = h->K; a.m_first = m_first;
-    a.nbw = h->opt_zero_skip ? nbw : 0;
+    a.nbw = nbw;
     const bool sweep = z < 0;
     if (sweep) {
       z = za;

@@ -107,15 +107,52 @@ __device__ __forceinline__ r4 mfma_f64(real a, real b, r4 c) {
   return mma16(a, b, c);
 }
 
+// Zero-weight streams (MOM_OPT_ZERO_SKIP bit 1): KW < KS k-steps of a strip product.  The stream entries from
+// 4 KW on have weight exactly 0, so every operator is [A 0; C D] with D diagonal or zero, and a strip -- columns c0 .. c0 + 15 of a
+// TRANSPOSED operator -- has in its rows k >= 4 KW exact zeros except the diagonal entry B[k][k], which lies in the strip that owns
+// column k.  The k-steps ks >= KW therefore multiply zero B operands in every wave and are left out; the one term they would have
+// added to column k, M[k + row*LD] B[k][k], is added here by a plain fma behind the kept k-steps (the matrix instruction
+// accumulates fused: the same bits).  Only the wave whose strip owns such columns (strip = its wave-uniform strip index) does
+// anything: per row tile t0 that holds rows >= 4 KW, the lanes of column col = 16 t0 + lr fetch d = B[col][col] from tile t0,
+// register lr >> 2, lane 16 (lr & 3) + lr, and the lanes with 4 KW <= col < N add M[col + row*LD] d to all their accumulators,
+// riding rows included -- the LDS addresses the k-steps left out would have read for that column.
+template <int KS, int KW>
+__device__ __forceinline__ void strip_diag_fixup(const real *M, int lr, int lq, int strip, const r4 (&B)[StripGeom<KS>::NT],
+                                                 r4 (&acc)[StripGeom<KS>::NT]) {
+  constexpr int N = StripGeom<KS>::N, NT = StripGeom<KS>::NT, LD = StripGeom<KS>::LD;
+#pragma unroll
+  for (int t0 = (4 * KW) >> 4; t0 < NT; ++t0) {
+    if (strip == t0) {
+      const int src = 16 * (lr & 3) + lr, col = 16 * t0 + lr;
+      real d = 0.0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const real v = __shfl(B[t0][r], src, 64);
+        d = ((lr >> 2) == r) ? v : d;
+      }
+      if (col >= 4 * KW && col < N) {
+        const real *m = M + col + lq * LD;
+#pragma unroll
+        for (int rt = 0; rt < NT; ++rt)  // one row tile at a time: four fragments in flight
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[rt][r] = fma(m[(16 * rt + 4 * r) * LD], d, acc[rt][r]);
+      }
+    }
+  }
+}
+
 // acc[rt] += sum_k M[k + row*LD] B[k][col], row = 16 rt + (l & 15): left-multiplication of the strip B by M^T
-template <int KS>
+// KW < KS (Float64; strip = the caller's strip index, not read otherwise): see strip_diag_fixup
+template <int KS, int KW = KS>
 __device__ __forceinline__ void strip_mul(const real *M, int lr, int lq, const r4 (&B)[StripGeom<KS>::NT],
-                                          r4 (&acc)[StripGeom<KS>::NT]) {
+                                          r4 (&acc)[StripGeom<KS>::NT], int strip = 0) {
   constexpr int NT = StripGeom<KS>::NT, LD = StripGeom<KS>::LD;
+  static_assert(KW <= KS && (kF64 || KW == KS), "Float32: the k order of a strip is permuted, no k-step can be left out");
+  constexpr int NKS = (KW < KS) ? KW : StripGeom<KS>::NKS;
   asm volatile("" : "+v"(lr), "+v"(lq));  // keep the address arithmetic inside (see item_straight)
   const real *base = M + strip_lq_base(lq) + lr * LD;
 #pragma unroll
-  for (int ks = 0; ks < StripGeom<KS>::NKS; ++ks) {
+  for (int ks = 0; ks < NKS; ++ks) {
     real a[NT];
 #pragma unroll
     for (int rt = 0; rt < NT; ++rt) a[rt] = base[strip_kofs(ks) + 16 * rt * LD];
@@ -128,18 +165,21 @@ __device__ __forceinline__ void strip_mul(const real *M, int lr, int lq, const r
     for (int rt = 0; rt < NT; ++rt) acc[rt] = mfma_f64(a[rt], b, acc[rt]);
     if ((ks + 1) % kStripChunk == 0) __builtin_amdgcn_sched_barrier(0);  // cap the A fragments in flight
   }
+  if constexpr (KW < KS) strip_diag_fixup<KS, KW>(M, lr, lq, strip, B, acc);
 }
 
 // two strips through the same multiplier: acc1 += M^T B1, acc2 += M^T B2 (A fragments loaded once)
-template <int KS>
+template <int KS, int KW = KS>
 __device__ __forceinline__ void strip_mul2(const real *M, int lr, int lq, const r4 (&B1)[StripGeom<KS>::NT],
                                            r4 (&acc1)[StripGeom<KS>::NT], const r4 (&B2)[StripGeom<KS>::NT],
-                                           r4 (&acc2)[StripGeom<KS>::NT]) {
+                                           r4 (&acc2)[StripGeom<KS>::NT], int strip = 0) {
   constexpr int NT = StripGeom<KS>::NT, LD = StripGeom<KS>::LD;
+  static_assert(KW <= KS && (kF64 || KW == KS), "Float32: the k order of a strip is permuted, no k-step can be left out");
+  constexpr int NKS = (KW < KS) ? KW : StripGeom<KS>::NKS;
   asm volatile("" : "+v"(lr), "+v"(lq));
   const real *base = M + strip_lq_base(lq) + lr * LD;
 #pragma unroll
-  for (int ks = 0; ks < StripGeom<KS>::NKS; ++ks) {
+  for (int ks = 0; ks < NKS; ++ks) {
     real a[NT];
 #pragma unroll
     for (int rt = 0; rt < NT; ++rt) a[rt] = base[strip_kofs(ks) + 16 * rt * LD];
@@ -150,6 +190,10 @@ __device__ __forceinline__ void strip_mul2(const real *M, int lr, int lq, const 
       acc2[rt] = mfma_f64(a[rt], b2, acc2[rt]);
     }
     if ((ks + 1) % kStripChunk == 0) __builtin_amdgcn_sched_barrier(0);
+  }
+  if constexpr (KW < KS) {
+    strip_diag_fixup<KS, KW>(M, lr, lq, strip, B1, acc1);
+    strip_diag_fixup<KS, KW>(M, lr, lq, strip, B2, acc2);
   }
 }
 

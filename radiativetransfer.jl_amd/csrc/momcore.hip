@@ -254,7 +254,10 @@ extern "C" int mom_set_option(mom_t *h, int option, int value) {
     if (value < 0 || value > 3) return fail(h, MOM_EINVAL, "mom_set_option: MOM_OPT_STRIP2_SCHED takes a mask of bits 0 and 1");
     h->opt_strip2_sched = value;
   }
-  else if (option == MOM_OPT_ZERO_SKIP) h->opt_zero_skip = value;
+  else if (option == MOM_OPT_ZERO_SKIP) {
+    if (value < 0 || value > 3) return fail(h, MOM_EINVAL, "mom_set_option: MOM_OPT_ZERO_SKIP takes a mask of bits 0 and 1");
+    h->opt_zero_skip = value;
+  }
   else if (option == MOM_OPT_DUAL_WORKSPACE_MB) {
     if (value < 0) return fail(h, MOM_EINVAL, "mom_set_option: MOM_OPT_DUAL_WORKSPACE_MB takes megabytes >= 0 (0 = 60 % of the free HBM)");
     h->opt_dual_budget = (size_t)value << 20;
