@@ -513,16 +513,21 @@ int mom_timers(mom_t *h, double *ms, int n, int *kernel_launches);
  *                         chains at raised wave priority (an experiment: the two units do not run in lock-step to begin with, and the
  *                         priority measured 1.6 ms slower on C2 on top of the queue, profiles/r08_C2_ab.txt).  0 = neither (the
  *                         scheduling before this option existed).  Results do not depend on it: units are independent.
- *   MOM_OPT_ZERO_SKIP     a mask (default 3) of the images whose products leave out what is an exact zero because of the zero-weight
+ *   MOM_OPT_ZERO_SKIP     a mask (default 7) of the images whose products leave out what is an exact zero because of the zero-weight
  *                         streams at the end of the stream set (the view angles, the Sun, dummy entries): the driver counts the
  *                         trailing weights that are exactly 0.0, and the first nbw = ceil((N - count) / 4) blocks of four entries
  *                         hold the weighted ones.  Bit 0 = the quad-block image (operator edges 20 .. 40, csrc/mom_q4.hpp) leaves
  *                         out the zero blocks: a launch takes the kernel compiled for nbw (or the next larger number it has: 0, 1,
  *                         2 or 4 blocks left out).  Bit 1 = the two-buffer strip image (edges 52 / 56 / 60, csrc/mom_strip2.hpp)
  *                         leaves out the last KS - nbw k-steps of every strip product (0 .. 3 of them, the largest number it has
- *                         that is still exact) and adds the diagonal entries of those columns by a fused multiply-add.  A bit
- *                         that is off = the kernel that multiplies everything.  The terms left out are exact zeros: stored
- *                         values, series lengths and resume decisions do not depend on the option (at most the sign of a zero does).
+ *                         that is still exact) and adds the diagonal entries of those columns by a fused multiply-add.  Bit 2 =
+ *                         the two-buffer strip image's row-block rule: a 16-row tile of a strip product in which only some blocks
+ *                         of four rows are live (rows of weighted entries, the riding source rows) runs one 4 x 4 x 4 matrix
+ *                         instruction per live block instead of the 16 x 16 x 4 one; the rows of the zero-weight streams get
+ *                         their one term from the fused multiply-add of bit 1, the rows past the riding rows are not computed.
+ *                         Without bit 1 it covers only the latter (edges 52 and 56).  A bit that is off = the kernel that
+ *                         multiplies everything.  The terms left out are exact zeros: stored values, series lengths and resume
+ *                         decisions do not depend on the option (at most the sign of a zero does).
  */
 int mom_set_option(mom_t *h, int option, int value);
 

@@ -40,7 +40,7 @@ MOM_OPT_RRS_KERNELS = 10   # mask: 1 WG pairs, 2 ... for 16 < N <= 32, 4 WG poin
 MOM_OPT_DUAL_WORKSPACE_MB = 11   # operator workspace of mom_rt_run_dual (0: 60 % of the free HBM)
 MOM_OPT_STRIP2 = 12              # N = 52, 56, 60 on the two-buffer 4-wave image first (1, default), 0 = the 8-wave image only
 MOM_OPT_STRIP2_SCHED = 13        # its scheduling, a mask (1, default): 1 = shared unit queue, 2 = asymmetric chain priority (off: measured slower); 0 = neither
-MOM_OPT_ZERO_SKIP = 14           # leave out the exact-zero products of the zero-weight trailing streams, a mask (3, default): 1 = quad-block image (blocks), 2 = two-buffer strip image (k-steps); 0 = every product
+MOM_OPT_ZERO_SKIP = 14           # leave out the exact-zero products of the zero-weight trailing streams, a mask (7, default): 1 = quad-block image (blocks), 2 = two-buffer strip image (k-steps), 4 = two-buffer strip image (blocks of four rows of a partly live row tile); 0 = every product
 
 
 class MomError(RuntimeError):

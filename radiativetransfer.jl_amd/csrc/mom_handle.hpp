@@ -89,8 +89,9 @@ struct mom_handle : MomSceneBufs<double> {
   int opt_strip2_sched = 1;  // MOM_OPT_STRIP2_SCHED: bit 0 = shared unit queue, bit 1 = asymmetric chain priority (mom_strip2.hpp; one
                              // kernel per value); the priority measured slower on top of the queue (profiles/r08_C2_ab.txt): off
   MomDevBuf<int> d_sched2;   // LayerArgs::sched of the two-buffer image: zeroed on the stream before each of its launches
-  int opt_zero_skip = 3;     // MOM_OPT_ZERO_SKIP, a mask: the exact-zero products of the zero-weight trailing streams are left out by
-                             // 1 the quad-block image (blocks), 2 the two-buffer strip image (k-steps of its strip products)
+  int opt_zero_skip = 7;     // MOM_OPT_ZERO_SKIP, a mask: the exact-zero products of the zero-weight trailing streams are left out by
+                             // 1 the quad-block image (blocks), 2 the two-buffer strip image (k-steps of its strip products);
+                             // 4 the two-buffer strip image multiplies only the live blocks of four rows of a partly live row tile
   int nbw_0 = 0;             // blocks of four entries with a weighted one (mom_q4_nbw) of the m = 0 sub-problem, after reduction and padding
   int Nk = 0;              // operator edge the scene-level kernels of the full problem run with (>= N)
   mom::DevStreams qk{};         // q with N = Nk

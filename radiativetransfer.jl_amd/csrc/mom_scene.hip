@@ -4,6 +4,7 @@
 #include "mom_handle.hpp"
 #include "mom_images.hpp"
 #include "mom_reduce.hpp"
+#include "mom_strip2_variants.hpp"
 
 using namespace mom;
 
@@ -331,9 +332,11 @@ static int launch_first_stage(mom_t *h, const FirstStage &fs, LayerArgs &a, bool
   HIPCHK(h, table.reserve(units, st));
   a.resume = table;
   int per_cu = fs.image->per_cu();
-  // MOM_OPT_ZERO_SKIP: bit 0 the quad-block image, bit 1 the two-buffer strip image; the other first-stage images have no such rule
+  // MOM_OPT_ZERO_SKIP: bit 0 the quad-block image, bit 1 the two-buffer strip image; the other first-stage images have no such rule.
+  // Bit 2, the row-block rule of the two-buffer strip image, rides in nbw as a flag (mom_strip2_variants.hpp)
   const int skip_bit = (fs.family == MOM_IMG_QUAD) ? 1 : two_buffer ? 2 : 0;
   if (!(h->opt_zero_skip & skip_bit)) a.nbw = 0;
+  if (two_buffer && (h->opt_zero_skip & 4)) a.nbw |= kS2RowBlocks;
   if (two_buffer) {
     h->resume2_units = units; h->resume2_nz = nzr;  // (mom_strip2_resumed)
     if (h->opt_strip2_sched) {  // the queue counter (and, for the chain priority, the per-CU tickets) start at zero: a memset ON

@@ -141,16 +141,84 @@ __device__ __forceinline__ void strip_diag_fixup(const real *M, int lr, int lq, 
   }
 }
 
+// Row blocks (MOM_OPT_ZERO_SKIP bit 2, RB; Float64).  Block row bi = 4 rt + r of a strip -- register r of row
+// tile rt, rows 4 bi .. 4 bi + 3 -- is
+//   live       bi < KW (rows of weighted entries) or bi == KS (the riding rows N, N + 1: 4 RT + RR0 == KS);
+//   passenger  KW <= bi < KS: rows of zero-weight streams.  Row i of M^T is column i of an operator [A 0; C D], zero but for M[i][i],
+//              and row i of the strip operand is zero but for column i: the one term of the product is the one strip_diag_fixup adds
+//              to every row, so RB with KW < KS relies on the fix-up;
+//   dead       bi > KS: rows past the riding rows, which nothing reads.
+// A row tile with four live block rows keeps its v_mfma_f64_16x16x4; one with L <= 3 issues L v_mfma_f64_4x4x4_4b on those
+// components of its accumulator: B and D of the small instruction are the strip's registers unchanged (B: k = lq, column lr; D:
+// row 4 bi + lq, column lr), its A operand is the 4 x 4 block M[4 ks + lq + (4 bi + (lr & 3)) LD], the same in all four lane
+// groups (the broadcast read of mom_q4.hpp).  Both forms add the four products of a k-step to the accumulator with the same
+// rounding (tools/mfma_f64_forms_check.hip, profiles/r15_mfma_forms.txt): a live element keeps its bits.  Passenger and dead
+// components keep the value they came in with (passenger: + the fix-up term), where the large instruction added exact zeros or
+// computed rows nobody reads.  (The riding block being an instruction of its own, the compiler drops it from the products whose
+// riding rows the caller does not pick -- the Horner loops.)
+template <int KS, int KW>
+__device__ __forceinline__ constexpr bool strip_blk_live(int bi) { return bi < KW || bi == KS; }
+template <int KS, int KW>
+__device__ __forceinline__ constexpr bool strip_tile_full(int rt) {
+  return strip_blk_live<KS, KW>(4 * rt) && strip_blk_live<KS, KW>(4 * rt + 1) && strip_blk_live<KS, KW>(4 * rt + 2) &&
+         strip_blk_live<KS, KW>(4 * rt + 3);
+}
+__device__ __forceinline__ real mfma4_f64(real a, real b, real c) { return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0); }
+// the A fragments of k-step ks under the row-block rule: a[rt] for the full tiles, a4[rt][r] for the live blocks of the others
+template <int KS, int KW>
+__device__ __forceinline__ void strip_frag_rb(const real *base, const real *base4, int ks, real (&a)[StripGeom<KS>::NT],
+                                              real (&a4)[StripGeom<KS>::NT][4]) {
+  constexpr int NT = StripGeom<KS>::NT, LD = StripGeom<KS>::LD;
+#pragma unroll
+  for (int rt = 0; rt < NT; ++rt) {
+    if (strip_tile_full<KS, KW>(rt)) {
+      a[rt] = base[4 * ks + 16 * rt * LD];
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (strip_blk_live<KS, KW>(4 * rt + r)) a4[rt][r] = base4[4 * ks + (16 * rt + 4 * r) * LD];
+    }
+  }
+}
+template <int KS, int KW>
+__device__ __forceinline__ void strip_mma_rb(const real (&a)[StripGeom<KS>::NT], const real (&a4)[StripGeom<KS>::NT][4], real b,
+                                             r4 (&acc)[StripGeom<KS>::NT]) {
+  constexpr int NT = StripGeom<KS>::NT;
+#pragma unroll
+  for (int rt = 0; rt < NT; ++rt) {
+    if (strip_tile_full<KS, KW>(rt)) {
+      acc[rt] = mfma_f64(a[rt], b, acc[rt]);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (strip_blk_live<KS, KW>(4 * rt + r)) acc[rt][r] = mfma4_f64(a4[rt][r], b, acc[rt][r]);
+    }
+  }
+}
+
 // acc[rt] += sum_k M[k + row*LD] B[k][col], row = 16 rt + (l & 15): left-multiplication of the strip B by M^T
-// KW < KS (Float64; strip = the caller's strip index, not read otherwise): see strip_diag_fixup
-template <int KS, int KW = KS>
+// KW < KS (Float64; strip = the caller's strip index, not read otherwise): see strip_diag_fixup; RB: the row-block rule above
+template <int KS, int KW = KS, bool RB = false>
 __device__ __forceinline__ void strip_mul(const real *M, int lr, int lq, const r4 (&B)[StripGeom<KS>::NT],
                                           r4 (&acc)[StripGeom<KS>::NT], int strip = 0) {
   constexpr int NT = StripGeom<KS>::NT, LD = StripGeom<KS>::LD;
   static_assert(KW <= KS && (kF64 || KW == KS), "Float32: the k order of a strip is permuted, no k-step can be left out");
+  static_assert(!RB || kF64, "Float32: register r of a tile is no block of four rows");
   constexpr int NKS = (KW < KS) ? KW : StripGeom<KS>::NKS;
   asm volatile("" : "+v"(lr), "+v"(lq));  // keep the address arithmetic inside (see item_straight)
   const real *base = M + strip_lq_base(lq) + lr * LD;
+  if constexpr (RB) {
+    const real *base4 = M + lq + (lr & 3) * LD;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+      real a[NT], a4[NT][4];
+      strip_frag_rb<KS, KW>(base, base4, ks, a, a4);
+      strip_mma_rb<KS, KW>(a, a4, B[ks >> 2][ks & 3], acc);
+      if ((ks + 1) % kStripChunk == 0) __builtin_amdgcn_sched_barrier(0);  // cap the A fragments in flight
+    }
+    if constexpr (KW < KS) strip_diag_fixup<KS, KW>(M, lr, lq, strip, B, acc);
+    return;
+  }
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) {
     real a[NT];
@@ -169,15 +237,32 @@ __device__ __forceinline__ void strip_mul(const real *M, int lr, int lq, const r
 }
 
 // two strips through the same multiplier: acc1 += M^T B1, acc2 += M^T B2 (A fragments loaded once)
-template <int KS, int KW = KS>
+template <int KS, int KW = KS, bool RB = false>
 __device__ __forceinline__ void strip_mul2(const real *M, int lr, int lq, const r4 (&B1)[StripGeom<KS>::NT],
                                            r4 (&acc1)[StripGeom<KS>::NT], const r4 (&B2)[StripGeom<KS>::NT],
                                            r4 (&acc2)[StripGeom<KS>::NT], int strip = 0) {
   constexpr int NT = StripGeom<KS>::NT, LD = StripGeom<KS>::LD;
   static_assert(KW <= KS && (kF64 || KW == KS), "Float32: the k order of a strip is permuted, no k-step can be left out");
+  static_assert(!RB || kF64, "Float32: register r of a tile is no block of four rows");
   constexpr int NKS = (KW < KS) ? KW : StripGeom<KS>::NKS;
   asm volatile("" : "+v"(lr), "+v"(lq));
   const real *base = M + strip_lq_base(lq) + lr * LD;
+  if constexpr (RB) {
+    const real *base4 = M + lq + (lr & 3) * LD;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+      real a[NT], a4[NT][4];
+      strip_frag_rb<KS, KW>(base, base4, ks, a, a4);
+      strip_mma_rb<KS, KW>(a, a4, B1[ks >> 2][ks & 3], acc1);
+      strip_mma_rb<KS, KW>(a, a4, B2[ks >> 2][ks & 3], acc2);
+      if ((ks + 1) % kStripChunk == 0) __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (KW < KS) {
+      strip_diag_fixup<KS, KW>(M, lr, lq, strip, B1, acc1);
+      strip_diag_fixup<KS, KW>(M, lr, lq, strip, B2, acc2);
+    }
+    return;
+  }
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) {
     real a[NT];

@@ -122,7 +122,7 @@ __device__ __forceinline__ void make_ctx_s2(Ctx &c, int N, int inv_mode, int ns,
 
 // One doubling step (doubling.jl:44-67) in two buffers; returns false, before anything of the step is stored, if it needs the
 // general path.  In: c.r (riding columns N, N + 1 = j0+, j0-), c.t, c.jp, c.jm; out: the same, as doubling_step_strip.
-template <int KS, int KW>
+template <int KS, int KW, bool RB>
 __device__ __forceinline__ bool doubling_step_s2(Ctx &c, real expk) {
   using G = StripGeom<KS>;
   constexpr int N = G::N, NT = G::NT, LD = G::LD;
@@ -141,7 +141,7 @@ __device__ __forceinline__ bool doubling_step_s2(Ctx &c, real expk) {
     r4 W[NT], B[NT];
     strip_load_lds<KS>(r, lr, lq, c0, W);
     strip_zero(B);
-    strip_mul<KS, KW>(r, lr, lq, W, B, wave);
+    strip_mul<KS, KW, RB>(r, lr, lq, W, B, wave);
     strip_store_lds<KS>(P, lr, lq, c0, colok, B);
     if (colok) {
       if (lq == G::LQ0) P[col + N * LD] = B[G::RT][G::RR0];        // (r j0+)[col]
@@ -170,21 +170,21 @@ __device__ __forceinline__ bool doubling_step_s2(Ctx &c, real expk) {
   for (int k = 1; k < p; ++k) {
     r4 acc[NT];
     strip_copy(acc, T0);
-    strip_mul<KS, KW>(P, lr, lq, Y, acc, wave);
+    strip_mul<KS, KW, RB>(P, lr, lq, Y, acc, wave);
     strip_copy(Y, acc);
   }
   r4 Zt[NT];
   strip_zero(Zt);
-  strip_mul<KS, KW>(r, lr, lq, Y, Zt, wave);  // (A r)^T ; rows N, N+1: (A w1)^T, (A w2)^T
+  strip_mul<KS, KW, RB>(r, lr, lq, Y, Zt, wave);  // (A r)^T ; rows N, N+1: (A w1)^T, (A w2)^T
   const real aw = Zt[G::RT][G::RR0], aw2 = Zt[G::RT][G::RR1];
   __syncthreads();  // every wave is done with P
   strip_store_lds<KS>(t, lr, lq, c0, colok, T0);  // t back
   __syncthreads();
   r4 Rn[NT], Tn[NT];
   strip_load_lds<KS>(r, lr, lq, c0, Rn);
-  strip_mul<KS, KW>(t, lr, lq, Zt, Rn, wave);  // r^T + t^T (A r)^T      (:64)
+  strip_mul<KS, KW, RB>(t, lr, lq, Zt, Rn, wave);  // r^T + t^T (A r)^T      (:64)
   strip_zero(Tn);
-  strip_mul<KS, KW>(t, lr, lq, Y, Tn, wave);   // t^T A^T                (:67)
+  strip_mul<KS, KW, RB>(t, lr, lq, Y, Tn, wave);   // t^T A^T                (:67)
   __syncthreads();  // every wave is done reading r and t of this step
   strip_store_lds<KS>(r, lr, lq, c0, colok, Rn);
   strip_store_lds<KS>(t, lr, lq, c0, colok, Tn);
@@ -203,7 +203,7 @@ __device__ __forceinline__ bool doubling_step_s2(Ctx &c, real expk) {
 }
 
 // nd doubling steps; bail = true (nothing of the layer has left the workgroup) if a step needs the general path
-template <int KS, bool PRIO, int KW>
+template <int KS, bool PRIO, int KW, bool RB>
 __device__ __forceinline__ real doubling_run_s2(Ctx &c, int nd, real expk, bool &bail) {
   const int N = c.N, ld = c.ld;
   bail = false;
@@ -216,7 +216,7 @@ __device__ __forceinline__ real doubling_run_s2(Ctx &c, int nd, real expk, bool 
   const int fav = PRIO ? s2_favoured(c) : 0;
   s2_chain<true, PRIO>(c, S2_SEC_ELEM, fav);  // a doubling step is products and barriers throughout
   for (int it = 0; it < nd; ++it) {
-    if (!doubling_step_s2<KS, KW>(c, expk)) {
+    if (!doubling_step_s2<KS, KW, RB>(c, expk)) {
       s2_chain<false, PRIO>(c, S2_SEC_DBL, fav);
       bail = true;
       return expk;
@@ -242,7 +242,7 @@ __device__ __forceinline__ real doubling_run_s2(Ctx &c, int nd, real expk, bool 
 
 // ScatteringInterface_11 in two buffers (see interaction_strip for the algebra; same products, same order).  Returns false,
 // nothing stored, if the series is too long.  Ends with a barrier.
-template <int KS, bool PRIO, int KW>
+template <int KS, bool PRIO, int KW, bool RB>
 __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) {
   using G = StripGeom<KS>;
   constexpr int N = G::N, NT = G::NT, LD = G::LD, NN = N * N, U = (NN + kThreads - 1) / kThreads;
@@ -283,7 +283,7 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
   r4 Bs[NT], W0[NT];
   real ss = 0.0;
   strip_zero(Bs);
-  strip_mul<KS, KW>(Rpm, lr, lq, rT, Bs, wave);
+  strip_mul<KS, KW, RB>(Rpm, lr, lq, rT, Bs, wave);
   if (colok) {
 #pragma unroll
     for (int rt = 0; rt < NT; ++rt)
@@ -295,7 +295,7 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
     r4 tT[NT];
     strip_load_lds<KS>(t, lr, lq, c0, tT);
     strip_zero(W0);
-    strip_mul<KS, KW>(Rpm, lr, lq, tT, W0, wave);
+    strip_mul<KS, KW, RB>(Rpm, lr, lq, tT, W0, wave);
   }
   __syncthreads();  // every wave is done with R+-
   real *B = r;      // B replaces R+-
@@ -316,7 +316,7 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
   for (int k = 1; k < p; ++k) {  // Y2 <- W0 + B^T Y2 : X^T
     r4 acc[NT];
     strip_copy(acc, W0);
-    strip_mul<KS, KW>(B, lr, lq, Y2, acc, wave);
+    strip_mul<KS, KW, RB>(B, lr, lq, Y2, acc, wave);
     strip_copy(Y2, acc);
   }
   {
@@ -327,7 +327,7 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
     for (int k = 1; k < p; ++k) {  // Y1 <- T--^T + B^T Y1 : T01^T
       r4 acc[NT];
       strip_copy(acc, T1);
-      strip_mul<KS, KW>(B, lr, lq, Y1, acc, wave);
+      strip_mul<KS, KW, RB>(B, lr, lq, Y1, acc, wave);
       strip_copy(Y1, acc);
     }
   }
@@ -341,25 +341,25 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
     strip_copy(Yf, Y1);
     strip_flip(Yf, mask);
     strip_zero(o);
-    strip_mul<KS, KW>(t, lr, lq, Yf, o, wave);
+    strip_mul<KS, KW, RB>(t, lr, lq, Yf, o, wave);
     strip_flip(o, mask);
     strip_store_glb<KS>(g.T_mm, lr, lq, c0, colok, o);
   }
   // V = (T01 r-+)^T = r-+^T Y1 ; row N: (T01 j0-)^T
   r4 V[NT];
   strip_zero(V);
-  strip_mul<KS, KW>(r, lr, lq, Y1, V, wave);
+  strip_mul<KS, KW, RB>(r, lr, lq, Y1, V, wave);
   // T21^T = t++^T + r-+^T X^T ; row N: (X j0-)^T
   r4 T21[NT];
   strip_load_lds<KS>(t, lr, lq, c0, T21);
-  strip_mul<KS, KW>(r, lr, lq, Y2, T21, wave);
+  strip_mul<KS, KW, RB>(r, lr, lq, Y2, T21, wave);
   {  // R+- = r+- + X t--  ->  D (D r+-^T + t^T D X^T), D r+-^T[row][col] = sg[col] r-+[col][row]   (:116)
     r4 acc[NT];
     const real sc = colok ? c.sg[col] : 1.0;
 #pragma unroll
     for (int rt = 0; rt < NT; ++rt) acc[rt] = rT[rt] * sc;
     strip_flip(Y2, mask);
-    strip_mul<KS, KW>(t, lr, lq, Y2, acc, wave);
+    strip_mul<KS, KW, RB>(t, lr, lq, Y2, acc, wave);
     strip_flip(acc, mask);
     strip_store_glb<KS>(g.R_pm, lr, lq, c0, colok, acc);
   }
@@ -396,7 +396,7 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
   s2_chain<true, PRIO>(c, S2_SEC_ICOPY2, fav);
   const real *Tpp = t;
   // R-+ = R-+ + (T01 r-+) T++  ->  R-+^T + T++^T V ; row N: (T01 r-+ J0+)^T        (:93)
-  strip_mul<KS, KW>(Tpp, lr, lq, V, Radd, wave);
+  strip_mul<KS, KW, RB>(Tpp, lr, lq, V, Radd, wave);
   strip_store_glb<KS>(g.R_mp, lr, lq, c0, colok, Radd);
   // J0- = J0- + T01 (r-+ J0+ + j0-)                                                (:90)
   if (colok && lq == G::LQ0) g.J0m[col] = j0m + (Radd[G::RT][G::RR0] + V[G::RT][G::RR0]);
@@ -404,7 +404,7 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
   {
     r4 o[NT];
     strip_zero(o);
-    strip_mul<KS, KW>(Tpp, lr, lq, T21, o, wave);
+    strip_mul<KS, KW, RB>(Tpp, lr, lq, T21, o, wave);
     strip_store_glb<KS>(g.T_pp, lr, lq, c0, colok, o);
     // J0+ = j0+ + T21 (J0+ + R+- j0-)                                                (:110)
     if (colok && lq == G::LQ0) g.J0p[col] = c.jp[col] + (o[G::RT][G::RR0] + T21[G::RT][G::RR0]);
@@ -421,7 +421,12 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
 // KW < KS (MOM_OPT_ZERO_SKIP bit 1; the host picks it from LayerArgs::nbw, mom_strip2_variants.hpp): every strip product of the
 // image runs KW k-steps and the diagonal fix-up (mom_strip.hpp strip_diag_fixup), strip index = wave.  Only the products change:
 // Frobenius sums, series lengths, resume decisions, stores and the elemental layer are those of KW = KS.
-template <int KS, int MODE, int KW = KS>
+// RB (MOM_OPT_ZERO_SKIP bit 2; default mode only): every strip product follows the row-block rule of mom_strip.hpp strip_mul -- the
+// row tiles that hold rows of zero-weight streams or rows past the riding rows run v_mfma_f64_4x4x4_4b on their live blocks of four
+// rows.  The strip rows that keep their incoming value under it are read by nothing: the stores and the Frobenius sums are guarded
+// by strip_rowok (rows < N), strip_flip only changes signs, the riding rows N, N + 1 lie in a live block, and a strip's rows >= N
+// never are a B operand (KS k-steps at most).
+template <int KS, int MODE, int KW = KS, bool RB = false>
 __global__ void __launch_bounds__(kThreads, 2) k_layer_s2(const LayerArgs a) {
   // (the argument block is never written: see k_layer_lean)
   constexpr int N = 4 * KS;
@@ -484,7 +489,7 @@ __global__ void __launch_bounds__(kThreads, 2) k_layer_s2(const LayerArgs a) {
       ZMix zmp{as_global(a.Zmp) + NNs * a.K * mrel, ls + 3, a.K, N};
       elemental_build<true>(c, a.q, m, nd, tau_sum, dtau, varpi, zpp, zmp);
       bool bail;
-      expk = doubling_run_s2<KS, PRIO, KW>(c, nd, expk, bail);
+      expk = doubling_run_s2<KS, PRIO, KW, RB>(c, nd, expk, bail);
       if (!bail) {
         if constexpr (QUEUE) pt = S2_UNIT(c);
         const CompPtrs g = comp_ptrs(a.comp, N, comp_pitch(N), pt);
@@ -493,7 +498,7 @@ __global__ void __launch_bounds__(kThreads, 2) k_layer_s2(const LayerArgs a) {
           __syncthreads();
           MOM_TL(c, S2_SEC_FIRST);
         } else {
-          bail = !interaction_strip_s2<KS, PRIO, KW>(c, g);
+          bail = !interaction_strip_s2<KS, PRIO, KW, RB>(c, g);
         }
       }
       if (bail) {  // workgroup-uniform: the 8-wave image redoes this layer and finishes the unit

@@ -255,7 +255,7 @@ extern "C" int mom_set_option(mom_t *h, int option, int value) {
     h->opt_strip2_sched = value;
   }
   else if (option == MOM_OPT_ZERO_SKIP) {
-    if (value < 0 || value > 3) return fail(h, MOM_EINVAL, "mom_set_option: MOM_OPT_ZERO_SKIP takes a mask of bits 0 and 1");
+    if (value < 0 || value > 7) return fail(h, MOM_EINVAL, "mom_set_option: MOM_OPT_ZERO_SKIP takes a mask of bits 0, 1 and 2");
     h->opt_zero_skip = value;
   }
   else if (option == MOM_OPT_DUAL_WORKSPACE_MB) {
