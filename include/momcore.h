@@ -3,8 +3,8 @@
  *
  * Drop-in boundary for ONE path of vSmartMOM.jl (RadiativeTransfer/RadiativeTransfer.jl):
  * the CoreRT layer-adding loop  elemental! -> doubling! -> interaction!  inside rt_run,
- * the Lambertian surface + post-processing that close it, and the Absorption Voigt
- * line-shape kernel.  Every entry point names the reference interface it replaces
+ * the Lambertian surface + post-processing that close it, and the Absorption line-shape
+ * kernel (Voigt, Doppler and Lorentz broadening).  Every entry point names the reference interface it replaces
  * (file:line relative to the reference root).  A Julia maintainer binds these with
  * `ccall((:mom_xxx, libmomcore), Cint, (...), ...)` -- see INTEGRATION.md.
  *
@@ -22,8 +22,8 @@
  *   - `dtype` of mom_create: 0 = Float64 (the reference's default float_type), 1 = Float32 (float_type = Float32,
  *     parameters_from_yaml.jl:160): operators, sources and products in f32 on the GPU.  The ABI keeps Float64 host
  *     arrays for both (inputs are rounded on upload, outputs widened on download).  A Float32 handle supports the
- *     scene-level path -- mom_set_streams, mom_scene_set, mom_scene_set_optics with the mom_absorption_* / mom_voigt_tau_abs*
- *     entry points that feed it (the layer optics are assembled in Float64 on the device and rounded to Float32 there),
+ *     scene-level path -- mom_set_streams, mom_scene_set, mom_scene_set_optics with the mom_absorption_* / mom_voigt_tau_abs* /
+ *     mom_lineshape_tau_abs* entry points that feed it, mom_absorption_set_model and mom_absorption_get_gamma_l included (the layer optics are assembled in Float64 on the device and rounded to Float32 there),
  *     mom_scene_set_surface, mom_set_option, mom_rt_run, mom_get_RT, mom_get_hdr, mom_timers, mom_sync, mom_check: the lane- and wave-per-point kernels (incl. the packed
  *     points at N = 5 ... 8), the strip-chained images (N = 36 ... 60, 4-wave builds: two workgroups per CU), the m = 0
  *     (I,Q) reduction and the padding to the strip sizes --, the operator-level API -- mom_elemental, mom_doubling,
@@ -353,6 +353,38 @@ int mom_voigt_tau_abs_profile_dual(mom_t *h, int Nz, const double *pressure, con
                                    double wing_cutoff, const double *factor, double *gpu_ms);
 int mom_absorption_get_partials(mom_t *h, double *dtau_abs);
 int mom_absorption_get_prefactor_partials(mom_t *h, int n, double *dnu, double *dgamma_d, double *dy, double *dS);
+enum { MOM_BROADENING_VOIGT = 0, MOM_BROADENING_DOPPLER = 1, MOM_BROADENING_LORENTZ = 2 };
+enum { MOM_CEF_HW32SD = 0, MOM_CEF_HW32VOIGT = 1 };
+/* ---- The absorption model: HitranModel.broadening and HitranModel.CEF (Absorption/types.jl; the YAML reader's
+ * `broadening: Voigt() | Doppler() | Lorentz()` and `CEF:`, parameters_from_yaml.jl:114-115) select the method of line_shape!
+ * (compute_absorption_cross_section.jl:167-183) and of w(CEF, z) (complex_error_functions.jl:195-271).  Built: Voigt with
+ * HumlicekWeidemann32SDErrorFunction (:226-234, the default) or HumlicekWeidemann32VoigtErrorFunction (:210-219), Doppler and
+ * Lorentz (which ignore the CEF, as the reference's methods do).  Value and Dual run, Float64 and Float32 handles alike.
+ *   mom_absorption_set_model    the model of every later absorption call on the handle, kept until changed (also across
+ *                               mom_absorption_begin, and allowed between two absorbers accumulated into one table); an unknown
+ *                               code: MOM_EINVAL with the code in the text.  The device-prefactor entry points
+ *                               (mom_voigt_tau_abs_layer, _profile, _profile_dual) follow it; mom_voigt_tau_abs / _dual take
+ *                               no gamma_l, run Voigt with the handle's CEF and return MOM_ESTATE (pointing to
+ *                               mom_lineshape_tau_abs) when the handle's broadening is not Voigt.
+ *   mom_lineshape_tau_abs       mom_voigt_tau_abs for the handle's model: the five per-line prefactors that line_shape! takes
+ *                               (compute_absorption_cross_section.jl:118-124).  An array the broadening does not read may be
+ *                               NULL (Voigt: gamma_l; Doppler: gamma_l, y; Lorentz: gamma_d, y), one it reads may not.
+ *   mom_lineshape_tau_abs_dual  mom_voigt_tau_abs_dual likewise, with the partials of the five (NULL = zeros)
+ *   mom_absorption_get_gamma_l  gamma_l (compute_absorption_cross_section.jl:82-84) of the last device-prefactor call (last
+ *                               layer of a profile call) and, NULL to skip, its partials [n, 2] column-major of the last Dual
+ *                               call (test access). */
+int mom_absorption_set_model(mom_t *h, int broadening, int cef);
+/* line_shape!(A, grid, nu, gamma_d, gamma_l, y, S, broadening, CEF) (compute_absorption_cross_section.jl:167-183) of the handle's
+ * model, accumulated into tau_abs[:, iz] like mom_voigt_tau_abs (atmo_prof.jl:427-449) */
+int mom_lineshape_tau_abs(mom_t *h, int iz_1based, int nLines, const double *nu, const double *gamma_d, const double *gamma_l,
+                          const double *y, const double *S, const int *ind_start_1based, const int *ind_stop_1based, double factor);
+/* ... on ForwardDiff.Dual numbers (autodiff_helper.jl:17-51), like mom_voigt_tau_abs_dual */
+int mom_lineshape_tau_abs_dual(mom_t *h, int iz_1based, int nLines, const double *nu, const double *gamma_d, const double *gamma_l,
+                               const double *y, const double *S, const double *dnu, const double *dgamma_d, const double *dgamma_l,
+                               const double *dy, const double *dS, const int *ind_start_1based, const int *ind_stop_1based,
+                               double factor);
+/* gamma_l of compute_absorption_cross_section.jl:82-84 as the device formed it (test access) */
+int mom_absorption_get_gamma_l(mom_t *h, int n, double *gamma_l, double *dgamma_l);
 int mom_scene_set_optics(mom_t *h, int Nz, int nAer, int M, const double *tau_rayl, double varpi_rayl,
                          const double *tau_aer, const double *omega_aer, const double *ft_aer, const double *Zpp,
                          const double *Zmp, double albedo, int nVza, const int *node_1based, const double *cos_mphi,
@@ -560,7 +592,24 @@ int mom_voigt_xsec_dual(int device, int nLines, const double *nu, const double *
                         const int *ind_start_1based, const int *ind_stop_1based, int nGrid, const double *grid,
                         double *sigma, double *dsigma);
 
-/* GPU time (HIP events around the kernel, ms) of the last mom_voigt_xsec / mom_voigt_xsec_dual call of the calling thread. */
+/* line_shape!(A, grid, nu, gamma_d, gamma_l, y, S, broadening, CEF) (compute_absorption_cross_section.jl:167-183) summed over
+ * the lines in line order: mom_voigt_xsec for any absorption model (MOM_BROADENING_*, MOM_CEF_*; see mom_absorption_set_model).
+ * gamma_l = the Lorentz half width of :82-84.  An array the broadening does not read may be NULL; an unknown code: MOM_EINVAL.
+ * With (MOM_BROADENING_VOIGT, MOM_CEF_HW32SD) the result is bitwise that of mom_voigt_xsec. */
+int mom_lineshape_xsec(int device, int broadening, int cef, int nLines, const double *nu, const double *gamma_d,
+                       const double *gamma_l, const double *y, const double *S, const int *ind_start_1based,
+                       const int *ind_stop_1based, int nGrid, const double *grid, double *sigma);
+
+/* The Dual run of mom_lineshape_xsec (ForwardDiff.Dual numbers through line_shape!, autodiff_helper.jl:17-51): the partials of
+ * the five prefactors as for mom_voigt_xsec_dual, dsigma [nGrid, 2] column-major.  The branch |x| + y > 15 of
+ * w(::HumlicekWeidemann32VoigtErrorFunction, z) (complex_error_functions.jl:210-219) is taken on the values. */
+int mom_lineshape_xsec_dual(int device, int broadening, int cef, int nLines, const double *nu, const double *gamma_d,
+                            const double *gamma_l, const double *y, const double *S, const double *dnu,
+                            const double *dgamma_d, const double *dgamma_l, const double *dy, const double *dS,
+                            const int *ind_start_1based, const int *ind_stop_1based, int nGrid, const double *grid,
+                            double *sigma, double *dsigma);
+
+/* GPU time (HIP events around the kernel, ms) of the last mom_voigt_xsec / mom_lineshape_xsec call (or Dual run) of the calling thread. */
 double mom_voigt_last_kernel_ms(void);
 
 #ifdef __cplusplus

@@ -286,15 +286,28 @@ end
 # <<< multigpu
 
 # >>> absorption
+# HitranModel.broadening / HitranModel.CEF (src/Absorption/types.jl) -> the codes of mom_absorption_set_model.  Doppler and Lorentz
+# ignore the CEF, as line_shape! does (compute_absorption_cross_section.jl:167-177); every other error function (CPF12, Erfc*) is
+# outside the built scope and raises a MethodError here.
+momcore_broadening(::Voigt) = MomCore.MOM_BROADENING_VOIGT
+momcore_broadening(::Doppler) = MomCore.MOM_BROADENING_DOPPLER
+momcore_broadening(::Lorentz) = MomCore.MOM_BROADENING_LORENTZ
+momcore_cef(::HumlicekWeidemann32SDErrorFunction) = MomCore.MOM_CEF_HW32SD
+momcore_cef(::HumlicekWeidemann32VoigtErrorFunction) = MomCore.MOM_CEF_HW32VOIGT
+
 """
-compute_absorption_profile! (src/CoreRT/tools/atmo_prof.jl:427-449) for a HitranModel with Voigt broadening: one
+compute_absorption_profile! (src/CoreRT/tools/atmo_prof.jl:427-449) for a HitranModel (`broadening`, `CEF`: its fields; default Voigt with
+HumlicekWeidemann32SDErrorFunction, as parameters_from_yaml.jl:114-115): one
 resident line table per absorber, then all layers of the profile in two launches (the reference: a loop over layers
 with one kernel launch per line, compute_absorption_cross_section.jl:118-124).  `dual = true`: the same two launches on
 ForwardDiff.Dual numbers -- the partials of τ_abs with respect to each layer's pressure and temperature accumulate in the
 resident ∂τ_abs table (absorption_partials).
 """
-function compute_absorption_profile!(h::MomHandle, grid, hitran, tips, p_full, T, vmr, vcd_dry, wing_cutoff; dual::Bool = false)
+function compute_absorption_profile!(h::MomHandle, grid, hitran, tips, p_full, T, vmr, vcd_dry, wing_cutoff; dual::Bool = false,
+                                     broadening = Voigt(), CEF = HumlicekWeidemann32SDErrorFunction())
     Nz = length(p_full)
+    broadening isa Voigt || (CEF = HumlicekWeidemann32SDErrorFunction())      # ignored by Doppler and Lorentz
+    MomCore.mom_absorption_set_model!(h.ptr, momcore_broadening(broadening), momcore_cef(CEF))
     MomCore.mom_absorption_begin!(h.ptr, Nz, collect(Float64, grid))
     keep = (minimum(grid) - wing_cutoff) .< hitran.νᵢ .< (maximum(grid) + wing_cutoff)      # compute_absorption_cross_section.jl:54-72
     MomCore.mom_absorption_set_lines!(h.ptr, count(keep), hitran.νᵢ[keep], hitran.Sᵢ[keep], hitran.γ_air[keep], hitran.γ_self[keep],
@@ -334,6 +347,29 @@ function voigt_xsec_dual(arch::MI355X, ν, γ_d, y, S, dν, dγ_d, dy, dS, ind_s
     momcheck(MomCore.mom_voigt_xsec_dual(arch.device, length(ν), ν, γ_d, y, S, collect(Float64, dν), collect(Float64, dγ_d),
                                          collect(Float64, dy), collect(Float64, dS), Cint.(ind_start), Cint.(ind_stop), length(grid),
                                          collect(Float64, grid), result, derivs))
+    return result, derivs
+end
+
+"""
+line_shape!(A, grid, ν, γ_d, γ_l, y, S, broadening, CEF) (compute_absorption_cross_section.jl:167-183) summed over all lines in ONE
+call: voigt_xsec for any built absorption model.  An array the broadening does not read may be `C_NULL`.
+"""
+function lineshape_xsec(arch::MI355X, broadening, CEF, ν, γ_d, γ_l, y, S, ind_start, ind_stop, grid)
+    result = zeros(Float64, length(grid))
+    cef = broadening isa Voigt ? momcore_cef(CEF) : MomCore.MOM_CEF_HW32SD
+    momcheck(MomCore.mom_lineshape_xsec(arch.device, momcore_broadening(broadening), cef, length(ν), ν, γ_d, γ_l, y, S, Cint.(ind_start),
+                                        Cint.(ind_stop), length(grid), collect(Float64, grid), result))
+    return result
+end
+
+"""Its Dual run: (σ, J[nGrid, 2]); dν, dγ_d, dγ_l, dy, dS as for voigt_xsec_dual."""
+function lineshape_xsec_dual(arch::MI355X, broadening, CEF, ν, γ_d, γ_l, y, S, dν, dγ_d, dγ_l, dy, dS, ind_start, ind_stop, grid)
+    result = zeros(Float64, length(grid));  derivs = zeros(Float64, length(grid), 2)
+    cef = broadening isa Voigt ? momcore_cef(CEF) : MomCore.MOM_CEF_HW32SD
+    momcheck(MomCore.mom_lineshape_xsec_dual(arch.device, momcore_broadening(broadening), cef, length(ν), ν, γ_d, γ_l, y, S,
+                                             collect(Float64, dν), collect(Float64, dγ_d), collect(Float64, dγ_l), collect(Float64, dy),
+                                             collect(Float64, dS), Cint.(ind_start), Cint.(ind_stop), length(grid),
+                                             collect(Float64, grid), result, derivs))
     return result, derivs
 end
 # <<< absorption

@@ -42,6 +42,10 @@ MOM_OPT_STRIP2 = 12              # N = 52, 56, 60 on the two-buffer 4-wave image
 MOM_OPT_STRIP2_SCHED = 13        # its scheduling, a mask (1, default): 1 = shared unit queue, 2 = asymmetric chain priority (off: measured slower); 0 = neither
 MOM_OPT_ZERO_SKIP = 14           # leave out the exact-zero products of the zero-weight trailing streams, a mask (7, default): 1 = quad-block image (blocks), 2 = two-buffer strip image (k-steps), 4 = two-buffer strip image (blocks of four rows of a partly live row tile); 0 = every product
 
+# the absorption model (mom_absorption_set_model, mom_lineshape_xsec): HitranModel.broadening, HitranModel.CEF
+BROADENING_VOIGT, BROADENING_DOPPLER, BROADENING_LORENTZ = 0, 1, 2
+CEF_HW32SD, CEF_HW32VOIGT = 0, 1
+
 
 class MomError(RuntimeError):
     def __init__(self, code, msg):
@@ -98,6 +102,10 @@ SIGNATURES = {
     "mom_voigt_tau_abs_profile_dual": (C.c_int, [c_h, C.c_int, c_dp, c_dp, C.c_double, C.c_double, c_dp, c_dp]),
     "mom_absorption_get_partials": (C.c_int, [c_h, c_dp]),
     "mom_absorption_get_prefactor_partials": (C.c_int, [c_h, C.c_int, c_dp, c_dp, c_dp, c_dp]),
+    "mom_absorption_set_model": (C.c_int, [c_h, C.c_int, C.c_int]),
+    "mom_lineshape_tau_abs": (C.c_int, [c_h, C.c_int, C.c_int] + [c_dp] * 5 + [c_ip, c_ip, C.c_double]),
+    "mom_lineshape_tau_abs_dual": (C.c_int, [c_h, C.c_int, C.c_int] + [c_dp] * 10 + [c_ip, c_ip, C.c_double]),
+    "mom_absorption_get_gamma_l": (C.c_int, [c_h, C.c_int, c_dp, c_dp]),
     "mom_scene_set_optics": (C.c_int, [c_h, C.c_int, C.c_int, C.c_int, c_dp, C.c_double, c_dp, c_dp, c_dp, c_dp, c_dp,
                                        C.c_double, C.c_int, c_ip, c_dp, c_dp]),
     "mom_scene_get_layers": (C.c_int, [c_h, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp]),
@@ -127,6 +135,8 @@ SIGNATURES = {
     "mom_strip2_resumed": (C.c_int, [c_h, c_ip, c_ip]),
     "mom_voigt_xsec": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip, C.c_int, c_dp, c_dp]),
     "mom_voigt_xsec_dual": (C.c_int, [C.c_int, C.c_int] + [c_dp] * 8 + [c_ip, c_ip, C.c_int, c_dp, c_dp, c_dp]),
+    "mom_lineshape_xsec": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [c_dp] * 5 + [c_ip, c_ip, C.c_int, c_dp, c_dp]),
+    "mom_lineshape_xsec_dual": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [c_dp] * 10 + [c_ip, c_ip, C.c_int, c_dp, c_dp, c_dp]),
     "mom_voigt_last_kernel_ms": (C.c_double, []),
 }
 
@@ -458,6 +468,34 @@ class Handle:
                                                            dp(ms)))
         return float(ms[0])
 
+    # -- the absorption model (HitranModel.broadening x HitranModel.CEF) ------------------------------------
+    def absorption_set_model(self, broadening=BROADENING_VOIGT, cef=CEF_HW32SD):
+        """mom_absorption_set_model: the model of every later absorption call on the handle (codes BROADENING_*, CEF_*)."""
+        self.check(self.lib.mom_absorption_set_model(self._h, int(broadening), int(cef)))
+
+    def lineshape_tau_abs(self, iz_1based, nu, gamma_d, gamma_l, y, S, ind_start, ind_stop, factor):
+        """mom_lineshape_tau_abs: voigt_tau_abs for the handle's model; an array its broadening does not read may be None."""
+        a = [None if x is None else f64(x) for x in (nu, gamma_d, gamma_l, y, S)]
+        i0, i1 = i32(ind_start), i32(ind_stop)
+        self.check(self.lib.mom_lineshape_tau_abs(self._h, int(iz_1based), len(a[0]), *[None if x is None else dp(x) for x in a],
+                                                  ip(i0), ip(i1), float(factor)))
+
+    def lineshape_tau_abs_dual(self, iz_1based, nu, gamma_d, gamma_l, y, S, dnu, dgamma_d, dgamma_l, dy, dS, ind_start, ind_stop,
+                               factor):
+        """mom_lineshape_tau_abs_dual: the partials of the five prefactors as [nLines, 2] numpy or None (zeros)."""
+        a = [None if x is None else f64(x) for x in (nu, gamma_d, gamma_l, y, S)]
+        d = [_partials(x, len(a[0])) for x in (dnu, dgamma_d, dgamma_l, dy, dS)]
+        i0, i1 = i32(ind_start), i32(ind_stop)
+        self.check(self.lib.mom_lineshape_tau_abs_dual(self._h, int(iz_1based), len(a[0]), *[None if x is None else dp(x) for x in a],
+                                                       *[None if x is None else dp(x) for x in d], ip(i0), ip(i1), float(factor)))
+
+    def absorption_get_gamma_l(self, n=None, partials=False):
+        """gamma_l [n] of the last device-prefactor call; partials=True: (gamma_l, dgamma_l [n, 2]) of the last Dual call."""
+        n = self._nLines if n is None else int(n)
+        g, d = np.empty(n), (np.empty(2 * n) if partials else None)
+        self.check(self.lib.mom_absorption_get_gamma_l(self._h, n, dp(g), dp(d) if partials else None))
+        return (g, d.reshape(2, n).T.copy()) if partials else g
+
     def absorption_get_partials(self):
         """dtau_abs as numpy [2, S, Nz]: [0] with respect to the layer's pressure, [1] to its temperature."""
         out = np.empty(2 * self.S * self._absNz)
@@ -645,6 +683,35 @@ def voigt_xsec_dual(nu, gamma_d, y, S, dnu, dgamma_d, dy, dS, ind_start, ind_sto
     sigma, dsigma = np.empty(len(g)), np.empty(2 * len(g))
     rc = lib.mom_voigt_xsec_dual(device, len(a[0]), *[dp(x) for x in a], *[None if x is None else dp(x) for x in d], ip(i0), ip(i1),
                                  len(g), dp(g), dp(sigma), dp(dsigma))
+    if rc != MOM_OK:
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return sigma, dsigma.reshape(2, len(g)).T.copy()
+
+
+def lineshape_xsec(broadening, cef, nu, gamma_d, gamma_l, y, S, ind_start, ind_stop, grid, device: int = 0):
+    """mom_lineshape_xsec: voigt_xsec for any absorption model (codes BROADENING_*, CEF_*); an array the broadening does not
+    read may be None."""
+    lib = load()
+    a = [None if x is None else f64(x) for x in (nu, gamma_d, gamma_l, y, S)]
+    i0, i1, g = i32(ind_start), i32(ind_stop), f64(grid)
+    sigma = np.empty(len(g))
+    rc = lib.mom_lineshape_xsec(device, int(broadening), int(cef), len(a[0]), *[None if x is None else dp(x) for x in a], ip(i0),
+                                ip(i1), len(g), dp(g), dp(sigma))
+    if rc != MOM_OK:
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return sigma
+
+
+def lineshape_xsec_dual(broadening, cef, nu, gamma_d, gamma_l, y, S, dnu, dgamma_d, dgamma_l, dy, dS, ind_start, ind_stop, grid,
+                        device: int = 0):
+    """mom_lineshape_xsec_dual: sigma [nGrid] and dsigma [nGrid, 2]; the partials [nLines, 2] numpy or None (zeros)."""
+    lib = load()
+    a = [None if x is None else f64(x) for x in (nu, gamma_d, gamma_l, y, S)]
+    d = [_partials(x, len(a[0])) for x in (dnu, dgamma_d, dgamma_l, dy, dS)]
+    i0, i1, g = i32(ind_start), i32(ind_stop), f64(grid)
+    sigma, dsigma = np.empty(len(g)), np.empty(2 * len(g))
+    rc = lib.mom_lineshape_xsec_dual(device, int(broadening), int(cef), len(a[0]), *[None if x is None else dp(x) for x in a],
+                                     *[None if x is None else dp(x) for x in d], ip(i0), ip(i1), len(g), dp(g), dp(sigma), dp(dsigma))
     if rc != MOM_OK:
         raise MomError(rc, lib.mom_last_global_error().decode())
     return sigma, dsigma.reshape(2, len(g)).T.copy()

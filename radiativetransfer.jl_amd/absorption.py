@@ -1,9 +1,10 @@
-"""Host side of the Voigt line-by-line path (src/Absorption of the reference).
+"""Host side of the line-by-line absorption path (src/Absorption of the reference).
 
 The per-line prefactors are cheap O(nLines) host work and stay on the host exactly as in
 compute_absorption_cross_section.jl:73-107; the O(nLines x window) line-shape sum -- the
 reference's one-kernel-launch-per-line hot loop (:118-124) -- runs as ONE launch in
-libmomcore.so (csrc/voigt.hip).
+libmomcore.so (csrc/voigt.hip).  The absorption model -- HitranModel.broadening x HitranModel.CEF -- is selected by
+`broadening=` and `cef=` (absorption_model below); the default is Voigt with HumlicekWeidemann32SDErrorFunction.
 """
 from __future__ import annotations
 
@@ -23,6 +24,27 @@ cc_ = 2.99792458e8
 cBolts_ = 1.3806503e-23
 p_ref = 1013.25
 t_ref = 296.0
+
+# HitranModel.broadening / HitranModel.CEF as the YAML reader spells them (parameters_from_yaml.jl:114-115), with or without the
+# parentheses -> the library's codes.  Doppler and Lorentz ignore the CEF, as the reference's line_shape! methods do.
+BROADENINGS = {"Voigt": _lib.BROADENING_VOIGT, "Doppler": _lib.BROADENING_DOPPLER, "Lorentz": _lib.BROADENING_LORENTZ}
+CEFS = {"HumlicekWeidemann32SDErrorFunction": _lib.CEF_HW32SD, "HumlicekWeidemann32VoigtErrorFunction": _lib.CEF_HW32VOIGT}
+
+
+def _model_code(name, table, what):
+    key = name[:-2] if isinstance(name, str) and name.endswith("()") else name
+    if not isinstance(key, str) or key not in table:
+        raise ValueError(f"unsupported {what} {name!r}: supported are " + ", ".join(f"{k}()" for k in table))
+    return table[key]
+
+
+def absorption_model(broadening="Voigt()", cef="HumlicekWeidemann32SDErrorFunction()"):
+    """(broadening code, CEF code) of the reference's names; any other name (CPF12ErrorFunction and the Erfc* error functions
+    included, which are not built) raises ValueError naming what is supported."""
+    return _model_code(broadening, BROADENINGS, "broadening"), _model_code(cef, CEFS, "CEF")
+
+
+_DEFAULT_MODEL = (_lib.BROADENING_VOIGT, _lib.CEF_HW32SD)
 
 
 @dataclass
@@ -211,6 +233,7 @@ class LinePrefactors:
     S: np.ndarray
     ind_start: np.ndarray  # 1-based inclusive
     ind_stop: np.ndarray
+    γ_l: Optional[np.ndarray] = None   # the Lorentz half width line_shape! takes next to y (:82-84)
 
 
 def line_prefactors(h: HitranTable, grid: np.ndarray, pressure: float, temperature: float, vmr: float = 0.0,
@@ -265,16 +288,17 @@ def line_prefactors(h: HitranTable, grid: np.ndarray, pressure: float, temperatu
     else:
         i0 = np.ones(ν.size, dtype=np.int32)
         i1 = np.ones(ν.size, dtype=np.int32)
-    return LinePrefactors(ν, γ_d, y, S, i0, i1)
+    return LinePrefactors(ν, γ_d, y, S, i0, i1, γ_l)
 
 
 def line_prefactors_dual(h: HitranTable, grid: np.ndarray, pressure: float, temperature: float, vmr: float = 0.0,
-                         wing_cutoff: float = 40.0, qratio=None, mol_weights: Optional[dict] = None):
+                         wing_cutoff: float = 40.0, qratio=None, mol_weights: Optional[dict] = None, with_γ_l: bool = False):
     """line_prefactors on ForwardDiff.Dual numbers with x = [p, T] (autodiff_helper.jl:17-51 through
     compute_absorption_cross_section.jl:79-101): returns the LinePrefactors (the values, as line_prefactors forms them) and
     dν, dγ_d, dy, dS, each [n, 2] with column 0 = d/dp and column 1 = d/dT -- the derivative of every statement as written,
     by the rule ForwardDiff applies to it.  Line selection, windows and the E″ != -1 test are taken on the values.  A
-    `qratio` override has no known derivative and raises ValueError."""
+    `qratio` override has no known derivative and raises ValueError.  with_γ_l=True appends dγ_l [n, 2] as a sixth value (the
+    partials of LinePrefactors.γ_l, which the Lorentz shape reads)."""
     if qratio is not None:
         raise ValueError("line_prefactors_dual: the derivative of a qratio override is unknown; the Dual run uses the reference's qoft!")
     pf = line_prefactors(h, grid, pressure, temperature, vmr, wing_cutoff, None, mol_weights)
@@ -315,6 +339,8 @@ def line_prefactors_dual(h: HitranTable, grid: np.ndarray, pressure: float, temp
         r1, dr1 = rate * e1, drate * e1 + rate * de1
         dS_T[sel] = S0[sel] * ((dr1 * e2 + r1 * de2) / e3)
     dS = np.stack([z, dS_T], axis=1)
+    if with_γ_l:
+        return pf, dν, dγd, dy, dS, np.stack([dγl_p, dγl_T], axis=1)
     return pf, dν, dγd, dy, dS
 
 
@@ -329,12 +355,19 @@ def _sqrt_weights(h: HitranTable, keep, mol_weights: Optional[dict] = None) -> n
 
 
 def absorption_cross_section(h: HitranTable, grid, pressure: float, temperature: float, autodiff: bool = False, vmr: float = 0.0,
-                             wing_cutoff: float = 40.0, device: int = 0):
+                             wing_cutoff: float = 40.0, device: int = 0, broadening="Voigt()",
+                             cef="HumlicekWeidemann32SDErrorFunction()"):
     """absorption_cross_section(model, grid, p, T; autodiff) (autodiff_helper.jl:17-51): σ[nGrid], or with autodiff=True
     (σ, J[nGrid, 2]) -- the Jacobian with respect to x = [p, T] that ForwardDiff.jacobian! returns as result.derivs[1],
-    from the Dual run of the Voigt kernel (mom_voigt_xsec_dual)."""
+    from the Dual run of the line-shape kernel (mom_voigt_xsec_dual; mom_lineshape_xsec_dual for another absorption model)."""
+    model = absorption_model(broadening, cef)
     if not autodiff:
-        return compute_absorption_cross_section(h, grid, pressure, temperature, vmr, wing_cutoff, device=device)
+        return compute_absorption_cross_section(h, grid, pressure, temperature, vmr, wing_cutoff, device=device, broadening=broadening,
+                                                cef=cef)
+    if model != _DEFAULT_MODEL:
+        pf, dν, dγd, dy, dS, dγl = line_prefactors_dual(h, grid, pressure, temperature, vmr, wing_cutoff, with_γ_l=True)
+        return _lib.lineshape_xsec_dual(*model, pf.ν, pf.γ_d, pf.γ_l, pf.y, pf.S, dν, dγd, dγl, dy, dS, pf.ind_start, pf.ind_stop,
+                                        np.asarray(grid, dtype=np.float64), device=device)
     pf, dν, dγd, dy, dS = line_prefactors_dual(h, grid, pressure, temperature, vmr, wing_cutoff)
     return _lib.voigt_xsec_dual(pf.ν, pf.γ_d, pf.y, pf.S, dν, dγd, dy, dS, pf.ind_start, pf.ind_stop,
                                 np.asarray(grid, dtype=np.float64), device=device)
@@ -351,11 +384,16 @@ def optics_partials(tau, varpi, dtau_abs_k):
 
 
 def compute_absorption_cross_section(h: HitranTable, grid, pressure: float, temperature: float, vmr: float = 0.0,
-                                     wing_cutoff: float = 40.0, qratio=None, device: int = 0) -> np.ndarray:
-    """compute_absorption_cross_section(model::HitranModel, grid, p, T) with Voigt broadening and
-    the HumlicekWeidemann32SD error function (the validated default, parameters_from_yaml.jl:115).
-    Returns σ[nGrid] in cm²/molecule, computed on the GPU."""
+                                     wing_cutoff: float = 40.0, qratio=None, device: int = 0, broadening="Voigt()",
+                                     cef="HumlicekWeidemann32SDErrorFunction()") -> np.ndarray:
+    """compute_absorption_cross_section(model::HitranModel, grid, p, T); by default with Voigt broadening and
+    the HumlicekWeidemann32SD error function (the validated default, parameters_from_yaml.jl:115), with `broadening` / `cef`
+    (absorption_model) any built method of line_shape! (:167-183).  Returns σ[nGrid] in cm²/molecule, computed on the GPU."""
+    model = absorption_model(broadening, cef)
     pf = line_prefactors(h, grid, pressure, temperature, vmr, wing_cutoff, qratio)
+    if model != _DEFAULT_MODEL:
+        return _lib.lineshape_xsec(*model, pf.ν, pf.γ_d, pf.γ_l, pf.y, pf.S, pf.ind_start, pf.ind_stop,
+                                   np.asarray(grid, dtype=np.float64), device=device)
     return _lib.voigt_xsec(pf.ν, pf.γ_d, pf.y, pf.S, pf.ind_start, pf.ind_stop, np.asarray(grid, dtype=np.float64),
                            device=device)
 
@@ -390,7 +428,8 @@ def resident_line_table(h, table: HitranTable, grid, wing_cutoff: float = 40.0):
 
 def compute_absorption_profile(h, table: HitranTable, grid, p_full, T, vcd_dry, vmr, wing_cutoff: float = 40.0,
                                model_vmr: float = 0.0, qratio=None, begin: bool = True, device_prefactors: bool = False,
-                               layer_by_layer: bool = False, dual: bool = False):
+                               layer_by_layer: bool = False, dual: bool = False, broadening="Voigt()",
+                               cef="HumlicekWeidemann32SDErrorFunction()"):
     """compute_absorption_profile!(τ_abs, absorption_model, grid, vmr, profile) (atmo_prof.jl:427-449) on the handle's
     resident τ_abs table: per layer the host builds the line prefactors (O(nLines)), the GPU adds
     σ(ν; p[iz], T[iz]) * vcd_dry[iz] * vmr[iz] into τ_abs[:, iz] (mom_voigt_tau_abs).  `vmr` scalar or per layer (the
@@ -400,7 +439,12 @@ def compute_absorption_profile(h, table: HitranTable, grid, p_full, T, vcd_dry, 
     two launches (mom_voigt_tau_abs_profile; returns their GPU time in ms); layer_by_layer=True keeps one
     mom_voigt_tau_abs_layer call per layer (same arithmetic, bitwise).  dual=True takes the Dual entry points on either route
     (mom_voigt_tau_abs_dual fed by line_prefactors_dual, or mom_voigt_tau_abs_profile_dual): the partials of τ_abs with
-    respect to each layer's pressure and temperature accumulate in the handle's dtau_abs table (absorption_get_partials)."""
+    respect to each layer's pressure and temperature accumulate in the handle's dtau_abs table (absorption_get_partials).
+    `broadening` / `cef` (absorption_model) become the handle's absorption model (mom_absorption_set_model), which the
+    device-prefactor entry points follow; on the host route another model than the default goes through
+    mom_lineshape_tau_abs(_dual), which takes γ_l."""
+    model = absorption_model(broadening, cef)
+    h.absorption_set_model(*model)
     p_full, T, vcd_dry = (np.asarray(x, dtype=np.float64) for x in (p_full, T, vcd_dry))
     Nz = p_full.size
     assert T.size == Nz and vcd_dry.size == Nz
@@ -422,6 +466,16 @@ def compute_absorption_profile(h, table: HitranTable, grid, p_full, T, vcd_dry, 
             return None
         return h.voigt_tau_abs_profile(p_full, T, model_vmr, wing_cutoff, vcd_dry * vmr_arr)   # all layers in two launches
     for iz in range(Nz):
+        if model != _DEFAULT_MODEL:
+            f = vcd_dry[iz] * vmr_arr[iz]
+            if dual:
+                pf, dν, dγd, dy, dS, dγl = line_prefactors_dual(table, grid, p_full[iz], T[iz], vmr=model_vmr, wing_cutoff=wing_cutoff,
+                                                                qratio=qratio, with_γ_l=True)
+                h.lineshape_tau_abs_dual(iz + 1, pf.ν, pf.γ_d, pf.γ_l, pf.y, pf.S, dν, dγd, dγl, dy, dS, pf.ind_start, pf.ind_stop, f)
+            else:
+                pf = line_prefactors(table, grid, p_full[iz], T[iz], vmr=model_vmr, wing_cutoff=wing_cutoff, qratio=qratio)
+                h.lineshape_tau_abs(iz + 1, pf.ν, pf.γ_d, pf.γ_l, pf.y, pf.S, pf.ind_start, pf.ind_stop, f)
+            continue
         if dual:
             pf, dν, dγd, dy, dS = line_prefactors_dual(table, grid, p_full[iz], T[iz], vmr=model_vmr, wing_cutoff=wing_cutoff,
                                                        qratio=qratio)

@@ -47,10 +47,12 @@ struct mom_handle : MomSceneBufs<double> {
   int abs_Nz = 0;
   size_t lines_per = 0;   // lines ONE layer's block of d_lines has room for (the stride of its arrays, not the size of the allocation)
   int lines_nz = 1;       // layers held in d_lines: arrays [nu | gamma_d | y | S][lines_nz][lines_per], then the two window arrays as ints
+                          // (one slot of doubles), then gamma_l [lines_nz][lines_per]
+  int abs_broadening = 0, abs_cef = 0;  // mom_absorption_set_model: MOM_BROADENING_*, MOM_CEF_* of the absorption calls (Voigt / HW32SD)
   MomDevBuf<double> d_prof;  // per-layer scalars of mom_voigt_tau_abs_profile
   // Dual run of the absorption path (mom_voigt_tau_abs_dual / _profile_dual): partials with respect to (p, T) of every layer
   MomDevBuf<double> d_dtau_abs;  // [S, abs_Nz, 2]; exists from the first Dual call after mom_absorption_begin
-  MomDevBuf<double> d_dlines;    // partials of d_lines' prefactors: [nu | gamma_d | y | S][2][lines_nz][lines_per]
+  MomDevBuf<double> d_dlines;    // partials of d_lines' prefactors: [nu | gamma_d | y | S | gamma_l][2][lines_nz][lines_per]
   MomDevBuf<double> d_vec[4];  // S-length temporaries (tau_sum, dtau, varpi, expk)
   MomDevBuf<double> d_Zop[2];
   // scene

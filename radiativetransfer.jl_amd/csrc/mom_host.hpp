@@ -9,6 +9,8 @@
 #include <utility>
 #include <vector>
 
+#include "momcore.h"
+
 // The one owner of a device allocation of the handles (mom_handle, momf_scene): pointer + capacity in elements of T, freed by
 // the destructor.  A member that is not a MomDevBuf (an alias into one, a pointer borrowed from another handle) is never freed.
 // After a failed call the buffer is empty, so an error return between two allocations leaves each buffer valid or empty.
@@ -215,17 +217,32 @@ inline hipError_t mom_launch_ldsm(void (*k_lds)(Args), void (*k_gen)(Args), bool
 // text for mom_last_global_error() (the thread's library-level error string, momcore.hip)
 void mom_set_global_error(const char *msg);
 
+// The absorption model as the line-shape kernels' shape (voigt.hip LineShape): 0 Voigt / HW32SD, 1 Voigt / HW32Voigt, 2 Doppler,
+// 3 Lorentz -- the CEF is ignored by Doppler and Lorentz, as line_shape! ignores it (compute_absorption_cross_section.jl:167-177).
+// An unknown code: -1 and, in *err, a text that starts with `fn` and holds the code
+inline int mom_line_shape(const char *fn, int broadening, int cef, std::string *err) {
+  const bool bad_b = broadening < MOM_BROADENING_VOIGT || broadening > MOM_BROADENING_LORENTZ;
+  if (bad_b || cef < MOM_CEF_HW32SD || cef > MOM_CEF_HW32VOIGT) {
+    *err = std::string(fn) + (bad_b ? ": unknown broadening code " + std::to_string(broadening) + " (0 Voigt, 1 Doppler, 2 Lorentz)"
+                                    : ": unknown CEF code " + std::to_string(cef) + " (0 HW32SD, 1 HW32Voigt)");
+    return -1;
+  }
+  return broadening == MOM_BROADENING_VOIGT ? cef : broadening + 1;
+}
+// does the shape read prefactor k of (nu, gamma_d, y, S, gamma_l)?  The others may be null at the C ABI
+inline bool mom_shape_reads(int shape, int k) { return k == 0 || k == 3 || (k == 1 ? shape != 3 : k == 2 ? shape <= 1 : shape == 3); }
+
 // voigt.hip: one launch for all lines (device pointers, stream st); out[g] = acc  or  out[g] += factor * acc
-hipError_t mom_voigt_launch(hipStream_t st, int nLines, const double *nu, const double *gamma_d, const double *y,
-                            const double *S, const int *i0, const int *i1, int nGrid, const double *grid, double *out,
+hipError_t mom_voigt_launch(hipStream_t st, int shape, int nLines, const double *nu, const double *gamma_d, const double *gamma_l,
+                            const double *y, const double *S, const int *i0, const int *i1, int nGrid, const double *grid, double *out,
                             double factor, int accumulate, int sorted);
 
 // its Dual run: the partials of the prefactors (k = 0 pressure, 1 temperature; partial k of line j at p[j + ks k], null = zeros)
 // and dout[g + os k] = d_k acc  or  += factor * d_k acc
-hipError_t mom_voigt_dual_launch(hipStream_t st, int nLines, const double *nu, const double *gamma_d, const double *y,
-                                 const double *S, const int *i0, const int *i1, int nGrid, const double *grid, double *out,
-                                 double factor, int accumulate, int sorted, const double *dnu, const double *dgd, const double *dy,
-                                 const double *dS, size_t ks, double *dout, size_t os);
+hipError_t mom_voigt_dual_launch(hipStream_t st, int shape, int nLines, const double *nu, const double *gamma_d, const double *gamma_l,
+                                 const double *y, const double *S, const int *i0, const int *i1, int nGrid, const double *grid,
+                                 double *out, double factor, int accumulate, int sorted, const double *dnu, const double *dgd,
+                                 const double *dgl, const double *dy, const double *dS, size_t ks, double *dout, size_t os);
 
 // resident HITRAN table of one absorber + the TIPS spline tables of its isotopologues (device pointers)
 struct MomLineTable {
@@ -236,16 +253,17 @@ struct MomLineTable {
   const double *tT, *tQ, *tZ;                                         // [nIso, nTmax] knots, values, second derivatives
 };
 // voigt.hip: per-line prefactors of one (p, T) on the device; *unsorted is set when the windows are not monotone
-// every layer of a profile: prefactors of all (layer, line) pairs, then the line shapes of all (layer, grid point) pairs
-hipError_t mom_voigt_profile_launch(hipStream_t st, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
+// every layer of a profile: prefactors of all (layer, line) pairs, then the line shapes of all (layer, grid point) pairs;
+// pf = [nu | gamma_d | y | S | the two window arrays as ints | gamma_l][Nz][cap]
+hipError_t mom_voigt_profile_launch(hipStream_t st, int shape, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
                                     const double *prm, double vmr, double wing, double *pf, int *win, int *unsorted, double *tau_abs,
                                     const double *factor);
 hipError_t mom_line_prefactors_launch(hipStream_t st, const MomLineTable &tb, int nGrid, const double *grid, double p, double T,
-                                      double vmr, double wing, double cgd, double *nu, double *gd, double *y, double *S, int *i0,
-                                      int *i1, int *unsorted);
+                                      double vmr, double wing, double cgd, double *nu, double *gd, double *y, double *S, double *gl,
+                                      int *i0, int *i1, int *unsorted);
 // the Dual run of mom_voigt_profile_launch: prm = [p | T | cgd | factor | d cgd / dT][Nz], the prefactors' partials at
-// dpf[nu | gamma_d | y | S][k][Nz][cap], dtau_abs [nGrid, Nz, 2]
-hipError_t mom_voigt_profile_dual_launch(hipStream_t st, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
+// dpf[nu | gamma_d | y | S | gamma_l][k][Nz][cap], dtau_abs [nGrid, Nz, 2]
+hipError_t mom_voigt_profile_dual_launch(hipStream_t st, int shape, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
                                          const double *prm, double vmr, double wing, double *pf, double *dpf, int *win, int *unsorted,
                                          double *tau_abs, double *dtau_abs, const double *factor);
 

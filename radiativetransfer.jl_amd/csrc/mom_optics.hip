@@ -1,5 +1,7 @@
 // mom_optics.hip -- the device-side layer optics of the C ABI (include/momcore.h): the resident absorption table
 // and the Voigt entry points (kernels: voigt.hip), k_optics and mom_scene_set_optics, mom_scene_get_layers.
+#include <cstring>
+
 #include "mom_handle.hpp"
 
 extern "C" int mom_absorption_begin(mom_t *h, int Nz, const double *grid) {
@@ -41,45 +43,115 @@ extern "C" int mom_absorption_get(mom_t *h, double *tau_abs) {
   return MOM_OK;
 }
 
-extern "C" int mom_voigt_tau_abs(mom_t *h, int iz_1based, int nLines, const double *nu, const double *gamma_d, const double *y,
-                                 const double *S, const int *ind_start_1based, const int *ind_stop_1based, double factor) {
+// HitranModel.broadening / .CEF of every later absorption call on the handle (Absorption/types.jl; parameters_from_yaml.jl:114-115)
+extern "C" int mom_absorption_set_model(mom_t *h, int broadening, int cef) {
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
-  if (!h->d_tau_abs || !h->d_grid) return fail(h, MOM_ESTATE, "mom_voigt_tau_abs: call mom_absorption_begin with the spectral grid first");
-  if (iz_1based < 1 || iz_1based > h->abs_Nz || nLines < 0 ||
-      (nLines > 0 && (!nu || !gamma_d || !y || !S || !ind_start_1based || !ind_stop_1based)))
-    return fail(h, MOM_EINVAL, "mom_voigt_tau_abs: bad argument");
+  std::string err;
+  if (mom_line_shape("mom_absorption_set_model", broadening, cef, &err) < 0) return fail(h, MOM_EINVAL, err.c_str());
+  h->abs_broadening = broadening;
+  h->abs_cef = cef;
+  return MOM_OK;
+}
+
+namespace {
+// the kernels' shape of the handle's model (cannot fail: mom_absorption_set_model checked the codes)
+int handle_shape(const mom_t *h) {
+  std::string err;
+  return mom_line_shape("", h->abs_broadening, h->abs_cef, &err);
+}
+// mom_voigt_tau_abs / _dual take no gamma_l: Voigt with the handle's CEF, MOM_ESTATE under another broadening
+int voigt_only(mom_t *h, const char *fn) {
+  if (h->abs_broadening == MOM_BROADENING_VOIGT) return MOM_OK;
+  char buf[200];
+  snprintf(buf, sizeof buf, "%s: the handle's broadening (mom_absorption_set_model) is not Voigt; call mom_lineshape_tau_abs%s, which takes gamma_l",
+           fn, strstr(fn, "_dual") ? "_dual" : "");
+  return fail(h, MOM_ESTATE, buf);
+}
+// the checks the host-prefactor entry points share; line[] = nu, gamma_d, y, S, gamma_l
+int lineshape_args(mom_t *h, const char *fn, int shape, int iz_1based, int nLines, const double *const *line, const int *ind_start_1based,
+                   const int *ind_stop_1based) {
+  char buf[200];
+  if (!h->d_tau_abs || !h->d_grid) {
+    snprintf(buf, sizeof buf, "%s: call mom_absorption_begin with the spectral grid first", fn);
+    return fail(h, MOM_ESTATE, buf);
+  }
+  bool lines_ok = ind_start_1based && ind_stop_1based;
+  for (int k = 0; k < 5; ++k) lines_ok = lines_ok && (line[k] || !mom_shape_reads(shape, k));
+  if (iz_1based < 1 || iz_1based > h->abs_Nz || nLines < 0 || (nLines > 0 && !lines_ok)) {
+    snprintf(buf, sizeof buf, "%s: bad argument", fn);
+    return fail(h, MOM_EINVAL, buf);
+  }
   for (int j = 0; j < nLines; ++j)
     if (ind_start_1based[j] < 1 || ind_stop_1based[j] > h->S) {
-      char buf[160];
-      snprintf(buf, sizeof buf, "mom_voigt_tau_abs: line %d: window [%d, %d] outside the grid 1..%d", j + 1, ind_start_1based[j],
-               ind_stop_1based[j], h->S);
+      snprintf(buf, sizeof buf, "%s: line %d: window [%d, %d] outside the grid 1..%d", fn, j + 1, ind_start_1based[j], ind_stop_1based[j],
+               h->S);
       return fail(h, MOM_EINVAL, buf);
     }
-  if (nLines == 0) return MOM_OK;
-  int sorted = 1;
+  return MOM_OK;
+}
+bool windows_sorted(int nLines, const int *i0, const int *i1) {
   for (int j = 1; j < nLines; ++j)
-    if (ind_start_1based[j] < ind_start_1based[j - 1] || ind_stop_1based[j] < ind_stop_1based[j - 1]) { sorted = 0; break; }
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t lb = (size_t)nLines;
-  if (lb > h->lines_per || h->lines_nz != 1) {  // 4 double + 2 int arrays per line, grown geometrically: no allocation in steady state
+    if (i0[j] < i0[j - 1] || i1[j] < i1[j - 1]) return false;
+  return true;
+}
+// d_lines of one layer: [nu | gamma_d | y | S | the two window arrays as ints | gamma_l][cap], grown geometrically: no allocation in
+// steady state
+int value_lines(mom_t *h, size_t lb) {
+  if (lb > h->lines_per || h->lines_nz != 1) {
     h->lines_nz = 1;
     if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
     const size_t cap = std::max<size_t>(lb, 1024) * 2;
-    HIPCHK(h, h->d_lines.renew(5 * cap));
+    HIPCHK(h, h->d_lines.renew(6 * cap));
     h->lines_per = cap;
   }
+  return MOM_OK;
+}
+const int kLineSlot[5] = {0, 1, 2, 3, 5};  // where nu, gamma_d, y, S, gamma_l sit in d_lines (slot 4: the windows)
+
+// mom_voigt_tau_abs and mom_lineshape_tau_abs
+int lineshape_tau_abs_run(mom_t *h, const char *fn, int shape, int iz_1based, int nLines, const double *const *line,
+                          const int *ind_start_1based, const int *ind_stop_1based, double factor) {
+  int rc = lineshape_args(h, fn, shape, iz_1based, nLines, line, ind_start_1based, ind_stop_1based);
+  if (rc) return rc;
+  if (nLines == 0) return MOM_OK;
+  const int sorted = windows_sorted(nLines, ind_start_1based, ind_stop_1based) ? 1 : 0;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t lb = (size_t)nLines;
+  rc = value_lines(h, lb);
+  if (rc) return rc;
   const size_t cap = h->lines_per;
   double *dl = h->d_lines;
   int *dw = reinterpret_cast<int *>(dl + 4 * cap);
-  const double *src[4] = {nu, gamma_d, y, S};
   // the host arrays are borrowed for the call only: the copies must have left them before we return
-  for (int k = 0; k < 4; ++k) HIPCHK(h, hipMemcpyAsync(dl + k * cap, src[k], lb * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  for (int k = 0; k < 5; ++k)
+    if (line[k] && mom_shape_reads(shape, k))
+      HIPCHK(h, hipMemcpyAsync(dl + kLineSlot[k] * cap, line[k], lb * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(dw, ind_start_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(dw + cap, ind_stop_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, mom_voigt_launch(h->stream, nLines, dl, dl + cap, dl + 2 * cap, dl + 3 * cap, dw, dw + cap, h->S, h->d_grid,
+  HIPCHK(h, mom_voigt_launch(h->stream, shape, nLines, dl, dl + cap, dl + 5 * cap, dl + 2 * cap, dl + 3 * cap, dw, dw + cap, h->S, h->d_grid,
                              h->d_tau_abs + (size_t)h->S * (iz_1based - 1), factor, 1, sorted));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MOM_OK;
+}
+}  // namespace
+
+extern "C" int mom_voigt_tau_abs(mom_t *h, int iz_1based, int nLines, const double *nu, const double *gamma_d, const double *y,
+                                 const double *S, const int *ind_start_1based, const int *ind_stop_1based, double factor) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  const int rc = voigt_only(h, "mom_voigt_tau_abs");
+  if (rc) return rc;
+  const double *line[5] = {nu, gamma_d, y, S, nullptr};
+  return lineshape_tau_abs_run(h, "mom_voigt_tau_abs", handle_shape(h), iz_1based, nLines, line, ind_start_1based, ind_stop_1based, factor);
+}
+
+// mom_voigt_tau_abs for the handle's model: the five prefactors line_shape! takes (compute_absorption_cross_section.jl:118-124)
+extern "C" int mom_lineshape_tau_abs(mom_t *h, int iz_1based, int nLines, const double *nu, const double *gamma_d, const double *gamma_l,
+                                     const double *y, const double *S, const int *ind_start_1based, const int *ind_stop_1based,
+                                     double factor) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  const double *line[5] = {nu, gamma_d, y, S, gamma_l};
+  return lineshape_tau_abs_run(h, "mom_lineshape_tau_abs", handle_shape(h), iz_1based, nLines, line, ind_start_1based, ind_stop_1based,
+                               factor);
 }
 
 // ---- The Dual run of the absorption path: tau_abs and its partials with respect to the layer's pressure (k = 0) and temperature
@@ -99,11 +171,51 @@ int dual_lines(mom_t *h, size_t lb, int nz) {
   const size_t per = std::max<size_t>(lb, 1024) * 2;
   if (lb > h->lines_per || h->lines_nz != nz || !h->d_lines) {
     if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
-    HIPCHK(h, h->d_lines.renew(5 * per * (size_t)nz));
+    HIPCHK(h, h->d_lines.renew(6 * per * (size_t)nz));
     h->lines_per = per;
     h->lines_nz = nz;
   }
-  HIPCHK(h, h->d_dlines.reserve(8 * h->lines_per * (size_t)nz, h->stream));
+  HIPCHK(h, h->d_dlines.reserve(10 * h->lines_per * (size_t)nz, h->stream));
+  return MOM_OK;
+}
+}  // namespace
+
+namespace {
+// mom_voigt_tau_abs_dual and mom_lineshape_tau_abs_dual; dline[] = the partials of line[], each [nLines, 2] column-major or null
+int lineshape_tau_abs_dual_run(mom_t *h, const char *fn, int shape, int iz_1based, int nLines, const double *const *line,
+                               const double *const *dline, const int *ind_start_1based, const int *ind_stop_1based, double factor) {
+  int rc = lineshape_args(h, fn, shape, iz_1based, nLines, line, ind_start_1based, ind_stop_1based);
+  if (rc) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  rc = dual_table(h);
+  if (rc) return rc;
+  if (nLines == 0) return MOM_OK;
+  const int sorted = windows_sorted(nLines, ind_start_1based, ind_stop_1based) ? 1 : 0;
+  const size_t lb = (size_t)nLines;
+  rc = dual_lines(h, lb, 1);
+  if (rc) return rc;
+  const size_t cap = h->lines_per;
+  double *dl = h->d_lines, *dd = h->d_dlines;
+  int *dw = reinterpret_cast<int *>(dl + 4 * cap);
+  const double *dev[5];
+  // the host arrays are borrowed for the call only: the copies must have left them before we return
+  for (int k = 0; k < 5; ++k)
+    if (line[k] && mom_shape_reads(shape, k))
+      HIPCHK(h, hipMemcpyAsync(dl + kLineSlot[k] * cap, line[k], lb * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  for (int q = 0; q < 5; ++q) {  // host [nLines, 2] column-major -> [q][k][cap]; a null array: zeros
+    dev[q] = dd + 2 * q * cap;
+    for (int k = 0; k < 2; ++k) {
+      if (dline[q]) HIPCHK(h, hipMemcpyAsync(dd + (2 * q + k) * cap, dline[q] + lb * k, lb * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      else HIPCHK(h, hipMemsetAsync(dd + (2 * q + k) * cap, 0, lb * sizeof(double), h->stream));
+    }
+  }
+  HIPCHK(h, hipMemcpyAsync(dw, ind_start_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(dw + cap, ind_stop_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  const size_t col = (size_t)h->S * (iz_1based - 1);
+  HIPCHK(h, mom_voigt_dual_launch(h->stream, shape, nLines, dl, dl + cap, dl + 5 * cap, dl + 2 * cap, dl + 3 * cap, dw, dw + cap, h->S,
+                                  h->d_grid, h->d_tau_abs + col, factor, 1, sorted, dev[0], dev[1], dev[4], dev[2], dev[3], cap,
+                                  h->d_dtau_abs + col, (size_t)h->S * h->abs_Nz));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return MOM_OK;
 }
 }  // namespace
@@ -112,49 +224,22 @@ extern "C" int mom_voigt_tau_abs_dual(mom_t *h, int iz_1based, int nLines, const
                                       const double *S, const double *dnu, const double *dgamma_d, const double *dy, const double *dS,
                                       const int *ind_start_1based, const int *ind_stop_1based, double factor) {
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
-  if (!h->d_tau_abs || !h->d_grid) return fail(h, MOM_ESTATE, "mom_voigt_tau_abs_dual: call mom_absorption_begin with the spectral grid first");
-  if (iz_1based < 1 || iz_1based > h->abs_Nz || nLines < 0 ||
-      (nLines > 0 && (!nu || !gamma_d || !y || !S || !ind_start_1based || !ind_stop_1based)))
-    return fail(h, MOM_EINVAL, "mom_voigt_tau_abs_dual: bad argument");
-  for (int j = 0; j < nLines; ++j)
-    if (ind_start_1based[j] < 1 || ind_stop_1based[j] > h->S) {
-      char buf[160];
-      snprintf(buf, sizeof buf, "mom_voigt_tau_abs_dual: line %d: window [%d, %d] outside the grid 1..%d", j + 1, ind_start_1based[j],
-               ind_stop_1based[j], h->S);
-      return fail(h, MOM_EINVAL, buf);
-    }
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc = dual_table(h);
+  const int rc = voigt_only(h, "mom_voigt_tau_abs_dual");
   if (rc) return rc;
-  if (nLines == 0) return MOM_OK;
-  int sorted = 1;
-  for (int j = 1; j < nLines; ++j)
-    if (ind_start_1based[j] < ind_start_1based[j - 1] || ind_stop_1based[j] < ind_stop_1based[j - 1]) { sorted = 0; break; }
-  const size_t lb = (size_t)nLines;
-  rc = dual_lines(h, lb, 1);
-  if (rc) return rc;
-  const size_t cap = h->lines_per;
-  double *dl = h->d_lines, *dd = h->d_dlines;
-  int *dw = reinterpret_cast<int *>(dl + 4 * cap);
-  const double *src[4] = {nu, gamma_d, y, S}, *dsrc[4] = {dnu, dgamma_d, dy, dS};
-  const double *dev[4];
-  // the host arrays are borrowed for the call only: the copies must have left them before we return
-  for (int k = 0; k < 4; ++k) HIPCHK(h, hipMemcpyAsync(dl + k * cap, src[k], lb * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  for (int q = 0; q < 4; ++q) {  // host [nLines, 2] column-major -> [q][k][cap]; a null array: zeros
-    dev[q] = dd + 2 * q * cap;
-    for (int k = 0; k < 2; ++k) {
-      if (dsrc[q]) HIPCHK(h, hipMemcpyAsync(dd + (2 * q + k) * cap, dsrc[q] + lb * k, lb * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      else HIPCHK(h, hipMemsetAsync(dd + (2 * q + k) * cap, 0, lb * sizeof(double), h->stream));
-    }
-  }
-  HIPCHK(h, hipMemcpyAsync(dw, ind_start_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(dw + cap, ind_stop_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  const size_t col = (size_t)h->S * (iz_1based - 1);
-  HIPCHK(h, mom_voigt_dual_launch(h->stream, nLines, dl, dl + cap, dl + 2 * cap, dl + 3 * cap, dw, dw + cap, h->S, h->d_grid,
-                                  h->d_tau_abs + col, factor, 1, sorted, dev[0], dev[1], dev[2], dev[3], cap,
-                                  h->d_dtau_abs + col, (size_t)h->S * h->abs_Nz));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return MOM_OK;
+  const double *line[5] = {nu, gamma_d, y, S, nullptr}, *dline[5] = {dnu, dgamma_d, dy, dS, nullptr};
+  return lineshape_tau_abs_dual_run(h, "mom_voigt_tau_abs_dual", handle_shape(h), iz_1based, nLines, line, dline, ind_start_1based,
+                                    ind_stop_1based, factor);
+}
+
+// mom_voigt_tau_abs_dual for the handle's model
+extern "C" int mom_lineshape_tau_abs_dual(mom_t *h, int iz_1based, int nLines, const double *nu, const double *gamma_d,
+                                          const double *gamma_l, const double *y, const double *S, const double *dnu,
+                                          const double *dgamma_d, const double *dgamma_l, const double *dy, const double *dS,
+                                          const int *ind_start_1based, const int *ind_stop_1based, double factor) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  const double *line[5] = {nu, gamma_d, y, S, gamma_l}, *dline[5] = {dnu, dgamma_d, dy, dS, dgamma_l};
+  return lineshape_tau_abs_dual_run(h, "mom_lineshape_tau_abs_dual", handle_shape(h), iz_1based, nLines, line, dline, ind_start_1based,
+                                    ind_stop_1based, factor);
 }
 
 extern "C" int mom_absorption_get_partials(mom_t *h, double *dtau_abs) {
@@ -227,14 +312,8 @@ extern "C" int mom_voigt_tau_abs_layer(mom_t *h, int iz_1based, double pressure,
   const int nLines = h->lt.nLines;
   if (nLines == 0) return MOM_OK;
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t lb = (size_t)nLines;
-  if (lb > h->lines_per || h->lines_nz != 1) {
-    h->lines_nz = 1;
-    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
-    const size_t cap = std::max<size_t>(lb, 1024) * 2;
-    HIPCHK(h, h->d_lines.renew(5 * cap));
-    h->lines_per = cap;
-  }
+  const int rcl = value_lines(h, (size_t)nLines);
+  if (rcl) return rcl;
   const size_t cap = h->lines_per;
   double *dl = h->d_lines;
   int *dw = reinterpret_cast<int *>(dl + 4 * cap);
@@ -243,12 +322,12 @@ extern "C" int mom_voigt_tau_abs_layer(mom_t *h, int iz_1based, double pressure,
   // γ_d = (cSqrt2Ln2 / cc_) sqrt(cBolts_ / cMassMol) sqrt(T) ν₀ / sqrt(mol_weight)   (:87-88): the scalar part once
   const double cgd = (1.1774100225 / 2.99792458e8) * std::sqrt(1.3806503e-23 / 1.66053873e-27) * std::sqrt(temperature);
   HIPCHK(h, mom_line_prefactors_launch(h->stream, h->lt, h->S, h->d_grid, pressure, temperature, vmr, wing_cutoff, cgd, dl, dl + cap,
-                                       dl + 2 * cap, dl + 3 * cap, dw, dw + cap, flag));
+                                       dl + 2 * cap, dl + 3 * cap, dl + 5 * cap, dw, dw + cap, flag));
   int unsorted = 0;
   HIPCHK(h, hipMemcpyAsync(&unsorted, flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, mom_voigt_launch(h->stream, nLines, dl, dl + cap, dl + 2 * cap, dl + 3 * cap, dw, dw + cap, h->S, h->d_grid,
-                             h->d_tau_abs + (size_t)h->S * (iz_1based - 1), factor, 1, unsorted ? 0 : 1));
+  HIPCHK(h, mom_voigt_launch(h->stream, handle_shape(h), nLines, dl, dl + cap, dl + 5 * cap, dl + 2 * cap, dl + 3 * cap, dw, dw + cap, h->S,
+                             h->d_grid, h->d_tau_abs + (size_t)h->S * (iz_1based - 1), factor, 1, unsorted ? 0 : 1));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MOM_OK;
 }
@@ -297,7 +376,7 @@ int voigt_profile_run(mom_t *h, const char *fn, bool dual, int Nz, const double 
     const size_t need = per * (size_t)Nz;
     if (need > h->lines_per * (size_t)std::max(h->lines_nz, 1) || h->lines_nz != Nz) {
       if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
-      HIPCHK(h, h->d_lines.renew(5 * need));
+      HIPCHK(h, h->d_lines.renew(6 * need));
       h->lines_per = per;
       h->lines_nz = Nz;
     }
@@ -328,10 +407,10 @@ int voigt_profile_run(mom_t *h, const char *fn, bool dual, int Nz, const double 
     HIPCHK(h, hipEventRecord(h->ev_voigt[0], h->stream));
   }
   if (dual)
-    HIPCHK(h, mom_voigt_profile_dual_launch(h->stream, h->lt, Nz, cap, h->S, h->d_grid, h->d_prof, vmr, wing_cutoff, pf, h->d_dlines, win,
+    HIPCHK(h, mom_voigt_profile_dual_launch(h->stream, handle_shape(h), h->lt, Nz, cap, h->S, h->d_grid, h->d_prof, vmr, wing_cutoff, pf, h->d_dlines, win,
                                             flags, h->d_tau_abs, h->d_dtau_abs, h->d_prof + 3 * (size_t)Nz));
   else
-    HIPCHK(h, mom_voigt_profile_launch(h->stream, h->lt, Nz, cap, h->S, h->d_grid, h->d_prof, vmr, wing_cutoff, pf, win, flags,
+    HIPCHK(h, mom_voigt_profile_launch(h->stream, handle_shape(h), h->lt, Nz, cap, h->S, h->d_grid, h->d_prof, vmr, wing_cutoff, pf, win, flags,
                                        h->d_tau_abs, h->d_prof + 3 * (size_t)Nz));
   if (gpu_ms) HIPCHK(h, hipEventRecord(h->ev_voigt[1], h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));   // prm is a host temporary
@@ -357,7 +436,7 @@ extern "C" int mom_voigt_tau_abs_profile_dual(mom_t *h, int Nz, const double *pr
 extern "C" int mom_absorption_get_prefactor_partials(mom_t *h, int n, double *dnu, double *dgamma_d, double *dy, double *dS) {
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
   const size_t cap = h->lines_per, nz = (size_t)std::max(h->lines_nz, 1), last = (nz - 1) * cap;  // the LAST layer of a profile call
-  if (!h->d_lines || !h->d_dlines || n < 0 || (size_t)n > cap || h->d_dlines.capacity() < 8 * nz * cap)
+  if (!h->d_lines || !h->d_dlines || n < 0 || (size_t)n > cap || h->d_dlines.capacity() < 10 * nz * cap)
     return fail(h, MOM_ESTATE, "mom_absorption_get_prefactor_partials: no prefactor partials resident");
   HIPCHK(h, hipSetDevice(h->device));
   double *dst[4] = {dnu, dgamma_d, dy, dS};
@@ -380,6 +459,21 @@ extern "C" int mom_absorption_get_prefactors(mom_t *h, int n, double *nu, double
   const int *dw = reinterpret_cast<const int *>(h->d_lines + 4 * nz * cap);
   if (ind_start_1based) HIPCHK(h, hipMemcpy(ind_start_1based, dw + last, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
   if (ind_stop_1based) HIPCHK(h, hipMemcpy(ind_stop_1based, dw + nz * cap + last, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  return MOM_OK;
+}
+
+// gamma_l (compute_absorption_cross_section.jl:82-84) of the last device-prefactor call (the LAST layer of a profile call) and,
+// null to skip, its partials [n, 2] of the last Dual call (test access).  Only the device route fills the slot under every model.
+extern "C" int mom_absorption_get_gamma_l(mom_t *h, int n, double *gamma_l, double *dgamma_l) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (!h->d_lines || n < 0 || (size_t)n > h->lines_per) return fail(h, MOM_ESTATE, "mom_absorption_get_gamma_l: no prefactors resident");
+  const size_t cap = h->lines_per, nz = (size_t)std::max(h->lines_nz, 1), last = (nz - 1) * cap;
+  if (dgamma_l && (!h->d_dlines || h->d_dlines.capacity() < 10 * nz * cap))
+    return fail(h, MOM_ESTATE, "mom_absorption_get_gamma_l: no prefactor partials resident");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (gamma_l) HIPCHK(h, hipMemcpy(gamma_l, h->d_lines + 5 * nz * cap + last, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  for (int k = 0; k < 2 && dgamma_l; ++k)
+    HIPCHK(h, hipMemcpy(dgamma_l + (size_t)n * k, h->d_dlines + (8 + k) * nz * cap + last, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   return MOM_OK;
 }
 

@@ -1,9 +1,11 @@
-// voigt.hip -- Voigt line-by-line absorption cross section on gfx950.
+// voigt.hip -- line-by-line absorption cross section on gfx950.
 //
 // Restates line_shape!(::Voigt) (src/Absorption/compute_absorption_cross_section.jl:179-183)
 // with w(::HumlicekWeidemann32SDErrorFunction, z) (complex_error_functions.jl:226-234:
 // humlicek2 :24-30 for |x|+y >= 8, weideman32a :170-190 otherwise), accumulated over the
-// host loop over lines (:73-126).  The reference launches one kernel per line; here ONE
+// host loop over lines (:73-126).  The other absorption models -- line_shape!(::Doppler) (:167-171),
+// line_shape!(::Lorentz) (:173-177) and Voigt with w(::HumlicekWeidemann32VoigtErrorFunction, z)
+// (complex_error_functions.jl:210-219) -- are further instantiations of the same block (LineShape below).  The reference launches one kernel per line; here ONE
 // launch covers all lines: a workgroup owns 256 consecutive grid points, compacts (in line
 // order) the lines whose window overlaps its range into LDS, and every thread sums its grid
 // point's contributions in ascending line order -- the same accumulation order as the
@@ -48,8 +50,22 @@ __device__ __forceinline__ double div_refined(double n, double d) {
   return fma(fma(-d, q, n), r, q);
 }
 
-__device__ __forceinline__ double w_hw32sd_re(double x, double y) {
+// V15 = false: w(::HumlicekWeidemann32SDErrorFunction, z); V15 = true: w(::HumlicekWeidemann32VoigtErrorFunction, z)
+// (complex_error_functions.jl:210-219): region I of Humlicek (1982), w = (i / sqrt(pi)) z / (z^2 - 1/2), where |x| + y > 15
+// (strictly), weideman32a elsewhere
+template <bool V15>
+__device__ __forceinline__ double w_hw32_re(double x, double y) {
   const double rsp = 0.5641895835477563;  // 1/sqrt(pi)
+  if constexpr (V15) {
+    if (fabs(x) + y > 15.0) {
+      const cplx z = {x, y};
+      cplx den = cmul(z, z);
+      den.re -= 0.5;
+      const cplx num = {-(rsp * y), rsp * x};  // (i / sqrt(pi)) z
+      // the real part of num / den by one division, as on the humlicek2 branch: |den| = |z^2 - 1/2| > 50 here
+      return div_refined(num.re * den.re + num.im * den.im, den.re * den.re + den.im * den.im);
+    }
+  } else
   if (fabs(x) + y >= 8.0) {               // humlicek2, t = y - i x
     const cplx t = {y, -x};
     const cplx u = cmul(t, t);
@@ -64,7 +80,7 @@ __device__ __forceinline__ double w_hw32sd_re(double x, double y) {
   const double L = 4.756828460010884;  // sqrt(32/sqrt(2))
   const cplx lpiz = {L - y, x}, lmiz = {L + y, -x};
   // 1 / (L - i z) = conj / |.|^2: ONE division and no branch (Julia's complex division, complex.jl, is Smith's
-  // branching three-division scheme; |L - i z|^2 lies in [22, 200] here, so the plain form differs from it by rounding
+  // branching three-division scheme; |L - i z|^2 lies in [22, 200] here ([22, 400) below |x| + y = 15), so the plain form differs from it by rounding
   // only, and a wave no longer executes both branches.  Measured (tests/test_gpu_voigt_edges.py): relative to the terms the
   // rational form adds up, a |1 / (L - i z)| / sqrt(pi), sigma is within 6.4e-15 of the oracle in extended precision on this
   // branch -- the Float64 oracle with Smith's division 6.0e-15 -- and its partials within 8.9e-16 of their largest (7.9e-16))
@@ -90,9 +106,24 @@ __device__ __forceinline__ double w_hw32sd_re(double x, double y) {
 //   weideman32a: r = 1 / (L - i z), Z = (L + i z) r, P = sum a_k Z^k (P' carried by the same Horner loop),
 //                w = (1 / sqrt(pi) + 2 P r) r;  r' = i r^2, Z' = i r (1 + Z),
 //                w' = (2 P' Z' r + 2 P r') r + (1 / sqrt(pi) + 2 P r) r'
-// The reciprocals take the refined form: |D|^2 > 1e5 and < 1e60, |L - i z|^2 in [22, 200] (see above).
-__device__ __forceinline__ double w_hw32sd_dual(double x, double y, cplx &dw) {
+//   region I:    D = z^2 - 1/2, w = (i / sqrt(pi)) z / D, w' = -(i / sqrt(pi)) (z^2 + 1/2) / D^2
+// The reciprocals take the refined form: |D|^2 > 1e5 and < 1e60, |L - i z|^2 in [22, 200] (see above); with V15 |L - i z|^2 stays
+// below 400 and region I has |D|^2 > 2500.
+template <bool V15>
+__device__ __forceinline__ double w_hw32_dual(double x, double y, cplx &dw) {
   const double rsp = 0.5641895835477563;  // 1/sqrt(pi)
+  if constexpr (V15) {
+    if (fabs(x) + y > 15.0) {
+      const cplx z = {x, y};
+      const cplx u = cmul(z, z);
+      const cplx den = {u.re - 0.5, u.im};
+      const double inv = rcp_refined(den.re * den.re + den.im * den.im);
+      const cplx rden = {den.re * inv, -den.im * inv};
+      const cplx q = cmul(cplx{u.re + 0.5, u.im}, cmul(rden, rden));
+      dw = {rsp * q.im, -(rsp * q.re)};  // times -i / sqrt(pi)
+      return cmul(cplx{-(rsp * y), rsp * x}, rden).re;
+    }
+  } else
   if (fabs(x) + y >= 8.0) {
     const cplx t = {y, -x};
     const cplx u = cmul(t, t);
@@ -150,15 +181,28 @@ struct VoigtDualArgs {
   size_t os;
 };
 
+// The absorption model (HitranModel.broadening x HitranModel.CEF) as the compile-time shape of voigt_block.  It decides what is
+// staged per candidate line, what is evaluated per (line, grid point) and which partials the Dual run stages; the candidate search,
+// the ordered compaction, the accumulation order, the window compare and the tau_abs epilogue are the same for all four.
+//   kVoigtSD, kVoigt15  a = S c / gamma_d, b = c' / gamma_d, y:  sigma = a Re w(b (g - nu) + i y)           (:179-183)
+//   kDoppler            a = S c / gamma_d, b = 1 / gamma_d:      sigma = a exp(-ln 2 (b (g - nu))^2)        (:167-171)
+//   kLorentz            a = S gamma_l, b = gamma_l^2:            sigma = a / (pi (b + (g - nu)^2))          (:173-177)
+// MOM_BROADENING_* / MOM_CEF_* -> shape: mom_line_shape (mom_host.hpp)
+enum LineShape : int { kVoigtSD = 0, kVoigt15 = 1, kDoppler = 2, kLorentz = 3 };
+
 // DUAL = false is the value kernel; DUAL = true shares its candidate search and ordered compaction, stages d a, d b, d nu, d y
-// (two each) next to a, b, nu, y and sums the two partials of every grid point in the same ascending line order
-template <bool DUAL>
+// (two each) next to a, b, nu, y and sums the two partials of every grid point in the same ascending line order.  gamma_l and its
+// partials dgl (laid out like dd's arrays) are read by kLorentz only, gamma_d by the other three, y by the two Voigt shapes.
+template <bool DUAL, int SHAPE>
 __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict__ nu,
-                                            const double *__restrict__ gamma_d, const double *__restrict__ y,
+                                            const double *__restrict__ gamma_d, const double *__restrict__ gamma_l,
+                                            const double *__restrict__ y,
                                             const double *__restrict__ S, const int *__restrict__ i0,
                                             const int *__restrict__ i1, int nGrid,
                                             const double *__restrict__ grid, double *__restrict__ sigma,
-                                            double factor, int accumulate, int sorted, const VoigtDualArgs dd) {
+                                            double factor, int accumulate, int sorted, const VoigtDualArgs dd,
+                                            const double *__restrict__ dgl) {
+  constexpr bool kIsVoigt = SHAPE == kVoigtSD || SHAPE == kVoigt15;
   // per-line constants of the candidates, staged once per workgroup: centre, S c/gamma_d, c'/gamma_d, y and the
   // 0-based window -- the two divisions by gamma_d are per LINE here, not per evaluation (same expressions, same values)
   __shared__ double c_nu[kBlock], c_a[kBlock], c_b[kBlock], c_y[kBlock];
@@ -171,6 +215,8 @@ __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict
   const int gi = g0 + tid;
   const double gx = (gi < nGrid) ? grid[gi] : 0.0;
   const double cSqrtLn2divSqrtPi = 0.469718639319144059835, cSqrtLn2 = 0.8325546111577;
+  [[maybe_unused]] const double cLn2 = 0.6931471805599, cPi = 3.141592653589793;
+  const double kB = SHAPE == kDoppler ? 1.0 : cSqrtLn2;  // numerator of b
   double acc = 0.0;
   [[maybe_unused]] double dacc[2] = {0.0, 0.0};
   // Range [jlo, jhi] of line indices whose window touches this block: one cheap strided pass (two loads and a compare
@@ -221,22 +267,40 @@ __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict
     for (int w = 0; w < wave; ++w) off += wcount[w];
     if (hit) {  // ordered compaction: candidates keep the line order (the reference's accumulation order)
       const int pos = off + __popcll(mask & ((1ull << lane) - 1ull));
-      const double gd = gamma_d[j];
-      c_nu[pos] = nu[j];
-      c_a[pos] = S[j] * cSqrtLn2divSqrtPi / gd;
-      c_b[pos] = cSqrtLn2 / gd;
-      c_y[pos] = y[j];
-      c_win[pos] = make_int2(lo, hi - lo);  // hi >= lo for a hit
-      if constexpr (DUAL) {  // a = S c / gamma_d, b = c' / gamma_d by the quotient rule, per LINE like the values
-        const double a = c_a[pos], b = c_b[pos];
+      if constexpr (SHAPE == kLorentz) {  // a = S gamma_l, b = gamma_l^2 and their partials by the product rule
+        const double gl = gamma_l[j], s = S[j];
+        c_nu[pos] = nu[j];
+        c_a[pos] = s * gl;
+        c_b[pos] = gl * gl;
+        c_win[pos] = make_int2(lo, hi - lo);
+        if constexpr (DUAL) {
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const size_t o = (size_t)j + dd.ks * k;
-          const double dg = dd.dgd ? dd.dgd[o] : 0.0, ds = dd.dS ? dd.dS[o] : 0.0;
-          c_d[k * kBlock + pos] = (ds * cSqrtLn2divSqrtPi - a * dg) / gd;
-          c_d[(2 + k) * kBlock + pos] = -(b * dg) / gd;
-          c_d[(4 + k) * kBlock + pos] = dd.dnu ? dd.dnu[o] : 0.0;
-          c_d[(6 + k) * kBlock + pos] = dd.dy ? dd.dy[o] : 0.0;
+          for (int k = 0; k < 2; ++k) {
+            const size_t o = (size_t)j + dd.ks * k;
+            const double dg = dgl ? dgl[o] : 0.0, ds = dd.dS ? dd.dS[o] : 0.0;
+            c_d[k * kBlock + pos] = ds * gl + s * dg;
+            c_d[(2 + k) * kBlock + pos] = 2.0 * gl * dg;
+            c_d[(4 + k) * kBlock + pos] = dd.dnu ? dd.dnu[o] : 0.0;
+          }
+        }
+      } else {
+        const double gd = gamma_d[j];
+        c_nu[pos] = nu[j];
+        c_a[pos] = S[j] * cSqrtLn2divSqrtPi / gd;
+        c_b[pos] = kB / gd;
+        if constexpr (kIsVoigt) c_y[pos] = y[j];
+        c_win[pos] = make_int2(lo, hi - lo);  // hi >= lo for a hit
+        if constexpr (DUAL) {  // a = S c / gamma_d, b = c' / gamma_d by the quotient rule, per LINE like the values
+          const double a = c_a[pos], b = c_b[pos];
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            const size_t o = (size_t)j + dd.ks * k;
+            const double dg = dd.dgd ? dd.dgd[o] : 0.0, ds = dd.dS ? dd.dS[o] : 0.0;
+            c_d[k * kBlock + pos] = (ds * cSqrtLn2divSqrtPi - a * dg) / gd;
+            c_d[(2 + k) * kBlock + pos] = -(b * dg) / gd;
+            c_d[(4 + k) * kBlock + pos] = dd.dnu ? dd.dnu[o] : 0.0;
+            if constexpr (kIsVoigt) c_d[(6 + k) * kBlock + pos] = dd.dy ? dd.dy[o] : 0.0;
+          }
         }
       }
     }
@@ -255,14 +319,50 @@ __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict
 #ifndef MOM_VOIGT_DIAG_NOEVAL
     for (int c = 0; c < nc; ++c) {
       const int2 win = c_win[c];
-      const double cn = c_nu[c], ca = c_a[c], cb = c_b[c], cy = c_y[c];
+      const double cn = c_nu[c], ca = c_a[c], cb = c_b[c];
+      [[maybe_unused]] double cy = 0.0;
+      if constexpr (kIsVoigt) cy = c_y[c];
       const bool in = (unsigned)(gt - win.x) <= (unsigned)win.y;
       if (__builtin_amdgcn_ballot_w64(in) == 0) continue;
-      if constexpr (DUAL) {
+      if constexpr (SHAPE == kDoppler) {
+        // q = b (g - nu), e = exp(-ln 2 q^2): far from the line e underflows to 0.0 and every product below is 0.0 with it
+        // (q^2 stays finite for any distance in cm^-1).  Dual run: d_k q = d_k b (g - nu) - b d_k nu (d_k b = -b d_k gamma_d / gamma_d),
+        // d_k e = e (-2 ln 2 q d_k q), d_k sigma = d_k a e + a d_k e
+        const double dist = gx - cn, q = cb * dist;
+        const double e = exp(-cLn2 * (q * q));
+        if (in) {
+          acc = fma(ca, e, acc);
+          if constexpr (DUAL) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              const double dq = c_d[(2 + k) * kBlock + c] * dist - cb * c_d[(4 + k) * kBlock + c];
+              dacc[k] += c_d[k * kBlock + c] * e + ca * (e * (-2.0 * cLn2 * q * dq));
+            }
+          }
+        }
+      } else if constexpr (SHAPE == kLorentz) {
+        // D = pi (gamma_l^2 + (g - nu)^2), sigma = S gamma_l / D: the reference's operations in its order (one IEEE division, no
+        // contraction).  Dual run: d_k D = pi (2 gamma_l d_k gamma_l - 2 (g - nu) d_k nu), d_k sigma = (d_k a - sigma d_k D) / D
+#pragma clang fp contract(off)
+        const double dist = gx - cn;
+        const double D = cPi * (cb + dist * dist);
+        const double sg = ca / D;
+        if (in) {
+          acc += sg;
+          if constexpr (DUAL) {
+            const double rD = 1.0 / D;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              const double dD = cPi * (c_d[(2 + k) * kBlock + c] - 2.0 * dist * c_d[(4 + k) * kBlock + c]);
+              dacc[k] += (c_d[k * kBlock + c] - sg * dD) * rD;
+            }
+          }
+        }
+      } else if constexpr (DUAL) {
         // x = b (g - nu): d_k x = d_k b (g - nu) - b d_k nu;  d_k sigma += d_k a Re w + a Re(w' (d_k x + i d_k y))
         const double dist = gx - cn;
         cplx dw;
-        const double w = w_hw32sd_dual(cb * dist, cy, dw);
+        const double w = w_hw32_dual<SHAPE == kVoigt15>(cb * dist, cy, dw);
         if (in) {
           acc = fma(ca, w, acc);
 #pragma unroll
@@ -272,13 +372,13 @@ __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict
           }
         }
       } else {
-        const double w = w_hw32sd_re(cb * (gx - cn), cy);
+        const double w = w_hw32_re<SHAPE == kVoigt15>(cb * (gx - cn), cy);
         if (in) acc = fma(ca, w, acc);   // acc += a w, one rounding as before
       }
     }
 #else
     (void)gt;
-    if (nc > 0) acc += c_a[nc - 1] + c_nu[0] + c_b[0] + c_y[0] + c_win[0].x;   // (diagnostic build: the setup without the evaluations)
+    if (nc > 0) acc += c_a[nc - 1] + c_nu[0] + c_b[0] + (kIsVoigt ? c_y[0] : 0.0) + c_win[0].x;   // (diagnostic build: the setup without the evaluations)
 #endif
     __syncthreads();
   }
@@ -305,7 +405,8 @@ __global__ void __launch_bounds__(kBlock) k_voigt(int nLines, const double *__re
                                                   const int *__restrict__ i1, int nGrid,
                                                   const double *__restrict__ grid, double *__restrict__ sigma,
                                                   double factor, int accumulate, int sorted) {
-  voigt_block<false>(nLines, nu, gamma_d, y, S, i0, i1, nGrid, grid, sigma, factor, accumulate, sorted, VoigtDualArgs{});
+  voigt_block<false, kVoigtSD>(nLines, nu, gamma_d, nullptr, y, S, i0, i1, nGrid, grid, sigma, factor, accumulate, sorted, VoigtDualArgs{},
+                               nullptr);
 }
 __global__ void __launch_bounds__(kBlock) k_voigt_dual(int nLines, const double *__restrict__ nu,
                                                        const double *__restrict__ gamma_d, const double *__restrict__ y,
@@ -313,11 +414,11 @@ __global__ void __launch_bounds__(kBlock) k_voigt_dual(int nLines, const double 
                                                        const int *__restrict__ i1, int nGrid,
                                                        const double *__restrict__ grid, double *__restrict__ sigma,
                                                        double factor, int accumulate, int sorted, VoigtDualArgs dd) {
-  voigt_block<true>(nLines, nu, gamma_d, y, S, i0, i1, nGrid, grid, sigma, factor, accumulate, sorted, dd);
+  voigt_block<true, kVoigtSD>(nLines, nu, gamma_d, nullptr, y, S, i0, i1, nGrid, grid, sigma, factor, accumulate, sorted, dd, nullptr);
 }
 
 // All layers of a profile in ONE launch (blockIdx.y = layer): the per-line prefactors of layer z sit at [k][z][cap]
-// (k = nu, gamma_d, y, S; the two window arrays likewise as ints), tau_abs[:, z] += sigma_z * factor[z]; whether the
+// (k = nu, gamma_d, y, S; the two window arrays likewise as ints in slot 4; gamma_l in slot 5), tau_abs[:, z] += sigma_z * factor[z]; whether the
 // bisection applies is read from the layer's flag on the device (no host round trip between the two kernels).
 __global__ void __launch_bounds__(kBlock) k_voigt_profile(int nLines, int Nz, size_t cap, const double *__restrict__ pf,
                                                           const int *__restrict__ win, int nGrid, const double *__restrict__ grid,
@@ -325,10 +426,10 @@ __global__ void __launch_bounds__(kBlock) k_voigt_profile(int nLines, int Nz, si
                                                           const int *__restrict__ unsorted) {
   const int z = blockIdx.y;
   const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
-  voigt_block<false>(nLines, pf + lz, pf + ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz, nGrid, grid,
-                     tau_abs + (size_t)nGrid * z, factor[z], 1, unsorted[z] ? 0 : 1, VoigtDualArgs{});
+  voigt_block<false, kVoigtSD>(nLines, pf + lz, pf + ks + lz, nullptr, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz, nGrid,
+                               grid, tau_abs + (size_t)nGrid * z, factor[z], 1, unsorted[z] ? 0 : 1, VoigtDualArgs{}, nullptr);
 }
-// ... and its Dual run: the partials of layer z's prefactors at dpf[q][k][z][cap] (q = nu, gamma_d, y, S), dtau_abs [nGrid, Nz, 2]
+// ... and its Dual run: the partials of layer z's prefactors at dpf[q][k][z][cap] (q = nu, gamma_d, y, S, gamma_l), dtau_abs [nGrid, Nz, 2]
 __global__ void __launch_bounds__(kBlock) k_voigt_profile_dual(int nLines, int Nz, size_t cap, const double *__restrict__ pf,
                                                                const double *__restrict__ dpf, const int *__restrict__ win, int nGrid,
                                                                const double *__restrict__ grid, double *__restrict__ tau_abs,
@@ -338,9 +439,61 @@ __global__ void __launch_bounds__(kBlock) k_voigt_profile_dual(int nLines, int N
   const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
   const VoigtDualArgs dd = {dpf + lz, dpf + 2 * ks + lz, dpf + 4 * ks + lz, dpf + 6 * ks + lz, ks, dtau_abs + (size_t)nGrid * z,
                             (size_t)nGrid * Nz};
-  voigt_block<true>(nLines, pf + lz, pf + ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz, nGrid, grid,
-                    tau_abs + (size_t)nGrid * z, factor[z], 1, unsorted[z] ? 0 : 1, dd);
+  voigt_block<true, kVoigtSD>(nLines, pf + lz, pf + ks + lz, nullptr, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz, nGrid,
+                              grid, tau_abs + (size_t)nGrid * z, factor[z], 1, unsorted[z] ? 0 : 1, dd, nullptr);
 }
+
+// The other three shapes: the same four kernels with gamma_l (and, Dual run, its partials) as one more argument.  The
+// Voigt / HW32SD kernels above keep their argument lists, so the default model runs the code it always ran.
+template <int SHAPE>
+__global__ void __launch_bounds__(kBlock) k_lineshape(int nLines, const double *__restrict__ nu, const double *__restrict__ gamma_d,
+                                                      const double *__restrict__ gamma_l, const double *__restrict__ y,
+                                                      const double *__restrict__ S, const int *__restrict__ i0,
+                                                      const int *__restrict__ i1, int nGrid, const double *__restrict__ grid,
+                                                      double *__restrict__ sigma, double factor, int accumulate, int sorted) {
+  voigt_block<false, SHAPE>(nLines, nu, gamma_d, gamma_l, y, S, i0, i1, nGrid, grid, sigma, factor, accumulate, sorted, VoigtDualArgs{},
+                            nullptr);
+}
+template <int SHAPE>
+__global__ void __launch_bounds__(kBlock) k_lineshape_dual(int nLines, const double *__restrict__ nu, const double *__restrict__ gamma_d,
+                                                           const double *__restrict__ gamma_l, const double *__restrict__ y,
+                                                           const double *__restrict__ S, const int *__restrict__ i0,
+                                                           const int *__restrict__ i1, int nGrid, const double *__restrict__ grid,
+                                                           double *__restrict__ sigma, double factor, int accumulate, int sorted,
+                                                           VoigtDualArgs dd, const double *__restrict__ dgl) {
+  voigt_block<true, SHAPE>(nLines, nu, gamma_d, gamma_l, y, S, i0, i1, nGrid, grid, sigma, factor, accumulate, sorted, dd, dgl);
+}
+template <int SHAPE>
+__global__ void __launch_bounds__(kBlock) k_lineshape_profile(int nLines, int Nz, size_t cap, const double *__restrict__ pf,
+                                                              const int *__restrict__ win, int nGrid, const double *__restrict__ grid,
+                                                              double *__restrict__ tau_abs, const double *__restrict__ factor,
+                                                              const int *__restrict__ unsorted) {
+  const int z = blockIdx.y;
+  const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
+  voigt_block<false, SHAPE>(nLines, pf + lz, pf + ks + lz, pf + 5 * ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz,
+                            nGrid, grid, tau_abs + (size_t)nGrid * z, factor[z], 1, unsorted[z] ? 0 : 1, VoigtDualArgs{}, nullptr);
+}
+template <int SHAPE>
+__global__ void __launch_bounds__(kBlock) k_lineshape_profile_dual(int nLines, int Nz, size_t cap, const double *__restrict__ pf,
+                                                                   const double *__restrict__ dpf, const int *__restrict__ win, int nGrid,
+                                                                   const double *__restrict__ grid, double *__restrict__ tau_abs,
+                                                                   double *__restrict__ dtau_abs, const double *__restrict__ factor,
+                                                                   const int *__restrict__ unsorted) {
+  const int z = blockIdx.y;
+  const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
+  const VoigtDualArgs dd = {dpf + lz, dpf + 2 * ks + lz, dpf + 4 * ks + lz, dpf + 6 * ks + lz, ks, dtau_abs + (size_t)nGrid * z,
+                            (size_t)nGrid * Nz};
+  voigt_block<true, SHAPE>(nLines, pf + lz, pf + ks + lz, pf + 5 * ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz,
+                           nGrid, grid, tau_abs + (size_t)nGrid * z, factor[z], 1, unsorted[z] ? 0 : 1, dd, dpf + 8 * ks + lz);
+}
+
+// STMT(shape) for one of the three shapes that are not the default
+#define MOM_SHAPE_SWITCH(shape, STMT)      \
+  switch (shape) {                         \
+    case kVoigt15: STMT(kVoigt15); break;  \
+    case kDoppler: STMT(kDoppler); break;  \
+    default: STMT(kLorentz); break;        \
+  }
 
 thread_local double v_last_ms = 0.0;
 
@@ -413,10 +566,10 @@ __device__ __forceinline__ double interp_index(const double *grid, int n, double
   const double slope = 1.0 / (grid[lo + 1] - grid[lo]);
   return slope * (x - grid[lo]) + (double)(lo + 1);
 }
-// Dual run: where the partials of nu, gamma_d, y, S of one layer go (partial k of line j at p[j + ks k]; k = 0 pressure,
+// Dual run: where the partials of nu, gamma_d, y, S, gamma_l of one layer go (partial k of line j at p[j + ks k]; k = 0 pressure,
 // 1 temperature) and d cgd / dT
 struct LineDualOut {
-  double *dnu, *dgd, *dy, *dS;
+  double *dnu, *dgd, *dy, *dS, *dgl;
   size_t ks;
   double dcgd;
 };
@@ -425,7 +578,7 @@ struct LineDualOut {
 template <bool DUAL>
 __device__ __forceinline__ void line_prefactors_one(int j, const MomLineTable &tb, int nGrid, const double *grid, double p, double T,
                                                     double vmr, double wing, double cgd, double *nu, double *gd, double *yy, double *SS,
-                                                    int *i0, int *i1, int *unsorted, const LineDualOut dd) {
+                                                    double *gll, int *i0, int *i1, int *unsorted, const LineDualOut dd) {
 #pragma clang fp contract(off)
   if (j >= tb.nLines) return;
   const double p_ref = 1013.25, t_ref = 296.0, c2 = 1.4387769, cLn2 = 0.6931471805599;
@@ -457,6 +610,7 @@ __device__ __forceinline__ void line_prefactors_one(int j, const MomLineTable &t
   const double ynum = sqrt(cLn2) * gl;
   yy[j] = ynum / g;
   SS[j] = S;
+  gll[j] = gl;   // line_shape! takes gamma_l next to y (:118-124): the fifth prefactor, read by the Lorentz shape
   if constexpr (DUAL) {
     // nu = nu0 + p / p_ref delta;  gamma_l = lin(p) (t_ref / T)^n: d/dp = the bracket times the power (no gamma_l / p),
     // d/dT = lin n (t_ref / T)^(n - 1) (-t_ref / T^2);  gamma_d = cgd(T) nu0 / sqrt(w);  y = sqrt(ln 2) gamma_l / gamma_d
@@ -473,6 +627,8 @@ __device__ __forceinline__ void line_prefactors_one(int j, const MomLineTable &t
     dd.dy[j + dd.ks] = sqrt(cLn2) * dgl_T * (1 / g) + dg_T * (-(ynum / (g * g)));
     dd.dS[j] = 0.0;
     dd.dS[j + dd.ks] = dS_T;
+    dd.dgl[j] = dgl_p;
+    dd.dgl[j + dd.ks] = dgl_T;
   }
   const int a = (int)rint(interp_index(grid, nGrid, v - wing, 1.0)), b = (int)rint(interp_index(grid, nGrid, v + wing, (double)nGrid));
   i0[j] = a;
@@ -484,28 +640,30 @@ __device__ __forceinline__ void line_prefactors_one(int j, const MomLineTable &t
   }
 }
 __global__ void k_line_prefactors(MomLineTable tb, int nGrid, const double *grid, double p, double T, double vmr, double wing,
-                                  double cgd, double *nu, double *gd, double *yy, double *SS, int *i0, int *i1, int *unsorted) {
-  line_prefactors_one<false>(blockIdx.x * blockDim.x + threadIdx.x, tb, nGrid, grid, p, T, vmr, wing, cgd, nu, gd, yy, SS, i0, i1, unsorted,
-                             LineDualOut{});
+                                  double cgd, double *nu, double *gd, double *yy, double *SS, double *gll, int *i0, int *i1,
+                                  int *unsorted) {
+  line_prefactors_one<false>(blockIdx.x * blockDim.x + threadIdx.x, tb, nGrid, grid, p, T, vmr, wing, cgd, nu, gd, yy, SS, gll, i0, i1,
+                             unsorted, LineDualOut{});
 }
-// blockIdx.y = layer; prm = [p | T | cgd][Nz]; outputs at [k][z][cap] (see k_voigt_profile)
+// blockIdx.y = layer; prm = [p | T | cgd][Nz]; outputs at [k][z][cap], gamma_l at k = 5 (see k_voigt_profile)
 __global__ void k_line_prefactors_profile(MomLineTable tb, int Nz, size_t cap, int nGrid, const double *grid, const double *prm,
                                           double vmr, double wing, double *pf, int *win, int *unsorted) {
   const int z = blockIdx.y;
   const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
   line_prefactors_one<false>(blockIdx.x * blockDim.x + threadIdx.x, tb, nGrid, grid, prm[z], prm[Nz + z], vmr, wing, prm[2 * Nz + z], pf + lz,
-                             pf + ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz, unsorted + z, LineDualOut{});
+                             pf + ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, pf + 5 * ks + lz, win + lz, win + ks + lz, unsorted + z,
+                             LineDualOut{});
 }
-// Dual run: prm = [p | T | cgd | factor | d cgd / dT][Nz]; partials at dpf[q][k][z][cap] (see k_voigt_profile_dual)
+// Dual run: prm = [p | T | cgd | factor | d cgd / dT][Nz]; partials at dpf[q][k][z][cap], q = 0 .. 4 (see k_voigt_profile_dual)
 __global__ void k_line_prefactors_profile_dual(MomLineTable tb, int Nz, size_t cap, int nGrid, const double *grid, const double *prm,
                                                double vmr, double wing, double *pf, double *dpf, int *win, int *unsorted) {
   const int z = blockIdx.y;
   const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
-  const LineDualOut dd = {dpf + lz, dpf + 2 * ks + lz, dpf + 4 * ks + lz, dpf + 6 * ks + lz, ks, prm[4 * Nz + z]};
+  const LineDualOut dd = {dpf + lz, dpf + 2 * ks + lz, dpf + 4 * ks + lz, dpf + 6 * ks + lz, dpf + 8 * ks + lz, ks, prm[4 * Nz + z]};
   line_prefactors_one<true>(blockIdx.x * blockDim.x + threadIdx.x, tb, nGrid, grid, prm[z], prm[Nz + z], vmr, wing, prm[2 * Nz + z], pf + lz,
-                            pf + ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz, unsorted + z, dd);
+                            pf + ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, pf + 5 * ks + lz, win + lz, win + ks + lz, unsorted + z, dd);
 }
-hipError_t mom_voigt_profile_launch(hipStream_t st, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
+hipError_t mom_voigt_profile_launch(hipStream_t st, int shape, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
                                     const double *prm, double vmr, double wing, double *pf, int *win, int *unsorted, double *tau_abs,
                                     const double *factor) {
   if (tb.nLines <= 0 || Nz <= 0) return hipSuccess;
@@ -513,11 +671,17 @@ hipError_t mom_voigt_profile_launch(hipStream_t st, const MomLineTable &tb, int 
                      wing, pf, win, unsorted);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_voigt_profile, dim3((nGrid + kBlock - 1) / kBlock, Nz), dim3(kBlock), 0, st, tb.nLines, Nz, cap, pf, win, nGrid,
-                     grid, tau_abs, factor, unsorted);
+  const dim3 blocks((nGrid + kBlock - 1) / kBlock, Nz);
+#define MOM_LAUNCH(SH) \
+  hipLaunchKernelGGL(k_lineshape_profile<SH>, blocks, dim3(kBlock), 0, st, tb.nLines, Nz, cap, pf, win, nGrid, grid, tau_abs, factor, unsorted)
+  if (shape == kVoigtSD)
+    hipLaunchKernelGGL(k_voigt_profile, blocks, dim3(kBlock), 0, st, tb.nLines, Nz, cap, pf, win, nGrid, grid, tau_abs, factor, unsorted);
+  else
+    MOM_SHAPE_SWITCH(shape, MOM_LAUNCH)
+#undef MOM_LAUNCH
   return hipGetLastError();
 }
-hipError_t mom_voigt_profile_dual_launch(hipStream_t st, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
+hipError_t mom_voigt_profile_dual_launch(hipStream_t st, int shape, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
                                          const double *prm, double vmr, double wing, double *pf, double *dpf, int *win, int *unsorted,
                                          double *tau_abs, double *dtau_abs, const double *factor) {
   if (tb.nLines <= 0 || Nz <= 0) return hipSuccess;
@@ -525,33 +689,57 @@ hipError_t mom_voigt_profile_dual_launch(hipStream_t st, const MomLineTable &tb,
                      vmr, wing, pf, dpf, win, unsorted);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_voigt_profile_dual, dim3((nGrid + kBlock - 1) / kBlock, Nz), dim3(kBlock), 0, st, tb.nLines, Nz, cap, pf, dpf, win,
-                     nGrid, grid, tau_abs, dtau_abs, factor, unsorted);
+  const dim3 blocks((nGrid + kBlock - 1) / kBlock, Nz);
+#define MOM_LAUNCH(SH)                                                                                                                \
+  hipLaunchKernelGGL(k_lineshape_profile_dual<SH>, blocks, dim3(kBlock), 0, st, tb.nLines, Nz, cap, pf, dpf, win, nGrid, grid, tau_abs, \
+                     dtau_abs, factor, unsorted)
+  if (shape == kVoigtSD)
+    hipLaunchKernelGGL(k_voigt_profile_dual, blocks, dim3(kBlock), 0, st, tb.nLines, Nz, cap, pf, dpf, win, nGrid, grid, tau_abs, dtau_abs,
+                       factor, unsorted);
+  else
+    MOM_SHAPE_SWITCH(shape, MOM_LAUNCH)
+#undef MOM_LAUNCH
   return hipGetLastError();
 }
 hipError_t mom_line_prefactors_launch(hipStream_t st, const MomLineTable &tb, int nGrid, const double *grid, double p, double T,
-                                      double vmr, double wing, double cgd, double *nu, double *gd, double *y, double *S, int *i0,
-                                      int *i1, int *unsorted) {
+                                      double vmr, double wing, double cgd, double *nu, double *gd, double *y, double *S, double *gl,
+                                      int *i0, int *i1, int *unsorted) {
   if (tb.nLines <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_line_prefactors, dim3((tb.nLines + 255) / 256), dim3(256), 0, st, tb, nGrid, grid, p, T, vmr, wing, cgd, nu,
-                     gd, y, S, i0, i1, unsorted);
+                     gd, y, S, gl, i0, i1, unsorted);
   return hipGetLastError();
 }
 
-hipError_t mom_voigt_launch(hipStream_t st, int nLines, const double *nu, const double *gamma_d, const double *y,
-                            const double *S, const int *i0, const int *i1, int nGrid, const double *grid, double *out,
+hipError_t mom_voigt_launch(hipStream_t st, int shape, int nLines, const double *nu, const double *gamma_d, const double *gamma_l,
+                            const double *y, const double *S, const int *i0, const int *i1, int nGrid, const double *grid, double *out,
                             double factor, int accumulate, int sorted) {
-  hipLaunchKernelGGL(k_voigt, dim3((nGrid + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nLines, nu, gamma_d, y, S, i0, i1,
-                     nGrid, grid, out, factor, accumulate, sorted);
+  const dim3 blocks((nGrid + kBlock - 1) / kBlock);
+#define MOM_LAUNCH(SH)                                                                                                            \
+  hipLaunchKernelGGL(k_lineshape<SH>, blocks, dim3(kBlock), 0, st, nLines, nu, gamma_d, gamma_l, y, S, i0, i1, nGrid, grid, out, factor, \
+                     accumulate, sorted)
+  if (shape == kVoigtSD)
+    hipLaunchKernelGGL(k_voigt, blocks, dim3(kBlock), 0, st, nLines, nu, gamma_d, y, S, i0, i1, nGrid, grid, out, factor, accumulate, sorted);
+  else
+    MOM_SHAPE_SWITCH(shape, MOM_LAUNCH)
+#undef MOM_LAUNCH
   return hipGetLastError();
 }
 
-hipError_t mom_voigt_dual_launch(hipStream_t st, int nLines, const double *nu, const double *gamma_d, const double *y,
-                                 const double *S, const int *i0, const int *i1, int nGrid, const double *grid, double *out,
-                                 double factor, int accumulate, int sorted, const double *dnu, const double *dgd, const double *dy,
-                                 const double *dS, size_t ks, double *dout, size_t os) {
-  hipLaunchKernelGGL(k_voigt_dual, dim3((nGrid + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nLines, nu, gamma_d, y, S, i0, i1,
-                     nGrid, grid, out, factor, accumulate, sorted, VoigtDualArgs{dnu, dgd, dy, dS, ks, dout, os});
+hipError_t mom_voigt_dual_launch(hipStream_t st, int shape, int nLines, const double *nu, const double *gamma_d, const double *gamma_l,
+                                 const double *y, const double *S, const int *i0, const int *i1, int nGrid, const double *grid,
+                                 double *out, double factor, int accumulate, int sorted, const double *dnu, const double *dgd,
+                                 const double *dgl, const double *dy, const double *dS, size_t ks, double *dout, size_t os) {
+  const dim3 blocks((nGrid + kBlock - 1) / kBlock);
+  const VoigtDualArgs dd = {dnu, dgd, dy, dS, ks, dout, os};
+#define MOM_LAUNCH(SH)                                                                                                                 \
+  hipLaunchKernelGGL(k_lineshape_dual<SH>, blocks, dim3(kBlock), 0, st, nLines, nu, gamma_d, gamma_l, y, S, i0, i1, nGrid, grid, out, factor, \
+                     accumulate, sorted, dd, dgl)
+  if (shape == kVoigtSD)
+    hipLaunchKernelGGL(k_voigt_dual, blocks, dim3(kBlock), 0, st, nLines, nu, gamma_d, y, S, i0, i1, nGrid, grid, out, factor, accumulate,
+                       sorted, dd);
+  else
+    MOM_SHAPE_SWITCH(shape, MOM_LAUNCH)
+#undef MOM_LAUNCH
   return hipGetLastError();
 }
 
@@ -568,14 +756,16 @@ hipError_t mom_voigt_dual_launch(hipStream_t st, int nLines, const double *nu, c
   } while (0)
 
 namespace {
-// mom_voigt_xsec (dsigma = nullptr: the value kernel) and mom_voigt_xsec_dual (dpart: dnu, dgamma_d, dy, dS, each [nLines, 2]
-// or null = zeros); `fn` is the entry point's name in the error texts
-int voigt_xsec_run(const char *fn, int device, int nLines, const double *nu, const double *gamma_d, const double *y, const double *S,
-                   const double *const *dpart, const int *ind_start, const int *ind_stop, int nGrid, const double *grid, double *sigma,
-                   double *dsigma) {
+// mom_voigt_xsec / mom_lineshape_xsec (dsigma = nullptr: the value kernel) and their Dual runs (dpart: dnu, dgamma_d, dy, dS,
+// dgamma_l, each [nLines, 2] or null = zeros); line[] = nu, gamma_d, y, S, gamma_l, of which the shape's broadening reads some (the
+// others may be null); `fn` is the entry point's name in the error texts
+int lineshape_xsec_run(const char *fn, int device, int shape, int nLines, const double *const *line, const double *const *dpart,
+                       const int *ind_start, const int *ind_stop, int nGrid, const double *grid, double *sigma, double *dsigma) {
   char buf[192];
   const bool dual = dsigma != nullptr;
-  if (nLines < 0 || nGrid <= 0 || !grid || !sigma || (nLines > 0 && (!nu || !gamma_d || !y || !S || !ind_start || !ind_stop))) {
+  bool lines_ok = ind_start && ind_stop;
+  for (int k = 0; k < 5; ++k) lines_ok = lines_ok && (line[k] || !mom_shape_reads(shape, k));
+  if (nLines < 0 || nGrid <= 0 || !grid || !sigma || (nLines > 0 && !lines_ok)) {
     snprintf(buf, sizeof buf, "%s: bad argument (null pointer or non-positive size)", fn);
     mom_set_global_error(buf);
     return MOM_EINVAL;
@@ -594,8 +784,8 @@ int voigt_xsec_run(const char *fn, int device, int nLines, const double *nu, con
   // one pinned-free staging copy per array on a private stream; callers that evaluate many layers should use the
   // handle-level mom_voigt_tau_abs, which keeps all of this resident
   const size_t lb = (size_t)(nLines > 0 ? nLines : 1);
-  const size_t dual_doubles = dual ? 8 * lb + 2 * (size_t)nGrid : 0;
-  const size_t bytes = (4 * lb + 2 * (size_t)nGrid + dual_doubles) * sizeof(double) + 2 * lb * sizeof(int);
+  const size_t dual_doubles = dual ? 10 * lb + 2 * (size_t)nGrid : 0;
+  const size_t bytes = (5 * lb + 2 * (size_t)nGrid + dual_doubles) * sizeof(double) + 2 * lb * sizeof(int);
   char *base = nullptr;
   hipStream_t st = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -614,20 +804,20 @@ int voigt_xsec_run(const char *fn, int device, int nLines, const double *nu, con
   VCHK(hipStreamCreate(&st));
   VCHK(hipMalloc((void **)&base, bytes));
   {
-    double *d_line = (double *)base, *d_grid = d_line + 4 * lb, *d_sig = d_grid + nGrid;
-    double *d_dline = d_sig + nGrid, *d_dsig = d_dline + (dual ? 8 * lb : 0);   // Dual run only: [q][k][lb], [nGrid, 2]
+    double *d_line = (double *)base, *d_grid = d_line + 5 * lb, *d_sig = d_grid + nGrid;
+    double *d_dline = d_sig + nGrid, *d_dsig = d_dline + (dual ? 10 * lb : 0);   // Dual run only: [q][k][lb], [nGrid, 2]
     int *d_win = (int *)(d_sig + nGrid + dual_doubles);
-    const double *hsrc[4] = {nu, gamma_d, y, S};
-    for (int k = 0; k < 4; ++k)
-      if (nLines) VCHK(hipMemcpyAsync(d_line + k * lb, hsrc[k], (size_t)nLines * sizeof(double), hipMemcpyHostToDevice, st));
+    for (int k = 0; k < 5; ++k)   // an array the shape does not read stays as allocated: the kernel never loads it
+      if (nLines && line[k] && mom_shape_reads(shape, k))
+        VCHK(hipMemcpyAsync(d_line + k * lb, line[k], (size_t)nLines * sizeof(double), hipMemcpyHostToDevice, st));
     if (nLines) {
       VCHK(hipMemcpyAsync(d_win, ind_start, (size_t)nLines * sizeof(int), hipMemcpyHostToDevice, st));
       VCHK(hipMemcpyAsync(d_win + lb, ind_stop, (size_t)nLines * sizeof(int), hipMemcpyHostToDevice, st));
     }
     VCHK(hipMemcpyAsync(d_grid, grid, (size_t)nGrid * sizeof(double), hipMemcpyHostToDevice, st));
-    const double *d_part[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int q = 0; q < 4 && dual && nLines; ++q) {
-      if (!dpart[q]) continue;
+    const double *d_part[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int q = 0; q < 5 && dual && nLines; ++q) {
+      if (!dpart[q] || !mom_shape_reads(shape, q)) continue;
       for (int k = 0; k < 2; ++k)   // host [nLines, 2] column-major -> [k][lb]
         VCHK(hipMemcpyAsync(d_dline + (2 * q + k) * lb, dpart[q] + (size_t)nLines * k, (size_t)nLines * sizeof(double),
                             hipMemcpyHostToDevice, st));
@@ -637,11 +827,12 @@ int voigt_xsec_run(const char *fn, int device, int nLines, const double *nu, con
     VCHK(hipEventCreate(&e1));
     VCHK(hipEventRecord(e0, st));
     if (dual)
-      VCHK(mom_voigt_dual_launch(st, nLines, d_line, d_line + lb, d_line + 2 * lb, d_line + 3 * lb, d_win, d_win + lb, nGrid, d_grid,
-                                 d_sig, 1.0, 0, sorted, d_part[0], d_part[1], d_part[2], d_part[3], lb, d_dsig, (size_t)nGrid));
+      VCHK(mom_voigt_dual_launch(st, shape, nLines, d_line, d_line + lb, d_line + 4 * lb, d_line + 2 * lb, d_line + 3 * lb, d_win,
+                                 d_win + lb, nGrid, d_grid, d_sig, 1.0, 0, sorted, d_part[0], d_part[1], d_part[4], d_part[2], d_part[3],
+                                 lb, d_dsig, (size_t)nGrid));
     else
-      VCHK(mom_voigt_launch(st, nLines, d_line, d_line + lb, d_line + 2 * lb, d_line + 3 * lb, d_win, d_win + lb, nGrid, d_grid,
-                            d_sig, 1.0, 0, sorted));
+      VCHK(mom_voigt_launch(st, shape, nLines, d_line, d_line + lb, d_line + 4 * lb, d_line + 2 * lb, d_line + 3 * lb, d_win, d_win + lb,
+                            nGrid, d_grid, d_sig, 1.0, 0, sorted));
     VCHK(hipEventRecord(e1, st));
     VCHK(hipMemcpyAsync(sigma, d_sig, (size_t)nGrid * sizeof(double), hipMemcpyDeviceToHost, st));
     if (dual) VCHK(hipMemcpyAsync(dsigma, d_dsig, 2 * (size_t)nGrid * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -662,7 +853,8 @@ done:
 extern "C" int mom_voigt_xsec(int device, int nLines, const double *nu, const double *gamma_d, const double *y,
                               const double *S, const int *ind_start, const int *ind_stop, int nGrid, const double *grid,
                               double *sigma) {
-  return voigt_xsec_run("mom_voigt_xsec", device, nLines, nu, gamma_d, y, S, nullptr, ind_start, ind_stop, nGrid, grid, sigma, nullptr);
+  const double *line[5] = {nu, gamma_d, y, S, nullptr};
+  return lineshape_xsec_run("mom_voigt_xsec", device, 0, nLines, line, nullptr, ind_start, ind_stop, nGrid, grid, sigma, nullptr);
 }
 
 extern "C" int mom_voigt_xsec_dual(int device, int nLines, const double *nu, const double *gamma_d, const double *y, const double *S,
@@ -673,9 +865,40 @@ extern "C" int mom_voigt_xsec_dual(int device, int nLines, const double *nu, con
     mom_set_global_error("mom_voigt_xsec_dual: bad argument (null pointer or non-positive size)");
     return MOM_EINVAL;
   }
-  const double *dpart[4] = {dnu, dgamma_d, dy, dS};
-  return voigt_xsec_run("mom_voigt_xsec_dual", device, nLines, nu, gamma_d, y, S, dpart, ind_start, ind_stop, nGrid, grid, sigma, dsigma);
+  const double *line[5] = {nu, gamma_d, y, S, nullptr}, *dpart[5] = {dnu, dgamma_d, dy, dS, nullptr};
+  return lineshape_xsec_run("mom_voigt_xsec_dual", device, 0, nLines, line, dpart, ind_start, ind_stop, nGrid, grid, sigma, dsigma);
 }
 
-// GPU time of the k_voigt / k_voigt_dual launch of the last mom_voigt_xsec / mom_voigt_xsec_dual call on this thread (HIP events), ms.
+// line_shape!(A, grid, nu, gamma_d, gamma_l, y, S, broadening, CEF) (compute_absorption_cross_section.jl:167-183) summed over the
+// lines: mom_voigt_xsec for any absorption model
+extern "C" int mom_lineshape_xsec(int device, int broadening, int cef, int nLines, const double *nu, const double *gamma_d,
+                                  const double *gamma_l, const double *y, const double *S, const int *ind_start, const int *ind_stop,
+                                  int nGrid, const double *grid, double *sigma) {
+  std::string err;
+  const int shape = mom_line_shape("mom_lineshape_xsec", broadening, cef, &err);
+  if (shape < 0) {
+    mom_set_global_error(err.c_str());
+    return MOM_EINVAL;
+  }
+  const double *line[5] = {nu, gamma_d, y, S, gamma_l};
+  return lineshape_xsec_run("mom_lineshape_xsec", device, shape, nLines, line, nullptr, ind_start, ind_stop, nGrid, grid, sigma, nullptr);
+}
+
+extern "C" int mom_lineshape_xsec_dual(int device, int broadening, int cef, int nLines, const double *nu, const double *gamma_d,
+                                       const double *gamma_l, const double *y, const double *S, const double *dnu,
+                                       const double *dgamma_d, const double *dgamma_l, const double *dy, const double *dS,
+                                       const int *ind_start, const int *ind_stop, int nGrid, const double *grid, double *sigma,
+                                       double *dsigma) {
+  std::string err;
+  const int shape = mom_line_shape("mom_lineshape_xsec_dual", broadening, cef, &err);
+  if (shape < 0 || !dsigma) {
+    mom_set_global_error(shape < 0 ? err.c_str() : "mom_lineshape_xsec_dual: bad argument (null pointer or non-positive size)");
+    return MOM_EINVAL;
+  }
+  const double *line[5] = {nu, gamma_d, y, S, gamma_l}, *dpart[5] = {dnu, dgamma_d, dy, dS, dgamma_l};
+  return lineshape_xsec_run("mom_lineshape_xsec_dual", device, shape, nLines, line, dpart, ind_start, ind_stop, nGrid, grid, sigma,
+                            dsigma);
+}
+
+// GPU time of the line-shape launch of the last mom_voigt_xsec / mom_lineshape_xsec call (or Dual run) on this thread (HIP events), ms.
 extern "C" double mom_voigt_last_kernel_ms(void) { return v_last_ms; }
