@@ -560,6 +560,8 @@ int mom_timers(mom_t *h, double *ms, int n, int *kernel_launches);
  *                         Without bit 1 it covers only the latter (edges 52 and 56).  A bit that is off = the kernel that
  *                         multiplies everything.  The terms left out are exact zeros: stored values, series lengths and resume
  *                         decisions do not depend on the option (at most the sign of a zero does).
+ *   MOM_OPT_LUT_BATCH     (p, T) nodes that mom_lut_build fills per pair of launches (default 0 = 64): the per-line prefactor block
+ *                         of a batch takes nodes x lines.  Nodes are independent: the table does not depend on it by a bit.
  */
 int mom_set_option(mom_t *h, int option, int value);
 
@@ -570,7 +572,56 @@ int mom_strip2_resumed(mom_t *h, int *units, int *left);
 enum { MOM_OPT_INVERSE = 0, MOM_OPT_FORCE_GENERIC = 1, MOM_OPT_M0_REDUCTION = 2, MOM_OPT_SMALL_WG = 3, MOM_OPT_STAGGER = 4,
        MOM_OPT_SMALL_N = 5, MOM_OPT_LAYER_SWEEP = 6, MOM_OPT_STRIP_PAD = 7, MOM_OPT_LEAN = 8, MOM_OPT_OVERLAP = 9,
        MOM_OPT_RRS_KERNELS = 10, MOM_OPT_DUAL_WORKSPACE_MB = 11, MOM_OPT_STRIP2 = 12, MOM_OPT_STRIP2_SCHED = 13,
-       MOM_OPT_ZERO_SKIP = 14 };
+       MOM_OPT_ZERO_SKIP = 14, MOM_OPT_LUT_BATCH = 15 };
+
+/* ---- The InterpolationModel: cross sections computed once on a (nu, p, T) grid and kept on the device as a cubic B-spline
+ * interpolant -- make_interpolation_model (make_model_helpers.jl:55-99) and compute_absorption_cross_section(model::InterpolationModel,
+ * grid, p, T) (compute_absorption_cross_section.jl:139-159): Interpolations.jl's interpolate(A, BSpline(Cubic(Line(OnGrid()))))
+ * scaled to the model's three ranges (first, step, length).  Per axis of n nodes the interpolant has n + 2 coefficients c_0 .. c_{n+1}
+ * with (c_{i-1} + 4 c_i + c_{i+1}) / 6 = f_i at the nodes and zero second derivative at the first and the last node (the natural cubic
+ * spline).  A point is evaluated at x = (value - first) / step + 1 -- one subtraction, one division --, i = clamp(floor(x), 1, n - 1),
+ * delta = x - i, with the cubic B-spline weights of c_{i-1} .. c_{i+2}; the 3-D value is the tensor product.  There is no
+ * extrapolation: a nu, p or T outside [first, last] of its axis is MOM_EINVAL, with a text that names the axis, the value and the
+ * range; the end points are inside.  A table belongs to the handle, is named by a small integer id and is Float64 on every handle;
+ * any number of tables live at once (one per absorber).  Not built: the ABSCO method of make_interpolation_model (:112-), whose
+ * interpolant is mixed linear / quadratic -- a table derived from ABSCO on the host goes through mom_lut_set_table --, and
+ * wavelength_flag.
+ *   mom_lut_create         an empty table on the three ranges; an axis of fewer than 3 nodes or a step <= 0: MOM_EINVAL.  *lut = its id
+ *   mom_lut_set_table      takes sigma [nNu, nP, nT] (nu fastest: the reference's cs_matrix) from the host and prefilters it on
+ *                          the device: the route of a model loaded from disk
+ *   mom_lut_build          make_model_helpers.jl:82-91 on the device: sigma at every node (p_i, T_j) from the resident line table
+ *                          (mom_absorption_set_lines, selected against the model's nu grid) under the handle's absorption model
+ *                          (mom_absorption_set_model), by the kernels of mom_voigt_tau_abs_profile with the nodes as layers and
+ *                          factor 1 -- column (i, j) of the table is bitwise what that call adds to a zeroed tau_abs[:, z] --, then the
+ *                          prefilter.  The nodes run in batches (MOM_OPT_LUT_BATCH).  The handle's tau_abs, dtau_abs and spectral grid
+ *                          are not touched.  Errors as mom_voigt_tau_abs_profile (the TIPS-2017 range of the T axis included).
+ *                          gpu_ms: NULL or two doubles, the HIP-event times of the fill and of the prefilter.
+ *   mom_lut_get_table, mom_lut_get_coefficients   test access: sigma [nNu, nP, nT] and the coefficients [nNu + 2, nP + 2, nT + 2]
+ *   mom_lut_xsec           sigma [n] at the points nu [n] (any values inside the nu range, in any order) and one (p, T).  J: NULL, or
+ *                          [n, 2] column-major like mom_voigt_xsec_dual's dsigma -- the Jacobian with respect to (p, T) of
+ *                          absorption_cross_section(...; autodiff = true) (autodiff_helper.jl:17-51): ForwardDiff through the weights,
+ *                          floor and clamp taken on the values.  sigma does not depend on whether J is asked for (bitwise).
+ *   mom_lut_tau_abs_profile        tau_abs[:, z] += sigma_lut(grid; p[z], T[z]) * factor[z] for layers 1..Nz on the grid of
+ *                          mom_absorption_begin, all layers in one launch; accumulating like mom_voigt_tau_abs_profile, so it adds
+ *                          to whatever absorbers the table holds already, line-by-line or interpolated.
+ *   mom_lut_tau_abs_profile_dual   the same, and adds d_k sigma * factor into dtau_abs[:, z, k] (mom_absorption_get_partials): the
+ *                          table is allocated and zeroed by the first Dual call after mom_absorption_begin, and a value call counts
+ *                          as an absorber with zero partials.
+ *   mom_lut_destroy        frees the table; its id may be handed out again.
+ * A wrong or destroyed id: MOM_EINVAL.  Evaluating a table that has no coefficients yet: MOM_ESTATE.  A profile call without
+ * mom_absorption_begin (with the grid): MOM_ESTATE. */
+int mom_lut_create(mom_t *h, int nNu, double nu_first, double nu_step, int nP, double p_first, double p_step, int nT, double t_first,
+                   double t_step, int *lut);
+int mom_lut_set_table(mom_t *h, int lut, const double *sigma);
+int mom_lut_build(mom_t *h, int lut, double vmr, double wing_cutoff, double *gpu_ms);
+int mom_lut_get_table(mom_t *h, int lut, double *sigma);
+int mom_lut_get_coefficients(mom_t *h, int lut, double *c);
+int mom_lut_xsec(mom_t *h, int lut, int n, const double *nu, double p, double T, double *sigma, double *J);
+int mom_lut_tau_abs_profile(mom_t *h, int lut, int Nz, const double *pressure, const double *temperature, const double *factor,
+                            double *gpu_ms);
+int mom_lut_tau_abs_profile_dual(mom_t *h, int lut, int Nz, const double *pressure, const double *temperature, const double *factor,
+                                 double *gpu_ms);
+int mom_lut_destroy(mom_t *h, int lut);
 
 /* ---- Voigt line-by-line cross section --------------------------------------------------
  * compute_absorption_cross_section(model::HitranModel, grid, p, T)

@@ -373,3 +373,85 @@ function lineshape_xsec_dual(arch::MI355X, broadening, CEF, ν, γ_d, γ_l, y, S
     return result, derivs
 end
 # <<< absorption
+
+# >>> interpolation
+"""
+The InterpolationModel on a handle (src/Absorption/types.jl; make_model_helpers.jl:55-99): `id` names the table of cubic B-spline
+coefficients resident on the device, the three grids are the model's ranges.
+"""
+struct MomInterpolationModel
+    h::MomHandle
+    id::Cint
+    mol::Int
+    iso::Int
+    ν_grid::AbstractRange
+    p_grid::AbstractRange
+    t_grid::AbstractRange
+end
+
+function lut_create(h::MomHandle, ν_grid::AbstractRange, p_grid::AbstractRange, t_grid::AbstractRange)
+    id = Ref{Cint}(-1)
+    MomCore.mom_lut_create!(h.ptr, length(ν_grid), Float64(first(ν_grid)), Float64(step(ν_grid)), length(p_grid), Float64(first(p_grid)),
+                            Float64(step(p_grid)), length(t_grid), Float64(first(t_grid)), Float64(step(t_grid)), id)
+    return id[]
+end
+
+"""
+make_interpolation_model(hitran, broadening, ν_grid, p_grid, t_grid; wing_cutoff, vmr, CEF) with architecture isa MI355X: the loop
+over the (p, T) nodes (make_model_helpers.jl:82-88) and `interpolate(cs_matrix, BSpline(Cubic(Line(OnGrid()))))` (:91) run on the
+device from the resident line table; only the line table crosses the bus.
+"""
+function make_interpolation_model(h::MomHandle, hitran, tips, broadening, ν_grid::AbstractRange, p_grid::AbstractRange,
+                                  t_grid::AbstractRange; wing_cutoff = 40, vmr = 0, CEF = HumlicekWeidemann32SDErrorFunction())
+    broadening isa Voigt || (CEF = HumlicekWeidemann32SDErrorFunction())
+    MomCore.mom_absorption_set_model!(h.ptr, momcore_broadening(broadening), momcore_cef(CEF))
+    keep = (first(ν_grid) - wing_cutoff) .< hitran.νᵢ .< (last(ν_grid) + wing_cutoff)
+    MomCore.mom_absorption_set_lines!(h.ptr, count(keep), hitran.νᵢ[keep], hitran.Sᵢ[keep], hitran.γ_air[keep], hitran.γ_self[keep],
+                                      hitran.E″[keep], hitran.n_air[keep], hitran.δ_air[keep], tips.sqrt_mol_weight[keep],
+                                      tips.iso_index[keep], tips.nIso, tips.nTmax, tips.nT, tips.T, tips.Q, tips.z)
+    id = lut_create(h, ν_grid, p_grid, t_grid)
+    MomCore.mom_lut_build!(h.ptr, id, Float64(vmr), Float64(wing_cutoff), C_NULL)
+    iso = all(x -> x == hitran.iso[1], hitran.iso) ? hitran.iso[1] : -1
+    return MomInterpolationModel(h, id, hitran.mol[1], iso, ν_grid, p_grid, t_grid)
+end
+
+"""An InterpolationModel of a finished cs_matrix [nν, np, nT] (loaded from disk, or derived from ABSCO on the host)."""
+function interpolation_model_from_table(h::MomHandle, cs_matrix::Array{Float64,3}, ν_grid, p_grid, t_grid, mol, iso)
+    id = lut_create(h, ν_grid, p_grid, t_grid)
+    MomCore.mom_lut_set_table!(h.ptr, id, cs_matrix)
+    return MomInterpolationModel(h, id, mol, iso, ν_grid, p_grid, t_grid)
+end
+
+"""compute_absorption_cross_section(model::InterpolationModel, grid, p, T) (compute_absorption_cross_section.jl:139-159)."""
+function compute_absorption_cross_section(model::MomInterpolationModel, grid, pressure::Real, temperature::Real)
+    ν = collect(Float64, grid);  σ = zeros(Float64, length(ν))
+    MomCore.mom_lut_xsec!(model.h.ptr, model.id, length(ν), ν, Float64(pressure), Float64(temperature), σ, C_NULL)
+    return σ
+end
+
+"""absorption_cross_section(model, grid, p, T; autodiff = true) (autodiff_helper.jl:17-51): (σ, J[nGrid, 2])."""
+function absorption_cross_section_dual(model::MomInterpolationModel, grid, pressure::Real, temperature::Real)
+    ν = collect(Float64, grid);  σ = zeros(Float64, length(ν));  J = zeros(Float64, length(ν), 2)
+    MomCore.mom_lut_xsec!(model.h.ptr, model.id, length(ν), ν, Float64(pressure), Float64(temperature), σ, J)
+    return σ, J
+end
+
+"""
+compute_absorption_profile! (atmo_prof.jl:427-449) for an InterpolationModel: τ_abs[:, iz] += σ(grid; p[iz], T[iz]) vcd_dry[iz] vmr for
+all layers in one launch, on the grid of mom_absorption_begin (`begin_table = false` adds another absorber to the same table).
+"""
+function compute_absorption_profile!(h::MomHandle, grid, model::MomInterpolationModel, p_full, T, vmr, vcd_dry; dual::Bool = false,
+                                     begin_table::Bool = true)
+    Nz = length(p_full)
+    begin_table && MomCore.mom_absorption_begin!(h.ptr, Nz, collect(Float64, grid))
+    ms = Ref{Cdouble}(0)
+    if dual
+        MomCore.mom_lut_tau_abs_profile_dual!(h.ptr, model.id, Nz, p_full, T, vcd_dry .* vmr, ms)
+    else
+        MomCore.mom_lut_tau_abs_profile!(h.ptr, model.id, Nz, p_full, T, vcd_dry .* vmr, ms)
+    end
+    return ms[]
+end
+
+destroy!(model::MomInterpolationModel) = MomCore.mom_lut_destroy!(model.h.ptr, model.id)
+# <<< interpolation

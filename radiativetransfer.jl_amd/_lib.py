@@ -41,6 +41,7 @@ MOM_OPT_DUAL_WORKSPACE_MB = 11   # operator workspace of mom_rt_run_dual (0: 60 
 MOM_OPT_STRIP2 = 12              # N = 52, 56, 60 on the two-buffer 4-wave image first (1, default), 0 = the 8-wave image only
 MOM_OPT_STRIP2_SCHED = 13        # its scheduling, a mask (1, default): 1 = shared unit queue, 2 = asymmetric chain priority (off: measured slower); 0 = neither
 MOM_OPT_ZERO_SKIP = 14           # leave out the exact-zero products of the zero-weight trailing streams, a mask (7, default): 1 = quad-block image (blocks), 2 = two-buffer strip image (k-steps), 4 = two-buffer strip image (blocks of four rows of a partly live row tile); 0 = every product
+MOM_OPT_LUT_BATCH = 15           # (p, T) nodes per batch of mom_lut_build (0, default: 64); the table does not depend on it
 
 # the absorption model (mom_absorption_set_model, mom_lineshape_xsec): HitranModel.broadening, HitranModel.CEF
 BROADENING_VOIGT, BROADENING_DOPPLER, BROADENING_LORENTZ = 0, 1, 2
@@ -133,6 +134,16 @@ SIGNATURES = {
     "mom_timers": (C.c_int, [c_h, c_dp, C.c_int, c_ip]),
     "mom_set_option": (C.c_int, [c_h, C.c_int, C.c_int]),
     "mom_strip2_resumed": (C.c_int, [c_h, c_ip, c_ip]),
+    "mom_lut_create": (C.c_int, [c_h, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double,
+                                 c_ip]),
+    "mom_lut_set_table": (C.c_int, [c_h, C.c_int, c_dp]),
+    "mom_lut_build": (C.c_int, [c_h, C.c_int, C.c_double, C.c_double, c_dp]),
+    "mom_lut_get_table": (C.c_int, [c_h, C.c_int, c_dp]),
+    "mom_lut_get_coefficients": (C.c_int, [c_h, C.c_int, c_dp]),
+    "mom_lut_xsec": (C.c_int, [c_h, C.c_int, C.c_int, c_dp, C.c_double, C.c_double, c_dp, c_dp]),
+    "mom_lut_tau_abs_profile": (C.c_int, [c_h, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp]),
+    "mom_lut_tau_abs_profile_dual": (C.c_int, [c_h, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp]),
+    "mom_lut_destroy": (C.c_int, [c_h, C.c_int]),
     "mom_voigt_xsec": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip, C.c_int, c_dp, c_dp]),
     "mom_voigt_xsec_dual": (C.c_int, [C.c_int, C.c_int] + [c_dp] * 8 + [c_ip, c_ip, C.c_int, c_dp, c_dp, c_dp]),
     "mom_lineshape_xsec": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [c_dp] * 5 + [c_ip, c_ip, C.c_int, c_dp, c_dp]),
@@ -508,6 +519,67 @@ class Handle:
         d = [np.empty(2 * n) for _ in range(4)]
         self.check(self.lib.mom_absorption_get_prefactor_partials(self._h, n, *[dp(x) for x in d]))
         return [x.reshape(2, n).T.copy() for x in d]
+
+    # -- the InterpolationModel: sigma(nu, p, T) tables resident on the device (mom_lut_*) ----------------------
+    def lut_create(self, nu_range, p_range, t_range) -> int:
+        """mom_lut_create: each range is (first, step, length); returns the table's id."""
+        (n0, s0, l0), (n1, s1, l1), (n2, s2, l2) = nu_range, p_range, t_range
+        lut = C.c_int(-1)
+        self.check(self.lib.mom_lut_create(self._h, int(l0), float(n0), float(s0), int(l1), float(n1), float(s1), int(l2), float(n2),
+                                           float(s2), C.byref(lut)))
+        self._lut_shape = getattr(self, "_lut_shape", {})
+        self._lut_shape[lut.value] = (int(l0), int(l1), int(l2))
+        return lut.value
+
+    def _lut_dims(self, lut):
+        return getattr(self, "_lut_shape", {}).get(int(lut), (1, 1, 1))   # an unknown id: the library reports it
+
+    def lut_set_table(self, lut, sigma):
+        """sigma: numpy [nNu, nP, nT] (the reference's cs_matrix); uploaded nu fastest and prefiltered on the device."""
+        s = np.asarray(sigma, dtype=np.float64)
+        assert s.shape == self._lut_dims(lut), (s.shape, self._lut_dims(lut))
+        flat = np.ascontiguousarray(s.transpose(2, 1, 0)).reshape(-1)
+        self.check(self.lib.mom_lut_set_table(self._h, int(lut), dp(flat)))
+
+    def lut_build(self, lut, vmr=0.0, wing_cutoff=40.0):
+        """mom_lut_build from the resident line table; returns (fill ms, prefilter ms) of the GPU."""
+        ms = np.zeros(2)
+        self.check(self.lib.mom_lut_build(self._h, int(lut), float(vmr), float(wing_cutoff), dp(ms)))
+        return float(ms[0]), float(ms[1])
+
+    def lut_get_table(self, lut):
+        n = self._lut_dims(lut)
+        out = np.empty(n[0] * n[1] * n[2])
+        self.check(self.lib.mom_lut_get_table(self._h, int(lut), dp(out)))
+        return out.reshape(n[2], n[1], n[0]).transpose(2, 1, 0).copy()
+
+    def lut_get_coefficients(self, lut):
+        """The padded cubic B-spline coefficients as numpy [nNu + 2, nP + 2, nT + 2]."""
+        n = [k + 2 for k in self._lut_dims(lut)]
+        out = np.empty(n[0] * n[1] * n[2])
+        self.check(self.lib.mom_lut_get_coefficients(self._h, int(lut), dp(out)))
+        return out.reshape(n[2], n[1], n[0]).transpose(2, 1, 0).copy()
+
+    def lut_xsec(self, lut, nu, p, T, jacobian=False):
+        """mom_lut_xsec: sigma [n], or with jacobian=True (sigma, J [n, 2]) with column 0 = d/dp and 1 = d/dT."""
+        nu = f64(nu).reshape(-1)
+        sigma, J = np.empty(nu.size), (np.empty(2 * nu.size) if jacobian else None)
+        self.check(self.lib.mom_lut_xsec(self._h, int(lut), int(nu.size), dp(nu), float(p), float(T), dp(sigma),
+                                         dp(J) if jacobian else None))
+        return (sigma, J.reshape(2, nu.size).T.copy()) if jacobian else sigma
+
+    def lut_tau_abs_profile(self, lut, p, T, factor, dual=False) -> float:
+        """mom_lut_tau_abs_profile(_dual) for layers 1..len(p); returns the GPU time of the launch in ms."""
+        p, T, f = f64(p), f64(T), f64(factor)
+        assert p.size == T.size == f.size
+        ms = np.zeros(1)
+        fn = self.lib.mom_lut_tau_abs_profile_dual if dual else self.lib.mom_lut_tau_abs_profile
+        self.check(fn(self._h, int(lut), int(p.size), dp(p), dp(T), dp(f), dp(ms)))
+        return float(ms[0])
+
+    def lut_destroy(self, lut):
+        self.check(self.lib.mom_lut_destroy(self._h, int(lut)))
+        getattr(self, "_lut_shape", {}).pop(int(lut), None)
 
     def scene_set_optics(self, Nz, M, tau_rayl, varpi_rayl, tau_aer, omega_aer, ft_aer, Zpp, Zmp, albedo, node, cos_mphi,
                          sin_mphi):

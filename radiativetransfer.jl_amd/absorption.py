@@ -354,12 +354,116 @@ def _sqrt_weights(h: HitranTable, keep, mol_weights: Optional[dict] = None) -> n
     return sqw
 
 
-def absorption_cross_section(h: HitranTable, grid, pressure: float, temperature: float, autodiff: bool = False, vmr: float = 0.0,
+# ------------------------------------------------------------------------------------------
+# The InterpolationModel (Absorption/types.jl, make_model_helpers.jl:55-110): σ on a (ν, p, T) grid of ranges, kept on the device
+# as the coefficients of a cubic B-spline interpolant (csrc/mom_lut.hip) and evaluated there.
+# ------------------------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class Range:
+    """first : step : first + step (length - 1), Julia's AbstractRange as the model's grids are given"""
+    first: float
+    step: float
+    length: int
+
+    @property
+    def last(self) -> float:
+        return self.first + self.step * (self.length - 1)
+
+    def values(self) -> np.ndarray:
+        return self.first + self.step * np.arange(self.length, dtype=np.float64)
+
+    def astuple(self):
+        return float(self.first), float(self.step), int(self.length)
+
+
+def _as_range(r) -> Range:
+    return r if isinstance(r, Range) else Range(*r)
+
+
+@dataclass
+class InterpolationModel:
+    """InterpolationModel(itp, mol, iso, ν_grid, p_grid, t_grid) (Absorption/types.jl): `itp` is table `id` of handle `h`
+    (mom_lut_*); iso = -1 for a table of mixed isotopologues."""
+    h: object
+    id: int
+    mol: int
+    iso: int
+    ν_grid: Range
+    p_grid: Range
+    t_grid: Range
+    build_ms: Optional[tuple] = None     # GPU time (fill, prefilter) of make_interpolation_model
+
+    def close(self):
+        """mom_lut_destroy; the handle frees whatever is left when it closes"""
+        if self.id is not None:
+            self.h.lut_destroy(self.id)
+            self.id = None
+
+    def _check_inside(self, ν, p, T):
+        """the scaled interpolant has no extrapolation (compute_absorption_cross_section.jl:155-158 raises a BoundsError)"""
+        for name, rng, v in (("nu", self.ν_grid, ν), ("p", self.p_grid, p), ("T", self.t_grid, T)):
+            v = np.atleast_1d(np.asarray(v, dtype=np.float64))
+            bad = ~((v >= rng.first) & (v <= rng.last))
+            if np.any(bad):
+                raise ValueError(f"{name} = {v[bad][0]!r} is outside the InterpolationModel's {name} axis [{rng.first}, {rng.last}]")
+
+
+def interpolation_model_from_table(h, σ, ν_grid, p_grid, t_grid, mol: int = -1, iso: int = -1) -> InterpolationModel:
+    """An InterpolationModel of a finished table σ [nν, np, nT] (the reference's cs_matrix): uploaded and prefiltered on the device
+    (mom_lut_set_table).  The route of a model loaded from disk or derived from ABSCO on the host."""
+    ν_grid, p_grid, t_grid = (_as_range(r) for r in (ν_grid, p_grid, t_grid))
+    lut = h.lut_create(ν_grid.astuple(), p_grid.astuple(), t_grid.astuple())
+    h.lut_set_table(lut, σ)
+    return InterpolationModel(h, lut, int(mol), int(iso), ν_grid, p_grid, t_grid)
+
+
+def make_interpolation_model(h, table: HitranTable, broadening, ν_grid, p_grid, t_grid, wing_cutoff: float = 40.0, vmr: float = 0.0,
+                             cef="HumlicekWeidemann32SDErrorFunction()") -> InterpolationModel:
+    """make_interpolation_model(hitran, broadening, ν_grid, p_grid, t_grid; wing_cutoff, vmr, CEF) (make_model_helpers.jl:55-99) on
+    handle `h`: the lines inside the padded ν grid become the handle's resident line table, `broadening` / `cef` its absorption
+    model, and mom_lut_build fills σ at every (p, T) node with the line-shape kernels and prefilters it -- nothing but the line
+    table crosses the bus.  The grids are Range(first, step, length) (or such tuples)."""
+    ν_grid, p_grid, t_grid = (_as_range(r) for r in (ν_grid, p_grid, t_grid))
+    h.absorption_set_model(*absorption_model(broadening, cef))
+    resident_line_table(h, table, ν_grid.values(), wing_cutoff)
+    lut = h.lut_create(ν_grid.astuple(), p_grid.astuple(), t_grid.astuple())
+    try:
+        ms = h.lut_build(lut, vmr, wing_cutoff)
+    except Exception:
+        h.lut_destroy(lut)
+        raise
+    iso = int(table.iso[0]) if np.all(table.iso == table.iso[0]) else -1          # :94-95
+    return InterpolationModel(h, lut, int(table.mol[0]), iso, ν_grid, p_grid, t_grid, build_ms=ms)
+
+
+def save_interpolation_model(model: InterpolationModel, path) -> None:
+    """save_interpolation_model (make_model_helpers.jl:101-104) as an .npz (in place of JLD2): the raw table and the three ranges."""
+    with open(path, "wb") as fh:
+        np.savez(fh, table=model.h.lut_get_table(model.id), nu_range=np.array(model.ν_grid.astuple()),
+                 p_range=np.array(model.p_grid.astuple()), t_range=np.array(model.t_grid.astuple()), mol=model.mol, iso=model.iso)
+
+
+def load_interpolation_model(h, path) -> InterpolationModel:
+    """load_interpolation_model (make_model_helpers.jl:106-110) onto handle `h`: the saved table is prefiltered again on the device."""
+    with np.load(path) as f:
+        rng = lambda k: Range(float(f[k][0]), float(f[k][1]), int(f[k][2]))
+        return interpolation_model_from_table(h, f["table"], rng("nu_range"), rng("p_range"), rng("t_range"), int(f["mol"]),
+                                              int(f["iso"]))
+
+
+def absorption_cross_section(h, grid, pressure: float, temperature: float, autodiff: bool = False, vmr: float = 0.0,
                              wing_cutoff: float = 40.0, device: int = 0, broadening="Voigt()",
                              cef="HumlicekWeidemann32SDErrorFunction()"):
     """absorption_cross_section(model, grid, p, T; autodiff) (autodiff_helper.jl:17-51): σ[nGrid], or with autodiff=True
     (σ, J[nGrid, 2]) -- the Jacobian with respect to x = [p, T] that ForwardDiff.jacobian! returns as result.derivs[1],
-    from the Dual run of the line-shape kernel (mom_voigt_xsec_dual; mom_lineshape_xsec_dual for another absorption model)."""
+    from the Dual run of the line-shape kernel (mom_voigt_xsec_dual; mom_lineshape_xsec_dual for another absorption model).
+    `h` is a HitranTable (line by line, the keywords apply) or an InterpolationModel (mom_lut_xsec on the model's handle: the grid
+    is any set of wavenumbers inside the model's ν range; a ν, p or T outside the model's axes raises ValueError)."""
+    if isinstance(h, InterpolationModel):
+        grid = np.asarray(grid, dtype=np.float64)
+        h._check_inside(grid, pressure, temperature)
+        return h.h.lut_xsec(h.id, grid, pressure, temperature, jacobian=autodiff)
     model = absorption_model(broadening, cef)
     if not autodiff:
         return compute_absorption_cross_section(h, grid, pressure, temperature, vmr, wing_cutoff, device=device, broadening=broadening,
@@ -426,7 +530,7 @@ def resident_line_table(h, table: HitranTable, grid, wing_cutoff: float = 40.0):
     return int(mol.size)
 
 
-def compute_absorption_profile(h, table: HitranTable, grid, p_full, T, vcd_dry, vmr, wing_cutoff: float = 40.0,
+def compute_absorption_profile(h, table, grid, p_full, T, vcd_dry, vmr, wing_cutoff: float = 40.0,
                                model_vmr: float = 0.0, qratio=None, begin: bool = True, device_prefactors: bool = False,
                                layer_by_layer: bool = False, dual: bool = False, broadening="Voigt()",
                                cef="HumlicekWeidemann32SDErrorFunction()"):
@@ -442,7 +546,12 @@ def compute_absorption_profile(h, table: HitranTable, grid, p_full, T, vcd_dry, 
     respect to each layer's pressure and temperature accumulate in the handle's dtau_abs table (absorption_get_partials).
     `broadening` / `cef` (absorption_model) become the handle's absorption model (mom_absorption_set_model), which the
     device-prefactor entry points follow; on the host route another model than the default goes through
-    mom_lineshape_tau_abs(_dual), which takes γ_l."""
+    mom_lineshape_tau_abs(_dual), which takes γ_l.
+    `table` may be an InterpolationModel of this handle instead of a HitranTable: all layers in one launch of the table's evaluation
+    kernel (mom_lut_tau_abs_profile; dual=True: its Dual run), accumulating into the same τ_abs / dτ_abs tables -- only `begin` and
+    `dual` of the keywords apply; returns the GPU time in ms."""
+    if isinstance(table, InterpolationModel):
+        return _interpolated_profile(h, table, grid, p_full, T, vcd_dry, vmr, begin, dual)
     model = absorption_model(broadening, cef)
     h.absorption_set_model(*model)
     p_full, T, vcd_dry = (np.asarray(x, dtype=np.float64) for x in (p_full, T, vcd_dry))
@@ -483,6 +592,22 @@ def compute_absorption_profile(h, table: HitranTable, grid, p_full, T, vcd_dry, 
             continue
         pf = line_prefactors(table, grid, p_full[iz], T[iz], vmr=model_vmr, wing_cutoff=wing_cutoff, qratio=qratio)
         h.voigt_tau_abs(iz + 1, pf.ν, pf.γ_d, pf.y, pf.S, pf.ind_start, pf.ind_stop, vcd_dry[iz] * vmr_arr[iz])
+
+
+def _interpolated_profile(h, model: InterpolationModel, grid, p_full, T, vcd_dry, vmr, begin: bool, dual: bool) -> float:
+    """compute_absorption_profile for an InterpolationModel: one launch for all layers (mom_lut_tau_abs_profile, or its Dual run,
+    which also adds into the handle's dtau_abs table); returns its GPU time in ms.  The line-by-line keywords do not apply."""
+    if model.h is not h:
+        raise ValueError("the InterpolationModel lives on another handle: its table is resident there")
+    p_full, T, vcd_dry = (np.asarray(x, dtype=np.float64) for x in (p_full, T, vcd_dry))
+    Nz = p_full.size
+    assert T.size == Nz and vcd_dry.size == Nz
+    vmr_arr = np.full(Nz, float(vmr)) if np.ndim(vmr) == 0 else np.asarray(vmr, dtype=np.float64)
+    assert vmr_arr.size == Nz, "Length of VMR array has to match profile size or be uniform"
+    model._check_inside(grid, p_full, T)
+    if begin:
+        h.absorption_begin(Nz, grid)
+    return h.lut_tau_abs_profile(model.id, p_full, T, vcd_dry * vmr_arr, dual=dual)
 
 
 def synthetic_o2a_lines(n_lines: int = 300, ν_lo: float = 12903.0, ν_hi: float = 13245.0, seed: int = 1234) -> HitranTable:

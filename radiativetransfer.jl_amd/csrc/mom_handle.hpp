@@ -18,6 +18,17 @@
 
 namespace momr { struct State; }  // mom_rrs.hpp
 
+// One InterpolationModel of the handle (mom_lut.hip): sigma on a (nu, p, T) grid of ranges, axis 0 = nu, 1 = p, 2 = T
+struct MomLut {
+  bool live = false;                // the id is handed out
+  int n[3] = {};                    // nodes per axis
+  double first[3] = {}, step[3] = {};
+  bool has_table = false, has_coef = false;
+  MomDevBuf<double> d_table;        // sigma [nNu, nP, nT], nu fastest (the reference's cs_matrix)
+  MomDevBuf<double> d_coef;         // the padded cubic B-spline coefficients [nNu + 2, nP + 2, nT + 2]
+  MomDevBuf<double> d_nu;           // the model's nu grid [nNu] (mom_lut_build's spectral grid)
+};
+
 // The resident scene's arrays and counts (d_mu ... d_scratch, Nz, K, nVza, scene_M, surf_kind, albedo, nd, iface) are the base:
 // MomSceneBufs, mom_host.hpp -- the declaration the Float32 scene shares
 struct mom_handle : MomSceneBufs<double> {
@@ -124,6 +135,15 @@ struct mom_handle : MomSceneBufs<double> {
   MomDevBuf<double> d_lt;   // one allocation behind lt's double arrays
   MomDevBuf<int> d_lt_i;    // iso index [nLines] | knots per isotopologue [nIso] | unsorted flag [1]
   double lt_Tmin = 0.0, lt_Tmax = 0.0;
+  // InterpolationModels (mom_lut_*): the id of a table is its index here; a destroyed slot is handed out again
+  std::vector<MomLut> luts;
+  MomDevBuf<double> d_lut_cp;    // the Thomas factors of the prefilter
+  MomDevBuf<double> d_lut_prm;   // per-layer weight blocks of an evaluation
+  MomDevBuf<double> d_lut_io;    // mom_lut_xsec: nu | sigma | J
+  int opt_lut_batch = 0;         // MOM_OPT_LUT_BATCH: (p, T) nodes per batch of mom_lut_build (0: 64)
+  // the spectral grid as mom_absorption_begin saw it: smallest and largest value, 1 ascending / -1 descending / 0 neither
+  double grid_min = 0.0, grid_max = 0.0;
+  int grid_order = 0;
   std::string err;
 };
 

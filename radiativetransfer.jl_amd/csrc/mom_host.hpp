@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <map>
 #include <string>
 #include <type_traits>
@@ -252,6 +253,12 @@ struct MomLineTable {
   const int *nT;                                                      // [nIso] knots per isotopologue
   const double *tT, *tQ, *tZ;                                         // [nIso, nTmax] knots, values, second derivatives
 };
+// the scalar part of gamma_d = (cSqrt2Ln2 / cc_) sqrt(cBolts_ / cMassMol) sqrt(T) nu_0 / sqrt(mol_weight)
+// (compute_absorption_cross_section.jl:87-88), the `cgd` the profile kernels take per layer
+inline double mom_doppler_scale(double T) {
+  const double cg = (1.1774100225 / 2.99792458e8) * std::sqrt(1.3806503e-23 / 1.66053873e-27);
+  return cg * std::sqrt(T);
+}
 // voigt.hip: per-line prefactors of one (p, T) on the device; *unsorted is set when the windows are not monotone
 // every layer of a profile: prefactors of all (layer, line) pairs, then the line shapes of all (layer, grid point) pairs;
 // pf = [nu | gamma_d | y | S | the two window arrays as ints | gamma_l][Nz][cap]

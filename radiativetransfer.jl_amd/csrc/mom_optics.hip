@@ -18,6 +18,18 @@ extern "C" int mom_absorption_begin(mom_t *h, int Nz, const double *grid) {
   h->abs_Nz = Nz;
   if (grid) {
     HIPCHK(h, mom_upload(h->d_grid, grid, S, h->stream));
+    // what mom_lut_tau_abs_profile asks of the grid: its extent against the table's nu axis, and whether it is monotone
+    bool up = true, down = true;
+    h->grid_min = h->grid_max = grid[0];
+    for (size_t n = 1; n < S; ++n) {
+      up = up && grid[n] >= grid[n - 1];
+      down = down && grid[n] <= grid[n - 1];
+      h->grid_min = std::min(h->grid_min, grid[n]);
+      h->grid_max = std::max(h->grid_max, grid[n]);
+    }
+    for (size_t n = 0; n < S; ++n)
+      if (grid[n] != grid[n]) h->grid_min = h->grid_max = grid[n];   // a NaN is inside no axis
+    h->grid_order = up ? 1 : (down ? -1 : 0);
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MOM_OK;
