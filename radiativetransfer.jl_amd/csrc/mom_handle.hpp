@@ -56,14 +56,13 @@ struct mom_handle : MomSceneBufs<double> {
   MomDevBuf<double> d_tau_abs, d_grid, d_lines, d_tau_rayl, d_layer_max, d_aer;
   MomDevBuf<int> d_aer_mode;
   int abs_Nz = 0;
-  size_t lines_per = 0;   // lines ONE layer's block of d_lines has room for (the stride of its arrays, not the size of the allocation)
-  int lines_nz = 1;       // layers held in d_lines: arrays [nu | gamma_d | y | S][lines_nz][lines_per], then the two window arrays as ints
-                          // (one slot of doubles), then gamma_l [lines_nz][lines_per]
+  size_t lines_per = 0;   // d_lines is a MomLineBlock (mom_host.hpp, which owns the format) of this capacity per layer ...
+  int lines_nz = 1;       // ... and this many layers, as the last absorption call left it (line_blocks, mom_optics.hip)
   int abs_broadening = 0, abs_cef = 0;  // mom_absorption_set_model: MOM_BROADENING_*, MOM_CEF_* of the absorption calls (Voigt / HW32SD)
   MomDevBuf<double> d_prof;  // per-layer scalars of mom_voigt_tau_abs_profile
   // Dual run of the absorption path (mom_voigt_tau_abs_dual / _profile_dual): partials with respect to (p, T) of every layer
   MomDevBuf<double> d_dtau_abs;  // [S, abs_Nz, 2]; exists from the first Dual call after mom_absorption_begin
-  MomDevBuf<double> d_dlines;    // partials of d_lines' prefactors: [nu | gamma_d | y | S | gamma_l][2][lines_nz][lines_per]
+  MomDevBuf<double> d_dlines;    // partials of d_lines' prefactors: the MomLinePartialBlock of the same (lines_per, lines_nz); grow-only
   MomDevBuf<double> d_vec[4];  // S-length temporaries (tau_sum, dtau, varpi, expk)
   MomDevBuf<double> d_Zop[2];
   // scene
@@ -151,6 +150,22 @@ struct mom_handle : MomSceneBufs<double> {
 #pragma GCC visibility push(hidden)
 int fail(mom_t *h, int code, const char *msg);  // momcore.hip: error text -> the handle (if any) and the thread's string; returns code
 int check_info(mom_t *h);                       // momcore.hip: the zero-pivot report of the handle's kernels (synchronises)
+// what an absorption entry point `fn` needs before it may run: the resident tau_abs table and grid (`table`), the resident line
+// table (`lines`); MOM_ESTATE with the call that is missing
+inline int mom_absorption_state(mom_t *h, const char *fn, bool table, bool lines) {
+  const bool no_table = table && (!h->d_tau_abs || !h->d_grid);
+  if (!no_table && !(lines && !h->d_lt)) return MOM_OK;
+  char buf[200];
+  snprintf(buf, sizeof buf, no_table ? "%s: call mom_absorption_begin with the spectral grid first" : "%s: call mom_absorption_set_lines first", fn);
+  return fail(h, MOM_ESTATE, buf);
+}
+// qoft! asserts Tmin < T < Tmax (compute_absorption_cross_section.jl:204): T against the common range of the resident TIPS tables
+inline int mom_tips_range(mom_t *h, double T) {
+  if (h->lt.nIso <= 0 || (h->lt_Tmin < T && T < h->lt_Tmax)) return MOM_OK;
+  char buf[160];
+  snprintf(buf, sizeof buf, "TIPS2017: T (%g) must be between %g K and %g K.", T, h->lt_Tmin, h->lt_Tmax);
+  return fail(h, MOM_EINVAL, buf);
+}
 // momcore.hip: one launch of k_combine<lds> for mom_rt_run_multisensor (why not from mom_scene.hip: see its definition)
 hipError_t mom_launch_combine(const mom::InterArgs &a, bool lds, int grid, size_t smem, hipStream_t st);
 // mom_scene.hip: everything of a scene that does not depend on how the layer optics reach the device: phase-matrix bases, view

@@ -233,17 +233,63 @@ inline int mom_line_shape(const char *fn, int broadening, int cef, std::string *
 // does the shape read prefactor k of (nu, gamma_d, y, S, gamma_l)?  The others may be null at the C ABI
 inline bool mom_shape_reads(int shape, int k) { return k == 0 || k == 3 || (k == 1 ? shape != 3 : k == 2 ? shape <= 1 : shape == 3); }
 
-// voigt.hip: one launch for all lines (device pointers, stream st); out[g] = acc  or  out[g] += factor * acc
-hipError_t mom_voigt_launch(hipStream_t st, int shape, int nLines, const double *nu, const double *gamma_d, const double *gamma_l,
-                            const double *y, const double *S, const int *i0, const int *i1, int nGrid, const double *grid, double *out,
-                            double factor, int accumulate, int sorted);
+// ---- The line buffers of the absorption path.  THE FORMAT IS DECIDED HERE AND NOWHERE ELSE: kernels, launchers, entry points and
+// getters take the views below and never index a buffer themselves.
+// One layer's prefactors (device pointers, [cap] each): the five line_shape! takes (compute_absorption_cross_section.jl:118-124) and
+// the line's 1-based grid window.  T = const double: what the line-shape kernels read; T = double: what k_line_prefactors* writes.
+template <class T>
+struct MomLineViewT {
+  using Int = std::conditional_t<std::is_const<T>::value, const int, int>;
+  T *nu, *gamma_d, *y, *S, *gamma_l;
+  Int *i0, *i1;
+  T *&prefactor(int k) { T **const m[5] = {&nu, &gamma_d, &y, &S, &gamma_l}; return *m[k]; }   // in the C ABI's order (mom_shape_reads)
+  __host__ __device__ operator MomLineViewT<const T>() const { return {nu, gamma_d, y, S, gamma_l, i0, i1}; }
+};
+using MomLineView = MomLineViewT<const double>;
+using MomLineOut = MomLineViewT<double>;
+// One layer's partials of the five prefactors with respect to (k = 0) pressure and (k = 1) temperature: partial k of line j at
+// p[j + ks k]; to a reader a null array counts as zeros
+template <class T>
+struct MomLinePartialsT {
+  T *dnu, *dgamma_d, *dy, *dS, *dgamma_l;
+  size_t ks;
+  T *&partial(int q) { T **const m[5] = {&dnu, &dgamma_d, &dy, &dS, &dgamma_l}; return *m[q]; }   // the order of prefactor()
+  __host__ __device__ operator MomLinePartialsT<const T>() const { return {dnu, dgamma_d, dy, dS, dgamma_l, ks}; }
+};
+using MomLinePartials = MomLinePartialsT<const double>;
+using MomLinePartialsOut = MomLinePartialsT<double>;
+// The resident partial block: [nu | gamma_d | y | S | gamma_l][2][nz][cap], (cap, nz) of the value block it belongs to
+// (MomLineBlock::partials)
+struct MomLinePartialBlock {
+  double *base;
+  size_t cap;
+  int nz;
+  size_t doubles() const { return 10 * cap * (size_t)nz; }
+  __host__ __device__ MomLinePartialsOut layer(int z) const {
+    const size_t ks = cap * (size_t)nz, lz = cap * (size_t)z;
+    return {base + lz, base + 2 * ks + lz, base + 4 * ks + lz, base + 6 * ks + lz, base + 8 * ks + lz, ks};
+  }
+};
+// The resident value block: [nu | gamma_d | y | S | the two window arrays as ints | gamma_l][nz][cap] in `doubles()` doubles at base
+struct MomLineBlock {
+  double *base;
+  size_t cap;   // lines one layer has room for: the stride of the arrays, not the size of the allocation
+  int nz;
+  // the one capacity rule: room to grow to twice the lines before the next allocation, and no small allocations
+  static size_t capacity_for(size_t nLines) { return std::max<size_t>(nLines, 1024) * 2; }
+  size_t doubles() const { return 6 * cap * (size_t)nz; }
+  __host__ __device__ MomLineOut layer(int z) const {
+    const size_t ks = cap * (size_t)nz, lz = cap * (size_t)z;
+    int *const win = reinterpret_cast<int *>(base + 4 * ks);
+    return {base + lz, base + ks + lz, base + 2 * ks + lz, base + 3 * ks + lz, base + 5 * ks + lz, win + lz, win + ks + lz};
+  }
+  MomLinePartialBlock partials(double *at) const { return {at, cap, nz}; }   // the partial block to match, in memory of its own
+};
 
-// its Dual run: the partials of the prefactors (k = 0 pressure, 1 temperature; partial k of line j at p[j + ks k], null = zeros)
-// and dout[g + os k] = d_k acc  or  += factor * d_k acc
-hipError_t mom_voigt_dual_launch(hipStream_t st, int shape, int nLines, const double *nu, const double *gamma_d, const double *gamma_l,
-                                 const double *y, const double *S, const int *i0, const int *i1, int nGrid, const double *grid,
-                                 double *out, double factor, int accumulate, int sorted, const double *dnu, const double *dgd,
-                                 const double *dgl, const double *dy, const double *dS, size_t ks, double *dout, size_t os);
+// voigt.hip: one launch for all lines (device pointers, stream st); out[g] = acc  or  out[g] += factor * acc.  With `dln`, the Dual
+// run: also dout[g + os k] = d_k acc  or  += factor * d_k acc
+hipError_t mom_voigt_launch(hipStream_t st, int shape, int nLines, const MomLineView &ln, const MomLinePartials *dln, int nGrid,
+                            const double *grid, double *out, double *dout, size_t os, double factor, int accumulate, int sorted);
 
 // resident HITRAN table of one absorber + the TIPS spline tables of its isotopologues (device pointers)
 struct MomLineTable {
@@ -254,25 +300,20 @@ struct MomLineTable {
   const double *tT, *tQ, *tZ;                                         // [nIso, nTmax] knots, values, second derivatives
 };
 // the scalar part of gamma_d = (cSqrt2Ln2 / cc_) sqrt(cBolts_ / cMassMol) sqrt(T) nu_0 / sqrt(mol_weight)
-// (compute_absorption_cross_section.jl:87-88), the `cgd` the profile kernels take per layer
-inline double mom_doppler_scale(double T) {
-  const double cg = (1.1774100225 / 2.99792458e8) * std::sqrt(1.3806503e-23 / 1.66053873e-27);
-  return cg * std::sqrt(T);
-}
+// (compute_absorption_cross_section.jl:87-88), the `cgd` the prefactor kernels take per layer, and its temperature derivative
+// (d sqrt(T) = 1 / (2 sqrt(T))) for the Dual run
+inline double mom_doppler_cg() { return (1.1774100225 / 2.99792458e8) * std::sqrt(1.3806503e-23 / 1.66053873e-27); }
+inline double mom_doppler_scale(double T) { return mom_doppler_cg() * std::sqrt(T); }
+inline double mom_doppler_scale_dT(double T) { return mom_doppler_cg() * (1.0 / (2.0 * std::sqrt(T))); }
 // voigt.hip: per-line prefactors of one (p, T) on the device; *unsorted is set when the windows are not monotone
-// every layer of a profile: prefactors of all (layer, line) pairs, then the line shapes of all (layer, grid point) pairs;
-// pf = [nu | gamma_d | y | S | the two window arrays as ints | gamma_l][Nz][cap]
-hipError_t mom_voigt_profile_launch(hipStream_t st, int shape, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
-                                    const double *prm, double vmr, double wing, double *pf, int *win, int *unsorted, double *tau_abs,
-                                    const double *factor);
 hipError_t mom_line_prefactors_launch(hipStream_t st, const MomLineTable &tb, int nGrid, const double *grid, double p, double T,
-                                      double vmr, double wing, double cgd, double *nu, double *gd, double *y, double *S, double *gl,
-                                      int *i0, int *i1, int *unsorted);
-// the Dual run of mom_voigt_profile_launch: prm = [p | T | cgd | factor | d cgd / dT][Nz], the prefactors' partials at
-// dpf[nu | gamma_d | y | S | gamma_l][k][Nz][cap], dtau_abs [nGrid, Nz, 2]
-hipError_t mom_voigt_profile_dual_launch(hipStream_t st, int shape, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
-                                         const double *prm, double vmr, double wing, double *pf, double *dpf, int *win, int *unsorted,
-                                         double *tau_abs, double *dtau_abs, const double *factor);
+                                      double vmr, double wing, double cgd, const MomLineOut &out, int *unsorted);
+// every layer of a profile (pf.nz of them): prefactors of all (layer, line) pairs into pf, then the line shapes of all (layer, grid
+// point) pairs; prm = [p | T | cgd | factor][nz], unsorted [nz].  With `dpf`, the Dual run: prm = [p | T | cgd | factor | d cgd / dT][nz],
+// the prefactors' partials into dpf, dtau_abs [nGrid, nz, 2]
+hipError_t mom_voigt_profile_launch(hipStream_t st, int shape, const MomLineTable &tb, const MomLineBlock &pf, const MomLinePartialBlock *dpf,
+                                    int nGrid, const double *grid, const double *prm, double vmr, double wing, int *unsorted,
+                                    double *tau_abs, double *dtau_abs, const double *factor);
 
 // mom_dual.hip: rt_run on ForwardDiff.Dual numbers (values + P partials) for the resident scene.  Device pointers unless noted;
 // partial arrays have the layout of their value arrays with the partial index as the slowest axis, nullptr = zero partials.

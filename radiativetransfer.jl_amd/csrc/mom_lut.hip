@@ -377,16 +377,13 @@ extern "C" int mom_lut_build(mom_t *h, int lut, double vmr, double wing_cutoff, 
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
   MomLut *t = lut_of(h, lut);
   if (!t) return bad_id(h, "mom_lut_build", lut);
-  if (!h->d_lt) return fail(h, MOM_ESTATE, "mom_lut_build: call mom_absorption_set_lines first");
+  int rc = mom_absorption_state(h, "mom_lut_build", false, true);
+  if (rc) return rc;
   const int nNu = t->n[0], nP = t->n[1], nT = t->n[2], nodes = nP * nT;
-  char buf[200];
   for (int j = 0; j < nT; ++j) {
     const double T = t->first[2] + t->step[2] * j;
     if (!(T > 0.0)) return fail(h, MOM_EINVAL, "mom_lut_build: the T axis reaches T <= 0");
-    if (h->lt.nIso > 0 && !(h->lt_Tmin < T && T < h->lt_Tmax)) {
-      snprintf(buf, sizeof buf, "TIPS2017: T (%g) must be between %g K and %g K.", T, h->lt_Tmin, h->lt_Tmax);
-      return fail(h, MOM_EINVAL, buf);
-    }
+    if ((rc = mom_tips_range(h, T))) return rc;
   }
   if (gpu_ms) gpu_ms[0] = gpu_ms[1] = 0.0;
   HIPCHK(h, hipSetDevice(h->device));
@@ -411,11 +408,12 @@ extern "C" int mom_lut_build(mom_t *h, int lut, double vmr, double wing_cutoff, 
   // the prefactor block of a batch grows with nodes x lines: kLutBatch nodes at a time (MOM_OPT_LUT_BATCH); nodes are independent,
   // so the batch size does not change a bit
   const int batch = std::min(nodes, h->opt_lut_batch > 0 ? h->opt_lut_batch : 64);
-  MomDevBuf<double> pf, prm;
+  MomDevBuf<double> d_pf, prm;
   std::vector<double> hp(4 * (size_t)nodes);
   if (nLines > 0) {
-    const size_t cap = std::max<size_t>((size_t)nLines, 1024) * 2;
-    HIPCHK(h, pf.renew(6 * cap * (size_t)batch));
+    MomLineBlock pf = {nullptr, MomLineBlock::capacity_for((size_t)nLines), batch};
+    HIPCHK(h, d_pf.renew(pf.doubles()));
+    pf.base = d_pf;
     HIPCHK(h, prm.renew(4 * (size_t)nodes + ((size_t)nodes + 1) / 2));
     for (int z0 = 0; z0 < nodes; z0 += batch) {   // [p | T | cgd | factor][nb] per batch
       const int nb = std::min(batch, nodes - z0);
@@ -434,15 +432,14 @@ extern "C" int mom_lut_build(mom_t *h, int lut, double vmr, double wing_cutoff, 
     for (int z0 = 0; z0 < nodes; z0 += batch) {
       const int nb = std::min(batch, nodes - z0);
       const double *b = prm + 4 * (size_t)z0;
-      HIPCHK(h, mom_voigt_profile_launch(h->stream, shape, h->lt, nb, cap, nNu, t->d_nu, b, vmr, wing_cutoff, pf,
-                                         reinterpret_cast<int *>(pf + 4 * cap * (size_t)nb), flags + z0, t->d_table + (size_t)nNu * z0,
-                                         b + 3 * (size_t)nb));
+      pf.nz = nb;   // the last batch may be shorter: a block of fewer layers in the same memory
+      HIPCHK(h, mom_voigt_profile_launch(h->stream, shape, h->lt, pf, nullptr, nNu, t->d_nu, b, vmr, wing_cutoff, flags + z0,
+                                         t->d_table + (size_t)nNu * z0, nullptr, b + 3 * (size_t)nb));
     }
   }
   if (gpu_ms) HIPCHK(h, hipEventRecord(ev[1], h->stream));
   t->has_table = true;
-  const int rc = lut_prefilter(h, *t);   // synchronises: hp, pf and prm may go
-  if (rc) return rc;
+  if ((rc = lut_prefilter(h, *t))) return rc;   // synchronises: hp, d_pf and prm may go
   if (gpu_ms) {
     HIPCHK(h, hipEventRecord(ev[2], h->stream));
     HIPCHK(h, hipEventSynchronize(ev[2]));
@@ -514,10 +511,8 @@ int lut_profile_run(mom_t *h, const char *fn, bool dual, int lut, int Nz, const 
   MomLut *t = lut_of(h, lut);
   if (!t) return bad_id(h, fn, lut);
   if (!t->has_coef) return no_coef(h, fn);
-  if (!h->d_tau_abs || !h->d_grid) {
-    snprintf(buf, sizeof buf, "%s: call mom_absorption_begin with the spectral grid first", fn);
-    return fail(h, MOM_ESTATE, buf);
-  }
+  int rc = mom_absorption_state(h, fn, true, false);
+  if (rc) return rc;
   snprintf(buf, sizeof buf, "%s: bad argument", fn);
   if (Nz < 1 || Nz > h->abs_Nz || Nz > 65535 || !pressure || !temperature || !factor) return fail(h, MOM_EINVAL, buf);
   for (int z = 0; z < Nz; ++z) {
@@ -542,9 +537,9 @@ int lut_profile_run(mom_t *h, const char *fn, bool dual, int lut, int Nz, const 
       if (!h->ev_voigt[k]) HIPCHK(h, hipEventCreate(&h->ev_voigt[k]));
     HIPCHK(h, hipEventRecord(h->ev_voigt[0], h->stream));
   }
-  const int rc = lut_eval_launch(h, *t, layers, h->d_grid, h->S, h->grid_order != 0, h->d_tau_abs, dual ? h->d_dtau_abs.get() : nullptr,
-                                 S * h->abs_Nz, 1);
-  if (rc) return rc;
+  if ((rc = lut_eval_launch(h, *t, layers, h->d_grid, h->S, h->grid_order != 0, h->d_tau_abs, dual ? h->d_dtau_abs.get() : nullptr,
+                            S * h->abs_Nz, 1)))
+    return rc;
   if (gpu_ms) HIPCHK(h, hipEventRecord(h->ev_voigt[1], h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));   // layers is a host temporary
   if (gpu_ms) {

@@ -83,10 +83,8 @@ int voigt_only(mom_t *h, const char *fn) {
 int lineshape_args(mom_t *h, const char *fn, int shape, int iz_1based, int nLines, const double *const *line, const int *ind_start_1based,
                    const int *ind_stop_1based) {
   char buf[200];
-  if (!h->d_tau_abs || !h->d_grid) {
-    snprintf(buf, sizeof buf, "%s: call mom_absorption_begin with the spectral grid first", fn);
-    return fail(h, MOM_ESTATE, buf);
-  }
+  const int rc = mom_absorption_state(h, fn, true, false);
+  if (rc) return rc;
   bool lines_ok = ind_start_1based && ind_stop_1based;
   for (int k = 0; k < 5; ++k) lines_ok = lines_ok && (line[k] || !mom_shape_reads(shape, k));
   if (iz_1based < 1 || iz_1based > h->abs_Nz || nLines < 0 || (nLines > 0 && !lines_ok)) {
@@ -106,42 +104,70 @@ bool windows_sorted(int nLines, const int *i0, const int *i1) {
     if (i0[j] < i0[j - 1] || i1[j] < i1[j - 1]) return false;
   return true;
 }
-// d_lines of one layer: [nu | gamma_d | y | S | the two window arrays as ints | gamma_l][cap], grown geometrically: no allocation in
-// steady state
-int value_lines(mom_t *h, size_t lb) {
-  if (lb > h->lines_per || h->lines_nz != 1) {
-    h->lines_nz = 1;
-    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
-    const size_t cap = std::max<size_t>(lb, 1024) * 2;
-    HIPCHK(h, h->d_lines.renew(6 * cap));
-    h->lines_per = cap;
-  }
+// dtau_abs [S, abs_Nz, 2], allocated and zeroed by the first Dual call after mom_absorption_begin
+int dual_table(mom_t *h) {
+  if (h->d_dtau_abs) return MOM_OK;
+  const size_t n = 2 * (size_t)h->S * h->abs_Nz;
+  HIPCHK(h, h->d_dtau_abs.renew(n));
+  HIPCHK(h, hipMemsetAsync(h->d_dtau_abs, 0, n * sizeof(double), h->stream));
   return MOM_OK;
 }
-const int kLineSlot[5] = {0, 1, 2, 3, 5};  // where nu, gamma_d, y, S, gamma_l sit in d_lines (slot 4: the windows)
+// The one owner of the handle's line buffers: d_lines as a block of `nz` layers with room for `nLines` lines each and, Dual run,
+// d_dlines as the partial block to match.  A block is kept while it has the layer count asked for and the capacity the rule gives
+// for nLines fits its stride (so a repeated call allocates nothing, and no entry point ever gets less room than the rule gives);
+// otherwise it is allocated afresh, after the stream that may still read the old one has drained.  d_dlines only grows.
+int line_blocks(mom_t *h, int nLines, int nz, MomLineBlock *pf, MomLinePartialBlock *dpf) {
+  const size_t cap = MomLineBlock::capacity_for((size_t)nLines);
+  if (!h->d_lines || cap > h->lines_per || nz != h->lines_nz) {
+    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
+    HIPCHK(h, h->d_lines.renew(MomLineBlock{nullptr, cap, nz}.doubles()));
+    h->lines_per = cap;
+    h->lines_nz = nz;
+  }
+  *pf = MomLineBlock{h->d_lines, h->lines_per, nz};
+  if (!dpf) return MOM_OK;
+  HIPCHK(h, h->d_dlines.reserve(pf->partials(nullptr).doubles(), h->stream));
+  *dpf = pf->partials(h->d_dlines);
+  return MOM_OK;
+}
+// the blocks as the last call left them, for the test-access getters: they read the LAST layer of the last call
+MomLineBlock resident_lines(const mom_t *h) { return {h->d_lines, h->lines_per, std::max(h->lines_nz, 1)}; }
+MomLinePartialBlock resident_partials(const mom_t *h) { return resident_lines(h).partials(h->d_dlines); }
+bool partials_resident(const mom_t *h) { return h->d_dlines && h->d_dlines.capacity() >= resident_partials(h).doubles(); }
 
-// mom_voigt_tau_abs and mom_lineshape_tau_abs
+// mom_voigt_tau_abs, mom_lineshape_tau_abs and, with dline[], their Dual runs: dline[] = the partials of line[], each [nLines, 2]
+// column-major or null (zeros)
 int lineshape_tau_abs_run(mom_t *h, const char *fn, int shape, int iz_1based, int nLines, const double *const *line,
-                          const int *ind_start_1based, const int *ind_stop_1based, double factor) {
+                          const double *const *dline, const int *ind_start_1based, const int *ind_stop_1based, double factor) {
   int rc = lineshape_args(h, fn, shape, iz_1based, nLines, line, ind_start_1based, ind_stop_1based);
   if (rc) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (dline && (rc = dual_table(h))) return rc;
   if (nLines == 0) return MOM_OK;
   const int sorted = windows_sorted(nLines, ind_start_1based, ind_stop_1based) ? 1 : 0;
-  HIPCHK(h, hipSetDevice(h->device));
   const size_t lb = (size_t)nLines;
-  rc = value_lines(h, lb);
-  if (rc) return rc;
-  const size_t cap = h->lines_per;
-  double *dl = h->d_lines;
-  int *dw = reinterpret_cast<int *>(dl + 4 * cap);
+  MomLineBlock pf;
+  MomLinePartialBlock dpf;
+  if ((rc = line_blocks(h, nLines, 1, &pf, dline ? &dpf : nullptr))) return rc;
+  MomLineOut ln = pf.layer(0);
   // the host arrays are borrowed for the call only: the copies must have left them before we return
   for (int k = 0; k < 5; ++k)
     if (line[k] && mom_shape_reads(shape, k))
-      HIPCHK(h, hipMemcpyAsync(dl + kLineSlot[k] * cap, line[k], lb * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(dw, ind_start_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(dw + cap, ind_stop_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, mom_voigt_launch(h->stream, shape, nLines, dl, dl + cap, dl + 5 * cap, dl + 2 * cap, dl + 3 * cap, dw, dw + cap, h->S, h->d_grid,
-                             h->d_tau_abs + (size_t)h->S * (iz_1based - 1), factor, 1, sorted));
+      HIPCHK(h, hipMemcpyAsync(ln.prefactor(k), line[k], lb * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(ln.i0, ind_start_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(ln.i1, ind_stop_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  MomLinePartialsOut dln{};
+  if (dline) dln = dpf.layer(0);
+  for (int q = 0; q < 5 && dline; ++q)   // a null array: zeros
+    for (int k = 0; k < 2; ++k) {
+      double *dst = dln.partial(q) + dln.ks * k;
+      if (dline[q]) HIPCHK(h, hipMemcpyAsync(dst, dline[q] + lb * k, lb * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      else HIPCHK(h, hipMemsetAsync(dst, 0, lb * sizeof(double), h->stream));
+    }
+  const MomLinePartials dread = dln;
+  const size_t col = (size_t)h->S * (iz_1based - 1);
+  HIPCHK(h, mom_voigt_launch(h->stream, shape, nLines, ln, dline ? &dread : nullptr, h->S, h->d_grid, h->d_tau_abs + col,
+                             dline ? h->d_dtau_abs + col : nullptr, (size_t)h->S * h->abs_Nz, factor, 1, sorted));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MOM_OK;
 }
@@ -153,7 +179,7 @@ extern "C" int mom_voigt_tau_abs(mom_t *h, int iz_1based, int nLines, const doub
   const int rc = voigt_only(h, "mom_voigt_tau_abs");
   if (rc) return rc;
   const double *line[5] = {nu, gamma_d, y, S, nullptr};
-  return lineshape_tau_abs_run(h, "mom_voigt_tau_abs", handle_shape(h), iz_1based, nLines, line, ind_start_1based, ind_stop_1based, factor);
+  return lineshape_tau_abs_run(h, "mom_voigt_tau_abs", handle_shape(h), iz_1based, nLines, line, nullptr, ind_start_1based, ind_stop_1based, factor);
 }
 
 // mom_voigt_tau_abs for the handle's model: the five prefactors line_shape! takes (compute_absorption_cross_section.jl:118-124)
@@ -162,76 +188,13 @@ extern "C" int mom_lineshape_tau_abs(mom_t *h, int iz_1based, int nLines, const 
                                      double factor) {
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
   const double *line[5] = {nu, gamma_d, y, S, gamma_l};
-  return lineshape_tau_abs_run(h, "mom_lineshape_tau_abs", handle_shape(h), iz_1based, nLines, line, ind_start_1based, ind_stop_1based,
-                               factor);
+  return lineshape_tau_abs_run(h, "mom_lineshape_tau_abs", handle_shape(h), iz_1based, nLines, line, nullptr, ind_start_1based,
+                               ind_stop_1based, factor);
 }
 
 // ---- The Dual run of the absorption path: tau_abs and its partials with respect to the layer's pressure (k = 0) and temperature
 // (k = 1), ForwardDiff.Dual through compute_absorption_cross_section as absorption_cross_section(...; autodiff = true) runs it
 // (autodiff_helper.jl:17-51).  Works on Float64 and Float32 handles alike: the absorption table is Float64 on both.
-namespace {
-// dtau_abs [S, abs_Nz, 2], allocated and zeroed by the first Dual call after mom_absorption_begin
-int dual_table(mom_t *h) {
-  if (h->d_dtau_abs) return MOM_OK;
-  const size_t n = 2 * (size_t)h->S * h->abs_Nz;
-  HIPCHK(h, h->d_dtau_abs.renew(n));
-  HIPCHK(h, hipMemsetAsync(h->d_dtau_abs, 0, n * sizeof(double), h->stream));
-  return MOM_OK;
-}
-// d_lines with room for `nz` layers of `lb` lines (the value entry points' layout and growth) and d_dlines to match
-int dual_lines(mom_t *h, size_t lb, int nz) {
-  const size_t per = std::max<size_t>(lb, 1024) * 2;
-  if (lb > h->lines_per || h->lines_nz != nz || !h->d_lines) {
-    if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
-    HIPCHK(h, h->d_lines.renew(6 * per * (size_t)nz));
-    h->lines_per = per;
-    h->lines_nz = nz;
-  }
-  HIPCHK(h, h->d_dlines.reserve(10 * h->lines_per * (size_t)nz, h->stream));
-  return MOM_OK;
-}
-}  // namespace
-
-namespace {
-// mom_voigt_tau_abs_dual and mom_lineshape_tau_abs_dual; dline[] = the partials of line[], each [nLines, 2] column-major or null
-int lineshape_tau_abs_dual_run(mom_t *h, const char *fn, int shape, int iz_1based, int nLines, const double *const *line,
-                               const double *const *dline, const int *ind_start_1based, const int *ind_stop_1based, double factor) {
-  int rc = lineshape_args(h, fn, shape, iz_1based, nLines, line, ind_start_1based, ind_stop_1based);
-  if (rc) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  rc = dual_table(h);
-  if (rc) return rc;
-  if (nLines == 0) return MOM_OK;
-  const int sorted = windows_sorted(nLines, ind_start_1based, ind_stop_1based) ? 1 : 0;
-  const size_t lb = (size_t)nLines;
-  rc = dual_lines(h, lb, 1);
-  if (rc) return rc;
-  const size_t cap = h->lines_per;
-  double *dl = h->d_lines, *dd = h->d_dlines;
-  int *dw = reinterpret_cast<int *>(dl + 4 * cap);
-  const double *dev[5];
-  // the host arrays are borrowed for the call only: the copies must have left them before we return
-  for (int k = 0; k < 5; ++k)
-    if (line[k] && mom_shape_reads(shape, k))
-      HIPCHK(h, hipMemcpyAsync(dl + kLineSlot[k] * cap, line[k], lb * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  for (int q = 0; q < 5; ++q) {  // host [nLines, 2] column-major -> [q][k][cap]; a null array: zeros
-    dev[q] = dd + 2 * q * cap;
-    for (int k = 0; k < 2; ++k) {
-      if (dline[q]) HIPCHK(h, hipMemcpyAsync(dd + (2 * q + k) * cap, dline[q] + lb * k, lb * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      else HIPCHK(h, hipMemsetAsync(dd + (2 * q + k) * cap, 0, lb * sizeof(double), h->stream));
-    }
-  }
-  HIPCHK(h, hipMemcpyAsync(dw, ind_start_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(dw + cap, ind_stop_1based, lb * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  const size_t col = (size_t)h->S * (iz_1based - 1);
-  HIPCHK(h, mom_voigt_dual_launch(h->stream, shape, nLines, dl, dl + cap, dl + 5 * cap, dl + 2 * cap, dl + 3 * cap, dw, dw + cap, h->S,
-                                  h->d_grid, h->d_tau_abs + col, factor, 1, sorted, dev[0], dev[1], dev[4], dev[2], dev[3], cap,
-                                  h->d_dtau_abs + col, (size_t)h->S * h->abs_Nz));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return MOM_OK;
-}
-}  // namespace
-
 extern "C" int mom_voigt_tau_abs_dual(mom_t *h, int iz_1based, int nLines, const double *nu, const double *gamma_d, const double *y,
                                       const double *S, const double *dnu, const double *dgamma_d, const double *dy, const double *dS,
                                       const int *ind_start_1based, const int *ind_stop_1based, double factor) {
@@ -239,8 +202,8 @@ extern "C" int mom_voigt_tau_abs_dual(mom_t *h, int iz_1based, int nLines, const
   const int rc = voigt_only(h, "mom_voigt_tau_abs_dual");
   if (rc) return rc;
   const double *line[5] = {nu, gamma_d, y, S, nullptr}, *dline[5] = {dnu, dgamma_d, dy, dS, nullptr};
-  return lineshape_tau_abs_dual_run(h, "mom_voigt_tau_abs_dual", handle_shape(h), iz_1based, nLines, line, dline, ind_start_1based,
-                                    ind_stop_1based, factor);
+  return lineshape_tau_abs_run(h, "mom_voigt_tau_abs_dual", handle_shape(h), iz_1based, nLines, line, dline, ind_start_1based,
+                               ind_stop_1based, factor);
 }
 
 // mom_voigt_tau_abs_dual for the handle's model
@@ -250,8 +213,8 @@ extern "C" int mom_lineshape_tau_abs_dual(mom_t *h, int iz_1based, int nLines, c
                                           const int *ind_start_1based, const int *ind_stop_1based, double factor) {
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
   const double *line[5] = {nu, gamma_d, y, S, gamma_l}, *dline[5] = {dnu, dgamma_d, dy, dS, dgamma_l};
-  return lineshape_tau_abs_dual_run(h, "mom_lineshape_tau_abs_dual", handle_shape(h), iz_1based, nLines, line, dline, ind_start_1based,
-                                    ind_stop_1based, factor);
+  return lineshape_tau_abs_run(h, "mom_lineshape_tau_abs_dual", handle_shape(h), iz_1based, nLines, line, dline, ind_start_1based,
+                               ind_stop_1based, factor);
 }
 
 extern "C" int mom_absorption_get_partials(mom_t *h, double *dtau_abs) {
@@ -313,33 +276,25 @@ extern "C" int mom_absorption_set_lines(mom_t *h, int nLines, const double *nu0,
 extern "C" int mom_voigt_tau_abs_layer(mom_t *h, int iz_1based, double pressure, double temperature, double vmr,
                                        double wing_cutoff, double factor) {
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
-  if (!h->d_tau_abs || !h->d_grid) return fail(h, MOM_ESTATE, "mom_voigt_tau_abs_layer: call mom_absorption_begin with the spectral grid first");
-  if (!h->d_lt) return fail(h, MOM_ESTATE, "mom_voigt_tau_abs_layer: call mom_absorption_set_lines first");
+  int rc = mom_absorption_state(h, "mom_voigt_tau_abs_layer", true, true);
+  if (rc) return rc;
   if (iz_1based < 1 || iz_1based > h->abs_Nz || !(temperature > 0.0)) return fail(h, MOM_EINVAL, "mom_voigt_tau_abs_layer: bad argument");
-  if (h->lt.nIso > 0 && !(h->lt_Tmin < temperature && temperature < h->lt_Tmax)) {
-    char buf[160];
-    snprintf(buf, sizeof buf, "TIPS2017: T (%g) must be between %g K and %g K.", temperature, h->lt_Tmin, h->lt_Tmax);
-    return fail(h, MOM_EINVAL, buf);
-  }
+  if ((rc = mom_tips_range(h, temperature))) return rc;
   const int nLines = h->lt.nLines;
   if (nLines == 0) return MOM_OK;
   HIPCHK(h, hipSetDevice(h->device));
-  const int rcl = value_lines(h, (size_t)nLines);
-  if (rcl) return rcl;
-  const size_t cap = h->lines_per;
-  double *dl = h->d_lines;
-  int *dw = reinterpret_cast<int *>(dl + 4 * cap);
+  MomLineBlock pf;
+  if ((rc = line_blocks(h, nLines, 1, &pf, nullptr))) return rc;
+  const MomLineOut ln = pf.layer(0);
   int *flag = h->d_lt_i + (size_t)std::max(nLines, 1) + std::max(h->lt.nIso, 1);
   HIPCHK(h, hipMemsetAsync(flag, 0, sizeof(int), h->stream));
-  // γ_d = (cSqrt2Ln2 / cc_) sqrt(cBolts_ / cMassMol) sqrt(T) ν₀ / sqrt(mol_weight)   (:87-88): the scalar part once
-  const double cgd = (1.1774100225 / 2.99792458e8) * std::sqrt(1.3806503e-23 / 1.66053873e-27) * std::sqrt(temperature);
-  HIPCHK(h, mom_line_prefactors_launch(h->stream, h->lt, h->S, h->d_grid, pressure, temperature, vmr, wing_cutoff, cgd, dl, dl + cap,
-                                       dl + 2 * cap, dl + 3 * cap, dl + 5 * cap, dw, dw + cap, flag));
+  HIPCHK(h, mom_line_prefactors_launch(h->stream, h->lt, h->S, h->d_grid, pressure, temperature, vmr, wing_cutoff, mom_doppler_scale(temperature),
+                                       ln, flag));
   int unsorted = 0;
   HIPCHK(h, hipMemcpyAsync(&unsorted, flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, mom_voigt_launch(h->stream, handle_shape(h), nLines, dl, dl + cap, dl + 5 * cap, dl + 2 * cap, dl + 3 * cap, dw, dw + cap, h->S,
-                             h->d_grid, h->d_tau_abs + (size_t)h->S * (iz_1based - 1), factor, 1, unsorted ? 0 : 1));
+  HIPCHK(h, mom_voigt_launch(h->stream, handle_shape(h), nLines, ln, nullptr, h->S, h->d_grid, h->d_tau_abs + (size_t)h->S * (iz_1based - 1),
+                             nullptr, 0, factor, 1, unsorted ? 0 : 1));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MOM_OK;
 }
@@ -355,45 +310,22 @@ int voigt_profile_run(mom_t *h, const char *fn, bool dual, int Nz, const double 
                       double wing_cutoff, const double *factor, double *gpu_ms) {
   char buf[200];
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
-  if (!h->d_tau_abs || !h->d_grid) {
-    snprintf(buf, sizeof buf, "%s: call mom_absorption_begin with the spectral grid first", fn);
-    return fail(h, MOM_ESTATE, buf);
-  }
-  if (!h->d_lt) {
-    snprintf(buf, sizeof buf, "%s: call mom_absorption_set_lines first", fn);
-    return fail(h, MOM_ESTATE, buf);
-  }
+  int rc = mom_absorption_state(h, fn, true, true);
+  if (rc) return rc;
   snprintf(buf, sizeof buf, "%s: bad argument", fn);
   if (Nz < 1 || Nz > h->abs_Nz || !pressure || !temperature || !factor) return fail(h, MOM_EINVAL, buf);
   for (int z = 0; z < Nz; ++z) {
     if (!(temperature[z] > 0.0)) return fail(h, MOM_EINVAL, buf);
-    if (h->lt.nIso > 0 && !(h->lt_Tmin < temperature[z] && temperature[z] < h->lt_Tmax)) {
-      snprintf(buf, sizeof buf, "TIPS2017: T (%g) must be between %g K and %g K.", temperature[z], h->lt_Tmin, h->lt_Tmax);
-      return fail(h, MOM_EINVAL, buf);
-    }
+    if ((rc = mom_tips_range(h, temperature[z]))) return rc;
   }
   if (gpu_ms) *gpu_ms = 0.0;
   HIPCHK(h, hipSetDevice(h->device));
-  if (dual) {
-    const int rc = dual_table(h);
-    if (rc) return rc;
-  }
+  if (dual && (rc = dual_table(h))) return rc;
   const int nLines = h->lt.nLines;
   if (nLines == 0) return MOM_OK;
-  if (dual) {
-    const int rc = dual_lines(h, (size_t)nLines, Nz);
-    if (rc) return rc;
-  } else {
-    const size_t per = std::max<size_t>((size_t)nLines, 1024) * 2;       // line capacity of one layer's block
-    const size_t need = per * (size_t)Nz;
-    if (need > h->lines_per * (size_t)std::max(h->lines_nz, 1) || h->lines_nz != Nz) {
-      if (h->d_lines) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->d_lines.reset(); h->lines_per = 0; }
-      HIPCHK(h, h->d_lines.renew(6 * need));
-      h->lines_per = per;
-      h->lines_nz = Nz;
-    }
-  }
-  const size_t cap = h->lines_per;
+  MomLineBlock pf;
+  MomLinePartialBlock dpf;
+  if ((rc = line_blocks(h, nLines, Nz, &pf, dual ? &dpf : nullptr))) return rc;
   // per-layer scalars [p | T | cgd | factor][Nz] (Dual run: | d cgd / dT) and the Nz sortedness flags
   const size_t nprm = dual ? 5 : 4;
   const size_t prm_doubles = nprm * (size_t)Nz + ((size_t)Nz + 1) / 2;
@@ -402,28 +334,20 @@ int voigt_profile_run(mom_t *h, const char *fn, bool dual, int Nz, const double 
   for (int z = 0; z < Nz; ++z) {
     prm[z] = pressure[z];
     prm[Nz + z] = temperature[z];
-    // γ_d = (cSqrt2Ln2 / cc_) sqrt(cBolts_ / cMassMol) sqrt(T) ν₀ / sqrt(mol_weight)   (:87-88): the scalar part
-    const double cg = (1.1774100225 / 2.99792458e8) * std::sqrt(1.3806503e-23 / 1.66053873e-27);
-    prm[2 * (size_t)Nz + z] = cg * std::sqrt(temperature[z]);
+    prm[2 * (size_t)Nz + z] = mom_doppler_scale(temperature[z]);
     prm[3 * (size_t)Nz + z] = factor[z];
-    if (dual) prm[4 * (size_t)Nz + z] = cg * (1.0 / (2.0 * std::sqrt(temperature[z])));   // d sqrt(T) = 1 / (2 sqrt(T))
+    if (dual) prm[4 * (size_t)Nz + z] = mom_doppler_scale_dT(temperature[z]);
   }
   HIPCHK(h, hipMemcpyAsync(h->d_prof, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   int *flags = reinterpret_cast<int *>(h->d_prof + nprm * (size_t)Nz);
   HIPCHK(h, hipMemsetAsync(flags, 0, sizeof(int) * (size_t)Nz, h->stream));
-  double *pf = h->d_lines;
-  int *win = reinterpret_cast<int *>(pf + 4 * cap * (size_t)Nz);
   if (gpu_ms) {
     for (int k = 0; k < 2; ++k)
       if (!h->ev_voigt[k]) HIPCHK(h, hipEventCreate(&h->ev_voigt[k]));
     HIPCHK(h, hipEventRecord(h->ev_voigt[0], h->stream));
   }
-  if (dual)
-    HIPCHK(h, mom_voigt_profile_dual_launch(h->stream, handle_shape(h), h->lt, Nz, cap, h->S, h->d_grid, h->d_prof, vmr, wing_cutoff, pf, h->d_dlines, win,
-                                            flags, h->d_tau_abs, h->d_dtau_abs, h->d_prof + 3 * (size_t)Nz));
-  else
-    HIPCHK(h, mom_voigt_profile_launch(h->stream, handle_shape(h), h->lt, Nz, cap, h->S, h->d_grid, h->d_prof, vmr, wing_cutoff, pf, win, flags,
-                                       h->d_tau_abs, h->d_prof + 3 * (size_t)Nz));
+  HIPCHK(h, mom_voigt_profile_launch(h->stream, handle_shape(h), h->lt, pf, dual ? &dpf : nullptr, h->S, h->d_grid, h->d_prof, vmr, wing_cutoff,
+                                     flags, h->d_tau_abs, dual ? h->d_dtau_abs.get() : nullptr, h->d_prof + 3 * (size_t)Nz));
   if (gpu_ms) HIPCHK(h, hipEventRecord(h->ev_voigt[1], h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));   // prm is a host temporary
   if (gpu_ms) {
@@ -447,14 +371,15 @@ extern "C" int mom_voigt_tau_abs_profile_dual(mom_t *h, int Nz, const double *pr
 // the partials of the prefactors of the last Dual call (test access), each [n, 2] column-major
 extern "C" int mom_absorption_get_prefactor_partials(mom_t *h, int n, double *dnu, double *dgamma_d, double *dy, double *dS) {
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
-  const size_t cap = h->lines_per, nz = (size_t)std::max(h->lines_nz, 1), last = (nz - 1) * cap;  // the LAST layer of a profile call
-  if (!h->d_lines || !h->d_dlines || n < 0 || (size_t)n > cap || h->d_dlines.capacity() < 10 * nz * cap)
+  const MomLineBlock pf = resident_lines(h);
+  if (!h->d_lines || n < 0 || (size_t)n > pf.cap || !partials_resident(h))
     return fail(h, MOM_ESTATE, "mom_absorption_get_prefactor_partials: no prefactor partials resident");
   HIPCHK(h, hipSetDevice(h->device));
+  MomLinePartialsOut dln = resident_partials(h).layer(pf.nz - 1);
   double *dst[4] = {dnu, dgamma_d, dy, dS};
   for (int q = 0; q < 4; ++q)
     for (int k = 0; k < 2 && dst[q]; ++k)
-      HIPCHK(h, hipMemcpy(dst[q] + (size_t)n * k, h->d_dlines + (2 * q + k) * nz * cap + last, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+      HIPCHK(h, hipMemcpy(dst[q] + (size_t)n * k, dln.partial(q) + dln.ks * k, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   return MOM_OK;
 }
 
@@ -464,13 +389,13 @@ extern "C" int mom_absorption_get_prefactors(mom_t *h, int n, double *nu, double
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
   if (!h->d_lines || n < 0 || (size_t)n > h->lines_per) return fail(h, MOM_ESTATE, "mom_absorption_get_prefactors: no prefactors resident");
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t cap = h->lines_per, nz = (size_t)std::max(h->lines_nz, 1), last = (nz - 1) * cap;  // the LAST layer of a profile call
+  const MomLineBlock pf = resident_lines(h);
+  MomLineOut ln = pf.layer(pf.nz - 1);
   double *dst[4] = {nu, gamma_d, y, S};
   for (int k = 0; k < 4; ++k)
-    if (dst[k]) HIPCHK(h, hipMemcpy(dst[k], h->d_lines + k * nz * cap + last, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-  const int *dw = reinterpret_cast<const int *>(h->d_lines + 4 * nz * cap);
-  if (ind_start_1based) HIPCHK(h, hipMemcpy(ind_start_1based, dw + last, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-  if (ind_stop_1based) HIPCHK(h, hipMemcpy(ind_stop_1based, dw + nz * cap + last, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    if (dst[k]) HIPCHK(h, hipMemcpy(dst[k], ln.prefactor(k), (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  if (ind_start_1based) HIPCHK(h, hipMemcpy(ind_start_1based, ln.i0, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  if (ind_stop_1based) HIPCHK(h, hipMemcpy(ind_stop_1based, ln.i1, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
   return MOM_OK;
 }
 
@@ -479,13 +404,13 @@ extern "C" int mom_absorption_get_prefactors(mom_t *h, int n, double *nu, double
 extern "C" int mom_absorption_get_gamma_l(mom_t *h, int n, double *gamma_l, double *dgamma_l) {
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
   if (!h->d_lines || n < 0 || (size_t)n > h->lines_per) return fail(h, MOM_ESTATE, "mom_absorption_get_gamma_l: no prefactors resident");
-  const size_t cap = h->lines_per, nz = (size_t)std::max(h->lines_nz, 1), last = (nz - 1) * cap;
-  if (dgamma_l && (!h->d_dlines || h->d_dlines.capacity() < 10 * nz * cap))
-    return fail(h, MOM_ESTATE, "mom_absorption_get_gamma_l: no prefactor partials resident");
+  if (dgamma_l && !partials_resident(h)) return fail(h, MOM_ESTATE, "mom_absorption_get_gamma_l: no prefactor partials resident");
   HIPCHK(h, hipSetDevice(h->device));
-  if (gamma_l) HIPCHK(h, hipMemcpy(gamma_l, h->d_lines + 5 * nz * cap + last, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  const MomLineBlock pf = resident_lines(h);
+  if (gamma_l) HIPCHK(h, hipMemcpy(gamma_l, pf.layer(pf.nz - 1).gamma_l, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  const MomLinePartialsOut dln = resident_partials(h).layer(pf.nz - 1);
   for (int k = 0; k < 2 && dgamma_l; ++k)
-    HIPCHK(h, hipMemcpy(dgamma_l + (size_t)n * k, h->d_dlines + (8 + k) * nz * cap + last, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(dgamma_l + (size_t)n * k, dln.dgamma_l + dln.ks * k, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   return MOM_OK;
 }
 

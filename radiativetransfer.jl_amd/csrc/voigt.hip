@@ -172,15 +172,6 @@ __device__ __forceinline__ double w_hw32_dual(double x, double y, cplx &dw) {
 #endif
 constexpr int kBlock = MOM_VOIGT_BLOCK;  // grid points per workgroup
 
-// Dual run of voigt_block: the partials of the per-line prefactors with respect to (k = 0) pressure and (k = 1) temperature,
-// partial k of line j at p[j + ks k] (a null array counts as zeros), and the output partials dsigma[g + os k]
-struct VoigtDualArgs {
-  const double *dnu, *dgd, *dy, *dS;
-  size_t ks;
-  double *dsigma;
-  size_t os;
-};
-
 // The absorption model (HitranModel.broadening x HitranModel.CEF) as the compile-time shape of voigt_block.  It decides what is
 // staged per candidate line, what is evaluated per (line, grid point) and which partials the Dual run stages; the candidate search,
 // the ordered compaction, the accumulation order, the window compare and the tau_abs epilogue are the same for all four.
@@ -191,8 +182,9 @@ struct VoigtDualArgs {
 enum LineShape : int { kVoigtSD = 0, kVoigt15 = 1, kDoppler = 2, kLorentz = 3 };
 
 // DUAL = false is the value kernel; DUAL = true shares its candidate search and ordered compaction, stages d a, d b, d nu, d y
-// (two each) next to a, b, nu, y and sums the two partials of every grid point in the same ascending line order.  gamma_l and its
-// partials dgl (laid out like dd's arrays) are read by kLorentz only, gamma_d by the other three, y by the two Voigt shapes.
+// (two each) next to a, b, nu, y and sums the two partials of every grid point in the same ascending line order: dd holds the
+// partials of the prefactors (MomLinePartials, mom_host.hpp), the output partials go to dsigma[g + os k].  gamma_l and its partials
+// are read by kLorentz only, gamma_d by the other three, y by the two Voigt shapes.
 template <bool DUAL, int SHAPE>
 __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict__ nu,
                                             const double *__restrict__ gamma_d, const double *__restrict__ gamma_l,
@@ -200,8 +192,8 @@ __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict
                                             const double *__restrict__ S, const int *__restrict__ i0,
                                             const int *__restrict__ i1, int nGrid,
                                             const double *__restrict__ grid, double *__restrict__ sigma,
-                                            double factor, int accumulate, int sorted, const VoigtDualArgs dd,
-                                            const double *__restrict__ dgl) {
+                                            double factor, int accumulate, int sorted, const MomLinePartials dd,
+                                            double *__restrict__ dsigma, size_t os) {
   constexpr bool kIsVoigt = SHAPE == kVoigtSD || SHAPE == kVoigt15;
   // per-line constants of the candidates, staged once per workgroup: centre, S c/gamma_d, c'/gamma_d, y and the
   // 0-based window -- the two divisions by gamma_d are per LINE here, not per evaluation (same expressions, same values)
@@ -277,7 +269,7 @@ __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict
 #pragma unroll
           for (int k = 0; k < 2; ++k) {
             const size_t o = (size_t)j + dd.ks * k;
-            const double dg = dgl ? dgl[o] : 0.0, ds = dd.dS ? dd.dS[o] : 0.0;
+            const double dg = dd.dgamma_l ? dd.dgamma_l[o] : 0.0, ds = dd.dS ? dd.dS[o] : 0.0;
             c_d[k * kBlock + pos] = ds * gl + s * dg;
             c_d[(2 + k) * kBlock + pos] = 2.0 * gl * dg;
             c_d[(4 + k) * kBlock + pos] = dd.dnu ? dd.dnu[o] : 0.0;
@@ -295,7 +287,7 @@ __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict
 #pragma unroll
           for (int k = 0; k < 2; ++k) {
             const size_t o = (size_t)j + dd.ks * k;
-            const double dg = dd.dgd ? dd.dgd[o] : 0.0, ds = dd.dS ? dd.dS[o] : 0.0;
+            const double dg = dd.dgamma_d ? dd.dgamma_d[o] : 0.0, ds = dd.dS ? dd.dS[o] : 0.0;
             c_d[k * kBlock + pos] = (ds * cSqrtLn2divSqrtPi - a * dg) / gd;
             c_d[(2 + k) * kBlock + pos] = -(b * dg) / gd;
             c_d[(4 + k) * kBlock + pos] = dd.dnu ? dd.dnu[o] : 0.0;
@@ -391,7 +383,7 @@ __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict
     if constexpr (DUAL) {
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
-        double *o = dd.dsigma + gi + dd.os * k;
+        double *o = dsigma + gi + os * k;
         const double dscaled = dacc[k] * factor;
         *o = accumulate ? *o + dscaled : dacc[k];
       }
@@ -399,108 +391,55 @@ __device__ __forceinline__ void voigt_block(int nLines, const double *__restrict
   }
 }
 
-__global__ void __launch_bounds__(kBlock) k_voigt(int nLines, const double *__restrict__ nu,
-                                                  const double *__restrict__ gamma_d, const double *__restrict__ y,
-                                                  const double *__restrict__ S, const int *__restrict__ i0,
-                                                  const int *__restrict__ i1, int nGrid,
-                                                  const double *__restrict__ grid, double *__restrict__ sigma,
-                                                  double factor, int accumulate, int sorted) {
-  voigt_block<false, kVoigtSD>(nLines, nu, gamma_d, nullptr, y, S, i0, i1, nGrid, grid, sigma, factor, accumulate, sorted, VoigtDualArgs{},
-                               nullptr);
+// The four line-shape kernels, each instantiated for the four shapes (the default model is the kVoigtSD instantiation).  A view
+// is unpacked into voigt_block's __restrict__ parameters: the qualifier is not honoured on struct members.
+template <int SHAPE>
+__global__ void __launch_bounds__(kBlock) k_voigt(int nLines, MomLineView ln, int nGrid, const double *__restrict__ grid,
+                                                  double *__restrict__ sigma, double factor, int accumulate, int sorted) {
+  voigt_block<false, SHAPE>(nLines, ln.nu, ln.gamma_d, ln.gamma_l, ln.y, ln.S, ln.i0, ln.i1, nGrid, grid, sigma, factor, accumulate, sorted,
+                            MomLinePartials{}, nullptr, 0);
 }
-__global__ void __launch_bounds__(kBlock) k_voigt_dual(int nLines, const double *__restrict__ nu,
-                                                       const double *__restrict__ gamma_d, const double *__restrict__ y,
-                                                       const double *__restrict__ S, const int *__restrict__ i0,
-                                                       const int *__restrict__ i1, int nGrid,
+template <int SHAPE>
+__global__ void __launch_bounds__(kBlock) k_voigt_dual(int nLines, MomLineView ln, MomLinePartials dd, int nGrid,
                                                        const double *__restrict__ grid, double *__restrict__ sigma,
-                                                       double factor, int accumulate, int sorted, VoigtDualArgs dd) {
-  voigt_block<true, kVoigtSD>(nLines, nu, gamma_d, nullptr, y, S, i0, i1, nGrid, grid, sigma, factor, accumulate, sorted, dd, nullptr);
+                                                       double *__restrict__ dsigma, size_t os, double factor, int accumulate, int sorted) {
+  voigt_block<true, SHAPE>(nLines, ln.nu, ln.gamma_d, ln.gamma_l, ln.y, ln.S, ln.i0, ln.i1, nGrid, grid, sigma, factor, accumulate, sorted, dd,
+                           dsigma, os);
 }
-
-// All layers of a profile in ONE launch (blockIdx.y = layer): the per-line prefactors of layer z sit at [k][z][cap]
-// (k = nu, gamma_d, y, S; the two window arrays likewise as ints in slot 4; gamma_l in slot 5), tau_abs[:, z] += sigma_z * factor[z]; whether the
-// bisection applies is read from the layer's flag on the device (no host round trip between the two kernels).
-__global__ void __launch_bounds__(kBlock) k_voigt_profile(int nLines, int Nz, size_t cap, const double *__restrict__ pf,
-                                                          const int *__restrict__ win, int nGrid, const double *__restrict__ grid,
+// All layers of a profile in ONE launch (blockIdx.y = layer): tau_abs[:, z] += sigma_z * factor[z]; whether the bisection applies is
+// read from the layer's flag on the device (no host round trip between the two kernels).
+template <int SHAPE>
+__global__ void __launch_bounds__(kBlock) k_voigt_profile(int nLines, MomLineBlock pf, int nGrid, const double *__restrict__ grid,
                                                           double *__restrict__ tau_abs, const double *__restrict__ factor,
                                                           const int *__restrict__ unsorted) {
   const int z = blockIdx.y;
-  const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
-  voigt_block<false, kVoigtSD>(nLines, pf + lz, pf + ks + lz, nullptr, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz, nGrid,
-                               grid, tau_abs + (size_t)nGrid * z, factor[z], 1, unsorted[z] ? 0 : 1, VoigtDualArgs{}, nullptr);
+  const MomLineView ln = pf.layer(z);
+  voigt_block<false, SHAPE>(nLines, ln.nu, ln.gamma_d, ln.gamma_l, ln.y, ln.S, ln.i0, ln.i1, nGrid, grid, tau_abs + (size_t)nGrid * z,
+                            factor[z], 1, unsorted[z] ? 0 : 1, MomLinePartials{}, nullptr, 0);
 }
-// ... and its Dual run: the partials of layer z's prefactors at dpf[q][k][z][cap] (q = nu, gamma_d, y, S, gamma_l), dtau_abs [nGrid, Nz, 2]
-__global__ void __launch_bounds__(kBlock) k_voigt_profile_dual(int nLines, int Nz, size_t cap, const double *__restrict__ pf,
-                                                               const double *__restrict__ dpf, const int *__restrict__ win, int nGrid,
+// ... and its Dual run: dtau_abs [nGrid, nz, 2]
+template <int SHAPE>
+__global__ void __launch_bounds__(kBlock) k_voigt_profile_dual(int nLines, MomLineBlock pf, MomLinePartialBlock dpf, int nGrid,
                                                                const double *__restrict__ grid, double *__restrict__ tau_abs,
                                                                double *__restrict__ dtau_abs, const double *__restrict__ factor,
                                                                const int *__restrict__ unsorted) {
   const int z = blockIdx.y;
-  const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
-  const VoigtDualArgs dd = {dpf + lz, dpf + 2 * ks + lz, dpf + 4 * ks + lz, dpf + 6 * ks + lz, ks, dtau_abs + (size_t)nGrid * z,
-                            (size_t)nGrid * Nz};
-  voigt_block<true, kVoigtSD>(nLines, pf + lz, pf + ks + lz, nullptr, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz, nGrid,
-                              grid, tau_abs + (size_t)nGrid * z, factor[z], 1, unsorted[z] ? 0 : 1, dd, nullptr);
+  const MomLineView ln = pf.layer(z);
+  voigt_block<true, SHAPE>(nLines, ln.nu, ln.gamma_d, ln.gamma_l, ln.y, ln.S, ln.i0, ln.i1, nGrid, grid, tau_abs + (size_t)nGrid * z,
+                           factor[z], 1, unsorted[z] ? 0 : 1, dpf.layer(z), dtau_abs + (size_t)nGrid * z, (size_t)nGrid * pf.nz);
 }
-
-// The other three shapes: the same four kernels with gamma_l (and, Dual run, its partials) as one more argument.  The
-// Voigt / HW32SD kernels above keep their argument lists, so the default model runs the code it always ran.
-template <int SHAPE>
-__global__ void __launch_bounds__(kBlock) k_lineshape(int nLines, const double *__restrict__ nu, const double *__restrict__ gamma_d,
-                                                      const double *__restrict__ gamma_l, const double *__restrict__ y,
-                                                      const double *__restrict__ S, const int *__restrict__ i0,
-                                                      const int *__restrict__ i1, int nGrid, const double *__restrict__ grid,
-                                                      double *__restrict__ sigma, double factor, int accumulate, int sorted) {
-  voigt_block<false, SHAPE>(nLines, nu, gamma_d, gamma_l, y, S, i0, i1, nGrid, grid, sigma, factor, accumulate, sorted, VoigtDualArgs{},
-                            nullptr);
-}
-template <int SHAPE>
-__global__ void __launch_bounds__(kBlock) k_lineshape_dual(int nLines, const double *__restrict__ nu, const double *__restrict__ gamma_d,
-                                                           const double *__restrict__ gamma_l, const double *__restrict__ y,
-                                                           const double *__restrict__ S, const int *__restrict__ i0,
-                                                           const int *__restrict__ i1, int nGrid, const double *__restrict__ grid,
-                                                           double *__restrict__ sigma, double factor, int accumulate, int sorted,
-                                                           VoigtDualArgs dd, const double *__restrict__ dgl) {
-  voigt_block<true, SHAPE>(nLines, nu, gamma_d, gamma_l, y, S, i0, i1, nGrid, grid, sigma, factor, accumulate, sorted, dd, dgl);
-}
-template <int SHAPE>
-__global__ void __launch_bounds__(kBlock) k_lineshape_profile(int nLines, int Nz, size_t cap, const double *__restrict__ pf,
-                                                              const int *__restrict__ win, int nGrid, const double *__restrict__ grid,
-                                                              double *__restrict__ tau_abs, const double *__restrict__ factor,
-                                                              const int *__restrict__ unsorted) {
-  const int z = blockIdx.y;
-  const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
-  voigt_block<false, SHAPE>(nLines, pf + lz, pf + ks + lz, pf + 5 * ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz,
-                            nGrid, grid, tau_abs + (size_t)nGrid * z, factor[z], 1, unsorted[z] ? 0 : 1, VoigtDualArgs{}, nullptr);
-}
-template <int SHAPE>
-__global__ void __launch_bounds__(kBlock) k_lineshape_profile_dual(int nLines, int Nz, size_t cap, const double *__restrict__ pf,
-                                                                   const double *__restrict__ dpf, const int *__restrict__ win, int nGrid,
-                                                                   const double *__restrict__ grid, double *__restrict__ tau_abs,
-                                                                   double *__restrict__ dtau_abs, const double *__restrict__ factor,
-                                                                   const int *__restrict__ unsorted) {
-  const int z = blockIdx.y;
-  const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
-  const VoigtDualArgs dd = {dpf + lz, dpf + 2 * ks + lz, dpf + 4 * ks + lz, dpf + 6 * ks + lz, ks, dtau_abs + (size_t)nGrid * z,
-                            (size_t)nGrid * Nz};
-  voigt_block<true, SHAPE>(nLines, pf + lz, pf + ks + lz, pf + 5 * ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, win + lz, win + ks + lz,
-                           nGrid, grid, tau_abs + (size_t)nGrid * z, factor[z], 1, unsorted[z] ? 0 : 1, dd, dpf + 8 * ks + lz);
-}
-
-// STMT(shape) for one of the three shapes that are not the default
-#define MOM_SHAPE_SWITCH(shape, STMT)      \
-  switch (shape) {                         \
-    case kVoigt15: STMT(kVoigt15); break;  \
-    case kDoppler: STMT(kDoppler); break;  \
-    default: STMT(kLorentz); break;        \
-  }
+// the instantiations of a kernel template, indexed by LineShape: the one place the shape is dispatched
+#define MOM_BY_SHAPE(K) {K<kVoigtSD>, K<kVoigt15>, K<kDoppler>, K<kLorentz>}
+decltype(&k_voigt<kVoigtSD>) const kValueKernel[4] = MOM_BY_SHAPE(k_voigt);
+decltype(&k_voigt_dual<kVoigtSD>) const kDualKernel[4] = MOM_BY_SHAPE(k_voigt_dual);
+decltype(&k_voigt_profile<kVoigtSD>) const kProfileKernel[4] = MOM_BY_SHAPE(k_voigt_profile);
+decltype(&k_voigt_profile_dual<kVoigtSD>) const kProfileDualKernel[4] = MOM_BY_SHAPE(k_voigt_profile_dual);
+#undef MOM_BY_SHAPE
 
 thread_local double v_last_ms = 0.0;
 
 }  // namespace
 
-// one launch for all lines on `st` (device pointers); used by mom_voigt_xsec below and by the handle-level
-// mom_voigt_tau_abs (mom_optics.hip), which accumulates straight into the resident tau_abs table
 // ---------------------------------------------------------------------------------------------------------------------
 // Per-line prefactors of compute_absorption_cross_section (compute_absorption_cross_section.jl:73-107) on the device, from
 // ONE resident HITRAN table per absorber: pressure shift (:79), Lorentz half width (:82-84), Doppler half width (:87-88),
@@ -566,19 +505,12 @@ __device__ __forceinline__ double interp_index(const double *grid, int n, double
   const double slope = 1.0 / (grid[lo + 1] - grid[lo]);
   return slope * (x - grid[lo]) + (double)(lo + 1);
 }
-// Dual run: where the partials of nu, gamma_d, y, S, gamma_l of one layer go (partial k of line j at p[j + ks k]; k = 0 pressure,
-// 1 temperature) and d cgd / dT
-struct LineDualOut {
-  double *dnu, *dgd, *dy, *dS, *dgl;
-  size_t ks;
-  double dcgd;
-};
 // DUAL: the same statements on ForwardDiff.Dual numbers -- every value below is formed exactly as in the value run, the
-// partials follow each statement by its rule; windows and the sortedness flag come from the values
+// partials follow each statement by its rule (into dd, with dcgd = d cgd / dT); windows and the sortedness flag come from the values
 template <bool DUAL>
 __device__ __forceinline__ void line_prefactors_one(int j, const MomLineTable &tb, int nGrid, const double *grid, double p, double T,
-                                                    double vmr, double wing, double cgd, double *nu, double *gd, double *yy, double *SS,
-                                                    double *gll, int *i0, int *i1, int *unsorted, const LineDualOut dd) {
+                                                    double vmr, double wing, double cgd, const MomLineOut out, int *unsorted,
+                                                    const MomLinePartialsOut dd, double dcgd) {
 #pragma clang fp contract(off)
   if (j >= tb.nLines) return;
   const double p_ref = 1013.25, t_ref = 296.0, c2 = 1.4387769, cLn2 = 0.6931471805599;
@@ -605,12 +537,12 @@ __device__ __forceinline__ void line_prefactors_one(int j, const MomLineTable &t
     }
     S = S * corr;
   }
-  nu[j] = v;
-  gd[j] = g;
+  out.nu[j] = v;
+  out.gamma_d[j] = g;
   const double ynum = sqrt(cLn2) * gl;
-  yy[j] = ynum / g;
-  SS[j] = S;
-  gll[j] = gl;   // line_shape! takes gamma_l next to y (:118-124): the fifth prefactor, read by the Lorentz shape
+  out.y[j] = ynum / g;
+  out.S[j] = S;
+  out.gamma_l[j] = gl;   // line_shape! takes gamma_l next to y (:118-124): the fifth prefactor, read by the Lorentz shape
   if constexpr (DUAL) {
     // nu = nu0 + p / p_ref delta;  gamma_l = lin(p) (t_ref / T)^n: d/dp = the bracket times the power (no gamma_l / p),
     // d/dT = lin n (t_ref / T)^(n - 1) (-t_ref / T^2);  gamma_d = cgd(T) nu0 / sqrt(w);  y = sqrt(ln 2) gamma_l / gamma_d
@@ -618,21 +550,21 @@ __device__ __forceinline__ void line_prefactors_one(int j, const MomLineTable &t
     const double dgl_p = (tb.g_air[j] * (1 - vmr) / p_ref + tb.g_self[j] * vmr / p_ref) * tpow;
     const double lin = tb.g_air[j] * (1 - vmr) * p / p_ref + tb.g_self[j] * vmr * p / p_ref;
     const double dgl_T = lin * (n * pow(t_ref / T, n - 1) * (-(t_ref / (T * T))));
-    const double dg_T = dd.dcgd * nu0 / tb.sqw[j];
+    const double dg_T = dcgd * nu0 / tb.sqw[j];
     dd.dnu[j] = (1 / p_ref) * tb.d_air[j];
     dd.dnu[j + dd.ks] = 0.0;
-    dd.dgd[j] = 0.0;
-    dd.dgd[j + dd.ks] = dg_T;
+    dd.dgamma_d[j] = 0.0;
+    dd.dgamma_d[j + dd.ks] = dg_T;
     dd.dy[j] = sqrt(cLn2) * dgl_p * (1 / g);
     dd.dy[j + dd.ks] = sqrt(cLn2) * dgl_T * (1 / g) + dg_T * (-(ynum / (g * g)));
     dd.dS[j] = 0.0;
     dd.dS[j + dd.ks] = dS_T;
-    dd.dgl[j] = dgl_p;
-    dd.dgl[j + dd.ks] = dgl_T;
+    dd.dgamma_l[j] = dgl_p;
+    dd.dgamma_l[j + dd.ks] = dgl_T;
   }
   const int a = (int)rint(interp_index(grid, nGrid, v - wing, 1.0)), b = (int)rint(interp_index(grid, nGrid, v + wing, (double)nGrid));
-  i0[j] = a;
-  i1[j] = b;
+  out.i0[j] = a;
+  out.i1[j] = b;
   if (j > 0) {  // does the Voigt kernel's bisection apply?  (window starts and stops non-decreasing in the line index)
     const double vp = tb.nu0[j - 1] + p / p_ref * tb.d_air[j - 1];
     const int ap = (int)rint(interp_index(grid, nGrid, vp - wing, 1.0)), bp = (int)rint(interp_index(grid, nGrid, vp + wing, (double)nGrid));
@@ -640,106 +572,50 @@ __device__ __forceinline__ void line_prefactors_one(int j, const MomLineTable &t
   }
 }
 __global__ void k_line_prefactors(MomLineTable tb, int nGrid, const double *grid, double p, double T, double vmr, double wing,
-                                  double cgd, double *nu, double *gd, double *yy, double *SS, double *gll, int *i0, int *i1,
-                                  int *unsorted) {
-  line_prefactors_one<false>(blockIdx.x * blockDim.x + threadIdx.x, tb, nGrid, grid, p, T, vmr, wing, cgd, nu, gd, yy, SS, gll, i0, i1,
-                             unsorted, LineDualOut{});
+                                  double cgd, MomLineOut out, int *unsorted) {
+  line_prefactors_one<false>(blockIdx.x * blockDim.x + threadIdx.x, tb, nGrid, grid, p, T, vmr, wing, cgd, out, unsorted, MomLinePartialsOut{},
+                             0.0);
 }
-// blockIdx.y = layer; prm = [p | T | cgd][Nz]; outputs at [k][z][cap], gamma_l at k = 5 (see k_voigt_profile)
-__global__ void k_line_prefactors_profile(MomLineTable tb, int Nz, size_t cap, int nGrid, const double *grid, const double *prm,
-                                          double vmr, double wing, double *pf, int *win, int *unsorted) {
-  const int z = blockIdx.y;
-  const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
-  line_prefactors_one<false>(blockIdx.x * blockDim.x + threadIdx.x, tb, nGrid, grid, prm[z], prm[Nz + z], vmr, wing, prm[2 * Nz + z], pf + lz,
-                             pf + ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, pf + 5 * ks + lz, win + lz, win + ks + lz, unsorted + z,
-                             LineDualOut{});
+// blockIdx.y = layer; prm = [p | T | cgd | factor][nz], Dual run: | d cgd / dT and the partials into dpf
+template <bool DUAL>
+__global__ void k_line_prefactors_profile(MomLineTable tb, MomLineBlock pf, MomLinePartialBlock dpf, int nGrid, const double *grid,
+                                          const double *prm, double vmr, double wing, int *unsorted) {
+  const int z = blockIdx.y, Nz = pf.nz;
+  line_prefactors_one<DUAL>(blockIdx.x * blockDim.x + threadIdx.x, tb, nGrid, grid, prm[z], prm[Nz + z], vmr, wing, prm[2 * Nz + z], pf.layer(z),
+                            unsorted + z, DUAL ? dpf.layer(z) : MomLinePartialsOut{}, DUAL ? prm[4 * Nz + z] : 0.0);
 }
-// Dual run: prm = [p | T | cgd | factor | d cgd / dT][Nz]; partials at dpf[q][k][z][cap], q = 0 .. 4 (see k_voigt_profile_dual)
-__global__ void k_line_prefactors_profile_dual(MomLineTable tb, int Nz, size_t cap, int nGrid, const double *grid, const double *prm,
-                                               double vmr, double wing, double *pf, double *dpf, int *win, int *unsorted) {
-  const int z = blockIdx.y;
-  const size_t lz = (size_t)z * cap, ks = (size_t)Nz * cap;
-  const LineDualOut dd = {dpf + lz, dpf + 2 * ks + lz, dpf + 4 * ks + lz, dpf + 6 * ks + lz, dpf + 8 * ks + lz, ks, prm[4 * Nz + z]};
-  line_prefactors_one<true>(blockIdx.x * blockDim.x + threadIdx.x, tb, nGrid, grid, prm[z], prm[Nz + z], vmr, wing, prm[2 * Nz + z], pf + lz,
-                            pf + ks + lz, pf + 2 * ks + lz, pf + 3 * ks + lz, pf + 5 * ks + lz, win + lz, win + ks + lz, unsorted + z, dd);
-}
-hipError_t mom_voigt_profile_launch(hipStream_t st, int shape, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
-                                    const double *prm, double vmr, double wing, double *pf, int *win, int *unsorted, double *tau_abs,
-                                    const double *factor) {
-  if (tb.nLines <= 0 || Nz <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_line_prefactors_profile, dim3((tb.nLines + 255) / 256, Nz), dim3(256), 0, st, tb, Nz, cap, nGrid, grid, prm, vmr,
-                     wing, pf, win, unsorted);
+hipError_t mom_voigt_profile_launch(hipStream_t st, int shape, const MomLineTable &tb, const MomLineBlock &pf, const MomLinePartialBlock *dpf,
+                                    int nGrid, const double *grid, const double *prm, double vmr, double wing, int *unsorted,
+                                    double *tau_abs, double *dtau_abs, const double *factor) {
+  if (tb.nLines <= 0 || pf.nz <= 0) return hipSuccess;
+  hipLaunchKernelGGL(dpf ? k_line_prefactors_profile<true> : k_line_prefactors_profile<false>, dim3((tb.nLines + 255) / 256, pf.nz), dim3(256),
+                     0, st, tb, pf, dpf ? *dpf : MomLinePartialBlock{}, nGrid, grid, prm, vmr, wing, unsorted);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const dim3 blocks((nGrid + kBlock - 1) / kBlock, Nz);
-#define MOM_LAUNCH(SH) \
-  hipLaunchKernelGGL(k_lineshape_profile<SH>, blocks, dim3(kBlock), 0, st, tb.nLines, Nz, cap, pf, win, nGrid, grid, tau_abs, factor, unsorted)
-  if (shape == kVoigtSD)
-    hipLaunchKernelGGL(k_voigt_profile, blocks, dim3(kBlock), 0, st, tb.nLines, Nz, cap, pf, win, nGrid, grid, tau_abs, factor, unsorted);
+  const dim3 blocks((nGrid + kBlock - 1) / kBlock, pf.nz);
+  if (dpf)
+    hipLaunchKernelGGL(kProfileDualKernel[shape], blocks, dim3(kBlock), 0, st, tb.nLines, pf, *dpf, nGrid, grid, tau_abs, dtau_abs, factor,
+                       unsorted);
   else
-    MOM_SHAPE_SWITCH(shape, MOM_LAUNCH)
-#undef MOM_LAUNCH
-  return hipGetLastError();
-}
-hipError_t mom_voigt_profile_dual_launch(hipStream_t st, int shape, const MomLineTable &tb, int Nz, size_t cap, int nGrid, const double *grid,
-                                         const double *prm, double vmr, double wing, double *pf, double *dpf, int *win, int *unsorted,
-                                         double *tau_abs, double *dtau_abs, const double *factor) {
-  if (tb.nLines <= 0 || Nz <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_line_prefactors_profile_dual, dim3((tb.nLines + 255) / 256, Nz), dim3(256), 0, st, tb, Nz, cap, nGrid, grid, prm,
-                     vmr, wing, pf, dpf, win, unsorted);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  const dim3 blocks((nGrid + kBlock - 1) / kBlock, Nz);
-#define MOM_LAUNCH(SH)                                                                                                                \
-  hipLaunchKernelGGL(k_lineshape_profile_dual<SH>, blocks, dim3(kBlock), 0, st, tb.nLines, Nz, cap, pf, dpf, win, nGrid, grid, tau_abs, \
-                     dtau_abs, factor, unsorted)
-  if (shape == kVoigtSD)
-    hipLaunchKernelGGL(k_voigt_profile_dual, blocks, dim3(kBlock), 0, st, tb.nLines, Nz, cap, pf, dpf, win, nGrid, grid, tau_abs, dtau_abs,
-                       factor, unsorted);
-  else
-    MOM_SHAPE_SWITCH(shape, MOM_LAUNCH)
-#undef MOM_LAUNCH
+    hipLaunchKernelGGL(kProfileKernel[shape], blocks, dim3(kBlock), 0, st, tb.nLines, pf, nGrid, grid, tau_abs, factor, unsorted);
   return hipGetLastError();
 }
 hipError_t mom_line_prefactors_launch(hipStream_t st, const MomLineTable &tb, int nGrid, const double *grid, double p, double T,
-                                      double vmr, double wing, double cgd, double *nu, double *gd, double *y, double *S, double *gl,
-                                      int *i0, int *i1, int *unsorted) {
+                                      double vmr, double wing, double cgd, const MomLineOut &out, int *unsorted) {
   if (tb.nLines <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_line_prefactors, dim3((tb.nLines + 255) / 256), dim3(256), 0, st, tb, nGrid, grid, p, T, vmr, wing, cgd, nu,
-                     gd, y, S, gl, i0, i1, unsorted);
+  hipLaunchKernelGGL(k_line_prefactors, dim3((tb.nLines + 255) / 256), dim3(256), 0, st, tb, nGrid, grid, p, T, vmr, wing, cgd, out, unsorted);
   return hipGetLastError();
 }
 
-hipError_t mom_voigt_launch(hipStream_t st, int shape, int nLines, const double *nu, const double *gamma_d, const double *gamma_l,
-                            const double *y, const double *S, const int *i0, const int *i1, int nGrid, const double *grid, double *out,
-                            double factor, int accumulate, int sorted) {
+// one launch for all lines on `st` (device pointers); used by mom_voigt_xsec below and by the handle-level
+// mom_voigt_tau_abs (mom_optics.hip), which accumulates straight into the resident tau_abs table
+hipError_t mom_voigt_launch(hipStream_t st, int shape, int nLines, const MomLineView &ln, const MomLinePartials *dln, int nGrid,
+                            const double *grid, double *out, double *dout, size_t os, double factor, int accumulate, int sorted) {
   const dim3 blocks((nGrid + kBlock - 1) / kBlock);
-#define MOM_LAUNCH(SH)                                                                                                            \
-  hipLaunchKernelGGL(k_lineshape<SH>, blocks, dim3(kBlock), 0, st, nLines, nu, gamma_d, gamma_l, y, S, i0, i1, nGrid, grid, out, factor, \
-                     accumulate, sorted)
-  if (shape == kVoigtSD)
-    hipLaunchKernelGGL(k_voigt, blocks, dim3(kBlock), 0, st, nLines, nu, gamma_d, y, S, i0, i1, nGrid, grid, out, factor, accumulate, sorted);
+  if (dln)
+    hipLaunchKernelGGL(kDualKernel[shape], blocks, dim3(kBlock), 0, st, nLines, ln, *dln, nGrid, grid, out, dout, os, factor, accumulate, sorted);
   else
-    MOM_SHAPE_SWITCH(shape, MOM_LAUNCH)
-#undef MOM_LAUNCH
-  return hipGetLastError();
-}
-
-hipError_t mom_voigt_dual_launch(hipStream_t st, int shape, int nLines, const double *nu, const double *gamma_d, const double *gamma_l,
-                                 const double *y, const double *S, const int *i0, const int *i1, int nGrid, const double *grid,
-                                 double *out, double factor, int accumulate, int sorted, const double *dnu, const double *dgd,
-                                 const double *dgl, const double *dy, const double *dS, size_t ks, double *dout, size_t os) {
-  const dim3 blocks((nGrid + kBlock - 1) / kBlock);
-  const VoigtDualArgs dd = {dnu, dgd, dy, dS, ks, dout, os};
-#define MOM_LAUNCH(SH)                                                                                                                 \
-  hipLaunchKernelGGL(k_lineshape_dual<SH>, blocks, dim3(kBlock), 0, st, nLines, nu, gamma_d, gamma_l, y, S, i0, i1, nGrid, grid, out, factor, \
-                     accumulate, sorted, dd, dgl)
-  if (shape == kVoigtSD)
-    hipLaunchKernelGGL(k_voigt_dual, blocks, dim3(kBlock), 0, st, nLines, nu, gamma_d, y, S, i0, i1, nGrid, grid, out, factor, accumulate,
-                       sorted, dd);
-  else
-    MOM_SHAPE_SWITCH(shape, MOM_LAUNCH)
-#undef MOM_LAUNCH
+    hipLaunchKernelGGL(kValueKernel[shape], blocks, dim3(kBlock), 0, st, nLines, ln, nGrid, grid, out, factor, accumulate, sorted);
   return hipGetLastError();
 }
 
@@ -780,12 +656,12 @@ int lineshape_xsec_run(const char *fn, int device, int shape, int nLines, const 
       return MOM_EINVAL;
     }
   int rc = MOM_OK;
-  // one device allocation (lines | grid | sigma | windows; Dual run: the line partials and dsigma in front of the windows) and
-  // one pinned-free staging copy per array on a private stream; callers that evaluate many layers should use the
-  // handle-level mom_voigt_tau_abs, which keeps all of this resident
-  const size_t lb = (size_t)(nLines > 0 ? nLines : 1);
-  const size_t dual_doubles = dual ? 10 * lb + 2 * (size_t)nGrid : 0;
-  const size_t bytes = (5 * lb + 2 * (size_t)nGrid + dual_doubles) * sizeof(double) + 2 * lb * sizeof(int);
+  // one device allocation (a one-layer line block | grid | sigma; Dual run: | its partial block | dsigma) and one pinned-free
+  // staging copy per array on a private stream; callers that evaluate many layers should use the handle-level mom_voigt_tau_abs,
+  // which keeps all of this resident
+  MomLineBlock blk = {nullptr, (size_t)(nLines > 0 ? nLines : 1), 1};
+  MomLinePartialBlock dblk = blk.partials(nullptr);
+  const size_t bytes = (blk.doubles() + 2 * (size_t)nGrid + (dual ? dblk.doubles() + 2 * (size_t)nGrid : 0)) * sizeof(double);
   char *base = nullptr;
   hipStream_t st = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -804,35 +680,31 @@ int lineshape_xsec_run(const char *fn, int device, int shape, int nLines, const 
   VCHK(hipStreamCreate(&st));
   VCHK(hipMalloc((void **)&base, bytes));
   {
-    double *d_line = (double *)base, *d_grid = d_line + 5 * lb, *d_sig = d_grid + nGrid;
-    double *d_dline = d_sig + nGrid, *d_dsig = d_dline + (dual ? 10 * lb : 0);   // Dual run only: [q][k][lb], [nGrid, 2]
-    int *d_win = (int *)(d_sig + nGrid + dual_doubles);
+    blk.base = (double *)base;
+    double *d_grid = blk.base + blk.doubles(), *d_sig = d_grid + nGrid;
+    dblk.base = d_sig + nGrid;
+    double *d_dsig = dual ? dblk.base + dblk.doubles() : nullptr;   // [nGrid, 2]
+    MomLineOut ln = blk.layer(0);
+    MomLinePartialsOut dln = dblk.layer(0);
     for (int k = 0; k < 5; ++k)   // an array the shape does not read stays as allocated: the kernel never loads it
       if (nLines && line[k] && mom_shape_reads(shape, k))
-        VCHK(hipMemcpyAsync(d_line + k * lb, line[k], (size_t)nLines * sizeof(double), hipMemcpyHostToDevice, st));
+        VCHK(hipMemcpyAsync(ln.prefactor(k), line[k], (size_t)nLines * sizeof(double), hipMemcpyHostToDevice, st));
     if (nLines) {
-      VCHK(hipMemcpyAsync(d_win, ind_start, (size_t)nLines * sizeof(int), hipMemcpyHostToDevice, st));
-      VCHK(hipMemcpyAsync(d_win + lb, ind_stop, (size_t)nLines * sizeof(int), hipMemcpyHostToDevice, st));
+      VCHK(hipMemcpyAsync(ln.i0, ind_start, (size_t)nLines * sizeof(int), hipMemcpyHostToDevice, st));
+      VCHK(hipMemcpyAsync(ln.i1, ind_stop, (size_t)nLines * sizeof(int), hipMemcpyHostToDevice, st));
     }
     VCHK(hipMemcpyAsync(d_grid, grid, (size_t)nGrid * sizeof(double), hipMemcpyHostToDevice, st));
-    const double *d_part[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int q = 0; q < 5 && dual && nLines; ++q) {
-      if (!dpart[q] || !mom_shape_reads(shape, q)) continue;
-      for (int k = 0; k < 2; ++k)   // host [nLines, 2] column-major -> [k][lb]
-        VCHK(hipMemcpyAsync(d_dline + (2 * q + k) * lb, dpart[q] + (size_t)nLines * k, (size_t)nLines * sizeof(double),
+    for (int q = 0; q < 5 && dual; ++q) {
+      if (!nLines || !dpart[q] || !mom_shape_reads(shape, q)) { dln.partial(q) = nullptr; continue; }   // null: zeros
+      for (int k = 0; k < 2; ++k)   // host [nLines, 2] column-major
+        VCHK(hipMemcpyAsync(dln.partial(q) + dln.ks * k, dpart[q] + (size_t)nLines * k, (size_t)nLines * sizeof(double),
                             hipMemcpyHostToDevice, st));
-      d_part[q] = d_dline + 2 * q * lb;
     }
+    const MomLinePartials dread = dln;
     VCHK(hipEventCreate(&e0));
     VCHK(hipEventCreate(&e1));
     VCHK(hipEventRecord(e0, st));
-    if (dual)
-      VCHK(mom_voigt_dual_launch(st, shape, nLines, d_line, d_line + lb, d_line + 4 * lb, d_line + 2 * lb, d_line + 3 * lb, d_win,
-                                 d_win + lb, nGrid, d_grid, d_sig, 1.0, 0, sorted, d_part[0], d_part[1], d_part[4], d_part[2], d_part[3],
-                                 lb, d_dsig, (size_t)nGrid));
-    else
-      VCHK(mom_voigt_launch(st, shape, nLines, d_line, d_line + lb, d_line + 4 * lb, d_line + 2 * lb, d_line + 3 * lb, d_win, d_win + lb,
-                            nGrid, d_grid, d_sig, 1.0, 0, sorted));
+    VCHK(mom_voigt_launch(st, shape, nLines, ln, dual ? &dread : nullptr, nGrid, d_grid, d_sig, d_dsig, (size_t)nGrid, 1.0, 0, sorted));
     VCHK(hipEventRecord(e1, st));
     VCHK(hipMemcpyAsync(sigma, d_sig, (size_t)nGrid * sizeof(double), hipMemcpyDeviceToHost, st));
     if (dual) VCHK(hipMemcpyAsync(dsigma, d_dsig, 2 * (size_t)nGrid * sizeof(double), hipMemcpyDeviceToHost, st));

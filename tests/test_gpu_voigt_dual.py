@@ -1,4 +1,4 @@
-"""The Dual run of the Voigt absorption path (k_voigt_dual, k_line_prefactors_profile_dual in csrc/voigt.hip; the
+"""The Dual run of the Voigt absorption path (k_voigt_dual, k_line_prefactors_profile<true> in csrc/voigt.hip; the
 mom_voigt_*_dual / mom_absorption_get_partials entry points) against the forward-mode oracle tests/absdual_oracle.py:
 sigma and its partials with respect to (p, T) as absorption_cross_section(...; autodiff = true) returns them."""
 import dataclasses

@@ -256,3 +256,73 @@ def test_two_absorbers_of_different_order_on_one_handle(rtamd, cref, lines, orde
         distance(tau_d[:, iz], ref[:, iz], f"tau_abs layer {iz}, Dual run", 1e-9)
         for k in range(2):
             distance(dtau[k][:, iz], dref[k][:, iz], f"dtau_abs[{k}] layer {iz}", 1e-6)
+
+
+# ---- F. the handle's line buffers across entry points ------------------------------------------------------------------
+def test_line_buffers_across_entry_points_on_one_handle(rtamd):
+    """One handle per column (value, Dual) takes, in this order: a three-layer profile of 300 lines, the single-layer device
+    entry, a host-prefactor call on one layer, a three-layer profile of 2500 lines (begin=False) -- so the resident line buffers
+    change their layer count twice and outgrow their first capacity (2048 lines) -- and then the getters.  600 grid points: three
+    workgroups, the last one partial.  Every call is repeated alone on a fresh handle; tau_abs and dtau_abs of the sequence equal
+    the fresh tables added on the host in the same order, and the getters return the last layer of the last call, all bitwise."""
+    ab = rtamd.absorption
+    grid = np.linspace(12903.0, 13245.0, 600)
+    small, big = ab.synthetic_o2a_lines(300), ab.synthetic_o2a_lines(2500, seed=4321)
+    p, T, f = vc.P_FULL[1:], vc.T_FULL[1:], vc.VCD[1:] * vc.PROFILE_VMR
+    wing, S = 3.0, grid.size
+    kw = dict(wing_cutoff=wing, model_vmr=vc.MODEL_VMR, device_prefactors=True)
+    pf, *dpf = ab.line_prefactors_dual(small, grid, p[0], T[0], vmr=vc.MODEL_VMR, wing_cutoff=wing, with_γ_l=True)
+    assert pf.ν.size == 300
+    line, dline = (pf.ν, pf.γ_d, pf.γ_l, pf.y, pf.S), (dpf[0], dpf[1], dpf[4], dpf[2], dpf[3])
+
+    def calls(dual):
+        """the four calls of a column, each a function of (handle, first call on it?)"""
+        def layer(h, first):
+            if first:
+                h.absorption_begin(3, grid)
+                assert ab.resident_line_table(h, small, grid, wing) == 300
+            h.voigt_tau_abs_layer(2, p[1], T[1], vc.MODEL_VMR, wing, f[1])
+
+        def host(h, first):
+            if first:
+                h.absorption_begin(3, grid)
+            if dual:
+                h.lineshape_tau_abs_dual(1, *line, *dline, pf.ind_start, pf.ind_stop, f[0])
+            else:
+                h.lineshape_tau_abs(1, *line, pf.ind_start, pf.ind_stop, f[0])
+
+        def profile(tab):
+            return lambda h, first: ab.compute_absorption_profile(h, tab, grid, p, T, vc.VCD[1:], vc.PROFILE_VMR, begin=first, dual=dual, **kw)
+        return [profile(small), layer, host, profile(big)]
+
+    def tables(h, dual, partials_exist=True):
+        return h.absorption_get(), (h.absorption_get_partials() if dual and partials_exist else np.zeros((2, S, 3)))
+
+    def getters(h, dual):
+        out = h.absorption_get_prefactors() + [h.absorption_get_gamma_l()]
+        if dual:
+            g, dg = h.absorption_get_gamma_l(partials=True)
+            out += h.absorption_get_prefactor_partials() + [g, dg]
+        return out
+
+    for dual in (False, True):
+        seq = calls(dual)
+        with rtamd.Handle(4, 1, S, 1) as h:
+            for i, call in enumerate(seq):
+                call(h, i == 0)
+            tau, dtau = tables(h, dual)
+            got = getters(h, dual)
+        tau_ref, dtau_ref = np.zeros((S, 3)), np.zeros((2, S, 3))
+        for i, call in enumerate(seq):
+            with rtamd.Handle(4, 1, S, 1) as fresh:
+                call(fresh, True)
+                t, dt = tables(fresh, dual, partials_exist=i != 1)      # the single-layer device entry has no Dual run
+                tau_ref, dtau_ref = tau_ref + t, dtau_ref + dt
+                ref = getters(fresh, dual) if i == len(seq) - 1 else None
+        assert tau.max() > 0 and np.all(tau[:, 0] > 0)
+        assert np.array_equal(tau, tau_ref), f"tau_abs, dual={dual}: {np.flatnonzero((tau != tau_ref).any(axis=1))[:8]}"
+        if dual:
+            assert np.abs(dtau).max() > 0 and np.array_equal(dtau, dtau_ref)
+        assert got[0].size == 2500 and len(got) == len(ref)
+        for k, (a, b) in enumerate(zip(got, ref)):
+            assert np.array_equal(a, b), f"getter array {k}, dual={dual}"

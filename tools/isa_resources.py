@@ -26,5 +26,5 @@ for r in rows:
     if d in seen or "k_" not in d:
         continue
     seen.add(d)
-    print(f"{r.get('VGPRs','?'):>5} {r.get('AGPRs','?'):>5} {r.get('SGPRs','?'):>5} {r.get('VGPRs Spill','?'):>6} "
+    print(f"{r.get('VGPRs','?'):>5} {r.get('AGPRs','?'):>5} {r.get('SGPRs', r.get('TotalSGPRs','?')):>5} {r.get('VGPRs Spill','?'):>6} "
           f"{r.get('ScratchSize [bytes/lane]','?'):>7} {r.get('LDS Size [bytes/block]','?'):>7} {r.get('Occupancy [waves/SIMD]','?'):>5}  {d[:110]}")
