@@ -436,6 +436,43 @@ int mom_scene_set_partials(mom_t *h, int P, const double *dtau, const double *dv
 int mom_rt_run_dual(mom_t *h);
 int mom_get_RT_partials(mom_t *h, double *dR_SFI, double *dT_SFI);
 int mom_get_hdr_partials(mom_t *h, double *dhdr, double *dbhr_uw, double *dbhr_dw);
+/* ---- The Dual run of the device-side layer optics: the scene's partials formed ON THE DEVICE ------------------------
+ * The reference gets dτ, dϖ and the partials of the basis weights by running constructCoreOpticalProperties / createAero
+ * (compEffectiveLayerProperties.jl:1-85) and the `+` of types.jl:632-678 on ForwardDiff.Dual element types.  This is that run
+ * for a scene that came from mom_scene_set_optics: k_optics_dual (csrc/mom_optics.hip) follows k_optics statement by statement
+ * with the product and quotient rules -- the Rayleigh start, each aerosol's `+` with its three cases (types.jl:641-661, decided
+ * on the values like every boolean), the gas term (types.jl:672-678) -- and writes dtau, dvarpi [S, Nz, P] and dzw [K, S, Nz, P]
+ * straight into the buffers mom_rt_run_dual reads.  Lines -> Dual line shape (mom_voigt_tau_abs_profile_dual,
+ * mom_lut_tau_abs_profile_dual) -> Dual layer optics -> mom_rt_run_dual is then one device pipeline: neither dtau_abs nor the
+ * scene's partials cross the bus.  Float64 handles.
+ *
+ * mom_scene_set_optics_partials   mom_scene_set_partials for such a scene, from the partials of the INGREDIENTS.  All layouts have
+ *                          the partial index as the SLOWEST axis; every array may be NULL (no dependence):
+ *                            w_abs [Nz, 3, P]   chain weights onto the resident absorption tables,
+ *                                 dτ_abs[s,z,k] = dtau_abs[s,z,0] w[z,0,k] + dtau_abs[s,z,1] w[z,1,k] + tau_abs[s,z] w[z,2,k]:
+ *                                 rows 0 and 1 are ∂p_z/∂x_k and ∂T_z/∂x_k (each layer's τ_abs depends on its own p and T only),
+ *                                 row 2 is the relative change of the layer's gas column, ∂ln(vcd vmr)_z/∂x_k, which needs no Dual
+ *                                 absorption call.  A nonzero row-0/1 weight without a resident dtau_abs table: MOM_ESTATE.
+ *                            w_rayl [Nz, P]     dτ_rayl[s,z,k] = tau_rayl[s,z] w_rayl[z,k]: the Rayleigh depth of a layer is a
+ *                                 spectral factor times the layer's column (atmo_prof.jl:210-224), so any parameter acts on it as a
+ *                                 per-layer relative change.  ϖ_Cabannes carries no partial.
+ *                            dtau_aer [nAer, Nz, P], domega_aer, dft_aer [nAer, P]   the partials of mom_scene_set_optics'
+ *                                 arguments; createAero on Duals (compEffectiveLayerProperties.jl:80-85) is O(nAer Nz P) host work
+ *                                 like its value form (mom_scene_set_optics keeps host copies of the three for it).
+ *                            dZpp, dZmp, dalbedo, dRsurf, dalbedo_spec   as in mom_scene_set_partials, by the same code.
+ *                          dzw exists only when nAer > 0 and one of w_rayl, dtau_aer, domega_aer, dft_aer is given (otherwise it
+ *                          is identically zero and the sweep keeps skipping it).  P = 0 clears the partials.  0 <= P <= 64.
+ *                          MOM_ESTATE without a resident scene, for a scene that came from mom_scene_set (host optics), and when
+ *                          mom_absorption_begin / mom_absorption_set was called after the mom_scene_set_optics that made the scene
+ *                          (the tables are no longer the scene's).  mom_timers right after the call reports the HIP-event time
+ *                          of the kernel as its total.
+ * mom_scene_get_partials   the resident dtau, dvarpi [S, Nz, P] and dzw [K, S, Nz, P] to the host, whichever of the two setters
+ *                          produced them (test access).  NULL skips an array; an absent device buffer reads as zeros; without
+ *                          partials (P = 0 or never set): MOM_ESTATE. */
+int mom_scene_set_optics_partials(mom_t *h, int P, const double *w_abs, const double *w_rayl, const double *dtau_aer,
+                                  const double *domega_aer, const double *dft_aer, const double *dZpp, const double *dZmp,
+                                  const double *dalbedo, const double *dRsurf, const double *dalbedo_spec);
+int mom_scene_get_partials(mom_t *h, double *dtau, double *dvarpi, double *dzw);
 
 /* rt_run_test_ms(RS_type::noRS, sensor_levels, model, iBand) (src/CoreRT/rt_run_multisensor.jl:14-191) for the resident
  * scene: sensors inside the atmosphere.  sensor_levels[ims] = 0 is the TOA/BOA pair (uwJ = R_SFI, dwJ = T_SFI of

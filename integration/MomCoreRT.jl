@@ -147,6 +147,21 @@ function rt_run_dual(RS_type::noRS, model::vSmartMOM_Model, iBand, arch::MI355X,
         close(h)
     end
 end
+
+"""
+The partials of a scene that came from mom_scene_set_optics, formed on the device from the partials of the INGREDIENTS (what the
+Dual numbers carry into constructCoreOpticalProperties / createAero, compEffectiveLayerProperties.jl:1-85, and the `+` of
+types.jl:632-678) instead of mom_scene_set_partials: w_abs [Nz, 3, P] = (∂p_z/∂x, ∂T_z/∂x, ∂ln(vcd vmr)_z/∂x) onto the resident
+∂τ_abs / τ_abs tables of compute_absorption_profile!(...; dual = true), w_rayl [Nz, P] = the relative change of the layer's
+Rayleigh depth (atmo_prof.jl:210-224), dτ_aer [nAer, Nz, P], dω̃, dfᵗ [nAer, P]; `nothing` = no dependence.  `surf`: the partials
+of the bases and the surface as rt_run_dual passes them.  mom_rt_run_dual follows; neither ∂τ_abs nor dτ, dϖ, dzw cross the bus.
+"""
+function scene_set_optics_partials!(h::MomHandle, P; w_abs = nothing, w_rayl = nothing, dτ_aer = nothing, dω̃ = nothing, dfᵗ = nothing,
+                                    surf = (dZpp = nothing, dZmp = nothing, dalbedo = nothing, dRsurf = nothing, dalbedo_spec = nothing))
+    nn(x) = x === nothing ? C_NULL : collect(Float64, x)
+    MomCore.mom_scene_set_optics_partials!(h.ptr, P, nn(w_abs), nn(w_rayl), nn(dτ_aer), nn(dω̃), nn(dfᵗ), nn(surf.dZpp), nn(surf.dZmp),
+                                           nn(surf.dalbedo), nn(surf.dRsurf), nn(surf.dalbedo_spec))
+end
 # <<< rt_run_dual
 
 # The architecture is a FIELD of model.params (vSmartMOM_Parameters), not a type parameter of vSmartMOM_Model

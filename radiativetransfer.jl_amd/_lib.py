@@ -113,6 +113,8 @@ SIGNATURES = {
     "mom_scene_set_surface": (C.c_int, [c_h, C.c_int, C.c_int, c_dp, c_dp]),
     "mom_rt_run": (C.c_int, [c_h]),
     "mom_scene_set_partials": (C.c_int, [c_h, C.c_int] + [c_dp] * 8),
+    "mom_scene_set_optics_partials": (C.c_int, [c_h, C.c_int] + [c_dp] * 10),
+    "mom_scene_get_partials": (C.c_int, [c_h, c_dp, c_dp, c_dp]),
     "mom_rt_run_dual": (C.c_int, [c_h]),
     "mom_get_RT_partials": (C.c_int, [c_h, c_dp, c_dp]),
     "mom_get_hdr_partials": (C.c_int, [c_h, c_dp, c_dp, c_dp]),
@@ -403,6 +405,7 @@ class Handle:
         nd, iface, node = i32(nd), i32(iface), i32(node)
         ts, cm, sm = f64(tau_sum).reshape(-1), f64(cos_mphi).reshape(-1), f64(sin_mphi).reshape(-1)
         self.nVza = len(node)
+        self._Nz, self._K = int(Nz), int(K)
         self.check(self.lib.mom_scene_set(self._h, int(Nz), int(K), int(M), *[dp(x) for x in d], ip(nd), ip(iface),
                                           dp(ts), float(albedo), len(node), ip(node), dp(cm), dp(sm)))
 
@@ -621,6 +624,26 @@ class Handle:
         bufs = [None if x is None else f64(x).reshape(-1) for x in (dtau, dvarpi, dzw, dZpp, dZmp, dalbedo, dRsurf, dalbedo_spec)]
         self.dual_P = int(P)
         self.check(self.lib.mom_scene_set_partials(self._h, int(P), *[None if b is None else dp(b) for b in bufs]))
+
+    def scene_set_optics_partials(self, P, w_abs=None, w_rayl=None, dtau_aer=None, domega_aer=None, dft_aer=None, dZpp=None,
+                                  dZmp=None, dalbedo=None, dRsurf=None, dalbedo_spec=None):
+        """mom_scene_set_optics_partials: the partials of the INGREDIENTS of a scene_set_optics scene, flat buffers in ABI order
+        (w_abs [Nz, 3, P], w_rayl [Nz, P], dtau_aer [nAer, Nz, P], domega_aer, dft_aer [nAer, P], partial index slowest; the rest as
+        in scene_set_partials); None = no dependence.  The device forms dtau, dvarpi, dzw."""
+        bufs = [None if x is None else f64(x).reshape(-1)
+                for x in (w_abs, w_rayl, dtau_aer, domega_aer, dft_aer, dZpp, dZmp, dalbedo, dRsurf, dalbedo_spec)]
+        self.check(self.lib.mom_scene_set_optics_partials(self._h, int(P), *[None if b is None else dp(b) for b in bufs]))
+        self.dual_P = int(P)
+
+    def scene_get_partials(self):
+        """The resident partials of the scene as numpy in the reference's shapes: dτ, dϖ [P, nSpec, Nz], dzw [P, K, nSpec, Nz]
+        (an absent device buffer reads as zeros)."""
+        P, S, Nz, K = getattr(self, "dual_P", 0), self.S, getattr(self, "_Nz", 1), getattr(self, "_K", 1)   # no scene: the library says so
+        n = max(P * S * Nz, 1)
+        dt, dv, dz = np.empty(n), np.empty(n), np.empty(K * n)
+        self.check(self.lib.mom_scene_get_partials(self._h, dp(dt), dp(dv), dp(dz)))
+        tr = lambda a: np.transpose(a.reshape(P, Nz, S), (0, 2, 1)).copy()
+        return tr(dt), tr(dv), np.transpose(dz.reshape(P, Nz, S, K), (0, 3, 2, 1)).copy()
 
     def rt_run_dual(self):
         self.check(self.lib.mom_rt_run_dual(self._h))

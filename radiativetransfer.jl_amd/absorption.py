@@ -487,6 +487,76 @@ def optics_partials(tau, varpi, dtau_abs_k):
     return ScenePartial(dτ=d.copy(), dϖ=-varpi * d / tau)
 
 
+def optics_partials_host(model, partials, dtau_abs=None):
+    """The numpy twin of k_optics_dual (mom_scene_set_optics_partials): corert.construct_layer_inputs restated in forward mode,
+    statement by statement, with ForwardDiff's rules d(a b) = da b + db a and d(a / b) = da (1 / b) + db (-(a / b²)) --
+    constructCoreOpticalProperties / createAero (compEffectiveLayerProperties.jl:1-85) and the `+` of types.jl:632-678 on Dual
+    element types.  The all-zero tests of types.jl:641-661 are taken on the values, as ForwardDiff takes them.  `partials`: a
+    sequence of corert.OpticsPartial; `dtau_abs` [2, nSpec, Nz]: the partials of model.τ_abs with respect to each layer's pressure
+    and temperature (Handle.absorption_get_partials), needed when a w_p or w_T is nonzero.  Returns one corert.ScenePartial per
+    parameter: dτ, dϖ [nSpec, Nz], dzw [K, nSpec, Nz] or None where the device leaves it absent, and the basis / surface fields."""
+    from .corert import ScenePartial
+    S, Nz = model.τ_rayl.shape
+    nAer = len(model.aerosol_optics)
+    K = 1 + nAer
+    zeros = np.zeros(Nz)
+    row = lambda x: zeros if x is None else np.asarray(x, dtype=np.float64).reshape(Nz)
+    div = lambda a, da, b, db: (a / b, da * (1.0 / b) + db * (-(a / (b * b))))
+    out = []
+    for q in partials:
+        w_p, w_T, w_gas, w_rayl = row(q.w_p), row(q.w_T), row(q.w_gas), row(q.w_rayl)
+        if dtau_abs is None and (np.any(w_p != 0.0) or np.any(w_T != 0.0)):
+            raise ValueError("a nonzero w_p or w_T needs dtau_abs, the partials of τ_abs with respect to (p, T)")
+        dτ_aer = np.zeros((nAer, Nz)) if q.dτ_aer is None else np.asarray(q.dτ_aer, dtype=np.float64)
+        dω̃ = np.zeros(nAer) if q.dω̃ is None else np.asarray(q.dω̃, dtype=np.float64)
+        dfᵗ = np.zeros(nAer) if q.dfᵗ is None else np.asarray(q.dfᵗ, dtype=np.float64)
+        dτ, dϖ, dzw = np.empty((S, Nz)), np.empty((S, Nz)), np.zeros((K, S, Nz))
+        for z in range(Nz):
+            τz = model.τ_rayl[:, z].copy()
+            dτz = τz * w_rayl[z]
+            ϖz, dϖz = np.full(S, float(model.ϖ_Cabannes)), np.zeros(S)
+            w, dw = np.zeros((K, S)), np.zeros((K, S))
+            w[0] = 1.0
+            for a, aer in enumerate(model.aerosol_optics, start=1):
+                # createAero on Duals
+                fo, dfo = aer.fᵗ * aer.ω̃, dfᵗ[a - 1] * aer.ω̃ + dω̃[a - 1] * aer.fᵗ
+                b, db = 1 - fo, -dfo
+                τy, dτy = b * model.τ_aer[a - 1, z], db * model.τ_aer[a - 1, z] + dτ_aer[a - 1, z] * b
+                c, dc = 1 - aer.fᵗ, -dfᵗ[a - 1]
+                num, dnum = c * aer.ω̃, dc * aer.ω̃ + dω̃[a - 1] * c
+                ϖy, dϖy = div(num, dnum, b, db)
+                wy_s, dwy_s = τy * ϖy, dτy * ϖy + dϖy * τy
+                # the `+` of types.jl:632-661
+                wx, dwx = τz * ϖz, dτz * ϖz + dϖz * τz
+                wy, dwy = np.full(S, wy_s), np.full(S, dwy_s)
+                tot, dtot = wx + wy, dwx + dwy
+                τn, dτn = τz + τy, dτz + dτy
+                if np.all(wx == 0.0):
+                    w[:], dw[:] = 0.0, 0.0
+                    w[a] = 1.0
+                elif not np.all(wy == 0.0):
+                    fx, dfx = div(wx, dwx, tot, dtot)
+                    fy, dfy = div(wy, dwy, tot, dtot)
+                    dw = dw * fx[None, :] + dfx[None, :] * w
+                    w = w * fx[None, :]
+                    w[a], dw[a] = fy, dfy
+                ϖz, dϖz = div(tot, dtot, τn, dτn)
+                τz, dτz = τn, dτn
+            # the gas term (types.jl:672-678)
+            τa = model.τ_abs[:, z]
+            dτa = τa * w_gas[z]
+            if dtau_abs is not None:
+                dτa = dtau_abs[0][:, z] * w_p[z] + dtau_abs[1][:, z] * w_T[z] + dτa
+            τn, dτn = τz + τa, dτz + dτa
+            num, dnum = τz * ϖz, dτz * ϖz + dϖz * τz
+            _, dϖz = div(num, dnum, τn, dτn)
+            dτ[:, z], dϖ[:, z], dzw[:, :, z] = dτn, dϖz, dw
+        has_zw = nAer > 0 and any(x is not None for x in (q.w_rayl, q.dτ_aer, q.dω̃, q.dfᵗ))
+        out.append(ScenePartial(dτ=dτ, dϖ=dϖ, dzw=dzw if has_zw else None, dZpp=q.dZpp, dZmp=q.dZmp, dalbedo=q.dalbedo,
+                                dRsurf=q.dRsurf, dalbedo_spec=q.dalbedo_spec))
+    return out
+
+
 def compute_absorption_cross_section(h: HitranTable, grid, pressure: float, temperature: float, vmr: float = 0.0,
                                      wing_cutoff: float = 40.0, qratio=None, device: int = 0, broadening="Voigt()",
                                      cef="HumlicekWeidemann32SDErrorFunction()") -> np.ndarray:

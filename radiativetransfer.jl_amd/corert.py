@@ -782,10 +782,9 @@ def rt_run_dual(model: vSmartMOM_Model, partials: Sequence[ScenePartial], worksp
     return R, T, dR, dT
 
 
-def run_scene_device_optics(h: _lib.Handle, model: vSmartMOM_Model, upload_tau_abs: bool = True):
-    """The same run with the layer optics assembled on the GPU (mom_scene_set_optics): the host hands over the
-    INGREDIENTS (τ_rayl, aerosol columns, Z bases) and the gas absorption is the handle's resident τ_abs table --
-    uploaded here from model.τ_abs, or (upload_tau_abs=False) already accumulated by mom_voigt_tau_abs."""
+def scene_set_device_optics(h: _lib.Handle, model: vSmartMOM_Model, upload_tau_abs: bool) -> int:
+    """mom_scene_set_optics (+ mom_scene_set_surface) from the model's ingredients: what run_scene_device_optics and its Dual twin
+    share.  Returns the surface kind."""
     p, qp = model.params, model.quad_points
     Zpp, Zmp = z_bases(model)
     M = p.max_m
@@ -802,8 +801,94 @@ def run_scene_device_optics(h: _lib.Handle, model: vSmartMOM_Model, upload_tau_a
                        view_nodes(model), cm.reshape(-1), sm.reshape(-1))
     if kind != 0:
         h.scene_set_surface(kind, M, None if Rs is None else _abi_mats(Rs), alb)
+    return kind
+
+
+def run_scene_device_optics(h: _lib.Handle, model: vSmartMOM_Model, upload_tau_abs: bool = True):
+    """The same run with the layer optics assembled on the GPU (mom_scene_set_optics): the host hands over the
+    INGREDIENTS (τ_rayl, aerosol columns, Z bases) and the gas absorption is the handle's resident τ_abs table --
+    uploaded here from model.τ_abs, or (upload_tau_abs=False) already accumulated by mom_voigt_tau_abs."""
+    scene_set_device_optics(h, model, upload_tau_abs)
     h.rt_run()
     return h.get_RT()
+
+
+@dataclass
+class OpticsPartial:
+    """Partials of the INGREDIENTS of the layer optics with respect to ONE parameter -- what the Dual numbers of
+    model_from_parameters carry into constructCoreOpticalProperties / createAero (compEffectiveLayerProperties.jl:1-85).  The
+    device (mom_scene_set_optics_partials) or absorption.optics_partials_host forms the ScenePartial from them.  None = no
+    dependence."""
+    w_p: Optional[np.ndarray] = None            # [Nz] ∂p_z/∂x: weight onto ∂τ_abs/∂p of the layer (the resident dtau_abs table)
+    w_T: Optional[np.ndarray] = None            # [Nz] ∂T_z/∂x: weight onto ∂τ_abs/∂T
+    w_gas: Optional[np.ndarray] = None          # [Nz] ∂ln(vcd vmr)_z/∂x: relative change of the layer's gas column, onto τ_abs
+    w_rayl: Optional[np.ndarray] = None         # [Nz] relative change of the layer's Rayleigh depth, onto τ_rayl
+    dτ_aer: Optional[np.ndarray] = None         # [nAer, Nz]
+    dω̃: Optional[np.ndarray] = None             # [nAer]
+    dfᵗ: Optional[np.ndarray] = None            # [nAer]
+    dZpp: Optional[np.ndarray] = None           # the basis / surface fields of ScenePartial
+    dZmp: Optional[np.ndarray] = None
+    dalbedo: float = 0.0
+    dRsurf: Optional[np.ndarray] = None
+    dalbedo_spec: Optional[np.ndarray] = None
+
+
+def _pack_partials(partials, get, conv, shape=None):
+    """One field of a sequence of partials in the ABI layout (partial index slowest); None when no parameter has it."""
+    xs = [get(p) for p in partials]
+    if all(x is None for x in xs):
+        return None
+    ref = np.asarray(next(x for x in xs if x is not None), dtype=np.float64)
+    if shape is not None and ref.shape != tuple(shape):
+        raise ValueError(f"a partial has shape {ref.shape}, expected {tuple(shape)}")
+    return np.concatenate([conv(np.zeros_like(ref) if x is None else np.asarray(x, dtype=np.float64)) for x in xs])
+
+
+def scene_set_optics_partials(h: _lib.Handle, model: vSmartMOM_Model, partials: Sequence[OpticsPartial], surf_kind: Optional[int] = None):
+    """Pack OpticsPartials into the ABI layout of mom_scene_set_optics_partials and call it: the device forms dτ, dϖ, dzw of the
+    resident scene_set_optics scene.  surf_kind: the scene's surface kind (default: from model.params.brdf)."""
+    P = len(partials)
+    S, Nz = model.τ_rayl.shape
+    nAer = len(model.aerosol_optics)
+    if surf_kind is None:
+        brdf = model.params.brdf
+        surf_kind = 0 if brdf is None or isinstance(brdf, LambertianSurfaceScalar) else (2 if isinstance(brdf, LambertianSurfaceLegendre) else 1)
+    flat = lambda a: a.reshape(-1)
+    w_abs = None
+    if any(x is not None for p in partials for x in (p.w_p, p.w_T, p.w_gas)):
+        w_abs = np.zeros((P, 3, Nz))                                   # flat: z fastest, then the row, then the partial
+        for k, p in enumerate(partials):
+            for c, x in enumerate((p.w_p, p.w_T, p.w_gas)):
+                if x is not None:
+                    w_abs[k, c] = np.asarray(x, dtype=np.float64).reshape(Nz)
+    h.scene_set_optics_partials(
+        P, w_abs=w_abs, w_rayl=_pack_partials(partials, lambda p: p.w_rayl, flat, (Nz,)),
+        dtau_aer=_pack_partials(partials, lambda p: p.dτ_aer, lambda a: np.ascontiguousarray(a.T).reshape(-1), (nAer, Nz)),
+        domega_aer=_pack_partials(partials, lambda p: p.dω̃, flat, (nAer,)), dft_aer=_pack_partials(partials, lambda p: p.dfᵗ, flat, (nAer,)),
+        dZpp=_pack_partials(partials, lambda p: p.dZpp, _abi_mats), dZmp=_pack_partials(partials, lambda p: p.dZmp, _abi_mats),
+        dalbedo=np.array([float(p.dalbedo) for p in partials]) if surf_kind == 0 and P else None,
+        dRsurf=_pack_partials(partials, lambda p: p.dRsurf, _abi_mats) if surf_kind == 1 else None,
+        dalbedo_spec=_pack_partials(partials, lambda p: p.dalbedo_spec, flat) if surf_kind == 2 else None)
+
+
+def rt_run_dual_device_optics(h: _lib.Handle, model: vSmartMOM_Model, partials: Sequence[OpticsPartial], upload_tau_abs: bool = True,
+                              full: bool = False):
+    """The Dual twin of run_scene_device_optics: layer optics AND their partials assembled on the GPU (mom_scene_set_optics,
+    mom_scene_set_optics_partials), then mom_rt_run_dual.  With upload_tau_abs=False the resident τ_abs / dτ_abs tables of a Dual
+    absorption call (compute_absorption_profile(dual=True)) are used as they stand: lines -> Dual line shape -> Dual layer optics
+    -> Dual rt_run without a host hop.  Returns what rt_run_dual returns."""
+    kind = scene_set_device_optics(h, model, upload_tau_abs)
+    scene_set_optics_partials(h, model, partials, surf_kind=kind)
+    h.rt_run_dual()
+    R, T = h.get_RT()
+    if len(partials) == 0:
+        return R, T, np.zeros((0,) + R.shape), np.zeros((0,) + T.shape)
+    dR, dT = h.get_RT_partials()
+    if full:
+        hdr, up, dw = h.get_hdr()
+        dhdr, dup, ddw = h.get_hdr_partials()
+        return (R, T, hdr, up, dw), (dR, dT, dhdr, dup, ddw)
+    return R, T, dR, dT
 
 
 def rt_run(model: vSmartMOM_Model, i_band: int = 1):

@@ -63,6 +63,13 @@ struct mom_handle : MomSceneBufs<double> {
   // Dual run of the absorption path (mom_voigt_tau_abs_dual / _profile_dual): partials with respect to (p, T) of every layer
   MomDevBuf<double> d_dtau_abs;  // [S, abs_Nz, 2]; exists from the first Dual call after mom_absorption_begin
   MomDevBuf<double> d_dlines;    // partials of d_lines' prefactors: the MomLinePartialBlock of the same (lines_per, lines_nz); grow-only
+  // Dual run of the layer optics (mom_scene_set_optics_partials): what mom_scene_set_optics keeps of its scene for it
+  bool optics_scene = false;     // the resident scene came from mom_scene_set_optics (mom_scene_set clears it) ...
+  bool optics_tables = false;    // ... and d_tau_abs / d_dtau_abs are still the tables it read (mom_absorption_begin / _set clear it)
+  int optics_nAer = 0;
+  double optics_varpi_rayl = 0.0;
+  std::vector<double> h_tau_aer, h_omega_aer, h_ft_aer;  // host copies of its aerosol arguments [nAer, Nz], [nAer], [nAer]
+  MomDevBuf<double> d_optics_prm;  // per-(layer, partial) scalars of k_optics_dual (OpticsDualArgs::w_abs | w_rayl | daer); grow-only
   MomDevBuf<double> d_vec[4];  // S-length temporaries (tau_sum, dtau, varpi, expk)
   MomDevBuf<double> d_Zop[2];
   // scene

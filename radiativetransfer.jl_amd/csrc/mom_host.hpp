@@ -340,6 +340,17 @@ struct MomDualScene {
 size_t momd_bytes_per_unit(int N, int P);
 int momd_run(const MomDualScene &sc, std::string *err);   // 0 ok, 1 unsupported, 2 HIP error (text in *err)
 
+// mom_scene.hip: what the two setters of the scene's partials share (mom_scene_set_partials there, mom_scene_set_optics_partials in
+// mom_optics.hip).  _check: 0 <= P <= 64 and dZpp / dZmp both or neither, else MOM_EINVAL with `fn` in the text; _reset: the partials,
+// outputs and workspaces of the previous call go and P becomes the scene's; _rest: everything but dtau / dvarpi / dzw (d_dual_in[0..2])
+// -- the partials of the bases (padded like the scene's operators), of the surface of the scene's kind, d_dual_out, d_dual_ts
+#pragma GCC visibility push(hidden)
+int mom_partials_check(mom_t *h, const char *fn, int P, const double *dZpp, const double *dZmp);
+void mom_partials_reset(mom_t *h, int P);
+int mom_partials_rest(mom_t *h, const double *dZpp, const double *dZmp, const double *dalbedo, const double *dRsurf,
+                      const double *dalbedo_spec);
+#pragma GCC visibility pop
+
 // argument blocks of the single-launch sweep kernels, shared by the launching translation unit (mom_scene.hip) and the
 // kernels' own (mom_small.hip: momsm::k_sweep; mom_wave.hip: momw::k_wsweep)
 template <class Real>

@@ -1,5 +1,6 @@
 // mom_optics.hip -- the device-side layer optics of the C ABI (include/momcore.h): the resident absorption table
-// and the Voigt entry points (kernels: voigt.hip), k_optics and mom_scene_set_optics, mom_scene_get_layers.
+// and the Voigt entry points (kernels: voigt.hip), k_optics and mom_scene_set_optics, mom_scene_get_layers, and the Dual run of the
+// layer optics: k_optics_dual and mom_scene_set_optics_partials, mom_scene_get_partials.
 #include <cstring>
 
 #include "mom_handle.hpp"
@@ -9,6 +10,7 @@ extern "C" int mom_absorption_begin(mom_t *h, int Nz, const double *grid) {
   if (Nz <= 0) return fail(h, MOM_EINVAL, "mom_absorption_begin: bad argument");
   HIPCHK(h, hipSetDevice(h->device));
   const size_t S = h->S;
+  h->optics_tables = false;  // a resident scene (mom_scene_set_optics) was assembled from the table that goes here
   HIPCHK(h, h->d_tau_abs.renew(S * Nz));
   HIPCHK(h, hipMemsetAsync(h->d_tau_abs, 0, S * Nz * sizeof(double), h->stream));  // τ_abs = zeros (model_from_parameters.jl:48)
   if (h->d_dtau_abs) {  // the partials restart with the table
@@ -500,10 +502,17 @@ extern "C" int mom_scene_set_optics(mom_t *h, int Nz, int nAer, int M, const dou
     return fail(h, MOM_ESTATE, "mom_scene_set_optics: no resident tau_abs table of this Nz (mom_absorption_begin / _set)");
   HIPCHK(h, hipSetDevice(h->device));
   h->scene_set = false;
+  h->optics_scene = h->optics_tables = false;
   const size_t S = h->S;
   const int K = 1 + nAer;
   int rc;
   HIPCHK(h, mom_upload(h->d_tau_rayl, tau_rayl, S * Nz, h->stream));
+  // the Dual run of this assembly (mom_scene_set_optics_partials) differentiates createAero on the host as well
+  h->optics_nAer = nAer;
+  h->optics_varpi_rayl = varpi_rayl;
+  h->h_tau_aer.assign(tau_aer, tau_aer + (nAer > 0 ? (size_t)nAer * Nz : 0));
+  h->h_omega_aer.assign(omega_aer, omega_aer + (nAer > 0 ? nAer : 0));
+  h->h_ft_aer.assign(ft_aer, ft_aer + (nAer > 0 ? nAer : 0));
   // createAero (compEffectiveLayerProperties.jl:80-85): τ' = (1 - fᵗ ω̃) τ_aer, ϖ' = (1 - fᵗ) ω̃ / (1 - fᵗ ω̃); the
   // all-zero tests of types.jl:641-661 are decided here on the host (they are properties of whole spectral columns)
   std::vector<double> aer((size_t)2 * std::max(nAer, 1) * Nz, 0.0);
@@ -566,6 +575,7 @@ extern "C" int mom_scene_set_optics(mom_t *h, int Nz, int nAer, int M, const dou
   }
   if ((rc = scene_common(h, Nz, K, M, Zpp, Zmp, albedo, nVza, node_1based, cos_mphi, sin_mphi))) return rc;
   h->scene_set = true;
+  h->optics_scene = h->optics_tables = true;
   return MOM_OK;
 }
 
@@ -582,6 +592,178 @@ extern "C" int mom_scene_get_layers(mom_t *h, int *ndoubl, int *iface, double *t
   if (varpi) HIPCHK(h, hipMemcpyAsync(varpi, h->d_varpi, S * Nz * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (zw) HIPCHK(h, hipMemcpyAsync(zw, h->d_zw, (size_t)h->K * S * Nz * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (tau_sum) HIPCHK(h, hipMemcpyAsync(tau_sum, h->d_tau_sum, S * (Nz + 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MOM_OK;
+}
+
+// ---- The Dual run of k_optics: the partials of τ, ϖ and the basis weights with respect to P parameters, formed from the partials
+// of the ingredients -- constructCoreOpticalProperties / createAero (compEffectiveLayerProperties.jl:1-85) and the `+` of
+// types.jl:632-678 on ForwardDiff.Dual element types.  It follows k_optics statement by statement with ForwardDiff's rules:
+// d(a b) = da b + db a, d(a / b) = da (1 / b) + db (-(a / b²)).  The three aerosol modes are the value run's (d_aer_mode): ForwardDiff
+// takes `all(τϖ .== 0)` on the values.  One thread per (spectral point, layer, partial), the spectral index fastest across lanes:
+// every load and store of an [S, ...] array is contiguous across a wavefront (dzw [K, S, ...] in runs of K doubles per lane, K stores
+// that together cover the same contiguous range); the per-(layer, partial) scalars are uniform across a workgroup (blockIdx.y, .z).
+// Unlike k_optics nothing here runs along the layers (dτ_sum is not formed: k_dtausum of the Dual sweep derives it from dτ), so the
+// layers are grid blocks, not a loop: at S = 10⁴ a thread per (point, partial) would be 469 wavefronts for 1024 SIMDs, each waiting
+// for its loads layer after layer.  The cheap value chain is recomputed per partial.
+// Contraction stays off as for k_optics: the statements round as the host twin's (absorption.optics_partials_host) do.
+struct OpticsDualArgs {
+  int S, Nz, nAer;
+  double varpi_rayl;
+  const double *tau_rayl, *tau_abs;  // [S,Nz]
+  const double *dtau_abs;            // [S,Nz,2] or null (no Dual absorption call: zeros)
+  const double *aer;                 // [2,nAer,Nz] as in OpticsArgs
+  const int *aer_mode;               // [nAer,Nz]
+  const double *w_abs, *w_rayl;      // [Nz,3,P], [Nz,P]: chain weights onto dtau_abs[.., 0], dtau_abs[.., 1], tau_abs; onto tau_rayl
+  const double *daer;                // [2,nAer,Nz,P]: partials of aer
+  double *dtau, *dvarpi;             // [S,Nz,P]
+  double *dzw;                       // [K,S,Nz,P] or null (identically zero: not stored)
+};
+__device__ __forceinline__ void dual_div(double a, double da, double b, double db, double &q, double &dq) {
+  q = a / b;
+  dq = da * (1.0 / b) + db * (-(a / (b * b)));
+}
+__global__ void __launch_bounds__(256) k_optics_dual(OpticsDualArgs a) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x, z = blockIdx.y, p = blockIdx.z;
+  if (n >= a.S) return;
+  const int K = 1 + a.nAer;
+  const size_t SZ = (size_t)a.S * a.Nz, AZ = (size_t)a.nAer * a.Nz;
+  const size_t o = n + (size_t)a.S * z, op = o + SZ * p;
+  double tau = a.tau_rayl[o], varpi = a.varpi_rayl;
+  double dtau = tau * a.w_rayl[z + (size_t)a.Nz * p], dvarpi = 0.0;
+  double w[8], dw[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { w[k] = k == 0 ? 1.0 : 0.0; dw[k] = 0.0; }
+  for (int x = 0; x < a.nAer; ++x) {
+    const size_t ax = x + (size_t)a.nAer * z;
+    const double ty = a.aer[ax], wy = a.aer[AZ + ax];
+    const double dty = a.daer[ax + 2 * AZ * p], dwy = a.daer[AZ + ax + 2 * AZ * p];
+    const int mode = a.aer_mode[ax];
+    const double wx = tau * varpi, dwx = dtau * varpi + dvarpi * tau;
+    const double tot = wx + wy, dtot = dwx + dwy, tn = tau + ty, dtn = dtau + dty;
+    if (mode == 0) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { w[k] = k == x + 1 ? 1.0 : 0.0; dw[k] = 0.0; }
+    } else if (mode == 1) {
+      double fx, dfx, fy, dfy;
+      dual_div(wx, dwx, tot, dtot, fx, dfx);
+      dual_div(wy, dwy, tot, dtot, fy, dfy);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const double dk = dw[k] * fx + dfx * w[k];
+        dw[k] = k == x + 1 ? dfy : dk;
+        w[k] = k == x + 1 ? fy : w[k] * fx;
+      }
+    }
+    dual_div(tot, dtot, tn, dtn, varpi, dvarpi);
+    tau = tn;
+    dtau = dtn;
+  }
+  const double ta = a.tau_abs[o];
+  const double *wa = a.w_abs + z + (size_t)a.Nz * 3 * p;
+  double dta = ta * wa[2 * a.Nz];
+  if (a.dtau_abs) dta = a.dtau_abs[o] * wa[0] + a.dtau_abs[o + SZ] * wa[a.Nz] + dta;
+  const double tn = tau + ta, dtn = dtau + dta;
+  const double num = tau * varpi, dnum = dtau * varpi + dvarpi * tau;
+  dual_div(num, dnum, tn, dtn, varpi, dvarpi);
+  a.dtau[op] = dtn;
+  a.dvarpi[op] = dvarpi;
+  if (a.dzw) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (k < K) a.dzw[k + (size_t)K * op] = dw[k];
+  }
+}
+
+// createAero (compEffectiveLayerProperties.jl:80-85) on Duals for one aerosol type and layer: τ_y = (1 - fᵗ ω̃) τ_aer,
+// ϖ_y = (1 - fᵗ) ω̃ / (1 - fᵗ ω̃), w_y = τ_y ϖ_y -> the partials of τ_y and w_y
+static void create_aero_dual(double tau_aer, double om, double ft, double dtau_aer, double dom, double dft, double *dty, double *dwy) {
+  const double fo = ft * om, dfo = dft * om + dom * ft;
+  const double b = 1 - fo, db = -dfo;
+  const double ty = b * tau_aer;
+  *dty = db * tau_aer + dtau_aer * b;
+  const double c = 1 - ft, dc = -dft;
+  const double num = c * om, dnum = dc * om + dom * c;
+  const double vy = num / b, dvy = dnum * (1.0 / b) + db * (-(num / (b * b)));
+  *dwy = *dty * vy + dvy * ty;
+}
+
+extern "C" int mom_scene_set_optics_partials(mom_t *h, int P, const double *w_abs, const double *w_rayl, const double *dtau_aer,
+                                             const double *domega_aer, const double *dft_aer, const double *dZpp, const double *dZmp,
+                                             const double *dalbedo, const double *dRsurf, const double *dalbedo_spec) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  F64_ONLY(h, "mom_scene_set_optics_partials");
+  if (!h->scene_set) return fail(h, MOM_ESTATE, "mom_scene_set_optics_partials: call mom_scene_set_optics first");
+  if (!h->optics_scene)
+    return fail(h, MOM_ESTATE, "mom_scene_set_optics_partials: the resident scene came from mom_scene_set (host optics): its partials go "
+                               "through mom_scene_set_partials");
+  if (!h->optics_tables || !h->d_tau_abs || h->abs_Nz != h->Nz)
+    return fail(h, MOM_ESTATE, "mom_scene_set_optics_partials: mom_absorption_begin / _set was called after the mom_scene_set_optics that "
+                               "made the scene: the resident tau_abs table is not the scene's");
+  int rc = mom_partials_check(h, "mom_scene_set_optics_partials", P, dZpp, dZmp);
+  if (rc) return rc;
+  const int Nz = h->Nz, nAer = h->optics_nAer, K = h->K;
+  if (w_abs && !h->d_dtau_abs)
+    for (size_t k = 0; k < (size_t)P; ++k)
+      for (size_t i = 0; i < 2 * (size_t)Nz; ++i)
+        if (w_abs[i + 3 * (size_t)Nz * k] != 0.0)
+          return fail(h, MOM_ESTATE, "mom_scene_set_optics_partials: w_abs has a nonzero pressure or temperature weight, but no dtau_abs "
+                                     "table is resident (no Dual absorption call since the table was set)");
+  HIPCHK(h, hipSetDevice(h->device));
+  mom_partials_reset(h, P);
+  if (P == 0) return MOM_OK;
+  const size_t S = h->S, SZ = S * Nz, AZ = (size_t)nAer * Nz;
+  // per-(layer, partial) scalars: w_abs [Nz,3,P] | w_rayl [Nz,P] | d aer [2,nAer,Nz,P]; a null argument: zeros
+  const size_t n_abs = 3 * (size_t)Nz * P, n_rayl = (size_t)Nz * P, n_aer = 2 * AZ * P;
+  std::vector<double> prm(n_abs + n_rayl + n_aer, 0.0);
+  if (w_abs) std::copy(w_abs, w_abs + n_abs, prm.begin());
+  if (w_rayl) std::copy(w_rayl, w_rayl + n_rayl, prm.begin() + n_abs);
+  if (nAer > 0 && (dtau_aer || domega_aer || dft_aer)) {
+    double *da = prm.data() + n_abs + n_rayl;
+    for (size_t k = 0; k < (size_t)P; ++k)
+      for (int z = 0; z < Nz; ++z)
+        for (int x = 0; x < nAer; ++x) {
+          const size_t ax = x + (size_t)nAer * z;
+          create_aero_dual(h->h_tau_aer[ax], h->h_omega_aer[x], h->h_ft_aer[x], dtau_aer ? dtau_aer[ax + AZ * k] : 0.0,
+                           domega_aer ? domega_aer[x + (size_t)nAer * k] : 0.0, dft_aer ? dft_aer[x + (size_t)nAer * k] : 0.0,
+                           &da[ax + 2 * AZ * k], &da[AZ + ax + 2 * AZ * k]);
+        }
+  }
+  HIPCHK(h, h->d_optics_prm.reserve(prm.size(), h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_optics_prm, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, h->d_dual_in[0].renew(SZ * P));
+  HIPCHK(h, h->d_dual_in[1].renew(SZ * P));
+  // the weights depend on the Rayleigh and aerosol ingredients only: without a partial of those dzw stays absent and the sweep skips it
+  if (nAer > 0 && (w_rayl || dtau_aer || domega_aer || dft_aer)) HIPCHK(h, h->d_dual_in[2].renew((size_t)K * SZ * P));
+  OpticsDualArgs a{};
+  a.S = h->S; a.Nz = Nz; a.nAer = nAer;
+  a.varpi_rayl = h->optics_varpi_rayl;
+  a.tau_rayl = h->d_tau_rayl; a.tau_abs = h->d_tau_abs; a.dtau_abs = h->d_dtau_abs; a.aer = h->d_aer; a.aer_mode = h->d_aer_mode;
+  a.w_abs = h->d_optics_prm; a.w_rayl = h->d_optics_prm + n_abs; a.daer = h->d_optics_prm + n_abs + n_rayl;
+  a.dtau = h->d_dual_in[0]; a.dvarpi = h->d_dual_in[1]; a.dzw = h->d_dual_in[2];
+  // the launch between the handle's timing events: mom_timers right after this call gives the kernel's time as its total
+  HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+  hipLaunchKernelGGL(k_optics_dual, dim3((unsigned)((S + 255) / 256), (unsigned)Nz, (unsigned)P), dim3(256), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  for (int k = 1; k < 4; ++k) HIPCHK(h, hipEventRecord(h->ev[k], h->stream));
+  h->launches = 1; h->launches_full = 0; h->launches_red = 0;
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // prm is a host temporary
+  return mom_partials_rest(h, dZpp, dZmp, dalbedo, dRsurf, dalbedo_spec);
+}
+
+extern "C" int mom_scene_get_partials(mom_t *h, double *dtau, double *dvarpi, double *dzw) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (!h->scene_set || h->dual_P == 0)
+    return fail(h, MOM_ESTATE, "mom_scene_get_partials: no partials resident (mom_scene_set_partials / mom_scene_set_optics_partials with P > 0)");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t SZP = (size_t)h->S * h->Nz * h->dual_P;
+  double *dst[3] = {dtau, dvarpi, dzw};
+  const size_t cnt[3] = {SZP, SZP, (size_t)h->K * SZP};
+  for (int k = 0; k < 3; ++k) {
+    if (!dst[k]) continue;
+    if (h->d_dual_in[k]) HIPCHK(h, hipMemcpyAsync(dst[k], h->d_dual_in[k], cnt[k] * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    else std::fill(dst[k], dst[k] + cnt[k], 0.0);   // an absent buffer: no dependence
+  }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MOM_OK;
 }

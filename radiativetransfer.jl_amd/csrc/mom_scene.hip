@@ -75,6 +75,7 @@ extern "C" int mom_scene_set(mom_t *h, int Nz, int K, int M, const double *tau, 
   HIPCHK(h, hipSetDevice(h->device));
   const size_t S = h->S;
   h->scene_set = false;
+  h->optics_scene = false;  // host optics: no ingredients for mom_scene_set_optics_partials
   int rc;
   if (h->f32) {
     for (int v = 0; v < nVza; ++v)
@@ -702,26 +703,22 @@ extern "C" int mom_rt_run_multisensor(mom_t *h, int nSensors, const int *sensor_
 }
 
 // ---- ForwardDiff.Dual through rt_run (mom_dual.hip) ---------------------------------------------------------------
-// The partials of everything mom_scene_set / mom_scene_set_surface uploaded, in the layout of the value arrays with the
-// partial index as the slowest axis; NULL = that input does not depend on the parameters.
-extern "C" int mom_scene_set_partials(mom_t *h, int P, const double *dtau, const double *dvarpi, const double *dzw,
-                                      const double *dZpp, const double *dZmp, const double *dalbedo, const double *dRsurf,
-                                      const double *dalbedo_spec) {
-  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
-  F64_ONLY(h, "mom_scene_set_partials");
-  if (!h->scene_set) return fail(h, MOM_ESTATE, "mom_scene_set_partials: call mom_scene_set first");
-  if (P < 0 || P > 64 || ((dZpp == nullptr) != (dZmp == nullptr)))
-    return fail(h, MOM_EINVAL, "mom_scene_set_partials: 0 <= P <= 64; dZpp and dZmp come together");
-  HIPCHK(h, hipSetDevice(h->device));
+// What mom_scene_set_partials and mom_scene_set_optics_partials (mom_optics.hip) share: mom_host.hpp
+int mom_partials_check(mom_t *h, const char *fn, int P, const double *dZpp, const double *dZmp) {
+  if (P >= 0 && P <= 64 && ((dZpp == nullptr) == (dZmp == nullptr))) return MOM_OK;
+  char buf[160];
+  snprintf(buf, sizeof buf, "%s: 0 <= P <= 64; dZpp and dZmp come together", fn);
+  return fail(h, MOM_EINVAL, buf);
+}
+void mom_partials_reset(mom_t *h, int P) {
   for (auto &b : h->d_dual_in) b.reset();
   h->d_dual_out.reset(); h->d_dual_ts.reset();
   h->dual_P = P;
   h->dual_ran = false;
-  if (P == 0) return MOM_OK;
-  const size_t S = h->S, Nz = h->Nz, K = h->K, M = h->scene_M, N = h->N, Nk = h->Nk;
-  if (dtau) HIPCHK(h, mom_upload(h->d_dual_in[0], dtau, S * Nz * P, h->stream));
-  if (dvarpi) HIPCHK(h, mom_upload(h->d_dual_in[1], dvarpi, S * Nz * P, h->stream));
-  if (dzw) HIPCHK(h, mom_upload(h->d_dual_in[2], dzw, K * S * Nz * P, h->stream));
+}
+int mom_partials_rest(mom_t *h, const double *dZpp, const double *dZmp, const double *dalbedo, const double *dRsurf,
+                      const double *dalbedo_spec) {
+  const size_t S = h->S, Nz = h->Nz, K = h->K, M = h->scene_M, N = h->N, Nk = h->Nk, P = h->dual_P;
   if (dZpp) {
     if (Nk == N) {
       HIPCHK(h, mom_upload(h->d_dual_in[3], dZpp, N * N * K * M * P, h->stream));
@@ -744,6 +741,26 @@ extern "C" int mom_scene_set_partials(mom_t *h, int P, const double *dtau, const
   HIPCHK(h, h->d_dual_ts.renew(S * (Nz + 1) * P));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MOM_OK;
+}
+
+// The partials of everything mom_scene_set / mom_scene_set_surface uploaded, in the layout of the value arrays with the
+// partial index as the slowest axis; NULL = that input does not depend on the parameters.
+extern "C" int mom_scene_set_partials(mom_t *h, int P, const double *dtau, const double *dvarpi, const double *dzw,
+                                      const double *dZpp, const double *dZmp, const double *dalbedo, const double *dRsurf,
+                                      const double *dalbedo_spec) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  F64_ONLY(h, "mom_scene_set_partials");
+  if (!h->scene_set) return fail(h, MOM_ESTATE, "mom_scene_set_partials: call mom_scene_set first");
+  const int rc = mom_partials_check(h, "mom_scene_set_partials", P, dZpp, dZmp);
+  if (rc) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  mom_partials_reset(h, P);
+  if (P == 0) return MOM_OK;
+  const size_t S = h->S, Nz = h->Nz, K = h->K;
+  if (dtau) HIPCHK(h, mom_upload(h->d_dual_in[0], dtau, S * Nz * P, h->stream));
+  if (dvarpi) HIPCHK(h, mom_upload(h->d_dual_in[1], dvarpi, S * Nz * P, h->stream));
+  if (dzw) HIPCHK(h, mom_upload(h->d_dual_in[2], dzw, K * S * Nz * P, h->stream));
+  return mom_partials_rest(h, dZpp, dZmp, dalbedo, dRsurf, dalbedo_spec);
 }
 
 // rt_run on Dual numbers for the resident scene: R_SFI / T_SFI (read with mom_get_RT) and their partials
