@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""The Mie / NAI-2 aerosol optics (csrc/mom_mie.hip) as a benchmark; prints one JSON line, `bench_mie.py OUT.json` also writes it
+(committed as profiles/mie_bench.json).
+
+Two points: the reference's own test point (test/test_Scattering.jl: λ = 0.55 µm, r_max = 30 µm, nquad_radius = 2500,
+m = 1.3 + 0.001i, LogNormal(log 0.3, log 6.82): x_max = 342.7, n_max = 381, n_μ = 761) and a small one (r_max = 1 µm, 37 radii:
+n_max = 31, n_μ = 61).  Per point: the HIP-event times of the three kernel groups (coefficients; amplitude GEMM with its epilogue
+and the reduction; projection), the wall time of the device call and of the whole compute_aerosol_optical_properties (host tables
+included), and the numpy oracle of tests/mie_oracle.py on the same inputs as the CPU baseline.
+
+Flop model of the amplitude GEMM: 16 flop per (μ, radius, l) -- S₁ and S₂, real and imaginary part, two products each.  The
+achieved rate counts the K extents the kernel actually runs (per radius tile of 16: the tile's largest n_max rounded up to 4,
+over all 32-row μ blocks, padding included), `algorithmic` the sums to each radius' own n_max over the n_μ live rows."""
+import json
+import math
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent
+sys.path.insert(0, str(ROOT))
+
+PEAK_FP64_MFMA_TFLOPS = 78.6  # MI355X FP64 matrix spec
+POINTS = {
+    "reference_test_point": dict(lam=0.55, r_max=30.0, nquad_radius=2500, n_r=1.3, n_i=0.001, r_m=0.3, sigma_g=6.82),
+    "small": dict(lam=0.55, r_max=1.0, nquad_radius=37, n_r=1.3, n_i=0.001, r_m=0.3, sigma_g=1.6),
+}
+
+
+def run_point(p, repeats=5, autodiff=False):
+    import rtamd
+    sc = rtamd.scattering
+    aer = sc.Aerosol(sc.LogNormal(math.log(p["r_m"]), math.log(p["sigma_g"])), p["n_r"], p["n_i"])
+    model = sc.make_mie_model(sc.NAI2(), aer, p["lam"], None, None, p["r_max"], p["nquad_radius"])
+    t0 = time.perf_counter()
+    inp = sc.mie_inputs(model, autodiff)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    args = (inp.r, inp.w, p["lam"], p["n_r"], p["n_i"], inp.w_μ, inp.π_, inp.τ_, inp.P, inp.P2, inp.R2, inp.T2)
+    best, call = np.full(3, 1e30), 1e30
+    for _ in range(repeats + 1):      # the first call loads the code objects
+        t0 = time.perf_counter()
+        bulk, C, greek, ms = rtamd._lib.mie_nai2(*args)
+        call = min(call, (time.perf_counter() - t0) * 1e3)
+        best = np.minimum(best, ms)
+    t0 = time.perf_counter()
+    sc.compute_aerosol_optical_properties(model, autodiff)
+    whole_ms = (time.perf_counter() - t0) * 1e3
+    # K extents of the amplitude GEMM as run
+    x = 2 * math.pi / p["lam"] * inp.r
+    nmax = sc.get_n_max(x)
+    n_mu, nR = inp.w_μ.size, inp.r.size
+    tiles = [int(-(-nmax[min(i0 + 15, nR - 1)] // 4) * 4) for i0 in range(0, nR, 16)]
+    flop_run = 16.0 * (-(-n_mu // 32) * 32) * 16 * float(sum(tiles))
+    flop_alg = 16.0 * n_mu * float(nmax.sum())
+    tf = flop_run / (best[1] * 1e-3) / 1e12
+    out = {"n_radii": int(nR), "n_mu": int(n_mu), "n_max": int(nmax.max()), "x_max": float(x.max()), "weight_rows": int(inp.w.shape[0]),
+           "kernels_ms": {"coefficients": float(best[0]), "amplitude_gemm_and_reduction": float(best[1]), "projection": float(best[2]),
+                          "sum": float(best.sum())},
+           "device_call_wall_ms": call, "host_tables_ms": host_ms, "compute_aerosol_optical_properties_wall_ms": whole_ms,
+           "amplitude_gemm": {"flop_run": flop_run, "flop_algorithmic": flop_alg, "flop_full_K": 16.0 * n_mu * nR * float(nmax.max()),
+                              "roofline": {"bound": "mfma", "achieved": tf, "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s",
+                                           "frac": tf / PEAK_FP64_MFMA_TFLOPS,
+                                           "algorithmic_achieved": flop_alg / (best[1] * 1e-3) / 1e12}}}
+    sys.path.insert(0, str(ROOT / "tests"))
+    import mie_oracle as mo
+    t0 = time.perf_counter()
+    o = mo.nai2_sums(inp.r, inp.w / (4 * np.pi * inp.r ** 2), p["lam"], p["n_r"], p["n_i"])
+    cpu_ms = (time.perf_counter() - t0) * 1e3
+    out["cpu_baseline"] = {"wall_ms": cpu_ms, "kind": "numpy oracle (tests/mie_oracle.py: vectorised recurrences, BLAS zgemm for S1, S2)",
+                           "speedup_kernels": cpu_ms / float(best.sum()), "speedup_device_call": cpu_ms / call}
+    out["distance_to_oracle"] = {q: mo.rel_max(g, o[q]) for q, g in (("bulk_f", bulk), ("C", C), ("greek", greek))}
+    return out
+
+
+def run():
+    out = {"metric": "Mie NAI-2 aerosol optics, kernels of one call", "unit": "ms"}
+    for name, p in POINTS.items():
+        out[name] = run_point(p)
+    out["reference_test_point_nW3"] = run_point(POINTS["reference_test_point"], autodiff=True)
+    out["value"] = out["reference_test_point"]["kernels_ms"]["sum"]
+    return out
+
+
+if __name__ == "__main__":
+    res = run()
+    if len(sys.argv) > 1:
+        Path(sys.argv[1]).parent.mkdir(parents=True, exist_ok=True)
+        Path(sys.argv[1]).write_text(json.dumps(res, indent=1, ensure_ascii=False) + "\n")
+    print(json.dumps(res, ensure_ascii=False))

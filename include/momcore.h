@@ -700,6 +700,39 @@ int mom_lineshape_xsec_dual(int device, int broadening, int cef, int nLines, con
 /* GPU time (HIP events around the kernel, ms) of the last mom_voigt_xsec / mom_lineshape_xsec call (or Dual run) of the calling thread. */
 double mom_voigt_last_kernel_ms(void);
 
+/* ---- Mie aerosol optics: Siewert NAI-2 -------------------------------------------------------
+ * compute_aerosol_optical_properties(model::MieModel{NAI2}) (src/Scattering/compute_NAI2.jl:16-182) for one wavelength and one
+ * refractive index m = n_r + i n_i (n_i >= 0, the absorbing convention with xi = psi - i chi), Float64.  Handle-free like
+ * mom_lineshape_xsec; error text: mom_last_global_error().  The host brings the quadratures and the tables:
+ *   r [nR]                  radii, ascending, r[0] > 0, in the unit of lambda; size parameter x_i = (2 pi / lambda) r_i,
+ *                           n_max,i = round(x_i + 4.05 x_i^(1/3) + 10), downward recurrence from round(max(n_max,i, |x_i (n_r - n_i)|) + 51)
+ *   w [nW, nR]              weight rows (row-major, 1 <= nW <= 4): row 0 = 4 pi r^2 w_x for the value, further rows the same with
+ *                           d w_x / d theta for a parameter of the size distribution (everything below is linear in w)
+ *   w_mu [n_mu]             Gauss weights of the scattering-angle nodes
+ *   pi_tab, tau_tab         pi_l(mu), tau_l(mu), l = 1..n_max: [n_max, n_mu], mu fastest (compute_mie_pi_tau, column-major [n_mu, n_max]);
+ *                           n_max >= the largest n_max,i
+ *   P, P2, R2, T2           compute_legendre_poly(mu, l_max): [l_max, n_mu], mu fastest
+ * Outputs (host), none of them divided by the bulk C_sca (that and the quotient rule of the partial rows are host arithmetic):
+ *   bulk_f [nW, 4, n_mu]    sum_i w[k, i] f(mu, i) for f = f11, f33, f12, f34 (compute_NAI2.jl:107-110, 119-123)
+ *   C [nW, 2]               sum_i w[k, i] / (4 pi r_i^2) * (C_sca,i, C_ext,i) (:103-104, 115-116)
+ *   greek [nW, 6, l_max]    the projections of :146-160 on bulk_f, in the order alpha, beta, gamma, delta, epsilon, zeta
+ *   gpu_ms [3] or NULL      HIP-event times (ms): coefficient kernel, amplitude GEMM with its reduction, projection
+ * The radii are tiled by 16 and a tile's sum over l ends at the tile's largest n_max,i rounded up to 4: only products with the
+ * exact zeros above a radius' own n_max,i are left out.  flags = MOM_MIE_FULL_K runs every tile to n_max instead (test access:
+ * the results are bitwise equal).  Two calls with the same arguments give bitwise equal results.
+ * MOM_EINVAL: nR < 1, n_mu < 1, l_max < 1, nW outside 1..4, lambda <= 0, n_i < 0, r not ascending or r[0] <= 0, n_max smaller
+ * than the largest n_max,i, an unknown flag, a null pointer (gpu_ms excepted). */
+enum { MOM_MIE_MAX_WEIGHT_ROWS = 4, MOM_MIE_FULL_K = 1 };
+int mom_mie_nai2(int device, int nR, const double *r, int nW, const double *w, double lambda, double n_r, double n_i,
+                 int n_mu, const double *w_mu, int n_max, const double *pi_tab, const double *tau_tab, int l_max,
+                 const double *P, const double *P2, const double *R2, const double *T2, int flags, double *bulk_f,
+                 double *C, double *greek, double *gpu_ms);
+
+/* Test access: the Mie coefficients a_n, b_n (compute_mie_ab!, mie_helper_functions.jl:31-71) of nX size parameters x > 0 (any
+ * order), n = 1..n_max, as four real arrays [n_max, nX], x fastest; zeros above each x's own n_max.  MOM_EINVAL as above. */
+int mom_mie_coefficients(int device, int nX, const double *x, double n_r, double n_i, int n_max, double *a_re, double *a_im,
+                         double *b_re, double *b_im);
+
 #ifdef __cplusplus
 }
 #endif

@@ -470,3 +470,30 @@ end
 
 destroy!(model::MomInterpolationModel) = MomCore.mom_lut_destroy!(model.h.ptr, model.id)
 # <<< interpolation
+
+# >>> mie
+"""
+compute_aerosol_optical_properties(model::MieModel{<:NAI2}) (src/Scattering/compute_NAI2.jl:16-182) with architecture isa MI355X:
+the loop over the radii (:80-112), the bulk sums (:115-123) and the projections (:146-160) are ONE call.  The host keeps what it
+already builds -- the radius quadrature, wₓ, μ, w_μ, the π/τ and P/P²/R²/T² tables (column-major [n_μ, n], the layout the ABI reads) --
+and the division by the bulk C_sca.  `w_rows` [nR, nW]: column 1 = wₓ, further columns ∂wₓ/∂θ of size-distribution parameters; the
+result carries one AerosolOptics-like named tuple per column, the partial ones through the quotient rule.
+"""
+function mie_nai2(arch::MI355X, r, w_rows, λ, nᵣ, nᵢ, w_μ, leg_π, leg_τ, P, P², R², T²)
+    nR, nW = size(w_rows, 1), size(w_rows, 2);  n_μ, n_max = size(leg_π);  l_max = size(P, 2)
+    w = collect(Float64, (4π .* r .^ 2) .* w_rows)                       # [nR, nW] column-major = the ABI's [nW, nR] rows
+    bulk_f = zeros(Float64, n_μ, 4, nW);  C = zeros(Float64, 2, nW);  greek = zeros(Float64, l_max, 6, nW);  ms = zeros(Float64, 3)
+    momcheck(MomCore.mom_mie_nai2(arch.device, nR, collect(Float64, r), nW, w, Float64(λ), Float64(nᵣ), Float64(nᵢ), n_μ,
+                                  collect(Float64, w_μ), n_max, collect(Float64, leg_π), collect(Float64, leg_τ), l_max,
+                                  collect(Float64, P), collect(Float64, P²), collect(Float64, R²), collect(Float64, T²), 0, bulk_f, C,
+                                  greek, ms))
+    C_sca, C_ext = C[1, 1], C[2, 1]
+    value = (α = greek[:, 1, 1] ./ C_sca, β = greek[:, 2, 1] ./ C_sca, γ = greek[:, 3, 1] ./ C_sca, δ = greek[:, 4, 1] ./ C_sca,
+             ϵ = greek[:, 5, 1] ./ C_sca, ζ = greek[:, 6, 1] ./ C_sca, ω̃ = C_sca / C_ext, k = C_ext, fᵗ = 1.0)
+    partials = map(2:nW) do j
+        d(q) = greek[:, q, j] ./ C_sca .- greek[:, q, 1] .* (C[1, j] / C_sca^2)
+        (α = d(1), β = d(2), γ = d(3), δ = d(4), ϵ = d(5), ζ = d(6), ω̃ = C[1, j] / C_ext - C_sca * C[2, j] / C_ext^2, k = C[2, j], fᵗ = 0.0)
+    end
+    return value, partials, ms
+end
+# <<< mie

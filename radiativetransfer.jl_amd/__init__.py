@@ -5,8 +5,10 @@ The directory name contains a dot, so import it through the root-level shim:
 """
 from . import _lib  # noqa: F401
 from ._lib import Handle, MomError, voigt_xsec, voigt_xsec_dual, load  # noqa: F401
-from . import corert, scenes, absorption, sharding  # noqa: F401,E402
+from . import corert, scenes, absorption, sharding, scattering  # noqa: F401,E402
 from .absorption import (Range, InterpolationModel, make_interpolation_model, interpolation_model_from_table,  # noqa: F401,E402
                          save_interpolation_model, load_interpolation_model)
 from .corert import (MI355X, rt_run, rt_run_dual, ScenePartial, OpticsPartial, rt_run_dual_device_optics, rt_run_test_ms, rt_run_operators, model_from_parameters, prepare_scene,  # noqa: F401,E402
                      vSmartMOM_Parameters, vSmartMOM_Model, Stokes_I, Stokes_IQU, Stokes_IQUV)
+from .scattering import (LogNormal, Aerosol, NAI2, δBGE, make_mie_model, compute_aerosol_optical_properties,  # noqa: F401,E402
+                         compute_ref_aerosol_extinction, truncate_phase)

@@ -46,6 +46,7 @@ MOM_OPT_LUT_BATCH = 15           # (p, T) nodes per batch of mom_lut_build (0, d
 # the absorption model (mom_absorption_set_model, mom_lineshape_xsec): HitranModel.broadening, HitranModel.CEF
 BROADENING_VOIGT, BROADENING_DOPPLER, BROADENING_LORENTZ = 0, 1, 2
 CEF_HW32SD, CEF_HW32VOIGT = 0, 1
+MOM_MIE_FULL_K = 1   # mom_mie_nai2 flag: every radius tile sums l to the global n_max (test access; bitwise the same result)
 
 
 class MomError(RuntimeError):
@@ -151,6 +152,9 @@ SIGNATURES = {
     "mom_lineshape_xsec": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [c_dp] * 5 + [c_ip, c_ip, C.c_int, c_dp, c_dp]),
     "mom_lineshape_xsec_dual": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int] + [c_dp] * 10 + [c_ip, c_ip, C.c_int, c_dp, c_dp, c_dp]),
     "mom_voigt_last_kernel_ms": (C.c_double, []),
+    "mom_mie_nai2": (C.c_int, [C.c_int, C.c_int, c_dp, C.c_int, c_dp, C.c_double, C.c_double, C.c_double, C.c_int, c_dp, C.c_int, c_dp,
+                               c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp]),
+    "mom_mie_coefficients": (C.c_int, [C.c_int, C.c_int, c_dp, C.c_double, C.c_double, C.c_int, c_dp, c_dp, c_dp, c_dp]),
 }
 
 _lib = None
@@ -814,3 +818,34 @@ def lineshape_xsec_dual(broadening, cef, nu, gamma_d, gamma_l, y, S, dnu, dgamma
 
 def voigt_last_kernel_ms() -> float:
     return float(load().mom_voigt_last_kernel_ms())
+
+
+def mie_nai2(r, w, lam, n_r, n_i, w_mu, pi_tab, tau_tab, P, P2, R2, T2, flags: int = 0, device: int = 0):
+    """mom_mie_nai2: r [nR] ascending, w [nW, nR] weight rows, pi_tab / tau_tab [n_mu, n_max] and P, P2, R2, T2 [n_mu, l_max] as
+    numpy builds them (the ABI's mu-fastest layout is their transpose).  Returns (bulk_f [nW, 4, n_mu], C [nW, 2],
+    greek [nW, 6, l_max], gpu_ms [3]), all unnormalised."""
+    lib = load()
+    r, w, w_mu = f64(r), f64(np.atleast_2d(w)), f64(w_mu)
+    tabs = [f64(np.asarray(t, dtype=np.float64).T) for t in (pi_tab, tau_tab, P, P2, R2, T2)]
+    nW, nR, n_mu = w.shape[0], len(r), len(w_mu)
+    if w.shape[1] != nR or any(t.shape[1] != n_mu for t in tabs) or tabs[0].shape != tabs[1].shape or \
+            any(t.shape != tabs[2].shape for t in tabs[3:]):
+        raise ValueError("mie_nai2: array shapes do not agree")
+    n_max, l_max = tabs[0].shape[0], tabs[2].shape[0]
+    bulk, Cx, greek, ms = np.empty((nW, 4, n_mu)), np.empty((nW, 2)), np.empty((nW, 6, l_max)), np.zeros(3)
+    rc = lib.mom_mie_nai2(device, nR, dp(r), nW, dp(w), float(lam), float(n_r), float(n_i), n_mu, dp(w_mu), n_max, dp(tabs[0]),
+                          dp(tabs[1]), l_max, *[dp(t) for t in tabs[2:]], int(flags), dp(bulk), dp(Cx), dp(greek), dp(ms))
+    if rc != MOM_OK:
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return bulk, Cx, greek, ms
+
+
+def mie_coefficients(x, n_r, n_i, n_max: int, device: int = 0):
+    """mom_mie_coefficients: (a, b) complex [n_max, nX] for the size parameters x (row n - 1 = order n)."""
+    lib = load()
+    x = f64(np.atleast_1d(x))
+    out = [np.empty((int(n_max), len(x))) for _ in range(4)]
+    rc = lib.mom_mie_coefficients(device, len(x), dp(x), float(n_r), float(n_i), int(n_max), *[dp(o) for o in out])
+    if rc != MOM_OK:
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return out[0] + 1j * out[1], out[2] + 1j * out[3]

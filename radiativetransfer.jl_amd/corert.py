@@ -478,10 +478,12 @@ def surface_inputs(brdf, pol_type: PolarizationType, qp_μ: np.ndarray, max_m: i
 
 @dataclass
 class AerosolOptics:
-    """The fields of the reference's AerosolOptics that the RT core consumes."""
+    """The fields of the reference's AerosolOptics that the RT core consumes; k (the bulk extinction cross section, which scales
+    τ_aer between wavelengths on the host) is carried for scattering.compute_aerosol_optical_properties."""
     greek_coefs: GreekCoefs
     ω̃: float
     fᵗ: float = 0.0
+    k: float = 1.0
 
 
 @dataclass
@@ -517,8 +519,8 @@ class vSmartMOM_Model:
 def model_from_parameters(params: vSmartMOM_Parameters, τ_rayl, τ_abs, τ_aer=None,
                           aerosol_optics: Optional[List[AerosolOptics]] = None) -> vSmartMOM_Model:
     """model_from_parameters(params) (model_from_parameters.jl:12-194) for callers that bring
-    their own optical-depth tables (the reference computes them from profiles/HITRAN/Mie, which
-    stays host-side Julia and is outside this package's scope)."""
+    their own optical-depth tables (absorption.py and scattering.py compute the gas and the aerosol
+    inputs on the device; the reference's profile handling stays host-side and is outside this package's scope)."""
     qp = rt_set_streams(params.quadrature_type, params.l_trunc, params.sza, params.vza, params.polarization_type)
     τ_rayl = np.asarray(τ_rayl, dtype=np.float64)
     τ_abs = np.asarray(τ_abs, dtype=np.float64)

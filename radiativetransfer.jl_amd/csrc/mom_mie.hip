@@ -1,0 +1,450 @@
+// mom_mie.hip -- Mie aerosol optics by the Siewert NAI-2 method on gfx950 (Float64).
+//
+// Restates compute_aerosol_optical_properties(::MieModel{NAI2}) (src/Scattering/compute_NAI2.jl:16-182) with
+// compute_mie_ab!, compute_mie_S1S2! and get_n_max (mie_helper_functions.jl:17-71, 154-167).  The reference loops over the
+// radii of the size distribution on the host; here the call is four launches:
+//   (a) k_mie_ab     one radius per lane: downward recurrence of the logarithmic derivative D_n(m x), upward recurrence of
+//                    psi, chi, xi and a_n, b_n; writes c_n a_n, c_n b_n (c_n = (2n+1) / (n (n+1))) as four real planes
+//                    [Kp, nRp], radius fastest, exact zeros above the radius' own n_max
+//   (b) k_mie_amp    S1 = sum_l (c a)_l tau_l + (c b)_l pi_l, S2 = sum_l (c a)_l pi_l + (c b)_l tau_l as a real GEMM on
+//                    v_mfma_f64_16x16x4 ([tau | pi] times the four planes), with the epilogue in registers: f11, f33, f12,
+//                    f34 of the tile, times each weight row, summed over the tile's radii.  No [n_mu, nR] array exists.
+//   (c) k_mie_sum    the per-chunk partials of (b) added in chunk order (no floating-point atomics: two runs are bitwise equal)
+//   (d) k_mie_greek  the projections of the bulk elements onto P, P2, R2, T2 (compute_NAI2.jl:146-160), one wavefront per l
+// The radii arrive ascending, so n_max is monotone over them and a radius tile's K loop ends at the tile's largest n_max
+// (rounded up to the k-step of 4): what is left out are products with the exact zeros of (a).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <vector>
+
+#include "momcore.h"
+#include "mom_host.hpp"
+
+namespace {
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+constexpr int kTileR = 16;    // radii per tile of (b): the N extent of the MFMA
+constexpr int kMuBlock = 32;  // mu rows per wavefront of (b): two M tiles share every B operand
+constexpr int kKStep = 4;     // K extent of the MFMA
+constexpr int kMaxChunks = 128;  // radius chunks of (b): beyond 2048 radii a wavefront takes several tiles
+
+// ---- (a) Mie coefficients ------------------------------------------------------------------------------------------------
+// SCALE: write c_n a_n, c_n b_n (the planes (b) reads); otherwise a_n, b_n themselves (mom_mie_coefficients).
+// Complex arithmetic is written out on the real and imaginary parts, a quotient u / v as u conj(v) / |v|^2, and the compiler
+// may not contract a product and a sum into an FMA here: the upward psi recurrence is only conditionally stable, so the
+// order and the rounding of every operation are part of the result (tests/mie_oracle.py performs the same operations).
+template <bool SCALE>
+__global__ void __launch_bounds__(64) k_mie_ab(int nR, int ld, const double *__restrict__ x, const int *__restrict__ nmax,
+                                               const int *__restrict__ nmx, double mr, double mi, double *__restrict__ Dre,
+                                               double *__restrict__ Dim, double *__restrict__ aR, double *__restrict__ aI,
+                                               double *__restrict__ bR, double *__restrict__ bI, double *__restrict__ ssca,
+                                               double *__restrict__ sext) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= nR) return;
+  const double xi = x[i];
+  const int nm = nmax[i], ntop = nmx[i];
+  // y = x m; (n + 1) / y = (n + 1) * (conj(y) / |y|^2)
+  const double yr = xi * mr, yi = xi * mi, y2 = yr * yr + yi * yi;
+  const double iyr = yr / y2, iyi = -yi / y2;
+  double dr = 0.0, di = 0.0;  // D_ntop = 0
+  for (int n = ntop - 1; n >= 1; --n) {
+    const double c = (double)(n + 1), qr = c * iyr, qi = c * iyi;
+    const double sr = dr + qr, si = di + qi, s2 = sr * sr + si * si;
+    dr = qr - sr / s2;  // D_n = (n+1)/y - 1 / (D_{n+1} + (n+1)/y)
+    di = qi + si / s2;
+    if (n <= nm) {
+      Dre[(size_t)(n - 1) * ld + i] = dr;
+      Dim[(size_t)(n - 1) * ld + i] = di;
+    }
+  }
+  const double m2 = mr * mr + mi * mi;
+  double psi0 = cos(xi), psi1 = sin(xi), chi0 = -psi1, chi1 = psi0;
+  double sca = 0.0, ext = 0.0;
+  for (int n = 1; n <= nm; ++n) {
+    const double tn = (double)(2 * n - 1);
+    const double psi = tn * psi1 / xi - psi0, chi = tn * chi1 / xi - chi0;  // xi_n = psi - i chi
+    const double er = Dre[(size_t)(n - 1) * ld + i], ei = Dim[(size_t)(n - 1) * ld + i];
+    const double nx = (double)n / xi;
+    // t_a = D / m + n / x, t_b = D m + n / x
+    const double tar = (er * mr + ei * mi) / m2 + nx, tai = (ei * mr - er * mi) / m2;
+    const double tbr = (er * mr - ei * mi) + nx, tbi = er * mi + ei * mr;
+    // (t psi - psi_1) / (t xi - xi_1)
+    const double anr = tar * psi - psi1, ani = tai * psi;
+    const double adr = (tar * psi + tai * chi) - psi1, adi = (tai * psi - tar * chi) + chi1, ad2 = adr * adr + adi * adi;
+    const double ar = (anr * adr + ani * adi) / ad2, ai = (ani * adr - anr * adi) / ad2;
+    const double bnr = tbr * psi - psi1, bni = tbi * psi;
+    const double bdr = (tbr * psi + tbi * chi) - psi1, bdi = (tbi * psi - tbr * chi) + chi1, bd2 = bdr * bdr + bdi * bdi;
+    const double br = (bnr * bdr + bni * bdi) / bd2, bi = (bni * bdr - bnr * bdi) / bd2;
+    const double w2 = (double)(2 * n + 1);
+    sca = sca + w2 * ((ar * ar + ai * ai) + (br * br + bi * bi));
+    ext = ext + w2 * (ar + br);
+    const double c = SCALE ? w2 / ((double)n * (double)(n + 1)) : 1.0;
+    const size_t o = (size_t)(n - 1) * ld + i;
+    aR[o] = c * ar;
+    aI[o] = c * ai;
+    bR[o] = c * br;
+    bI[o] = c * bi;
+    psi0 = psi1;
+    psi1 = psi;
+    chi0 = chi1;
+    chi1 = chi;
+  }
+  if (ssca) ssca[i] = sca;
+  if (sext) sext[i] = ext;
+}
+
+// ---- (b) amplitude GEMM with the phase-matrix epilogue -------------------------------------------------------------------
+// One wavefront per block: 32 mu rows (blockIdx.x) times the radius tiles of chunk g = blockIdx.y (one tile of every G, in ascending order).
+// Operand layouts of v_mfma_f64_16x16x4 as in mom_tile.hpp: A lane l = A[row l & 15][k l >> 4], B lane l = B[k l >> 4][col l & 15],
+// C lane l register r = C[row (l >> 4) + 4 r][col l & 15].  tau, pi: [Kp, nMuP]; the planes: [Kp, nRp]; all zero padded, so
+// the loads carry no masks.  partial: [G, NW, 4, nMuP].
+template <int NW>
+__global__ void __launch_bounds__(64) k_mie_amp(int nR, int nMuP, int nRp, int Kp, int nTiles, int G,
+                                                const double *__restrict__ tau, const double *__restrict__ pi,
+                                                const double *__restrict__ caR, const double *__restrict__ caI,
+                                                const double *__restrict__ cbR, const double *__restrict__ cbI,
+                                                const double *__restrict__ x, const int *__restrict__ nmax,
+                                                const double *__restrict__ w, int fullK, double *__restrict__ partial) {
+  const int lane = threadIdx.x, lr = lane & 15, lq = lane >> 4;
+  const int mu0 = kMuBlock * blockIdx.x, g = blockIdx.y;
+  d4 bulk[NW][4][2];
+#pragma unroll
+  for (int k = 0; k < NW; ++k)
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+      for (int m = 0; m < 2; ++m) bulk[k][f][m] = (d4){0.0, 0.0, 0.0, 0.0};
+  for (int j = 0; j * G < nTiles; ++j) {
+    const int t = j * G + ((j & 1) ? G - 1 - g : g);  // boustrophedon: n_max grows with t, so the chunks' K sums stay close
+    if (t >= nTiles) continue;
+    const int i0 = kTileR * t, ilast = min(i0 + kTileR - 1, nR - 1);
+    const int kEnd = fullK ? Kp : min(Kp, (nmax[ilast] + kKStep - 1) / kKStep * kKStep);
+    d4 s[4][2];  // S1 re, S1 im, S2 re, S2 im of the two M tiles
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int m = 0; m < 2; ++m) s[q][m] = (d4){0.0, 0.0, 0.0, 0.0};
+    const double *pt = tau + (size_t)lq * nMuP + mu0 + lr, *pp = pi + (size_t)lq * nMuP + mu0 + lr;
+    const size_t ob = (size_t)lq * nRp + i0 + lr;
+    for (int k0 = 0; k0 < kEnd; k0 += kKStep) {
+      const size_t oa = (size_t)k0 * nMuP, obk = ob + (size_t)k0 * nRp;
+      const double aT[2] = {pt[oa], pt[oa + 16]}, aP[2] = {pp[oa], pp[oa + 16]};
+      const double bAR = caR[obk], bAI = caI[obk], bBR = cbR[obk], bBI = cbI[obk];
+#pragma unroll
+      for (int m = 0; m < 2; ++m) {
+        s[0][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aT[m], bAR, s[0][m], 0, 0, 0);
+        s[1][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aT[m], bAI, s[1][m], 0, 0, 0);
+        s[2][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aP[m], bAR, s[2][m], 0, 0, 0);
+        s[3][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aP[m], bAI, s[3][m], 0, 0, 0);
+      }
+#pragma unroll
+      for (int m = 0; m < 2; ++m) {
+        s[0][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aP[m], bBR, s[0][m], 0, 0, 0);
+        s[1][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aP[m], bBI, s[1][m], 0, 0, 0);
+        s[2][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aT[m], bBR, s[2][m], 0, 0, 0);
+        s[3][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aT[m], bBI, s[3][m], 0, 0, 0);
+      }
+    }
+    // epilogue: this lane's column is radius i0 + lr (padding: x = 0, weights 0, S = 0)
+    const double xi = x[i0 + lr], hx = xi > 0.0 ? 0.5 / (xi * xi) : 0.0;
+    double wk[NW];
+#pragma unroll
+    for (int k = 0; k < NW; ++k) wk[k] = w[(size_t)k * nRp + i0 + lr];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double s1r = s[0][m][r], s1i = s[1][m][r], s2r = s[2][m][r], s2i = s[3][m][r];
+        const double n1 = s1r * s1r + s1i * s1i, n2 = s2r * s2r + s2i * s2i;
+        const double f[4] = {hx * (n1 + n2),                            // f11 =  1/2x^2 (|S1|^2 + |S2|^2)
+                             hx * (2.0 * (s1r * s2r + s1i * s2i)),      // f33 =  1/2x^2 Re(S1 S2* + S2 S1*)
+                             -hx * (n1 - n2),                           // f12 = -1/2x^2 (|S1|^2 - |S2|^2)
+                             -hx * (2.0 * (s1i * s2r - s1r * s2i))};    // f34 = -1/2x^2 Im(S1 S2* - S2 S1*)
+#pragma unroll
+        for (int k = 0; k < NW; ++k)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) bulk[k][q][m][r] = fma(wk[k], f[q], bulk[k][q][m][r]);
+      }
+  }
+  // sum over the 16 radii of the tile columns (fixed butterfly), lane lr = 0 of every row writes
+#pragma unroll
+  for (int k = 0; k < NW; ++k)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          double v = bulk[k][q][m][r];
+#pragma unroll
+          for (int off = 1; off < 16; off <<= 1) v += __shfl_xor(v, off);
+          if (lr == 0) partial[(((size_t)g * NW + k) * 4 + q) * nMuP + mu0 + 16 * m + lq + 4 * r] = v;
+        }
+}
+
+// ---- (c) partials of the G radius chunks, in chunk order -----------------------------------------------------------------
+__global__ void k_mie_sum(int G, int rows, int n_mu, int nMuP, const double *__restrict__ partial, double *__restrict__ bulk) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;  // (row = k * 4 + q, mu)
+  if (j >= rows * n_mu) return;
+  const int row = j / n_mu, mu = j - row * n_mu;
+  double v = 0.0;
+  for (int g = 0; g < G; ++g) v += partial[((size_t)g * rows + row) * nMuP + mu];
+  bulk[j] = v;
+}
+
+// ---- (d) Greek coefficients (unnormalised) -------------------------------------------------------------------------------
+// one wavefront per (l, weight row); bulk: [nW, 4, n_mu] in the order f11, f33, f12, f34; tables [l_max, n_mu], mu fastest;
+// greek: [nW, 6, l_max] in the order alpha, beta, gamma, delta, epsilon, zeta
+__global__ void __launch_bounds__(64) k_mie_greek(int n_mu, int l_max, const double *__restrict__ w_mu, const double *__restrict__ bulk,
+                                                  const double *__restrict__ P, const double *__restrict__ P2,
+                                                  const double *__restrict__ R2, const double *__restrict__ T2,
+                                                  double *__restrict__ greek) {
+  const int l = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
+  const double *f11 = bulk + (size_t)k * 4 * n_mu, *f33 = f11 + n_mu, *f12 = f33 + n_mu, *f34 = f12 + n_mu;
+  double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int j = lane; j < n_mu; j += 64) {
+    const size_t o = (size_t)l * n_mu + j;
+    const double wm = w_mu[j], p = P[o], p2 = P2[o], r2 = R2[o], t2 = T2[o];
+    a[0] += wm * (f11[j] * r2 + f33[j] * t2);
+    a[1] += wm * (f11[j] * p);
+    a[2] += wm * (f12[j] * p2);
+    a[3] += wm * (f33[j] * p);
+    a[4] += wm * (f34[j] * p2);
+    a[5] += wm * (f33[j] * r2 + f11[j] * t2);
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q)
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) a[q] += __shfl_xor(a[q], off);
+  if (lane == 0) {
+    const double dl = (double)l, pre = (2.0 * dl + 1.0) / 2.0;
+    const double fac = l >= 2 ? pre * sqrt(1.0 / ((dl - 1.0) * dl * (dl + 1.0) * (dl + 2.0))) : 0.0;
+    double *o = greek + (size_t)k * 6 * l_max + l;
+    o[0] = fac * a[0];
+    o[(size_t)l_max] = pre * a[1];
+    o[(size_t)2 * l_max] = fac * a[2];
+    o[(size_t)3 * l_max] = pre * a[3];
+    o[(size_t)4 * l_max] = fac * a[4];
+    o[(size_t)5 * l_max] = fac * a[5];
+  }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------
+int mie_fail(const char *fn, const char *what) {
+  char buf[256];
+  snprintf(buf, sizeof buf, "%s: %s", fn, what);
+  mom_set_global_error(buf);
+  return MOM_EINVAL;
+}
+
+// get_n_max (mie_helper_functions.jl:17) and the start of the downward recurrence (compute_NAI2.jl:94-95); round = to nearest even
+int mie_n_max(double x) { return (int)std::nearbyint(x + 4.05 * std::pow(x, 1.0 / 3.0) + 10.0); }
+int mie_nmx(double x, int nmax, double n_r, double n_i) {
+  return (int)std::nearbyint(std::fmax((double)nmax, std::fabs(x * (n_r - n_i))) + 51.0);
+}
+
+int mie_device(const char *fn, int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    char buf[128];
+    snprintf(buf, sizeof buf, "%s: no HIP device available", fn);
+    mom_set_global_error(buf);
+    return MOM_EHIP;
+  }
+  if (device < 0 || device >= ndev) return mie_fail(fn, "device index out of range");
+  return MOM_OK;
+}
+
+#define MCHK(call)                                                                                     \
+  do {                                                                                                 \
+    hipError_t e__ = (call);                                                                           \
+    if (e__ != hipSuccess) {                                                                           \
+      char buf__[384];                                                                                 \
+      snprintf(buf__, sizeof buf__, "%s: %s failed: %s", fn, #call, hipGetErrorString(e__));           \
+      mom_set_global_error(buf__);                                                                     \
+      rc = MOM_EHIP;                                                                                   \
+      goto done;                                                                                       \
+    }                                                                                                  \
+  } while (0)
+
+inline size_t round_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
+
+template <int NW>
+void launch_amp(hipStream_t st, dim3 grid, int nR, int nMuP, int nRp, int Kp, int nTiles, int G, const double *tau, const double *pi,
+                const double *const *pl, const double *x, const int *nmax, const double *w, int fullK, double *partial) {
+  hipLaunchKernelGGL(k_mie_amp<NW>, grid, dim3(64), 0, st, nR, nMuP, nRp, Kp, nTiles, G, tau, pi, pl[0], pl[1], pl[2], pl[3], x, nmax, w,
+                     fullK, partial);
+}
+
+}  // namespace
+
+extern "C" int mom_mie_nai2(int device, int nR, const double *r, int nW, const double *w, double lambda, double n_r, double n_i,
+                            int n_mu, const double *w_mu, int n_max, const double *pi_tab, const double *tau_tab, int l_max,
+                            const double *P, const double *P2, const double *R2, const double *T2, int flags, double *bulk_f,
+                            double *C, double *greek, double *gpu_ms) {
+  const char *fn = "mom_mie_nai2";
+  if (nR < 1 || n_mu < 1) return mie_fail(fn, "nR and n_mu must be at least 1");
+  if (nW < 1 || nW > MOM_MIE_MAX_WEIGHT_ROWS) return mie_fail(fn, "nW must be 1..4");
+  if (!(lambda > 0.0)) return mie_fail(fn, "lambda must be positive");
+  if (!(n_i >= 0.0) || !std::isfinite(n_r) || !std::isfinite(n_i)) return mie_fail(fn, "n_i must be >= 0 (m = n_r + i n_i)");
+  if (l_max < 1 || n_max < 1) return mie_fail(fn, "l_max and n_max must be at least 1");
+  if (flags & ~MOM_MIE_FULL_K) return mie_fail(fn, "unknown flag");
+  if (!r || !w || !w_mu || !pi_tab || !tau_tab || !P || !P2 || !R2 || !T2 || !bulk_f || !C || !greek)
+    return mie_fail(fn, "null pointer");
+  if (!(r[0] > 0.0) || !std::isfinite(r[nR - 1])) return mie_fail(fn, "r[0] must be positive and r finite");
+  for (int i = 1; i < nR; ++i)
+    if (!(r[i] > r[i - 1])) return mie_fail(fn, "r must be ascending");
+  const size_t nRp = round_up(nR, kTileR), Kp = round_up(n_max, kKStep), nMuP = round_up(n_mu, kMuBlock);
+  const double kw = 2.0 * M_PI / lambda;  // wavenumber; x = k r
+  std::vector<double> hx(nRp, 0.0);
+  std::vector<int> hn(2 * nRp, 0);  // n_max,i | nmx_i
+  for (int i = 0; i < nR; ++i) {
+    hx[i] = kw * r[i];
+    hn[i] = mie_n_max(hx[i]);
+    hn[nRp + i] = mie_nmx(hx[i], hn[i], n_r, n_i);
+    if (hn[i] > n_max) return mie_fail(fn, "n_max is smaller than the largest per-radius n_max");
+    if (i > 0 && hn[i] < hn[i - 1]) return mie_fail(fn, "per-radius n_max not monotone");
+  }
+  int rc = mie_device(fn, device);
+  if (rc != MOM_OK) return rc;
+
+  const int nTiles = (int)(nRp / kTileR), nMuBlk = (int)(nMuP / kMuBlock);
+  int G = 2048 / nMuBlk;  // about two wavefronts per SIMD of the device, at most kMaxChunks partials per bulk element
+  G = G < 1 ? 1 : (G > kMaxChunks ? kMaxChunks : G);
+  G = G > nTiles ? nTiles : G;
+  // one allocation, carved in doubles (the two int arrays last)
+  const size_t nTab = Kp * nMuP, nPl = Kp * nRp, nD = (size_t)n_max * nRp, nLeg = (size_t)l_max * n_mu;
+  const size_t nPart = (size_t)G * nW * 4 * nMuP, nBulk = (size_t)nW * 4 * n_mu, nGreek = (size_t)nW * 6 * l_max;
+  const size_t doubles = 2 * nTab + 4 * nPl + 2 * nD + 3 * nRp + (size_t)nW * nRp + n_mu + 4 * nLeg + nPart + nBulk + nGreek;
+  const size_t bytes = doubles * sizeof(double) + 2 * nRp * sizeof(int);
+  char *base = nullptr;
+  hipStream_t st = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  std::vector<double> hs(2 * nRp);
+  MCHK(hipSetDevice(device));
+  MCHK(hipStreamCreate(&st));
+  MCHK(hipMalloc((void **)&base, bytes));
+  {
+    double *p = (double *)base;
+    double *d_tau = p; p += nTab;
+    double *d_pi = p; p += nTab;
+    double *d_pl[4];
+    for (int q = 0; q < 4; ++q) { d_pl[q] = p; p += nPl; }
+    double *d_Dre = p; p += nD;
+    double *d_Dim = p; p += nD;
+    double *d_x = p; p += nRp;
+    double *d_ss = p; p += 2 * nRp;  // sum (2n+1)(|a|^2 + |b|^2) | sum (2n+1) Re(a + b)
+    double *d_w = p; p += (size_t)nW * nRp;
+    double *d_wmu = p; p += n_mu;
+    double *d_leg[4];
+    for (int q = 0; q < 4; ++q) { d_leg[q] = p; p += nLeg; }
+    double *d_part = p; p += nPart;
+    double *d_bulk = p; p += nBulk;
+    double *d_greek = p; p += nGreek;
+    int *d_n = (int *)p;
+    MCHK(hipMemsetAsync(base, 0, bytes, st));  // the padding of every table and plane, and the planes above each radius' n_max
+    MCHK(hipMemcpy2DAsync(d_tau, nMuP * sizeof(double), tau_tab, (size_t)n_mu * sizeof(double), (size_t)n_mu * sizeof(double), n_max,
+                          hipMemcpyHostToDevice, st));
+    MCHK(hipMemcpy2DAsync(d_pi, nMuP * sizeof(double), pi_tab, (size_t)n_mu * sizeof(double), (size_t)n_mu * sizeof(double), n_max,
+                          hipMemcpyHostToDevice, st));
+    MCHK(hipMemcpyAsync(d_x, hx.data(), nRp * sizeof(double), hipMemcpyHostToDevice, st));
+    MCHK(hipMemcpyAsync(d_n, hn.data(), 2 * nRp * sizeof(int), hipMemcpyHostToDevice, st));
+    MCHK(hipMemcpy2DAsync(d_w, nRp * sizeof(double), w, (size_t)nR * sizeof(double), (size_t)nR * sizeof(double), nW,
+                          hipMemcpyHostToDevice, st));
+    MCHK(hipMemcpyAsync(d_wmu, w_mu, (size_t)n_mu * sizeof(double), hipMemcpyHostToDevice, st));
+    const double *leg[4] = {P, P2, R2, T2};
+    for (int q = 0; q < 4; ++q) MCHK(hipMemcpyAsync(d_leg[q], leg[q], nLeg * sizeof(double), hipMemcpyHostToDevice, st));
+    for (int q = 0; q < 4; ++q) MCHK(hipEventCreate(&ev[q]));
+    MCHK(hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(k_mie_ab<true>, dim3((nR + 63) / 64), dim3(64), 0, st, nR, (int)nRp, d_x, d_n, d_n + nRp, n_r, n_i, d_Dre, d_Dim,
+                       d_pl[0], d_pl[1], d_pl[2], d_pl[3], d_ss, d_ss + nRp);
+    MCHK(hipGetLastError());
+    MCHK(hipEventRecord(ev[1], st));
+    {
+      const dim3 grid(nMuBlk, G);
+      const int fullK = (flags & MOM_MIE_FULL_K) ? 1 : 0;
+      switch (nW) {
+        case 1: launch_amp<1>(st, grid, nR, (int)nMuP, (int)nRp, (int)Kp, nTiles, G, d_tau, d_pi, d_pl, d_x, d_n, d_w, fullK, d_part); break;
+        case 2: launch_amp<2>(st, grid, nR, (int)nMuP, (int)nRp, (int)Kp, nTiles, G, d_tau, d_pi, d_pl, d_x, d_n, d_w, fullK, d_part); break;
+        case 3: launch_amp<3>(st, grid, nR, (int)nMuP, (int)nRp, (int)Kp, nTiles, G, d_tau, d_pi, d_pl, d_x, d_n, d_w, fullK, d_part); break;
+        default: launch_amp<4>(st, grid, nR, (int)nMuP, (int)nRp, (int)Kp, nTiles, G, d_tau, d_pi, d_pl, d_x, d_n, d_w, fullK, d_part); break;
+      }
+      MCHK(hipGetLastError());
+      hipLaunchKernelGGL(k_mie_sum, dim3((unsigned)((nBulk + 255) / 256)), dim3(256), 0, st, G, nW * 4, n_mu, (int)nMuP, d_part, d_bulk);
+      MCHK(hipGetLastError());
+    }
+    MCHK(hipEventRecord(ev[2], st));
+    hipLaunchKernelGGL(k_mie_greek, dim3(l_max, nW), dim3(64), 0, st, n_mu, l_max, d_wmu, d_bulk, d_leg[0], d_leg[1], d_leg[2], d_leg[3],
+                       d_greek);
+    MCHK(hipGetLastError());
+    MCHK(hipEventRecord(ev[3], st));
+    MCHK(hipMemcpyAsync(bulk_f, d_bulk, nBulk * sizeof(double), hipMemcpyDeviceToHost, st));
+    MCHK(hipMemcpyAsync(greek, d_greek, nGreek * sizeof(double), hipMemcpyDeviceToHost, st));
+    MCHK(hipMemcpyAsync(hs.data(), d_ss, 2 * nRp * sizeof(double), hipMemcpyDeviceToHost, st));
+    MCHK(hipStreamSynchronize(st));
+    // C_sca,i = 2 pi / k^2 * sum, weighted by w_i / (4 pi r_i^2): w_i * sum_i / (2 x_i^2), added in radius order (the terms in
+    // Float64, the running sum in the host's long double, so that the O(nR) sum adds no rounding of its own)
+    for (int k = 0; k < nW; ++k)
+      for (int q = 0; q < 2; ++q) {
+        long double acc = 0.0L;
+        for (int i = 0; i < nR; ++i) acc += (long double)(w[(size_t)k * nR + i] * (hs[q * nRp + i] / (2.0 * hx[i] * hx[i])));
+        C[2 * k + q] = (double)acc;
+      }
+    if (gpu_ms)
+      for (int q = 0; q < 3; ++q) {
+        float ms = 0.f;
+        MCHK(hipEventElapsedTime(&ms, ev[q], ev[q + 1]));
+        gpu_ms[q] = ms;
+      }
+  }
+done:
+  for (int q = 0; q < 4; ++q)
+    if (ev[q]) (void)hipEventDestroy(ev[q]);
+  if (base) (void)hipFree(base);
+  if (st) (void)hipStreamDestroy(st);
+  return rc;
+}
+
+extern "C" int mom_mie_coefficients(int device, int nX, const double *x, double n_r, double n_i, int n_max, double *a_re, double *a_im,
+                                    double *b_re, double *b_im) {
+  const char *fn = "mom_mie_coefficients";
+  if (nX < 1 || n_max < 1 || !x || !a_re || !a_im || !b_re || !b_im) return mie_fail(fn, "bad argument (null pointer or non-positive size)");
+  if (!(n_i >= 0.0) || !std::isfinite(n_r) || !std::isfinite(n_i)) return mie_fail(fn, "n_i must be >= 0 (m = n_r + i n_i)");
+  std::vector<int> hn(2 * (size_t)nX);
+  for (int i = 0; i < nX; ++i) {
+    if (!(x[i] > 0.0) || !std::isfinite(x[i])) return mie_fail(fn, "x must be positive");
+    hn[i] = mie_n_max(x[i]);
+    hn[nX + i] = mie_nmx(x[i], hn[i], n_r, n_i);
+    if (hn[i] > n_max) return mie_fail(fn, "n_max is smaller than the largest per-x n_max");
+  }
+  int rc = mie_device(fn, device);
+  if (rc != MOM_OK) return rc;
+  const size_t nPl = (size_t)n_max * nX;
+  const size_t bytes = (6 * nPl + nX) * sizeof(double) + 2 * (size_t)nX * sizeof(int);
+  char *base = nullptr;
+  hipStream_t st = nullptr;
+  MCHK(hipSetDevice(device));
+  MCHK(hipStreamCreate(&st));
+  MCHK(hipMalloc((void **)&base, bytes));
+  {
+    double *d_pl = (double *)base, *d_D = d_pl + 4 * nPl, *d_x = d_D + 2 * nPl;
+    int *d_n = (int *)(d_x + nX);
+    double *out[4] = {a_re, a_im, b_re, b_im};
+    MCHK(hipMemsetAsync(base, 0, bytes, st));
+    MCHK(hipMemcpyAsync(d_x, x, (size_t)nX * sizeof(double), hipMemcpyHostToDevice, st));
+    MCHK(hipMemcpyAsync(d_n, hn.data(), 2 * (size_t)nX * sizeof(int), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_mie_ab<false>, dim3((nX + 63) / 64), dim3(64), 0, st, nX, nX, d_x, d_n, d_n + nX, n_r, n_i, d_D, d_D + nPl, d_pl,
+                       d_pl + nPl, d_pl + 2 * nPl, d_pl + 3 * nPl, (double *)nullptr, (double *)nullptr);
+    MCHK(hipGetLastError());
+    for (int q = 0; q < 4; ++q) MCHK(hipMemcpyAsync(out[q], d_pl + q * nPl, nPl * sizeof(double), hipMemcpyDeviceToHost, st));
+    MCHK(hipStreamSynchronize(st));
+  }
+done:
+  if (base) (void)hipFree(base);
+  if (st) (void)hipStreamDestroy(st);
+  return rc;
+}

@@ -1,0 +1,285 @@
+"""Mie aerosol optics (src/Scattering): make_mie_model(NAI2(), ...), compute_aerosol_optical_properties,
+compute_ref_aerosol_extinction and truncate_phase(δBGE, ...).
+
+The sums over radii, orders and angles run on the device (mom_mie_nai2, csrc/mom_mie.hip); the host builds what they read --
+the radius quadrature, the Gauss nodes of the scattering angle, the π/τ and P/P²/R²/T² tables (O(n_μ²) recurrences, vectorised
+over μ) -- and does the arithmetic that follows the sums: the division by the bulk C_sca and, for autodiff=True, the quotient
+rule of the partial rows.  Float64 only; NAI2 only (no PCW).  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import _lib
+from . import corert as rt
+
+
+# ------------------------------------------------------------------------------------------
+# types (src/Scattering/types.jl)
+# ------------------------------------------------------------------------------------------
+
+
+@dataclass
+class LogNormal:
+    """Distributions.LogNormal(μ, σ): ln r ~ Normal(μ, σ).  The reference builds it as LogNormal(log(r_m), log(σ_g))."""
+    μ: float
+    σ: float
+
+    def pdf(self, r: np.ndarray) -> np.ndarray:
+        r = np.asarray(r, dtype=np.float64)
+        z = (np.log(r) - self.μ) / self.σ
+        return np.exp(-0.5 * z * z) / (r * self.σ * math.sqrt(2.0 * math.pi))
+
+    def dpdf(self, r: np.ndarray) -> np.ndarray:
+        """∂pdf/∂(r_m, σ_g) [2, len(r)] for r_m = exp(μ), σ_g = exp(σ)."""
+        r = np.asarray(r, dtype=np.float64)
+        d = np.log(r) - self.μ
+        p = self.pdf(r)
+        dμ = p * d / self.σ ** 2
+        dσ = p * (d * d / self.σ ** 3 - 1.0 / self.σ)
+        return np.stack([dμ / math.exp(self.μ), dσ / math.exp(self.σ)])
+
+
+@dataclass
+class Aerosol:
+    size_distribution: LogNormal
+    nᵣ: float
+    nᵢ: float
+
+
+@dataclass
+class NAI2:
+    """Siewert's numerical angular integration (the only computation type built here)."""
+
+
+@dataclass
+class δBGE:
+    l_max: int
+    Δ_angle: float = 0.0
+
+
+@dataclass
+class MieModel:
+    computation_type: NAI2
+    aerosol: Aerosol
+    λ: float
+    polarization_type: object
+    truncation_type: Optional[δBGE]
+    r_max: float
+    nquad_radius: int
+
+
+def make_mie_model(computation_type, aerosol: Aerosol, λ: float, polarization_type, truncation_type, r_max: float,
+                   nquad_radius: int) -> MieModel:
+    if not isinstance(computation_type, NAI2):
+        raise NotImplementedError("only NAI2() is built (PCW needs Wigner 3j symbols)")
+    if aerosol.nᵢ < 0:
+        raise ValueError("the imaginary part of the refractive index must be >= 0")
+    return MieModel(computation_type, aerosol, float(λ), polarization_type, truncation_type, float(r_max), int(nquad_radius))
+
+
+# ------------------------------------------------------------------------------------------
+# quadratures and tables
+# ------------------------------------------------------------------------------------------
+
+
+def gausslegendre(n: int):
+    """Gauss-Legendre nodes (ascending) and weights on [-1, 1]: Newton's method on P_n, all nodes at once."""
+    if n == 1:
+        return np.zeros(1), np.full(1, 2.0)
+
+    def p_and_dp(x):
+        p0, p1 = np.ones_like(x), x.copy()
+        for l in range(2, n + 1):
+            p0, p1 = p1, ((2 * l - 1) * x * p1 - (l - 1) * p0) / l
+        return p1, n * (x * p1 - p0) / (x * x - 1.0)
+
+    x = np.cos(math.pi * (np.arange(n, 0, -1, dtype=np.float64) - 0.25) / (n + 0.5))
+    for _ in range(20):
+        p, dp = p_and_dp(x)
+        x = x - p / dp
+        if np.max(np.abs(p / dp)) < 4e-16:
+            break
+    x = 0.5 * (x - x[::-1])   # the nodes are symmetric: make them so to the last bit
+    _, dp = p_and_dp(x)
+    return x, 2.0 / ((1.0 - x * x) * dp * dp)
+
+
+def gauleg(n: int, xmin: float, xmax: float, norm: bool = False):
+    """mie_helper_functions.jl:177-182"""
+    ξ, w = gausslegendre(n)
+    ξ = (xmax - xmin) / 2 * ξ + (xmin + xmax) / 2
+    w = w / w.sum() if norm else w * (xmax - xmin) / 2
+    return ξ, w
+
+
+def get_n_max(x):
+    """mie_helper_functions.jl:17 (round: ties to even, as Julia's)"""
+    x = np.asarray(x, dtype=np.float64)
+    return np.rint(x + 4.05 * x ** (1 / 3) + 10).astype(np.int64)
+
+
+def compute_mie_π_τ(μ: np.ndarray, nmax: int):
+    """legendre_functions.jl:188-208 -> π, τ [n_μ, nmax] (column l - 1 = order l)"""
+    μ = np.asarray(μ, dtype=np.float64)
+    π_, τ_ = np.zeros((μ.size, nmax)), np.zeros((μ.size, nmax))
+    π_[:, 0], τ_[:, 0] = 1.0, μ
+    if nmax > 1:
+        π_[:, 1], τ_[:, 1] = 3 * μ, 6 * μ ** 2 - 3
+    for n in range(2, nmax):
+        π_[:, n] = ((2 * n + 1) * μ * π_[:, n - 1] - (n + 1) * π_[:, n - 2]) / n
+        τ_[:, n] = (n + 1) * μ * π_[:, n] - (n + 2) * π_[:, n - 1]
+    return π_, τ_
+
+
+def compute_legendre_poly(x: np.ndarray, nmax: int):
+    """legendre_functions.jl:217-259 -> P, P², R², T² [len(x), nmax] (column l = degree l)"""
+    x = np.asarray(x, dtype=np.float64)
+    P, P2, R2, T2 = (np.zeros((x.size, nmax)) for _ in range(4))
+    P[:, 0] = 1.0
+    if nmax > 1:
+        P[:, 1] = x
+    if nmax > 2:
+        P2[:, 2] = 3 * (1 - x ** 2)
+        R2[:, 2] = math.sqrt(1.5) * (1 + x ** 2)
+        T2[:, 2] = math.sqrt(6) * x
+    for c in range(2, nmax):
+        l = c - 1
+        P[:, c] = ((2 * l + 1) * x * P[:, c - 1] - l * P[:, c - 2]) / (l + 1)
+        if l >= 2:
+            ia = (2 * l + 1) * x
+            ib = math.sqrt((l + 2) * (l - 2)) * (l + 2) / l
+            ic = 4.0 * (2 * l + 1) / ((l + 1) * l)
+            id_ = math.sqrt((l + 3) * (l - 1)) * (l - 1) / (l + 1)
+            P2[:, c] = (ia * P2[:, c - 1] - (l + 2) * P2[:, c - 2]) / (l - 1)
+            R2[:, c] = (ia * R2[:, c - 1] - ib * R2[:, c - 2] - ic * T2[:, c - 1]) / id_
+            T2[:, c] = (ia * T2[:, c - 1] - ib * T2[:, c - 2] - ic * R2[:, c - 1]) / id_
+    return P, P2, R2, T2
+
+
+# ------------------------------------------------------------------------------------------
+# compute_aerosol_optical_properties (compute_NAI2.jl:16-182)
+# ------------------------------------------------------------------------------------------
+
+
+@dataclass
+class MieInputs:
+    """What mom_mie_nai2 reads for a model: everything the host prepares."""
+    r: np.ndarray
+    w: np.ndarray         # [nW, nR]: row 0 = 4π r² wₓ, rows 1, 2 = 4π r² ∂wₓ/∂(r_m, σ_g)
+    μ: np.ndarray
+    w_μ: np.ndarray
+    π_: np.ndarray
+    τ_: np.ndarray
+    P: np.ndarray
+    P2: np.ndarray
+    R2: np.ndarray
+    T2: np.ndarray
+
+
+def mie_inputs(model: MieModel, autodiff: bool = False) -> MieInputs:
+    aer = model.aerosol
+    r, wᵣ = gauleg(model.nquad_radius, 0.0, model.r_max, norm=True)
+    n_max = int(get_n_max(np.max(2 * math.pi / model.λ * r)))
+    μ, w_μ = gausslegendre(2 * n_max - 1)
+    π_, τ_ = compute_mie_π_τ(μ, n_max)
+    P, P2, R2, T2 = compute_legendre_poly(μ, μ.size)
+    # compute_wₓ (mie_helper_functions.jl:266-276): wₓ = pdf wᵣ / Σ pdf wᵣ
+    p = aer.size_distribution.pdf(r) * wᵣ
+    rows = [p / p.sum()]
+    if autodiff:
+        for dp in aer.size_distribution.dpdf(r) * wᵣ:
+            rows.append(dp / p.sum() - p * dp.sum() / p.sum() ** 2)
+    w = 4 * math.pi * r ** 2 * np.stack(rows)
+    return MieInputs(r, w, μ, w_μ, π_, τ_, P, P2, R2, T2)
+
+
+def _device_call(model: MieModel, autodiff: bool, flags: int = 0):
+    inp = mie_inputs(model, autodiff)
+    return inp, _lib.mie_nai2(inp.r, inp.w, model.λ, model.aerosol.nᵣ, model.aerosol.nᵢ, inp.w_μ, inp.π_, inp.τ_, inp.P, inp.P2,
+                              inp.R2, inp.T2, flags=flags)
+
+
+def _greek(g: np.ndarray) -> rt.GreekCoefs:
+    return rt.GreekCoefs(α=g[0].copy(), β=g[1].copy(), γ=g[2].copy(), δ=g[3].copy(), ϵ=g[4].copy(), ζ=g[5].copy())
+
+
+def optics_from_sums(C: np.ndarray, greek: np.ndarray):
+    """The host arithmetic after the device sums: (AerosolOptics, [∂/∂θ of it for every further weight row]).  C [nW, 2] =
+    bulk (C_sca, C_ext), greek [nW, 6, l_max] unnormalised."""
+    Cs, Ce = C[0]
+    aero = rt.AerosolOptics(greek_coefs=_greek(greek[0] / Cs), ω̃=float(Cs / Ce), fᵗ=1.0, k=float(Ce))
+    partials = []
+    for k in range(1, C.shape[0]):
+        dCs, dCe = C[k]
+        dg = greek[k] / Cs - greek[0] * dCs / Cs ** 2
+        partials.append(rt.AerosolOptics(greek_coefs=_greek(dg), ω̃=float(dCs / Ce - Cs * dCe / Ce ** 2), fᵗ=0.0, k=float(dCe)))
+    return aero, partials
+
+
+def compute_aerosol_optical_properties(model: MieModel, autodiff: bool = False):
+    """AerosolOptics(greek_coefs, ω̃, k, fᵗ = 1) of the model; with autodiff=True also the partials of every field with respect to
+    (r_m, σ_g) of the log-normal size distribution, as two AerosolOptics holding the derivatives: (optics, [∂/∂r_m, ∂/∂σ_g])."""
+    _, (_, C, greek, _) = _device_call(model, autodiff)
+    aero, partials = optics_from_sums(C, greek)
+    return (aero, partials) if autodiff else aero
+
+
+def compute_ref_aerosol_extinction(model: MieModel) -> float:
+    """compute_NAI2.jl:184-260: the bulk extinction cross section."""
+    _, (_, C, _, _) = _device_call(model, False)
+    return float(C[0, 1])
+
+
+# ------------------------------------------------------------------------------------------
+# δ-BGE truncation (truncate_phase.jl:95-220)
+# ------------------------------------------------------------------------------------------
+
+
+def reconstruct_phase(greek: rt.GreekCoefs, μ: np.ndarray):
+    """mie_helper_functions.jl:198-229 -> (f₁₁, f₁₂, f₂₂, f₃₃, f₃₄, f₄₄), P, P²"""
+    l_max = len(greek.α)
+    P, P2, R2, T2 = compute_legendre_poly(μ, l_max)
+    fac = np.zeros(l_max)
+    for l in range(2, l_max):
+        fac[l] = math.sqrt(1 / ((l - 1) * l * (l + 1) * (l + 2)))
+    f11, f44 = P @ greek.β, P @ greek.δ
+    f12, f34 = P2 @ (fac * greek.γ), P2 @ (fac * greek.ϵ)
+    f22 = R2 @ (fac * greek.α) + T2 @ (fac * greek.ζ)
+    f33 = R2 @ (fac * greek.ζ) + T2 @ (fac * greek.α)
+    return (f11, f12, f22, f33, f34, f44), P, P2
+
+
+def _weighted_fit(w_μ, B, f, first):
+    """the normal equations of truncate_phase.jl:129-141 / 154-167: A_ij = Σ w B_i B_j / f², b_i = Σ w B_i / f, rows from `first`"""
+    Bf = B[:, first:] / f[:, None]
+    return np.linalg.solve((w_μ[:, None] * Bf).T @ Bf, Bf.T @ w_μ)
+
+
+def truncate_phase(mod: δBGE, aero: rt.AerosolOptics) -> rt.AerosolOptics:
+    """truncate_phase(mod::δBGE, aero) as the reference writes it: three weighted least-squares fits over ALL Gauss nodes
+    (Δ_angle is read, the index set it selects is never used), β, δ, α, ζ rescaled by c₀ = cl[1], γᵗ and ϵᵗ the fits themselves,
+    ω̃ and k unchanged, fᵗ = 1 - c₀."""
+    g = aero.greek_coefs
+    l_tr = int(mod.l_max)
+    μ, w_μ = gausslegendre(len(g.β))
+    (f11, f12, _, _, f34, _), P, P2 = reconstruct_phase(g, μ)
+    _ = μ < rt.cosd(mod.Δ_angle)   # iμ of the reference: computed, not used
+    fac = np.zeros(l_tr)
+    for l in range(2, l_tr):
+        fac[l] = math.sqrt(1.0 / ((l - 1.0) * l * (l + 1.0) * (l + 2.0)))
+    cl = _weighted_fit(w_μ, P[:, :l_tr], f11, 0)
+    γᵗ, ϵᵗ = np.zeros(l_tr), np.zeros(l_tr)
+    if l_tr > 2:
+        γᵗ[2:] = _weighted_fit(w_μ, fac * P2[:, :l_tr], f12, 2)
+        ϵᵗ[2:] = _weighted_fit(w_μ, fac * P2[:, :l_tr], f34, 2)
+    c0 = cl[0]
+    βᵗ = cl / c0
+    δᵗ = (g.δ[:l_tr] - (g.β[:l_tr] - cl)) / c0
+    αᵗ = (g.α[:l_tr] - (g.β[:l_tr] - cl)) / c0
+    ζᵗ = (g.ζ[:l_tr] - (g.β[:l_tr] - cl)) / c0
+    return rt.AerosolOptics(greek_coefs=rt.GreekCoefs(α=αᵗ, β=βᵗ, γ=γᵗ, δ=δᵗ, ϵ=ϵᵗ, ζ=ζᵗ), ω̃=aero.ω̃, fᵗ=float(1.0 - c0), k=aero.k)

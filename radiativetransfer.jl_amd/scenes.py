@@ -84,6 +84,21 @@ def make_scene(nStokes: int, l_trunc: int, Nz: int, S: int, ν_lo: float = 12903
     return rt.model_from_parameters(params, τ_rayl, τ_abs, τ_aer, aer)
 
 
+def make_mie_scene(nStokes: int, l_trunc: int, Nz: int, S: int, r_m: float = 0.3, σ_g: float = 1.6, nᵣ: float = 1.3, nᵢ: float = 0.001,
+                   λ: float = 0.76, r_max: float = 1.0, nquad_radius: int = 37, truncation=None, **kw) -> rt.vSmartMOM_Model:
+    """make_scene with a Mie aerosol in place of hg_like_greek: a log-normal size distribution (median radius r_m, geometric
+    width σ_g, in the unit of λ) of spheres with refractive index nᵣ + i nᵢ through compute_aerosol_optical_properties (device)
+    and truncate_phase(truncation), by default δBGE(l_trunc, 2.0)."""
+    from . import scattering as sc
+    m = make_scene(nStokes, l_trunc, Nz, S, **kw)
+    if not m.aerosol_optics:
+        raise ValueError("make_mie_scene needs aerosol_total > 0")
+    aerosol = sc.Aerosol(sc.LogNormal(math.log(r_m), math.log(σ_g)), nᵣ, nᵢ)
+    mie = sc.make_mie_model(sc.NAI2(), aerosol, λ, m.params.polarization_type, truncation or sc.δBGE(l_trunc, 2.0), r_max, nquad_radius)
+    m.aerosol_optics = [sc.truncate_phase(mie.truncation_type, sc.compute_aerosol_optical_properties(mie))]
+    return m
+
+
 def scene_C1(S: int = 100, **kw):
     """scalar I, Nquad_eff = 4 (2 Gauss nodes + μ=1 + μ₀), 10 layers."""
     return make_scene(1, 3, 10, S, vza=(0.0,), vaz=(0.0,), **kw)
