@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """The Mie / NAI-2 aerosol optics (csrc/mom_mie.hip) as a benchmark; prints one JSON line, `bench_mie.py OUT.json` also writes it
-(committed as profiles/mie_bench.json).
+(committed as profiles/mie_bench.json).  `bench_mie.py --dual OUT.json`: the Dual run with respect to all four aerosol
+parameters beside the value call in the same process (committed as profiles/mie_dual_bench.json).
 
 Two points: the reference's own test point (test/test_Scattering.jl: λ = 0.55 µm, r_max = 30 µm, nquad_radius = 2500,
 m = 1.3 + 0.001i, LogNormal(log 0.3, log 6.82): x_max = 342.7, n_max = 381, n_μ = 761) and a small one (r_max = 1 µm, 37 radii:
@@ -74,6 +75,43 @@ def run_point(p, repeats=5, autodiff=False):
     return out
 
 
+def run_dual_point(p, repeats=7):
+    """The Dual run (mom_mie_nai2_dual, wrt = all four parameters: three weight rows and the two index rows) beside the value call
+    (mom_mie_nai2, one weight row) in the same process: the median over `repeats` calls of each call's HIP-event kernel times.
+    The Dual call stands for the value call plus four more (central differences in n_r and n_i), so the criterion is
+    ratio = Dual / value < 5.  Flop model of the Dual amplitude GEMM: 32 flop per (μ, radius, l) -- S and S'."""
+    import rtamd
+    sc = rtamd.scattering
+    aer = sc.Aerosol(sc.LogNormal(math.log(p["r_m"]), math.log(p["sigma_g"])), p["n_r"], p["n_i"])
+    model = sc.make_mie_model(sc.NAI2(), aer, p["lam"], None, None, p["r_max"], p["nquad_radius"])
+    legs = {}
+    for name, autodiff, fn in (("value", False, rtamd._lib.mie_nai2), ("dual", True, rtamd._lib.mie_nai2_dual)):
+        inp = sc.mie_inputs(model, autodiff)
+        args = (inp.r, inp.w, p["lam"], p["n_r"], p["n_i"], inp.w_μ, inp.π_, inp.τ_, inp.P, inp.P2, inp.R2, inp.T2)
+        fn(*args)                     # the first call loads the code objects
+        ms = np.array([fn(*args)[3] for _ in range(repeats)])
+        med = np.median(ms, axis=0)
+        legs[name] = {"weight_rows": int(inp.w.shape[0]), "repeats": repeats,
+                      "kernels_ms_median": {"coefficients": float(med[0]), "amplitude_gemm_and_reduction": float(med[1]),
+                                            "projection": float(med[2]), "sum": float(np.median(ms.sum(axis=1)))},
+                      "kernels_ms_min_sum": float(ms.sum(axis=1).min())}
+    t0 = time.perf_counter()
+    sc.compute_aerosol_optical_properties(model, autodiff=True, wrt=sc.ALL_AEROSOL_PARAMETERS)
+    whole_ms = (time.perf_counter() - t0) * 1e3
+    x = 2 * math.pi / p["lam"] * inp.r
+    nmax = sc.get_n_max(x)
+    n_mu, nR = inp.w_μ.size, inp.r.size
+    tiles = [int(-(-nmax[min(i0 + 15, nR - 1)] // 4) * 4) for i0 in range(0, nR, 16)]
+    flop_run = 32.0 * (-(-n_mu // 32) * 32) * 16 * float(sum(tiles))
+    tf = flop_run / (legs["dual"]["kernels_ms_median"]["amplitude_gemm_and_reduction"] * 1e-3) / 1e12
+    ratio = legs["dual"]["kernels_ms_median"]["sum"] / legs["value"]["kernels_ms_median"]["sum"]
+    return {"n_radii": int(nR), "n_mu": int(n_mu), "n_max": int(nmax.max()), "wrt": list(sc.ALL_AEROSOL_PARAMETERS), **legs,
+            "ratio_dual_to_value": ratio, "criterion": "ratio_dual_to_value < 5 (a value call plus four for central differences)",
+            "criterion_met": bool(ratio < 5.0), "compute_aerosol_optical_properties_wall_ms": whole_ms,
+            "amplitude_gemm": {"flop_run": flop_run, "roofline": {"bound": "mfma", "achieved": tf, "peak": PEAK_FP64_MFMA_TFLOPS,
+                                                                  "unit": "TFLOP/s", "frac": tf / PEAK_FP64_MFMA_TFLOPS}}}
+
+
 def run():
     out = {"metric": "Mie NAI-2 aerosol optics, kernels of one call", "unit": "ms"}
     for name, p in POINTS.items():
@@ -83,9 +121,17 @@ def run():
     return out
 
 
+def run_dual():
+    out = {"metric": "Mie NAI-2 aerosol optics, Dual run with respect to (r_m, σ_g, nᵣ, nᵢ): kernels of one call", "unit": "ms"}
+    out["reference_test_point"] = run_dual_point(POINTS["reference_test_point"])
+    out["value"] = out["reference_test_point"]["dual"]["kernels_ms_median"]["sum"]
+    return out
+
+
 if __name__ == "__main__":
-    res = run()
-    if len(sys.argv) > 1:
-        Path(sys.argv[1]).parent.mkdir(parents=True, exist_ok=True)
-        Path(sys.argv[1]).write_text(json.dumps(res, indent=1, ensure_ascii=False) + "\n")
+    argv = [a for a in sys.argv[1:] if a != "--dual"]
+    res = run_dual() if "--dual" in sys.argv[1:] else run()
+    if argv:
+        Path(argv[0]).parent.mkdir(parents=True, exist_ok=True)
+        Path(argv[0]).write_text(json.dumps(res, indent=1, ensure_ascii=False) + "\n")
     print(json.dumps(res, ensure_ascii=False))

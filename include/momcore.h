@@ -733,6 +733,25 @@ int mom_mie_nai2(int device, int nR, const double *r, int nW, const double *w, d
 int mom_mie_coefficients(int device, int nX, const double *x, double n_r, double n_i, int n_max, double *a_re, double *a_im,
                          double *b_re, double *b_im);
 
+/* The Dual run of mom_mie_nai2 with respect to the refractive index (phase_function_autodiff.jl:41-95, the columns n_r and n_i of
+ * x = (r_m, sigma_g, n_r, n_i)): same arguments, 1 <= nW <= 3, and nW + 2 output rows,
+ *   bulk_f [nW + 2, 4, n_mu], C [nW + 2, 2], greek [nW + 2, 6, l_max].
+ * Rows 0 .. nW - 1 are bitwise what mom_mie_nai2 writes for the same arguments; row nW is d/dn_r and row nW + 1 is d/dn_i of row
+ * 0's sums.  a_n and b_n are holomorphic in m = n_r + i n_i, so the coefficient kernel carries ONE complex derivative d/dm
+ * (d/dn_r = d/dm, d/dn_i = i d/dm) through both recurrences; n_max,i and the start of the downward recurrence are integers and
+ * are taken on the values, as ForwardDiff's round(Int, .) does.  gpu_ms and flags as for mom_mie_nai2; two calls are bitwise equal.
+ * MOM_EINVAL: the list of mom_mie_nai2 with nW outside 1..3. */
+enum { MOM_MIE_DUAL_MAX_WEIGHT_ROWS = 3, MOM_MIE_INDEX_ROWS = 2 };
+int mom_mie_nai2_dual(int device, int nR, const double *r, int nW, const double *w, double lambda, double n_r, double n_i,
+                      int n_mu, const double *w_mu, int n_max, const double *pi_tab, const double *tau_tab, int l_max,
+                      const double *P, const double *P2, const double *R2, const double *T2, int flags, double *bulk_f,
+                      double *C, double *greek, double *gpu_ms);
+
+/* Test access: mom_mie_coefficients and da_n / dm, db_n / dm as four more real arrays [n_max, nX] (d/dn_r = d/dm, d/dn_i = i d/dm);
+ * a and b are bitwise those of mom_mie_coefficients.  MOM_EINVAL as there; no pointer may be null. */
+int mom_mie_coefficients_dual(int device, int nX, const double *x, double n_r, double n_i, int n_max, double *a_re, double *a_im,
+                              double *b_re, double *b_im, double *da_re, double *da_im, double *db_re, double *db_im);
+
 #ifdef __cplusplus
 }
 #endif

@@ -496,4 +496,28 @@ function mie_nai2(arch::MI355X, r, w_rows, λ, nᵣ, nᵢ, w_μ, leg_π, leg_τ,
     end
     return value, partials, ms
 end
+
+"""
+compute_aerosol_optical_properties(model; autodiff = true) (src/Scattering/phase_function_autodiff.jl:41-95) with the columns nᵣ and nᵢ
+of x = (r_m, σ_g, nᵣ, nᵢ): the same call with the Dual run of the Mie coefficients.  `w_rows` has at most 3 columns (wₓ, ∂wₓ/∂r_m,
+∂wₓ/∂σ_g); the device appends two rows, ∂/∂nᵣ and ∂/∂nᵢ of column 1's sums, so `partials` holds nW - 1 + 2 named tuples in the
+reference's order of x.
+"""
+function mie_nai2_dual(arch::MI355X, r, w_rows, λ, nᵣ, nᵢ, w_μ, leg_π, leg_τ, P, P², R², T²)
+    nR, nW = size(w_rows, 1), size(w_rows, 2);  n_μ, n_max = size(leg_π);  l_max = size(P, 2);  nO = nW + Int(MomCore.MOM_MIE_INDEX_ROWS)
+    w = collect(Float64, (4π .* r .^ 2) .* w_rows)
+    bulk_f = zeros(Float64, n_μ, 4, nO);  C = zeros(Float64, 2, nO);  greek = zeros(Float64, l_max, 6, nO);  ms = zeros(Float64, 3)
+    momcheck(MomCore.mom_mie_nai2_dual(arch.device, nR, collect(Float64, r), nW, w, Float64(λ), Float64(nᵣ), Float64(nᵢ), n_μ,
+                                       collect(Float64, w_μ), n_max, collect(Float64, leg_π), collect(Float64, leg_τ), l_max,
+                                       collect(Float64, P), collect(Float64, P²), collect(Float64, R²), collect(Float64, T²), 0, bulk_f, C,
+                                       greek, ms))
+    C_sca, C_ext = C[1, 1], C[2, 1]
+    value = (α = greek[:, 1, 1] ./ C_sca, β = greek[:, 2, 1] ./ C_sca, γ = greek[:, 3, 1] ./ C_sca, δ = greek[:, 4, 1] ./ C_sca,
+             ϵ = greek[:, 5, 1] ./ C_sca, ζ = greek[:, 6, 1] ./ C_sca, ω̃ = C_sca / C_ext, k = C_ext, fᵗ = 1.0)
+    partials = map(2:nO) do j
+        d(q) = greek[:, q, j] ./ C_sca .- greek[:, q, 1] .* (C[1, j] / C_sca^2)
+        (α = d(1), β = d(2), γ = d(3), δ = d(4), ϵ = d(5), ζ = d(6), ω̃ = C[1, j] / C_ext - C_sca * C[2, j] / C_ext^2, k = C[2, j], fᵗ = 0.0)
+    end
+    return value, partials, ms
+end
 # <<< mie

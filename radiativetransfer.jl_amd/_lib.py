@@ -47,6 +47,7 @@ MOM_OPT_LUT_BATCH = 15           # (p, T) nodes per batch of mom_lut_build (0, d
 BROADENING_VOIGT, BROADENING_DOPPLER, BROADENING_LORENTZ = 0, 1, 2
 CEF_HW32SD, CEF_HW32VOIGT = 0, 1
 MOM_MIE_FULL_K = 1   # mom_mie_nai2 flag: every radius tile sums l to the global n_max (test access; bitwise the same result)
+MOM_MIE_DUAL_MAX_WEIGHT_ROWS, MOM_MIE_INDEX_ROWS = 3, 2   # mom_mie_nai2_dual: at most 3 weight rows; 2 more output rows (n_r, n_i)
 
 
 class MomError(RuntimeError):
@@ -155,6 +156,9 @@ SIGNATURES = {
     "mom_mie_nai2": (C.c_int, [C.c_int, C.c_int, c_dp, C.c_int, c_dp, C.c_double, C.c_double, C.c_double, C.c_int, c_dp, C.c_int, c_dp,
                                c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp]),
     "mom_mie_coefficients": (C.c_int, [C.c_int, C.c_int, c_dp, C.c_double, C.c_double, C.c_int, c_dp, c_dp, c_dp, c_dp]),
+    "mom_mie_nai2_dual": (C.c_int, [C.c_int, C.c_int, c_dp, C.c_int, c_dp, C.c_double, C.c_double, C.c_double, C.c_int, c_dp, C.c_int,
+                                    c_dp, c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp]),
+    "mom_mie_coefficients_dual": (C.c_int, [C.c_int, C.c_int, c_dp, C.c_double, C.c_double, C.c_int] + [c_dp] * 8),
 }
 
 _lib = None
@@ -820,24 +824,37 @@ def voigt_last_kernel_ms() -> float:
     return float(load().mom_voigt_last_kernel_ms())
 
 
-def mie_nai2(r, w, lam, n_r, n_i, w_mu, pi_tab, tau_tab, P, P2, R2, T2, flags: int = 0, device: int = 0):
-    """mom_mie_nai2: r [nR] ascending, w [nW, nR] weight rows, pi_tab / tau_tab [n_mu, n_max] and P, P2, R2, T2 [n_mu, l_max] as
-    numpy builds them (the ABI's mu-fastest layout is their transpose).  Returns (bulk_f [nW, 4, n_mu], C [nW, 2],
-    greek [nW, 6, l_max], gpu_ms [3]), all unnormalised."""
+def _mie_nai2(dual: bool, r, w, lam, n_r, n_i, w_mu, pi_tab, tau_tab, P, P2, R2, T2, flags, device):
     lib = load()
+    name = "mie_nai2_dual" if dual else "mie_nai2"
     r, w, w_mu = f64(r), f64(np.atleast_2d(w)), f64(w_mu)
     tabs = [f64(np.asarray(t, dtype=np.float64).T) for t in (pi_tab, tau_tab, P, P2, R2, T2)]
     nW, nR, n_mu = w.shape[0], len(r), len(w_mu)
     if w.shape[1] != nR or any(t.shape[1] != n_mu for t in tabs) or tabs[0].shape != tabs[1].shape or \
             any(t.shape != tabs[2].shape for t in tabs[3:]):
-        raise ValueError("mie_nai2: array shapes do not agree")
+        raise ValueError(f"{name}: array shapes do not agree")
     n_max, l_max = tabs[0].shape[0], tabs[2].shape[0]
-    bulk, Cx, greek, ms = np.empty((nW, 4, n_mu)), np.empty((nW, 2)), np.empty((nW, 6, l_max)), np.zeros(3)
-    rc = lib.mom_mie_nai2(device, nR, dp(r), nW, dp(w), float(lam), float(n_r), float(n_i), n_mu, dp(w_mu), n_max, dp(tabs[0]),
-                          dp(tabs[1]), l_max, *[dp(t) for t in tabs[2:]], int(flags), dp(bulk), dp(Cx), dp(greek), dp(ms))
+    nO = nW + MOM_MIE_INDEX_ROWS if dual else nW
+    bulk, Cx, greek, ms = np.empty((nO, 4, n_mu)), np.empty((nO, 2)), np.empty((nO, 6, l_max)), np.zeros(3)
+    fn = lib.mom_mie_nai2_dual if dual else lib.mom_mie_nai2
+    rc = fn(device, nR, dp(r), nW, dp(w), float(lam), float(n_r), float(n_i), n_mu, dp(w_mu), n_max, dp(tabs[0]), dp(tabs[1]), l_max,
+            *[dp(t) for t in tabs[2:]], int(flags), dp(bulk), dp(Cx), dp(greek), dp(ms))
     if rc != MOM_OK:
         raise MomError(rc, lib.mom_last_global_error().decode())
     return bulk, Cx, greek, ms
+
+
+def mie_nai2(r, w, lam, n_r, n_i, w_mu, pi_tab, tau_tab, P, P2, R2, T2, flags: int = 0, device: int = 0):
+    """mom_mie_nai2: r [nR] ascending, w [nW, nR] weight rows, pi_tab / tau_tab [n_mu, n_max] and P, P2, R2, T2 [n_mu, l_max] as
+    numpy builds them (the ABI's mu-fastest layout is their transpose).  Returns (bulk_f [nW, 4, n_mu], C [nW, 2],
+    greek [nW, 6, l_max], gpu_ms [3]), all unnormalised."""
+    return _mie_nai2(False, r, w, lam, n_r, n_i, w_mu, pi_tab, tau_tab, P, P2, R2, T2, flags, device)
+
+
+def mie_nai2_dual(r, w, lam, n_r, n_i, w_mu, pi_tab, tau_tab, P, P2, R2, T2, flags: int = 0, device: int = 0):
+    """mom_mie_nai2_dual: the arguments of mie_nai2 (nW <= 3); every output has nW + 2 rows, the last two the partials of row 0's
+    sums with respect to n_r and n_i."""
+    return _mie_nai2(True, r, w, lam, n_r, n_i, w_mu, pi_tab, tau_tab, P, P2, R2, T2, flags, device)
 
 
 def mie_coefficients(x, n_r, n_i, n_max: int, device: int = 0):
@@ -849,3 +866,14 @@ def mie_coefficients(x, n_r, n_i, n_max: int, device: int = 0):
     if rc != MOM_OK:
         raise MomError(rc, lib.mom_last_global_error().decode())
     return out[0] + 1j * out[1], out[2] + 1j * out[3]
+
+
+def mie_coefficients_dual(x, n_r, n_i, n_max: int, device: int = 0):
+    """mom_mie_coefficients_dual: (a, b, da/dm, db/dm) complex [n_max, nX]; d/dn_r = d/dm, d/dn_i = i d/dm."""
+    lib = load()
+    x = f64(np.atleast_1d(x))
+    out = [np.empty((int(n_max), len(x))) for _ in range(8)]
+    rc = lib.mom_mie_coefficients_dual(device, len(x), dp(x), float(n_r), float(n_i), int(n_max), *[dp(o) for o in out])
+    if rc != MOM_OK:
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return out[0] + 1j * out[1], out[2] + 1j * out[3], out[4] + 1j * out[5], out[6] + 1j * out[7]

@@ -13,6 +13,12 @@
 //   (d) k_mie_greek  the projections of the bulk elements onto P, P2, R2, T2 (compute_NAI2.jl:146-160), one wavefront per l
 // The radii arrive ascending, so n_max is monotone over them and a radius tile's K loop ends at the tile's largest n_max
 // (rounded up to the k-step of 4): what is left out are products with the exact zeros of (a).
+//
+// The Dual run (mom_mie_nai2_dual) adds the partials with respect to the refractive index m = n_r + i n_i.  a_n and b_n are
+// holomorphic in m, so ONE complex derivative a' = da/dm carries both: d/dn_r = a', d/dn_i = i a'.  k_mie_ab<., true> carries
+// D' = dD/dm through the downward recurrence and writes c a', c b' as four more planes; k_mie_amp<NW, true> forms S1', S2' with
+// the same A operands and accumulates two more bulk rows, weight row 0 times df/dn_r and df/dn_i; (c) and (d) are linear and
+// run unchanged on NW + 2 rows.  n_max and the start of the downward recurrence are integers and are not differentiated.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -36,17 +42,27 @@ constexpr int kMaxChunks = 128;  // radius chunks of (b): beyond 2048 radii a wa
 // Complex arithmetic is written out on the real and imaginary parts, a quotient u / v as u conj(v) / |v|^2, and the compiler
 // may not contract a product and a sum into an FMA here: the upward psi recurrence is only conditionally stable, so the
 // order and the rounding of every operation are part of the result (tests/mie_oracle.py performs the same operations).
-template <bool SCALE>
+// DUAL: also D' = dD/dm (two more [n_max, ld] planes), c a', c b' (four more planes) and the d/dn_r, d/dn_i forms of the two
+// cross-section sums (dsum [4, ld]: sca, ext for n_r, then for n_i).  The value statements are the same in both forms.
+struct MieDualOut {
+  double *Dre, *Dim, *aR, *aI, *bR, *bI, *sum;
+};
+
+template <bool SCALE, bool DUAL>
 __global__ void __launch_bounds__(64) k_mie_ab(int nR, int ld, const double *__restrict__ x, const int *__restrict__ nmax,
                                                const int *__restrict__ nmx, double mr, double mi, double *__restrict__ Dre,
                                                double *__restrict__ Dim, double *__restrict__ aR, double *__restrict__ aI,
                                                double *__restrict__ bR, double *__restrict__ bI, double *__restrict__ ssca,
-                                               double *__restrict__ sext) {
+                                               double *__restrict__ sext, MieDualOut dd) {
 #pragma clang fp contract(off)
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= nR) return;
   const double xi = x[i];
   const int nm = nmax[i], ntop = nmx[i];
+  // 1 / m and 1 / m^2 (Dual run)
+  const double mm = mr * mr + mi * mi, imr = mr / mm, imi = -mi / mm;
+  [[maybe_unused]] const double i2r = imr * imr - imi * imi, i2i = 2.0 * (imr * imi);
+  [[maybe_unused]] double ddr = 0.0, ddi = 0.0;  // D'_ntop = 0
   // y = x m; (n + 1) / y = (n + 1) * (conj(y) / |y|^2)
   const double yr = xi * mr, yi = xi * mi, y2 = yr * yr + yi * yi;
   const double iyr = yr / y2, iyi = -yi / y2;
@@ -60,10 +76,23 @@ __global__ void __launch_bounds__(64) k_mie_ab(int nR, int ld, const double *__r
       Dre[(size_t)(n - 1) * ld + i] = dr;
       Dim[(size_t)(n - 1) * ld + i] = di;
     }
+    if constexpr (DUAL) {
+      // q = (n+1)/y, q' = -q / m;  D'_n = q' + (D'_{n+1} + q') / (D_{n+1} + q)^2
+      const double pr = -(qr * imr - qi * imi), pi_ = -(qr * imi + qi * imr);
+      const double ur = sr / s2, ui = -si / s2, vr = ur * ur - ui * ui, vi = 2.0 * (ur * ui);
+      const double gr = ddr + pr, gi = ddi + pi_;
+      ddr = pr + (gr * vr - gi * vi);
+      ddi = pi_ + (gr * vi + gi * vr);
+      if (n <= nm) {
+        dd.Dre[(size_t)(n - 1) * ld + i] = ddr;
+        dd.Dim[(size_t)(n - 1) * ld + i] = ddi;
+      }
+    }
   }
   const double m2 = mr * mr + mi * mi;
   double psi0 = cos(xi), psi1 = sin(xi), chi0 = -psi1, chi1 = psi0;
   double sca = 0.0, ext = 0.0;
+  [[maybe_unused]] double dsca_r = 0.0, dext_r = 0.0, dsca_i = 0.0, dext_i = 0.0;
   for (int n = 1; n <= nm; ++n) {
     const double tn = (double)(2 * n - 1);
     const double psi = tn * psi1 / xi - psi0, chi = tn * chi1 / xi - chi0;  // xi_n = psi - i chi
@@ -88,6 +117,29 @@ __global__ void __launch_bounds__(64) k_mie_ab(int nR, int ld, const double *__r
     aI[o] = c * ai;
     bR[o] = c * br;
     bI[o] = c * bi;
+    if constexpr (DUAL) {
+      const double fr = dd.Dre[o], fi = dd.Dim[o];
+      // t_a' = D' / m - D / m^2, t_b' = D' m + D
+      const double tapr = (fr * imr - fi * imi) - (er * i2r - ei * i2i), tapi = (fr * imi + fi * imr) - (er * i2i + ei * i2r);
+      const double tbpr = (fr * mr - fi * mi) + er, tbpi = (fr * mi + fi * mr) + ei;
+      // a' = t' (xi_n psi_{n-1} - psi_n xi_{n-1}) / (t xi_n - xi_{n-1})^2; the bracket is i (psi_n chi_{n-1} - chi_n psi_{n-1})
+      const double wi = psi * chi1 - chi * psi1;
+      const double uar = adr / ad2, uai = -adi / ad2, var = uar * uar - uai * uai, vai = 2.0 * (uar * uai);
+      const double par = tapr * var - tapi * vai, pai = tapr * vai + tapi * var;
+      const double dar = -(wi * pai), dai = wi * par;
+      const double ubr = bdr / bd2, ubi = -bdi / bd2, vbr = ubr * ubr - ubi * ubi, vbi = 2.0 * (ubr * ubi);
+      const double pbr = tbpr * vbr - tbpi * vbi, pbi = tbpr * vbi + tbpi * vbr;
+      const double dbr = -(wi * pbi), dbi = wi * pbr;
+      // d/dn_r: e = a'; d/dn_i: e = i a'.  d|a|^2 = 2 Re(conj(a) e), d Re(a) = Re(e)
+      dsca_r = dsca_r + w2 * (2.0 * ((ar * dar + ai * dai) + (br * dbr + bi * dbi)));
+      dext_r = dext_r + w2 * (dar + dbr);
+      dsca_i = dsca_i - w2 * (2.0 * ((ar * dai - ai * dar) + (br * dbi - bi * dbr)));
+      dext_i = dext_i - w2 * (dai + dbi);
+      dd.aR[o] = c * dar;
+      dd.aI[o] = c * dai;
+      dd.bR[o] = c * dbr;
+      dd.bI[o] = c * dbi;
+    }
     psi0 = psi1;
     psi1 = psi;
     chi0 = chi1;
@@ -95,58 +147,95 @@ __global__ void __launch_bounds__(64) k_mie_ab(int nR, int ld, const double *__r
   }
   if (ssca) ssca[i] = sca;
   if (sext) sext[i] = ext;
+  if constexpr (DUAL)
+    if (dd.sum) {
+      dd.sum[i] = dsca_r;
+      dd.sum[(size_t)ld + i] = dext_r;
+      dd.sum[(size_t)2 * ld + i] = dsca_i;
+      dd.sum[(size_t)3 * ld + i] = dext_i;
+    }
 }
 
 // ---- (b) amplitude GEMM with the phase-matrix epilogue -------------------------------------------------------------------
-// One wavefront per block: 32 mu rows (blockIdx.x) times the radius tiles of chunk g = blockIdx.y (one tile of every G, in ascending order).
+// One wavefront per block: MT M tiles of 16 mu rows (blockIdx.x) times the radius tiles of chunk g = blockIdx.y (one tile of every G,
+// in ascending order).  The value form has MT = 2 (32 mu rows: two M tiles share every B operand); the Dual form has MT = 1 and twice
+// the blocks in x, because its eight accumulators and NW + 2 bulk rows of two M tiles do not fit the 512 registers of a wavefront.
 // Operand layouts of v_mfma_f64_16x16x4 as in mom_tile.hpp: A lane l = A[row l & 15][k l >> 4], B lane l = B[k l >> 4][col l & 15],
 // C lane l register r = C[row (l >> 4) + 4 r][col l & 15].  tau, pi: [Kp, nMuP]; the planes: [Kp, nRp]; all zero padded, so
-// the loads carry no masks.  partial: [G, NW, 4, nMuP].
-template <int NW>
+// the loads carry no masks.  partial: [G, NWO, 4, nMuP] with NWO = NW (+ 2 in the Dual form: weight row 0 times df/dn_r, df/dn_i).
+// Every element of S1, S2 and of the bulk rows 0 .. NW - 1 sees the same operations in the same order in both forms.
+struct MieDualPlanes {
+  const double *aR, *aI, *bR, *bI;  // c a', c b' (d/dm)
+};
+
+template <int NW, bool DUAL>
 __global__ void __launch_bounds__(64) k_mie_amp(int nR, int nMuP, int nRp, int Kp, int nTiles, int G,
                                                 const double *__restrict__ tau, const double *__restrict__ pi,
                                                 const double *__restrict__ caR, const double *__restrict__ caI,
                                                 const double *__restrict__ cbR, const double *__restrict__ cbI,
                                                 const double *__restrict__ x, const int *__restrict__ nmax,
-                                                const double *__restrict__ w, int fullK, double *__restrict__ partial) {
+                                                const double *__restrict__ w, int fullK, double *__restrict__ partial, MieDualPlanes dp) {
+  constexpr int MT = DUAL ? 1 : 2, NWO = DUAL ? NW + 2 : NW, NS = DUAL ? 8 : 4;
   const int lane = threadIdx.x, lr = lane & 15, lq = lane >> 4;
-  const int mu0 = kMuBlock * blockIdx.x, g = blockIdx.y;
-  d4 bulk[NW][4][2];
+  const int mu0 = 16 * MT * blockIdx.x, g = blockIdx.y;
+  d4 bulk[NWO][4][MT];
 #pragma unroll
-  for (int k = 0; k < NW; ++k)
+  for (int k = 0; k < NWO; ++k)
 #pragma unroll
     for (int f = 0; f < 4; ++f)
 #pragma unroll
-      for (int m = 0; m < 2; ++m) bulk[k][f][m] = (d4){0.0, 0.0, 0.0, 0.0};
+      for (int m = 0; m < MT; ++m) bulk[k][f][m] = (d4){0.0, 0.0, 0.0, 0.0};
   for (int j = 0; j * G < nTiles; ++j) {
     const int t = j * G + ((j & 1) ? G - 1 - g : g);  // boustrophedon: n_max grows with t, so the chunks' K sums stay close
     if (t >= nTiles) continue;
     const int i0 = kTileR * t, ilast = min(i0 + kTileR - 1, nR - 1);
     const int kEnd = fullK ? Kp : min(Kp, (nmax[ilast] + kKStep - 1) / kKStep * kKStep);
-    d4 s[4][2];  // S1 re, S1 im, S2 re, S2 im of the two M tiles
+    d4 s[NS][MT];  // S1 re, S1 im, S2 re, S2 im of the M tiles (Dual: then the same of S1', S2')
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
+    for (int q = 0; q < NS; ++q)
 #pragma unroll
-      for (int m = 0; m < 2; ++m) s[q][m] = (d4){0.0, 0.0, 0.0, 0.0};
+      for (int m = 0; m < MT; ++m) s[q][m] = (d4){0.0, 0.0, 0.0, 0.0};
     const double *pt = tau + (size_t)lq * nMuP + mu0 + lr, *pp = pi + (size_t)lq * nMuP + mu0 + lr;
     const size_t ob = (size_t)lq * nRp + i0 + lr;
     for (int k0 = 0; k0 < kEnd; k0 += kKStep) {
       const size_t oa = (size_t)k0 * nMuP, obk = ob + (size_t)k0 * nRp;
-      const double aT[2] = {pt[oa], pt[oa + 16]}, aP[2] = {pp[oa], pp[oa + 16]};
+      double aT[MT], aP[MT];
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        aT[m] = pt[oa + 16 * m];
+        aP[m] = pp[oa + 16 * m];
+      }
       const double bAR = caR[obk], bAI = caI[obk], bBR = cbR[obk], bBI = cbI[obk];
 #pragma unroll
-      for (int m = 0; m < 2; ++m) {
+      for (int m = 0; m < MT; ++m) {
         s[0][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aT[m], bAR, s[0][m], 0, 0, 0);
         s[1][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aT[m], bAI, s[1][m], 0, 0, 0);
         s[2][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aP[m], bAR, s[2][m], 0, 0, 0);
         s[3][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aP[m], bAI, s[3][m], 0, 0, 0);
       }
 #pragma unroll
-      for (int m = 0; m < 2; ++m) {
+      for (int m = 0; m < MT; ++m) {
         s[0][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aP[m], bBR, s[0][m], 0, 0, 0);
         s[1][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aP[m], bBI, s[1][m], 0, 0, 0);
         s[2][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aT[m], bBR, s[2][m], 0, 0, 0);
         s[3][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aT[m], bBI, s[3][m], 0, 0, 0);
+      }
+      if constexpr (DUAL) {
+        const double dAR = dp.aR[obk], dAI = dp.aI[obk], dBR = dp.bR[obk], dBI = dp.bI[obk];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+          s[4][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aT[m], dAR, s[4][m], 0, 0, 0);
+          s[5][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aT[m], dAI, s[5][m], 0, 0, 0);
+          s[6][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aP[m], dAR, s[6][m], 0, 0, 0);
+          s[7][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aP[m], dAI, s[7][m], 0, 0, 0);
+        }
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+          s[4][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aP[m], dBR, s[4][m], 0, 0, 0);
+          s[5][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aP[m], dBI, s[5][m], 0, 0, 0);
+          s[6][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aT[m], dBR, s[6][m], 0, 0, 0);
+          s[7][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(aT[m], dBI, s[7][m], 0, 0, 0);
+        }
       }
     }
     // epilogue: this lane's column is radius i0 + lr (padding: x = 0, weights 0, S = 0)
@@ -155,7 +244,7 @@ __global__ void __launch_bounds__(64) k_mie_amp(int nR, int nMuP, int nRp, int K
 #pragma unroll
     for (int k = 0; k < NW; ++k) wk[k] = w[(size_t)k * nRp + i0 + lr];
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
+    for (int m = 0; m < MT; ++m)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const double s1r = s[0][m][r], s1i = s[1][m][r], s2r = s[2][m][r], s2i = s[3][m][r];
@@ -168,21 +257,36 @@ __global__ void __launch_bounds__(64) k_mie_amp(int nR, int nMuP, int nRp, int K
         for (int k = 0; k < NW; ++k)
 #pragma unroll
           for (int q = 0; q < 4; ++q) bulk[k][q][m][r] = fma(wk[k], f[q], bulk[k][q][m][r]);
+        if constexpr (DUAL) {
+          // e_j = S_j' for d/dn_r and i S_j' for d/dn_i:  df11 = 1/2x^2 2 (Re(S1* e1) + Re(S2* e2)), df12 = -1/2x^2 2 (Re(S1* e1) - Re(S2* e2)),
+          // df33 = 1/2x^2 2 Re(e1 S2* + S1 e2*), df34 = -1/2x^2 2 Im(e1 S2* + S1 e2*)
+          const double d1r = s[4][m][r], d1i = s[5][m][r], d2r = s[6][m][r], d2i = s[7][m][r];
+#pragma unroll
+          for (int c = 0; c < 2; ++c) {
+            const double e1r = c ? -d1i : d1r, e1i = c ? d1r : d1i, e2r = c ? -d2i : d2r, e2i = c ? d2r : d2i;
+            const double p1 = s1r * e1r + s1i * e1i, p2 = s2r * e2r + s2i * e2i;
+            const double zr = (e1r * s2r + e1i * s2i) + (s1r * e2r + s1i * e2i);
+            const double zi = (e1i * s2r - e1r * s2i) + (s1i * e2r - s1r * e2i);
+            const double df[4] = {hx * (2.0 * (p1 + p2)), hx * (2.0 * zr), -hx * (2.0 * (p1 - p2)), -hx * (2.0 * zi)};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) bulk[NW + c][q][m][r] = fma(wk[0], df[q], bulk[NW + c][q][m][r]);
+          }
+        }
       }
   }
   // sum over the 16 radii of the tile columns (fixed butterfly), lane lr = 0 of every row writes
 #pragma unroll
-  for (int k = 0; k < NW; ++k)
+  for (int k = 0; k < NWO; ++k)
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
-      for (int m = 0; m < 2; ++m)
+      for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           double v = bulk[k][q][m][r];
 #pragma unroll
           for (int off = 1; off < 16; off <<= 1) v += __shfl_xor(v, off);
-          if (lr == 0) partial[(((size_t)g * NW + k) * 4 + q) * nMuP + mu0 + 16 * m + lq + 4 * r] = v;
+          if (lr == 0) partial[(((size_t)g * NWO + k) * 4 + q) * nMuP + mu0 + 16 * m + lq + 4 * r] = v;
         }
 }
 
@@ -273,22 +377,23 @@ int mie_device(const char *fn, int device) {
 
 inline size_t round_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
-template <int NW>
-void launch_amp(hipStream_t st, dim3 grid, int nR, int nMuP, int nRp, int Kp, int nTiles, int G, const double *tau, const double *pi,
+template <int NW, bool DUAL>
+void launch_amp(hipStream_t st, int nMuP, int G, int nR, int nRp, int Kp, int nTiles, const double *tau, const double *pi,
                 const double *const *pl, const double *x, const int *nmax, const double *w, int fullK, double *partial) {
-  hipLaunchKernelGGL(k_mie_amp<NW>, grid, dim3(64), 0, st, nR, nMuP, nRp, Kp, nTiles, G, tau, pi, pl[0], pl[1], pl[2], pl[3], x, nmax, w,
-                     fullK, partial);
+  const dim3 grid(nMuP / (DUAL ? 16 : kMuBlock), G);
+  const MieDualPlanes dp = {pl[4], pl[5], pl[6], pl[7]};
+  hipLaunchKernelGGL((k_mie_amp<NW, DUAL>), grid, dim3(64), 0, st, nR, nMuP, nRp, Kp, nTiles, G, tau, pi, pl[0], pl[1], pl[2], pl[3], x, nmax,
+                     w, fullK, partial, dp);
 }
 
-}  // namespace
-
-extern "C" int mom_mie_nai2(int device, int nR, const double *r, int nW, const double *w, double lambda, double n_r, double n_i,
-                            int n_mu, const double *w_mu, int n_max, const double *pi_tab, const double *tau_tab, int l_max,
-                            const double *P, const double *P2, const double *R2, const double *T2, int flags, double *bulk_f,
-                            double *C, double *greek, double *gpu_ms) {
-  const char *fn = "mom_mie_nai2";
+// mom_mie_nai2 (dual = false) and mom_mie_nai2_dual (dual = true): the two differ in the kernel forms, in the four more planes,
+// the two more D planes and the four more per-radius sums of the Dual run, and in nO = nW + 2 output rows.
+int mie_nai2_run(const char *fn, bool dual, int device, int nR, const double *r, int nW, const double *w, double lambda, double n_r,
+                 double n_i, int n_mu, const double *w_mu, int n_max, const double *pi_tab, const double *tau_tab, int l_max,
+                 const double *P, const double *P2, const double *R2, const double *T2, int flags, double *bulk_f, double *C,
+                 double *greek, double *gpu_ms) {
   if (nR < 1 || n_mu < 1) return mie_fail(fn, "nR and n_mu must be at least 1");
-  if (nW < 1 || nW > MOM_MIE_MAX_WEIGHT_ROWS) return mie_fail(fn, "nW must be 1..4");
+  if (nW < 1 || nW > (dual ? MOM_MIE_DUAL_MAX_WEIGHT_ROWS : MOM_MIE_MAX_WEIGHT_ROWS)) return mie_fail(fn, dual ? "nW must be 1..3" : "nW must be 1..4");
   if (!(lambda > 0.0)) return mie_fail(fn, "lambda must be positive");
   if (!(n_i >= 0.0) || !std::isfinite(n_r) || !std::isfinite(n_i)) return mie_fail(fn, "n_i must be >= 0 (m = n_r + i n_i)");
   if (l_max < 1 || n_max < 1) return mie_fail(fn, "l_max and n_max must be at least 1");
@@ -315,16 +420,19 @@ extern "C" int mom_mie_nai2(int device, int nR, const double *r, int nW, const d
   const int nTiles = (int)(nRp / kTileR), nMuBlk = (int)(nMuP / kMuBlock);
   int G = 2048 / nMuBlk;  // about two wavefronts per SIMD of the device, at most kMaxChunks partials per bulk element
   G = G < 1 ? 1 : (G > kMaxChunks ? kMaxChunks : G);
-  G = G > nTiles ? nTiles : G;
+  G = G > nTiles ? nTiles : G;  // the same chunks in both forms: the rows they share are bitwise equal
+  const int nO = dual ? nW + MOM_MIE_INDEX_ROWS : nW;      // output rows
+  const int nPlanes = dual ? 8 : 4, nDp = dual ? 4 : 2, nSum = dual ? 6 : 2;
   // one allocation, carved in doubles (the two int arrays last)
   const size_t nTab = Kp * nMuP, nPl = Kp * nRp, nD = (size_t)n_max * nRp, nLeg = (size_t)l_max * n_mu;
-  const size_t nPart = (size_t)G * nW * 4 * nMuP, nBulk = (size_t)nW * 4 * n_mu, nGreek = (size_t)nW * 6 * l_max;
-  const size_t doubles = 2 * nTab + 4 * nPl + 2 * nD + 3 * nRp + (size_t)nW * nRp + n_mu + 4 * nLeg + nPart + nBulk + nGreek;
+  const size_t nPart = (size_t)G * nO * 4 * nMuP, nBulk = (size_t)nO * 4 * n_mu, nGreek = (size_t)nO * 6 * l_max;
+  const size_t doubles =
+      2 * nTab + nPlanes * nPl + nDp * nD + (1 + nSum) * nRp + (size_t)nW * nRp + n_mu + 4 * nLeg + nPart + nBulk + nGreek;
   const size_t bytes = doubles * sizeof(double) + 2 * nRp * sizeof(int);
   char *base = nullptr;
   hipStream_t st = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  std::vector<double> hs(2 * nRp);
+  std::vector<double> hs(nSum * nRp);
   MCHK(hipSetDevice(device));
   MCHK(hipStreamCreate(&st));
   MCHK(hipMalloc((void **)&base, bytes));
@@ -332,12 +440,13 @@ extern "C" int mom_mie_nai2(int device, int nR, const double *r, int nW, const d
     double *p = (double *)base;
     double *d_tau = p; p += nTab;
     double *d_pi = p; p += nTab;
-    double *d_pl[4];
-    for (int q = 0; q < 4; ++q) { d_pl[q] = p; p += nPl; }
-    double *d_Dre = p; p += nD;
-    double *d_Dim = p; p += nD;
+    double *d_pl[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // c a, c b; Dual: c a', c b'
+    for (int q = 0; q < nPlanes; ++q) { d_pl[q] = p; p += nPl; }
+    double *d_D[4] = {nullptr, nullptr, nullptr, nullptr};  // D re, im; Dual: D' re, im
+    for (int q = 0; q < nDp; ++q) { d_D[q] = p; p += nD; }
     double *d_x = p; p += nRp;
-    double *d_ss = p; p += 2 * nRp;  // sum (2n+1)(|a|^2 + |b|^2) | sum (2n+1) Re(a + b)
+    // sum (2n+1)(|a|^2 + |b|^2) | sum (2n+1) Re(a + b); Dual: their d/dn_r forms, then their d/dn_i forms
+    double *d_ss = p; p += nSum * nRp;
     double *d_w = p; p += (size_t)nW * nRp;
     double *d_wmu = p; p += n_mu;
     double *d_leg[4];
@@ -360,38 +469,52 @@ extern "C" int mom_mie_nai2(int device, int nR, const double *r, int nW, const d
     for (int q = 0; q < 4; ++q) MCHK(hipMemcpyAsync(d_leg[q], leg[q], nLeg * sizeof(double), hipMemcpyHostToDevice, st));
     for (int q = 0; q < 4; ++q) MCHK(hipEventCreate(&ev[q]));
     MCHK(hipEventRecord(ev[0], st));
-    hipLaunchKernelGGL(k_mie_ab<true>, dim3((nR + 63) / 64), dim3(64), 0, st, nR, (int)nRp, d_x, d_n, d_n + nRp, n_r, n_i, d_Dre, d_Dim,
-                       d_pl[0], d_pl[1], d_pl[2], d_pl[3], d_ss, d_ss + nRp);
+    {
+      const MieDualOut dd = {d_D[2], d_D[3], d_pl[4], d_pl[5], d_pl[6], d_pl[7], dual ? d_ss + 2 * nRp : nullptr};
+      if (dual)
+        hipLaunchKernelGGL((k_mie_ab<true, true>), dim3((nR + 63) / 64), dim3(64), 0, st, nR, (int)nRp, d_x, d_n, d_n + nRp, n_r, n_i, d_D[0],
+                           d_D[1], d_pl[0], d_pl[1], d_pl[2], d_pl[3], d_ss, d_ss + nRp, dd);
+      else
+        hipLaunchKernelGGL((k_mie_ab<true, false>), dim3((nR + 63) / 64), dim3(64), 0, st, nR, (int)nRp, d_x, d_n, d_n + nRp, n_r, n_i, d_D[0],
+                           d_D[1], d_pl[0], d_pl[1], d_pl[2], d_pl[3], d_ss, d_ss + nRp, dd);
+    }
     MCHK(hipGetLastError());
     MCHK(hipEventRecord(ev[1], st));
     {
-      const dim3 grid(nMuBlk, G);
       const int fullK = (flags & MOM_MIE_FULL_K) ? 1 : 0;
-      switch (nW) {
-        case 1: launch_amp<1>(st, grid, nR, (int)nMuP, (int)nRp, (int)Kp, nTiles, G, d_tau, d_pi, d_pl, d_x, d_n, d_w, fullK, d_part); break;
-        case 2: launch_amp<2>(st, grid, nR, (int)nMuP, (int)nRp, (int)Kp, nTiles, G, d_tau, d_pi, d_pl, d_x, d_n, d_w, fullK, d_part); break;
-        case 3: launch_amp<3>(st, grid, nR, (int)nMuP, (int)nRp, (int)Kp, nTiles, G, d_tau, d_pi, d_pl, d_x, d_n, d_w, fullK, d_part); break;
-        default: launch_amp<4>(st, grid, nR, (int)nMuP, (int)nRp, (int)Kp, nTiles, G, d_tau, d_pi, d_pl, d_x, d_n, d_w, fullK, d_part); break;
+#define MIE_AMP(NW, DUAL) \
+  launch_amp<NW, DUAL>(st, (int)nMuP, G, nR, (int)nRp, (int)Kp, nTiles, d_tau, d_pi, d_pl, d_x, d_n, d_w, fullK, d_part)
+      switch (dual ? 4 + nW : nW) {
+        case 1: MIE_AMP(1, false); break;
+        case 2: MIE_AMP(2, false); break;
+        case 3: MIE_AMP(3, false); break;
+        case 4: MIE_AMP(4, false); break;
+        case 5: MIE_AMP(1, true); break;
+        case 6: MIE_AMP(2, true); break;
+        default: MIE_AMP(3, true); break;
       }
+#undef MIE_AMP
       MCHK(hipGetLastError());
-      hipLaunchKernelGGL(k_mie_sum, dim3((unsigned)((nBulk + 255) / 256)), dim3(256), 0, st, G, nW * 4, n_mu, (int)nMuP, d_part, d_bulk);
+      hipLaunchKernelGGL(k_mie_sum, dim3((unsigned)((nBulk + 255) / 256)), dim3(256), 0, st, G, nO * 4, n_mu, (int)nMuP, d_part, d_bulk);
       MCHK(hipGetLastError());
     }
     MCHK(hipEventRecord(ev[2], st));
-    hipLaunchKernelGGL(k_mie_greek, dim3(l_max, nW), dim3(64), 0, st, n_mu, l_max, d_wmu, d_bulk, d_leg[0], d_leg[1], d_leg[2], d_leg[3],
+    hipLaunchKernelGGL(k_mie_greek, dim3(l_max, nO), dim3(64), 0, st, n_mu, l_max, d_wmu, d_bulk, d_leg[0], d_leg[1], d_leg[2], d_leg[3],
                        d_greek);
     MCHK(hipGetLastError());
     MCHK(hipEventRecord(ev[3], st));
     MCHK(hipMemcpyAsync(bulk_f, d_bulk, nBulk * sizeof(double), hipMemcpyDeviceToHost, st));
     MCHK(hipMemcpyAsync(greek, d_greek, nGreek * sizeof(double), hipMemcpyDeviceToHost, st));
-    MCHK(hipMemcpyAsync(hs.data(), d_ss, 2 * nRp * sizeof(double), hipMemcpyDeviceToHost, st));
+    MCHK(hipMemcpyAsync(hs.data(), d_ss, nSum * nRp * sizeof(double), hipMemcpyDeviceToHost, st));
     MCHK(hipStreamSynchronize(st));
     // C_sca,i = 2 pi / k^2 * sum, weighted by w_i / (4 pi r_i^2): w_i * sum_i / (2 x_i^2), added in radius order (the terms in
-    // Float64, the running sum in the host's long double, so that the O(nR) sum adds no rounding of its own)
-    for (int k = 0; k < nW; ++k)
+    // Float64, the running sum in the host's long double, so that the O(nR) sum adds no rounding of its own).  The two index rows
+    // of the Dual run: weight row 0 on the d/dn_r and d/dn_i sums.
+    for (int k = 0; k < nO; ++k)
       for (int q = 0; q < 2; ++q) {
+        const double *wk = w + (size_t)(k < nW ? k : 0) * nR, *sk = hs.data() + (size_t)((k < nW ? 0 : 2 * (k - nW + 1)) + q) * nRp;
         long double acc = 0.0L;
-        for (int i = 0; i < nR; ++i) acc += (long double)(w[(size_t)k * nR + i] * (hs[q * nRp + i] / (2.0 * hx[i] * hx[i])));
+        for (int i = 0; i < nR; ++i) acc += (long double)(wk[i] * (sk[i] / (2.0 * hx[i] * hx[i])));
         C[2 * k + q] = (double)acc;
       }
     if (gpu_ms)
@@ -409,10 +532,12 @@ done:
   return rc;
 }
 
-extern "C" int mom_mie_coefficients(int device, int nX, const double *x, double n_r, double n_i, int n_max, double *a_re, double *a_im,
-                                    double *b_re, double *b_im) {
-  const char *fn = "mom_mie_coefficients";
-  if (nX < 1 || n_max < 1 || !x || !a_re || !a_im || !b_re || !b_im) return mie_fail(fn, "bad argument (null pointer or non-positive size)");
+// mom_mie_coefficients (out: a, b as four planes) and mom_mie_coefficients_dual (out: then a', b' as four more)
+int mie_coefficients_run(const char *fn, bool dual, int device, int nX, const double *x, double n_r, double n_i, int n_max,
+                         double *const *out) {
+  bool null = !x;
+  for (int q = 0; q < (dual ? 8 : 4); ++q) null = null || !out[q];
+  if (nX < 1 || n_max < 1 || null) return mie_fail(fn, "bad argument (null pointer or non-positive size)");
   if (!(n_i >= 0.0) || !std::isfinite(n_r) || !std::isfinite(n_i)) return mie_fail(fn, "n_i must be >= 0 (m = n_r + i n_i)");
   std::vector<int> hn(2 * (size_t)nX);
   for (int i = 0; i < nX; ++i) {
@@ -424,27 +549,65 @@ extern "C" int mom_mie_coefficients(int device, int nX, const double *x, double 
   int rc = mie_device(fn, device);
   if (rc != MOM_OK) return rc;
   const size_t nPl = (size_t)n_max * nX;
-  const size_t bytes = (6 * nPl + nX) * sizeof(double) + 2 * (size_t)nX * sizeof(int);
+  const int nOut = dual ? 8 : 4, nDp = dual ? 4 : 2;  // planes a, b (Dual: a', b'), then D (Dual: D')
+  const size_t bytes = ((nOut + nDp) * nPl + nX) * sizeof(double) + 2 * (size_t)nX * sizeof(int);
   char *base = nullptr;
   hipStream_t st = nullptr;
   MCHK(hipSetDevice(device));
   MCHK(hipStreamCreate(&st));
   MCHK(hipMalloc((void **)&base, bytes));
   {
-    double *d_pl = (double *)base, *d_D = d_pl + 4 * nPl, *d_x = d_D + 2 * nPl;
+    double *d_pl = (double *)base, *d_D = d_pl + nOut * nPl, *d_x = d_D + nDp * nPl;
     int *d_n = (int *)(d_x + nX);
-    double *out[4] = {a_re, a_im, b_re, b_im};
     MCHK(hipMemsetAsync(base, 0, bytes, st));
     MCHK(hipMemcpyAsync(d_x, x, (size_t)nX * sizeof(double), hipMemcpyHostToDevice, st));
     MCHK(hipMemcpyAsync(d_n, hn.data(), 2 * (size_t)nX * sizeof(int), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_mie_ab<false>, dim3((nX + 63) / 64), dim3(64), 0, st, nX, nX, d_x, d_n, d_n + nX, n_r, n_i, d_D, d_D + nPl, d_pl,
-                       d_pl + nPl, d_pl + 2 * nPl, d_pl + 3 * nPl, (double *)nullptr, (double *)nullptr);
+    if (dual) {
+      const MieDualOut dd = {d_D + 2 * nPl, d_D + 3 * nPl, d_pl + 4 * nPl, d_pl + 5 * nPl, d_pl + 6 * nPl, d_pl + 7 * nPl, nullptr};
+      hipLaunchKernelGGL((k_mie_ab<false, true>), dim3((nX + 63) / 64), dim3(64), 0, st, nX, nX, d_x, d_n, d_n + nX, n_r, n_i, d_D, d_D + nPl,
+                         d_pl, d_pl + nPl, d_pl + 2 * nPl, d_pl + 3 * nPl, (double *)nullptr, (double *)nullptr, dd);
+    } else {
+      const MieDualOut dd = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+      hipLaunchKernelGGL((k_mie_ab<false, false>), dim3((nX + 63) / 64), dim3(64), 0, st, nX, nX, d_x, d_n, d_n + nX, n_r, n_i, d_D, d_D + nPl,
+                         d_pl, d_pl + nPl, d_pl + 2 * nPl, d_pl + 3 * nPl, (double *)nullptr, (double *)nullptr, dd);
+    }
     MCHK(hipGetLastError());
-    for (int q = 0; q < 4; ++q) MCHK(hipMemcpyAsync(out[q], d_pl + q * nPl, nPl * sizeof(double), hipMemcpyDeviceToHost, st));
+    for (int q = 0; q < nOut; ++q) MCHK(hipMemcpyAsync(out[q], d_pl + q * nPl, nPl * sizeof(double), hipMemcpyDeviceToHost, st));
     MCHK(hipStreamSynchronize(st));
   }
 done:
   if (base) (void)hipFree(base);
   if (st) (void)hipStreamDestroy(st);
   return rc;
+}
+
+}  // namespace
+
+extern "C" int mom_mie_nai2(int device, int nR, const double *r, int nW, const double *w, double lambda, double n_r, double n_i,
+                            int n_mu, const double *w_mu, int n_max, const double *pi_tab, const double *tau_tab, int l_max,
+                            const double *P, const double *P2, const double *R2, const double *T2, int flags, double *bulk_f,
+                            double *C, double *greek, double *gpu_ms) {
+  return mie_nai2_run("mom_mie_nai2", false, device, nR, r, nW, w, lambda, n_r, n_i, n_mu, w_mu, n_max, pi_tab, tau_tab, l_max, P, P2, R2,
+                      T2, flags, bulk_f, C, greek, gpu_ms);
+}
+
+extern "C" int mom_mie_nai2_dual(int device, int nR, const double *r, int nW, const double *w, double lambda, double n_r, double n_i,
+                                 int n_mu, const double *w_mu, int n_max, const double *pi_tab, const double *tau_tab, int l_max,
+                                 const double *P, const double *P2, const double *R2, const double *T2, int flags, double *bulk_f,
+                                 double *C, double *greek, double *gpu_ms) {
+  return mie_nai2_run("mom_mie_nai2_dual", true, device, nR, r, nW, w, lambda, n_r, n_i, n_mu, w_mu, n_max, pi_tab, tau_tab, l_max, P, P2,
+                      R2, T2, flags, bulk_f, C, greek, gpu_ms);
+}
+
+extern "C" int mom_mie_coefficients(int device, int nX, const double *x, double n_r, double n_i, int n_max, double *a_re, double *a_im,
+                                    double *b_re, double *b_im) {
+  double *const out[8] = {a_re, a_im, b_re, b_im, nullptr, nullptr, nullptr, nullptr};
+  return mie_coefficients_run("mom_mie_coefficients", false, device, nX, x, n_r, n_i, n_max, out);
+}
+
+extern "C" int mom_mie_coefficients_dual(int device, int nX, const double *x, double n_r, double n_i, int n_max, double *a_re,
+                                         double *a_im, double *b_re, double *b_im, double *da_re, double *da_im, double *db_re,
+                                         double *db_im) {
+  double *const out[8] = {a_re, a_im, b_re, b_im, da_re, da_im, db_re, db_im};
+  return mie_coefficients_run("mom_mie_coefficients_dual", true, device, nX, x, n_r, n_i, n_max, out);
 }

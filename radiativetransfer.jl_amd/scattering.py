@@ -4,7 +4,9 @@ compute_ref_aerosol_extinction and truncate_phase(δBGE, ...).
 The sums over radii, orders and angles run on the device (mom_mie_nai2, csrc/mom_mie.hip); the host builds what they read --
 the radius quadrature, the Gauss nodes of the scattering angle, the π/τ and P/P²/R²/T² tables (O(n_μ²) recurrences, vectorised
 over μ) -- and does the arithmetic that follows the sums: the division by the bulk C_sca and, for autodiff=True, the quotient
-rule of the partial rows.  Float64 only; NAI2 only (no PCW).  There is no CPU fallback.
+rule of the partial rows.  Partials with respect to the refractive index (nᵣ, nᵢ) come from the Dual run of the same kernels
+(mom_mie_nai2_dual); truncate_phase and aerosol_optics_partial carry them on to rt_run_dual_device_optics.
+Float64 only; NAI2 only (no PCW).  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -198,10 +200,16 @@ def mie_inputs(model: MieModel, autodiff: bool = False) -> MieInputs:
     return MieInputs(r, w, μ, w_μ, π_, τ_, P, P2, R2, T2)
 
 
-def _device_call(model: MieModel, autodiff: bool, flags: int = 0):
+ALL_AEROSOL_PARAMETERS = ("r_m", "σ_g", "nᵣ", "nᵢ")    # the reference's x (phase_function_autodiff.jl:48)
+_SIZE_PARAMETERS, _INDEX_PARAMETERS = ALL_AEROSOL_PARAMETERS[:2], ALL_AEROSOL_PARAMETERS[2:]
+
+
+def _device_call(model: MieModel, autodiff: bool, flags: int = 0, dual: bool = False):
+    """mom_mie_nai2 on the model's inputs, or (dual) mom_mie_nai2_dual: two more output rows, ∂/∂nᵣ and ∂/∂nᵢ of row 0's sums"""
     inp = mie_inputs(model, autodiff)
-    return inp, _lib.mie_nai2(inp.r, inp.w, model.λ, model.aerosol.nᵣ, model.aerosol.nᵢ, inp.w_μ, inp.π_, inp.τ_, inp.P, inp.P2,
-                              inp.R2, inp.T2, flags=flags)
+    call = _lib.mie_nai2_dual if dual else _lib.mie_nai2
+    return inp, call(inp.r, inp.w, model.λ, model.aerosol.nᵣ, model.aerosol.nᵢ, inp.w_μ, inp.π_, inp.τ_, inp.P, inp.P2, inp.R2, inp.T2,
+                     flags=flags)
 
 
 def _greek(g: np.ndarray) -> rt.GreekCoefs:
@@ -209,8 +217,9 @@ def _greek(g: np.ndarray) -> rt.GreekCoefs:
 
 
 def optics_from_sums(C: np.ndarray, greek: np.ndarray):
-    """The host arithmetic after the device sums: (AerosolOptics, [∂/∂θ of it for every further weight row]).  C [nW, 2] =
-    bulk (C_sca, C_ext), greek [nW, 6, l_max] unnormalised."""
+    """The host arithmetic after the device sums: (AerosolOptics, [∂/∂θ of it for every further row]).  C [nW, 2] =
+    bulk (C_sca, C_ext), greek [nW, 6, l_max] unnormalised.  A further row holds the partial of row 0's sums with respect to one
+    parameter, whichever it is: a weight row of ∂wₓ/∂θ, or an index row of mom_mie_nai2_dual."""
     Cs, Ce = C[0]
     aero = rt.AerosolOptics(greek_coefs=_greek(greek[0] / Cs), ω̃=float(Cs / Ce), fᵗ=1.0, k=float(Ce))
     partials = []
@@ -221,12 +230,42 @@ def optics_from_sums(C: np.ndarray, greek: np.ndarray):
     return aero, partials
 
 
-def compute_aerosol_optical_properties(model: MieModel, autodiff: bool = False):
+def compute_aerosol_optical_properties(model: MieModel, autodiff: bool = False, wrt=_SIZE_PARAMETERS):
     """AerosolOptics(greek_coefs, ω̃, k, fᵗ = 1) of the model; with autodiff=True also the partials of every field with respect to
-    (r_m, σ_g) of the log-normal size distribution, as two AerosolOptics holding the derivatives: (optics, [∂/∂r_m, ∂/∂σ_g])."""
-    _, (_, C, greek, _) = _device_call(model, autodiff)
+    the parameters named in `wrt`, a subset of ALL_AEROSOL_PARAMETERS = (r_m, σ_g, nᵣ, nᵢ): the median radius and geometric width
+    of the log-normal size distribution and the real and imaginary part of the refractive index.  Returns
+    (optics, [∂/∂p for p in wrt]), each partial an AerosolOptics holding the derivatives.  The size-distribution partials are
+    further weight rows of the same sums (mom_mie_nai2); an index parameter takes the Dual run of the Mie coefficients
+    (mom_mie_nai2_dual).  The default, (r_m, σ_g), is the call without `wrt`."""
+    if not autodiff:
+        _, (_, C, greek, _) = _device_call(model, False)
+        return optics_from_sums(C, greek)[0]
+    wrt = tuple(wrt)
+    unknown = [p for p in wrt if p not in ALL_AEROSOL_PARAMETERS]
+    if unknown or len(set(wrt)) != len(wrt):
+        raise ValueError(f"wrt must be distinct names out of {ALL_AEROSOL_PARAMETERS}, got {wrt}")
+    if not any(p in _INDEX_PARAMETERS for p in wrt):
+        _, (_, C, greek, _) = _device_call(model, True)
+        rows = _SIZE_PARAMETERS
+    else:
+        size_rows = any(p in _SIZE_PARAMETERS for p in wrt)
+        _, (_, C, greek, _) = _device_call(model, size_rows, dual=True)
+        rows = (_SIZE_PARAMETERS if size_rows else ()) + _INDEX_PARAMETERS
     aero, partials = optics_from_sums(C, greek)
-    return (aero, partials) if autodiff else aero
+    return aero, [partials[rows.index(p)] for p in wrt]
+
+
+def aerosol_derivs(optics: rt.AerosolOptics, partials) -> np.ndarray:
+    """The reference's `derivs` [6 l_max + 2, len(partials)]: one column per partial, the rows in the order of the Jacobian that
+    convert_jacobian_result_to_aerosol_optics unpacks (phase_function_autodiff.jl:9-29): α, β, γ, δ, ϵ, ζ, then ω̃ and k."""
+    l_max = len(optics.greek_coefs.β)
+    out = np.zeros((6 * l_max + 2, len(partials)))
+    for j, p in enumerate(partials):
+        g = p.greek_coefs
+        if any(len(a) != l_max for a in (g.α, g.β, g.γ, g.δ, g.ϵ, g.ζ)):
+            raise ValueError("a partial's Greek coefficients do not have the length of the optics'")
+        out[:, j] = np.concatenate([g.α, g.β, g.γ, g.δ, g.ϵ, g.ζ, [p.ω̃, p.k]])
+    return out
 
 
 def compute_ref_aerosol_extinction(model: MieModel) -> float:
@@ -254,16 +293,28 @@ def reconstruct_phase(greek: rt.GreekCoefs, μ: np.ndarray):
     return (f11, f12, f22, f33, f34, f44), P, P2
 
 
-def _weighted_fit(w_μ, B, f, first):
-    """the normal equations of truncate_phase.jl:129-141 / 154-167: A_ij = Σ w B_i B_j / f², b_i = Σ w B_i / f, rows from `first`"""
+def _weighted_fit(w_μ, B, f, first, dfs=()):
+    """the normal equations of truncate_phase.jl:129-141 / 154-167: A_ij = Σ w B_i B_j / f², b_i = Σ w B_i / f, rows from `first`.
+    With partials dfs of f also the forward-mode derivative of the solution: ∂c = A⁻¹ (∂b - ∂A c), with ∂(B / f) = -(B / f) ∂f / f."""
     Bf = B[:, first:] / f[:, None]
-    return np.linalg.solve((w_μ[:, None] * Bf).T @ Bf, Bf.T @ w_μ)
+    A = (w_μ[:, None] * Bf).T @ Bf
+    c = np.linalg.solve(A, Bf.T @ w_μ)
+    if not len(dfs):
+        return c
+    dcs = []
+    for df in dfs:
+        dBf = -Bf * (df / f)[:, None]
+        dA = (w_μ[:, None] * dBf).T @ Bf + (w_μ[:, None] * Bf).T @ dBf
+        dcs.append(np.linalg.solve(A, dBf.T @ w_μ - dA @ c))
+    return c, dcs
 
 
-def truncate_phase(mod: δBGE, aero: rt.AerosolOptics) -> rt.AerosolOptics:
+def truncate_phase(mod: δBGE, aero: rt.AerosolOptics, partials=None):
     """truncate_phase(mod::δBGE, aero) as the reference writes it: three weighted least-squares fits over ALL Gauss nodes
     (Δ_angle is read, the index set it selects is never used), β, δ, α, ζ rescaled by c₀ = cl[1], γᵗ and ϵᵗ the fits themselves,
-    ω̃ and k unchanged, fᵗ = 1 - c₀."""
+    ω̃ and k unchanged, fᵗ = 1 - c₀.
+    With `partials` (AerosolOptics holding ∂aero/∂θ, as compute_aerosol_optical_properties(autodiff=True) returns them) the result
+    is (truncated, [∂truncated/∂θ]): the forward-mode derivative of the fits and of the quotients, ∂fᵗ = -∂c₀, ∂ω̃ and ∂k passed on."""
     g = aero.greek_coefs
     l_tr = int(mod.l_max)
     μ, w_μ = gausslegendre(len(g.β))
@@ -272,14 +323,53 @@ def truncate_phase(mod: δBGE, aero: rt.AerosolOptics) -> rt.AerosolOptics:
     fac = np.zeros(l_tr)
     for l in range(2, l_tr):
         fac[l] = math.sqrt(1.0 / ((l - 1.0) * l * (l + 1.0) * (l + 2.0)))
-    cl = _weighted_fit(w_μ, P[:, :l_tr], f11, 0)
+    nP = 0 if partials is None else len(partials)
+    # the reconstruction is linear in the Greek coefficients: ∂f₁₁ = P ∂β, ∂f₁₂ and ∂f₃₄ from ∂γ and ∂ϵ
+    dphase = [reconstruct_phase(p.greek_coefs, μ)[0] for p in partials] if nP else []
+    fit = lambda B, f, first, q: _weighted_fit(w_μ, B, f, first, [d[q] for d in dphase]) if nP else (_weighted_fit(w_μ, B, f, first), [])
+    cl, dcl = fit(P[:, :l_tr], f11, 0, 0)
     γᵗ, ϵᵗ = np.zeros(l_tr), np.zeros(l_tr)
+    dγᵗ, dϵᵗ = [np.zeros(l_tr) for _ in range(nP)], [np.zeros(l_tr) for _ in range(nP)]
     if l_tr > 2:
-        γᵗ[2:] = _weighted_fit(w_μ, fac * P2[:, :l_tr], f12, 2)
-        ϵᵗ[2:] = _weighted_fit(w_μ, fac * P2[:, :l_tr], f34, 2)
+        γᵗ[2:], dγ = fit(fac * P2[:, :l_tr], f12, 2, 1)
+        ϵᵗ[2:], dϵ = fit(fac * P2[:, :l_tr], f34, 2, 4)
+        for j in range(nP):
+            dγᵗ[j][2:], dϵᵗ[j][2:] = dγ[j], dϵ[j]
     c0 = cl[0]
     βᵗ = cl / c0
     δᵗ = (g.δ[:l_tr] - (g.β[:l_tr] - cl)) / c0
     αᵗ = (g.α[:l_tr] - (g.β[:l_tr] - cl)) / c0
     ζᵗ = (g.ζ[:l_tr] - (g.β[:l_tr] - cl)) / c0
-    return rt.AerosolOptics(greek_coefs=rt.GreekCoefs(α=αᵗ, β=βᵗ, γ=γᵗ, δ=δᵗ, ϵ=ϵᵗ, ζ=ζᵗ), ω̃=aero.ω̃, fᵗ=float(1.0 - c0), k=aero.k)
+    out = rt.AerosolOptics(greek_coefs=rt.GreekCoefs(α=αᵗ, β=βᵗ, γ=γᵗ, δ=δᵗ, ϵ=ϵᵗ, ζ=ζᵗ), ω̃=aero.ω̃, fᵗ=float(1.0 - c0), k=aero.k)
+    if partials is None:
+        return out
+    d_out = []
+    for j, p in enumerate(partials):
+        dg, dc, dc0 = p.greek_coefs, dcl[j], dcl[j][0]
+        # (a - (β - cl)) / c₀ for a = δ, α, ζ; cl / c₀
+        rescaled = lambda a, da: (da[:l_tr] - (dg.β[:l_tr] - dc)) / c0 - (a[:l_tr] - (g.β[:l_tr] - cl)) * dc0 / c0 ** 2
+        d_out.append(rt.AerosolOptics(
+            greek_coefs=rt.GreekCoefs(α=rescaled(g.α, dg.α), β=dc / c0 - cl * dc0 / c0 ** 2, γ=dγᵗ[j], δ=rescaled(g.δ, dg.δ), ϵ=dϵᵗ[j],
+                                      ζ=rescaled(g.ζ, dg.ζ)), ω̃=p.ω̃, fᵗ=float(-dc0), k=p.k))
+    return out, d_out
+
+
+def aerosol_optics_partial(model: rt.vSmartMOM_Model, i_aer: int, d_optics: rt.AerosolOptics, dτ_aer=None) -> rt.OpticsPartial:
+    """The OpticsPartial of one parameter of aerosol i_aer (0-based) of the scene `model`, from ∂(aerosol optics)/∂θ as
+    truncate_phase(..., partials=) returns it: dω̃ and dfᵗ at i_aer, dZpp / dZmp = compute_Z_moments of the derivative Greek
+    coefficients (the moments are linear in them) at basis 1 + i_aer (basis 0 is Rayleigh), zeros elsewhere.  dτ_aer [nAer, Nz]
+    is passed on (the scene's τ_aer is an input of its own; a caller that scales it with k supplies its partial).  The result goes
+    into rt_run_dual_device_optics."""
+    nAer = len(model.aerosol_optics)
+    if not 0 <= i_aer < nAer:
+        raise ValueError(f"i_aer = {i_aer} outside the model's {nAer} aerosols")
+    pol, μ, M = model.params.polarization_type, model.quad_points.qp_μ, model.params.max_m
+    if len(d_optics.greek_coefs.β) != len(model.aerosol_optics[i_aer].greek_coefs.β):
+        raise ValueError("the derivative Greek coefficients do not have the length of the aerosol's")
+    N = pol.n * len(μ)
+    dZpp, dZmp = np.zeros((M, 1 + nAer, N, N)), np.zeros((M, 1 + nAer, N, N))
+    for m in range(M):
+        dZpp[m, 1 + i_aer], dZmp[m, 1 + i_aer] = rt.compute_Z_moments(pol, μ, d_optics.greek_coefs, m)[:2]
+    dω̃, dfᵗ = np.zeros(nAer), np.zeros(nAer)
+    dω̃[i_aer], dfᵗ[i_aer] = d_optics.ω̃, d_optics.fᵗ
+    return rt.OpticsPartial(dτ_aer=None if dτ_aer is None else np.asarray(dτ_aer, dtype=np.float64), dω̃=dω̃, dfᵗ=dfᵗ, dZpp=dZpp, dZmp=dZmp)
