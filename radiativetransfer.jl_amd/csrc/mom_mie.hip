@@ -44,12 +44,16 @@ constexpr int kMaxChunks = 128;  // radius chunks of (b): beyond 2048 radii a wa
 // order and the rounding of every operation are part of the result (tests/mie_oracle.py performs the same operations).
 // DUAL: also D' = dD/dm (two more [n_max, ld] planes), c a', c b' (four more planes) and the d/dn_r, d/dn_i forms of the two
 // cross-section sums (dsum [4, ld]: sca, ext for n_r, then for n_i).  The value statements are the same in both forms.
+// sin x and cos x, the start values psi_0, psi_1 of the upward recurrence, come from the host (mie_sin_cos): psi_1 = sin x / x - cos x
+// cancels to x^2 / 3 and the recurrence above x magnifies what is left of a last-bit error further, so they have to be as good
+// as Float64 allows; the device's sin and cos miss the correctly rounded value in a good third of the arguments.
 struct MieDualOut {
   double *Dre, *Dim, *aR, *aI, *bR, *bI, *sum;
 };
 
 template <bool SCALE, bool DUAL>
-__global__ void __launch_bounds__(64) k_mie_ab(int nR, int ld, const double *__restrict__ x, const int *__restrict__ nmax,
+__global__ void __launch_bounds__(64) k_mie_ab(int nR, int ld, const double *__restrict__ x, const double *__restrict__ sinx,
+                                               const double *__restrict__ cosx, const int *__restrict__ nmax,
                                                const int *__restrict__ nmx, double mr, double mi, double *__restrict__ Dre,
                                                double *__restrict__ Dim, double *__restrict__ aR, double *__restrict__ aI,
                                                double *__restrict__ bR, double *__restrict__ bI, double *__restrict__ ssca,
@@ -90,7 +94,7 @@ __global__ void __launch_bounds__(64) k_mie_ab(int nR, int ld, const double *__r
     }
   }
   const double m2 = mr * mr + mi * mi;
-  double psi0 = cos(xi), psi1 = sin(xi), chi0 = -psi1, chi1 = psi0;
+  double psi0 = cosx[i], psi1 = sinx[i], chi0 = -psi1, chi1 = psi0;
   double sca = 0.0, ext = 0.0;
   [[maybe_unused]] double dsca_r = 0.0, dext_r = 0.0, dsca_i = 0.0, dext_i = 0.0;
   for (int n = 1; n <= nm; ++n) {
@@ -351,6 +355,16 @@ int mie_nmx(double x, int nmax, double n_r, double n_i) {
   return (int)std::nearbyint(std::fmax((double)nmax, std::fabs(x * (n_r - n_i))) + 51.0);
 }
 
+// sin x | cos x for k_mie_ab, [2, n]: the host library's, which rounds correctly in all but a few arguments in a thousand
+std::vector<double> mie_sin_cos(const double *x, int n, size_t ld) {
+  std::vector<double> sc(2 * ld, 0.0);
+  for (int i = 0; i < n; ++i) {
+    sc[i] = std::sin(x[i]);
+    sc[ld + i] = std::cos(x[i]);
+  }
+  return sc;
+}
+
 int mie_device(const char *fn, int device) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -427,12 +441,13 @@ int mie_nai2_run(const char *fn, bool dual, int device, int nR, const double *r,
   const size_t nTab = Kp * nMuP, nPl = Kp * nRp, nD = (size_t)n_max * nRp, nLeg = (size_t)l_max * n_mu;
   const size_t nPart = (size_t)G * nO * 4 * nMuP, nBulk = (size_t)nO * 4 * n_mu, nGreek = (size_t)nO * 6 * l_max;
   const size_t doubles =
-      2 * nTab + nPlanes * nPl + nDp * nD + (1 + nSum) * nRp + (size_t)nW * nRp + n_mu + 4 * nLeg + nPart + nBulk + nGreek;
+      2 * nTab + nPlanes * nPl + nDp * nD + (3 + nSum) * nRp + (size_t)nW * nRp + n_mu + 4 * nLeg + nPart + nBulk + nGreek;
   const size_t bytes = doubles * sizeof(double) + 2 * nRp * sizeof(int);
   char *base = nullptr;
   hipStream_t st = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   std::vector<double> hs(nSum * nRp);
+  const std::vector<double> hsc = mie_sin_cos(hx.data(), nR, nRp);
   MCHK(hipSetDevice(device));
   MCHK(hipStreamCreate(&st));
   MCHK(hipMalloc((void **)&base, bytes));
@@ -445,6 +460,7 @@ int mie_nai2_run(const char *fn, bool dual, int device, int nR, const double *r,
     double *d_D[4] = {nullptr, nullptr, nullptr, nullptr};  // D re, im; Dual: D' re, im
     for (int q = 0; q < nDp; ++q) { d_D[q] = p; p += nD; }
     double *d_x = p; p += nRp;
+    double *d_sc = p; p += 2 * nRp;  // sin x | cos x
     // sum (2n+1)(|a|^2 + |b|^2) | sum (2n+1) Re(a + b); Dual: their d/dn_r forms, then their d/dn_i forms
     double *d_ss = p; p += nSum * nRp;
     double *d_w = p; p += (size_t)nW * nRp;
@@ -461,6 +477,7 @@ int mie_nai2_run(const char *fn, bool dual, int device, int nR, const double *r,
     MCHK(hipMemcpy2DAsync(d_pi, nMuP * sizeof(double), pi_tab, (size_t)n_mu * sizeof(double), (size_t)n_mu * sizeof(double), n_max,
                           hipMemcpyHostToDevice, st));
     MCHK(hipMemcpyAsync(d_x, hx.data(), nRp * sizeof(double), hipMemcpyHostToDevice, st));
+    MCHK(hipMemcpyAsync(d_sc, hsc.data(), 2 * nRp * sizeof(double), hipMemcpyHostToDevice, st));
     MCHK(hipMemcpyAsync(d_n, hn.data(), 2 * nRp * sizeof(int), hipMemcpyHostToDevice, st));
     MCHK(hipMemcpy2DAsync(d_w, nRp * sizeof(double), w, (size_t)nR * sizeof(double), (size_t)nR * sizeof(double), nW,
                           hipMemcpyHostToDevice, st));
@@ -472,10 +489,10 @@ int mie_nai2_run(const char *fn, bool dual, int device, int nR, const double *r,
     {
       const MieDualOut dd = {d_D[2], d_D[3], d_pl[4], d_pl[5], d_pl[6], d_pl[7], dual ? d_ss + 2 * nRp : nullptr};
       if (dual)
-        hipLaunchKernelGGL((k_mie_ab<true, true>), dim3((nR + 63) / 64), dim3(64), 0, st, nR, (int)nRp, d_x, d_n, d_n + nRp, n_r, n_i, d_D[0],
+        hipLaunchKernelGGL((k_mie_ab<true, true>), dim3((nR + 63) / 64), dim3(64), 0, st, nR, (int)nRp, d_x, d_sc, d_sc + nRp, d_n, d_n + nRp, n_r, n_i, d_D[0],
                            d_D[1], d_pl[0], d_pl[1], d_pl[2], d_pl[3], d_ss, d_ss + nRp, dd);
       else
-        hipLaunchKernelGGL((k_mie_ab<true, false>), dim3((nR + 63) / 64), dim3(64), 0, st, nR, (int)nRp, d_x, d_n, d_n + nRp, n_r, n_i, d_D[0],
+        hipLaunchKernelGGL((k_mie_ab<true, false>), dim3((nR + 63) / 64), dim3(64), 0, st, nR, (int)nRp, d_x, d_sc, d_sc + nRp, d_n, d_n + nRp, n_r, n_i, d_D[0],
                            d_D[1], d_pl[0], d_pl[1], d_pl[2], d_pl[3], d_ss, d_ss + nRp, dd);
     }
     MCHK(hipGetLastError());
@@ -550,7 +567,8 @@ int mie_coefficients_run(const char *fn, bool dual, int device, int nX, const do
   if (rc != MOM_OK) return rc;
   const size_t nPl = (size_t)n_max * nX;
   const int nOut = dual ? 8 : 4, nDp = dual ? 4 : 2;  // planes a, b (Dual: a', b'), then D (Dual: D')
-  const size_t bytes = ((nOut + nDp) * nPl + nX) * sizeof(double) + 2 * (size_t)nX * sizeof(int);
+  const size_t bytes = ((nOut + nDp) * nPl + 3 * (size_t)nX) * sizeof(double) + 2 * (size_t)nX * sizeof(int);
+  const std::vector<double> hsc = mie_sin_cos(x, nX, (size_t)nX);
   char *base = nullptr;
   hipStream_t st = nullptr;
   MCHK(hipSetDevice(device));
@@ -558,17 +576,19 @@ int mie_coefficients_run(const char *fn, bool dual, int device, int nX, const do
   MCHK(hipMalloc((void **)&base, bytes));
   {
     double *d_pl = (double *)base, *d_D = d_pl + nOut * nPl, *d_x = d_D + nDp * nPl;
-    int *d_n = (int *)(d_x + nX);
+    double *d_sc = d_x + nX;  // sin x | cos x
+    int *d_n = (int *)(d_sc + 2 * (size_t)nX);
     MCHK(hipMemsetAsync(base, 0, bytes, st));
     MCHK(hipMemcpyAsync(d_x, x, (size_t)nX * sizeof(double), hipMemcpyHostToDevice, st));
+    MCHK(hipMemcpyAsync(d_sc, hsc.data(), 2 * (size_t)nX * sizeof(double), hipMemcpyHostToDevice, st));
     MCHK(hipMemcpyAsync(d_n, hn.data(), 2 * (size_t)nX * sizeof(int), hipMemcpyHostToDevice, st));
     if (dual) {
       const MieDualOut dd = {d_D + 2 * nPl, d_D + 3 * nPl, d_pl + 4 * nPl, d_pl + 5 * nPl, d_pl + 6 * nPl, d_pl + 7 * nPl, nullptr};
-      hipLaunchKernelGGL((k_mie_ab<false, true>), dim3((nX + 63) / 64), dim3(64), 0, st, nX, nX, d_x, d_n, d_n + nX, n_r, n_i, d_D, d_D + nPl,
+      hipLaunchKernelGGL((k_mie_ab<false, true>), dim3((nX + 63) / 64), dim3(64), 0, st, nX, nX, d_x, d_sc, d_sc + nX, d_n, d_n + nX, n_r, n_i, d_D, d_D + nPl,
                          d_pl, d_pl + nPl, d_pl + 2 * nPl, d_pl + 3 * nPl, (double *)nullptr, (double *)nullptr, dd);
     } else {
       const MieDualOut dd = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-      hipLaunchKernelGGL((k_mie_ab<false, false>), dim3((nX + 63) / 64), dim3(64), 0, st, nX, nX, d_x, d_n, d_n + nX, n_r, n_i, d_D, d_D + nPl,
+      hipLaunchKernelGGL((k_mie_ab<false, false>), dim3((nX + 63) / 64), dim3(64), 0, st, nX, nX, d_x, d_sc, d_sc + nX, d_n, d_n + nX, n_r, n_i, d_D, d_D + nPl,
                          d_pl, d_pl + nPl, d_pl + 2 * nPl, d_pl + 3 * nPl, (double *)nullptr, (double *)nullptr, dd);
     }
     MCHK(hipGetLastError());

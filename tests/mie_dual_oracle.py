@@ -112,19 +112,25 @@ def mie_ab_dual(x, n_r, n_i, dtype=np.float64, n_rows=None):
     return out[0], out[1], out[2], out[3], nmax
 
 
-def nai2_sums_dual(r, wx, lam, n_r, n_i):
-    """mie_oracle.nai2_sums for ONE weight row wx with Duals: the value entries of nai2_sums (row 0) and d_bulk_f [2, 4, n_mu],
-    d_C [2, 2], d_greek [2, 6, l_max]: the partials (d/dn_r, d/dn_i) of row 0's sums."""
+def nai2_sums_dual(r, wx, lam, n_r, n_i, *, mu=None, w_mu=None, n_rows=None, l_max=None):
+    """mie_oracle.nai2_sums with Duals, with its keyword arguments: the value entries of nai2_sums for the weight rows wx (one row,
+    or up to 3 as the device call takes), and d_bulk_f [2, 4, n_mu], d_C [2, 2], d_greek [2, 6, l_max]: the partials
+    (d/dn_r, d/dn_i) of row 0's sums."""
     dt = r.dtype.type
-    wx = np.asarray(wx, dtype=r.dtype).reshape(1, -1)
+    wx = np.atleast_2d(np.asarray(wx, dtype=r.dtype))
+    assert 1 <= wx.shape[0] <= 3
     k = 2 * mo.pi_of(dt) / dt(lam)
     x = k * r
-    ar, ai, br, bi, nmax = mie_ab_dual(x, n_r, n_i, dt)
     n_top = int(mo.n_max_of(np.max(x).astype(np.float64)))
-    assert n_top == ar.v.shape[0]
-    mu, w_mu = mo.gausslegendre(2 * n_top - 1, dt)
-    p, t = mo.mie_pi_tau(mu, n_top)
-    l = np.arange(1, n_top + 1).astype(dt)
+    rows = n_top if n_rows is None else int(n_rows)
+    ar, ai, br, bi, nmax = mie_ab_dual(x, n_r, n_i, dt, n_rows=rows)
+    assert rows >= n_top and rows == ar.v.shape[0]
+    if mu is None:
+        assert w_mu is None
+        mu, w_mu = mo.gausslegendre(2 * n_top - 1, dt)
+    assert mu.dtype == r.dtype and w_mu.dtype == r.dtype and mu.shape == w_mu.shape
+    p, t = mo.mie_pi_tau(mu, rows)
+    l = np.arange(1, rows + 1).astype(dt)
     c = ((2 * l + 1) / (l * (l + 1)))[:, None]
     a, b = c * (ar.v + 1j * ai.v), c * (br.v + 1j * bi.v)
     S1, S2 = t @ a + p @ b, p @ a + t @ b          # [n_mu, nR]
@@ -151,7 +157,7 @@ def nai2_sums_dual(r, wx, lam, n_r, n_i):
     wr = 4 * mo.pi_of(dt) * r * r * wx
     bulk = np.einsum("fmi,ki->kfm", f, wr)
     d_bulk = np.einsum("cfmi,i->cfm", df, wr[0])
-    l_max = mu.size
+    l_max = mu.size if l_max is None else int(l_max)
     P, P2, R2, T2 = mo.legendre_tables(mu, l_max)
     ll = np.arange(l_max).astype(dt)
     pre = (2 * ll + 1) / 2
@@ -163,8 +169,9 @@ def nai2_sums_dual(r, wx, lam, n_r, n_i):
         return [fac * (f11 @ R2 + f33 @ T2), pre * (f11 @ P), fac * (f12 @ P2), pre * (f33 @ P), fac * (f34 @ P2),
                 fac * (f33 @ R2 + f11 @ T2)]
 
-    greek = np.zeros((1, 6, l_max), dt)
-    greek[0] = project(bulk[0])
+    greek = np.zeros((wx.shape[0], 6, l_max), dt)
+    for kk in range(wx.shape[0]):
+        greek[kk] = project(bulk[kk])
     d_greek = np.zeros((2, 6, l_max), dt)
     for cc in range(2):
         d_greek[cc] = project(d_bulk[cc])

@@ -2,7 +2,8 @@
 (src/Scattering/compute_NAI2.jl:16-182, mie_helper_functions.jl:17-71, 154-182, 266-276, legendre_functions.jl:188-259) that takes a
 dtype, so that the same text runs in np.float64 and in np.longdouble (x87 extended precision: the arbiter between the Float64
 oracle and the device, the role oracle/momref_ext.c has for the RT core), and an independent route to a_n, b_n through
-Bohren & Huffman eq. 4.53 with Bessel functions of half-integer order from scipy.
+Bohren & Huffman eq. 4.53 with Bessel functions of half-integer order from scipy, and from mpmath where Float64 Bessel functions no
+longer arbitrate (x up to 343.7).  nai2_sums takes the shapes the reference ties together (n_mu, table rows, l_max) as free arguments.
 
 Nothing here is imported by the product; the tests feed both sides the same physical parameters."""
 import numpy as np
@@ -127,6 +128,30 @@ def mie_ab_bessel(x, m, n_max):
     return a, b
 
 
+def mie_ab_mp(x, m, n_max, dps=60):
+    """a_n, b_n, n = 1..n_max, by Bohren & Huffman eq. 4.53 in mpmath at `dps` digits: psi_n, chi_n and xi_n = psi_n - i chi_n from
+    mpmath's besselj / bessely of order n + 1/2, no recurrence over n anywhere but in the derivative f_n' = f_{n-1} - n f_n / z.
+    x (a Float64) and m (a complex128) are taken exactly.  The arbiter of mie_ab where scipy's Float64 Bessel functions are not
+    (large x): it shares nothing with mie_ab and nothing with Float64 arithmetic.  -> complex128 arrays a, b [n_max]"""
+    import mpmath as mp
+    with mp.workdps(dps):
+        xx, mm = mp.mpf(float(x)), mp.mpc(complex(m))
+        zz = mm * xx
+        half = mp.mpf(1) / 2
+        root_x, root_z = mp.sqrt(mp.pi * xx / 2), mp.sqrt(mp.pi * zz / 2)
+        psi_x = [root_x * mp.besselj(n + half, xx) for n in range(n_max + 1)]
+        xi_x = [psi_x[n] + mp.j * (root_x * mp.bessely(n + half, xx)) for n in range(n_max + 1)]      # chi_n = -sqrt(.) Y
+        psi_z = [root_z * mp.besselj(n + half, zz) for n in range(n_max + 1)]
+        a, b = [], []
+        for n in range(1, n_max + 1):
+            d_psi_x = psi_x[n - 1] - n * psi_x[n] / xx
+            d_xi_x = xi_x[n - 1] - n * xi_x[n] / xx
+            d_psi_z = psi_z[n - 1] - n * psi_z[n] / zz
+            a.append(complex((mm * psi_z[n] * d_psi_x - psi_x[n] * d_psi_z) / (mm * psi_z[n] * d_xi_x - xi_x[n] * d_psi_z)))
+            b.append(complex((psi_z[n] * d_psi_x - mm * psi_x[n] * d_psi_z) / (psi_z[n] * d_xi_x - mm * xi_x[n] * d_psi_z)))
+    return np.array(a), np.array(b)
+
+
 def mie_pi_tau(mu, nmax):
     """compute_mie_pi_tau -> pi, tau [n_mu, nmax]"""
     p, t = np.zeros((mu.size, nmax), mu.dtype), np.zeros((mu.size, nmax), mu.dtype)
@@ -143,7 +168,8 @@ def legendre_tables(x, nmax):
     dt = x.dtype.type
     P, P2, R2, T2 = (np.zeros((x.size, nmax), x.dtype) for _ in range(4))
     P[:, 0] = 1
-    P[:, 1] = x
+    if nmax > 1:
+        P[:, 1] = x
     if nmax > 2:
         P2[:, 2] = 3 * (1 - x * x)
         R2[:, 2] = np.sqrt(dt(3) / 2) * (1 + x * x)
@@ -176,20 +202,27 @@ def weights_wx(r, wr, r_m, sigma_g):
     return w / w.sum()
 
 
-def nai2_sums(r, wx_rows, lam, n_r, n_i):
+def nai2_sums(r, wx_rows, lam, n_r, n_i, *, mu=None, w_mu=None, n_rows=None, l_max=None):
     """The sums of compute_aerosol_optical_properties for the radii r and the rows of w_x (row 0 the weights themselves, further
     rows their partials), in the dtype of r, none divided by the bulk C_sca:
-       bulk_f [nW, 4, n_mu] (f11, f33, f12, f34), C [nW, 2] (C_sca, C_ext), greek [nW, 6, l_max] (alpha .. zeta), mu, w_mu"""
+       bulk_f [nW, 4, n_mu] (f11, f33, f12, f34), C [nW, 2] (C_sca, C_ext), greek [nW, 6, l_max] (alpha .. zeta), mu, w_mu
+    The reference ties every shape to n_top, the n_max of the largest radius; the device call does not, so neither does this:
+    mu, w_mu: nodes and weights of any length (default: the Gauss rule of 2 n_top - 1 nodes); n_rows >= n_top: rows of the pi / tau
+    tables and of the coefficient planes (default n_top; the further rows multiply exact zeros); l_max: default n_mu."""
     dt = r.dtype.type
     wx_rows = np.atleast_2d(wx_rows)
     k = 2 * pi_of(dt) / dt(lam)
     x = k * r
-    ar, ai, br, bi, nmax = mie_ab(x, n_r, n_i, dt)
     n_top = int(n_max_of(np.max(x).astype(np.float64)))
-    assert n_top == ar.shape[0]
-    mu, w_mu = gausslegendre(2 * n_top - 1, dt)
-    p, t = mie_pi_tau(mu, n_top)
-    l = np.arange(1, n_top + 1).astype(dt)
+    rows = n_top if n_rows is None else int(n_rows)
+    ar, ai, br, bi, nmax = mie_ab(x, n_r, n_i, dt, n_rows=rows)
+    assert rows >= n_top and rows == ar.shape[0]
+    if mu is None:
+        assert w_mu is None
+        mu, w_mu = gausslegendre(2 * n_top - 1, dt)
+    assert mu.dtype == r.dtype and w_mu.dtype == r.dtype and mu.shape == w_mu.shape
+    p, t = mie_pi_tau(mu, rows)
+    l = np.arange(1, rows + 1).astype(dt)
     c = ((2 * l + 1) / (l * (l + 1)))[:, None]
     a, b = c * (ar + 1j * ai), c * (br + 1j * bi)
     S1, S2 = t @ a + p @ b, p @ a + t @ b          # [n_mu, nR]
@@ -202,7 +235,7 @@ def nai2_sums(r, wx_rows, lam, n_r, n_i):
     C = np.stack([wx_rows @ C_sca, wx_rows @ C_ext], axis=1)
     wr = 4 * pi_of(dt) * r * r * wx_rows
     bulk = np.einsum("fmi,ki->kfm", f, wr)
-    l_max = mu.size
+    l_max = mu.size if l_max is None else int(l_max)
     P, P2, R2, T2 = legendre_tables(mu, l_max)
     ll = np.arange(l_max).astype(dt)
     pre = (2 * ll + 1) / 2
