@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """The Mie / NAI-2 aerosol optics (csrc/mom_mie.hip) as a benchmark; prints one JSON line, `bench_mie.py OUT.json` also writes it
 (committed as profiles/mie_bench.json).  `bench_mie.py --dual OUT.json`: the Dual run with respect to all four aerosol
-parameters beside the value call in the same process (committed as profiles/mie_dual_bench.json).
+parameters beside the value call in the same process (committed as profiles/mie_dual_bench.json).  `bench_mie.py --spectral
+OUT.json`: 16 wavelengths in one call (mom_mie_nai2_spectral) beside 16 single calls (committed as
+profiles/mie_spectral_bench.json).
 
 Two points: the reference's own test point (test/test_Scattering.jl: λ = 0.55 µm, r_max = 30 µm, nquad_radius = 2500,
 m = 1.3 + 0.001i, LogNormal(log 0.3, log 6.82): x_max = 342.7, n_max = 381, n_μ = 761) and a small one (r_max = 1 µm, 37 radii:
@@ -112,6 +114,55 @@ def run_dual_point(p, repeats=7):
                                                                   "unit": "TFLOP/s", "frac": tf / PEAK_FP64_MFMA_TFLOPS}}}
 
 
+def run_spectral_point(p, lam, repeats=5):
+    """nL wavelengths at the point's radii in one spectral call: the HIP-event times of the four kernel groups (tables;
+    coefficients; amplitude GEMM with reduction; projection) and the wall time of the device call, best of `repeats`; then the
+    wall time of compute_spectral_aerosol_optical_properties beside nL calls of compute_aerosol_optical_properties in the same
+    process (both after a first call that loads the code objects), median of three."""
+    import rtamd
+    sc = rtamd.scattering
+    aer = sc.Aerosol(sc.LogNormal(math.log(p["r_m"]), math.log(p["sigma_g"])), p["n_r"], p["n_i"])
+    model = sc.make_mie_model(sc.NAI2(), aer, p["lam"], None, None, p["r_max"], p["nquad_radius"])
+    lam = np.asarray(lam, dtype=np.float64)
+    n_r, n_i = np.full(lam.size, p["n_r"]), np.full(lam.size, p["n_i"])
+    t0 = time.perf_counter()
+    inp = sc.spectral_mie_inputs(model, lam)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    best, call = np.full(4, 1e30), 1e30
+    for _ in range(repeats + 1):
+        t0 = time.perf_counter()
+        ms = rtamd._lib.mie_nai2_spectral(inp.r, inp.w, lam, n_r, n_i, inp.μ, inp.w_μ, inp.n_top, inp.l_max)[3]
+        call = min(call, (time.perf_counter() - t0) * 1e3)
+        best = np.minimum(best, ms)
+    models = [sc.make_mie_model(sc.NAI2(), aer, l, None, None, p["r_max"], p["nquad_radius"]) for l in lam]
+    sc.compute_aerosol_optical_properties(models[0])
+    batch, singles = [], []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        sc.compute_spectral_aerosol_optical_properties(model, lam)
+        batch.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        for m in models:
+            sc.compute_aerosol_optical_properties(m)
+        singles.append((time.perf_counter() - t0) * 1e3)
+    return {"n_wavelengths": int(lam.size), "wavelengths_um": [float(l) for l in lam], "n_radii": int(inp.r.size),
+            "n_mu": int(inp.μ.size), "n_max": [int(v) for v in inp.n_max], "repeats": repeats,
+            "kernels_ms": {"tables": float(best[0]), "coefficients": float(best[1]), "amplitude_gemm_and_reduction": float(best[2]),
+                           "projection": float(best[3]), "sum": float(best.sum())},
+            "device_call_wall_ms": call, "host_inputs_ms": host_ms,
+            "compute_spectral_aerosol_optical_properties_wall_ms": {"median": float(np.median(batch)), "all": batch},
+            "single_calls_wall_ms": {"median": float(np.median(singles)), "all": singles, "calls": int(lam.size)},
+            "speedup_batch_over_single_calls": float(np.median(singles) / np.median(batch))}
+
+
+def run_spectral():
+    out = {"metric": "Mie NAI-2 aerosol optics, 16 wavelengths (0.4 .. 2.2 µm) in one spectral call: wall time of the public call",
+           "unit": "ms"}
+    out["reference_test_point"] = run_spectral_point(POINTS["reference_test_point"], np.linspace(0.4, 2.2, 16))
+    out["value"] = out["reference_test_point"]["compute_spectral_aerosol_optical_properties_wall_ms"]["median"]
+    return out
+
+
 def run():
     out = {"metric": "Mie NAI-2 aerosol optics, kernels of one call", "unit": "ms"}
     for name, p in POINTS.items():
@@ -129,8 +180,8 @@ def run_dual():
 
 
 if __name__ == "__main__":
-    argv = [a for a in sys.argv[1:] if a != "--dual"]
-    res = run_dual() if "--dual" in sys.argv[1:] else run()
+    argv = [a for a in sys.argv[1:] if a not in ("--dual", "--spectral")]
+    res = run_dual() if "--dual" in sys.argv[1:] else (run_spectral() if "--spectral" in sys.argv[1:] else run())
     if argv:
         Path(argv[0]).parent.mkdir(parents=True, exist_ok=True)
         Path(argv[0]).write_text(json.dumps(res, indent=1, ensure_ascii=False) + "\n")

@@ -752,6 +752,36 @@ int mom_mie_nai2_dual(int device, int nR, const double *r, int nW, const double 
 int mom_mie_coefficients_dual(int device, int nX, const double *x, double n_r, double n_i, int n_max, double *a_re, double *a_im,
                               double *b_re, double *b_im, double *da_re, double *da_im, double *db_re, double *db_im);
 
+/* The angle tables of mom_mie_nai2 built on the device from the nodes mu [n_mu], one lane per mu, serial over the order:
+ *   pi_tab, tau_tab         [n_max, n_mu], mu fastest (compute_mie_pi_tau)
+ *   P, P2, R2, T2           [l_max, n_mu], mu fastest (compute_legendre_poly)
+ * The kernel performs the statements of the host's recurrences in their order, without contraction: the tables are bitwise those
+ * the host builds.  Test access, and of use on its own.  MOM_EINVAL: n_mu, n_max or l_max < 1, a null pointer. */
+int mom_mie_tables(int device, int n_mu, const double *mu, int n_max, int l_max, double *pi_tab, double *tau_tab, double *P,
+                   double *P2, double *R2, double *T2);
+
+/* mom_mie_nai2 for a batch of nL wavelengths lambda [nL], each with its own refractive index n_r [nL] + i n_i [nL], in one call.
+ * Radii and weight rows are shared (w = 4 pi r^2 w_x does not depend on lambda), and so is ONE angle grid mu, w_mu [n_mu], which
+ * the caller sizes for the shortest wavelength; the tables are built on the device from mu (mom_mie_tables), none is uploaded.
+ * n_max is the row count of the pi / tau tables, at least the largest per-radius n_max,i over all wavelengths: a longer
+ * wavelength runs with spare table rows.  Outputs, wavelength slowest:
+ *   bulk_f [nL, nW, 4, n_mu], C [nL, nW, 2], greek [nL, nW, 6, l_max]
+ *   gpu_ms [4] or NULL      HIP-event times (ms): tables, coefficient kernel, amplitude GEMM with its reduction, projection
+ * The wavelength is one more grid dimension of the kernels of mom_mie_nai2, and each wavelength keeps the single call's radius
+ * chunks, tile walk and reduction order: its rows are bitwise those of mom_mie_nai2 on the same grid and tables, whatever else is
+ * in the batch.  max_batch = 0 runs sub-batches of consecutive wavelengths sized to a workspace of 2 GiB; max_batch > 0 caps the
+ * sub-batch (test access).  flags as for mom_mie_nai2.
+ * MOM_EINVAL: the list of mom_mie_nai2, per wavelength (the message names the wavelength's index), and nL < 1, max_batch < 0. */
+int mom_mie_nai2_spectral(int device, int nR, const double *r, int nW, const double *w, int nL, const double *lambda,
+                          const double *n_r, const double *n_i, int n_mu, const double *mu, const double *w_mu, int n_max,
+                          int l_max, int flags, int max_batch, double *bulk_f, double *C, double *greek, double *gpu_ms);
+
+/* The Dual run of mom_mie_nai2_spectral: 1 <= nW <= 3 and nO = nW + 2 rows per wavelength, the last two d/dn_r and d/dn_i of row
+ * 0's sums as in mom_mie_nai2_dual: bulk_f [nL, nO, 4, n_mu], C [nL, nO, 2], greek [nL, nO, 6, l_max]. */
+int mom_mie_nai2_spectral_dual(int device, int nR, const double *r, int nW, const double *w, int nL, const double *lambda,
+                               const double *n_r, const double *n_i, int n_mu, const double *mu, const double *w_mu, int n_max,
+                               int l_max, int flags, int max_batch, double *bulk_f, double *C, double *greek, double *gpu_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -520,4 +520,34 @@ function mie_nai2_dual(arch::MI355X, r, w_rows, λ, nᵣ, nᵢ, w_μ, leg_π, le
     end
     return value, partials, ms
 end
+
+"""
+A batch of wavelengths `λ` [nL], each with its own refractive index `nᵣ`, `nᵢ` [nL], in ONE call: radii and weight rows are shared,
+and so is one angle grid `μ`, `w_μ` (sized by the caller for the shortest wavelength, `n_max` = its largest per-radius n_max).  The
+π/τ and P/P²/R²/T² tables are built on the device from `μ`; the host brings none.  Returns (bulk_f [n_μ, 4, nW, nL], C [2, nW, nL],
+greek [l_max, 6, nW, nL], ms [4]), unnormalised as the device returns them: the division by C_sca is that of `mie_nai2`, per wavelength.
+"""
+function mie_nai2_spectral(arch::MI355X, r, w_rows, λ, nᵣ, nᵢ, μ, w_μ, n_max, l_max; max_batch = 0)
+    nR, nW, nL, n_μ = size(w_rows, 1), size(w_rows, 2), length(λ), length(μ)
+    w = collect(Float64, (4π .* r .^ 2) .* w_rows)
+    bulk_f = zeros(Float64, n_μ, 4, nW, nL);  C = zeros(Float64, 2, nW, nL);  greek = zeros(Float64, l_max, 6, nW, nL);  ms = zeros(Float64, 4)
+    momcheck(MomCore.mom_mie_nai2_spectral(arch.device, nR, collect(Float64, r), nW, w, nL, collect(Float64, λ), collect(Float64, nᵣ),
+                                           collect(Float64, nᵢ), n_μ, collect(Float64, μ), collect(Float64, w_μ), n_max, l_max, 0,
+                                           max_batch, bulk_f, C, greek, ms))
+    return bulk_f, C, greek, ms
+end
+
+"""
+The Dual run of `mie_nai2_spectral` (at most 3 columns of `w_rows`): nW + 2 rows per wavelength, the last two ∂/∂nᵣ and ∂/∂nᵢ of
+column 1's sums, as `mie_nai2_dual` has them.
+"""
+function mie_nai2_spectral_dual(arch::MI355X, r, w_rows, λ, nᵣ, nᵢ, μ, w_μ, n_max, l_max; max_batch = 0)
+    nR, nW, nL, n_μ = size(w_rows, 1), size(w_rows, 2), length(λ), length(μ);  nO = nW + Int(MomCore.MOM_MIE_INDEX_ROWS)
+    w = collect(Float64, (4π .* r .^ 2) .* w_rows)
+    bulk_f = zeros(Float64, n_μ, 4, nO, nL);  C = zeros(Float64, 2, nO, nL);  greek = zeros(Float64, l_max, 6, nO, nL);  ms = zeros(Float64, 4)
+    momcheck(MomCore.mom_mie_nai2_spectral_dual(arch.device, nR, collect(Float64, r), nW, w, nL, collect(Float64, λ), collect(Float64, nᵣ),
+                                                collect(Float64, nᵢ), n_μ, collect(Float64, μ), collect(Float64, w_μ), n_max, l_max, 0,
+                                                max_batch, bulk_f, C, greek, ms))
+    return bulk_f, C, greek, ms
+end
 # <<< mie

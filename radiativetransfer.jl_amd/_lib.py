@@ -159,6 +159,11 @@ SIGNATURES = {
     "mom_mie_nai2_dual": (C.c_int, [C.c_int, C.c_int, c_dp, C.c_int, c_dp, C.c_double, C.c_double, C.c_double, C.c_int, c_dp, C.c_int,
                                     c_dp, c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp, C.c_int, c_dp, c_dp, c_dp, c_dp]),
     "mom_mie_coefficients_dual": (C.c_int, [C.c_int, C.c_int, c_dp, C.c_double, C.c_double, C.c_int] + [c_dp] * 8),
+    "mom_mie_tables": (C.c_int, [C.c_int, C.c_int, c_dp, C.c_int, C.c_int] + [c_dp] * 6),
+    "mom_mie_nai2_spectral": (C.c_int, [C.c_int, C.c_int, c_dp, C.c_int, c_dp, C.c_int, c_dp, c_dp, c_dp, C.c_int, c_dp, c_dp, C.c_int,
+                                        C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp]),
+    "mom_mie_nai2_spectral_dual": (C.c_int, [C.c_int, C.c_int, c_dp, C.c_int, c_dp, C.c_int, c_dp, c_dp, c_dp, C.c_int, c_dp, c_dp,
+                                             C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp]),
 }
 
 _lib = None
@@ -877,3 +882,48 @@ def mie_coefficients_dual(x, n_r, n_i, n_max: int, device: int = 0):
     if rc != MOM_OK:
         raise MomError(rc, lib.mom_last_global_error().decode())
     return out[0] + 1j * out[1], out[2] + 1j * out[3], out[4] + 1j * out[5], out[6] + 1j * out[7]
+
+
+def mie_tables(mu, n_max: int, l_max: int, device: int = 0):
+    """mom_mie_tables: (pi, tau [n_mu, n_max], P, P2, R2, T2 [n_mu, l_max]) of the nodes mu, built on the device, in the orientation
+    numpy builds them in (scattering.compute_mie_π_τ, compute_legendre_poly): the transposes of the ABI's mu-fastest layout, so they
+    go into mie_nai2 as they are."""
+    lib = load()
+    mu = f64(np.atleast_1d(mu))
+    n_mu, n_max, l_max = len(mu), int(n_max), int(l_max)
+    out = [np.empty((max(n_max, 0), n_mu)) for _ in range(2)] + [np.empty((max(l_max, 0), n_mu)) for _ in range(4)]
+    rc = lib.mom_mie_tables(device, n_mu, dp(mu), n_max, l_max, *[dp(o) for o in out])
+    if rc != MOM_OK:
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return tuple(o.T for o in out)
+
+
+def _mie_nai2_spectral(dual: bool, r, w, lam, n_r, n_i, mu, w_mu, n_max, l_max, flags, max_batch, device):
+    lib = load()
+    name = "mie_nai2_spectral_dual" if dual else "mie_nai2_spectral"
+    r, w, mu, w_mu = f64(r), f64(np.atleast_2d(w)), f64(mu), f64(w_mu)
+    lam, n_r, n_i = (f64(np.atleast_1d(a)) for a in (lam, n_r, n_i))
+    nW, nR, n_mu, nL, l_max = w.shape[0], len(r), len(w_mu), len(lam), int(l_max)
+    if w.shape[1] != nR or len(mu) != n_mu or len(n_r) != nL or len(n_i) != nL:
+        raise ValueError(f"{name}: array shapes do not agree")
+    nO = nW + MOM_MIE_INDEX_ROWS if dual else nW
+    bulk, Cx = np.empty((nL, nO, 4, n_mu)), np.empty((nL, nO, 2))
+    greek, ms = np.empty((nL, nO, 6, max(l_max, 0))), np.zeros(4)
+    fn = lib.mom_mie_nai2_spectral_dual if dual else lib.mom_mie_nai2_spectral
+    rc = fn(device, nR, dp(r), nW, dp(w), nL, dp(lam), dp(n_r), dp(n_i), n_mu, dp(mu), dp(w_mu), int(n_max), l_max, int(flags),
+            int(max_batch), dp(bulk), dp(Cx), dp(greek), dp(ms))
+    if rc != MOM_OK:
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return bulk, Cx, greek, ms
+
+
+def mie_nai2_spectral(r, w, lam, n_r, n_i, mu, w_mu, n_max: int, l_max: int, flags: int = 0, max_batch: int = 0, device: int = 0):
+    """mom_mie_nai2_spectral: mie_nai2 for the wavelengths lam [nL] with the refractive indices n_r, n_i [nL] on ONE angle grid mu,
+    w_mu, whose tables the device builds (n_max: their row count).  Returns (bulk_f [nL, nW, 4, n_mu], C [nL, nW, 2],
+    greek [nL, nW, 6, l_max], gpu_ms [4]: tables, coefficients, GEMM with reduction, projection)."""
+    return _mie_nai2_spectral(False, r, w, lam, n_r, n_i, mu, w_mu, n_max, l_max, flags, max_batch, device)
+
+
+def mie_nai2_spectral_dual(r, w, lam, n_r, n_i, mu, w_mu, n_max: int, l_max: int, flags: int = 0, max_batch: int = 0, device: int = 0):
+    """mom_mie_nai2_spectral_dual: as mie_nai2_spectral (nW <= 3) with nW + 2 rows per wavelength, the last two d/dn_r and d/dn_i"""
+    return _mie_nai2_spectral(True, r, w, lam, n_r, n_i, mu, w_mu, n_max, l_max, flags, max_batch, device)

@@ -6,6 +6,8 @@ the radius quadrature, the Gauss nodes of the scattering angle, the π/τ and P/
 over μ) -- and does the arithmetic that follows the sums: the division by the bulk C_sca and, for autodiff=True, the quotient
 rule of the partial rows.  Partials with respect to the refractive index (nᵣ, nᵢ) come from the Dual run of the same kernels
 (mom_mie_nai2_dual); truncate_phase and aerosol_optics_partial carry them on to rt_run_dual_device_optics.
+compute_spectral_aerosol_optical_properties runs a whole array of wavelengths in one device call (mom_mie_nai2_spectral) on one
+angle grid, whose tables the device builds itself (mom_mie_tables): there the host brings the nodes only.
 Float64 only; NAI2 only (no PCW).  There is no CPU fallback.
 """
 from __future__ import annotations
@@ -183,20 +185,25 @@ class MieInputs:
     T2: np.ndarray
 
 
-def mie_inputs(model: MieModel, autodiff: bool = False) -> MieInputs:
+def _radii_and_weight_rows(model: MieModel, autodiff: bool):
+    """(r, w [nW, nR]) of the model: the radius quadrature and 4π r² times wₓ (and, autodiff, its partials)"""
     aer = model.aerosol
     r, wᵣ = gauleg(model.nquad_radius, 0.0, model.r_max, norm=True)
-    n_max = int(get_n_max(np.max(2 * math.pi / model.λ * r)))
-    μ, w_μ = gausslegendre(2 * n_max - 1)
-    π_, τ_ = compute_mie_π_τ(μ, n_max)
-    P, P2, R2, T2 = compute_legendre_poly(μ, μ.size)
     # compute_wₓ (mie_helper_functions.jl:266-276): wₓ = pdf wᵣ / Σ pdf wᵣ
     p = aer.size_distribution.pdf(r) * wᵣ
     rows = [p / p.sum()]
     if autodiff:
         for dp in aer.size_distribution.dpdf(r) * wᵣ:
             rows.append(dp / p.sum() - p * dp.sum() / p.sum() ** 2)
-    w = 4 * math.pi * r ** 2 * np.stack(rows)
+    return r, 4 * math.pi * r ** 2 * np.stack(rows)
+
+
+def mie_inputs(model: MieModel, autodiff: bool = False) -> MieInputs:
+    r, w = _radii_and_weight_rows(model, autodiff)
+    n_max = int(get_n_max(np.max(2 * math.pi / model.λ * r)))
+    μ, w_μ = gausslegendre(2 * n_max - 1)
+    π_, τ_ = compute_mie_π_τ(μ, n_max)
+    P, P2, R2, T2 = compute_legendre_poly(μ, μ.size)
     return MieInputs(r, w, μ, w_μ, π_, τ_, P, P2, R2, T2)
 
 
@@ -253,6 +260,67 @@ def compute_aerosol_optical_properties(model: MieModel, autodiff: bool = False, 
         rows = (_SIZE_PARAMETERS if size_rows else ()) + _INDEX_PARAMETERS
     aero, partials = optics_from_sums(C, greek)
     return aero, [partials[rows.index(p)] for p in wrt]
+
+
+@dataclass
+class SpectralMieInputs:
+    """What mom_mie_nai2_spectral reads for a model and a set of wavelengths: no tables, the device builds them from μ."""
+    r: np.ndarray
+    w: np.ndarray         # as MieInputs.w: it does not depend on λ
+    μ: np.ndarray         # ONE grid for all wavelengths, sized for the shortest
+    w_μ: np.ndarray
+    n_max: np.ndarray     # [nL]: get_n_max at the largest radius, per wavelength
+    n_top: int            # the largest of them: the row count of the π/τ tables
+    l_max: int            # = n_μ
+
+
+def spectral_mie_inputs(model: MieModel, λ, autodiff: bool = False) -> SpectralMieInputs:
+    """r and w as mie_inputs(model) has them; the shared grid is gausslegendre(2 n_top - 1), n_top = get_n_max at the largest radius
+    and the shortest wavelength (the grid the single call takes there); l_max = n_μ.  model.λ is not read."""
+    λ = np.atleast_1d(np.asarray(λ, dtype=np.float64))
+    if λ.size < 1 or not np.all(λ > 0):
+        raise ValueError("λ must hold at least one positive wavelength")
+    r, w = _radii_and_weight_rows(model, autodiff)
+    n_max = np.array([int(get_n_max(np.max(2 * math.pi / l * r))) for l in λ])
+    n_top = int(n_max.max())
+    μ, w_μ = gausslegendre(2 * n_top - 1)
+    return SpectralMieInputs(r, w, μ, w_μ, n_max, n_top, int(μ.size))
+
+
+def compute_spectral_aerosol_optical_properties(model: MieModel, λ, nᵣ=None, nᵢ=None, autodiff: bool = False, wrt=_SIZE_PARAMETERS,
+                                                max_batch: int = 0):
+    """compute_aerosol_optical_properties at the wavelengths λ [nL] in ONE device call (mom_mie_nai2_spectral): a list of
+    AerosolOptics, one per wavelength; with autodiff=True (list, [partials of wavelength j in the order of `wrt`]).  nᵣ, nᵢ [nL] are
+    the refractive index per wavelength (default: the aerosol's constant index).  All wavelengths share the radii, the weight rows
+    and ONE angle grid, that of the shortest wavelength (spectral_mie_inputs), whose tables the device builds; each wavelength's
+    Greek coefficients are cut to the length 2 n_max(λ) - 1 the single call returns there -- what is cut off is rounding.  The Dual
+    run is taken when `wrt` names an index parameter, as in compute_aerosol_optical_properties."""
+    λ = np.atleast_1d(np.asarray(λ, dtype=np.float64))
+    aer = model.aerosol
+    nᵣ = np.full(λ.size, aer.nᵣ) if nᵣ is None else np.atleast_1d(np.asarray(nᵣ, dtype=np.float64))
+    nᵢ = np.full(λ.size, aer.nᵢ) if nᵢ is None else np.atleast_1d(np.asarray(nᵢ, dtype=np.float64))
+    if nᵣ.shape != λ.shape or nᵢ.shape != λ.shape:
+        raise ValueError("λ, nᵣ and nᵢ must have the same length")
+    if np.any(nᵢ < 0):
+        raise ValueError("the imaginary part of the refractive index must be >= 0")
+    rows, dual, size_rows = (), False, False
+    if autodiff:
+        wrt = tuple(wrt)
+        unknown = [p for p in wrt if p not in ALL_AEROSOL_PARAMETERS]
+        if unknown or len(set(wrt)) != len(wrt):
+            raise ValueError(f"wrt must be distinct names out of {ALL_AEROSOL_PARAMETERS}, got {wrt}")
+        dual = any(p in _INDEX_PARAMETERS for p in wrt)
+        size_rows = not dual or any(p in _SIZE_PARAMETERS for p in wrt)
+        rows = (_SIZE_PARAMETERS if size_rows else ()) + (_INDEX_PARAMETERS if dual else ())
+    inp = spectral_mie_inputs(model, λ, size_rows)
+    call = _lib.mie_nai2_spectral_dual if dual else _lib.mie_nai2_spectral
+    _, C, greek, _ = call(inp.r, inp.w, λ, nᵣ, nᵢ, inp.μ, inp.w_μ, inp.n_top, inp.l_max, max_batch=max_batch)
+    optics, partials = [], []
+    for j in range(λ.size):
+        aero, parts = optics_from_sums(C[j], greek[j][:, :, :2 * int(inp.n_max[j]) - 1])
+        optics.append(aero)
+        partials.append([parts[rows.index(p)] for p in wrt] if autodiff else [])
+    return (optics, partials) if autodiff else optics
 
 
 def aerosol_derivs(optics: rt.AerosolOptics, partials) -> np.ndarray:
