@@ -599,6 +599,20 @@ int mom_timers(mom_t *h, double *ms, int n, int *kernel_launches);
  *                         decisions do not depend on the option (at most the sign of a zero does).
  *   MOM_OPT_LUT_BATCH     (p, T) nodes that mom_lut_build fills per pair of launches (default 0 = 64): the per-line prefactor block
  *                         of a batch takes nodes x lines.  Nodes are independent: the table does not depend on it by a bit.
+ *   MOM_OPT_SOURCES_ONLY  1 (default) = a sweep launch of mom_rt_run that holds no observable Fourier moment leaves the composite
+ *                         operators R-+ and T++ out of its layers.  Such a launch is the (I,Q) sub-problem's (moment 0 under
+ *                         MOM_OPT_M0_REDUCTION: mom_download answers MOM_ESTATE for it) or a full-problem launch that starts at
+ *                         moment 1 or later (mom_download returns moment 0 only); and the rule exists in the two-buffer strip image
+ *                         (edges 52 / 56 / 60, csrc/mom_strip2.hpp) and the quad-block image (csrc/mom_q4.hpp) alone.  R-+ and T++
+ *                         feed nothing but themselves: the sources J0-, J0+ -- all that R, T, hdr and the BHRs are formed from --
+ *                         take from the two products one row each, J0+^T (T01 r-+)^T and J0+^T T21^T, which the launch forms on its
+ *                         own with the same matrix instructions in the same order.  After such a launch the two arrays hold the
+ *                         FIRST layer's r-+ and t++ (finite, rewritten by every run, meaningless); a unit that the 8-wave image
+ *                         finishes, and the surface kernel, go on updating the two operators from there, and nothing of them reaches
+ *                         a source, a series length or a resume decision.  mom_rt_run_multisensor, the Dual and RRS runs, the
+ *                         operator-level calls, the finishers, the surface kernel, the other images and the Float32 handles never
+ *                         take this form; with MOM_OPT_M0_REDUCTION = 0 the one launch carries moment 0 and keeps all four
+ *                         operators.  0 = every launch updates all four.  No output and no return value depends on the option.
  */
 int mom_set_option(mom_t *h, int option, int value);
 
@@ -609,7 +623,7 @@ int mom_strip2_resumed(mom_t *h, int *units, int *left);
 enum { MOM_OPT_INVERSE = 0, MOM_OPT_FORCE_GENERIC = 1, MOM_OPT_M0_REDUCTION = 2, MOM_OPT_SMALL_WG = 3, MOM_OPT_STAGGER = 4,
        MOM_OPT_SMALL_N = 5, MOM_OPT_LAYER_SWEEP = 6, MOM_OPT_STRIP_PAD = 7, MOM_OPT_LEAN = 8, MOM_OPT_OVERLAP = 9,
        MOM_OPT_RRS_KERNELS = 10, MOM_OPT_DUAL_WORKSPACE_MB = 11, MOM_OPT_STRIP2 = 12, MOM_OPT_STRIP2_SCHED = 13,
-       MOM_OPT_ZERO_SKIP = 14, MOM_OPT_LUT_BATCH = 15 };
+       MOM_OPT_ZERO_SKIP = 14, MOM_OPT_LUT_BATCH = 15, MOM_OPT_SOURCES_ONLY = 16 };
 
 /* ---- The InterpolationModel: cross sections computed once on a (nu, p, T) grid and kept on the device as a cubic B-spline
  * interpolant -- make_interpolation_model (make_model_helpers.jl:55-99) and compute_absorption_cross_section(model::InterpolationModel,

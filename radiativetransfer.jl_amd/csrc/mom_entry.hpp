@@ -50,7 +50,8 @@ struct LayerArgs {
   // hold a weighted stream entry -- the entries from 4 nbw on are zero-weight streams, whose exact-zero blocks (k-steps) the
   // products leave out; 0 (or N / 4): no such rule.  Set per first-stage launch: 0 where the image's bit of the option is off.
   // Read by the host only (the launch picks an instantiation): the two-buffer image's launch finds bit 2 of the option beside the
-  // count, as the flag kS2RowBlocks (mom_strip2_variants.hpp)
+  // count, as the flag kS2RowBlocks (mom_strip2_variants.hpp), and both images MOM_OPT_SOURCES_ONLY as the flag kMomNbwSourcesOnly
+  // (mom_images.hpp)
   int nbw;
 };
 

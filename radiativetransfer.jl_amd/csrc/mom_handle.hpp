@@ -111,6 +111,9 @@ struct mom_handle : MomSceneBufs<double> {
   int opt_zero_skip = 7;     // MOM_OPT_ZERO_SKIP, a mask: the exact-zero products of the zero-weight trailing streams are left out by
                              // 1 the quad-block image (blocks), 2 the two-buffer strip image (k-steps of its strip products);
                              // 4 the two-buffer strip image multiplies only the live blocks of four rows of a partly live row tile
+  int opt_sources_only = 1;  // MOM_OPT_SOURCES_ONLY: mom_rt_run's launches without an observable moment (the (I,Q) sub-problem's, a
+                             // full-problem launch from moment 1 on) leave the composite R-+ and T++ out (two-buffer strip and
+                             // quad-block images; the flag kMomNbwSourcesOnly of LayerArgs::nbw)
   int nbw_0 = 0;             // blocks of four entries with a weighted one (mom_q4_nbw) of the m = 0 sub-problem, after reduction and padding
   int Nk = 0;              // operator edge the scene-level kernels of the full problem run with (>= N)
   mom::DevStreams qk{};         // q with N = Nk

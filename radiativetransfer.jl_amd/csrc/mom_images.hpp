@@ -74,6 +74,11 @@ inline const MomLayerImage *mom_find_image(MomImageFamily family, int N) {
   return nullptr;
 }
 
+// MOM_OPT_SOURCES_ONLY: a flag in LayerArgs::nbw beside the count (<= 15) and the two-buffer image's kS2RowBlocks (0x100), read by
+// the host only.  mom_rt_run sets it on a first-stage launch whose moments no caller can observe; the two-buffer strip image and
+// the quad-block image then take their instantiation that leaves the composite R-+ and T++ out (mom_strip2.hpp)
+constexpr int kMomNbwSourcesOnly = 0x200;
+
 // ints of LayerArgs::sched of the two-buffer images (the unit queue's counter + the arrival tickets per CU: kS2SchedInts of
 // mom_strip2.hpp, momcore_strip2.hip checks the two against each other), zeroed on the stream before each of their launches
 constexpr size_t kMomStrip2SchedInts = 1 + 2048;

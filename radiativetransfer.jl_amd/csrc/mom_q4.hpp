@@ -254,6 +254,27 @@ __device__ __forceinline__ void q4_mul_c(const real *M, const real (&X)[Q4Geom<K
 #undef Q4_XLIVE
 }
 
+// The riding block row of a product alone (MOM_OPT_SOURCES_ONLY): accR(Jg) += sum_K V(K) X(K, Jg) with the fragments of `ride` and
+// nothing of M^T X -- the mma4 sequence q4_mul_c<KS, NV, .., NBW> issues for accR: K ascending per accumulator, the same guard on
+// the exact-zero operands, for both parities of NBW (the parity only decides where q4_mul_c requests the riding fragments).
+template <int KS, int NV, int NBW = Q4Geom<KS>::NB>
+__device__ __forceinline__ void q4_ride(const real *ride, const real (&X)[Q4Geom<KS>::NB][Q4Geom<KS>::NJ], real (&accR)[Q4Geom<KS>::NJ]) {
+  using G = Q4Geom<KS>;
+  static_assert(NV >= 1 && NBW >= 1 && NBW <= G::NB, "q4_ride: NV >= 1, 1 <= NBW <= NB");
+  int l = wg_lane();
+  asm volatile("" : "+v"(l));
+  const int k = l >> 4, i = l & 3;
+  const real *rb = ride + k + i * G::N;
+  real a[G::NB];
+#pragma unroll
+  for (int K = 0; K < G::NB; ++K) a[K] = (i < NV) ? rb[4 * K] : 0.0;
+#pragma unroll
+  for (int K = 0; K < G::NB; ++K)
+#pragma unroll
+    for (int J = 0; J < G::NJ; ++J)
+      if (K < NBW || J == (K >> 2)) accR[J] = mma4(a[K], X[K][J], accR[J]);   // (Q4_XLIVE of q4_mul_c)
+}
+
 template <int KS, int NV = 0, int NBW = Q4Geom<KS>::NB>
 __device__ __forceinline__ void q4_mul(const real *M, const real (&X)[Q4Geom<KS>::NB][Q4Geom<KS>::NJ],
                                        real (&acc)[Q4Geom<KS>::NB][Q4Geom<KS>::NJ], const real *ride = nullptr,
@@ -463,7 +484,10 @@ __device__ __forceinline__ real doubling_run_q4(Ctx &c, int nd, real expk, bool 
 // ScatteringInterface_11 (interaction.jl:69-117) in the algebra of interaction_strip / interaction_strip_lean.  Returns false,
 // nothing stored, if the series is too long.  Riding vectors: c.jm rides with r (column "N" of r = j0-); the composite J0+ is
 // fetched into c.v1 and rides with P = T++.
-template <int KS, int NBW = Q4Geom<KS>::NB>
+// SRC (MOM_OPT_SOURCES_ONLY; the header of mom_strip2.hpp says which launches and why): R-+ and T++ are neither loaded nor stored,
+// T++ is not staged in P, and the riding rows of the two products with T++ -- all the sources take from them -- come from q4_ride
+// with c.v1 = J0+.  The two arrays keep the first layer's r-+ and t++.
+template <int KS, int NBW = Q4Geom<KS>::NB, bool SRC = false>
 __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
   using G = Q4Geom<KS>;
   constexpr int N = G::N, NB = G::NB, NJ = G::NJ, NN = N * N;
@@ -529,13 +553,15 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
     q4_load_glb_T<KS>(g.T_mm, q, T1);
     __builtin_amdgcn_sched_barrier(0);
     q4_horner<KS, NBW>(P, W0, p, Y2);       // Y2 <- W0 + B^T Y2 : X^T, X = t++ R+- (I - B)^-1
+    if constexpr (!SRC) {
 #pragma unroll
-    for (int u = 0; u < UT; ++u) {
-      const int e = lane + 64 * u;
-      if (e < NN) {
-        int i, j;
-        c.fd.split(e, i, j);
-        vt[u] = MOM_NT_LOAD(g.T_pp + i + j * G::CP);
+      for (int u = 0; u < UT; ++u) {
+        const int e = lane + 64 * u;
+        if (e < NN) {
+          int i, j;
+          c.fd.split(e, i, j);
+          vt[u] = MOM_NT_LOAD(g.T_pp + i + j * G::CP);
+        }
       }
     }
     vj = (lane < N) ? g.J0p[lane] : 0.0;
@@ -545,14 +571,16 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
   q4_fence();
   MOM_STAMP(55);
   // P = T++ (plain); c.v1 = J0+ (rides with P)
+  if constexpr (!SRC) {
 #pragma unroll
-  for (int u = 0; u < UT; ++u) {
-    const int e = lane + 64 * u;
-    if (e < NN) P[e] = vt[u];
+    for (int u = 0; u < UT; ++u) {
+      const int e = lane + 64 * u;
+      if (e < NN) P[e] = vt[u];
+    }
   }
   if (lane < N) c.v1[lane] = vj;
   real Radd[NB][NJ];
-  q4_load_glb_T<KS>(g.R_mp, q, Radd);
+  if constexpr (!SRC) q4_load_glb_T<KS>(g.R_mp, q, Radd);
   q4_fence();
   MOM_STAMP(56);
   // ---- chain 1: T-- = T01 t--, R-+ += (T01 r-+) T++, J0- += T01 (r-+ J0+ + j0-)                (:90-96)
@@ -569,8 +597,12 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
 #pragma unroll
     for (int J = 0; J < NJ; ++J) { Vr[J] = 0.0; Rr[J] = 0.0; }
     q4_mul_z<KS, 1, NBW>(r, Y1, V, c.jm, &Vr);                 // (T01 r-+)^T ; riding row: (T01 j0-)^T
-    q4_mul<KS, 1, NBW>(P, V, Radd, c.v1, &Rr);               // R-+^T + T++^T (T01 r)^T ; riding row: (T01 r J0+)^T
-    q4_store_glb_T<KS>(g.R_mp, q, Radd);
+    if constexpr (SRC) {
+      q4_ride<KS, 1, NBW>(c.v1, V, Rr);                      // the riding row alone: (T01 r J0+)^T
+    } else {
+      q4_mul<KS, 1, NBW>(P, V, Radd, c.v1, &Rr);             // R-+^T + T++^T (T01 r)^T ; riding row: (T01 r J0+)^T
+      q4_store_glb_T<KS>(g.R_mp, q, Radd);
+    }
 #pragma unroll
     for (int J = 0; J < NJ; ++J) {
       const int col = 16 * J + q.c16;
@@ -585,7 +617,9 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
 #pragma unroll
     for (int J = 0; J < NJ; ++J) { Tr[J] = 0.0; Or[J] = 0.0; }
     q4_mul<KS, 1, NBW>(r, Y2, T21, c.jm, &Tr);               // riding row: (X j0-)^T = (T21 R+- j0-)^T
-    {
+    if constexpr (SRC) {
+      q4_ride<KS, 1, NBW>(c.v1, T21, Or);                      // the riding row alone: (T21 J0+)^T
+    } else {
       real o[NB][NJ];
       q4_mul_z<KS, 1, NBW>(P, T21, o, c.v1, &Or);              // (T21 T++)^T ; riding row: (T21 J0+)^T
       q4_store_glb_T<KS>(g.T_pp, q, o);
@@ -622,7 +656,8 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
 #else
 #define MOM_Q4_ATTR
 #endif
-template <int KS, int NBW = Q4Geom<KS>::NB>
+// SRC: the sources-only form of the interaction (MOM_OPT_SOURCES_ONLY, the flag kMomNbwSourcesOnly in LayerArgs::nbw)
+template <int KS, int NBW = Q4Geom<KS>::NB, bool SRC = false>
 __global__ void __launch_bounds__(64) MOM_Q4_ATTR k_layer_q4(const LayerArgs a) {
   using G = Q4Geom<KS>;
   constexpr int N = G::N;
@@ -671,7 +706,7 @@ __global__ void __launch_bounds__(64) MOM_Q4_ATTR k_layer_q4(const LayerArgs a) 
           q4_fence();
           MOM_STAMP(42);
         } else {
-          bail = !interaction_q4<KS, NBW>(c, g);
+          bail = !interaction_q4<KS, NBW, SRC>(c, g);
         }
       }
       if (bail) {  // the full image redoes this layer and finishes the unit

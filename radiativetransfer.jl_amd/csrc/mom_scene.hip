@@ -319,7 +319,9 @@ static FirstStage choose_first_stage(const mom_t *h, Finisher fin, const DevStre
 // The first-stage launch of `fs` for the sweep described by `a`, if it applies: a whole-slab sweep of a single-target run, no
 // forced pivoted inverse, interface code 3 on every layer that interacts (the images handle no other).  On return a.resume (and
 // a.sched) are set for the finisher as well.
-static int launch_first_stage(mom_t *h, const FirstStage &fs, LayerArgs &a, bool multi_target, hipStream_t st) {
+// sources_only (MOM_OPT_SOURCES_ONLY): no caller can observe a moment of this launch -- the two-buffer strip image and the
+// quad-block image leave the composite R-+ and T++ out of it (the flag kMomNbwSourcesOnly in a.nbw); the other images ignore it.
+static int launch_first_stage(mom_t *h, const FirstStage &fs, LayerArgs &a, bool multi_target, bool sources_only, hipStream_t st) {
   const int nzr = a.Nz_sweep;  // 0: a per-layer launch
   bool ok = fs.image && nzr > 0 && !multi_target && a.q.inv_mode == 0;
   for (int k = 1; k < nzr && ok; ++k) ok = (a.iface_z[k] == 3);
@@ -338,6 +340,7 @@ static int launch_first_stage(mom_t *h, const FirstStage &fs, LayerArgs &a, bool
   const int skip_bit = (fs.family == MOM_IMG_QUAD) ? 1 : two_buffer ? 2 : 0;
   if (!(h->opt_zero_skip & skip_bit)) a.nbw = 0;
   if (two_buffer && (h->opt_zero_skip & 4)) a.nbw |= kS2RowBlocks;
+  if (sources_only && (two_buffer || fs.family == MOM_IMG_QUAD)) a.nbw |= kMomNbwSourcesOnly;
   if (two_buffer) {
     h->resume2_units = units; h->resume2_nz = nzr;  // (mom_strip2_resumed)
     if (h->opt_strip2_sched) {  // the queue counter (and, for the chain priority, the per-CU tickets) start at zero: a memset ON
@@ -362,13 +365,13 @@ static int launch_first_stage(mom_t *h, const FirstStage &fs, LayerArgs &a, bool
 }
 
 // One k_layer launch (plus the first-stage launch in front of it, if any) of the argument block `a` on stream `st`
-static int launch_layer_images(mom_t *h, LayerArgs &a, bool multi_target, hipStream_t st) {
+static int launch_layer_images(mom_t *h, LayerArgs &a, bool multi_target, bool sources_only, hipStream_t st) {
   const DevStreams &q = a.q;
   const size_t units = (size_t)a.S * a.M;
   const bool lds = (q.N <= 64) && !h->opt_force_generic;
   const int ns_tab = q.regular ? q.nS : 1;  // Stokes components per stream of the elemental layer's stream-pair tables
   const Finisher fin = choose_finisher(h, q, ns_tab, lds);
-  const int rc = launch_first_stage(h, choose_first_stage(h, fin, q, ns_tab), a, multi_target, st);
+  const int rc = launch_first_stage(h, choose_first_stage(h, fin, q, ns_tab), a, multi_target, sources_only, st);
   if (rc) return rc;
   if (fin == kFinStrip4 || fin == kFinStrip8) {  // strip-chained kernels (momcore_strip.hip), one image per N
     const MomLayerImage *im = mom_find_image(fin == kFinStrip4 ? MOM_IMG_STRIP4 : MOM_IMG_STRIP8, q.N);
@@ -454,7 +457,10 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, const Comp6 &co
         for (int t = 0; t < kMaxTargets; ++t) a.act_z[r][t] = tg->act[(size_t)(r0 + r) * kMaxTargets + t];
     }
     a.scratch = scratch; a.info = h->d_info;
-    return launch_layer_images(h, a, tg != nullptr, cur);
+    // MOM_OPT_SOURCES_ONLY: mom_rt_run alone (allow_red and no targets: mom_rt_run_multisensor has neither), and only a launch
+    // that holds no observable moment -- the (I,Q) sub-problem's (mom_download: MOM_ESTATE) or one that starts behind moment 0
+    const bool unobserved = h->opt_sources_only && allow_red && !tg && (&q == &h->q0 || m_first >= 1);
+    return launch_layer_images(h, a, tg != nullptr, unobserved, cur);
   };
   // MOM_OPT_OVERLAP: the two launches of a sweep -- moments 1..M-1 on the full problem, moment 0 on the (I,Q) sub-problem --
   // are independent.  What runs at the edges 52 / 56 / 60 (C2: N = 60, sub-problem N = 40): the sub-problem on the quad-block image

@@ -236,6 +236,42 @@ __device__ __forceinline__ void strip_mul(const real *M, int lr, int lq, const r
   if constexpr (KW < KS) strip_diag_fixup<KS, KW>(M, lr, lq, strip, B, acc);
 }
 
+// The riding block row of a strip product alone (MOM_OPT_SOURCES_ONLY, mom_strip2.hpp; Float64): ride += row N (lanes lq == 0) /
+// row N + 1 (lanes lq == 1) of M^T B, column lr of the strip -- the component [RT][RR0] of the accumulators of strip_mul<KS, KW>
+// and nothing else of the product.  It is the v_mfma_f64_4x4x4_4b of block row KS under the row-block rule: the same KW k-steps in
+// the same order, the A fragment read as strip_frag_rb reads it (the 4 x 4 block M[4 ks + lq + (4 KS + (lr & 3)) LD], i.e. columns
+// N .. N + 3 of M's buffer, of which the rows N and N + 1 of the result see only N and N + 1), then the one term of strip_diag_fixup
+// on that component.  Where strip_mul forms the riding rows with the 16 x 16 x 4 instruction (no RB, or a full riding tile) the two
+// forms round alike (tools/mfma_f64_forms_check.hip, profiles/r15_mfma_forms.txt): the same bits either way.
+template <int KS, int KW = KS>
+__device__ __forceinline__ void strip_ride(const real *M, int lr, int lq, const r4 (&B)[StripGeom<KS>::NT], real &ride, int strip = 0) {
+  constexpr int N = StripGeom<KS>::N, NT = StripGeom<KS>::NT, LD = StripGeom<KS>::LD;
+  static_assert(KW <= KS && (kF64 || KW < 0), "strip_ride: the Float64 strip layout (block rows of four)");
+  static_assert(4 * StripGeom<KS>::RT + StripGeom<KS>::RR0 == KS, "strip_ride: the riding rows are block row KS");
+  asm volatile("" : "+v"(lr), "+v"(lq));
+  const real *base4 = M + lq + (lr & 3) * LD + 4 * KS * LD;
+#pragma unroll
+  for (int ks = 0; ks < KW; ++ks) {
+    ride = mfma4_f64(base4[4 * ks], B[ks >> 2][ks & 3], ride);
+    if ((ks + 1) % kStripChunk == 0) __builtin_amdgcn_sched_barrier(0);  // as strip_mul: cap the A fragments in flight
+  }
+  if constexpr (KW < KS) {
+#pragma unroll
+    for (int t0 = (4 * KW) >> 4; t0 < NT; ++t0) {
+      if (strip == t0) {
+        const int src = 16 * (lr & 3) + lr, col = 16 * t0 + lr;
+        real d = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const real v = __shfl(B[t0][r], src, 64);
+          d = ((lr >> 2) == r) ? v : d;
+        }
+        if (col >= 4 * KW && col < N) ride = fma(M[col + lq * LD + 4 * KS * LD], d, ride);
+      }
+    }
+  }
+}
+
 // two strips through the same multiplier: acc1 += M^T B1, acc2 += M^T B2 (A fragments loaded once)
 template <int KS, int KW = KS, bool RB = false>
 __device__ __forceinline__ void strip_mul2(const real *M, int lr, int lq, const r4 (&B1)[StripGeom<KS>::NT],

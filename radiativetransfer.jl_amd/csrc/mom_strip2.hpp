@@ -21,6 +21,23 @@
 // Every product is the one of the 8-wave image's strip path (mom_strip.hpp) on the same operands in the same order: the results
 // are bitwise those of the 8-wave image.
 // Scope: Float64, 4-wave build, sweep mode, single composite (no multi-target), interface 11 on every layer after the first.
+//
+// Sources only (MOM_OPT_SOURCES_ONLY, k_layer_s2<.., SRC = true>; the quad-block image has the same form, mom_q4.hpp).  Of the four
+// composite operators R+- and T-- feed the next layer's B, W0, the two series and the sources; R-+ += (T01 r-+) T++ and
+// T++ = T21 T++ feed only themselves.  The sources take ONE ROW from each of those two products, the riding row:
+// J0- += T01 (r-+ J0+ + j0-) takes J0+^T V, J0+ = j0+ + T21 (J0+ + R+- j0-) takes J0+^T T21^T.  Everything mom_rt_run hands out
+// (R, T, hdr, the BHRs) comes from J0+-, and mom_download returns moment 0 of the full problem only (MOM_ESTATE when moment 0 ran on
+// the sub-problem).  So in a launch of mom_rt_run that holds no observable moment -- the (I,Q) sub-problem's, or a full-problem launch
+// with m_first >= 1 -- the host asks for SRC, and section (d) of the interaction neither loads R-+, nor stages T++ in t's buffer,
+// nor stores either: J0+ goes to column N of t's buffer and strip_ride (mom_strip.hpp) forms the two riding rows with the matrix
+// instructions the full products would have issued for them, in the same order: J0+- keep their bits.
+// What the two arrays hold afterwards: store_added_as_composite is unchanged, so the FIRST layer's r-+ and t++ -- finite, rewritten
+// by every run, meaningless.  Who reads them: the 8-wave image where it finishes a unit (interaction_strip / interaction_core) and
+// k_surface, which go on updating the two operators from there.  In all three R-+ is read only as the addend of its own update and
+// T++ only as the multiplier of the two products above, whose riding rows come from the riding column J0+, not from T++: nothing of
+// the two arrays enters a J0+-, a Frobenius sum (those are taken over B = r-+ R+- alone) or, through it, a series length or a resume
+// decision.  mom_rt_run_multisensor (k_combine, k_interlayer read all four operators), the Dual and RRS runs and the operator-level
+// calls never launch SRC; nor do the scheduling modes 0, 2, 3, which keep the recorded forms of their experiments.
 #pragma once
 #include "mom_diag.hpp"
 #include "mom_entry.hpp"
@@ -241,8 +258,8 @@ __device__ __forceinline__ real doubling_run_s2(Ctx &c, int nd, real expk, bool 
 }
 
 // ScatteringInterface_11 in two buffers (see interaction_strip for the algebra; same products, same order).  Returns false,
-// nothing stored, if the series is too long.  Ends with a barrier.
-template <int KS, bool PRIO, int KW, bool RB>
+// nothing stored, if the series is too long.  Ends with a barrier.  SRC: the sources-only form (the header of this file).
+template <int KS, bool PRIO, int KW, bool RB, bool SRC = false>
 __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) {
   using G = StripGeom<KS>;
   constexpr int N = G::N, NT = G::NT, LD = G::LD, NN = N * N, U = (NN + kThreads - 1) / kThreads;
@@ -364,6 +381,27 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
     strip_store_glb<KS>(g.R_pm, lr, lq, c0, colok, acc);
   }
   s2_chain<false, PRIO>(c, S2_SEC_ICH1, fav);
+  if constexpr (SRC) {
+    // ---- (d), sources only: neither R-+ nor T++ is loaded, staged or stored.  J0+ alone goes to column N of t's buffer, and the
+    // two riding rows the sources take from the products with T++ -- J0+^T V and J0+^T T21^T -- are formed on their own
+    const real j0m = (colok && lq == G::LQ0) ? g.J0m[col] : 0.0;
+    const real vj = (wg_tid() < N) ? g.J0p[wg_tid()] : 0.0;
+    __syncthreads();  // every wave is done with t
+    if (wg_tid() < N) t[wg_tid() + N * LD] = vj;
+    __syncthreads();
+    s2_chain<true, PRIO>(c, S2_SEC_ICOPY2, fav);
+    real ride1 = 0.0, ride2 = 0.0;
+    strip_ride<KS, KW>(t, lr, lq, V, ride1, wave);    // row N: (T01 r-+ J0+)^T
+    // J0- = J0- + T01 (r-+ J0+ + j0-)                                                (:90)
+    if (colok && lq == G::LQ0) g.J0m[col] = j0m + (ride1 + V[G::RT][G::RR0]);
+    strip_ride<KS, KW>(t, lr, lq, T21, ride2, wave);  // row N: (T21 J0+)^T
+    // J0+ = j0+ + T21 (J0+ + R+- j0-)                                                (:110)
+    if (colok && lq == G::LQ0) g.J0p[col] = c.jp[col] + (ride2 + T21[G::RT][G::RR0]);
+    s2_chain<false, PRIO>(c, S2_SEC_ICH2, fav);
+    __syncthreads();
+    MOM_TL(c, S2_SEC_IEND);
+    return true;
+  }
   // ---- (d) T++ (+ J0+ as its riding column N) into t's buffer; the products with T++
   r4 Radd[NT];
   strip_load_glb<KS>(g.R_mp, lr, lq, c0, colok, Radd);
@@ -426,7 +464,9 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
 // rows.  The strip rows that keep their incoming value under it are read by nothing: the stores and the Frobenius sums are guarded
 // by strip_rowok (rows < N), strip_flip only changes signs, the riding rows N, N + 1 lie in a live block, and a strip's rows >= N
 // never are a B operand (KS k-steps at most).
-template <int KS, int MODE, int KW = KS, bool RB = false>
+// SRC (MOM_OPT_SOURCES_ONLY; default mode only; the flag kMomNbwSourcesOnly in LayerArgs::nbw): the sources-only form of the
+// interaction, see the header of this file.  SRC = false is the kernel as it was before the option existed.
+template <int KS, int MODE, int KW = KS, bool RB = false, bool SRC = false>
 __global__ void __launch_bounds__(kThreads, 2) k_layer_s2(const LayerArgs a) {
   // (the argument block is never written: see k_layer_lean)
   constexpr int N = 4 * KS;
@@ -498,7 +538,7 @@ __global__ void __launch_bounds__(kThreads, 2) k_layer_s2(const LayerArgs a) {
           __syncthreads();
           MOM_TL(c, S2_SEC_FIRST);
         } else {
-          bail = !interaction_strip_s2<KS, PRIO, KW, RB>(c, g);
+          bail = !interaction_strip_s2<KS, PRIO, KW, RB, SRC>(c, g);
         }
       }
       if (bail) {  // workgroup-uniform: the 8-wave image redoes this layer and finishes the unit
