@@ -506,5 +506,3 @@ hipError_t momw_launch_sweep(const void *args, hipStream_t st);
 hipError_t momw_launch_sweep8(const void *args, hipStream_t st);
 hipError_t momwf_launch_sweep(const void *args, hipStream_t st);  // mom_wave.hip built with -DMOMW_FLOAT
 hipError_t momwf_launch_sweep8(const void *args, hipStream_t st);
-// mom_rrs.hip built with -DMOMR_BIG_TU: the one launcher of the 3 x 3- and 4 x 4-tile RRS images (32 < N <= 64)
-hipError_t momr_big_launch(int which, int nt, int v0, int v1, unsigned grid, void *stream, const void *args, int iface);

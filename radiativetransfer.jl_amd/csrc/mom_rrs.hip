@@ -35,8 +35,9 @@
 #include "mom_host.hpp"
 #include "mom_tile.hpp"
 
-// The 3 x 3- and 4 x 4-tile images (32 < N <= 64) are built as a second object from this source (-DMOMR_BIG_TU, namespace
-// momr_big, without -amdgpu-mfma-vgpr-form, which crashes the compiler on them): device code + ONE launcher, momr_big_launch
+// The 3 x 3- and 4 x 4-tile images (32 < N <= 64) and the workgroup forms (mom_rrs_wg.hpp) are built as a second object from this
+// source (-DMOMR_BIG_TU, namespace momr_big, without -amdgpu-mfma-vgpr-form, which crashes the compiler on them): device code +
+// ONE launcher, momr_big_launch, which takes the same description of a kernel form (momr::Form) as this object's momr::launch
 #ifdef MOMR_BIG_TU
 #define MOMR_NS momr_big
 #else
@@ -113,9 +114,6 @@ __device__ __forceinline__ double dsgn(int ci, int cj) { return (((ci <= 2) && (
 
 constexpr int kWavesPerBlock = 4;
 // waves per SIMD the pair kernels are compiled for (register budget 512 / MOMR_WPE); measured in profiles/r03_C5_*.txt
-#ifndef MOMR_FAST_DEFAULT
-#define MOMR_FAST_DEFAULT 3
-#endif
 #ifndef MOMR_WPE
 #define MOMR_WPE 2
 #endif
@@ -1626,97 +1624,119 @@ __global__ void k_unpack(double *nat, const double *dev, int rows, int cols, int
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
+// A runtime flag as a template argument: `f` is a generic lambda and receives a std::integral_constant, which converts to its
+// value in constant expressions.  with_int covers Lo ... Hi and refuses the rest, so nothing outside that range is instantiated.
+template <class F>
+static hipError_t with_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <int Lo, int Hi, class F>
+static hipError_t with_int(int v, F &&f) {
+  if (v == Lo) return f(std::integral_constant<int, Lo>{});
+  if constexpr (Lo < Hi) return with_int<Lo + 1, Hi>(v, f);
+  else return hipErrorInvalidValue;
+}
+
+// the one launch of a kernel with dynamic LDS (above 64 KB the limit of the function has to be raised first)
+template <class K, class... Args>
+static hipError_t launch_lds(K kern, unsigned grid, unsigned block, size_t lds_bytes, hipStream_t st, Args... args) {
+  if (lds_bytes > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds_bytes, st, args...);
+  return hipGetLastError();
+}
+
+// the one-tile pair bodies with LDS prefetch (dbl_pair_body1; int_pair_body1: ScatteringInterface_11 only): their work items are
+// (n1, chunk of offsets), and every wave has prefetch slots behind the slices
+static bool prefetch_body(Family f, int nt, int iface) {
+  return MOMR_LDSPF != 0 && nt == 1 && (f == Family::DblPair || (f == Family::IntPair && iface == 3));
+}
+
+// the wave-per-pair kernels carry the tile count in their names; each object holds its own two
+template <int NT, bool FUSE, int MODE>
+static auto dbl_pair_kernel() {
 #ifdef MOMR_BIG_TU
-#include "mom_rrs_wg.hpp"
-}  // namespace momr_big
-// which: 0 k_el_point, 1 k_dbl_point, 2 k_int_point, 3 k_dbl_pair (v0 = fused elemental, v1 = mode), 4 k_int_pair (v0 = surface,
-// v1 = derived +- / -- blocks), 5 k_dbl_pair_wg, 6 k_int_pair_wg (workgroup per pair, mom_rrs_wg.hpp; grid = workgroups), 7 k_dbl_point_wg (workgroup per point, nt >= 3), 8 k_ie_elemental_tile (v0 = layer without doublings), 9 k_int_point_wg; nt = 3 or 4; args: the
-// KArgs of the caller (layout-identical in both namespaces)
-hipError_t momr_big_launch(int which, int nt, int v0, int v1, unsigned grid, void *stream, const void *args, int iface) {
-  using namespace momr_big;
-  const KArgs a = *reinterpret_cast<const KArgs *>(args);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 gr(grid), bl(64 * kWavesPerBlock);
-  const size_t lds = (size_t)kWavesPerBlock * (nt == 3 ? slice_bytes<3>() : slice_bytes<4>());
-#define BIG_GO(KERN, ...)                                                                                                      \
-  do {                                                                                                                         \
-    const hipError_t e__ = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    if (e__ != hipSuccess) return e__;                                                                                         \
-    hipLaunchKernelGGL(KERN, gr, bl, lds, st, __VA_ARGS__);                                                                    \
-    return hipGetLastError();                                                                                                  \
-  } while (0)
-#define BIG_NT(KERN3, KERN4, ...) do { if (nt == 3) BIG_GO(KERN3, __VA_ARGS__); else BIG_GO(KERN4, __VA_ARGS__); } while (0)
-  const dim3 blw(64 * nt);
-  const size_t ldw = (nt == 2) ? wg_lds_bytes<2>(4) : ((nt == 3) ? wg_lds_bytes<3>(4) : wg_lds_bytes<4>(4));
-#define WG_GO(KERN)                                                                                                            \
-  do {                                                                                                                         \
-    const hipError_t e__ = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldw); \
-    if (e__ != hipSuccess) return e__;                                                                                         \
-    hipLaunchKernelGGL(KERN, gr, blw, ldw, st, a);                                                                             \
-    return hipGetLastError();                                                                                                  \
-  } while (0)
-  switch (which) {
-    case 0: BIG_NT(k_el_point<3>, k_el_point<4>, a);
-    case 1: BIG_NT(k_dbl_point<3>, k_dbl_point<4>, a);
-    case 2: BIG_NT(k_int_point<3>, k_int_point<4>, a, iface);
-    case 3:
-#define BIG_DBL(F, M) BIG_NT((k_dbl_pair3<F, M>), (k_dbl_pair4<F, M>), a)
-      if (v0) { if (v1 == 0) BIG_DBL(true, 0); else if (v1 == 1) BIG_DBL(true, 1); else BIG_DBL(true, 2); }
-      else { if (v1 == 0) BIG_DBL(false, 0); else if (v1 == 1) BIG_DBL(false, 1); else BIG_DBL(false, 2); }
-#undef BIG_DBL
-    case 4:
-      if (v0) BIG_NT((k_int_pair3<true, false>), (k_int_pair4<true, false>), a, iface);
-      else if (v1) BIG_NT((k_int_pair3<false, true>), (k_int_pair4<false, true>), a, iface);
-      else BIG_NT((k_int_pair3<false, false>), (k_int_pair4<false, false>), a, iface);
-    case 5: {
-      // products without the per-k-step guards where no k-step lies in the zero padding, or one of sixteen (mom_rrs_wg.hpp NG;
-      // one of twelve -- N = 42 ... 44 -- measured slower than the guards: profiles/r05_rrs_wg_ab.txt (13))
-      const int padded_steps = (16 * nt - a.N) / 4;
-      const bool ng = padded_steps == 0 || (padded_steps == 1 && nt == 4);
-#define WG_DBL_G(F, M, G) do { if (nt == 2) WG_GO((k_dbl_pair_wg2<F, M, G>)); else if (nt == 3) WG_GO((k_dbl_pair_wg3<F, M, G>)); else WG_GO((k_dbl_pair_wg4<F, M, G>)); } while (0)
-#define WG_DBL(F, M) do { if (ng) WG_DBL_G(F, M, true); else WG_DBL_G(F, M, false); } while (0)
-      if (v0) { if (v1 == 0) WG_DBL(true, 0); else if (v1 == 1) WG_DBL(true, 1); else WG_DBL(true, 2); }
-      else { if (v1 == 0) WG_DBL(false, 0); else if (v1 == 1) WG_DBL(false, 1); else WG_DBL(false, 2); }
-#undef WG_DBL
-#undef WG_DBL_G
-    }
-    case 6: {  // ScatteringInterface_11 only
-#define WG_INT(SF, DV) do { if (nt == 2) WG_GO((k_int_pair_wg2<SF, DV>)); else if (nt == 3) WG_GO((k_int_pair_wg3<SF, DV>)); else WG_GO((k_int_pair_wg4<SF, DV>)); } while (0)
-      if (v0) WG_INT(true, false);
-      else if (v1) WG_INT(false, true);
-      else WG_INT(false, false);
-#undef WG_INT
-    }
-    case 9: {  // k_int_point_wg (interface 11): one workgroup per spectral point
-      const size_t ldp = (nt == 2) ? wg_point_lds_bytes<2>() : ((nt == 3) ? wg_point_lds_bytes<3>() : wg_point_lds_bytes<4>());
-      const void *kp = (nt == 2) ? reinterpret_cast<const void *>(k_int_point_wg2)
-                                 : ((nt == 3) ? reinterpret_cast<const void *>(k_int_point_wg3) : reinterpret_cast<const void *>(k_int_point_wg4));
-      const hipError_t e__ = hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldp);
-      if (e__ != hipSuccess) return e__;
-      if (nt == 2) hipLaunchKernelGGL(k_int_point_wg2, gr, blw, ldp, st, a);
-      else if (nt == 3) hipLaunchKernelGGL(k_int_point_wg3, gr, blw, ldp, st, a);
-      else hipLaunchKernelGGL(k_int_point_wg4, gr, blw, ldp, st, a);
-      return hipGetLastError();
-    }
-    case 8:
-      if (v0) BIG_NT((k_ie_elemental_tile<3, true>), (k_ie_elemental_tile<4, true>), a);
-      else BIG_NT((k_ie_elemental_tile<3, false>), (k_ie_elemental_tile<4, false>), a);
-    case 7: {  // k_dbl_point_wg: one workgroup per spectral point (grid = workgroups)
-      const size_t ldp = (nt == 2) ? wg_point_lds_bytes<2>() : ((nt == 3) ? wg_point_lds_bytes<3>() : wg_point_lds_bytes<4>());
-      const void *kp = (nt == 2) ? reinterpret_cast<const void *>(k_dbl_point_wg2)
-                                 : ((nt == 3) ? reinterpret_cast<const void *>(k_dbl_point_wg3) : reinterpret_cast<const void *>(k_dbl_point_wg4));
-      const hipError_t e__ = hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldp);
-      if (e__ != hipSuccess) return e__;
-      if (nt == 2) hipLaunchKernelGGL(k_dbl_point_wg2, gr, blw, ldp, st, a);
-      else if (nt == 3) hipLaunchKernelGGL(k_dbl_point_wg3, gr, blw, ldp, st, a);
-      else hipLaunchKernelGGL(k_dbl_point_wg4, gr, blw, ldp, st, a);
-      return hipGetLastError();
-    }
+  if constexpr (NT == 3) return k_dbl_pair3<FUSE, MODE>; else return k_dbl_pair4<FUSE, MODE>;
+#else
+  if constexpr (NT == 1) return k_dbl_pair1<FUSE, MODE>; else return k_dbl_pair2<FUSE, MODE>;
+#endif
+}
+template <int NT, bool SURF, bool DERIVE>
+static auto int_pair_kernel() {
+#ifdef MOMR_BIG_TU
+  if constexpr (NT == 3) return k_int_pair3<SURF, DERIVE>; else return k_int_pair4<SURF, DERIVE>;
+#else
+  if constexpr (NT == 1) return k_int_pair1<SURF, DERIVE>; else return k_int_pair2<SURF, DERIVE>;
+#endif
+}
+
+// A wave family at NT x NT tiles (this object's images: NT = 1, 2; mom_rrs_big.o: 3, 4) as a launch: kWavesPerBlock waves per
+// block, a slice of LDS per wave.
+template <int NT>
+static hipError_t launch_wave(const Form &f, unsigned grid, hipStream_t st, const KArgs &a, int iface) {
+  size_t lds = (size_t)kWavesPerBlock * slice_bytes<NT>();
+  if (prefetch_body(f.family, NT, iface)) lds += kWavesPerBlock * (f.family == Family::DblPair ? kPfBytes : kPfIntBytes);
+  auto go = [&](auto kern, auto... more) { return launch_lds(kern, grid, 64 * kWavesPerBlock, lds, st, a, more...); };
+  switch (f.family) {
+    case Family::ElPoint: return go(k_el_point<NT>);
+    case Family::DblPoint: return go(k_dbl_point<NT>);
+    case Family::IntPoint: return go(k_int_point<NT>, iface);
+    case Family::TileElemental: return with_bool(f.nd0, [&](auto nd0) { return go(k_ie_elemental_tile<NT, nd0>); });
+    case Family::DblPair:
+      return with_bool(f.fuse_el, [&](auto fuse) {
+        return with_int<0, 2>(f.mode, [&](auto mode) { return go(dbl_pair_kernel<NT, fuse, mode>()); });
+      });
+    case Family::IntPair:  // three forms are built: the surface, derived +- / -- blocks, neither (never both: the surface's ie* are zeros)
+      return with_int<0, 2>(f.surface ? 2 : (f.derive ? 1 : 0),
+                            [&](auto v) { return go(int_pair_kernel<NT, (v == 2), (v == 1)>(), iface); });
     default: return hipErrorInvalidValue;
   }
-#undef WG_GO
-#undef BIG_NT
-#undef BIG_GO
+}
+
+#ifdef MOMR_BIG_TU
+#include "mom_rrs_wg.hpp"
+// the workgroup kernels carry the tile count in their names: the one for NT among those for 2, 3, 4
+template <int NT, class K>
+static K wg_kernel(K k2, K k3, K k4) { return NT == 2 ? k2 : (NT == 3 ? k3 : k4); }
+
+// A workgroup family (mom_rrs_wg.hpp) as a launch: NT waves per workgroup, grid = workgroups; the per-pair forms hold four
+// operator copies in LDS, the per-point forms their strips and the pivot bookkeeping of the inverse.
+template <int NT>
+static hipError_t launch_wg(const Form &f, unsigned grid, hipStream_t st, const KArgs &a) {
+  const bool point = f.family == Family::DblPointWg || f.family == Family::IntPointWg;
+  const size_t lds = point ? wg_point_lds_bytes<NT>() : wg_lds_bytes<NT>(4);
+  auto go = [&](auto kern) { return launch_lds(kern, grid, 64 * NT, lds, st, a); };
+  switch (f.family) {
+    case Family::DblPointWg: return go(wg_kernel<NT>(k_dbl_point_wg2, k_dbl_point_wg3, k_dbl_point_wg4));
+    case Family::IntPointWg: return go(wg_kernel<NT>(k_int_point_wg2, k_int_point_wg3, k_int_point_wg4));  // interface 11
+    case Family::DblPairWg: {
+      // products without the per-k-step guards where no k-step lies in the zero padding, or one of sixteen (mom_rrs_wg.hpp NG;
+      // one of twelve -- N = 42 ... 44 -- measured slower than the guards: profiles/r05_rrs_wg_ab.txt (13))
+      const int padded_steps = (16 * NT - a.N) / 4;
+      const bool no_guards = padded_steps == 0 || (padded_steps == 1 && NT == 4);
+      return with_bool(f.fuse_el, [&](auto fuse) {
+        return with_int<0, 2>(f.mode, [&](auto mode) {
+          return with_bool(no_guards, [&](auto ng) {
+            return go(wg_kernel<NT>(k_dbl_pair_wg2<fuse, mode, ng>, k_dbl_pair_wg3<fuse, mode, ng>, k_dbl_pair_wg4<fuse, mode, ng>));
+          });
+        });
+      });
+    }
+    case Family::IntPairWg:  // interface 11; the same three forms as Family::IntPair
+      return with_int<0, 2>(f.surface ? 2 : (f.derive ? 1 : 0), [&](auto v) {
+        return go(wg_kernel<NT>(k_int_pair_wg2<(v == 2), (v == 1)>, k_int_pair_wg3<(v == 2), (v == 1)>, k_int_pair_wg4<(v == 2), (v == 1)>));
+      });
+    default: return hipErrorInvalidValue;
+  }
+}
+}  // namespace momr_big
+
+// The one function of this object that turns a Form into a launch (declared in mom_rrs.hpp, which says why `args` is a void *).
+hipError_t momr_big_launch(const momr::Form &f, unsigned grid, hipStream_t stream, const void *args, int iface) {
+  using namespace momr_big;
+  const KArgs &a = *static_cast<const KArgs *>(args);
+  if (workgroup_form(f.family)) return with_int<2, 4>(f.nt, [&](auto nt) { return launch_wg<nt>(f, grid, stream, a); });
+  return with_int<3, 4>(f.nt, [&](auto nt) { return launch_wave<nt>(f, grid, stream, a, iface); });
 }
 #else
 #define RCHK(call)                                 \
@@ -1724,6 +1744,13 @@ hipError_t momr_big_launch(int which, int nt, int v0, int v1, unsigned grid, voi
     hipError_t e__ = (call);                       \
     if (e__ != hipSuccess) return e__;             \
   } while (0)
+
+// The one function of this object that turns a Form into a launch: its own images (wave families, one or 2 x 2 tiles), or the
+// second object's.
+static hipError_t launch(const State *s, const Form &f, unsigned grid, const KArgs &a, int iface = 0) {
+  if (f.nt > 2 || workgroup_form(f.family)) return momr_big_launch(f, grid, s->stream, &a, iface);
+  return with_int<1, 2>(f.nt, [&](auto nt) { return launch_wave<nt>(f, grid, s->stream, a, iface); });
+}
 
 static KArgs base_args(const State *s, const Streams &q) {
   KArgs a{};
@@ -1749,30 +1776,14 @@ static KArgs base_args(const State *s, const Streams &q) {
   return a;
 }
 
-template <class T>
-static hipError_t dm(T **p, size_t count) {
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T));
-  if (e == hipSuccess) e = hipMemset(*p, 0, count * sizeof(T));
-  return e;
+hipError_t GuardedBuf::renew(size_t n) {
+  count = 0;
+  RCHK(mem.renew(n + 2 * kGuard));
+  count = n;
+  RCHK(hipMemset(data(), 0, n * sizeof(double)));
+  RCHK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(mem.get()), (int)kCanary, 2 * kGuard));
+  return hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(data() + n), (int)kCanary, 2 * kGuard);
 }
-// Layer arrays sit between two GUARD BANDS of kGuard doubles filled with a canary pattern (r5, ADVICE r4: the kernels store whole
-// tiles without edge masks; the zero-padding invariant only sees writes that land INSIDE an array).  count_padding checks the
-// bands of every array too: a store before the first or behind the last block of any layer array shows up as a violation
-// (tests/test_gpu_rrs.py::test_rrs_zero_padding_invariant, N = 15 ... 60, both switch positions).
-constexpr size_t kGuard = 2048;               // doubles per band (16 KB: more than a 4 x 4-tile block row)
-constexpr unsigned kCanary = 0xDEADBEEFu;     // both halves of a canary double
-static hipError_t dmg(State *s, double **p, size_t count) {
-  double *base = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&base), (count + 2 * kGuard) * sizeof(double));
-  if (e == hipSuccess) e = hipMemset(base + kGuard, 0, count * sizeof(double));
-  if (e == hipSuccess) e = hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(base), (int)kCanary, 2 * kGuard);
-  if (e == hipSuccess) e = hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(base + kGuard + count), (int)kCanary, 2 * kGuard);
-  if (e != hipSuccess) { (void)hipFree(base); return e; }
-  *p = base + kGuard;
-  s->guarded.emplace_back(*p, count);
-  return hipSuccess;
-}
-static void dfreeg(double *p) { if (p) (void)hipFree(p - kGuard); }
 
 hipError_t create(State **out, hipStream_t st, int N, int nS, int S, int nR, const int *off_host, const double *varpi_host,
                   int strict_rrs) {
@@ -1781,57 +1792,67 @@ hipError_t create(State **out, hipStream_t st, int N, int nS, int S, int nR, con
   s->n1_lo = 0; s->n1_hi = S;
   s->P = 16 * ((N + 15) / 16);  // device blocks are zero-padded to the MFMA tiling: P x P per matrix, P per vector
   *out = s;
-  const size_t NN = (size_t)s->P * s->P, m3 = NN * S, v3 = (size_t)s->P * S, m4 = m3 * nR, v4 = v3 * nR;
-  RCHK(dm(&s->d_off, nR));
-  RCHK(dm(&s->d_varpiR, nR));
+  RCHK(s->d_off.renew(nR));
+  RCHK(s->d_varpiR.renew(nR));
   RCHK(hipMemcpy(s->d_off, off_host, sizeof(int) * nR, hipMemcpyHostToDevice));
   RCHK(hipMemcpy(s->d_varpiR, varpi_host, sizeof(double) * nR, hipMemcpyHostToDevice));
   for (int k = 0; k < nR; ++k) s->max_off = std::max(s->max_off, std::abs(off_host[k]));
+  // This is the one enumeration of the layer arrays: an owner of nblk blocks of `block` doubles joins State::arrays, its role
+  // pointer aliases the inside.  reset_layers and count_padding walk the list by what each owner recorded.
+  using Use = GuardedBuf::Use;
+  const size_t P = s->P, NN = P * P, SR = (size_t)S * nR;
+  auto add = [s, P](double *&role, Use use, size_t block, size_t nblk) {
+    s->arrays.emplace_back();
+    GuardedBuf &g = s->arrays.back();
+    g.use = use; g.matrix = block > P; g.nblk = nblk;
+    const hipError_t e = g.renew(block * nblk);
+    if (e == hipSuccess) role = g.data();
+    return e;
+  };
+  auto add6 = [&](double *(&set)[6], size_t nblk) {  // four operators, two sources
+    for (int k = 0; k < 6; ++k) RCHK(add(set[k], Use::Layer, k < 4 ? NN : P, nblk));
+    return hipSuccess;
+  };
   for (int b = 0; b < 2; ++b) {
     for (int k = 0; k < 6; ++k) {
-      if (b == 1 && (k == R_PM || k == T_MM)) continue;
-      RCHK(dmg(s, &s->added[b][k], k < 4 ? m3 : v3));
+      // r+- / t-- of the added layer exist once (written after the doubling): the second buffer's are the first's
+      if (b == 1 && (k == R_PM || k == T_MM)) s->added[1][k] = s->added[0][k];
+      else RCHK(add(s->added[b][k], Use::Layer, k < 4 ? NN : P, S));
     }
-    for (int k = 0; k < 6; ++k) RCHK(dmg(s, &s->comp[b][k], k < 4 ? m3 : v3));
-    RCHK(dmg(s, &s->expk[b], S));
+    RCHK(add6(s->comp[b], S));
+    RCHK(add(s->expk[b], Use::Sequence, 1, S));
   }
-  s->added[1][R_PM] = s->added[0][R_PM];
-  s->added[1][T_MM] = s->added[0][T_MM];
-  for (int k = 0; k < 6; ++k) RCHK(dmg(s, &s->surf[k], k < 4 ? m3 : v3));
-  for (int k = 0; k < 10; ++k) RCHK(dmg(s, &s->smat[k], m3));
-  for (int k = 0; k < 6; ++k) RCHK(dmg(s, &s->svec[k], v3));
-  if (strict_rrs) RCHK(dmg(s, &s->jpseq, v4));
+  RCHK(add6(s->surf, S));
+  for (int k = 0; k < 10; ++k) RCHK(add(s->smat[k], Use::Scratch, NN, S));
+  for (int k = 0; k < 6; ++k) RCHK(add(s->svec[k], Use::Scratch, P, S));
+  if (strict_rrs) RCHK(add(s->jpseq, Use::Sequence, P, SR));
+  // (added and composite arrays alternate: the order of allocation is the address layout the C5 figures were measured with)
   for (int k = 0; k < 6; ++k) {
-    RCHK(dmg(s, &s->ie_added[k], k < 4 ? m4 : v4));
-    RCHK(dmg(s, &s->ie_comp[k], k < 4 ? m4 : v4));
+    RCHK(add(s->ie_added[k], Use::Layer, k < 4 ? NN : P, SR));
+    RCHK(add(s->ie_comp[k], Use::Layer, k < 4 ? NN : P, SR));
   }
-  RCHK(dm(&s->d_info, 1));
-  return hipSuccess;
+  RCHK(s->d_info.renew(1));
+  return hipMemset(s->d_info, 0, sizeof(int));
 }
 
+// doubles of nblk blocks in the ABI's memory order; the staging buffer holds at least as many afterwards
+static hipError_t stage(State *s, bool matrix, size_t nblk, size_t *nat) {
+  *nat = (size_t)s->N * (matrix ? s->N : 1) * nblk;
+  return s->d_stage.reserve(*nat, s->stream);
+}
 // one array of the layers between the ABI's memory order (host) and the padded device blocks; nblk = S or S x nR
 hipError_t upload(State *s, double *dev, const double *host, bool matrix, size_t nblk) {
-  const size_t nat = (size_t)s->N * (matrix ? s->N : 1) * nblk;
-  if (nat > s->stage_cap) {
-    (void)hipFree(s->d_stage);
-    s->d_stage = nullptr; s->stage_cap = 0;
-    RCHK(hipMalloc(reinterpret_cast<void **>(&s->d_stage), nat * sizeof(double)));
-    s->stage_cap = nat;
-  }
+  size_t nat;
+  RCHK(stage(s, matrix, nblk, &nat));
   RCHK(hipMemcpyAsync(s->d_stage, host, nat * sizeof(double), hipMemcpyHostToDevice, s->stream));
-  hipLaunchKernelGGL(k_pack, dim3(2048), dim3(256), 0, s->stream, dev, s->d_stage, s->N, matrix ? s->N : 1, s->P, nblk);
+  hipLaunchKernelGGL(k_pack, dim3(2048), dim3(256), 0, s->stream, dev, s->d_stage.get(), s->N, matrix ? s->N : 1, s->P, nblk);
   RCHK(hipGetLastError());
   return hipStreamSynchronize(s->stream);
 }
 hipError_t download(State *s, double *host, const double *dev, bool matrix, size_t nblk) {
-  const size_t nat = (size_t)s->N * (matrix ? s->N : 1) * nblk;
-  if (nat > s->stage_cap) {
-    (void)hipFree(s->d_stage);
-    s->d_stage = nullptr; s->stage_cap = 0;
-    RCHK(hipMalloc(reinterpret_cast<void **>(&s->d_stage), nat * sizeof(double)));
-    s->stage_cap = nat;
-  }
-  hipLaunchKernelGGL(k_unpack, dim3(2048), dim3(256), 0, s->stream, s->d_stage, dev, s->N, matrix ? s->N : 1, s->P, nblk);
+  size_t nat;
+  RCHK(stage(s, matrix, nblk, &nat));
+  hipLaunchKernelGGL(k_unpack, dim3(2048), dim3(256), 0, s->stream, s->d_stage.get(), dev, s->N, matrix ? s->N : 1, s->P, nblk);
   RCHK(hipGetLastError());
   RCHK(hipMemcpyAsync(host, s->d_stage, nat * sizeof(double), hipMemcpyDeviceToHost, s->stream));
   return hipStreamSynchronize(s->stream);
@@ -1839,31 +1860,8 @@ hipError_t download(State *s, double *host, const double *dev, bool matrix, size
 
 void destroy(State *s) {
   if (!s) return;
-  (void)hipFree(s->d_stage);
-  (void)hipFree(s->d_off); (void)hipFree(s->d_varpiR); (void)hipFree(s->d_out); (void)hipFree(s->d_info);
-  for (auto &g : s->guarded) dfreeg(g.first);   // every layer array (added, comp, expk, surf, smat, svec, jpseq, ie_added, ie_comp)
   for (auto e : s->ev_pool) (void)hipEventDestroy(e);
-  delete s;
-}
-
-// scene-level fast-mode features (A/B switch for profiling: MOM_RRS_FAST = bit 0 deferred elemental, bit 1 derived ier+- / iet--)
-static int fast_bits() {
-#ifdef MOM_EXPERIMENTS
-  static const int bits = [] { const char *e = getenv("MOM_RRS_FAST"); return e ? atoi(e) : MOMR_FAST_DEFAULT; }();
-  return bits;
-#else
-  return MOMR_FAST_DEFAULT;
-#endif
-}
-// experiment-only knobs: environment variables in -DMOM_EXPERIMENTS builds, constants in the shipped library
-static int exp_int(const char *name, int dflt) {
-#ifdef MOM_EXPERIMENTS
-  const char *e = getenv(name);
-  return e ? atoi(e) : dflt;
-#else
-  (void)name;
-  return dflt;
-#endif
+  delete s;  // the device memory goes with its owners (State::arrays and the MomDevBuf members)
 }
 
 void timing_reset(State *s, bool on) {
@@ -1894,49 +1892,61 @@ hipError_t timing_read(State *s, double *ms, int *launches) {
   return hipSuccess;
 }
 
-// Kernel-form switches of the handle (State::kopt, MOM_OPT_RRS_KERNELS of mom_set_option; r5 read them from the environment):
-// 16 < N <= 64: the pair kernels as one workgroup per pair (mom_rrs_wg.hpp); KOPT_WG off selects the wave-per-pair bodies
-static bool wg_pairs(const State *s) { return (s->kopt & KOPT_WG) != 0; }
-// tile count of the workgroup-per-pair image for this edge, 0 = wave-per-pair kernels (N <= 16; 16 < N <= 32 without KOPT_WG2)
-static int wg_nt(const State *s) {
-  if (!wg_pairs(s) || s->N <= 16) return 0;
-  if (s->N <= 32) return (s->kopt & KOPT_WG2) ? 2 : 0;
-  return s->N <= 48 ? 3 : 4;
-}
-static size_t wg_grid(const State *s, int nt) {  // persistent workgroups, one round of the chip
-  static const int mult = std::max(1, exp_int("MOM_RRS_WG_GRID", 1));
-  const size_t np = (size_t)(s->n1_hi - s->n1_lo) * s->nR, per_cu = (nt == 2) ? 4 : ((nt == 3) ? 2 : 1);
-  return std::max<size_t>(1, std::min<size_t>(np, 256 * per_cu * mult));
-}
-static int grid_points(const State *s) { return std::max(1, std::min((s->S + kWavesPerBlock - 1) / kWavesPerBlock, 256 * 8)); }
-static int grid_pairs(const State *s) {
-  const size_t np = (size_t)(s->n1_hi - s->n1_lo) * s->nR;
-  return (int)std::max<size_t>(1, std::min<size_t>((np + kWavesPerBlock - 1) / kWavesPerBlock, 256 * 16));
-}
-template <int NT>
-static size_t lds() { return (size_t)kWavesPerBlock * slice_bytes<NT>(); }
+// What r3 ... r5 tuned through environment variables, as measured.  (Two more, the features of the scene-level fast mode --
+// the inelastic elemental deferred into the first doubling step / formed by the tile kernel, ier+- / iet-- derived where they
+// are read -- are simply what State::fast means: profiles/r03_C5_ab.txt, second batch.)
+constexpr int kItemsPerWave = 4;     // work items per resident wave of the one-tile prefetch bodies (profiles/r05_C5_ab.txt)
+constexpr int kWgGridRounds = 1;     // rounds of the chip a persistent workgroup grid covers: 2 and 8 made no difference (profiles/r05_rrs_wg_ab.txt)
+constexpr int kWgPointMinTiles = 2;  // smallest tile count with a workgroup per point; 3 was slower at 16 < N <= 32 (profiles/r05_rrs_wg_ab.txt (12))
 
-// launch with the dynamic LDS of the image's tile count (above 64 KB the limit of the function has to be raised first)
-template <class K, class... Args>
-static hipError_t launch_lds(K kern, dim3 grid, size_t lds_bytes, hipStream_t st, Args... args) {
-  if (lds_bytes > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(64 * kWavesPerBlock), lds_bytes, st, args...);
-  return hipGetLastError();
+// tiles per operator edge of the images this handle runs (N <= 64)
+static int tiles(const State *s) { return s->P / 16; }
+// Kernel-form switches of the handle (State::kopt, MOM_OPT_RRS_KERNELS of mom_set_option; r5 read them from the environment):
+// 16 < N <= 64: the pair kernels as one workgroup per pair (mom_rrs_wg.hpp); KOPT_WG off selects the wave-per-pair bodies.
+// Tile count of the workgroup-per-pair image for this edge, 0 = wave-per-pair kernels (N <= 16; 16 < N <= 32 without KOPT_WG2)
+static int wg_nt(const State *s) {
+  if (!(s->kopt & KOPT_WG) || s->N <= 16) return 0;
+  if (s->N <= 32) return (s->kopt & KOPT_WG2) ? 2 : 0;
+  return tiles(s);
 }
-template <class T> static const void *first_arg(const T &a) { return &a; }
-template <class T, class U> static const void *first_arg(const T &a, const U &) { return &a; }
-template <class T> static int iface_arg(const T &) { return 0; }
-template <class T> static int iface_arg(const T &, int iface) { return iface; }
-#define LAUNCH_NT(s, kern, which, grid, ...)                                                               \
-  do {                                                                                                    \
-    if ((s)->N <= 16) RCHK(launch_lds(kern<1>, dim3(grid), lds<1>(), (s)->stream, __VA_ARGS__));          \
-    else if ((s)->N <= 32) RCHK(launch_lds(kern<2>, dim3(grid), lds<2>(), (s)->stream, __VA_ARGS__));     \
-    else RCHK(momr_big_launch(which, (s)->N <= 48 ? 3 : 4, 0, 0, (unsigned)(grid), (void *)(s)->stream,   \
-                              first_arg(__VA_ARGS__), iface_arg(__VA_ARGS__)));                           \
-  } while (0)
+static size_t owned_pairs(const State *s) { return (size_t)(s->n1_hi - s->n1_lo) * s->nR; }
+static unsigned grid_points(const State *s) { return (unsigned)std::max(1, std::min((s->S + kWavesPerBlock - 1) / kWavesPerBlock, 256 * 8)); }
+static unsigned grid_waves(size_t items) {  // one wave per item, at most sixteen blocks per CU
+  return (unsigned)std::max<size_t>(1, std::min<size_t>((items + kWavesPerBlock - 1) / kWavesPerBlock, 256 * 16));
+}
+
+// The point kernel of a step.  Above N = 16, where the pair kernels are workgroups: one workgroup per point (mom_rrs_wg.hpp
+// dbl_point_wg / int_point_wg: products in strips from LDS copies, Gauss-Jordan inverse over all waves; `has_wg`: the family
+// exists for this call); KOPT_WG_POINT off selects the wave-per-point kernel (operators in scratch, inverse on one wave).
+static Form point_form(const State *s, Family wave, Family wg, bool has_wg, unsigned *grid) {
+  const int nt = wg_nt(s);
+  if (has_wg && (s->kopt & KOPT_WG_POINT) && nt >= kWgPointMinTiles) {
+    *grid = (unsigned)std::max(1, std::min(s->S, 256 * 8));
+    return Form{wg, nt};
+  }
+  *grid = grid_points(s);
+  return Form{wave, tiles(s)};
+}
+// The pair kernel of a step: one workgroup per pair where wg_nt says so and the family exists, else one wave per pair.
+static Form pair_form(const State *s, Family wave, Family wg, bool has_wg) {
+  const int nt = has_wg ? wg_nt(s) : 0;
+  return nt ? Form{wg, nt} : Form{wave, tiles(s)};
+}
+// ... and its grid.  Workgroups are persistent, kWgGridRounds rounds of the chip, and walk ~np / grid pairs each.  Waves take one
+// pair each, except in the prefetch bodies: there a work item is (n1, chunk of a.dn_chunk Raman offsets), about kItemsPerWave
+// items per resident wave (`waves_per_simd` of them on 4 x 256 SIMDs), so that the n1-side operands are loaded once per
+// ~nR / nch pairs and the tail of the launch stays short.
+static unsigned pair_grid(const State *s, const Form &f, int iface, int waves_per_simd, KArgs &a) {
+  if (workgroup_form(f.family)) {
+    const size_t per_cu = (f.nt == 2) ? 4 : ((f.nt == 3) ? 2 : 1);
+    return (unsigned)std::max<size_t>(1, std::min<size_t>(owned_pairs(s), 256 * per_cu * kWgGridRounds));
+  }
+  if (!prefetch_body(f.family, f.nt, iface)) return grid_waves(owned_pairs(s));
+  const size_t span = (size_t)(s->n1_hi - s->n1_lo), want = (size_t)kItemsPerWave * waves_per_simd * 4 * 256;
+  const size_t nch = std::max<size_t>(1, std::min<size_t>((size_t)s->nR, (want + span - 1) / std::max<size_t>(span, 1)));
+  a.dn_chunk = std::min(64, (int)(((size_t)s->nR + nch - 1) / nch));  // the offsets of a chunk live in the lanes of a wave
+  return grid_waves(span * (((size_t)s->nR + a.dn_chunk - 1) / a.dn_chunk));
+}
 
 hipError_t elemental(State *s, const Streams &q, int m, int nd, int shift, const double *tau_sum, const double *tau, const double *varpi,
                      const double *Zpp, const double *Zmp, int nTerms, const double *zw, const double *fscatt,
@@ -1944,36 +1954,33 @@ hipError_t elemental(State *s, const Streams &q, int m, int nd, int shift, const
   KArgs a = base_args(s, q);
   a.m = m; a.nd = nd; a.sh = shift; a.tau_sum = tau_sum; a.tau = tau; a.varpi = varpi; a.Zpp = Zpp; a.Zmp = Zmp; a.nTerms = nTerms; a.zw = zw;
   a.fscatt = fscatt; a.Zr_pp = Zr_pp; a.Zr_mp = Zr_mp;
-  if (elastic) LAUNCH_NT(s, k_el_point, 0, grid_points(s), a);
+  if (elastic) RCHK(launch(s, Form{Family::ElPoint, tiles(s)}, grid_points(s), a));
   s->el_pending = false;
   if (inelastic) {
     // scene-level fast mode: the tile form (k_ie_elemental_tile).  For a layer with doublings the alternative is to form the layer
     // inside the first doubling step (fuse_el): KOPT_EL_FUSE_ON / _OFF (neither: only above N = 48; below, the separate tile kernel +
     // the plain first step measured faster, profiles/r05_C5_ab.txt (5)).  KOPT_EL_TILE off: the element-wise kernel below / the fused form as in r4.
     const bool el_tile = (s->kopt & KOPT_EL_TILE) != 0;
-    const int el_fuse_env = (s->kopt & KOPT_EL_FUSE_ON) ? 1 : ((s->kopt & KOPT_EL_FUSE_OFF) ? 0 : -1);
-    const bool el_fuse = el_fuse_env >= 0 ? el_fuse_env == 1 : s->N > 48;  // 4 x 4 tiles: the fused form stays ahead (N = 60: 414 vs 420 ms per run)
-    if (s->fast && nd >= 1 && (fast_bits() & 1) && (el_fuse || !el_tile)) {  // deferred into the first doubling step (k_dbl_pair, fuse_el)
+    const int el_fuse_opt = (s->kopt & KOPT_EL_FUSE_ON) ? 1 : ((s->kopt & KOPT_EL_FUSE_OFF) ? 0 : -1);
+    const bool el_fuse = el_fuse_opt >= 0 ? el_fuse_opt == 1 : s->N > 48;  // 4 x 4 tiles: the fused form stays ahead (N = 60: 414 vs 420 ms per run)
+    if (s->fast && nd >= 1 && (el_fuse || !el_tile)) {  // deferred into the first doubling step (k_dbl_pair, fuse_el)
       s->el_pending = true;
       s->el.m = m; s->el.nd = nd; s->el.sh = shift; s->el.tau_sum = tau_sum; s->el.tau = tau; s->el.varpi = varpi;
       s->el.fscatt = fscatt; s->el.Zr_pp = Zr_pp; s->el.Zr_mp = Zr_mp;
       return hipSuccess;
     }
-    if (s->fast && (fast_bits() & 1) && el_tile) {
-      const bool derive = !s->strict_rrs && (fast_bits() & 2);
+    if (s->fast && el_tile) {
+      const bool derive = !s->strict_rrs;
       a.derive_pm = derive ? 1 : 0;  // (read by the ND0 image only)
+      Form f{Family::TileElemental, tiles(s)};
+      f.nd0 = nd < 1;
       RCHK(tick(s, TK_IE_ELEMENTAL, true));
-      if ((size_t)(s->n1_hi - s->n1_lo) * s->nR) {
-        const dim3 gr(grid_pairs(s));
-        if (s->N <= 16) { if (nd < 1) RCHK(launch_lds((k_ie_elemental_tile<1, true>), gr, lds<1>(), s->stream, a)); else RCHK(launch_lds((k_ie_elemental_tile<1, false>), gr, lds<1>(), s->stream, a)); }
-        else if (s->N <= 32) { if (nd < 1) RCHK(launch_lds((k_ie_elemental_tile<2, true>), gr, lds<2>(), s->stream, a)); else RCHK(launch_lds((k_ie_elemental_tile<2, false>), gr, lds<2>(), s->stream, a)); }
-        else RCHK(momr_big_launch(8, s->N <= 48 ? 3 : 4, nd < 1 ? 1 : 0, 0, gr.x, (void *)s->stream, &a, 0));
-      }
+      if (owned_pairs(s)) RCHK(launch(s, f, grid_waves(owned_pairs(s)), a));  // empty owned range: nothing to do
       RCHK(tick(s, TK_IE_ELEMENTAL, false));
       if (nd < 1) { s->pm_valid = !derive; s->pm_derivable = true; }
       return hipSuccess;
     }
-    const size_t tot = (size_t)s->N * s->N * (size_t)(s->n1_hi - s->n1_lo) * s->nR;
+    const size_t tot = (size_t)s->N * s->N * owned_pairs(s);
     RCHK(tick(s, TK_IE_ELEMENTAL, true));
     if (tot) hipLaunchKernelGGL(k_ie_elemental, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s->stream, a);  // empty owned range: nothing to do
     RCHK(hipGetLastError());
@@ -1994,7 +2001,7 @@ hipError_t ensure_pm(State *s, const Streams &q) {
 
 hipError_t doubling(State *s, const Streams &q, int nd) {
   if (nd == 0) return hipSuccess;  // doubling_inelastic.jl:29
-  const bool derive = s->fast && !s->strict_rrs && (fast_bits() & 2);
+  const bool derive = s->fast && !s->strict_rrs;
   for (int k = 0; k < nd; ++k) {
     KArgs a = base_args(s, q);
     a.last = (k == nd - 1);
@@ -2005,42 +2012,15 @@ hipError_t doubling(State *s, const Streams &q, int nd) {
       a.fscatt = s->el.fscatt; a.Zr_pp = s->el.Zr_pp; a.Zr_mp = s->el.Zr_mp;
       s->el_pending = false;
     }
-    // above N = 16: one workgroup per point (mom_rrs_wg.hpp dbl_point_wg: products in strips from LDS copies, Gauss-Jordan inverse
-    // over all waves); KOPT_WG_POINT off selects the wave-per-point kernel (operators in scratch, inverse on one wave)
-    const bool wg_point = (s->kopt & KOPT_WG_POINT) != 0;
-    static const int wg_point_min = exp_int("MOM_RRS_WG_POINT_MIN", 2);  // smallest tile count
-    if (wg_point && wg_nt(s) >= wg_point_min)
-      RCHK(momr_big_launch(7, wg_nt(s), 0, 0, (unsigned)std::max(1, std::min(s->S, 256 * 8)), (void *)s->stream, &a, 0));
-    else LAUNCH_NT(s, k_dbl_point, 1, grid_points(s), a);
+    unsigned grid;
+    const Form point = point_form(s, Family::DblPoint, Family::DblPointWg, true, &grid);
+    RCHK(launch(s, point, grid, a));
+    Form pair = pair_form(s, Family::DblPair, Family::DblPairWg, true);
+    pair.fuse_el = a.fuse_el != 0;
+    pair.mode = s->strict_rrs ? 2 : (a.last ? 1 : 0);
+    grid = pair_grid(s, pair, 0, 3, a);  // dbl_pair_body1 runs at three waves per SIMD
     RCHK(tick(s, TK_DBL_PAIR, true));
-    {
-      dim3 gr(grid_pairs(s));
-      size_t lds1 = lds<1>();
-      if (MOMR_LDSPF != 0 && s->N <= 16) {
-        // work items (n1, chunk of Raman offsets) of dbl_pair_body1: about four items per resident wave, so that
-        // the n1-side operands are loaded once per ~nR / nch pairs and the tail of the launch stays short
-        static const int ipw = exp_int("MOMR_ITEMS_PER_WAVE", 4);
-        const size_t span = (size_t)(s->n1_hi - s->n1_lo), want = (size_t)std::max(ipw, 1) * 3 * 4 * 256;
-        const size_t nch = std::max<size_t>(1, std::min<size_t>((size_t)s->nR, (want + span - 1) / std::max<size_t>(span, 1)));
-        a.dn_chunk = std::min(64, (int)(((size_t)s->nR + nch - 1) / nch));  // the offsets of a chunk live in the lanes of a wave
-        const size_t items = span * (((size_t)s->nR + a.dn_chunk - 1) / a.dn_chunk);
-        gr = dim3((unsigned)std::max<size_t>(1, std::min<size_t>((items + kWavesPerBlock - 1) / kWavesPerBlock, 256 * 16)));
-        lds1 = (size_t)kWavesPerBlock * (slice_bytes<1>() + kPfBytes);
-      }
-      const int mode = s->strict_rrs ? 2 : (a.last ? 1 : 0);
-#define DBL_PAIR(NT_, FUSE_, MODE_) RCHK(launch_lds(k_dbl_pair##NT_<FUSE_, MODE_>, gr, (NT_ == 1) ? lds1 : lds<NT_>(), s->stream, a))
-#define DBL_PAIR_M(NT_, FUSE_) do { if (mode == 0) DBL_PAIR(NT_, FUSE_, 0); else if (mode == 1) DBL_PAIR(NT_, FUSE_, 1); else DBL_PAIR(NT_, FUSE_, 2); } while (0)
-#define DBL_PAIR_F(NT_) do { if (a.fuse_el) DBL_PAIR_M(NT_, true); else DBL_PAIR_M(NT_, false); } while (0)
-      if (const int nt = wg_nt(s)) {  // one workgroup per pair (mom_rrs_wg.hpp): each walks ~np / grid pairs
-        RCHK(momr_big_launch(5, nt, a.fuse_el ? 1 : 0, mode, (unsigned)wg_grid(s, nt), (void *)s->stream, &a, 0));
-      } else if (s->N <= 16) DBL_PAIR_F(1);
-      else if (s->N <= 32) DBL_PAIR_F(2);
-      else RCHK(momr_big_launch(3, s->N <= 48 ? 3 : 4, a.fuse_el ? 1 : 0, mode, gr.x, (void *)s->stream, &a, 0));
-#undef DBL_PAIR_F
-#undef DBL_PAIR_M
-#undef DBL_PAIR
-      RCHK(hipGetLastError());
-    }
+    RCHK(launch(s, pair, grid, a));
     RCHK(tick(s, TK_DBL_PAIR, false));
     s->cur = 1 - s->cur;
   }
@@ -2064,18 +2044,19 @@ hipError_t doubling(State *s, const Streams &q, int nd) {
 
 hipError_t copy_added_to_composite(State *s, const Streams &q) {
   RCHK(ensure_pm(s, q));
-  const size_t NN = (size_t)s->P * s->P, m3 = NN * s->S * 8, v3 = (size_t)s->P * s->S * 8, m4 = m3 * s->nR, v4 = v3 * s->nR;
   static const int amap[6] = {R_MP, R_PM, T_PP, T_MM, J0P, J0M};  // composite field k <- added field amap[k]
   for (int k = 0; k < 6; ++k) {
-    RCHK(hipMemcpyAsync(s->comp[s->ccur][k], s->added[s->cur][amap[k]], k < 4 ? m3 : v3, hipMemcpyDeviceToDevice, s->stream));
+    const size_t el = (k < 4 ? (size_t)s->P * s->P : (size_t)s->P) * s->S * sizeof(double), ie = el * s->nR;
+    RCHK(hipMemcpyAsync(s->comp[s->ccur][k], s->added[s->cur][amap[k]], el, hipMemcpyDeviceToDevice, s->stream));
     if (s->fast && !s->strict_rrs && k < 4) {
       // scene-level run, corrected position (the strict one reads stale ier+- / iet-- of the added layer's OWN arrays, D5):
       // the four 4-D operator arrays (2.5 GB each at C5) change roles instead of being copied -- the next
       // layer's elemental overwrites every block of the added layer's arrays before anything reads them, and the entries
-      // off the grid are zero in both sets (nothing ever writes them)
+      // off the grid are zero in both sets (nothing ever writes them).  Only the role pointers change hands: the two
+      // arrays have the same shape and the same Use, so State::arrays, which is keyed by allocation, describes them as before.
       std::swap(s->ie_comp[k], s->ie_added[amap[k]]);
     } else {
-      RCHK(hipMemcpyAsync(s->ie_comp[k], s->ie_added[amap[k]], k < 4 ? m4 : v4, hipMemcpyDeviceToDevice, s->stream));
+      RCHK(hipMemcpyAsync(s->ie_comp[k], s->ie_added[amap[k]], ie, hipMemcpyDeviceToDevice, s->stream));
     }
   }
   return hipSuccess;
@@ -2089,47 +2070,24 @@ hipError_t interaction(State *s, const Streams &q, int iface, bool with_surface)
     return hipErrorInvalidValue;
   }
   KArgs a = base_args(s, q);
-  a.derive_pm = (!with_surface && !s->strict_rrs && s->fast && s->pm_derivable && (fast_bits() & 2)) ? 1 : 0;
+  a.derive_pm = (!with_surface && !s->strict_rrs && s->fast && s->pm_derivable) ? 1 : 0;
   if (!with_surface && !a.derive_pm) RCHK(ensure_pm(s, q));
   for (int k = 0; k < 6; ++k) a.x[k] = with_surface ? s->surf[k] : s->added[s->cur][k];
   if (!with_surface) { a.x[R_PM] = s->added[0][R_PM]; a.x[T_MM] = s->added[0][T_MM]; }
-  const bool wg_point = (s->kopt & KOPT_WG_POINT) != 0;
-  static const int wg_point_min = exp_int("MOM_RRS_WG_POINT_MIN", 2);
-  if (wg_point && iface == 3 && wg_nt(s) >= wg_point_min)  // one workgroup per point (mom_rrs_wg.hpp int_point_wg)
-    RCHK(momr_big_launch(9, wg_nt(s), 0, 0, (unsigned)std::max(1, std::min(s->S, 256 * 8)), (void *)s->stream, &a, 0));
-  else LAUNCH_NT(s, k_int_point, 2, grid_points(s), a, iface);
+  unsigned grid;
+  const Form point = point_form(s, Family::IntPoint, Family::IntPointWg, iface == 3, &grid);  // workgroup forms: interface 11 only
+  RCHK(launch(s, point, grid, a, iface));
   if (iface == 0) {  // interaction_inelastic.jl:16-17
-    const size_t v4 = (size_t)s->P * s->S * s->nR * 8;
+    const size_t v4 = (size_t)s->P * s->S * s->nR * sizeof(double);
     RCHK(hipMemsetAsync(s->ie_comp[C_J0P], 0, v4, s->stream));
     RCHK(hipMemsetAsync(s->ie_comp[C_J0M], 0, v4, s->stream));
   } else {
+    Form pair = pair_form(s, Family::IntPair, Family::IntPairWg, iface == 3);
+    pair.surface = with_surface;
+    pair.derive = a.derive_pm != 0;
+    grid = pair_grid(s, pair, iface, 2, a);  // int_pair_body1 runs at two waves per SIMD
     RCHK(tick(s, TK_INT_PAIR, true));
-    dim3 gr(grid_pairs(s));
-    size_t lds1 = lds<1>();
-    if (MOMR_LDSPF != 0 && s->N <= 16 && iface == 3) {  // int_pair_body1: (n1, chunk) items, as for the doubling pair kernel
-      static const int ipw = exp_int("MOMR_ITEMS_PER_WAVE", 4);
-      const size_t span = (size_t)(s->n1_hi - s->n1_lo), want = (size_t)std::max(ipw, 1) * 2 * 4 * 256;
-      const size_t nch = std::max<size_t>(1, std::min<size_t>((size_t)s->nR, (want + span - 1) / std::max<size_t>(span, 1)));
-      a.dn_chunk = std::min(64, (int)(((size_t)s->nR + nch - 1) / nch));
-      const size_t items = span * (((size_t)s->nR + a.dn_chunk - 1) / a.dn_chunk);
-      gr = dim3((unsigned)std::max<size_t>(1, std::min<size_t>((items + kWavesPerBlock - 1) / kWavesPerBlock, 256 * 16)));
-      lds1 = (size_t)kWavesPerBlock * (slice_bytes<1>() + kPfIntBytes);
-    }
-#define INT_PAIR(NT_)                                                                                                      \
-  do {                                                                                                                     \
-    const size_t l_ = (NT_ == 1) ? lds1 : lds<NT_>();                                                                       \
-    if (with_surface) RCHK(launch_lds(k_int_pair##NT_<true, false>, gr, l_, s->stream, a, iface));                         \
-    else if (a.derive_pm) RCHK(launch_lds(k_int_pair##NT_<false, true>, gr, l_, s->stream, a, iface));                     \
-    else RCHK(launch_lds(k_int_pair##NT_<false, false>, gr, l_, s->stream, a, iface));                                     \
-  } while (0)
-    const int nt_wg = (iface == 3) ? wg_nt(s) : 0;
-    if (nt_wg) {  // one workgroup per pair (mom_rrs_wg.hpp)
-      RCHK(momr_big_launch(6, nt_wg, with_surface ? 1 : 0, a.derive_pm ? 1 : 0, (unsigned)wg_grid(s, nt_wg), (void *)s->stream, &a, iface));
-    } else if (s->N <= 16) INT_PAIR(1);
-    else if (s->N <= 32) INT_PAIR(2);
-    else RCHK(momr_big_launch(4, s->N <= 48 ? 3 : 4, with_surface ? 1 : 0, a.derive_pm ? 1 : 0, gr.x, (void *)s->stream, &a, iface));
-#undef INT_PAIR
-    RCHK(hipGetLastError());
+    RCHK(launch(s, pair, grid, a, iface));
     RCHK(tick(s, TK_INT_PAIR, false));
   }
   s->ccur = 1 - s->ccur;
@@ -2163,33 +2121,22 @@ __global__ void k_count_canary(const unsigned *p, size_t n, unsigned long long *
     if (p[e] != kCanary) ++mine;
   if (mine) atomicAdd(cnt, mine);
 }
+}  // namespace momr
+template class __attribute__((visibility("hidden"))) MomDevBuf<unsigned long long>;  // the counter below: no new export
+namespace momr {
 hipError_t count_padding(State *s, unsigned long long *out) {
-  unsigned long long *d = nullptr;
-  RCHK(hipMalloc(reinterpret_cast<void **>(&d), sizeof(unsigned long long)));
-  RCHK(hipMemsetAsync(d, 0, sizeof(unsigned long long), s->stream));
-  auto scan = [&](const double *p, bool matrix, size_t nblk) {
-    if (p) hipLaunchKernelGGL(k_count_padding, dim3(1024), dim3(256), 0, s->stream, p, s->N, s->P, matrix ? 1 : 0, nblk, d);
-  };
-  const size_t S = s->S, SR = S * (size_t)s->nR;
-  for (int b = 0; b < 2; ++b)
-    for (int k = 0; k < 6; ++k) {
-      if (!(b == 1 && (k == R_PM || k == T_MM))) scan(s->added[b][k], k < 4, S);
-      scan(s->comp[b][k], k < 4, S);
-    }
-  for (int k = 0; k < 6; ++k) {
-    scan(s->surf[k], k < 4, S);
-    scan(s->ie_added[k], k < 4, SR);
-    scan(s->ie_comp[k], k < 4, SR);
+  MomDevBuf<unsigned long long> cnt;  // freed on every return (freeing waits for the launches below)
+  RCHK(cnt.renew(1));
+  RCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), s->stream));
+  for (const GuardedBuf &g : s->arrays) {
+    if (g.use == GuardedBuf::Use::Layer)
+      hipLaunchKernelGGL(k_count_padding, dim3(1024), dim3(256), 0, s->stream, g.data(), s->N, s->P, g.matrix ? 1 : 0, g.nblk, cnt.get());
+    for (const double *band : {g.data() - kGuard, g.data() + g.count})
+      hipLaunchKernelGGL(k_count_canary, dim3(8), dim3(256), 0, s->stream, reinterpret_cast<const unsigned *>(band), 2 * kGuard, cnt.get());
   }
-  for (auto &g : s->guarded) {
-    hipLaunchKernelGGL(k_count_canary, dim3(8), dim3(256), 0, s->stream, reinterpret_cast<const unsigned *>(g.first - kGuard), 2 * kGuard, d);
-    hipLaunchKernelGGL(k_count_canary, dim3(8), dim3(256), 0, s->stream, reinterpret_cast<const unsigned *>(g.first + g.second), 2 * kGuard, d);
-  }
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  (void)hipFree(d);
-  return e;
+  RCHK(hipGetLastError());
+  RCHK(hipMemcpyAsync(out, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
+  return hipStreamSynchronize(s->stream);
 }
 
 // rt_run allocates its added / composite / surface layers zeroed on every call (rt_run.jl:108-116: make_added_layer /
@@ -2199,20 +2146,8 @@ hipError_t count_padding(State *s, unsigned long long *out) {
 // operator-level uploads leave arbitrary values.  A corrected-position scene-level run itself is stateless: every block
 // it reads it has written before in the same run, and the entries off the grid are never written (they stay zero).
 hipError_t reset_layers(State *s) {
-  const size_t NN = (size_t)s->P * s->P, m3 = NN * s->S * 8, v3 = (size_t)s->P * s->S * 8, m4 = m3 * s->nR, v4 = v3 * s->nR;
-  for (int b = 0; b < 2; ++b) {
-    for (int k = 0; k < 6; ++k) {
-      if (!(b == 1 && (k == R_PM || k == T_MM))) RCHK(hipMemsetAsync(s->added[b][k], 0, k < 4 ? m3 : v3, s->stream));
-      RCHK(hipMemsetAsync(s->comp[b][k], 0, k < 4 ? m3 : v3, s->stream));
-    }
-    RCHK(hipMemsetAsync(s->expk[b], 0, (size_t)s->S * 8, s->stream));
-  }
-  for (int k = 0; k < 6; ++k) {
-    RCHK(hipMemsetAsync(s->surf[k], 0, k < 4 ? m3 : v3, s->stream));
-    RCHK(hipMemsetAsync(s->ie_added[k], 0, k < 4 ? m4 : v4, s->stream));
-    RCHK(hipMemsetAsync(s->ie_comp[k], 0, k < 4 ? m4 : v4, s->stream));
-  }
-  if (s->jpseq) RCHK(hipMemsetAsync(s->jpseq, 0, v4, s->stream));
+  for (const GuardedBuf &g : s->arrays)
+    if (g.use != GuardedBuf::Use::Scratch) RCHK(hipMemsetAsync(g.data(), 0, g.count * sizeof(double), s->stream));
   return hipSuccess;
 }
 
@@ -2223,12 +2158,11 @@ hipError_t begin_run(State *s, int nVza) {
   s->pm_valid = true; s->pm_derivable = false; s->el_pending = false;
   const size_t cnt = (size_t)5 * nVza * s->nS * s->S + (size_t)2 * s->nS * s->S;
   if (s->out_nVza != nVza) {
-    (void)hipFree(s->d_out);
-    s->d_out = nullptr;
-    RCHK(hipMalloc(reinterpret_cast<void **>(&s->d_out), cnt * 8));
+    s->out_nVza = 0;
+    RCHK(s->d_out.renew(cnt));
     s->out_nVza = nVza;
   }
-  return hipMemsetAsync(s->d_out, 0, cnt * 8, s->stream);
+  return hipMemsetAsync(s->d_out, 0, cnt * sizeof(double), s->stream);
 }
 
 hipError_t postprocess(State *s, const Streams &q, int m, int nVza, const int *d_node, const double *d_cos, const double *d_sin,
@@ -2237,7 +2171,7 @@ hipError_t postprocess(State *s, const Streams &q, int m, int nVza, const int *d
   a.m = m; a.weight = weight;
   for (int k = 0; k < 6; ++k) a.x[k] = s->surf[k];
   const size_t tot = (size_t)nVza * s->nS * s->S;
-  hipLaunchKernelGGL(k_post, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s->stream, a, nVza, d_node, d_cos, d_sin, M, s->d_out);
+  hipLaunchKernelGGL(k_post, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s->stream, a, nVza, d_node, d_cos, d_sin, M, s->d_out.get());
   return hipGetLastError();
 }
 

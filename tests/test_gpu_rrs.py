@@ -353,7 +353,7 @@ def test_rrs_zero_padding_invariant(rtamd, nS, lt, nv, strict):
     """The device blocks of the RRS layers are zero-padded to the MFMA tiling (16 x 16 at N <= 16, 32 x 32 above) and the kernels
     store WHOLE tiles: every stored quantity must keep the padding at exact zeros.  mom_rrs_check_padding counts
     the violations over all layer arrays after a scene-level run (which goes through every kernel of the path) -- and, r5, the
-    damaged words of the 16 KB guard bands every layer array is allocated between (mom_rrs.hip dmg): an unmasked store that lands
+    damaged words of the 16 KB guard bands every layer array is allocated between (mom_rrs.hpp GuardedBuf): an unmasked store that lands
     before the first or behind the last block of ANY array is a violation too, for one-tile ... 4 x 4-tile images."""
     rt = rtamd.corert
     m = rtamd.scenes.make_scene(nS, lt, 3, 26, seed=2 + nS + lt, aerosol_total=0.1, **VIEWS[nv])
@@ -375,14 +375,27 @@ def test_rrs_zero_padding_invariant(rtamd, nS, lt, nv, strict):
         assert h.rrs_check_padding() == 0
 
 
-@pytest.mark.parametrize("nS,lt,S,Nz", [(4, 9, 12, 2), (3, 21, 10, 2), (4, 21, 8, 2), (3, 33, 8, 2)])   # N = 32, 42, 56, 60: 2, 3, 4, 4 waves per pair
+# N = 32, 42, 56, 60: 2, 3, 4, 4 waves per pair; nd0: the first layer's ndoubl forced to 0 (the ids of the other cases are the old ones)
+@pytest.mark.parametrize("nS,lt,S,Nz,nd0", [pytest.param(4, 9, 12, 2, False, id="4-9-12-2"), pytest.param(3, 21, 10, 2, False, id="3-21-10-2"),
+                                            pytest.param(4, 21, 8, 2, False, id="4-21-8-2"), pytest.param(3, 33, 8, 2, False, id="3-33-8-2"),
+                                            pytest.param(1, 21, 12, 2, False, id="1-21-12-2"),   # N = 14: the one-tile pair kernel with the fused elemental
+                                            pytest.param(3, 23, 8, 2, False, id="3-23-8-2"),     # N = 45: 3 x 3 tiles without k-step guards
+                                            pytest.param(4, 9, 12, 2, True, id="4-9-12-2-nd0"), pytest.param(3, 21, 10, 2, True, id="3-21-10-2-nd0"),
+                                            pytest.param(3, 33, 8, 2, True, id="3-33-8-2-nd0")])
 @pytest.mark.parametrize("strict", [True, False])
-def test_rrs_workgroup_and_wave_kernels_agree(rtamd, nS, lt, S, Nz, strict):
+def test_rrs_workgroup_and_wave_kernels_agree(rtamd, nS, lt, S, Nz, nd0, strict):
     """Above N = 16 the RRS pair kernels run as one WORKGROUP per pair (mom_rrs_wg.hpp: column strips per wave, left factors from
     LDS); MOM_OPT_RRS_KERNELS without bit 0 selects the wave-per-pair bodies they replace.  Both execute the same products in the
     same order on the same operands, so a scene-level run must agree to rounding of the last place -- asserted at 1e-13 of the
     elastic intensity, three orders below the parity bound against the restatement (which test_rt_run_rrs_parity holds for the
-    workgroup form).  (r5 needed a process per switch position: the switches were environment variables read once.)"""
+    workgroup form).  (r5 needed a process per switch position: the switches were environment variables read once.)
+
+    nd0: no seeded scene above N = 20 has a layer without doublings, so the ND0 image of the tile-form elemental kernel
+    (k_ie_elemental_tile<NT, true>: the D kernels applied at once, ier+- / iet-- not stored in the corrected position) at
+    2 x 2, 3 x 3 and 4 x 4 tiles was reached by no test that looks at values.  The prepared ndoubl of the first layer is set to 0
+    on both sides -- the run then takes that layer's optical thickness in one elemental step, coarser physics but the same
+    arithmetic for every form -- and the default forms are held against the element-wise kernel (mask without bit 3) under
+    that pair's bound of the cases above."""
     rt = rtamd.corert
     m = rtamd.scenes.make_scene(nS, lt, Nz, S, seed=nS + lt + S, aerosol_total=0.1)
     offs = np.asarray([-4, -1, 2, 7, 3])
@@ -390,17 +403,106 @@ def test_rrs_workgroup_and_wave_kernels_agree(rtamd, nS, lt, S, Nz, strict):
     RS = rt.RRS(greek_raman=rt.get_greek_rayleigh(0.2), ϖ_Cabannes=0.96, ϖ_λ1λ0=vp, i_λ1λ0=offs, rrs_strict_reference=bool(strict))
     # mask bits: 1 workgroup per pair, 2 ... for 16 < N <= 32 too, 4 workgroup per point, 8 tile-form elemental, 16 / 32 the
     # inelastic elemental layer formed inside the first doubling step always / never.
-    # "point": the point kernels as one wave per point; "fuse": elemental inside the first doubling step; "elementwise": r4's kernel
-    masks = {"0": 2 | 4 | 8, "1": 15, "point": 1 | 2 | 8, "fuse": 15 | 16, "fuse0": 2 | 4 | 8 | 16, "elementwise": 1 | 2 | 4}
+    # "point": the point kernels as one wave per point; "fuse": elemental inside the first doubling step; "nofuse": never there (the
+    # default above N = 48 is "fuse": without this mask the 4 x 4-tile elemental kernel of a layer with doublings would not run);
+    # "elementwise": r4's kernel
+    masks = {"0": 2 | 4 | 8, "1": 15, "point": 1 | 2 | 8, "fuse": 15 | 16, "fuse0": 2 | 4 | 8 | 16, "nofuse": 15 | 32,
+             "elementwise": 1 | 2 | 4}
+    if nd0:
+        masks = {"0": 15, "elementwise": 1 | 2 | 4}
+    model = rt._with_cabannes(RS, m)
+    sc = rtamd.prepare_scene(model)
+    assert int(sc.N) == {(1, 21): 14, (4, 9): 32, (3, 21): 42, (3, 23): 45, (4, 21): 56, (3, 33): 60}[(nS, lt)]
+    if nd0:
+        assert sc.ndoubl[0] > 0 and sc.ndoubl[1] > 0
+        sc.ndoubl = np.concatenate([[0], sc.ndoubl[1:]]).astype(sc.ndoubl.dtype)
     out = {}
     for wg, mask in masks.items():
-        out[wg] = dict(zip(("R", "T", "ieR", "ieT", "hdr", "up", "dw"), rt.rt_run_rrs(RS, m, kernels=mask)))
-        out[wg]["N"] = rtamd.prepare_scene(rt._with_cabannes(RS, m)).N
-    assert int(out["0"]["N"]) == {(4, 9): 32, (3, 21): 42, (4, 21): 56, (3, 33): 60}[(nS, lt)]
+        got = _run_prepared(rtamd, RS, model, sc, mask) if nd0 else rt.rt_run_rrs(RS, m, kernels=mask)
+        out[wg] = dict(zip(("R", "T", "ieR", "ieT", "hdr", "up", "dw"), got))
     scale = np.abs(out["0"]["R"][:, 0:1, :]).max()
     assert np.abs(out["0"]["ieR"]).max() > 0
-    for other in ("1", "point", "fuse", "fuse0", "elementwise"):
+    for other in masks:
+        if other == "0":
+            continue
         for k in ("R", "T", "ieR", "ieT", "hdr", "up", "dw"):
             d = np.abs(out["0"][k] - out[other][k]).max()
             # the element-wise elemental kernel evaluates 1 - exp(-(x + y)) where the tile forms evaluate 1 - exp(-x) exp(-y)
             assert d <= (1e-11 if other == "elementwise" else 1e-13) * scale, (other, k, d, scale)
+
+
+def _load_and_run(rt, h, RS, model, sc):
+    """The prepared scene `sc` of `model` and its Raman inputs onto the handle, one scene-level run, the 7-tuple of rt_run_rrs."""
+    Zr_pp, Zr_mp = rt.raman_z(RS, model)
+    rt.scene_set(h, sc)
+    h.scene_set_rrs(np.ascontiguousarray(rt.fscatt_rayleigh(model).T), rt._abi_mats(Zr_pp), rt._abi_mats(Zr_mp))
+    h.rt_run_rrs()
+    hdr, up, dw = h.get_hdr_rrs()
+    return h.get_RT_rrs()[:4] + (hdr, up[0], dw[0])
+
+
+def _run_prepared(rtamd, RS, model, sc, kernels):
+    """corert.rt_run_rrs for a scene that was changed after prepare_scene (whole axis owned, fresh handle)."""
+    rt = rtamd.corert
+    with rt.make_handle(model) as h:
+        h.set_option(rtamd._lib.MOM_OPT_STRIP_PAD, 0)
+        h.set_option(rtamd._lib.MOM_OPT_RRS_KERNELS, int(kernels))
+        h.rrs_set(RS.i_λ1λ0, RS.ϖ_λ1λ0, RS.rrs_strict_reference)
+        return _load_and_run(rt, h, RS, model, sc)
+
+
+@pytest.mark.parametrize("strict", [True, False])
+def test_rrs_one_handle_changing_shapes(rtamd, strict):
+    """What a handle's RRS state owns changes shape under it: a scene with three views after one with one (the output block is
+    resized), then mom_rrs_set with two Raman offsets instead of five (the state is destroyed and created), then the first
+    geometry again.  Every run equals a fresh handle's run of the same inputs bit for bit, and the padding and the guard bands
+    are intact after each.  N = 15 (nS = 3, l_trunc = 5, one view; ndoubl = 0, 4, 11), Nz = 3, S = 24.  The three views share
+    the zenith angle of the one (three azimuths): a view at another zenith angle is one more stream, and N belongs to the handle."""
+    rt = rtamd.corert
+    one, three = VIEWS[1], dict(vza=(30.0, 30.0, 30.0), vaz=(20.0, 45.0, 120.0))
+    scenes = {k: rtamd.scenes.make_scene(3, 5, 3, 24, seed=9, aerosol_total=0.1, **v) for k, v in (("one", one), ("three", three))}
+    offs5, offs2 = [-4, -1, 2, 7, 3], [-4, 2]
+    steps = [("one", offs5), ("three", offs5), ("one", offs2)]
+    RS0, _ = _rrs_inputs(rtamd, offs5, strict)
+    fresh = {}
+    with rt.make_handle(rt._with_cabannes(RS0, scenes["one"])) as h:
+        h.set_option(rtamd._lib.MOM_OPT_STRIP_PAD, 0)
+        assert h.N == 15
+        resident = None
+        for views, offs in steps:
+            RS, _ = _rrs_inputs(rtamd, offs, strict)
+            if offs is not resident:
+                h.rrs_set(RS.i_λ1λ0, RS.ϖ_λ1λ0, strict)
+                assert h.rrs_check_padding() == 0
+                resident = offs
+            model = rt._with_cabannes(RS, scenes[views])
+            sc = rtamd.prepare_scene(model)
+            assert sc.N == 15 and len(sc.node) == (3 if views == "three" else 1)
+            got = _load_and_run(rt, h, RS, model, sc)
+            assert h.rrs_check_padding() == 0
+            key = (views, len(offs))
+            if key not in fresh:
+                fresh[key] = rt.rt_run_rrs(RS, scenes[views])
+            assert np.abs(fresh[key][2]).max() > 0
+            for k, name in enumerate(("R", "T", "ieR", "ieT", "hdr", "bhr_uw", "bhr_dw")):
+                assert got[k].shape == fresh[key][k].shape and np.array_equal(got[k], fresh[key][k]), (views, len(offs), name)
+
+
+def test_rrs_staging_buffer_grows_in_both_directions(rtamd):
+    """mom_rrs_upload / mom_rrs_download go through one staging buffer that grows on demand: a vector field up (small), a 4-D
+    operator field down (the buffer grows inside the download; the untouched layer reads as zeros), a 4-D field up and down
+    again, the vector field down through the grown buffer.  N = 27 (2 x 2 tiles, 5 rows of padding), S = 12, five offsets."""
+    S, offs = 12, [-4, -1, 2, 7, 3]
+    m, h = model_and_handle(rtamd, 3, 11, S)
+    with h:
+        N, nR = h.N, len(offs)
+        assert N == 27
+        h.rrs_set(offs, np.ones(nR), False)
+        rng = np.random.default_rng(11)
+        vec, op4 = rng.standard_normal(N * S), rng.standard_normal(N * N * S * nR)
+        h.rrs_upload(4, vec)                                    # j0+ of the added layer
+        assert not np.any(h.rrs_download(19))                   # ier-+: four-dimensional, never written
+        h.rrs_upload(19, op4)
+        assert np.array_equal(h.rrs_download(19), op4)
+        assert np.array_equal(h.rrs_download(4), vec)
+        assert h.rrs_check_padding() == 0
