@@ -613,6 +613,16 @@ int mom_timers(mom_t *h, double *ms, int n, int *kernel_launches);
  *                         operator-level calls, the finishers, the surface kernel, the other images and the Float32 handles never
  *                         take this form; with MOM_OPT_M0_REDUCTION = 0 the one launch carries moment 0 and keeps all four
  *                         operators.  0 = every launch updates all four.  No output and no return value depends on the option.
+ *   MOM_OPT_ELEMENTAL     1 (default) = the two-buffer strip image (edges 52 / 56 / 60, default scheduling mode) and the quad-block
+ *                         image build the elemental layer in its table form (csrc/mom_elemental_tab.hpp).  The layer-independent
+ *                         stream-pair tables 1/mu_i + 1/mu_j, mu_j/(mu_i + mu_j), mu_j/(mu_i - mu_j) are computed once per scene on
+ *                         the device (mom_scene_set and its kin) instead of once per layer and unit; a layer evaluates only
+ *                         1 - exp(-dtau (1/mu_i + 1/mu_j)), on the pairs i <= j; the elements are formed in batches of four, all
+ *                         operands requested together, every alternative computed with the expressions of the other form and picked
+ *                         by select.  It applies to regular streams, two phase-matrix bases and an edge of whole streams; any other
+ *                         launch of the two images, every other image, the finishers, the Float32 handles, the multisensor, Dual,
+ *                         RRS and operator-level paths build the layer as before.  0 = the other form everywhere: the kernels of the
+ *                         library without the option.  Every output is bit for bit the same under both values.
  */
 int mom_set_option(mom_t *h, int option, int value);
 
@@ -623,7 +633,7 @@ int mom_strip2_resumed(mom_t *h, int *units, int *left);
 enum { MOM_OPT_INVERSE = 0, MOM_OPT_FORCE_GENERIC = 1, MOM_OPT_M0_REDUCTION = 2, MOM_OPT_SMALL_WG = 3, MOM_OPT_STAGGER = 4,
        MOM_OPT_SMALL_N = 5, MOM_OPT_LAYER_SWEEP = 6, MOM_OPT_STRIP_PAD = 7, MOM_OPT_LEAN = 8, MOM_OPT_OVERLAP = 9,
        MOM_OPT_RRS_KERNELS = 10, MOM_OPT_DUAL_WORKSPACE_MB = 11, MOM_OPT_STRIP2 = 12, MOM_OPT_STRIP2_SCHED = 13,
-       MOM_OPT_ZERO_SKIP = 14, MOM_OPT_LUT_BATCH = 15, MOM_OPT_SOURCES_ONLY = 16 };
+       MOM_OPT_ZERO_SKIP = 14, MOM_OPT_LUT_BATCH = 15, MOM_OPT_SOURCES_ONLY = 16, MOM_OPT_ELEMENTAL = 17 };
 
 /* ---- The InterpolationModel: cross sections computed once on a (nu, p, T) grid and kept on the device as a cubic B-spline
  * interpolant -- make_interpolation_model (make_model_helpers.jl:55-99) and compute_absorption_cross_section(model::InterpolationModel,

@@ -43,6 +43,7 @@ MOM_OPT_STRIP2_SCHED = 13        # its scheduling, a mask (1, default): 1 = shar
 MOM_OPT_ZERO_SKIP = 14           # leave out the exact-zero products of the zero-weight trailing streams, a mask (7, default): 1 = quad-block image (blocks), 2 = two-buffer strip image (k-steps), 4 = two-buffer strip image (blocks of four rows of a partly live row tile); 0 = every product
 MOM_OPT_LUT_BATCH = 15           # (p, T) nodes per batch of mom_lut_build (0, default: 64); the table does not depend on it
 MOM_OPT_SOURCES_ONLY = 16        # 1 (default): a sweep launch of mom_rt_run without an observable moment (the (I,Q) sub-problem's, a full-problem launch from moment 1 on) leaves the composite R-+ and T++ out (two-buffer strip and quad-block images); the two arrays then hold the first layer's r-+, t++; 0 = all four operators
+MOM_OPT_ELEMENTAL = 17           # 1 (default): the two-buffer strip and quad-block images build the elemental layer in its table form (stream-pair tables once per scene, branch-free batches of four elements; csrc/mom_elemental_tab.hpp); 0 = elemental_build everywhere; outputs are bit for bit the same
 
 # the absorption model (mom_absorption_set_model, mom_lineshape_xsec): HitranModel.broadening, HitranModel.CEF
 BROADENING_VOIGT, BROADENING_DOPPLER, BROADENING_LORENTZ = 0, 1, 2

@@ -53,6 +53,11 @@ struct LayerArgs {
   // count, as the flag kS2RowBlocks (mom_strip2_variants.hpp), and both images MOM_OPT_SOURCES_ONLY as the flag kMomNbwSourcesOnly
   // (mom_images.hpp)
   int nbw;
+  // MOM_OPT_ELEMENTAL: the handle's stream-pair tables SI | F1 | F2, [3][Nq][Nq] with Nq = q.N / q.nS, of the stream set q
+  // (mom_scene.hip k_stream_tables); nullptr: none.  Read by the table form of the elemental layer alone (mom_elemental_tab.hpp: the
+  // two-buffer strip image and the quad-block image, where the flag kMomNbwElemental beside the count selects it); last in the
+  // block, so that no other field moves
+  const real *etab;
 };
 
 struct ZMix {

@@ -78,6 +78,10 @@ inline const MomLayerImage *mom_find_image(MomImageFamily family, int N) {
 // the host only.  mom_rt_run sets it on a first-stage launch whose moments no caller can observe; the two-buffer strip image and
 // the quad-block image then take their instantiation that leaves the composite R-+ and T++ out (mom_strip2.hpp)
 constexpr int kMomNbwSourcesOnly = 0x200;
+// MOM_OPT_ELEMENTAL: likewise a host-only flag beside the count.  The two-buffer strip image (default scheduling mode) and the
+// quad-block image then take their instantiation with the table form of the elemental layer (mom_elemental_tab.hpp); the host sets
+// it only together with LayerArgs::etab
+constexpr int kMomNbwElemental = 0x400;
 
 // ints of LayerArgs::sched of the two-buffer images (the unit queue's counter + the arrival tickets per CU: kS2SchedInts of
 // mom_strip2.hpp, momcore_strip2.hip checks the two against each other), zeroed on the stream before each of their launches

@@ -25,6 +25,7 @@
 // the full image where to pick the unit up.  Scope: Float64, MOM_WAVES = 1 build (namespace momq), sweep mode.
 #pragma once
 #include "mom_entry.hpp"
+#include "mom_elemental_tab.hpp"
 
 namespace MOM_NS {
 
@@ -657,7 +658,9 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
 #define MOM_Q4_ATTR
 #endif
 // SRC: the sources-only form of the interaction (MOM_OPT_SOURCES_ONLY, the flag kMomNbwSourcesOnly in LayerArgs::nbw)
-template <int KS, int NBW = Q4Geom<KS>::NB, bool SRC = false>
+// EL: the table form of the elemental layer (MOM_OPT_ELEMENTAL, the flag kMomNbwElemental in LayerArgs::nbw, which the host sets only
+// where the form applies to the launch; mom_elemental_tab.hpp).  EL = false is the kernel without the option
+template <int KS, int NBW = Q4Geom<KS>::NB, bool SRC = false, bool EL = false>
 __global__ void __launch_bounds__(64) MOM_Q4_ATTR k_layer_q4(const LayerArgs a) {
   using G = Q4Geom<KS>;
   constexpr int N = G::N;
@@ -696,7 +699,8 @@ __global__ void __launch_bounds__(64) MOM_Q4_ATTR k_layer_q4(const LayerArgs a) 
       real expk = exp(-dtau / a.q.mu0);          // init_layer      (rt_kernel.jl:273)
       ZMix zpp{as_global(a.Zpp) + NNs * a.K * mrel, lay + 3, a.K, N};
       ZMix zmp{as_global(a.Zmp) + NNs * a.K * mrel, lay + 3, a.K, N};
-      elemental_build(c, a.q, m, nd, tau_sum, dtau, varpi, zpp, zmp);
+      if constexpr (EL) elemental_build_tab<false, 4, N, N>(c, a.q, a.etab, m, nd, tau_sum, dtau, varpi, zpp, zmp);
+      else elemental_build(c, a.q, m, nd, tau_sum, dtau, varpi, zpp, zmp);
       MOM_STAMP(41);
       bool bail;
       expk = doubling_run_q4<KS, NBW>(c, nd, expk, bail);

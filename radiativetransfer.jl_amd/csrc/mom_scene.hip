@@ -2,6 +2,7 @@
 // runs, the layer-launch policy over the image table, rt_run_core, mom_rt_run, mom_rt_run_multisensor, the Dual run's entry
 // points, the getters.  Handle and shared helpers: mom_handle.hpp.
 #include "mom_handle.hpp"
+#include "mom_elemental_tab.hpp"
 #include "mom_images.hpp"
 #include "mom_reduce.hpp"
 #include "mom_strip2_variants.hpp"
@@ -53,6 +54,29 @@ __global__ void k_postprocess(PostArgs a) {
   a.R[idx] = r;
   a.T[idx] = t;
   a.hdr[idx] = h;  // Lambertian surfaces: only m = 0 contributes (r-+ = 0, j0- = 0 for m > 0)
+}
+
+// MOM_OPT_ELEMENTAL: the layer-independent stream-pair tables of the elemental layer, once per stream set instead of once per layer
+// and unit: out = SI | F1 | F2, [3][Nq][Nq], entry iq + jq Nq, with the very expressions of elemental_build (mom_kernels.hpp) on the
+// stream values mu[iq ns] it reads -- on the device, so that they are the same instructions
+__global__ void k_stream_tables(const double *mu, int ns, int Nq, double *out) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= Nq * Nq) return;
+  const int jq = e / Nq, iq = e - jq * Nq;
+  const double mui = mu[iq * ns], muj = mu[jq * ns];
+  out[e] = (1 / mui) + (1 / muj);
+  out[Nq * Nq + e] = muj / (mui + muj);
+  out[2 * Nq * Nq + e] = muj / (mui - muj);
+}
+// the tables of stream set q into `buf`, where the table form can apply to it (regular streams, an edge of whole streams); else none
+static int stream_tables(mom_t *h, const DevStreams &q, MomDevBuf<double> &buf) {
+  buf.reset();
+  if (!q.regular || q.nS < 1 || q.N % q.nS != 0) return MOM_OK;
+  const int Nq = q.N / q.nS;
+  HIPCHK(h, buf.renew(3 * (size_t)Nq * Nq));
+  hipLaunchKernelGGL(k_stream_tables, dim3((Nq * Nq + 255) / 256), dim3(256), 0, h->stream, q.mu, q.nS, Nq, buf.get());
+  HIPCHK(h, hipGetLastError());
+  return MOM_OK;
 }
 
 // the edges that have a strip-chained finisher, of the 4-wave or the 8-wave build (the pad rule: mom_host.hpp)
@@ -176,6 +200,12 @@ int scene_common(mom_t *h, int Nz, int K, int M, const double *Zpp, const double
       q0.N = N0; q0.nS = nS0;
       for (int k = nS0; k < 4; ++k) { q0.I0[k] = 0.0; q0.D[k] = 1.0; }
     }
+  }
+  {  // MOM_OPT_ELEMENTAL: the stream-pair tables of both stream sets, behind the uploads of their stream values on the same stream
+    int rc;
+    if ((rc = stream_tables(h, h->qk, h->d_etab))) return rc;
+    h->d_etab0.reset();
+    if (h->red0 && (rc = stream_tables(h, h->q0, h->d_etab0))) return rc;
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->Nz = Nz; h->K = K; h->scene_M = M; h->nVza = nVza; h->albedo = albedo;
@@ -341,6 +371,8 @@ static int launch_first_stage(mom_t *h, const FirstStage &fs, LayerArgs &a, bool
   if (!(h->opt_zero_skip & skip_bit)) a.nbw = 0;
   if (two_buffer && (h->opt_zero_skip & 4)) a.nbw |= kS2RowBlocks;
   if (sources_only && (two_buffer || fs.family == MOM_IMG_QUAD)) a.nbw |= kMomNbwSourcesOnly;
+  // MOM_OPT_ELEMENTAL: the same two images, where the stream set of the launch has its tables (launch_layer sets a.etab)
+  if ((two_buffer || fs.family == MOM_IMG_QUAD) && mom_elemental_tab_applies(a.q, a.K, a.etab)) a.nbw |= kMomNbwElemental;
   if (two_buffer) {
     h->resume2_units = units; h->resume2_nz = nzr;  // (mom_strip2_resumed)
     if (h->opt_strip2_sched) {  // the queue counter (and, for the chain priority, the per-CU tickets) start at zero: a memset ON
@@ -457,6 +489,8 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, const Comp6 &co
         for (int t = 0; t < kMaxTargets; ++t) a.act_z[r][t] = tg->act[(size_t)(r0 + r) * kMaxTargets + t];
     }
     a.scratch = scratch; a.info = h->d_info;
+    // MOM_OPT_ELEMENTAL: the stream-pair tables of the stream set this launch runs with
+    if (h->opt_elemental) a.etab = (&q == &h->q0) ? h->d_etab0.get() : h->d_etab.get();
     // MOM_OPT_SOURCES_ONLY: mom_rt_run alone (allow_red and no targets: mom_rt_run_multisensor has neither), and only a launch
     // that holds no observable moment -- the (I,Q) sub-problem's (mom_download: MOM_ESTATE) or one that starts behind moment 0
     const bool unobserved = h->opt_sources_only && allow_red && !tg && (&q == &h->q0 || m_first >= 1);

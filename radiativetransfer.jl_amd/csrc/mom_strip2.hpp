@@ -41,6 +41,7 @@
 #pragma once
 #include "mom_diag.hpp"
 #include "mom_entry.hpp"
+#include "mom_elemental_tab.hpp"
 
 namespace MOM_NS {
 
@@ -466,7 +467,10 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
 // never are a B operand (KS k-steps at most).
 // SRC (MOM_OPT_SOURCES_ONLY; default mode only; the flag kMomNbwSourcesOnly in LayerArgs::nbw): the sources-only form of the
 // interaction, see the header of this file.  SRC = false is the kernel as it was before the option existed.
-template <int KS, int MODE, int KW = KS, bool RB = false, bool SRC = false>
+// EL (MOM_OPT_ELEMENTAL; default mode only; the flag kMomNbwElemental in LayerArgs::nbw): the table form of the elemental layer
+// (mom_elemental_tab.hpp).  The host asks for it only where the form applies to the launch (mom_elemental_tab_applies: regular
+// streams, their tables, two bases); any other launch takes EL = false, the kernel as it was before the option existed.
+template <int KS, int MODE, int KW = KS, bool RB = false, bool SRC = false, bool EL = false>
 __global__ void __launch_bounds__(kThreads, 2) k_layer_s2(const LayerArgs a) {
   // (the argument block is never written: see k_layer_lean)
   constexpr int N = 4 * KS;
@@ -527,7 +531,8 @@ __global__ void __launch_bounds__(kThreads, 2) k_layer_s2(const LayerArgs a) {
       real expk = exp(-dtau / a.q.mu0);          // init_layer      (rt_kernel.jl:273)
       ZMix zpp{as_global(a.Zpp) + NNs * a.K * mrel, ls + 3, a.K, N};
       ZMix zmp{as_global(a.Zmp) + NNs * a.K * mrel, ls + 3, a.K, N};
-      elemental_build<true>(c, a.q, m, nd, tau_sum, dtau, varpi, zpp, zmp);
+      if constexpr (EL) elemental_build_tab<true, 2, N, StripGeom<KS>::LD>(c, a.q, a.etab, m, nd, tau_sum, dtau, varpi, zpp, zmp);
+      else elemental_build<true>(c, a.q, m, nd, tau_sum, dtau, varpi, zpp, zmp);
       bool bail;
       expk = doubling_run_s2<KS, PRIO, KW, RB>(c, nd, expk, bail);
       if (!bail) {

@@ -26,7 +26,8 @@ inline int s2_variant_for(int KS, int nbw) {
 }
 
 constexpr int kS2RowBlocks = 0x100;  // flag in LayerArgs::nbw beside the count (<= 15)
-// the count without the flags beside it (kS2RowBlocks and, above it, MOM_OPT_SOURCES_ONLY's kMomNbwSourcesOnly of mom_images.hpp)
+// the count without the flags beside it (kS2RowBlocks and, above it, MOM_OPT_SOURCES_ONLY's kMomNbwSourcesOnly and MOM_OPT_ELEMENTAL's
+// kMomNbwElemental of mom_images.hpp)
 inline int s2_nbw_count(int nbw) { return nbw & (kS2RowBlocks - 1); }
 // does the row-block rule change a product of KW k-steps: is some block row 0 .. 4 NT - 1 neither < KW nor the riding block KS?
 constexpr bool s2_row_blocks_change(int KS, int KW) { return KW < KS || 4 * ((KS + 3) / 4) - 1 > KS; }

@@ -259,6 +259,7 @@ extern "C" int mom_set_option(mom_t *h, int option, int value) {
     h->opt_zero_skip = value;
   }
   else if (option == MOM_OPT_SOURCES_ONLY) h->opt_sources_only = value;
+  else if (option == MOM_OPT_ELEMENTAL) h->opt_elemental = value;
   else if (option == MOM_OPT_LUT_BATCH) {
     if (value < 0) return fail(h, MOM_EINVAL, "mom_set_option: MOM_OPT_LUT_BATCH takes a number of (p, T) nodes >= 0 (0 = the default of 64)");
     h->opt_lut_batch = value;

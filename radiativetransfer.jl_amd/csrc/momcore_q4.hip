@@ -21,53 +21,61 @@ constexpr int kNB = MOM_STRIP_KS;
 constexpr int kSkip[] = {0, 1, 2, 4};
 static_assert(kNB > 4, "momcore_q4.hip: NB - 4 >= 1");
 // SRC: every variant once more in the sources-only form (MOM_OPT_SOURCES_ONLY; the flag kMomNbwSourcesOnly beside the count)
-template <int V, bool SRC = false>
-static const void *variant_fn() { return reinterpret_cast<const void *>(k_layer_q4<MOM_STRIP_KS, kNB - kSkip[V], SRC>); }
+// EL: and each of those once more with the table form of the elemental layer (MOM_OPT_ELEMENTAL; the flag kMomNbwElemental)
+template <int V, bool SRC = false, bool EL = false>
+static const void *variant_fn() { return reinterpret_cast<const void *>(k_layer_q4<MOM_STRIP_KS, kNB - kSkip[V], SRC, EL>); }
 static int variant_for(int nbw) {
-  nbw &= ~kMomNbwSourcesOnly;
+  nbw &= ~(kMomNbwSourcesOnly | kMomNbwElemental);
   if (nbw < 1 || nbw > kNB) return 0;
   int v = 0;
   for (int c = 1; c < (int)(sizeof kSkip / sizeof kSkip[0]); ++c)
     if (kNB - kSkip[c] >= nbw) v = c;
   return v;
 }
-template <int V, bool SRC>
+template <int V, bool SRC, bool EL>
 static hipError_t launch_variant(const LayerArgs &a, int grid, hipStream_t st) {
   const size_t smem = q4_lds_bytes(4 * MOM_STRIP_KS);
-  hipError_t e = mom_allow_lds(variant_fn<V, SRC>(), smem);
+  hipError_t e = mom_allow_lds(variant_fn<V, SRC, EL>(), smem);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_layer_q4<MOM_STRIP_KS, kNB - kSkip[V], SRC>), dim3(grid), dim3(64), smem, st, a);
+  hipLaunchKernelGGL((k_layer_q4<MOM_STRIP_KS, kNB - kSkip[V], SRC, EL>), dim3(grid), dim3(64), smem, st, a);
   return hipGetLastError();
 }
-template <bool SRC>
+template <bool SRC, bool EL>
 static hipError_t launch_form(const LayerArgs &a, int grid, hipStream_t st) {
   switch (variant_for(a.nbw)) {
-    case 1: return launch_variant<1, SRC>(a, grid, st);
-    case 2: return launch_variant<2, SRC>(a, grid, st);
-    case 3: return launch_variant<3, SRC>(a, grid, st);
-    default: return launch_variant<0, SRC>(a, grid, st);
+    case 1: return launch_variant<1, SRC, EL>(a, grid, st);
+    case 2: return launch_variant<2, SRC, EL>(a, grid, st);
+    case 3: return launch_variant<3, SRC, EL>(a, grid, st);
+    default: return launch_variant<0, SRC, EL>(a, grid, st);
   }
+}
+template <bool EL>
+static hipError_t launch_el(const LayerArgs &a, int grid, hipStream_t st) {
+  return (a.nbw & kMomNbwSourcesOnly) ? launch_form<true, EL>(a, grid, st) : launch_form<false, EL>(a, grid, st);
 }
 static hipError_t image_launch(const void *layer_args, int, int grid, hipStream_t st) {
   const LayerArgs a = *reinterpret_cast<const LayerArgs *>(layer_args);
-  return (a.nbw & kMomNbwSourcesOnly) ? launch_form<true>(a, grid, st) : launch_form<false>(a, grid, st);
+  return (a.nbw & kMomNbwElemental) ? launch_el<true>(a, grid, st) : launch_el<false>(a, grid, st);
 }
 // workgroups of this image a CU holds: by LDS and by the registers the compiler gave the kernel (occupancy API); the least of the
 // instantiations, so that the persistent grid fits whichever of them a launch takes
-template <int V, bool SRC>
+template <int V, bool SRC, bool EL>
 static int query_variant_per_cu() {
   int nb = 0;
   const size_t smem = q4_lds_bytes(4 * MOM_STRIP_KS);
-  if (mom_allow_lds(variant_fn<V, SRC>(), smem) != hipSuccess) return 4;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_layer_q4<MOM_STRIP_KS, kNB - kSkip[V], SRC>, 64, smem) != hipSuccess || nb < 1) return 4;
+  if (mom_allow_lds(variant_fn<V, SRC, EL>(), smem) != hipSuccess) return 4;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_layer_q4<MOM_STRIP_KS, kNB - kSkip[V], SRC, EL>, 64, smem) != hipSuccess || nb < 1) return 4;
   return nb;
 }
-template <bool SRC>
+template <bool SRC, bool EL>
 static int query_form_per_cu() {
-  return std::min(std::min(query_variant_per_cu<0, SRC>(), query_variant_per_cu<1, SRC>()),
-                  std::min(query_variant_per_cu<2, SRC>(), query_variant_per_cu<3, SRC>()));
+  return std::min(std::min(query_variant_per_cu<0, SRC, EL>(), query_variant_per_cu<1, SRC, EL>()),
+                  std::min(query_variant_per_cu<2, SRC, EL>(), query_variant_per_cu<3, SRC, EL>()));
 }
-static int query_per_cu() { return std::min(query_form_per_cu<false>(), query_form_per_cu<true>()); }
+static int query_per_cu() {
+  return std::min(std::min(query_form_per_cu<false, false>(), query_form_per_cu<true, false>()),
+                  std::min(query_form_per_cu<false, true>(), query_form_per_cu<true, true>()));
+}
 static int image_per_cu() {
   static const int per_cu = query_per_cu();  // (per process: the occupancy of an image does not depend on the handle)
   return per_cu;

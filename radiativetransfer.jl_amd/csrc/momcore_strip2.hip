@@ -23,32 +23,37 @@ static_assert(kMomStrip2SchedInts == (size_t)kS2SchedInts, "mom_images.hpp: size
 // form (MOM_OPT_SOURCES_ONLY, the flag kMomNbwSourcesOnly in LayerArgs::nbw), default mode only, for every (KW, RB) of it; a launch
 // in another mode takes its kernel with all four composite operators
 static_assert(MOM_STRIP_KS > kS2Skip[kS2Variants - 1], "momcore_strip2.hip: KS - skip >= 1");
-template <int MODE, int V = 0, bool RB = false, bool SRC = false>
+// EL: the table form of the elemental layer (MOM_OPT_ELEMENTAL, the flag kMomNbwElemental in LayerArgs::nbw), default mode only,
+// for every (KW, RB, SRC) of it
+template <int MODE, int V = 0, bool RB = false, bool SRC = false, bool EL = false>
 static hipError_t launch_s2(const LayerArgs &a, int grid, hipStream_t st) {
   constexpr int KW = MOM_STRIP_KS - kS2Skip[V];
   constexpr bool RBK = RB && s2_row_blocks_change(MOM_STRIP_KS, KW);
   const size_t smem = s2_lds_bytes(4 * MOM_STRIP_KS);
-  hipError_t e = mom_allow_lds(reinterpret_cast<const void *>(k_layer_s2<MOM_STRIP_KS, MODE, KW, RBK, SRC>), smem);
+  hipError_t e = mom_allow_lds(reinterpret_cast<const void *>(k_layer_s2<MOM_STRIP_KS, MODE, KW, RBK, SRC, EL>), smem);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_layer_s2<MOM_STRIP_KS, MODE, KW, RBK, SRC>), dim3(grid), dim3(kThreads), smem, st, a);
+  hipLaunchKernelGGL((k_layer_s2<MOM_STRIP_KS, MODE, KW, RBK, SRC, EL>), dim3(grid), dim3(kThreads), smem, st, a);
   return hipGetLastError();
 }
-template <bool RB, bool SRC>
+template <bool RB, bool SRC, bool EL>
 static hipError_t launch_s2_default(const LayerArgs &a, int grid, hipStream_t st) {
   switch (s2_variant_for(MOM_STRIP_KS, s2_nbw_count(a.nbw))) {
-    case 1: return launch_s2<1, 1, RB, SRC>(a, grid, st);
-    case 2: return launch_s2<1, 2, RB, SRC>(a, grid, st);
-    case 3: return launch_s2<1, 3, RB, SRC>(a, grid, st);
-    default: return launch_s2<1, 0, RB, SRC>(a, grid, st);
+    case 1: return launch_s2<1, 1, RB, SRC, EL>(a, grid, st);
+    case 2: return launch_s2<1, 2, RB, SRC, EL>(a, grid, st);
+    case 3: return launch_s2<1, 3, RB, SRC, EL>(a, grid, st);
+    default: return launch_s2<1, 0, RB, SRC, EL>(a, grid, st);
   }
+}
+template <bool EL>
+static hipError_t launch_s2_form(const LayerArgs &a, int grid, hipStream_t st) {
+  if (a.nbw & kMomNbwSourcesOnly)
+    return s2_row_blocks_for(MOM_STRIP_KS, a.nbw) ? launch_s2_default<true, true, EL>(a, grid, st) : launch_s2_default<false, true, EL>(a, grid, st);
+  return s2_row_blocks_for(MOM_STRIP_KS, a.nbw) ? launch_s2_default<true, false, EL>(a, grid, st) : launch_s2_default<false, false, EL>(a, grid, st);
 }
 static hipError_t image_launch(const void *layer_args, int, int grid, hipStream_t st) {
   const LayerArgs a = *reinterpret_cast<const LayerArgs *>(layer_args);
   switch (a.sched_mode & 3) {
-    case 1:
-      if (a.nbw & kMomNbwSourcesOnly)
-        return s2_row_blocks_for(MOM_STRIP_KS, a.nbw) ? launch_s2_default<true, true>(a, grid, st) : launch_s2_default<false, true>(a, grid, st);
-      return s2_row_blocks_for(MOM_STRIP_KS, a.nbw) ? launch_s2_default<true, false>(a, grid, st) : launch_s2_default<false, false>(a, grid, st);
+    case 1: return (a.nbw & kMomNbwElemental) ? launch_s2_form<true>(a, grid, st) : launch_s2_form<false>(a, grid, st);
     case 2: return launch_s2<2>(a, grid, st);
     case 3: return launch_s2<3>(a, grid, st);
     default: return launch_s2<0>(a, grid, st);
