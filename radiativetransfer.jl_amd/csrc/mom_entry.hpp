@@ -42,21 +42,13 @@ struct LayerArgs {
   // (its composite state in global memory is the one after layer resume - 1) and skips the finished ones.  nullptr: all layers.
   int *resume;
   // two-buffer strip image (mom_strip2.hpp), MOM_OPT_STRIP2_SCHED: sched[0] = the shared unit queue's ticket counter, sched[1 + cu]
-  // = arrival tickets per CU; zeroed on the stream before the launch.  sched_mode: bit 0 = units from the queue (else static
-  // striding), bit 1 = the second workgroup to arrive on a CU runs its strip chains at raised wave priority.
+  // = arrival tickets per CU; zeroed on the stream before the launch.  (Which scheduling mode, and every other choice among an
+  // image's instantiations -- MOM_OPT_ZERO_SKIP, MOM_OPT_SOURCES_ONLY, MOM_OPT_ELEMENTAL -- is no kernel's business: the host
+  // hands it to the image's launch function beside this block, as a MomLaunchForm of mom_images.hpp.)
   int *sched;
-  int sched_mode;
-  // quad-block image (mom_q4.hpp) and two-buffer strip image (mom_strip2.hpp), MOM_OPT_ZERO_SKIP: block rows of four entries that
-  // hold a weighted stream entry -- the entries from 4 nbw on are zero-weight streams, whose exact-zero blocks (k-steps) the
-  // products leave out; 0 (or N / 4): no such rule.  Set per first-stage launch: 0 where the image's bit of the option is off.
-  // Read by the host only (the launch picks an instantiation): the two-buffer image's launch finds bit 2 of the option beside the
-  // count, as the flag kS2RowBlocks (mom_strip2_variants.hpp), and both images MOM_OPT_SOURCES_ONLY as the flag kMomNbwSourcesOnly
-  // (mom_images.hpp)
-  int nbw;
   // MOM_OPT_ELEMENTAL: the handle's stream-pair tables SI | F1 | F2, [3][Nq][Nq] with Nq = q.N / q.nS, of the stream set q
   // (mom_scene.hip k_stream_tables); nullptr: none.  Read by the table form of the elemental layer alone (mom_elemental_tab.hpp: the
-  // two-buffer strip image and the quad-block image, where the flag kMomNbwElemental beside the count selects it); last in the
-  // block, so that no other field moves
+  // two-buffer strip image and the quad-block image, where MomLaunchForm::elemental_tab selects it)
   const real *etab;
 };
 

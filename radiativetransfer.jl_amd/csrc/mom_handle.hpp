@@ -113,10 +113,10 @@ struct mom_handle : MomSceneBufs<double> {
                              // 4 the two-buffer strip image multiplies only the live blocks of four rows of a partly live row tile
   int opt_sources_only = 1;  // MOM_OPT_SOURCES_ONLY: mom_rt_run's launches without an observable moment (the (I,Q) sub-problem's, a
                              // full-problem launch from moment 1 on) leave the composite R-+ and T++ out (two-buffer strip and
-                             // quad-block images; the flag kMomNbwSourcesOnly of LayerArgs::nbw)
+                             // quad-block images; MomLaunchForm::sources_only)
   int opt_elemental = 1;     // MOM_OPT_ELEMENTAL: the two-buffer strip image (default scheduling mode) and the quad-block image build
-                             // the elemental layer in its table form (mom_elemental_tab.hpp; the flag kMomNbwElemental of
-                             // LayerArgs::nbw, the tables below in LayerArgs::etab); 0 = elemental_build everywhere
+                             // the elemental layer in its table form (mom_elemental_tab.hpp; MomLaunchForm::elemental_tab,
+                             // the tables below in LayerArgs::etab); 0 = elemental_build everywhere
   MomDevBuf<double> d_etab, d_etab0;  // stream-pair tables SI | F1 | F2, [3][Nq][Nq], of the full problem's streams (qk) and of the
                                       // (I,Q) sub-problem's (q0): built by scene_common where the table form can apply, else empty
   int nbw_0 = 0;             // blocks of four entries with a weighted one (mom_q4_nbw) of the m = 0 sub-problem, after reduction and padding

@@ -192,16 +192,34 @@ inline hipError_t mom_allow_lds(const void *fn, size_t bytes) {
   return e;
 }
 
-// One launch of a kernel templated on LDSM (operators in LDS / in per-workgroup global slabs): `k_lds` and `k_gen` are its two
-// instantiations, MOM_LDSM(KERN, further template arguments...) names them
+// A run-time value as a template argument: `f` is a generic lambda and receives a std::integral_constant, which converts to its
+// value in constant expressions; what `f` returns (a launch's hipError_t, a kernel's function pointer) comes back.  mom_with_int
+// covers Lo ... Hi and refuses the rest (hipErrorInvalidValue, or a null pointer), so nothing outside that range is instantiated.
+template <class F>
+inline auto mom_with_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <int Lo, int Hi, class F>
+inline auto mom_with_int(int v, F &&f) -> decltype(f(std::integral_constant<int, Lo>{})) {
+  using R = decltype(f(std::integral_constant<int, Lo>{}));
+  if (v == Lo) return f(std::integral_constant<int, Lo>{});
+  if constexpr (Lo < Hi) return mom_with_int<Lo + 1, Hi>(v, f);
+  else if constexpr (std::is_same<R, hipError_t>::value) return hipErrorInvalidValue;
+  else return R{};
+}
+
+// One launch of a kernel with `smem` bytes of dynamic LDS
 template <class Args>
-inline hipError_t mom_launch_ldsm(void (*k_lds)(Args), void (*k_gen)(Args), bool lds, int grid, int threads, size_t smem,
-                                  hipStream_t st, const Args &a) {
-  void (*const k)(Args) = lds ? k_lds : k_gen;
+inline hipError_t mom_launch_lds(void (*k)(Args), int grid, int threads, size_t smem, hipStream_t st, const Args &a) {
   const hipError_t e = mom_allow_lds(reinterpret_cast<const void *>(k), smem);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k, dim3(grid), dim3(threads), smem, st, a);
   return hipGetLastError();
+}
+// ... of a kernel templated on LDSM (operators in LDS / in per-workgroup global slabs): `k_lds` and `k_gen` are its two
+// instantiations, MOM_LDSM(KERN, further template arguments...) names them
+template <class Args>
+inline hipError_t mom_launch_ldsm(void (*k_lds)(Args), void (*k_gen)(Args), bool lds, int grid, int threads, size_t smem,
+                                  hipStream_t st, const Args &a) {
+  return mom_launch_lds(lds ? k_lds : k_gen, grid, threads, smem, st, a);
 }
 #define MOM_LDSM(KERN, ...) KERN<true, ##__VA_ARGS__>, KERN<false, ##__VA_ARGS__>
 

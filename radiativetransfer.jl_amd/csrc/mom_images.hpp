@@ -12,12 +12,30 @@
 
 #include <cstddef>
 
+// What the host knows about a launch and no kernel reads: which of the instantiations an image holds the launch takes
+// (mom_image_variants.hpp has the rules).  An image ignores what it has no instantiation for; a default-constructed form is the
+// plain kernel, which is what the finishers and the Float32 driver pass.
+struct MomLaunchForm {
+  // MOM_OPT_ZERO_SKIP: block rows of four entries that hold a weighted stream entry (mom_host.hpp mom_q4_nbw) -- the entries from
+  // 4 nbw on are zero-weight streams, whose exact-zero blocks (quad-block image) or k-steps (two-buffer strip image) the products
+  // leave out; 0 (or N / 4): no such rule
+  int nbw = 0;
+  bool row_blocks = false;     // MOM_OPT_ZERO_SKIP bit 2: the row-block rule of the two-buffer strip image (mom_strip.hpp strip_mul)
+  // MOM_OPT_SOURCES_ONLY: no caller can observe a moment of this launch; the two-buffer strip image and the quad-block image then
+  // leave the composite R-+ and T++ out (mom_strip2.hpp)
+  bool sources_only = false;
+  // MOM_OPT_ELEMENTAL: the table form of the elemental layer (mom_elemental_tab.hpp; the two-buffer strip image in its default
+  // scheduling mode and the quad-block image); the host sets it only together with LayerArgs::etab
+  bool elemental_tab = false;
+  int sched_mode = 0;          // MOM_OPT_STRIP2_SCHED: the scheduling mode of the two-buffer strip image (mom_strip2.hpp), 1 = default
+};
+
 struct MomLayerImage {
   int N;  // operator edge the image was compiled for
-  // layer_args: the LayerArgs of the image's build (layout-identical in every namespace of a precision); iface: the interface
-  // code the kernel is instantiated for (finishers; the first-stage images handle code 3 only and ignore it).  The dynamic LDS
-  // size is the image's own business
-  hipError_t (*launch)(const void *layer_args, int iface, int grid, hipStream_t st);
+  // layer_args: the LayerArgs of the image's build (layout-identical in every namespace of a precision); the finishers read the
+  // interface code their kernel is instantiated for from it (LayerArgs::iface; the first-stage images handle code 3 only).  The
+  // dynamic LDS size is the image's own business
+  hipError_t (*launch)(const void *layer_args, const MomLaunchForm &form, int grid, hipStream_t st);
   // LDS bytes of one workgroup for ns Stokes components per stream of the elemental layer's stream-pair tables, nS per stream
   // entry of the scene, K phase-matrix bases; 0: the image does not apply to such a scene
   size_t (*lds_bytes)(int ns, int nS, int K);
@@ -73,15 +91,6 @@ inline const MomLayerImage *mom_find_image(MomImageFamily family, int N) {
     if (e.family == family && e.image->N == N) return e.image;
   return nullptr;
 }
-
-// MOM_OPT_SOURCES_ONLY: a flag in LayerArgs::nbw beside the count (<= 15) and the two-buffer image's kS2RowBlocks (0x100), read by
-// the host only.  mom_rt_run sets it on a first-stage launch whose moments no caller can observe; the two-buffer strip image and
-// the quad-block image then take their instantiation that leaves the composite R-+ and T++ out (mom_strip2.hpp)
-constexpr int kMomNbwSourcesOnly = 0x200;
-// MOM_OPT_ELEMENTAL: likewise a host-only flag beside the count.  The two-buffer strip image (default scheduling mode) and the
-// quad-block image then take their instantiation with the table form of the elemental layer (mom_elemental_tab.hpp); the host sets
-// it only together with LayerArgs::etab
-constexpr int kMomNbwElemental = 0x400;
 
 // ints of LayerArgs::sched of the two-buffer images (the unit queue's counter + the arrival tickets per CU: kS2SchedInts of
 // mom_strip2.hpp, momcore_strip2.hip checks the two against each other), zeroed on the stream before each of their launches

@@ -657,8 +657,8 @@ __device__ __forceinline__ bool interaction_q4(Ctx &c, const CompPtrs &g) {
 #else
 #define MOM_Q4_ATTR
 #endif
-// SRC: the sources-only form of the interaction (MOM_OPT_SOURCES_ONLY, the flag kMomNbwSourcesOnly in LayerArgs::nbw)
-// EL: the table form of the elemental layer (MOM_OPT_ELEMENTAL, the flag kMomNbwElemental in LayerArgs::nbw, which the host sets only
+// SRC: the sources-only form of the interaction (MOM_OPT_SOURCES_ONLY, MomLaunchForm::sources_only)
+// EL: the table form of the elemental layer (MOM_OPT_ELEMENTAL, MomLaunchForm::elemental_tab of mom_images.hpp, which the host sets only
 // where the form applies to the launch; mom_elemental_tab.hpp).  EL = false is the kernel without the option
 template <int KS, int NBW = Q4Geom<KS>::NB, bool SRC = false, bool EL = false>
 __global__ void __launch_bounds__(64) MOM_Q4_ATTR k_layer_q4(const LayerArgs a) {

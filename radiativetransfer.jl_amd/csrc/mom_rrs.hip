@@ -1624,17 +1624,7 @@ __global__ void k_unpack(double *nat, const double *dev, int rows, int cols, int
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-// A runtime flag as a template argument: `f` is a generic lambda and receives a std::integral_constant, which converts to its
-// value in constant expressions.  with_int covers Lo ... Hi and refuses the rest, so nothing outside that range is instantiated.
-template <class F>
-static hipError_t with_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
-template <int Lo, int Hi, class F>
-static hipError_t with_int(int v, F &&f) {
-  if (v == Lo) return f(std::integral_constant<int, Lo>{});
-  if constexpr (Lo < Hi) return with_int<Lo + 1, Hi>(v, f);
-  else return hipErrorInvalidValue;
-}
-
+// (run-time flags become template arguments through mom_with_bool / mom_with_int of mom_host.hpp)
 // the one launch of a kernel with dynamic LDS (above 64 KB the limit of the function has to be raised first)
 template <class K, class... Args>
 static hipError_t launch_lds(K kern, unsigned grid, unsigned block, size_t lds_bytes, hipStream_t st, Args... args) {
@@ -1681,13 +1671,13 @@ static hipError_t launch_wave(const Form &f, unsigned grid, hipStream_t st, cons
     case Family::ElPoint: return go(k_el_point<NT>);
     case Family::DblPoint: return go(k_dbl_point<NT>);
     case Family::IntPoint: return go(k_int_point<NT>, iface);
-    case Family::TileElemental: return with_bool(f.nd0, [&](auto nd0) { return go(k_ie_elemental_tile<NT, nd0>); });
+    case Family::TileElemental: return mom_with_bool(f.nd0, [&](auto nd0) { return go(k_ie_elemental_tile<NT, nd0>); });
     case Family::DblPair:
-      return with_bool(f.fuse_el, [&](auto fuse) {
-        return with_int<0, 2>(f.mode, [&](auto mode) { return go(dbl_pair_kernel<NT, fuse, mode>()); });
+      return mom_with_bool(f.fuse_el, [&](auto fuse) {
+        return mom_with_int<0, 2>(f.mode, [&](auto mode) { return go(dbl_pair_kernel<NT, fuse, mode>()); });
       });
     case Family::IntPair:  // three forms are built: the surface, derived +- / -- blocks, neither (never both: the surface's ie* are zeros)
-      return with_int<0, 2>(f.surface ? 2 : (f.derive ? 1 : 0),
+      return mom_with_int<0, 2>(f.surface ? 2 : (f.derive ? 1 : 0),
                             [&](auto v) { return go(int_pair_kernel<NT, (v == 2), (v == 1)>(), iface); });
     default: return hipErrorInvalidValue;
   }
@@ -1714,16 +1704,16 @@ static hipError_t launch_wg(const Form &f, unsigned grid, hipStream_t st, const 
       // one of twelve -- N = 42 ... 44 -- measured slower than the guards: profiles/r05_rrs_wg_ab.txt (13))
       const int padded_steps = (16 * NT - a.N) / 4;
       const bool no_guards = padded_steps == 0 || (padded_steps == 1 && NT == 4);
-      return with_bool(f.fuse_el, [&](auto fuse) {
-        return with_int<0, 2>(f.mode, [&](auto mode) {
-          return with_bool(no_guards, [&](auto ng) {
+      return mom_with_bool(f.fuse_el, [&](auto fuse) {
+        return mom_with_int<0, 2>(f.mode, [&](auto mode) {
+          return mom_with_bool(no_guards, [&](auto ng) {
             return go(wg_kernel<NT>(k_dbl_pair_wg2<fuse, mode, ng>, k_dbl_pair_wg3<fuse, mode, ng>, k_dbl_pair_wg4<fuse, mode, ng>));
           });
         });
       });
     }
     case Family::IntPairWg:  // interface 11; the same three forms as Family::IntPair
-      return with_int<0, 2>(f.surface ? 2 : (f.derive ? 1 : 0), [&](auto v) {
+      return mom_with_int<0, 2>(f.surface ? 2 : (f.derive ? 1 : 0), [&](auto v) {
         return go(wg_kernel<NT>(k_int_pair_wg2<(v == 2), (v == 1)>, k_int_pair_wg3<(v == 2), (v == 1)>, k_int_pair_wg4<(v == 2), (v == 1)>));
       });
     default: return hipErrorInvalidValue;
@@ -1735,8 +1725,8 @@ static hipError_t launch_wg(const Form &f, unsigned grid, hipStream_t st, const 
 hipError_t momr_big_launch(const momr::Form &f, unsigned grid, hipStream_t stream, const void *args, int iface) {
   using namespace momr_big;
   const KArgs &a = *static_cast<const KArgs *>(args);
-  if (workgroup_form(f.family)) return with_int<2, 4>(f.nt, [&](auto nt) { return launch_wg<nt>(f, grid, stream, a); });
-  return with_int<3, 4>(f.nt, [&](auto nt) { return launch_wave<nt>(f, grid, stream, a, iface); });
+  if (workgroup_form(f.family)) return mom_with_int<2, 4>(f.nt, [&](auto nt) { return launch_wg<nt>(f, grid, stream, a); });
+  return mom_with_int<3, 4>(f.nt, [&](auto nt) { return launch_wave<nt>(f, grid, stream, a, iface); });
 }
 #else
 #define RCHK(call)                                 \
@@ -1749,7 +1739,7 @@ hipError_t momr_big_launch(const momr::Form &f, unsigned grid, hipStream_t strea
 // second object's.
 static hipError_t launch(const State *s, const Form &f, unsigned grid, const KArgs &a, int iface = 0) {
   if (f.nt > 2 || workgroup_form(f.family)) return momr_big_launch(f, grid, s->stream, &a, iface);
-  return with_int<1, 2>(f.nt, [&](auto nt) { return launch_wave<nt>(f, grid, s->stream, a, iface); });
+  return mom_with_int<1, 2>(f.nt, [&](auto nt) { return launch_wave<nt>(f, grid, s->stream, a, iface); });
 }
 
 static KArgs base_args(const State *s, const Streams &q) {

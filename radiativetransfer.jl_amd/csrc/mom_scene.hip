@@ -5,7 +5,6 @@
 #include "mom_elemental_tab.hpp"
 #include "mom_images.hpp"
 #include "mom_reduce.hpp"
-#include "mom_strip2_variants.hpp"
 
 using namespace mom;
 
@@ -349,9 +348,9 @@ static FirstStage choose_first_stage(const mom_t *h, Finisher fin, const DevStre
 // The first-stage launch of `fs` for the sweep described by `a`, if it applies: a whole-slab sweep of a single-target run, no
 // forced pivoted inverse, interface code 3 on every layer that interacts (the images handle no other).  On return a.resume (and
 // a.sched) are set for the finisher as well.
-// sources_only (MOM_OPT_SOURCES_ONLY): no caller can observe a moment of this launch -- the two-buffer strip image and the
-// quad-block image leave the composite R-+ and T++ out of it (the flag kMomNbwSourcesOnly in a.nbw); the other images ignore it.
-static int launch_first_stage(mom_t *h, const FirstStage &fs, LayerArgs &a, bool multi_target, bool sources_only, hipStream_t st) {
+// nbw: the blocks of four entries with a weighted one of a.q (mom_q4_nbw).  sources_only (MOM_OPT_SOURCES_ONLY): no caller can
+// observe a moment of this launch -- the two-buffer strip image and the quad-block image leave the composite R-+ and T++ out of it.
+static int launch_first_stage(mom_t *h, const FirstStage &fs, LayerArgs &a, int nbw, bool multi_target, bool sources_only, hipStream_t st) {
   const int nzr = a.Nz_sweep;  // 0: a per-layer launch
   bool ok = fs.image && nzr > 0 && !multi_target && a.q.inv_mode == 0;
   for (int k = 1; k < nzr && ok; ++k) ok = (a.iface_z[k] == 3);
@@ -365,14 +364,15 @@ static int launch_first_stage(mom_t *h, const FirstStage &fs, LayerArgs &a, bool
   HIPCHK(h, table.reserve(units, st));
   a.resume = table;
   int per_cu = fs.image->per_cu();
-  // MOM_OPT_ZERO_SKIP: bit 0 the quad-block image, bit 1 the two-buffer strip image; the other first-stage images have no such rule.
-  // Bit 2, the row-block rule of the two-buffer strip image, rides in nbw as a flag (mom_strip2_variants.hpp)
-  const int skip_bit = (fs.family == MOM_IMG_QUAD) ? 1 : two_buffer ? 2 : 0;
-  if (!(h->opt_zero_skip & skip_bit)) a.nbw = 0;
-  if (two_buffer && (h->opt_zero_skip & 4)) a.nbw |= kS2RowBlocks;
-  if (sources_only && (two_buffer || fs.family == MOM_IMG_QUAD)) a.nbw |= kMomNbwSourcesOnly;
+  // which instantiation the image launches (mom_image_variants.hpp); the lean images have one
+  const bool quad = (fs.family == MOM_IMG_QUAD);
+  MomLaunchForm form;
+  // MOM_OPT_ZERO_SKIP: bit 0 the quad-block image, bit 1 the two-buffer strip image, bit 2 the row-block rule of the latter
+  if (h->opt_zero_skip & (quad ? 1 : two_buffer ? 2 : 0)) form.nbw = nbw;
+  form.row_blocks = two_buffer && (h->opt_zero_skip & 4);
+  form.sources_only = sources_only && (two_buffer || quad);
   // MOM_OPT_ELEMENTAL: the same two images, where the stream set of the launch has its tables (launch_layer sets a.etab)
-  if ((two_buffer || fs.family == MOM_IMG_QUAD) && mom_elemental_tab_applies(a.q, a.K, a.etab)) a.nbw |= kMomNbwElemental;
+  form.elemental_tab = (two_buffer || quad) && mom_elemental_tab_applies(a.q, a.K, a.etab);
   if (two_buffer) {
     h->resume2_units = units; h->resume2_nz = nzr;  // (mom_strip2_resumed)
     if (h->opt_strip2_sched) {  // the queue counter (and, for the chain priority, the per-CU tickets) start at zero: a memset ON
@@ -381,7 +381,7 @@ static int launch_first_stage(mom_t *h, const FirstStage &fs, LayerArgs &a, bool
       if (!h->d_sched2) HIPCHK(h, h->d_sched2.renew(ints));
       HIPCHK(h, hipMemsetAsync(h->d_sched2, 0, ((h->opt_strip2_sched & 2) ? ints : 1) * sizeof(int), st));
       a.sched = h->d_sched2;
-      a.sched_mode = h->opt_strip2_sched;
+      form.sched_mode = h->opt_strip2_sched;
     }
   }
 #ifdef MOM_EXPERIMENTS
@@ -391,19 +391,19 @@ static int launch_first_stage(mom_t *h, const FirstStage &fs, LayerArgs &a, bool
   }
 #endif
   const int grid = (int)std::min<size_t>(units, (size_t)per_cu * h->num_cu);  // persistent workgroups
-  HIPCHK(h, fs.image->launch(&a, a.iface, grid, st));
+  HIPCHK(h, fs.image->launch(&a, form, grid, st));
   h->launches++;
   return MOM_OK;
 }
 
 // One k_layer launch (plus the first-stage launch in front of it, if any) of the argument block `a` on stream `st`
-static int launch_layer_images(mom_t *h, LayerArgs &a, bool multi_target, bool sources_only, hipStream_t st) {
+static int launch_layer_images(mom_t *h, LayerArgs &a, int nbw, bool multi_target, bool sources_only, hipStream_t st) {
   const DevStreams &q = a.q;
   const size_t units = (size_t)a.S * a.M;
   const bool lds = (q.N <= 64) && !h->opt_force_generic;
   const int ns_tab = q.regular ? q.nS : 1;  // Stokes components per stream of the elemental layer's stream-pair tables
   const Finisher fin = choose_finisher(h, q, ns_tab, lds);
-  const int rc = launch_first_stage(h, choose_first_stage(h, fin, q, ns_tab), a, multi_target, sources_only, st);
+  const int rc = launch_first_stage(h, choose_first_stage(h, fin, q, ns_tab), a, nbw, multi_target, sources_only, st);
   if (rc) return rc;
   if (fin == kFinStrip4 || fin == kFinStrip8) {  // strip-chained kernels (momcore_strip.hip), one image per N
     const MomLayerImage *im = mom_find_image(fin == kFinStrip4 ? MOM_IMG_STRIP4 : MOM_IMG_STRIP8, q.N);
@@ -415,7 +415,7 @@ static int launch_layer_images(mom_t *h, LayerArgs &a, bool multi_target, bool s
       a.stagger = (int)(unit_us * 100.0 / 32.0);
     }
     const int grid = (int)std::min<size_t>(units, (size_t)im->per_cu() * h->num_cu);  // persistent: two per CU (4-wave), one (8-wave)
-    HIPCHK(h, im->launch(&a, a.iface, grid, st));
+    HIPCHK(h, im->launch(&a, MomLaunchForm{}, grid, st));
   } else if (fin == kFinGen4) {
     HIPCHK(h, mom4_launch_layer(&a, a.iface, true, (int)((a.S >= 2048) ? a.S : units), mom4_lds_bytes(q.N, true), st));
   } else {
@@ -457,7 +457,7 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, const Comp6 &co
   if (cont && can_sweep) can_sweep = (h->iface[za] == h->iface[za + 1]);
   for (int z = za; z < zb && can_sweep; ++z) can_sweep = (h->nd[z] <= 127);
   hipStream_t cur = h->stream;  // the stream launch_layer issues to (MOM_OPT_OVERLAP switches it for the m = 0 sub-problem)
-  // nbw: LayerArgs::nbw of the stream set q (launch_first_stage clears it where MOM_OPT_ZERO_SKIP has the image's bit off).  Full
+  // nbw: MomLaunchForm::nbw of the stream set q (launch_first_stage leaves it 0 where MOM_OPT_ZERO_SKIP has the image's bit off).  Full
   // problem: from the weights mom_set_streams
   // uploaded (the dummy entries behind the N real ones only lengthen the run of zero weights); sub-problem: scene_common's count
   const int nbw_k = mom_q4_nbw(h->h_wt.data(), h->N);
@@ -465,7 +465,6 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, const Comp6 &co
                           const auto &comp, double *scratch) -> int {  // comp[6]: buffers or raw pointers
     LayerArgs a{};
     a.q = q; a.S = h->S; a.M = Mcount; a.K = h->K; a.m_first = m_first;
-    a.nbw = nbw;
     const bool sweep = z < 0;
     if (sweep) {
       z = za;
@@ -494,7 +493,7 @@ static int rt_run_core(mom_t *h, int za, int zb, bool allow_red, const Comp6 &co
     // MOM_OPT_SOURCES_ONLY: mom_rt_run alone (allow_red and no targets: mom_rt_run_multisensor has neither), and only a launch
     // that holds no observable moment -- the (I,Q) sub-problem's (mom_download: MOM_ESTATE) or one that starts behind moment 0
     const bool unobserved = h->opt_sources_only && allow_red && !tg && (&q == &h->q0 || m_first >= 1);
-    return launch_layer_images(h, a, tg != nullptr, unobserved, cur);
+    return launch_layer_images(h, a, nbw, tg != nullptr, unobserved, cur);
   };
   // MOM_OPT_OVERLAP: the two launches of a sweep -- moments 1..M-1 on the full problem, moment 0 on the (I,Q) sub-problem --
   // are independent.  What runs at the edges 52 / 56 / 60 (C2: N = 60, sub-problem N = 40): the sub-problem on the quad-block image

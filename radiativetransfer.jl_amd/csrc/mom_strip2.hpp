@@ -45,7 +45,7 @@
 
 namespace MOM_NS {
 
-// MOM_OPT_STRIP2_SCHED (LayerArgs::sched, sched_mode): how the workgroups share the units and the two of a CU its matrix pipe.
+// MOM_OPT_STRIP2_SCHED (LayerArgs::sched, MomLaunchForm::sched_mode): how the workgroups share the units and the two of a CU its matrix pipe.
 //   * Bit 0 (default on), a shared unit queue: the units are handed out by an atomic ticket instead of pt += gridDim.x, so no
 //     workgroup idles through a partial last round; resume[] stays indexed by unit.  Units are independent: the order does not
 //     change a result.  C2: full layers 272.7 -> 263.0 ms, N = 52 / 56 -2 % (profiles/r08_C2_ab.txt).
@@ -455,9 +455,9 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
 }
 
 // One launch walks all layers of every unit (sweep mode only); see the header of this file for what it does not do.
-// MODE = the bits of LayerArgs::sched_mode, one instantiation each: without bit 0 the unit loop is the fixed stride, without bit 1
+// MODE = the bits of MomLaunchForm::sched_mode, one instantiation each: without bit 0 the unit loop is the fixed stride, without bit 1
 // no chain boundary emits anything, so MODE 0 is the kernel as it was before the option existed.
-// KW < KS (MOM_OPT_ZERO_SKIP bit 1; the host picks it from LayerArgs::nbw, mom_strip2_variants.hpp): every strip product of the
+// KW < KS (MOM_OPT_ZERO_SKIP bit 1; the host picks it from MomLaunchForm::nbw, mom_image_variants.hpp): every strip product of the
 // image runs KW k-steps and the diagonal fix-up (mom_strip.hpp strip_diag_fixup), strip index = wave.  Only the products change:
 // Frobenius sums, series lengths, resume decisions, stores and the elemental layer are those of KW = KS.
 // RB (MOM_OPT_ZERO_SKIP bit 2; default mode only): every strip product follows the row-block rule of mom_strip.hpp strip_mul -- the
@@ -465,9 +465,9 @@ __device__ __forceinline__ bool interaction_strip_s2(Ctx &c, const CompPtrs &g) 
 // rows.  The strip rows that keep their incoming value under it are read by nothing: the stores and the Frobenius sums are guarded
 // by strip_rowok (rows < N), strip_flip only changes signs, the riding rows N, N + 1 lie in a live block, and a strip's rows >= N
 // never are a B operand (KS k-steps at most).
-// SRC (MOM_OPT_SOURCES_ONLY; default mode only; the flag kMomNbwSourcesOnly in LayerArgs::nbw): the sources-only form of the
+// SRC (MOM_OPT_SOURCES_ONLY; default mode only; MomLaunchForm::sources_only): the sources-only form of the
 // interaction, see the header of this file.  SRC = false is the kernel as it was before the option existed.
-// EL (MOM_OPT_ELEMENTAL; default mode only; the flag kMomNbwElemental in LayerArgs::nbw): the table form of the elemental layer
+// EL (MOM_OPT_ELEMENTAL; default mode only; MomLaunchForm::elemental_tab): the table form of the elemental layer
 // (mom_elemental_tab.hpp).  The host asks for it only where the form applies to the launch (mom_elemental_tab_applies: regular
 // streams, their tables, two bases); any other launch takes EL = false, the kernel as it was before the option existed.
 template <int KS, int MODE, int KW = KS, bool RB = false, bool SRC = false, bool EL = false>

@@ -449,7 +449,7 @@ int momf_rt_run(momf_scene *s) {
     const MomLayerImage *im = (lds && s->strips && s->w4) ? mom_find_image(MOM_IMG_F32_STRIP4, N) : nullptr;
     if (!im && lds && s->strips) im = mom_find_image(MOM_IMG_F32_STRIP8, N);
     if (im) {
-      FCHK(s, im->launch(&a, a.iface, grid, s->stream));
+      FCHK(s, im->launch(&a, MomLaunchForm{}, grid, s->stream));
       s->launches++;
       continue;
     }

@@ -13,13 +13,9 @@
 
 using namespace MOM_NS;
 
-static hipError_t image_launch(const void *layer_args, int, int grid, hipStream_t st) {
-  const LayerArgs a = *reinterpret_cast<const LayerArgs *>(layer_args);
-  const size_t smem = lean_lds_bytes(4 * MOM_STRIP_KS);
-  hipError_t e = mom_allow_lds(reinterpret_cast<const void *>(k_layer_lean<MOM_STRIP_KS>), smem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_layer_lean<MOM_STRIP_KS>), dim3(grid), dim3(kThreads), smem, st, a);
-  return hipGetLastError();
+static hipError_t image_launch(const void *layer_args, const MomLaunchForm &, int grid, hipStream_t st) {
+  return mom_launch_lds(k_layer_lean<MOM_STRIP_KS>, grid, kThreads, lean_lds_bytes(4 * MOM_STRIP_KS), st,
+                        *reinterpret_cast<const LayerArgs *>(layer_args));
 }
 static size_t image_lds_bytes(int ns, int, int) { return lean_applies(4 * MOM_STRIP_KS, ns) ? lean_lds_bytes(4 * MOM_STRIP_KS) : 0; }
 static int image_per_cu() { return 2; }

@@ -37,22 +37,16 @@ using namespace MOM_NS;
 static size_t image_lds_bytes(int ns, int, int) { return strip_lds_bytes(4 * MOM_STRIP_KS, ns); }
 static int image_per_cu() { return kWaves == 4 ? 2 : 1; }  // 4-wave builds: two LDS images fit a CU (mom_kernels.hpp ld_for)
 
-static hipError_t image_launch(const void *layer_args, int iface, int grid, hipStream_t st) {
-  const LayerArgs a = *reinterpret_cast<const LayerArgs *>(layer_args);
+static hipError_t image_launch(const void *layer_args, const MomLaunchForm &, int grid, hipStream_t st) {
+  const LayerArgs &a = *reinterpret_cast<const LayerArgs *>(layer_args);
   const size_t smem = image_lds_bytes(a.q.regular ? a.q.nS : 1, 0, 0);
+  // multi-target form (interface code dispatched at run time)
+  if (a.ntgt > 0) return mom_launch_lds(k_layer<true, -1, MOM_STRIP_KS, true>, grid, kThreads, smem, st, a);
   hipError_t e = hipSuccess;
-#define STRIP_LAUNCH(IF)                                                                                            \
-  if ((e = mom_allow_lds(reinterpret_cast<const void *>(k_layer<true, IF, MOM_STRIP_KS>), smem)) != hipSuccess)     \
-    return e;                                                                                                       \
-  hipLaunchKernelGGL((k_layer<true, IF, MOM_STRIP_KS>), dim3(grid), dim3(kThreads), smem, st, a)
-  if (a.ntgt > 0) {  // multi-target form (interface code dispatched at run time)
-    if ((e = mom_allow_lds(reinterpret_cast<const void *>(k_layer<true, -1, MOM_STRIP_KS, true>), smem)) != hipSuccess) return e;
-    hipLaunchKernelGGL((k_layer<true, -1, MOM_STRIP_KS, true>), dim3(grid), dim3(kThreads), smem, st, a);
-    return hipGetLastError();
-  }
-  MOM_IFACE_SWITCH(iface, STRIP_LAUNCH)
+#define STRIP_LAUNCH(IF) e = mom_launch_lds(k_layer<true, IF, MOM_STRIP_KS>, grid, kThreads, smem, st, a)
+  MOM_IFACE_SWITCH(a.iface, STRIP_LAUNCH)
 #undef STRIP_LAUNCH
-  return hipGetLastError();
+  return e;
 }
 MOM_DEFINE_IMAGE(MOM_IMAGE_FAMILY, MOM_STRIP_KS, image_launch, image_lds_bytes, image_per_cu)
 
@@ -60,13 +54,9 @@ MOM_DEFINE_IMAGE(MOM_IMAGE_FAMILY, MOM_STRIP_KS, image_launch, image_lds_bytes, 
 // the lean sweep kernel of the same build: LDS bytes 0 if it does not apply to ns Stokes components per stream
 static size_t lean_image_lds_bytes(int ns, int, int) { return lean_applies(4 * MOM_STRIP_KS, ns) ? lean_lds_bytes(4 * MOM_STRIP_KS) : 0; }
 static int lean_image_per_cu() { return 3; }
-static hipError_t lean_image_launch(const void *layer_args, int, int grid, hipStream_t st) {
-  const LayerArgs a = *reinterpret_cast<const LayerArgs *>(layer_args);
-  const size_t smem = lean_lds_bytes(4 * MOM_STRIP_KS);
-  hipError_t e = mom_allow_lds(reinterpret_cast<const void *>(k_layer_lean<MOM_STRIP_KS>), smem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_layer_lean<MOM_STRIP_KS>), dim3(grid), dim3(kThreads), smem, st, a);
-  return hipGetLastError();
+static hipError_t lean_image_launch(const void *layer_args, const MomLaunchForm &, int grid, hipStream_t st) {
+  return mom_launch_lds(k_layer_lean<MOM_STRIP_KS>, grid, kThreads, lean_lds_bytes(4 * MOM_STRIP_KS), st,
+                        *reinterpret_cast<const LayerArgs *>(layer_args));
 }
 MOM_DEFINE_IMAGE(LEAN, MOM_STRIP_KS, lean_image_launch, lean_image_lds_bytes, lean_image_per_cu)
 #endif

@@ -10,54 +10,38 @@
 #include "mom_host.hpp"
 #include "mom_images.hpp"
 #include "mom_strip2.hpp"
-#include "mom_strip2_variants.hpp"
+#include "mom_image_variants.hpp"
 
 using namespace MOM_NS;
 
 static_assert(kMomStrip2SchedInts == (size_t)kS2SchedInts, "mom_images.hpp: size of LayerArgs::sched");
 
 // the sweep kernel, one per scheduling mode (mom_strip2.hpp) and, for the default mode 1, one per number of k-steps the zero-weight
-// streams let a strip product leave out (MOM_OPT_ZERO_SKIP bit 1, LayerArgs::nbw; mom_strip2_variants.hpp): KW = KS - kS2Skip[V].
-// Modes 0, 2 and 3 are the recorded forms of the scheduling experiments and keep KW = KS.  RB: the row-block rule (MOM_OPT_ZERO_SKIP
-// bit 2, the flag kS2RowBlocks in LayerArgs::nbw), default mode only and only where it changes a row tile.  SRC: the sources-only
-// form (MOM_OPT_SOURCES_ONLY, the flag kMomNbwSourcesOnly in LayerArgs::nbw), default mode only, for every (KW, RB) of it; a launch
-// in another mode takes its kernel with all four composite operators
-static_assert(MOM_STRIP_KS > kS2Skip[kS2Variants - 1], "momcore_strip2.hip: KS - skip >= 1");
-// EL: the table form of the elemental layer (MOM_OPT_ELEMENTAL, the flag kMomNbwElemental in LayerArgs::nbw), default mode only,
-// for every (KW, RB, SRC) of it
-template <int MODE, int V = 0, bool RB = false, bool SRC = false, bool EL = false>
-static hipError_t launch_s2(const LayerArgs &a, int grid, hipStream_t st) {
-  constexpr int KW = MOM_STRIP_KS - kS2Skip[V];
-  constexpr bool RBK = RB && s2_row_blocks_change(MOM_STRIP_KS, KW);
-  const size_t smem = s2_lds_bytes(4 * MOM_STRIP_KS);
-  hipError_t e = mom_allow_lds(reinterpret_cast<const void *>(k_layer_s2<MOM_STRIP_KS, MODE, KW, RBK, SRC, EL>), smem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_layer_s2<MOM_STRIP_KS, MODE, KW, RBK, SRC, EL>), dim3(grid), dim3(kThreads), smem, st, a);
-  return hipGetLastError();
+// streams let a strip product leave out (MOM_OPT_ZERO_SKIP bit 1, MomLaunchForm::nbw; mom_image_variants.hpp): KW = KS - kS2Skip[V].
+// Modes 0, 2 and 3 are the recorded forms of the scheduling experiments: KW = KS, all four composite operators, elemental_build.
+// Default mode only: RB, the row-block rule (MOM_OPT_ZERO_SKIP bit 2), instantiated only where it changes a row tile; SRC, the
+// sources-only form (MOM_OPT_SOURCES_ONLY), for every (KW, RB); EL, the table form of the elemental layer (MOM_OPT_ELEMENTAL), for
+// every (KW, RB, SRC)
+static_assert(MOM_STRIP_KS > kS2Skip[kSkipVariants - 1], "momcore_strip2.hip: KS - skip >= 1");
+using LayerKernel = void (*)(LayerArgs);
+static LayerKernel s2_kernel(int mode, int v, bool rb, bool src, bool el) {
+  if (mode != 1) return mode == 2 ? k_layer_s2<MOM_STRIP_KS, 2> : mode == 3 ? k_layer_s2<MOM_STRIP_KS, 3> : k_layer_s2<MOM_STRIP_KS, 0>;
+  return mom_with_int<0, kSkipVariants - 1>(v, [&](auto V) {
+    return mom_with_bool(rb, [&](auto RB) {
+      return mom_with_bool(src, [&](auto SRC) {
+        return mom_with_bool(el, [&](auto EL) -> LayerKernel {
+          constexpr int KW = MOM_STRIP_KS - kS2Skip[V];
+          constexpr bool RBK = RB && s2_row_blocks_change(MOM_STRIP_KS, KW);
+          return k_layer_s2<MOM_STRIP_KS, 1, KW, RBK, SRC, EL>;
+        });
+      });
+    });
+  });
 }
-template <bool RB, bool SRC, bool EL>
-static hipError_t launch_s2_default(const LayerArgs &a, int grid, hipStream_t st) {
-  switch (s2_variant_for(MOM_STRIP_KS, s2_nbw_count(a.nbw))) {
-    case 1: return launch_s2<1, 1, RB, SRC, EL>(a, grid, st);
-    case 2: return launch_s2<1, 2, RB, SRC, EL>(a, grid, st);
-    case 3: return launch_s2<1, 3, RB, SRC, EL>(a, grid, st);
-    default: return launch_s2<1, 0, RB, SRC, EL>(a, grid, st);
-  }
-}
-template <bool EL>
-static hipError_t launch_s2_form(const LayerArgs &a, int grid, hipStream_t st) {
-  if (a.nbw & kMomNbwSourcesOnly)
-    return s2_row_blocks_for(MOM_STRIP_KS, a.nbw) ? launch_s2_default<true, true, EL>(a, grid, st) : launch_s2_default<false, true, EL>(a, grid, st);
-  return s2_row_blocks_for(MOM_STRIP_KS, a.nbw) ? launch_s2_default<true, false, EL>(a, grid, st) : launch_s2_default<false, false, EL>(a, grid, st);
-}
-static hipError_t image_launch(const void *layer_args, int, int grid, hipStream_t st) {
-  const LayerArgs a = *reinterpret_cast<const LayerArgs *>(layer_args);
-  switch (a.sched_mode & 3) {
-    case 1: return (a.nbw & kMomNbwElemental) ? launch_s2_form<true>(a, grid, st) : launch_s2_form<false>(a, grid, st);
-    case 2: return launch_s2<2>(a, grid, st);
-    case 3: return launch_s2<3>(a, grid, st);
-    default: return launch_s2<0>(a, grid, st);
-  }
+static hipError_t image_launch(const void *layer_args, const MomLaunchForm &f, int grid, hipStream_t st) {
+  const LayerKernel k = s2_kernel(f.sched_mode & 3, mom_skip_variant(kS2Skip, MOM_STRIP_KS, f.nbw), s2_row_blocks_for(MOM_STRIP_KS, f),
+                                  f.sources_only, f.elemental_tab);
+  return mom_launch_lds(k, grid, kThreads, s2_lds_bytes(4 * MOM_STRIP_KS), st, *reinterpret_cast<const LayerArgs *>(layer_args));
 }
 // LDS bytes, 0 if the image does not apply to ns Stokes components per stream (nS per stream entry of the scene)
 static size_t image_lds_bytes(int ns, int nS, int) { return s2_applies(4 * MOM_STRIP_KS, ns, nS) ? s2_lds_bytes(4 * MOM_STRIP_KS) : 0; }

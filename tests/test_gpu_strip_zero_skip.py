@@ -61,12 +61,13 @@ def test_strip_zero_skip_equal_and_oracle(rtamd, cref, nS, lt, N, kw, brdf):
 
 
 def test_strip2_variant_host(tmp_path):
-    """Host only: the instantiation a launch of the two-buffer image takes for LayerArgs::nbw (mom_strip2_variants.hpp) -- the largest
-    instantiated skip that is still exact, none for nbw = 0 or out of range (tools/strip2_variant_check.hip)."""
-    exe = tmp_path / "strip2_variant_check"
+    """Host only: the instantiation a launch of the two-buffer image (KS = 13 .. 15, seven counts each) and of the quad-block image
+    (KS = 5 .. 10: the counts 0, KS + 1 and KS .. KS - 5 down to 1) takes for its MomLaunchForm (mom_image_variants.hpp) -- the
+    largest instantiated skip that is still exact, none for nbw = 0 or out of range (tools/image_variant_check.hip)."""
+    exe = tmp_path / "image_variant_check"
     csrc = ROOT / "radiativetransfer.jl_amd" / "csrc"
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "--offload-arch=gfx950", f"-I{ROOT / 'include'}", f"-I{csrc}",
-                           str(ROOT / "tools" / "strip2_variant_check.hip"), "-o", str(exe)])
+                           str(ROOT / "tools" / "image_variant_check.hip"), "-o", str(exe)])
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout
-    assert out.stdout.count(" ok") == 3 * 7 and "WRONG" not in out.stdout, out.stdout
+    assert out.stdout.count(" ok") == 3 * 7 + (6 * 8 - 1) and "WRONG" not in out.stdout, out.stdout   # (KS = 5 has no count KS - 5)
