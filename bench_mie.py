@@ -3,7 +3,8 @@
 (committed as profiles/mie_bench.json).  `bench_mie.py --dual OUT.json`: the Dual run with respect to all four aerosol
 parameters beside the value call in the same process (committed as profiles/mie_dual_bench.json).  `bench_mie.py --spectral
 OUT.json`: 16 wavelengths in one call (mom_mie_nai2_spectral) beside 16 single calls (committed as
-profiles/mie_spectral_bench.json).
+profiles/mie_spectral_bench.json).  `bench_mie.py --pcw OUT.json`: the Domke-PCW route (csrc/mom_pcw.hip, mom_mie_pcw) beside the
+NAI-2 call at the reference's test point (committed as profiles/mie_pcw_bench.json).
 
 Two points: the reference's own test point (test/test_Scattering.jl: λ = 0.55 µm, r_max = 30 µm, nquad_radius = 2500,
 m = 1.3 + 0.001i, LogNormal(log 0.3, log 6.82): x_max = 342.7, n_max = 381, n_μ = 761) and a small one (r_max = 1 µm, 37 radii:
@@ -155,6 +156,70 @@ def run_spectral_point(p, lam, repeats=5):
             "speedup_batch_over_single_calls": float(np.median(singles) / np.median(batch))}
 
 
+def run_pcw_point(p, repeats=7):
+    """mom_mie_pcw at the point beside mom_mie_nai2 on the same model, in the same process: the HIP-event times of the three kernel
+    groups of each (median and minimum over `repeats` calls after one that loads the code objects), the wall time of the device call
+    and of the public compute_aerosol_optical_properties, and the distance between the two routes' results.
+    Flop model of the Gram product X~ diag(w) X~^T: the lower triangle of a (4 N) x (4 N) product over nR radii, 2 (4 N)^2 nR / 2;
+    `flop_run` counts what the kernel runs (the lower triangle of 32 x 32 macro tiles of the (4 Np)^2 product, Np = N rounded up to
+    16, over the radii rounded up to 16)."""
+    import rtamd
+    sc = rtamd.scattering
+    aer = sc.Aerosol(sc.LogNormal(math.log(p["r_m"]), math.log(p["sigma_g"])), p["n_r"], p["n_i"])
+    legs, optics = {}, {}
+    for name, ctype in (("pcw", sc.PCW()), ("nai2", sc.NAI2())):
+        model = sc.make_mie_model(ctype, aer, p["lam"], None, None, p["r_max"], p["nquad_radius"])
+        if name == "pcw":
+            r, wx, N = sc.pcw_inputs(model)
+            call_dev = lambda: rtamd._lib.mie_pcw(r, wx, p["lam"], p["n_r"], p["n_i"], N)[2]
+            groups = ("coefficients", "radius_averages", "symbols_and_sums")
+        else:
+            inp = sc.mie_inputs(model)
+            args = (inp.r, inp.w, p["lam"], p["n_r"], p["n_i"], inp.w_μ, inp.π_, inp.τ_, inp.P, inp.P2, inp.R2, inp.T2)
+            call_dev = lambda: rtamd._lib.mie_nai2(*args)[3]
+            groups = ("coefficients", "amplitude_gemm_and_reduction", "projection")
+        call_dev()
+        ms, wall = [], []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            ms.append(call_dev())
+            wall.append((time.perf_counter() - t0) * 1e3)
+        ms = np.array(ms)
+        whole = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            optics[name] = sc.compute_aerosol_optical_properties(model)
+            whole.append((time.perf_counter() - t0) * 1e3)
+        legs[name] = {"repeats": repeats,
+                      "kernels_ms_median": {**{g: float(v) for g, v in zip(groups, np.median(ms, axis=0))}, "sum": float(np.median(ms.sum(axis=1)))},
+                      "kernels_ms_min": {**{g: float(v) for g, v in zip(groups, ms.min(axis=0))}, "sum": float(ms.sum(axis=1).min())},
+                      "device_call_wall_ms_median": float(np.median(wall)),
+                      "compute_aerosol_optical_properties_wall_ms_median": float(np.median(whole))}
+    Np, ld = -(-N // 16) * 16, -(-r.size // 16) * 16
+    mrows = 4 * Np // 32
+    flop_run = 2.0 * (mrows * (mrows + 1) // 2) * 32 * 32 * ld
+    flop_alg = 2.0 * (4 * N) ** 2 * r.size / 2
+    t = legs["pcw"]["kernels_ms_median"]["radius_averages"] * 1e-3
+    rows = lambda g: (g.α, g.β, g.γ, g.δ, g.ϵ, g.ζ)
+    dist = {q: float(np.linalg.norm(a - b) / max(np.linalg.norm(a), np.linalg.norm(b)))
+            for q, a, b in zip(("α", "β", "γ", "δ", "ϵ", "ζ"), rows(optics["pcw"].greek_coefs), rows(optics["nai2"].greek_coefs))}
+    return {"n_radii": int(r.size), "N_max": int(N), "degrees": int(2 * N - 1), **legs,
+            "radius_averages": {"note": "the group holds the diagonal sums, the Gram product and the chunk sum with the plane layout; the rate "
+                                        "below divides the Gram product's flop by the time of the whole group",
+                                "flop_algorithmic": flop_alg, "flop_run": flop_run,
+                                "roofline": {"bound": "mfma", "achieved": flop_run / t / 1e12, "algorithmic_achieved": flop_alg / t / 1e12,
+                                             "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": flop_run / t / 1e12 / PEAK_FP64_MFMA_TFLOPS}},
+            "pcw_minus_nai2": {"norm2_relative": dist, "omega": float(optics["pcw"].ω̃ - optics["nai2"].ω̃),
+                               "k_relative": float(optics["pcw"].k / optics["nai2"].k - 1)}}
+
+
+def run_pcw():
+    out = {"metric": "Mie Domke-PCW aerosol optics at the reference's test point: kernels of one call", "unit": "ms"}
+    out["reference_test_point"] = run_pcw_point(POINTS["reference_test_point"])
+    out["value"] = out["reference_test_point"]["pcw"]["kernels_ms_median"]["sum"]
+    return out
+
+
 def run_spectral():
     out = {"metric": "Mie NAI-2 aerosol optics, 16 wavelengths (0.4 .. 2.2 µm) in one spectral call: wall time of the public call",
            "unit": "ms"}
@@ -180,8 +245,11 @@ def run_dual():
 
 
 if __name__ == "__main__":
-    argv = [a for a in sys.argv[1:] if a not in ("--dual", "--spectral")]
-    res = run_dual() if "--dual" in sys.argv[1:] else (run_spectral() if "--spectral" in sys.argv[1:] else run())
+    argv = [a for a in sys.argv[1:] if a not in ("--dual", "--spectral", "--pcw")]
+    if "--pcw" in sys.argv[1:]:
+        res = run_pcw()
+    else:
+        res = run_dual() if "--dual" in sys.argv[1:] else (run_spectral() if "--spectral" in sys.argv[1:] else run())
     if argv:
         Path(argv[0]).parent.mkdir(parents=True, exist_ok=True)
         Path(argv[0]).write_text(json.dumps(res, indent=1, ensure_ascii=False) + "\n")

@@ -806,6 +806,47 @@ int mom_mie_nai2_spectral_dual(int device, int nR, const double *r, int nW, cons
                                const double *n_r, const double *n_i, int n_mu, const double *mu, const double *w_mu, int n_max,
                                int l_max, int flags, int max_batch, double *bulk_f, double *C, double *greek, double *gpu_ms);
 
+/* ---- Mie aerosol optics: Domke-PCW -------------------------------------------------------------
+ * compute_aerosol_optical_properties(model::MieModel{PCW}) (src/Scattering/compute_PCW.jl:16-193; Sanghavi 2014, eq. 22-24): the
+ * Greek coefficients expanded directly in the Mie coefficients, with Wigner 3j symbols and no scattering-angle quadrature; the
+ * independent check of mom_mie_nai2.  Float64, handle-free, error text: mom_last_global_error().  The reference reads the symbols
+ * from two tables it loads (compute_wigner_values); here they are produced in registers by the recursions of
+ * compute_wigner_values.jl and no table exists.
+ *   r [nR], lambda, n_r, n_i as for mom_mie_nai2
+ *   w [nR]                  w_x, the weights of the size distribution themselves (NOT times 4 pi r^2)
+ *   N_max                   get_n_max(2 pi r_max / lambda), at least the largest n_max,i; 1 <= N_max <= MOM_PCW_MAX_ORDER
+ *   flags                   0
+ * Outputs (host):
+ *   greek [6, 2 N_max - 1]  alpha, beta, gamma, delta, epsilon, zeta of compute_PCW.jl:86-100, NOT divided by C_sca (host arithmetic)
+ *   C [2]                   compute_avg_C_scatt_ext: C_sca, C_ext
+ *   gpu_ms [3] or NULL      HIP-event times (ms): coefficient kernel, radius averages, symbols and sums
+ * The pair averages of compute_avg_anbns! are one symmetric product X~ diag(w) X~^T on v_mfma_f64_16x16x4, X = [Re a; Im a; Re b;
+ * Im b]; as in the reference a radius enters a pair average only for orders below its own n_max,i (strict), and keeps order
+ * n_max,i in C_sca, C_ext and the sums of |a_n +- b_n|^2.  Every reduction has a fixed order: two calls are bitwise equal.
+ * MOM_EINVAL: nR < 1, lambda <= 0, n_i < 0, r not ascending or r[0] <= 0, N_max outside 1..MOM_PCW_MAX_ORDER or smaller than the
+ * largest n_max,i, flags != 0, a null pointer (gpu_ms excepted). */
+enum { MOM_PCW_MAX_ORDER = 640 };
+int mom_mie_pcw(int device, int nR, const double *r, const double *w, double lambda, double n_r, double n_i, int N_max, int flags,
+                double *greek, double *C, double *gpu_ms);
+
+/* compute_wigner_values(m_max, n_max, l_max) (compute_wigner_values.jl:190-210): wigner_A = (m n l-1; -1 1 0) and wigner_B =
+ * (m n l-1; -1 -1 2) as two tables [l_max, n_max, m_max] with m fastest (the reference's column-major [m_max, n_max, l_max]),
+ * entry (m - 1, n - 1, l - 1); exact zeros outside |n - (l - 1)| <= m <= n + l - 1 and, in wigner_B, for l - 1 < 2.  One lane per
+ * (n, l) column runs the device function mom_mie_pcw walks.  A column starts at m = n + l - 1 whatever m_max is, so a table keeps
+ * the symbols' values where the reference's memoised recursion, which answers 0 beyond the table's extent, leaves zeros (columns
+ * with n + l - 1 > m_max).  Two calls are bitwise equal.
+ * MOM_EINVAL: a size < 1, n_max + l_max > 1900 (the recursion's 64-bit integer products), a table above
+ * MOM_WIGNER_MAX_TABLE_BYTES (checked before any allocation), a null pointer. */
+enum { MOM_WIGNER_MAX_TABLE_BYTES = 1073741824 };   /* 1 GiB */
+int mom_wigner_tables(int device, int m_max, int n_max, int l_max, double *A, double *B);
+
+/* Test access: the four pair averages of compute_avg_anbns! for the arguments of mom_mie_pcw, sum_i w_i conj(a_n) a_m, conj(a_n) b_m,
+ * conj(b_n) a_m, conj(b_n) b_m, as eight real arrays [N_max, N_max], entry [m - 1][n - 1] for m >= n, zeros above the diagonal.
+ * MOM_EINVAL as mom_mie_pcw; no pointer may be null. */
+int mom_pcw_pair_averages(int device, int nR, const double *r, const double *w, double lambda, double n_r, double n_i, int N_max,
+                          double *anam_re, double *anam_im, double *anbm_re, double *anbm_im, double *bnam_re, double *bnam_im,
+                          double *bnbm_re, double *bnbm_im);
+
 #ifdef __cplusplus
 }
 #endif

@@ -550,4 +550,30 @@ function mie_nai2_spectral_dual(arch::MI355X, r, w_rows, Î», náµ£, náµ¢, Î¼, w_Î
                                                 max_batch, bulk_f, C, greek, ms))
     return bulk_f, C, greek, ms
 end
+"""
+compute_aerosol_optical_properties(model::MieModel{<:PCW}) (src/Scattering/compute_PCW.jl:16-104) with architecture isa MI355X: the
+Mie coefficients, the pair averages of compute_avg_anbns!, the Wigner 3j symbols and the sums S_l of eq. 22 are ONE call.  The device
+produces the symbols in registers, so `model.wigner_A` / `model.wigner_B` are not read and need not be loaded.  The host keeps the
+radius quadrature and `wâ‚“` [nR] (the weights themselves, not times 4Ï€ rÂ²), N_max = get_n_max(2Ï€ r_max / Î»), and the (1 / C_sca).
+"""
+function mie_pcw(arch::MI355X, r, wâ‚“, Î», náµ£, náµ¢, N_max)
+    nR = length(r);  L = 2N_max - 1
+    greek = zeros(Float64, L, 6);  C = zeros(Float64, 2);  ms = zeros(Float64, 3)
+    momcheck(MomCore.mom_mie_pcw(arch.device, nR, collect(Float64, r), collect(Float64, wâ‚“), Float64(Î»), Float64(náµ£), Float64(náµ¢), N_max, 0,
+                                 greek, C, ms))
+    C_sca, C_ext = C[1], C[2]
+    value = (Î± = (1 / C_sca) .* greek[:, 1], Î² = (1 / C_sca) .* greek[:, 2], Î³ = (1 / C_sca) .* greek[:, 3], Î´ = (1 / C_sca) .* greek[:, 4],
+             Ïµ = (1 / C_sca) .* greek[:, 5], Î¶ = (1 / C_sca) .* greek[:, 6], Ï‰Ìƒ = C_sca / C_ext, k = C_ext, fáµ— = 1.0)
+    return value, ms
+end
+
+"""
+compute_wigner_values(m_max, n_max, l_max) (src/Scattering/compute_wigner_values.jl:190-210) on the device: wigner_A and wigner_B
+[m_max, n_max, l_max], column-major as the ABI writes them.  A PCW run on the device needs neither.
+"""
+function compute_wigner_values(arch::MI355X, m_max, n_max, l_max)
+    A = zeros(Float64, m_max, n_max, l_max);  B = zeros(Float64, m_max, n_max, l_max)
+    momcheck(MomCore.mom_wigner_tables(arch.device, m_max, n_max, l_max, A, B))
+    return A, B
+end
 # <<< mie

@@ -49,6 +49,7 @@ MOM_OPT_ELEMENTAL = 17           # 1 (default): the two-buffer strip and quad-bl
 BROADENING_VOIGT, BROADENING_DOPPLER, BROADENING_LORENTZ = 0, 1, 2
 CEF_HW32SD, CEF_HW32VOIGT = 0, 1
 MOM_MIE_FULL_K = 1   # mom_mie_nai2 flag: every radius tile sums l to the global n_max (test access; bitwise the same result)
+MOM_PCW_MAX_ORDER, MOM_WIGNER_MAX_TABLE_BYTES = 640, 1 << 30   # mom_mie_pcw: largest N_max; mom_wigner_tables: largest table
 MOM_MIE_DUAL_MAX_WEIGHT_ROWS, MOM_MIE_INDEX_ROWS = 3, 2   # mom_mie_nai2_dual: at most 3 weight rows; 2 more output rows (n_r, n_i)
 
 
@@ -166,6 +167,9 @@ SIGNATURES = {
                                         C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp]),
     "mom_mie_nai2_spectral_dual": (C.c_int, [C.c_int, C.c_int, c_dp, C.c_int, c_dp, C.c_int, c_dp, c_dp, c_dp, C.c_int, c_dp, c_dp,
                                              C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp]),
+    "mom_mie_pcw": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, c_dp, c_dp, c_dp]),
+    "mom_wigner_tables": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp]),
+    "mom_pcw_pair_averages": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, C.c_double, C.c_double, C.c_double, C.c_int] + [c_dp] * 8),
 }
 
 _lib = None
@@ -929,3 +933,45 @@ def mie_nai2_spectral(r, w, lam, n_r, n_i, mu, w_mu, n_max: int, l_max: int, fla
 def mie_nai2_spectral_dual(r, w, lam, n_r, n_i, mu, w_mu, n_max: int, l_max: int, flags: int = 0, max_batch: int = 0, device: int = 0):
     """mom_mie_nai2_spectral_dual: as mie_nai2_spectral (nW <= 3) with nW + 2 rows per wavelength, the last two d/dn_r and d/dn_i"""
     return _mie_nai2_spectral(True, r, w, lam, n_r, n_i, mu, w_mu, n_max, l_max, flags, max_batch, device)
+
+
+def mie_pcw(r, w, lam, n_r, n_i, N_max: int, flags: int = 0, device: int = 0):
+    """mom_mie_pcw: r [nR] ascending, w [nR] = w_x.  Returns (greek [6, 2 N_max - 1] not divided by C_sca, C [2] = (C_sca, C_ext),
+    gpu_ms [3])."""
+    lib = load()
+    r, w = f64(r), f64(w)
+    if r.ndim != 1 or w.shape != r.shape:
+        raise ValueError("mie_pcw: r and w must be vectors of one length")
+    N_max = int(N_max)
+    greek, Cx, ms = np.empty((6, max(2 * N_max - 1, 1))), np.empty(2), np.zeros(3)
+    rc = lib.mom_mie_pcw(device, len(r), dp(r), dp(w), float(lam), float(n_r), float(n_i), N_max, int(flags), dp(greek), dp(Cx), dp(ms))
+    if rc != MOM_OK:
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return greek, Cx, ms
+
+
+def wigner_tables(m_max: int, n_max: int, l_max: int, device: int = 0):
+    """mom_wigner_tables: (wigner_A, wigner_B), each indexed [m - 1, n - 1, l - 1] like the reference's arrays (views of the ABI's
+    m-fastest layout: column-major, as Julia holds them)."""
+    lib = load()
+    m_max, n_max, l_max = int(m_max), int(n_max), int(l_max)
+    ok = min(m_max, n_max, l_max) >= 1 and m_max * n_max * l_max * 8 <= MOM_WIGNER_MAX_TABLE_BYTES
+    out = [np.empty((l_max, n_max, m_max) if ok else (1,)) for _ in range(2)]   # a refused size is refused by the library, unallocated
+    rc = lib.mom_wigner_tables(device, m_max, n_max, l_max, dp(out[0]), dp(out[1]))
+    if rc != MOM_OK:
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return out[0].transpose(2, 1, 0), out[1].transpose(2, 1, 0)
+
+
+def pcw_pair_averages(r, w, lam, n_r, n_i, N_max: int, device: int = 0):
+    """mom_pcw_pair_averages: (anam, anbm, bnam, bnbm) complex [N_max, N_max], entry [m - 1, n - 1] for m >= n."""
+    lib = load()
+    r, w = f64(r), f64(w)
+    if r.ndim != 1 or w.shape != r.shape:
+        raise ValueError("pcw_pair_averages: r and w must be vectors of one length")
+    N_max = int(N_max)
+    out = [np.empty((max(N_max, 1), max(N_max, 1))) for _ in range(8)]
+    rc = lib.mom_pcw_pair_averages(device, len(r), dp(r), dp(w), float(lam), float(n_r), float(n_i), N_max, *[dp(o) for o in out])
+    if rc != MOM_OK:
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return tuple(out[2 * q] + 1j * out[2 * q + 1] for q in range(4))

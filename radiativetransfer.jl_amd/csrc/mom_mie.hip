@@ -24,6 +24,8 @@
 // grid and its tables are shared, and what differs per wavelength -- m, x, sin x, cos x, n_max, the planes, the sums -- is found
 // through a small device array (MieWave) indexed by that dimension.  The single-wavelength calls are the batch of one.  For a batch
 // the tables of (b) and (d) are built on the device from the Gauss nodes (k_mie_tables) instead of uploaded.
+//
+// The PCW route (mom_pcw.hip) starts from the same a_n, b_n: it launches (a) through mom_mie_ab.hpp (at the end of this file).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,6 +35,7 @@
 
 #include "momcore.h"
 #include "mom_host.hpp"
+#include "mom_mie_ab.hpp"
 
 namespace {
 
@@ -794,45 +797,27 @@ int mie_coefficients_run(const char *fn, bool dual, int device, int nX, const do
   for (int q = 0; q < (dual ? 8 : 4); ++q) null = null || !out[q];
   if (nX < 1 || n_max < 1 || null) return mie_fail(fn, "bad argument (null pointer or non-positive size)");
   if (!(n_i >= 0.0) || !std::isfinite(n_r) || !std::isfinite(n_i)) return mie_fail(fn, "n_i must be >= 0 (m = n_r + i n_i)");
-  std::vector<int> hn(2 * (size_t)nX);
   for (int i = 0; i < nX; ++i) {
     if (!(x[i] > 0.0) || !std::isfinite(x[i])) return mie_fail(fn, "x must be positive");
-    hn[i] = mie_n_max(x[i]);
-    hn[nX + i] = mie_nmx(x[i], hn[i], n_r, n_i);
-    if (hn[i] > n_max) return mie_fail(fn, "n_max is smaller than the largest per-x n_max");
+    if (mie_n_max(x[i]) > n_max) return mie_fail(fn, "n_max is smaller than the largest per-x n_max");
   }
   int rc = mie_device(fn, device);
   if (rc != MOM_OK) return rc;
   const size_t nPl = (size_t)n_max * nX;
-  const int nOut = dual ? 8 : 4, nDp = dual ? 4 : 2;  // planes a, b (Dual: a', b'), then D (Dual: D')
-  const size_t bytes = ((nOut + nDp) * nPl + 3 * (size_t)nX) * sizeof(double) + sizeof(MieWave) + 2 * (size_t)nX * sizeof(int);
-  const MieWave hw = {n_r, n_i, 0, 0, 0, 0};  // a batch of one
-  const std::vector<double> hsc = mie_sin_cos(x, nX, (size_t)nX);
+  const int nOut = dual ? 8 : 4;  // planes a, b (Dual: a', b')
+  const size_t bytes = nOut * nPl * sizeof(double) + mom_mie_ab::workspace_bytes(n_max, (size_t)nX, dual);
   char *base = nullptr;
   hipStream_t st = nullptr;
   MCHK(hipSetDevice(device));
   MCHK(hipStreamCreate(&st));
   MCHK(hipMalloc((void **)&base, bytes));
   {
-    double *d_pl = (double *)base, *d_D = d_pl + nOut * nPl, *d_x = d_D + nDp * nPl;
-    double *d_sc = d_x + nX;  // sin x | cos x
-    MieWave *d_wave = (MieWave *)(d_sc + 2 * (size_t)nX);
-    int *d_n = (int *)(d_wave + 1);
+    double *d_pl = (double *)base;
+    const int *d_n = nullptr;
     MCHK(hipMemsetAsync(base, 0, bytes, st));
-    MCHK(hipMemcpyAsync(d_wave, &hw, sizeof hw, hipMemcpyHostToDevice, st));
-    MCHK(hipMemcpyAsync(d_x, x, (size_t)nX * sizeof(double), hipMemcpyHostToDevice, st));
-    MCHK(hipMemcpyAsync(d_sc, hsc.data(), 2 * (size_t)nX * sizeof(double), hipMemcpyHostToDevice, st));
-    MCHK(hipMemcpyAsync(d_n, hn.data(), 2 * (size_t)nX * sizeof(int), hipMemcpyHostToDevice, st));
-    if (dual) {
-      const MieDualOut dd = {d_D + 2 * nPl, d_D + 3 * nPl, d_pl + 4 * nPl, d_pl + 5 * nPl, d_pl + 6 * nPl, d_pl + 7 * nPl, nullptr};
-      hipLaunchKernelGGL((k_mie_ab<false, true>), dim3((nX + 63) / 64), dim3(64), 0, st, nX, nX, d_wave, d_x, d_sc, d_sc + nX, d_n, d_n + nX, d_D, d_D + nPl,
-                         d_pl, d_pl + nPl, d_pl + 2 * nPl, d_pl + 3 * nPl, (double *)nullptr, (double *)nullptr, dd);
-    } else {
-      const MieDualOut dd = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-      hipLaunchKernelGGL((k_mie_ab<false, false>), dim3((nX + 63) / 64), dim3(64), 0, st, nX, nX, d_wave, d_x, d_sc, d_sc + nX, d_n, d_n + nX, d_D, d_D + nPl,
-                         d_pl, d_pl + nPl, d_pl + 2 * nPl, d_pl + 3 * nPl, (double *)nullptr, (double *)nullptr, dd);
-    }
-    MCHK(hipGetLastError());
+    rc = mom_mie_ab::launch(fn, st, nX, (size_t)nX, x, n_r, n_i, n_max, nPl, d_pl, base + nOut * nPl * sizeof(double), nullptr, &d_n, nullptr,
+                            nullptr, dual);
+    if (rc != MOM_OK) goto done;
     for (int q = 0; q < nOut; ++q) MCHK(hipMemcpyAsync(out[q], d_pl + q * nPl, nPl * sizeof(double), hipMemcpyDeviceToHost, st));
     MCHK(hipStreamSynchronize(st));
   }
@@ -843,6 +828,58 @@ done:
 }
 
 }  // namespace
+
+// ---- the coefficient kernel for the other routes (mom_mie_ab.hpp) ---------------------------------------------------------
+namespace mom_mie_ab {
+
+int n_max_of(double x) { return mie_n_max(x); }
+
+size_t workspace_bytes(int n_max, size_t ld, bool dual) {
+  return ((dual ? 4 : 2) * (size_t)n_max * ld + 3 * ld) * sizeof(double) + sizeof(MieWave) + 2 * ld * sizeof(int);
+}
+
+int launch(const char *fn, hipStream_t st, int nX, size_t ld, const double *x, double n_r, double n_i, int n_max, size_t plane_stride,
+           double *d_planes, char *d_ws, int *h_nmax, const int **d_nmax, hipEvent_t ev0, hipEvent_t ev1, bool dual) {
+  std::vector<int> hn(2 * ld, 0);
+  for (int i = 0; i < nX; ++i) {
+    hn[i] = mie_n_max(x[i]);
+    hn[ld + i] = mie_nmx(x[i], hn[i], n_r, n_i);
+    if (hn[i] > n_max) return mie_fail(fn, "n_max is smaller than the largest per-x n_max");
+    if (h_nmax) h_nmax[i] = hn[i];
+  }
+  const MieWave hw = {n_r, n_i, 0, 0, 0, 0};  // a batch of one
+  const std::vector<double> hsc = mie_sin_cos(x, nX, ld);
+  const size_t nD = (size_t)n_max * ld, ps = plane_stride;
+  double *d_D = (double *)d_ws, *d_x = d_D + (dual ? 4 : 2) * nD, *d_sc = d_x + ld;  // D (Dual: D'), x, sin x | cos x
+  MieWave *d_wave = (MieWave *)(d_sc + 2 * ld);
+  int *d_n = (int *)(d_wave + 1);
+  int rc = MOM_OK;
+  MCHK(hipMemcpyAsync(d_wave, &hw, sizeof hw, hipMemcpyHostToDevice, st));
+  MCHK(hipMemcpyAsync(d_x, x, (size_t)nX * sizeof(double), hipMemcpyHostToDevice, st));
+  MCHK(hipMemcpyAsync(d_sc, hsc.data(), 2 * ld * sizeof(double), hipMemcpyHostToDevice, st));
+  MCHK(hipMemcpyAsync(d_n, hn.data(), 2 * ld * sizeof(int), hipMemcpyHostToDevice, st));
+  MCHK(hipStreamSynchronize(st));  // the host arrays above end with this call
+  if (ev0) MCHK(hipEventRecord(ev0, st));
+  {
+    const dim3 grid((nX + 63) / 64);
+    if (dual) {
+      const MieDualOut dd = {d_D + 2 * nD, d_D + 3 * nD, d_planes + 4 * ps, d_planes + 5 * ps, d_planes + 6 * ps, d_planes + 7 * ps, nullptr};
+      hipLaunchKernelGGL((k_mie_ab<false, true>), grid, dim3(64), 0, st, nX, (int)ld, d_wave, d_x, d_sc, d_sc + ld, d_n, d_n + ld, d_D, d_D + nD,
+                         d_planes, d_planes + ps, d_planes + 2 * ps, d_planes + 3 * ps, (double *)nullptr, (double *)nullptr, dd);
+    } else {
+      const MieDualOut dd = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+      hipLaunchKernelGGL((k_mie_ab<false, false>), grid, dim3(64), 0, st, nX, (int)ld, d_wave, d_x, d_sc, d_sc + ld, d_n, d_n + ld, d_D, d_D + nD,
+                         d_planes, d_planes + ps, d_planes + 2 * ps, d_planes + 3 * ps, (double *)nullptr, (double *)nullptr, dd);
+    }
+  }
+  MCHK(hipGetLastError());
+  if (ev1) MCHK(hipEventRecord(ev1, st));
+  *d_nmax = d_n;
+done:
+  return rc;
+}
+
+}  // namespace mom_mie_ab
 
 // the single-wavelength calls: the batch of one on the host's tables; gpu_ms [3] is without the tables group
 static int mie_nai2_single(const char *fn, bool dual, int device, int nR, const double *r, int nW, const double *w, double lambda,

@@ -1,5 +1,5 @@
-"""Mie aerosol optics (src/Scattering): make_mie_model(NAI2(), ...), compute_aerosol_optical_properties,
-compute_ref_aerosol_extinction and truncate_phase(δBGE, ...).
+"""Mie aerosol optics (src/Scattering): make_mie_model(NAI2() or PCW(), ...), compute_aerosol_optical_properties,
+compute_ref_aerosol_extinction, compute_wigner_values and truncate_phase(δBGE, ...).
 
 The sums over radii, orders and angles run on the device (mom_mie_nai2, csrc/mom_mie.hip); the host builds what they read --
 the radius quadrature, the Gauss nodes of the scattering angle, the π/τ and P/P²/R²/T² tables (O(n_μ²) recurrences, vectorised
@@ -8,7 +8,11 @@ rule of the partial rows.  Partials with respect to the refractive index (nᵣ, 
 (mom_mie_nai2_dual); truncate_phase and aerosol_optics_partial carry them on to rt_run_dual_device_optics.
 compute_spectral_aerosol_optical_properties runs a whole array of wavelengths in one device call (mom_mie_nai2_spectral) on one
 angle grid, whose tables the device builds itself (mom_mie_tables): there the host brings the nodes only.
-Float64 only; NAI2 only (no PCW).  There is no CPU fallback.
+A PCW() model takes the Domke-PCW route (mom_mie_pcw, csrc/mom_pcw.hip): the Greek coefficients expanded directly in the Mie
+coefficients with Wigner 3j symbols, no angle quadrature -- the independent check of NAI-2.  The device produces the symbols in
+registers, so the model's wigner_A / wigner_B are accepted and not needed; compute_wigner_values returns the reference's two tables
+for whoever wants them (mom_wigner_tables).  The host brings the radii and w_x and divides by C_sca.  No partials on this route.
+Float64 only.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -57,7 +61,12 @@ class Aerosol:
 
 @dataclass
 class NAI2:
-    """Siewert's numerical angular integration (the only computation type built here)."""
+    """Siewert's numerical angular integration (the default; the route that carries partials and wavelength batches)."""
+
+
+@dataclass
+class PCW:
+    """Domke's expansion in Wigner 3j symbols (Sanghavi 2014, eq. 22-24): values only."""
 
 
 @dataclass
@@ -68,22 +77,29 @@ class δBGE:
 
 @dataclass
 class MieModel:
-    computation_type: NAI2
+    computation_type: object      # NAI2 or PCW
     aerosol: Aerosol
     λ: float
     polarization_type: object
     truncation_type: Optional[δBGE]
     r_max: float
     nquad_radius: int
+    wigner_A: Optional[np.ndarray] = None    # the reference's PCW models carry their tables; the device needs none
+    wigner_B: Optional[np.ndarray] = None
 
 
 def make_mie_model(computation_type, aerosol: Aerosol, λ: float, polarization_type, truncation_type, r_max: float,
-                   nquad_radius: int) -> MieModel:
-    if not isinstance(computation_type, NAI2):
-        raise NotImplementedError("only NAI2() is built (PCW needs Wigner 3j symbols)")
+                   nquad_radius: int, wigner_A=None, wigner_B=None) -> MieModel:
+    """make_mie_model.jl: NAI2() takes the seven arguments; PCW() also takes the reference's wigner_A, wigner_B, which are kept on
+    the model and not read (mom_mie_pcw produces the symbols itself)."""
+    if not isinstance(computation_type, (NAI2, PCW)):
+        raise NotImplementedError(f"computation type {computation_type!r}: NAI2() and PCW() are built")
+    if isinstance(computation_type, NAI2) and (wigner_A is not None or wigner_B is not None):
+        raise ValueError("wigner_A and wigner_B belong to a PCW() model")
     if aerosol.nᵢ < 0:
         raise ValueError("the imaginary part of the refractive index must be >= 0")
-    return MieModel(computation_type, aerosol, float(λ), polarization_type, truncation_type, float(r_max), int(nquad_radius))
+    return MieModel(computation_type, aerosol, float(λ), polarization_type, truncation_type, float(r_max), int(nquad_radius),
+                    wigner_A, wigner_B)
 
 
 # ------------------------------------------------------------------------------------------
@@ -237,13 +253,46 @@ def optics_from_sums(C: np.ndarray, greek: np.ndarray):
     return aero, partials
 
 
+def compute_wigner_values(m_max: int, n_max: Optional[int] = None, l_max: Optional[int] = None):
+    """compute_wigner_values(m_max, n_max, l_max) -> (wigner_A, wigner_B), indexed [m - 1, n - 1, l - 1]: the 3j symbols
+    (m n l-1; -1 1 0) and (m n l-1; -1 -1 2), by the reference's recursions on the device (mom_wigner_tables).  The shorthand
+    compute_wigner_values(N_max) is compute_wigner_values(2 N_max + 1, N_max + 1, 2 N_max + 1).  A table holds the symbols' values
+    in every column, also where the column starts beyond m_max (the reference's memoised recursion leaves zeros there)."""
+    if n_max is None and l_max is None:
+        m_max, n_max, l_max = 2 * int(m_max) + 1, int(m_max) + 1, 2 * int(m_max) + 1
+    elif n_max is None or l_max is None:
+        raise TypeError("compute_wigner_values takes (N_max) or (m_max, n_max, l_max)")
+    return _lib.wigner_tables(m_max, n_max, l_max)
+
+
+def pcw_inputs(model: MieModel):
+    """(r, wₓ, N_max) of a PCW model (compute_PCW.jl:30-36): N_max from r_max, not from the largest quadrature node"""
+    r, wᵣ = gauleg(model.nquad_radius, 0.0, model.r_max, norm=True)
+    p = model.aerosol.size_distribution.pdf(r) * wᵣ
+    return r, p / p.sum(), int(get_n_max(2 * math.pi * model.r_max / model.λ))
+
+
+def _pcw_optics(model: MieModel):
+    """compute_PCW.jl:16-104: the device sums, then (1 / C_sca) times each of them"""
+    r, wₓ, N_max = pcw_inputs(model)
+    greek, C, _ = _lib.mie_pcw(r, wₓ, model.λ, model.aerosol.nᵣ, model.aerosol.nᵢ, N_max)
+    Cs, Ce = C
+    return rt.AerosolOptics(greek_coefs=_greek((1 / Cs) * greek), ω̃=float(Cs / Ce), fᵗ=1.0, k=float(Ce))
+
+
 def compute_aerosol_optical_properties(model: MieModel, autodiff: bool = False, wrt=_SIZE_PARAMETERS):
     """AerosolOptics(greek_coefs, ω̃, k, fᵗ = 1) of the model; with autodiff=True also the partials of every field with respect to
     the parameters named in `wrt`, a subset of ALL_AEROSOL_PARAMETERS = (r_m, σ_g, nᵣ, nᵢ): the median radius and geometric width
     of the log-normal size distribution and the real and imaginary part of the refractive index.  Returns
     (optics, [∂/∂p for p in wrt]), each partial an AerosolOptics holding the derivatives.  The size-distribution partials are
     further weight rows of the same sums (mom_mie_nai2); an index parameter takes the Dual run of the Mie coefficients
-    (mom_mie_nai2_dual).  The default, (r_m, σ_g), is the call without `wrt`."""
+    (mom_mie_nai2_dual).  The default, (r_m, σ_g), is the call without `wrt`.
+    The model's computation type chooses the route: NAI2() the sums over scattering angles, PCW() the expansion in Wigner 3j symbols
+    (mom_mie_pcw), which has values only (autodiff=True raises NotImplementedError)."""
+    if isinstance(model.computation_type, PCW):
+        if autodiff:
+            raise NotImplementedError("autodiff=True is NAI-2's (as in the reference): make the model with NAI2()")
+        return _pcw_optics(model)
     if not autodiff:
         _, (_, C, greek, _) = _device_call(model, False)
         return optics_from_sums(C, greek)[0]

@@ -85,16 +85,17 @@ def make_scene(nStokes: int, l_trunc: int, Nz: int, S: int, ν_lo: float = 12903
 
 
 def make_mie_scene(nStokes: int, l_trunc: int, Nz: int, S: int, r_m: float = 0.3, σ_g: float = 1.6, nᵣ: float = 1.3, nᵢ: float = 0.001,
-                   λ: float = 0.76, r_max: float = 1.0, nquad_radius: int = 37, truncation=None, **kw) -> rt.vSmartMOM_Model:
+                   λ: float = 0.76, r_max: float = 1.0, nquad_radius: int = 37, truncation=None, computation_type=None,
+                   **kw) -> rt.vSmartMOM_Model:
     """make_scene with a Mie aerosol in place of hg_like_greek: a log-normal size distribution (median radius r_m, geometric
     width σ_g, in the unit of λ) of spheres with refractive index nᵣ + i nᵢ through compute_aerosol_optical_properties (device)
-    and truncate_phase(truncation), by default δBGE(l_trunc, 2.0)."""
+    and truncate_phase(truncation), by default δBGE(l_trunc, 2.0).  computation_type: NAI2() (the default) or PCW()."""
     from . import scattering as sc
     m = make_scene(nStokes, l_trunc, Nz, S, **kw)
     if not m.aerosol_optics:
         raise ValueError("make_mie_scene needs aerosol_total > 0")
     aerosol = sc.Aerosol(sc.LogNormal(math.log(r_m), math.log(σ_g)), nᵣ, nᵢ)
-    mie = sc.make_mie_model(sc.NAI2(), aerosol, λ, m.params.polarization_type, truncation or sc.δBGE(l_trunc, 2.0), r_max, nquad_radius)
+    mie = sc.make_mie_model(computation_type or sc.NAI2(), aerosol, λ, m.params.polarization_type, truncation or sc.δBGE(l_trunc, 2.0), r_max, nquad_radius)
     m.aerosol_optics = [sc.truncate_phase(mie.truncation_type, sc.compute_aerosol_optical_properties(mie))]
     return m
 
