@@ -390,6 +390,29 @@ int mom_scene_set_optics(mom_t *h, int Nz, int nAer, int M, const double *tau_ra
                          const double *Zmp, double albedo, int nVza, const int *node_1based, const double *cos_mphi,
                          const double *sin_mphi);
 int mom_scene_get_layers(mom_t *h, int *ndoubl, int *iface, double *tau, double *varpi, double *zw, double *tau_sum);
+/* ---- Band-resolved aerosol optics: mom_scene_set_optics for a spectral axis that concatenates nBand bands ----------
+ * The reference keeps the aerosols per band -- model.aerosol_optics[iBand][iAer], model.τ_aer[iBand][iAer, iz]
+ * (model_from_parameters.jl:92-166), RS_type.ϖ_Cabannes[iB] -- and constructCoreOpticalProperties runs the `+` algebra band by
+ * band before it concatenates the bands with `*` (compEffectiveLayerProperties.jl:24-75, types.jl:632-678).
+ *
+ * mom_scene_set_optics_bands   band b (0-based) owns the points band_start[b] <= n < band_start[b+1] of the spectral axis;
+ *                          band_start [nBand + 1] runs strictly ascending from 0 to nSpec, otherwise MOM_EINVAL with the reason.
+ *                          varpi_rayl [nBand] = ϖ_Cabannes[iB]; tau_aer [nAer, Nz, nBand] = τ_aer[iB][iAer, iz] (iAer fastest);
+ *                          omega_aer, ft_aer [nAer, nBand] = ω̃, fᵗ of aerosol_optics[iB][iAer].  The scene has
+ *                          K = 1 + nAer nBand <= 64 phase-matrix bases: Zpp/Zmp [N, N, K, M] with basis 0 = Rayleigh and basis
+ *                          1 + iAer + nAer b = aerosol type iAer of band b; a point's weights zw outside its own band are exact
+ *                          zeros.  Per band the statements are mom_scene_set_optics' (createAero, the three cases of `+` with the
+ *                          two all(. == 0) tests taken over the band's own points, the gas term); ndoubl, the interface codes and
+ *                          τ_sum are taken over the concatenated axis (rt_kernel.jl:241-242, compEffectiveLayerProperties.jl:
+ *                          104-108).  Results are bitwise those of the host route (mom_scene_set).  nAer <= 7, nBand >= 1.
+ *                          Everything else as mom_scene_set_optics, Float32 handles included.  A handle with a communicator
+ *                          (mom_comm_init): MOM_EUNSUPPORTED -- the per-band all-zero tests would need a reduction over the
+ *                          ranks; a sharded band-resolved run keeps the host route (mom_scene_set with the slices of the host's
+ *                          arrays). */
+int mom_scene_set_optics_bands(mom_t *h, int Nz, int nAer, int nBand, const int *band_start, int M, const double *tau_rayl,
+                               const double *varpi_rayl, const double *tau_aer, const double *omega_aer, const double *ft_aer,
+                               const double *Zpp, const double *Zmp, double albedo, int nVza, const int *node_1based,
+                               const double *cos_mphi, const double *sin_mphi);
 
 /* Surface type of the resident scene (call after mom_scene_set / mom_scene_set_optics, which select
  * LambertianSurfaceScalar(albedo)):
@@ -473,6 +496,16 @@ int mom_scene_set_optics_partials(mom_t *h, int P, const double *w_abs, const do
                                   const double *domega_aer, const double *dft_aer, const double *dZpp, const double *dZmp,
                                   const double *dalbedo, const double *dRsurf, const double *dalbedo_spec);
 int mom_scene_get_partials(mom_t *h, double *dtau, double *dvarpi, double *dzw);
+/* mom_scene_set_optics_partials for a scene that came from mom_scene_set_optics_bands: constructCoreOpticalProperties' loop over
+ * iBand (compEffectiveLayerProperties.jl:24-75) on ForwardDiff.Dual element types.  The aerosol partials carry a band axis:
+ * dtau_aer [nAer, Nz, nBand, P], domega_aer, dft_aer [nAer, nBand, P]; a parameter of one band's aerosol has zeros in the other
+ * bands, and so has its dR_SFI / dT_SFI on their points.  dZpp, dZmp [N, N, K, M, P], K = 1 + nAer nBand.  dzw [K, S, Nz, P]
+ * exists under the conditions of mom_scene_set_optics_partials, exact zeros outside a point's own band.  The MOM_ESTATE rules
+ * are those of mom_scene_set_optics_partials; a scene without bands here, or a band-resolved scene there, is MOM_ESTATE too.
+ * Float64 handles. */
+int mom_scene_set_optics_bands_partials(mom_t *h, int P, const double *w_abs, const double *w_rayl, const double *dtau_aer,
+                                        const double *domega_aer, const double *dft_aer, const double *dZpp, const double *dZmp,
+                                        const double *dalbedo, const double *dRsurf, const double *dalbedo_spec);
 
 /* rt_run_test_ms(RS_type::noRS, sensor_levels, model, iBand) (src/CoreRT/rt_run_multisensor.jl:14-191) for the resident
  * scene: sensors inside the atmosphere.  sensor_levels[ims] = 0 is the TOA/BOA pair (uwJ = R_SFI, dwJ = T_SFI of

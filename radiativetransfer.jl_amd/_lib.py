@@ -114,6 +114,9 @@ SIGNATURES = {
     "mom_absorption_get_gamma_l": (C.c_int, [c_h, C.c_int, c_dp, c_dp]),
     "mom_scene_set_optics": (C.c_int, [c_h, C.c_int, C.c_int, C.c_int, c_dp, C.c_double, c_dp, c_dp, c_dp, c_dp, c_dp,
                                        C.c_double, C.c_int, c_ip, c_dp, c_dp]),
+    "mom_scene_set_optics_bands": (C.c_int, [c_h, C.c_int, C.c_int, C.c_int, c_ip, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp,
+                                             C.c_double, C.c_int, c_ip, c_dp, c_dp]),
+    "mom_scene_set_optics_bands_partials": (C.c_int, [c_h, C.c_int] + [c_dp] * 10),
     "mom_scene_get_layers": (C.c_int, [c_h, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp]),
     "mom_scene_set_surface": (C.c_int, [c_h, C.c_int, C.c_int, c_dp, c_dp]),
     "mom_rt_run": (C.c_int, [c_h]),
@@ -619,6 +622,27 @@ class Handle:
         self.check(self.lib.mom_scene_set_optics(self._h, int(Nz), nAer, int(M), dp(tr), float(varpi_rayl), dp(taf), dp(om),
                                                  dp(ft), dp(zp), dp(zm), float(albedo), len(node), ip(node), dp(cm), dp(sm)))
 
+    def scene_set_optics_bands(self, Nz, M, band_start, tau_rayl, varpi_rayl, tau_aer, omega_aer, ft_aer, Zpp, Zmp, albedo, node,
+                               cos_mphi, sin_mphi):
+        """mom_scene_set_optics_bands: band_start [nBand + 1], tau_rayl [S, Nz], varpi_rayl [nBand], tau_aer [nBand, nAer, Nz],
+        omega_aer / ft_aer [nBand, nAer] numpy (reference layouts); Zpp/Zmp already in ABI order, K = 1 + nAer nBand bases."""
+        bs = i32(np.asarray(band_start).reshape(-1))
+        nBand = bs.size - 1
+        tr = np.ascontiguousarray(np.asarray(tau_rayl, dtype=np.float64).T).reshape(-1)
+        ta = np.asarray(tau_aer, dtype=np.float64)
+        nAer = ta.shape[1] if ta.ndim == 3 and ta.size else 0
+        vr = f64(varpi_rayl).reshape(-1)
+        taf = np.ascontiguousarray(ta.transpose(0, 2, 1)).reshape(-1) if nAer else np.zeros(1)  # [nAer, Nz, nBand], iAer fastest
+        om, ft = (f64(omega_aer).reshape(-1), f64(ft_aer).reshape(-1)) if nAer else (np.zeros(1), np.zeros(1))
+        assert vr.size == max(nBand, 1) and (not nAer or (ta.shape[0] == nBand and om.size == ft.size == nBand * nAer))
+        zp, zm = f64(Zpp).reshape(-1), f64(Zmp).reshape(-1)
+        node = i32(node)
+        cm, sm = f64(cos_mphi).reshape(-1), f64(sin_mphi).reshape(-1)
+        self.nVza = len(node)
+        self._Nz, self._K = int(Nz), 1 + nAer * nBand
+        self.check(self.lib.mom_scene_set_optics_bands(self._h, int(Nz), nAer, nBand, ip(bs), int(M), dp(tr), dp(vr), dp(taf), dp(om),
+                                                       dp(ft), dp(zp), dp(zm), float(albedo), len(node), ip(node), dp(cm), dp(sm)))
+
     def scene_get_layers(self, Nz, K, arrays=True):
         nd, iface = np.zeros(Nz, dtype=np.int32), np.zeros(Nz, dtype=np.int32)
         S = self.S
@@ -652,6 +676,15 @@ class Handle:
         bufs = [None if x is None else f64(x).reshape(-1)
                 for x in (w_abs, w_rayl, dtau_aer, domega_aer, dft_aer, dZpp, dZmp, dalbedo, dRsurf, dalbedo_spec)]
         self.check(self.lib.mom_scene_set_optics_partials(self._h, int(P), *[None if b is None else dp(b) for b in bufs]))
+        self.dual_P = int(P)
+
+    def scene_set_optics_bands_partials(self, P, w_abs=None, w_rayl=None, dtau_aer=None, domega_aer=None, dft_aer=None, dZpp=None,
+                                        dZmp=None, dalbedo=None, dRsurf=None, dalbedo_spec=None):
+        """mom_scene_set_optics_bands_partials: scene_set_optics_partials for a scene_set_optics_bands scene; the aerosol partials carry
+        a band axis (dtau_aer [nAer, Nz, nBand, P], domega_aer, dft_aer [nAer, nBand, P])."""
+        bufs = [None if x is None else f64(x).reshape(-1)
+                for x in (w_abs, w_rayl, dtau_aer, domega_aer, dft_aer, dZpp, dZmp, dalbedo, dRsurf, dalbedo_spec)]
+        self.check(self.lib.mom_scene_set_optics_bands_partials(self._h, int(P), *[None if b is None else dp(b) for b in bufs]))
         self.dual_P = int(P)
 
     def scene_get_partials(self):

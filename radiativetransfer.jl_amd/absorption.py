@@ -494,11 +494,16 @@ def optics_partials_host(model, partials, dtau_abs=None):
     element types.  The all-zero tests of types.jl:641-661 are taken on the values, as ForwardDiff takes them.  `partials`: a
     sequence of corert.OpticsPartial; `dtau_abs` [2, nSpec, Nz]: the partials of model.τ_abs with respect to each layer's pressure
     and temperature (Handle.absorption_get_partials), needed when a w_p or w_T is nonzero.  Returns one corert.ScenePartial per
-    parameter: dτ, dϖ [nSpec, Nz], dzw [K, nSpec, Nz] or None where the device leaves it absent, and the basis / surface fields."""
+    parameter: dτ, dϖ [nSpec, Nz], dzw [K, nSpec, Nz] or None where the device leaves it absent, and the basis / surface fields.
+    A model with bands (the twin of k_optics_bands_dual, mom_scene_set_optics_bands_partials): the same statements band by band
+    with the band's aerosols, ϖ_Cabannes and the band's rows of dτ_aer [nBand, nAer, Nz], dω̃, dfᵗ [nBand, nAer]; K = 1 + nAer nBand,
+    dzw exact zeros outside a point's own band."""
     from .corert import ScenePartial
     S, Nz = model.τ_rayl.shape
-    nAer = len(model.aerosol_optics)
-    K = 1 + nAer
+    bands = model.bands
+    nAer = len(model.aerosol_optics) if bands is None else bands.nAer
+    aer_shape = (nAer,) if bands is None else (bands.nBand, nAer)
+    K = 1 + int(np.prod(aer_shape))
     zeros = np.zeros(Nz)
     row = lambda x: zeros if x is None else np.asarray(x, dtype=np.float64).reshape(Nz)
     div = lambda a, da, b, db: (a / b, da * (1.0 / b) + db * (-(a / (b * b))))
@@ -507,28 +512,31 @@ def optics_partials_host(model, partials, dtau_abs=None):
         w_p, w_T, w_gas, w_rayl = row(q.w_p), row(q.w_T), row(q.w_gas), row(q.w_rayl)
         if dtau_abs is None and (np.any(w_p != 0.0) or np.any(w_T != 0.0)):
             raise ValueError("a nonzero w_p or w_T needs dtau_abs, the partials of τ_abs with respect to (p, T)")
-        dτ_aer = np.zeros((nAer, Nz)) if q.dτ_aer is None else np.asarray(q.dτ_aer, dtype=np.float64)
-        dω̃ = np.zeros(nAer) if q.dω̃ is None else np.asarray(q.dω̃, dtype=np.float64)
-        dfᵗ = np.zeros(nAer) if q.dfᵗ is None else np.asarray(q.dfᵗ, dtype=np.float64)
+        dτ_aer_q = np.zeros(aer_shape + (Nz,)) if q.dτ_aer is None else np.asarray(q.dτ_aer, dtype=np.float64).reshape(aer_shape + (Nz,))
+        dω̃_q = np.zeros(aer_shape) if q.dω̃ is None else np.asarray(q.dω̃, dtype=np.float64).reshape(aer_shape)
+        dfᵗ_q = np.zeros(aer_shape) if q.dfᵗ is None else np.asarray(q.dfᵗ, dtype=np.float64).reshape(aer_shape)
         dτ, dϖ, dzw = np.empty((S, Nz)), np.empty((S, Nz)), np.zeros((K, S, Nz))
-        for z in range(Nz):
-            τz = model.τ_rayl[:, z].copy()
+
+        def one_band(sl, z, ϖ_Cabannes, aerosol_optics, τ_aer, dτ_aer, dω̃, dfᵗ):
+            """one layer of one band (the whole axis without bands) -> dτ, dϖ [S_b], dw [1 + nAer, S_b]"""
+            τz = model.τ_rayl[sl, z].copy()
+            n = τz.size
             dτz = τz * w_rayl[z]
-            ϖz, dϖz = np.full(S, float(model.ϖ_Cabannes)), np.zeros(S)
-            w, dw = np.zeros((K, S)), np.zeros((K, S))
+            ϖz, dϖz = np.full(n, float(ϖ_Cabannes)), np.zeros(n)
+            w, dw = np.zeros((1 + nAer, n)), np.zeros((1 + nAer, n))
             w[0] = 1.0
-            for a, aer in enumerate(model.aerosol_optics, start=1):
+            for a, aer in enumerate(aerosol_optics, start=1):
                 # createAero on Duals
                 fo, dfo = aer.fᵗ * aer.ω̃, dfᵗ[a - 1] * aer.ω̃ + dω̃[a - 1] * aer.fᵗ
                 b, db = 1 - fo, -dfo
-                τy, dτy = b * model.τ_aer[a - 1, z], db * model.τ_aer[a - 1, z] + dτ_aer[a - 1, z] * b
+                τy, dτy = b * τ_aer[a - 1, z], db * τ_aer[a - 1, z] + dτ_aer[a - 1, z] * b
                 c, dc = 1 - aer.fᵗ, -dfᵗ[a - 1]
                 num, dnum = c * aer.ω̃, dc * aer.ω̃ + dω̃[a - 1] * c
                 ϖy, dϖy = div(num, dnum, b, db)
                 wy_s, dwy_s = τy * ϖy, dτy * ϖy + dϖy * τy
                 # the `+` of types.jl:632-661
                 wx, dwx = τz * ϖz, dτz * ϖz + dϖz * τz
-                wy, dwy = np.full(S, wy_s), np.full(S, dwy_s)
+                wy, dwy = np.full(n, wy_s), np.full(n, dwy_s)
                 tot, dtot = wx + wy, dwx + dwy
                 τn, dτn = τz + τy, dτz + dτy
                 if np.all(wx == 0.0):
@@ -543,14 +551,25 @@ def optics_partials_host(model, partials, dtau_abs=None):
                 ϖz, dϖz = div(tot, dtot, τn, dτn)
                 τz, dτz = τn, dτn
             # the gas term (types.jl:672-678)
-            τa = model.τ_abs[:, z]
+            τa = model.τ_abs[sl, z]
             dτa = τa * w_gas[z]
             if dtau_abs is not None:
-                dτa = dtau_abs[0][:, z] * w_p[z] + dtau_abs[1][:, z] * w_T[z] + dτa
+                dτa = dtau_abs[0][sl, z] * w_p[z] + dtau_abs[1][sl, z] * w_T[z] + dτa
             τn, dτn = τz + τa, dτz + dτa
             num, dnum = τz * ϖz, dτz * ϖz + dϖz * τz
             _, dϖz = div(num, dnum, τn, dτn)
-            dτ[:, z], dϖ[:, z], dzw[:, :, z] = dτn, dϖz, dw
+            return dτn, dϖz, dw
+
+        for z in range(Nz):
+            if bands is None:
+                dτ[:, z], dϖ[:, z], dzw[:, :, z] = one_band(slice(None), z, model.ϖ_Cabannes, model.aerosol_optics, model.τ_aer,
+                                                            dτ_aer_q, dω̃_q, dfᵗ_q)
+                continue
+            for b, sl in enumerate(bands.slices()):
+                dτ[sl, z], dϖ[sl, z], dw = one_band(sl, z, bands.ϖ_Cabannes[b], bands.aerosol_optics[b], bands.τ_aer[b],
+                                                    dτ_aer_q[b], dω̃_q[b], dfᵗ_q[b])
+                dzw[0, sl, z] = dw[0]
+                dzw[1 + nAer * b:1 + nAer * (b + 1), sl, z] = dw[1:]
         has_zw = nAer > 0 and any(x is not None for x in (q.w_rayl, q.dτ_aer, q.dω̃, q.dfᵗ))
         out.append(ScenePartial(dτ=dτ, dϖ=dϖ, dzw=dzw if has_zw else None, dZpp=q.dZpp, dZmp=q.dZmp, dalbedo=q.dalbedo,
                                 dRsurf=q.dRsurf, dalbedo_spec=q.dalbedo_spec))

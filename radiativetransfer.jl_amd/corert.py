@@ -504,8 +504,36 @@ class vSmartMOM_Parameters:
 
 
 @dataclass
+class Bands:
+    """The per-band fields of the reference's model on ONE concatenated spectral axis: model.τ_aer[iBand][iAer, iz],
+    model.aerosol_optics[iBand][iAer] (model_from_parameters.jl:92-166) and RS_type.ϖ_Cabannes[iB].  Band b (0-based) owns the
+    points band_start[b] <= n < band_start[b + 1].  Every band has the same number of aerosol types."""
+    band_start: np.ndarray                       # [nBand + 1] 0-based offsets, band_start[0] = 0, band_start[-1] = nSpec, strictly ascending
+    τ_aer: np.ndarray                            # [nBand, nAer, Nz]
+    aerosol_optics: List[List[AerosolOptics]]    # [nBand][nAer]
+    ϖ_Cabannes: np.ndarray                       # [nBand]
+
+    @property
+    def nBand(self) -> int:
+        return len(self.band_start) - 1
+
+    @property
+    def nAer(self) -> int:
+        return len(self.aerosol_optics[0]) if len(self.aerosol_optics) else 0
+
+    def slices(self):
+        return [slice(int(self.band_start[b]), int(self.band_start[b + 1])) for b in range(self.nBand)]
+
+    def band_of(self) -> np.ndarray:
+        """[nSpec] the band of every spectral point"""
+        return np.repeat(np.arange(self.nBand), np.diff(self.band_start))
+
+
+@dataclass
 class vSmartMOM_Model:
-    """types.jl:476-520, restricted to one concatenated band: τ arrays are [nSpec, Nz]."""
+    """types.jl:476-520 on one concatenated spectral axis: τ arrays are [nSpec, Nz].  Without `bands` the axis is one band: one
+    ϖ_Cabannes, τ_aer [nAer, Nz] and aerosol_optics [nAer] for every point.  With `bands` the aerosols and ϖ_Cabannes are those of
+    `bands`, per band as the reference keeps them, and the model's own τ_aer / aerosol_optics / ϖ_Cabannes are not read."""
     params: vSmartMOM_Parameters
     quad_points: QuadPoints
     greek_rayleigh: GreekCoefs
@@ -514,23 +542,58 @@ class vSmartMOM_Model:
     τ_aer: np.ndarray  # [nAer, Nz]
     aerosol_optics: List[AerosolOptics]
     ϖ_Cabannes: float = 1.0
+    bands: Optional[Bands] = None
+
+
+def _checked_bands(bands: Bands, S: int, Nz: int) -> Bands:
+    bs = np.asarray(bands.band_start)
+    if bs.ndim != 1 or bs.size < 2 or not np.issubdtype(bs.dtype, np.integer):
+        raise ValueError("bands.band_start must be [nBand + 1] integers with nBand >= 1")
+    if bs[0] != 0 or bs[-1] != S or np.any(np.diff(bs) <= 0):
+        raise ValueError(f"bands.band_start must run strictly ascending from 0 to nSpec = {S}, got {bs.tolist()}")
+    nBand = bs.size - 1
+    optics = [list(x) for x in bands.aerosol_optics]
+    if len(optics) != nBand or any(len(x) != len(optics[0]) for x in optics):
+        raise ValueError("bands.aerosol_optics must be [nBand][nAer], the same nAer in every band")
+    nAer = len(optics[0])
+    τ_aer = np.zeros((nBand, 0, Nz)) if bands.τ_aer is None else np.asarray(bands.τ_aer, dtype=np.float64)
+    if τ_aer.shape != (nBand, nAer, Nz):
+        raise ValueError(f"bands.τ_aer must be [nBand, nAer, Nz] = {(nBand, nAer, Nz)}, got {τ_aer.shape}")
+    ϖ = np.asarray(bands.ϖ_Cabannes, dtype=np.float64)
+    if ϖ.shape != (nBand,):
+        raise ValueError("bands.ϖ_Cabannes must be [nBand]")
+    if nAer > 7 or 1 + nAer * nBand > 64:
+        raise ValueError(f"nAer = {nAer} (at most 7) and 1 + nAer nBand = {1 + nAer * nBand} phase-matrix bases (at most 64)")
+    return Bands(bs.astype(np.int32), τ_aer, optics, ϖ)
 
 
 def model_from_parameters(params: vSmartMOM_Parameters, τ_rayl, τ_abs, τ_aer=None,
-                          aerosol_optics: Optional[List[AerosolOptics]] = None) -> vSmartMOM_Model:
+                          aerosol_optics: Optional[List[AerosolOptics]] = None, bands: Optional[Bands] = None) -> vSmartMOM_Model:
     """model_from_parameters(params) (model_from_parameters.jl:12-194) for callers that bring
     their own optical-depth tables (absorption.py and scattering.py compute the gas and the aerosol
-    inputs on the device; the reference's profile handling stays host-side and is outside this package's scope)."""
+    inputs on the device; the reference's profile handling stays host-side and is outside this package's scope).
+    bands: the aerosols and ϖ_Cabannes per band (Bands); τ_aer and aerosol_optics are then left out."""
     qp = rt_set_streams(params.quadrature_type, params.l_trunc, params.sza, params.vza, params.polarization_type)
     τ_rayl = np.asarray(τ_rayl, dtype=np.float64)
     τ_abs = np.asarray(τ_abs, dtype=np.float64)
     if τ_rayl.shape != τ_abs.shape or τ_rayl.ndim != 2:
         raise ValueError("τ_rayl and τ_abs must both be [nSpec, Nz]")
+    if bands is not None and (τ_aer is not None or aerosol_optics):
+        raise ValueError("a model with bands takes its aerosols from bands.τ_aer / bands.aerosol_optics only")
     aerosol_optics = list(aerosol_optics or [])
     τ_aer = np.zeros((0, τ_rayl.shape[1])) if τ_aer is None else np.asarray(τ_aer, dtype=np.float64)
     if τ_aer.shape != (len(aerosol_optics), τ_rayl.shape[1]):
         raise ValueError("τ_aer must be [nAer, Nz]")
-    return vSmartMOM_Model(params, qp, get_greek_rayleigh(params.depol), τ_rayl, τ_abs, τ_aer, aerosol_optics)
+    if bands is not None:
+        bands = _checked_bands(bands, *τ_rayl.shape)
+    return vSmartMOM_Model(params, qp, get_greek_rayleigh(params.depol), τ_rayl, τ_abs, τ_aer, aerosol_optics, bands=bands)
+
+
+def with_bands(model: vSmartMOM_Model, bands: Bands) -> vSmartMOM_Model:
+    """`model` with its aerosols replaced by the per-band ones of `bands` (validated as in model_from_parameters)."""
+    import dataclasses
+    S, Nz = model.τ_rayl.shape
+    return dataclasses.replace(model, τ_aer=np.zeros((0, Nz)), aerosol_optics=[], bands=_checked_bands(bands, S, Nz))
 
 
 # ------------------------------------------------------------------------------------------
@@ -573,21 +636,29 @@ class LayerInputs:
 def construct_layer_inputs(model: vSmartMOM_Model) -> LayerInputs:
     """constructCoreOpticalProperties (compEffectiveLayerProperties.jl:1-78) with the `+` of
     types.jl:632-678, createAero (:80-85), extractEffectiveProps (:88-111) and
-    get_scattering_interface (rt_helper_functions.jl:8-27).  None of it depends on m."""
+    get_scattering_interface (rt_helper_functions.jl:8-27).  None of it depends on m.
+    With model.bands the `+` algebra runs band by band with the band's own aerosols and ϖ_Cabannes, as the reference's loop over
+    iBand does; ndoubl, the interface codes and τ_sum are taken over the concatenated axis (rt_kernel.jl:241-242,
+    compEffectiveLayerProperties.jl:104-108).  This is the host twin of mom_scene_set_optics_bands, bitwise."""
     S, Nz = model.τ_rayl.shape
-    K = 1 + len(model.aerosol_optics)
+    bands = model.bands
+    K = 1 + (len(model.aerosol_optics) if bands is None else bands.nAer * bands.nBand)
     τ = np.empty((S, Nz))
     ϖ = np.empty((S, Nz))
     zw = np.zeros((K, S, Nz))
-    for z in range(Nz):
-        τz = model.τ_rayl[:, z].copy()
-        ϖz = np.full(S, float(model.ϖ_Cabannes))
-        w = np.zeros((K, S))
+
+    def one_band(sl, z, ϖ_Cabannes, aerosol_optics, τ_aer):
+        """one layer of one band (the whole axis without bands): Rayleigh `+` each aerosol type `+` the gas term, the two all(. == 0)
+        tests over the band's own points -> τ, ϖ [S_b] and the weights [1 + nAer, S_b] of the band's own bases"""
+        τz = model.τ_rayl[sl, z].copy()
+        n = τz.size
+        ϖz = np.full(n, float(ϖ_Cabannes))
+        w = np.zeros((1 + len(aerosol_optics), n))
         w[0] = 1.0
-        for a, aer in enumerate(model.aerosol_optics, start=1):
-            τy = (1 - aer.fᵗ * aer.ω̃) * model.τ_aer[a - 1, z]
+        for a, aer in enumerate(aerosol_optics, start=1):
+            τy = (1 - aer.fᵗ * aer.ω̃) * τ_aer[a - 1, z]
             ϖy = (1 - aer.fᵗ) * aer.ω̃ / (1 - aer.fᵗ * aer.ω̃)
-            wx, wy = τz * ϖz, np.full(S, τy * ϖy)
+            wx, wy = τz * ϖz, np.full(n, τy * ϖy)
             tot = wx + wy
             τn = τz + τy
             ϖn = tot / τn
@@ -598,9 +669,20 @@ def construct_layer_inputs(model: vSmartMOM_Model) -> LayerInputs:
                 w *= (wx / tot)[None, :]
                 w[a] = wy / tot
             τz, ϖz = τn, ϖn
-        τn = τz + model.τ_abs[:, z]
+        τn = τz + model.τ_abs[sl, z]
         ϖz = (τz * ϖz) / τn
-        τ[:, z], ϖ[:, z], zw[:, :, z] = τn, ϖz, w
+        return τn, ϖz, w
+
+    for z in range(Nz):
+        if bands is None:
+            τ[:, z], ϖ[:, z], zw[:, :, z] = one_band(slice(None), z, model.ϖ_Cabannes, model.aerosol_optics, model.τ_aer)
+            continue
+        # the reference's loop over iBand and the concatenation `*` (compEffectiveLayerProperties.jl:24-75, types.jl:664-669):
+        # basis 0 is Rayleigh, basis 1 + x + nAer b is aerosol type x of band b; the other bands' bases keep weight 0.0
+        for b, sl in enumerate(bands.slices()):
+            τ[sl, z], ϖ[sl, z], w = one_band(sl, z, bands.ϖ_Cabannes[b], bands.aerosol_optics[b], bands.τ_aer[b])
+            zw[0, sl, z] = w[0]
+            zw[1 + bands.nAer * b:1 + bands.nAer * (b + 1), sl, z] = w[1:]
     iface = np.zeros(Nz, dtype=np.int32)
     nd = np.zeros(Nz, dtype=np.int32)
     τ_sum = np.zeros((S, Nz + 1))
@@ -620,8 +702,13 @@ def construct_layer_inputs(model: vSmartMOM_Model) -> LayerInputs:
 
 
 def z_bases(model: vSmartMOM_Model):
-    """Z⁺⁺/Z⁻⁺ bases [M, K, N, N] (k = 0 Rayleigh, then aerosols) for m = 0..max_m-1."""
+    """Z⁺⁺/Z⁻⁺ bases [M, K, N, N] (k = 0 Rayleigh, then aerosols) for m = 0..max_m-1.  With model.bands: K = 1 + nAer nBand,
+    basis 1 + x + nAer b = aerosol type x of band b, each (m, Greek set) computed once."""
     pol, μ = model.params.polarization_type, model.quad_points.qp_μ
+    if model.bands is not None:
+        greeks = [model.greek_rayleigh] + [a.greek_coefs for band in model.bands.aerosol_optics for a in band]
+        Z = [[compute_Z_moments(pol, μ, g, m) for g in greeks] for m in range(model.params.max_m)]
+        return np.array([[z[0] for z in row] for row in Z]), np.array([[z[1] for z in row] for row in Z])
     greeks = [model.greek_rayleigh] + [a.greek_coefs for a in model.aerosol_optics]
     Zpp = np.array([[compute_Z_moments(pol, μ, g, m)[0] for g in greeks] for m in range(model.params.max_m)])
     Zmp = np.array([[compute_Z_moments(pol, μ, g, m)[1] for g in greeks] for m in range(model.params.max_m)])
@@ -646,7 +733,9 @@ def view_nodes(model: vSmartMOM_Model) -> np.ndarray:
 
 @dataclass
 class SceneInputs:
-    """Everything mom_scene_set consumes, already in ABI memory order."""
+    """Everything mom_scene_set consumes, already in ABI memory order.  A band-resolved model (model.bands) needs nothing else on
+    this route: its K = 1 + nAer nBand bases and their per-point weights are ordinary mom_scene_set inputs, spectral_slice and
+    sharding included (a shard may start or end inside a band)."""
     N: int
     nStokes: int
     S: int
@@ -685,7 +774,7 @@ class SceneInputs:
 
 
 def prepare_scene(model: vSmartMOM_Model) -> SceneInputs:
-    """Host preparation of rt_run.jl:43-138 for every Fourier moment at once."""
+    """Host preparation of rt_run.jl:43-138 for every Fourier moment at once (models with and without bands)."""
     p, qp = model.params, model.quad_points
     L = construct_layer_inputs(model)
     Zpp, Zmp = z_bases(model)
@@ -765,7 +854,8 @@ def scene_set_partials(h: _lib.Handle, sc: SceneInputs, partials: Sequence[Scene
 def rt_run_dual(model: vSmartMOM_Model, partials: Sequence[ScenePartial], workspace_mb: int = 0, full: bool = False):
     """rt_run on ForwardDiff.Dual inputs (rt_run.jl:41-230 with FT_dual element types): returns
     (R_SFI, T_SFI [nVza, nStokes, nSpec], dR_SFI, dT_SFI [P, nVza, nStokes, nSpec]); full = True: the rest of the reference's
-    tuple as well -- ((R, T, hdr, bhr_uw, bhr_dw), (dR, dT, dhdr, dbhr_uw, dbhr_dw)), bhr_* [nStokes, nSpec]."""
+    tuple as well -- ((R, T, hdr, bhr_uw, bhr_dw), (dR, dT, dhdr, dbhr_uw, dbhr_dw)), bhr_* [nStokes, nSpec].  A model with bands:
+    the ScenePartials carry K = 1 + nAer nBand bases (absorption.optics_partials_host forms them from OpticsPartials)."""
     sc = prepare_scene(model)
     with make_handle(model) as h:
         if workspace_mb:
@@ -785,8 +875,8 @@ def rt_run_dual(model: vSmartMOM_Model, partials: Sequence[ScenePartial], worksp
 
 
 def scene_set_device_optics(h: _lib.Handle, model: vSmartMOM_Model, upload_tau_abs: bool) -> int:
-    """mom_scene_set_optics (+ mom_scene_set_surface) from the model's ingredients: what run_scene_device_optics and its Dual twin
-    share.  Returns the surface kind."""
+    """mom_scene_set_optics -- mom_scene_set_optics_bands for a model with bands -- (+ mom_scene_set_surface) from the model's
+    ingredients: what run_scene_device_optics and its Dual twin share.  Returns the surface kind."""
     p, qp = model.params, model.quad_points
     Zpp, Zmp = z_bases(model)
     M = p.max_m
@@ -798,9 +888,15 @@ def scene_set_device_optics(h: _lib.Handle, model: vSmartMOM_Model, upload_tau_a
     brdf = p.brdf if p.brdf is not None else LambertianSurfaceScalar(float(p.brdf_albedo))
     kind, Rs, alb = surface_inputs(brdf, p.polarization_type, qp.qp_μ, M, S)
     albedo = float(brdf.albedo) if isinstance(brdf, LambertianSurfaceScalar) else 0.0
-    h.scene_set_optics(Nz, M, model.τ_rayl, model.ϖ_Cabannes, model.τ_aer, [a.ω̃ for a in model.aerosol_optics],
-                       [a.fᵗ for a in model.aerosol_optics], _abi_mats(Zpp), _abi_mats(Zmp), albedo,
-                       view_nodes(model), cm.reshape(-1), sm.reshape(-1))
+    if model.bands is not None:
+        bd = model.bands
+        h.scene_set_optics_bands(Nz, M, bd.band_start, model.τ_rayl, bd.ϖ_Cabannes, bd.τ_aer,
+                                 [[a.ω̃ for a in band] for band in bd.aerosol_optics], [[a.fᵗ for a in band] for band in bd.aerosol_optics],
+                                 _abi_mats(Zpp), _abi_mats(Zmp), albedo, view_nodes(model), cm.reshape(-1), sm.reshape(-1))
+    else:
+        h.scene_set_optics(Nz, M, model.τ_rayl, model.ϖ_Cabannes, model.τ_aer, [a.ω̃ for a in model.aerosol_optics],
+                           [a.fᵗ for a in model.aerosol_optics], _abi_mats(Zpp), _abi_mats(Zmp), albedo,
+                           view_nodes(model), cm.reshape(-1), sm.reshape(-1))
     if kind != 0:
         h.scene_set_surface(kind, M, None if Rs is None else _abi_mats(Rs), alb)
     return kind
@@ -809,7 +905,8 @@ def scene_set_device_optics(h: _lib.Handle, model: vSmartMOM_Model, upload_tau_a
 def run_scene_device_optics(h: _lib.Handle, model: vSmartMOM_Model, upload_tau_abs: bool = True):
     """The same run with the layer optics assembled on the GPU (mom_scene_set_optics): the host hands over the
     INGREDIENTS (τ_rayl, aerosol columns, Z bases) and the gas absorption is the handle's resident τ_abs table --
-    uploaded here from model.τ_abs, or (upload_tau_abs=False) already accumulated by mom_voigt_tau_abs."""
+    uploaded here from model.τ_abs, or (upload_tau_abs=False) already accumulated by mom_voigt_tau_abs.  A model with bands goes
+    through mom_scene_set_optics_bands."""
     scene_set_device_optics(h, model, upload_tau_abs)
     h.rt_run()
     return h.get_RT()
@@ -825,10 +922,10 @@ class OpticsPartial:
     w_T: Optional[np.ndarray] = None            # [Nz] ∂T_z/∂x: weight onto ∂τ_abs/∂T
     w_gas: Optional[np.ndarray] = None          # [Nz] ∂ln(vcd vmr)_z/∂x: relative change of the layer's gas column, onto τ_abs
     w_rayl: Optional[np.ndarray] = None         # [Nz] relative change of the layer's Rayleigh depth, onto τ_rayl
-    dτ_aer: Optional[np.ndarray] = None         # [nAer, Nz]
-    dω̃: Optional[np.ndarray] = None             # [nAer]
-    dfᵗ: Optional[np.ndarray] = None            # [nAer]
-    dZpp: Optional[np.ndarray] = None           # the basis / surface fields of ScenePartial
+    dτ_aer: Optional[np.ndarray] = None         # [nAer, Nz]; a model with bands: [nBand, nAer, Nz]
+    dω̃: Optional[np.ndarray] = None             # [nAer]; with bands: [nBand, nAer]
+    dfᵗ: Optional[np.ndarray] = None            # [nAer]; with bands: [nBand, nAer]
+    dZpp: Optional[np.ndarray] = None           # the basis / surface fields of ScenePartial ([M, K, N, N], with bands K = 1 + nAer nBand)
     dZmp: Optional[np.ndarray] = None
     dalbedo: float = 0.0
     dRsurf: Optional[np.ndarray] = None
@@ -848,10 +945,16 @@ def _pack_partials(partials, get, conv, shape=None):
 
 def scene_set_optics_partials(h: _lib.Handle, model: vSmartMOM_Model, partials: Sequence[OpticsPartial], surf_kind: Optional[int] = None):
     """Pack OpticsPartials into the ABI layout of mom_scene_set_optics_partials and call it: the device forms dτ, dϖ, dzw of the
-    resident scene_set_optics scene.  surf_kind: the scene's surface kind (default: from model.params.brdf)."""
+    resident scene_set_optics scene.  surf_kind: the scene's surface kind (default: from model.params.brdf).  A model with bands
+    goes to mom_scene_set_optics_bands_partials, its aerosol partials with the leading band axis."""
     P = len(partials)
     S, Nz = model.τ_rayl.shape
     nAer = len(model.aerosol_optics)
+    bd = model.bands
+    aer_shape, aer_conv, setter = (nAer,), (lambda a: np.ascontiguousarray(a.T).reshape(-1)), h.scene_set_optics_partials
+    if bd is not None:   # ABI: dtau_aer [nAer, Nz, nBand, P], domega_aer / dft_aer [nAer, nBand, P], the first index fastest
+        nAer, aer_shape, setter = bd.nAer, (bd.nBand, bd.nAer), h.scene_set_optics_bands_partials
+        aer_conv = lambda a: np.ascontiguousarray(a.transpose(0, 2, 1)).reshape(-1)
     if surf_kind is None:
         brdf = model.params.brdf
         surf_kind = 0 if brdf is None or isinstance(brdf, LambertianSurfaceScalar) else (2 if isinstance(brdf, LambertianSurfaceLegendre) else 1)
@@ -863,10 +966,10 @@ def scene_set_optics_partials(h: _lib.Handle, model: vSmartMOM_Model, partials: 
             for c, x in enumerate((p.w_p, p.w_T, p.w_gas)):
                 if x is not None:
                     w_abs[k, c] = np.asarray(x, dtype=np.float64).reshape(Nz)
-    h.scene_set_optics_partials(
+    setter(
         P, w_abs=w_abs, w_rayl=_pack_partials(partials, lambda p: p.w_rayl, flat, (Nz,)),
-        dtau_aer=_pack_partials(partials, lambda p: p.dτ_aer, lambda a: np.ascontiguousarray(a.T).reshape(-1), (nAer, Nz)),
-        domega_aer=_pack_partials(partials, lambda p: p.dω̃, flat, (nAer,)), dft_aer=_pack_partials(partials, lambda p: p.dfᵗ, flat, (nAer,)),
+        dtau_aer=_pack_partials(partials, lambda p: p.dτ_aer, aer_conv, aer_shape + (Nz,)),
+        domega_aer=_pack_partials(partials, lambda p: p.dω̃, flat, aer_shape), dft_aer=_pack_partials(partials, lambda p: p.dfᵗ, flat, aer_shape),
         dZpp=_pack_partials(partials, lambda p: p.dZpp, _abi_mats), dZmp=_pack_partials(partials, lambda p: p.dZmp, _abi_mats),
         dalbedo=np.array([float(p.dalbedo) for p in partials]) if surf_kind == 0 and P else None,
         dRsurf=_pack_partials(partials, lambda p: p.dRsurf, _abi_mats) if surf_kind == 1 else None,
@@ -878,7 +981,8 @@ def rt_run_dual_device_optics(h: _lib.Handle, model: vSmartMOM_Model, partials: 
     """The Dual twin of run_scene_device_optics: layer optics AND their partials assembled on the GPU (mom_scene_set_optics,
     mom_scene_set_optics_partials), then mom_rt_run_dual.  With upload_tau_abs=False the resident τ_abs / dτ_abs tables of a Dual
     absorption call (compute_absorption_profile(dual=True)) are used as they stand: lines -> Dual line shape -> Dual layer optics
-    -> Dual rt_run without a host hop.  Returns what rt_run_dual returns."""
+    -> Dual rt_run without a host hop.  Returns what rt_run_dual returns.  A model with bands goes through
+    mom_scene_set_optics_bands / mom_scene_set_optics_bands_partials, its OpticsPartials with the leading band axis."""
     kind = scene_set_device_optics(h, model, upload_tau_abs)
     scene_set_optics_partials(h, model, partials, surf_kind=kind)
     h.rt_run_dual()
@@ -897,7 +1001,8 @@ def rt_run(model: vSmartMOM_Model, i_band: int = 1):
     """rt_run(model; i_band) (rt_run.jl:19-21 -> :41-230), SFI = true, noRS.  Returns the
     reference's 7-tuple (rt_run.jl:226):
         (R_SFI, T_SFI, ieR_SFI, ieT_SFI, hdr, bhr_uw[1,:], bhr_dw[1,:])
-    R/T/hdr are [nVza, nStokes, nSpec]; the inelastic terms are zero for noRS."""
+    R/T/hdr are [nVza, nStokes, nSpec]; the inelastic terms are zero for noRS.  A model with bands (model.bands) runs all its
+    bands on the concatenated axis, each with its own aerosols."""
     sc = prepare_scene(model)
     with make_handle(model) as h:
         R, T = run_scene(h, sc)
@@ -916,7 +1021,7 @@ def rt_run_test_ms(sensor_levels, model: vSmartMOM_Model, i_band: int = 1):
     """rt_run_test_ms(RS_type::noRS, sensor_levels, model, iBand) (rt_run_multisensor.jl:14-191): sensors inside the
     atmosphere, labelled from the top (0 = the TOA/BOA pair, L = below layer L), all sharing the view angles.
     Returns the reference's 4-tuple (uwJ, dwJ, uwieJ, dwieJ): lists over the sensors of [nVza, nStokes, nSpec] arrays;
-    the inelastic terms are zero for noRS."""
+    the inelastic terms are zero for noRS.  Models with and without bands."""
     sc = prepare_scene(model)
     with make_handle(model) as h:
         scene_set(h, sc)

@@ -67,8 +67,11 @@ struct mom_handle : MomSceneBufs<double> {
   bool optics_scene = false;     // the resident scene came from mom_scene_set_optics (mom_scene_set clears it) ...
   bool optics_tables = false;    // ... and d_tau_abs / d_dtau_abs are still the tables it read (mom_absorption_begin / _set clear it)
   int optics_nAer = 0;
-  double optics_varpi_rayl = 0.0;
-  std::vector<double> h_tau_aer, h_omega_aer, h_ft_aer;  // host copies of its aerosol arguments [nAer, Nz], [nAer], [nAer]
+  int optics_nBand = 0;          // 0: the scene came from mom_scene_set_optics; >= 1: from mom_scene_set_optics_bands, this many bands
+  std::vector<double> h_varpi_rayl;                      // host copy of ϖ_Cabannes, one per band (one entry without bands)
+  std::vector<double> h_tau_aer, h_omega_aer, h_ft_aer;  // host copies of its aerosol arguments [nAer, Nz(, nBand)], [nAer(, nBand)] twice
+  MomDevBuf<int> d_band_start;     // [nBand + 1] offsets of the bands on the spectral axis (k_optics_bands, k_optics_bands_dual)
+  MomDevBuf<double> d_varpi_band;  // [nBand] ϖ_Cabannes per band
   MomDevBuf<double> d_optics_prm;  // per-(layer, partial) scalars of k_optics_dual (OpticsDualArgs::w_abs | w_rayl | daer); grow-only
   MomDevBuf<double> d_vec[4];  // S-length temporaries (tau_sum, dtau, varpi, expk)
   MomDevBuf<double> d_Zop[2];

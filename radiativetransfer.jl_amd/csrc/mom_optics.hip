@@ -1,6 +1,7 @@
 // mom_optics.hip -- the device-side layer optics of the C ABI (include/momcore.h): the resident absorption table
-// and the Voigt entry points (kernels: voigt.hip), k_optics and mom_scene_set_optics, mom_scene_get_layers, and the Dual run of the
-// layer optics: k_optics_dual and mom_scene_set_optics_partials, mom_scene_get_partials.
+// and the Voigt entry points (kernels: voigt.hip), k_optics and mom_scene_set_optics, mom_scene_get_layers, the Dual run of the
+// layer optics: k_optics_dual and mom_scene_set_optics_partials, mom_scene_get_partials, and both for band-resolved scenes:
+// k_optics_bands / mom_scene_set_optics_bands, k_optics_bands_dual / mom_scene_set_optics_bands_partials.
 #include <cstring>
 
 #include "mom_handle.hpp"
@@ -428,8 +429,57 @@ struct OpticsArgs {
   const double *aer;                 // [2,nAer,Nz]: τ_y, w_y = τ_y ϖ_y per aerosol type and layer (spectrally flat)
   const int *aer_mode;               // [nAer,Nz]: 0 = Rayleigh side all zero, 1 = mix, 2 = aerosol side all zero
   double *tau, *varpi, *zw, *tau_sum, *layer_max;
+  // k_optics_bands only: `aer` and `aer_mode` are then one such block per band, [2,nAer,Nz,nBand] and [nAer,Nz,nBand]
+  int nBand;
+  const int *band_start;     // [nBand + 1]
+  const double *varpi_band;  // [nBand] ϖ_Cabannes per band, in place of varpi_rayl
 };
 #pragma clang fp contract(off)
+// One spectral point of one layer: Rayleigh `+` each aerosol type `+` the gas term; `aer` / `mode` are the [2,nAer,Nz] / [nAer,Nz]
+// block of the point's band.  Leaves τ, ϖ and the 1 + nAer weights w of the point's own bases.
+__device__ __forceinline__ void optics_point(const OpticsArgs &a, size_t o, int z, double varpi_rayl, const double *aer, const int *mode,
+                                             double (&w)[8], double &tau, double &varpi) {
+  const int K = 1 + a.nAer;
+  tau = a.tau_rayl[o];
+  varpi = varpi_rayl;
+  w[0] = 1.0;
+  for (int k = 1; k < K; ++k) w[k] = 0.0;
+  for (int x = 0; x < a.nAer; ++x) {
+    const double ty = aer[x + (size_t)a.nAer * z], wy = aer[a.nAer * a.Nz + x + (size_t)a.nAer * z];
+    const int md = mode[x + (size_t)a.nAer * z];
+    const double wx = tau * varpi, tot = wx + wy, tn = tau + ty;
+    if (md == 0) {
+      for (int k = 0; k < K; ++k) w[k] = 0.0;
+      w[x + 1] = 1.0;
+    } else if (md == 1) {
+      const double fx = wx / tot;
+      for (int k = 0; k < K; ++k) w[k] *= fx;
+      w[x + 1] = wy / tot;
+    }
+    varpi = tot / tn;
+    tau = tn;
+  }
+  const double tn = tau + a.tau_abs[o];
+  varpi = (tau * varpi) / tn;
+  tau = tn;
+}
+// max(τ ϖ) of a layer over the wavefront, then over the grid by atomic max on the bit pattern
+__device__ __forceinline__ void optics_layer_max(double tw, double *layer_max) {
+  // NaN (0/0 in an empty layer) must not win silently: fmax drops it like Julia's maximum would propagate it --
+  // the host path would fail on such a scene as well; keep it visible as +inf
+  if (tw != tw) tw = __longlong_as_double(0x7ff0000000000000ll);
+  double m = tw;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off));
+  if ((threadIdx.x & 63) == 0 && m > 0.0)
+    atomicMax(reinterpret_cast<unsigned long long *>(layer_max), (unsigned long long)__double_as_longlong(m));
+}
+// the band of spectral point n < S: band_start is strictly ascending from 0 to S
+__device__ __forceinline__ int optics_band(int n, int nBand, const int *band_start) {
+  int b = 0;
+  while (b + 1 < nBand && n >= band_start[b + 1]) ++b;
+  return b;
+}
 __global__ void k_optics(OpticsArgs a) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   const int K = 1 + a.nAer;
@@ -440,28 +490,8 @@ __global__ void k_optics(OpticsArgs a) {
     double tw = 0.0;
     if (live) {
       const size_t o = n + (size_t)a.S * z;
-      double tau = a.tau_rayl[o], varpi = a.varpi_rayl;
-      double w[8];
-      w[0] = 1.0;
-      for (int k = 1; k < K; ++k) w[k] = 0.0;
-      for (int x = 0; x < a.nAer; ++x) {
-        const double ty = a.aer[x + (size_t)a.nAer * z], wy = a.aer[a.nAer * a.Nz + x + (size_t)a.nAer * z];
-        const int mode = a.aer_mode[x + (size_t)a.nAer * z];
-        const double wx = tau * varpi, tot = wx + wy, tn = tau + ty;
-        if (mode == 0) {
-          for (int k = 0; k < K; ++k) w[k] = 0.0;
-          w[x + 1] = 1.0;
-        } else if (mode == 1) {
-          const double fx = wx / tot;
-          for (int k = 0; k < K; ++k) w[k] *= fx;
-          w[x + 1] = wy / tot;
-        }
-        varpi = tot / tn;
-        tau = tn;
-      }
-      const double tn = tau + a.tau_abs[o];
-      varpi = (tau * varpi) / tn;
-      tau = tn;
+      double tau, varpi, w[8];
+      optics_point(a, o, z, a.varpi_rayl, a.aer, a.aer_mode, w, tau, varpi);
       a.tau[o] = tau;
       a.varpi[o] = varpi;
       for (int k = 0; k < K; ++k) a.zw[k + (size_t)K * o] = w[k];
@@ -469,14 +499,43 @@ __global__ void k_optics(OpticsArgs a) {
       a.tau_sum[o + a.S] = tsum;
       tw = tau * varpi;
     }
-    // NaN (0/0 in an empty layer) must not win silently: fmax drops it like Julia's maximum would propagate it --
-    // the host path would fail on such a scene as well; keep it visible as +inf
-    if (tw != tw) tw = __longlong_as_double(0x7ff0000000000000ll);
-    double m = tw;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off));
-    if ((threadIdx.x & 63) == 0 && m > 0.0)
-      atomicMax(reinterpret_cast<unsigned long long *>(a.layer_max + z), (unsigned long long)__double_as_longlong(m));
+    optics_layer_max(tw, a.layer_max + z);
+  }
+}
+
+// k_optics for a band-resolved scene (constructCoreOpticalProperties' loop over iBand, compEffectiveLayerProperties.jl:24-75, and
+// the concatenation `*` of types.jl:664-669): K = 1 + nAer nBand bases, basis 1 + x + nAer b = aerosol type x of band b.  A thread
+// finds its band once and runs that band's statements -- its ϖ_Cabannes, its createAero columns, its three-way modes -- which are
+// k_optics' own, so the results are bitwise the host twin's.  Of a point's K weights only the 1 + nAer of its own band can be
+// nonzero: the host zeroes zw on the stream before the launch and a thread stores those alone.  The per-layer maxima run over all
+// bands (rt_kernel.jl:241-242 takes them over the concatenated axis).
+__global__ void k_optics_bands(OpticsArgs a) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  const int K = 1 + a.nAer * a.nBand;
+  double tsum = 0.0;
+  const bool live = n < a.S;
+  const int b = live ? optics_band(n, a.nBand, a.band_start) : 0;
+  const size_t AZ = (size_t)a.nAer * a.Nz;
+  const double *aer = a.aer + 2 * AZ * b;
+  const int *mode = a.aer_mode + AZ * b;
+  const double varpi_rayl = a.varpi_band[b];
+  if (live) a.tau_sum[n] = 0.0;
+  for (int z = 0; z < a.Nz; ++z) {
+    double tw = 0.0;
+    if (live) {
+      const size_t o = n + (size_t)a.S * z;
+      double tau, varpi, w[8];
+      optics_point(a, o, z, varpi_rayl, aer, mode, w, tau, varpi);
+      a.tau[o] = tau;
+      a.varpi[o] = varpi;
+      double *zw = a.zw + (size_t)K * o;
+      zw[0] = w[0];
+      for (int x = 0; x < a.nAer; ++x) zw[1 + x + a.nAer * b] = w[x + 1];
+      tsum = tsum + 1.0 * tau;
+      a.tau_sum[o + a.S] = tsum;
+      tw = tau * varpi;
+    }
+    optics_layer_max(tw, a.layer_max + z);
   }
 }
 
@@ -489,49 +548,77 @@ static int doubling_number_host(double dtau_max, double tau_end) {
   return (int)nlimit + 1;
 }
 
-extern "C" int mom_scene_set_optics(mom_t *h, int Nz, int nAer, int M, const double *tau_rayl, double varpi_rayl,
-                                    const double *tau_aer, const double *omega_aer, const double *ft_aer,
-                                    const double *Zpp, const double *Zmp, double albedo, int nVza, const int *node_1based,
-                                    const double *cos_mphi, const double *sin_mphi) {
-  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
-  if (!h->streams_set) return fail(h, MOM_ESTATE, "mom_scene_set_optics: call mom_set_streams first");
-  if (Nz <= 0 || nAer < 0 || nAer > 7 || M <= 0 || M > h->M || nVza <= 0 || !tau_rayl || !Zpp || !Zmp || !node_1based ||
+namespace {
+// MOM_EINVAL with the reason unless band_start [nBand + 1] runs strictly ascending from 0 to S and 1 + nAer nBand bases fit
+int bands_check(mom_t *h, const char *fn, int nAer, int nBand, const int *band_start) {
+  char buf[200];
+  buf[0] = 0;
+  if (nBand < 1) snprintf(buf, sizeof buf, "%s: nBand = %d: a band-resolved scene has at least one band", fn, nBand);
+  else if (!band_start) snprintf(buf, sizeof buf, "%s: band_start is NULL", fn);
+  else if (nAer >= 0 && 1 + (long long)nAer * nBand > 64)
+    snprintf(buf, sizeof buf, "%s: 1 + nAer nBand = 1 + %d x %d phase-matrix bases, at most 64", fn, nAer, nBand);
+  else if (band_start[0] != 0) snprintf(buf, sizeof buf, "%s: band_start[0] = %d, not 0", fn, band_start[0]);
+  else if (band_start[nBand] != h->S) snprintf(buf, sizeof buf, "%s: band_start[nBand] = %d, not nSpec = %d", fn, band_start[nBand], h->S);
+  else
+    for (int b = 0; b < nBand && !buf[0]; ++b)
+      if (band_start[b + 1] <= band_start[b])
+        snprintf(buf, sizeof buf, "%s: band_start is not strictly ascending: band %d is [%d, %d)", fn, b + 1, band_start[b], band_start[b + 1]);
+  return buf[0] ? fail(h, MOM_EINVAL, buf) : MOM_OK;
+}
+
+// mom_scene_set_optics (nBand = 0: one ϖ_Cabannes, one aerosol set for the whole axis, k_optics) and mom_scene_set_optics_bands
+// (nBand >= 1, k_optics_bands): the checks, createAero and the three-way modes per band on the host, the launch, ndoubl / interface
+// codes from the per-layer maxima and the tail every scene shares.  tau_aer [nAer, Nz, nB], omega_aer / ft_aer [nAer, nB],
+// varpi_rayl [nB], nB = max(nBand, 1).
+int scene_set_optics_run(mom_t *h, const char *fn, int Nz, int nAer, int nBand, const int *band_start, int M, const double *tau_rayl,
+                         const double *varpi_rayl, const double *tau_aer, const double *omega_aer, const double *ft_aer,
+                         const double *Zpp, const double *Zmp, double albedo, int nVza, const int *node_1based, const double *cos_mphi,
+                         const double *sin_mphi) {
+  const std::string f(fn);
+  if (!h->streams_set) return fail(h, MOM_ESTATE, (f + ": call mom_set_streams first").c_str());
+  if (Nz <= 0 || nAer < 0 || nAer > 7 || M <= 0 || M > h->M || nVza <= 0 || !tau_rayl || !varpi_rayl || !Zpp || !Zmp || !node_1based ||
       !cos_mphi || !sin_mphi || (nAer > 0 && (!tau_aer || !omega_aer || !ft_aer)))
-    return fail(h, MOM_EINVAL, "mom_scene_set_optics: bad argument");
+    return fail(h, MOM_EINVAL, (f + ": bad argument").c_str());
   if (!h->d_tau_abs || h->abs_Nz != Nz)
-    return fail(h, MOM_ESTATE, "mom_scene_set_optics: no resident tau_abs table of this Nz (mom_absorption_begin / _set)");
+    return fail(h, MOM_ESTATE, (f + ": no resident tau_abs table of this Nz (mom_absorption_begin / _set)").c_str());
   HIPCHK(h, hipSetDevice(h->device));
   h->scene_set = false;
   h->optics_scene = h->optics_tables = false;
-  const size_t S = h->S;
-  const int K = 1 + nAer;
+  const size_t S = h->S, AZ = (size_t)nAer * Nz;
+  const int nB = std::max(nBand, 1);
+  const int K = 1 + nAer * nB;
+  const int whole_axis[2] = {0, h->S};
+  const int *bs = nBand ? band_start : whole_axis;
   int rc;
   HIPCHK(h, mom_upload(h->d_tau_rayl, tau_rayl, S * Nz, h->stream));
-  // the Dual run of this assembly (mom_scene_set_optics_partials) differentiates createAero on the host as well
+  // the Dual run of this assembly (mom_scene_set_optics_partials / _bands_partials) differentiates createAero on the host as well
   h->optics_nAer = nAer;
-  h->optics_varpi_rayl = varpi_rayl;
-  h->h_tau_aer.assign(tau_aer, tau_aer + (nAer > 0 ? (size_t)nAer * Nz : 0));
-  h->h_omega_aer.assign(omega_aer, omega_aer + (nAer > 0 ? nAer : 0));
-  h->h_ft_aer.assign(ft_aer, ft_aer + (nAer > 0 ? nAer : 0));
+  h->optics_nBand = nBand;
+  h->h_varpi_rayl.assign(varpi_rayl, varpi_rayl + nB);
+  h->h_tau_aer.assign(tau_aer, tau_aer + (nAer > 0 ? AZ * nB : 0));
+  h->h_omega_aer.assign(omega_aer, omega_aer + (nAer > 0 ? nAer * nB : 0));
+  h->h_ft_aer.assign(ft_aer, ft_aer + (nAer > 0 ? nAer * nB : 0));
   // createAero (compEffectiveLayerProperties.jl:80-85): τ' = (1 - fᵗ ω̃) τ_aer, ϖ' = (1 - fᵗ) ω̃ / (1 - fᵗ ω̃); the
-  // all-zero tests of types.jl:641-661 are decided here on the host (they are properties of whole spectral columns)
-  std::vector<double> aer((size_t)2 * std::max(nAer, 1) * Nz, 0.0);
-  std::vector<int> mode((size_t)std::max(nAer, 1) * Nz, 2);
-  for (int z = 0; z < Nz; ++z) {
-    bool x_zero = true;  // all(τ ϖ == 0) of the accumulated left operand
-    if (varpi_rayl != 0.0)
-      for (size_t n = 0; n < S; ++n)
-        if (tau_rayl[n + S * z] != 0.0) { x_zero = false; break; }
-    for (int x = 0; x < nAer; ++x) {
-      const double ty = (1 - ft_aer[x] * omega_aer[x]) * tau_aer[x + (size_t)nAer * z];
-      const double vy = (1 - ft_aer[x]) * omega_aer[x] / (1 - ft_aer[x] * omega_aer[x]);
-      const double wy = ty * vy;
-      aer[x + (size_t)nAer * z] = ty;
-      aer[(size_t)nAer * Nz + x + (size_t)nAer * z] = wy;
-      mode[x + (size_t)nAer * z] = x_zero ? 0 : (wy != 0.0 ? 1 : 2);
-      x_zero = x_zero && (wy == 0.0);
+  // all-zero tests of types.jl:641-661 are decided here on the host (they are properties of a band's whole spectral columns)
+  std::vector<double> aer((size_t)2 * std::max(nAer, 1) * Nz * nB, 0.0);
+  std::vector<int> mode((size_t)std::max(nAer, 1) * Nz * nB, 2);
+  for (int b = 0; b < nB; ++b)
+    for (int z = 0; z < Nz; ++z) {
+      bool x_zero = true;  // all(τ ϖ == 0) of the accumulated left operand
+      if (varpi_rayl[b] != 0.0)
+        for (size_t n = (size_t)bs[b]; n < (size_t)bs[b + 1]; ++n)
+          if (tau_rayl[n + S * z] != 0.0) { x_zero = false; break; }
+      for (int x = 0; x < nAer; ++x) {
+        const size_t ax = x + (size_t)nAer * z, xb = x + (size_t)nAer * b;
+        const double ty = (1 - ft_aer[xb] * omega_aer[xb]) * tau_aer[ax + AZ * b];
+        const double vy = (1 - ft_aer[xb]) * omega_aer[xb] / (1 - ft_aer[xb] * omega_aer[xb]);
+        const double wy = ty * vy;
+        aer[2 * AZ * b + ax] = ty;
+        aer[2 * AZ * b + AZ + ax] = wy;
+        mode[AZ * b + ax] = x_zero ? 0 : (wy != 0.0 ? 1 : 2);
+        x_zero = x_zero && (wy == 0.0);
+      }
     }
-  }
   HIPCHK(h, mom_upload(h->d_aer, aer.data(), aer.size(), h->stream));
   HIPCHK(h, mom_upload(h->d_aer_mode, mode.data(), mode.size(), h->stream));
   HIPCHK(h, h->d_tau.renew(S * Nz));
@@ -541,10 +628,19 @@ extern "C" int mom_scene_set_optics(mom_t *h, int Nz, int nAer, int M, const dou
   HIPCHK(h, h->d_layer_max.renew((size_t)Nz));
   HIPCHK(h, hipMemsetAsync(h->d_layer_max, 0, (size_t)Nz * sizeof(double), h->stream));
   OpticsArgs a{};
-  a.S = h->S; a.Nz = Nz; a.nAer = nAer; a.varpi_rayl = varpi_rayl;
+  a.S = h->S; a.Nz = Nz; a.nAer = nAer; a.varpi_rayl = varpi_rayl[0];
   a.tau_rayl = h->d_tau_rayl; a.tau_abs = h->d_tau_abs; a.aer = h->d_aer; a.aer_mode = h->d_aer_mode;
   a.tau = h->d_tau; a.varpi = h->d_varpi; a.zw = h->d_zw; a.tau_sum = h->d_tau_sum; a.layer_max = h->d_layer_max;
-  hipLaunchKernelGGL(k_optics, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, h->stream, a);
+  if (nBand) {
+    HIPCHK(h, mom_upload(h->d_band_start, band_start, (size_t)nBand + 1, h->stream));
+    HIPCHK(h, mom_upload(h->d_varpi_band, varpi_rayl, (size_t)nBand, h->stream));
+    a.nBand = nBand; a.band_start = h->d_band_start; a.varpi_band = h->d_varpi_band;
+    // a point's weights outside its own band are exact zeros: zeroed here, and the kernel stores the 1 + nAer live ones only
+    HIPCHK(h, hipMemsetAsync(h->d_zw, 0, (size_t)K * S * Nz * sizeof(double), h->stream));
+    hipLaunchKernelGGL(k_optics_bands, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, h->stream, a);
+  } else {
+    hipLaunchKernelGGL(k_optics, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, h->stream, a);
+  }
   HIPCHK(h, hipGetLastError());
   // get_dtau_ndoubl takes maximum(τ .* ϖ) over the WHOLE spectral axis (rt_kernel.jl:241-242): across the ranks of a
   // sharded run the per-layer maxima are combined first (one tiny all-reduce at set-up time, not in the sweep)
@@ -558,9 +654,9 @@ extern "C" int mom_scene_set_optics(mom_t *h, int Nz, int nAer, int M, const dou
   h->iface.assign((size_t)Nz, 0);
   int prev = 0;
   for (int z = 0; z < Nz; ++z) {
-    if (!std::isfinite(mx[z])) return fail(h, MOM_EINVAL, "mom_scene_set_optics: a layer has non-finite τ ϖ (empty layer: τ = 0?)");
+    if (!std::isfinite(mx[z])) return fail(h, MOM_EINVAL, (f + ": a layer has non-finite τ ϖ (empty layer: τ = 0?)").c_str());
     h->nd[z] = doubling_number_host(std::min(mx[z], 0.001 * mu_min), mx[z]);
-    if (h->nd[z] > 60) return fail(h, MOM_EINVAL, "mom_scene_set_optics: ndoubl out of range");
+    if (h->nd[z] > 60) return fail(h, MOM_EINVAL, (f + ": ndoubl out of range").c_str());
     const bool scatter = mx[z] > 2 * 2.220446049250313e-16;  // compEffectiveLayerProperties.jl:104
     prev = (z == 0) ? (scatter ? 3 : 0) : (prev == 0 ? (scatter ? 1 : 0) : (scatter ? 3 : 2));  // rt_helper_functions.jl:8-27
     h->iface[z] = prev;
@@ -577,6 +673,32 @@ extern "C" int mom_scene_set_optics(mom_t *h, int Nz, int nAer, int M, const dou
   h->scene_set = true;
   h->optics_scene = h->optics_tables = true;
   return MOM_OK;
+}
+}  // namespace
+
+extern "C" int mom_scene_set_optics(mom_t *h, int Nz, int nAer, int M, const double *tau_rayl, double varpi_rayl,
+                                    const double *tau_aer, const double *omega_aer, const double *ft_aer,
+                                    const double *Zpp, const double *Zmp, double albedo, int nVza, const int *node_1based,
+                                    const double *cos_mphi, const double *sin_mphi) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  return scene_set_optics_run(h, "mom_scene_set_optics", Nz, nAer, 0, nullptr, M, tau_rayl, &varpi_rayl, tau_aer, omega_aer, ft_aer, Zpp,
+                              Zmp, albedo, nVza, node_1based, cos_mphi, sin_mphi);
+}
+
+extern "C" int mom_scene_set_optics_bands(mom_t *h, int Nz, int nAer, int nBand, const int *band_start, int M, const double *tau_rayl,
+                                          const double *varpi_rayl, const double *tau_aer, const double *omega_aer,
+                                          const double *ft_aer, const double *Zpp, const double *Zmp, double albedo, int nVza,
+                                          const int *node_1based, const double *cos_mphi, const double *sin_mphi) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  const char *fn = "mom_scene_set_optics_bands";
+  const int rc = bands_check(h, fn, nAer, nBand, band_start);
+  if (rc) return rc;
+  if (h->comm)
+    return fail(h, MOM_EUNSUPPORTED, "mom_scene_set_optics_bands: the handle has a communicator: the per-band all-zero tests of the `+` "
+                                     "(types.jl:641-661) would need a reduction over the ranks; a sharded band-resolved run takes the host "
+                                     "route (mom_scene_set)");
+  return scene_set_optics_run(h, fn, Nz, nAer, nBand, band_start, M, tau_rayl, varpi_rayl, tau_aer, omega_aer, ft_aer, Zpp, Zmp, albedo,
+                              nVza, node_1based, cos_mphi, sin_mphi);
 }
 
 extern "C" int mom_scene_get_layers(mom_t *h, int *ndoubl, int *iface, double *tau, double *varpi, double *zw, double *tau_sum) {
@@ -618,27 +740,31 @@ struct OpticsDualArgs {
   const double *daer;                // [2,nAer,Nz,P]: partials of aer
   double *dtau, *dvarpi;             // [S,Nz,P]
   double *dzw;                       // [K,S,Nz,P] or null (identically zero: not stored)
+  // k_optics_bands_dual only: aer, aer_mode one block per band as in OpticsArgs, daer [2,nAer,Nz,nBand,P]
+  int nBand;
+  const int *band_start;             // [nBand + 1]
+  const double *varpi_band;          // [nBand]
 };
 __device__ __forceinline__ void dual_div(double a, double da, double b, double db, double &q, double &dq) {
   q = a / b;
   dq = da * (1.0 / b) + db * (-(a / (b * b)));
 }
-__global__ void __launch_bounds__(256) k_optics_dual(OpticsDualArgs a) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x, z = blockIdx.y, p = blockIdx.z;
-  if (n >= a.S) return;
-  const int K = 1 + a.nAer;
+// One (spectral point, layer, partial): stores dτ and dϖ and leaves the partials dw of the 1 + nAer weights of the point's own bases;
+// `aer` / `mode` are the value blocks of the point's band, `daer` the [2,nAer,Nz] partial block of (band, partial).
+__device__ __forceinline__ void optics_point_dual(const OpticsDualArgs &a, int n, int z, int p, double varpi_rayl, const double *aer,
+                                                  const int *aer_mode, const double *daer, double (&dw)[8]) {
   const size_t SZ = (size_t)a.S * a.Nz, AZ = (size_t)a.nAer * a.Nz;
   const size_t o = n + (size_t)a.S * z, op = o + SZ * p;
-  double tau = a.tau_rayl[o], varpi = a.varpi_rayl;
+  double tau = a.tau_rayl[o], varpi = varpi_rayl;
   double dtau = tau * a.w_rayl[z + (size_t)a.Nz * p], dvarpi = 0.0;
-  double w[8], dw[8];
+  double w[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) { w[k] = k == 0 ? 1.0 : 0.0; dw[k] = 0.0; }
   for (int x = 0; x < a.nAer; ++x) {
     const size_t ax = x + (size_t)a.nAer * z;
-    const double ty = a.aer[ax], wy = a.aer[AZ + ax];
-    const double dty = a.daer[ax + 2 * AZ * p], dwy = a.daer[AZ + ax + 2 * AZ * p];
-    const int mode = a.aer_mode[ax];
+    const double ty = aer[ax], wy = aer[AZ + ax];
+    const double dty = daer[ax], dwy = daer[AZ + ax];
+    const int mode = aer_mode[ax];
     const double wx = tau * varpi, dwx = dtau * varpi + dvarpi * tau;
     const double tot = wx + wy, dtot = dwx + dwy, tn = tau + ty, dtn = dtau + dty;
     if (mode == 0) {
@@ -668,10 +794,38 @@ __global__ void __launch_bounds__(256) k_optics_dual(OpticsDualArgs a) {
   dual_div(num, dnum, tn, dtn, varpi, dvarpi);
   a.dtau[op] = dtn;
   a.dvarpi[op] = dvarpi;
+}
+__global__ void __launch_bounds__(256) k_optics_dual(OpticsDualArgs a) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x, z = blockIdx.y, p = blockIdx.z;
+  if (n >= a.S) return;
+  const int K = 1 + a.nAer;
+  const size_t AZ = (size_t)a.nAer * a.Nz, op = n + (size_t)a.S * z + (size_t)a.S * a.Nz * p;
+  double dw[8];
+  optics_point_dual(a, n, z, p, a.varpi_rayl, a.aer, a.aer_mode, a.daer + 2 * AZ * p, dw);
   if (a.dzw) {
 #pragma unroll
     for (int k = 0; k < 8; ++k)
       if (k < K) a.dzw[k + (size_t)K * op] = dw[k];
+  }
+}
+// k_optics_dual for a band-resolved scene, as k_optics_bands is k_optics': the same grid, the band found once per thread, that
+// band's ϖ_Cabannes, value blocks and partial block (a partial that names one band's aerosol has zero blocks in the others, so the
+// other bands' points see the Rayleigh and gas partials only).  dzw [K,S,Nz,P], K = 1 + nAer nBand, is zeroed by the host and a thread
+// stores the 1 + nAer entries of its own band.
+__global__ void __launch_bounds__(256) k_optics_bands_dual(OpticsDualArgs a) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x, z = blockIdx.y, p = blockIdx.z;
+  if (n >= a.S) return;
+  const int K = 1 + a.nAer * a.nBand;
+  const int b = optics_band(n, a.nBand, a.band_start);
+  const size_t AZ = (size_t)a.nAer * a.Nz, op = n + (size_t)a.S * z + (size_t)a.S * a.Nz * p;
+  double dw[8];
+  optics_point_dual(a, n, z, p, a.varpi_band[b], a.aer + 2 * AZ * b, a.aer_mode + AZ * b, a.daer + 2 * AZ * (b + (size_t)a.nBand * p), dw);
+  if (a.dzw) {
+    double *dzw = a.dzw + (size_t)K * op;
+    dzw[0] = dw[0];
+#pragma unroll
+    for (int x = 0; x < 7; ++x)
+      if (x < a.nAer) dzw[1 + x + a.nAer * b] = dw[x + 1];
   }
 }
 
@@ -688,67 +842,103 @@ static void create_aero_dual(double tau_aer, double om, double ft, double dtau_a
   *dwy = *dty * vy + dvy * ty;
 }
 
-extern "C" int mom_scene_set_optics_partials(mom_t *h, int P, const double *w_abs, const double *w_rayl, const double *dtau_aer,
-                                             const double *domega_aer, const double *dft_aer, const double *dZpp, const double *dZmp,
-                                             const double *dalbedo, const double *dRsurf, const double *dalbedo_spec) {
-  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
-  F64_ONLY(h, "mom_scene_set_optics_partials");
-  if (!h->scene_set) return fail(h, MOM_ESTATE, "mom_scene_set_optics_partials: call mom_scene_set_optics first");
+namespace {
+// mom_scene_set_optics_partials (banded = false, k_optics_dual) and mom_scene_set_optics_bands_partials (k_optics_bands_dual): the
+// state rules, createAero on Duals per (band, layer, type, partial), the launch and mom_partials_rest.  dtau_aer [nAer, Nz, nB, P],
+// domega_aer / dft_aer [nAer, nB, P], nB = the scene's bands (1 without).
+int scene_set_optics_partials_run(mom_t *h, const char *fn, bool banded, int P, const double *w_abs, const double *w_rayl,
+                                  const double *dtau_aer, const double *domega_aer, const double *dft_aer, const double *dZpp,
+                                  const double *dZmp, const double *dalbedo, const double *dRsurf, const double *dalbedo_spec) {
+  const std::string f(fn), setter = banded ? "mom_scene_set_optics_bands" : "mom_scene_set_optics";
+  if (!h->scene_set) return fail(h, MOM_ESTATE, (f + ": call " + setter + " first").c_str());
   if (!h->optics_scene)
-    return fail(h, MOM_ESTATE, "mom_scene_set_optics_partials: the resident scene came from mom_scene_set (host optics): its partials go "
-                               "through mom_scene_set_partials");
+    return fail(h, MOM_ESTATE, (f + ": the resident scene came from mom_scene_set (host optics): its partials go through "
+                                    "mom_scene_set_partials").c_str());
+  if (banded != (h->optics_nBand != 0))
+    return fail(h, MOM_ESTATE, (f + ": the resident scene came from " + (banded ? "mom_scene_set_optics (no bands): its partials go through "
+                                    "mom_scene_set_optics_partials" : "mom_scene_set_optics_bands: its partials go through "
+                                    "mom_scene_set_optics_bands_partials")).c_str());
   if (!h->optics_tables || !h->d_tau_abs || h->abs_Nz != h->Nz)
-    return fail(h, MOM_ESTATE, "mom_scene_set_optics_partials: mom_absorption_begin / _set was called after the mom_scene_set_optics that "
-                               "made the scene: the resident tau_abs table is not the scene's");
-  int rc = mom_partials_check(h, "mom_scene_set_optics_partials", P, dZpp, dZmp);
+    return fail(h, MOM_ESTATE, (f + ": mom_absorption_begin / _set was called after the " + setter + " that made the scene: the resident "
+                                    "tau_abs table is not the scene's").c_str());
+  int rc = mom_partials_check(h, fn, P, dZpp, dZmp);
   if (rc) return rc;
-  const int Nz = h->Nz, nAer = h->optics_nAer, K = h->K;
+  const int Nz = h->Nz, nAer = h->optics_nAer, K = h->K, nB = std::max(h->optics_nBand, 1);
   if (w_abs && !h->d_dtau_abs)
     for (size_t k = 0; k < (size_t)P; ++k)
       for (size_t i = 0; i < 2 * (size_t)Nz; ++i)
         if (w_abs[i + 3 * (size_t)Nz * k] != 0.0)
-          return fail(h, MOM_ESTATE, "mom_scene_set_optics_partials: w_abs has a nonzero pressure or temperature weight, but no dtau_abs "
-                                     "table is resident (no Dual absorption call since the table was set)");
+          return fail(h, MOM_ESTATE, (f + ": w_abs has a nonzero pressure or temperature weight, but no dtau_abs table is resident (no "
+                                          "Dual absorption call since the table was set)").c_str());
   HIPCHK(h, hipSetDevice(h->device));
   mom_partials_reset(h, P);
   if (P == 0) return MOM_OK;
   const size_t S = h->S, SZ = S * Nz, AZ = (size_t)nAer * Nz;
-  // per-(layer, partial) scalars: w_abs [Nz,3,P] | w_rayl [Nz,P] | d aer [2,nAer,Nz,P]; a null argument: zeros
-  const size_t n_abs = 3 * (size_t)Nz * P, n_rayl = (size_t)Nz * P, n_aer = 2 * AZ * P;
+  // per-(layer, partial) scalars: w_abs [Nz,3,P] | w_rayl [Nz,P] | d aer [2,nAer,Nz,nB,P]; a null argument: zeros
+  const size_t n_abs = 3 * (size_t)Nz * P, n_rayl = (size_t)Nz * P, n_aer = 2 * AZ * nB * P;
   std::vector<double> prm(n_abs + n_rayl + n_aer, 0.0);
   if (w_abs) std::copy(w_abs, w_abs + n_abs, prm.begin());
   if (w_rayl) std::copy(w_rayl, w_rayl + n_rayl, prm.begin() + n_abs);
   if (nAer > 0 && (dtau_aer || domega_aer || dft_aer)) {
     double *da = prm.data() + n_abs + n_rayl;
     for (size_t k = 0; k < (size_t)P; ++k)
-      for (int z = 0; z < Nz; ++z)
-        for (int x = 0; x < nAer; ++x) {
-          const size_t ax = x + (size_t)nAer * z;
-          create_aero_dual(h->h_tau_aer[ax], h->h_omega_aer[x], h->h_ft_aer[x], dtau_aer ? dtau_aer[ax + AZ * k] : 0.0,
-                           domega_aer ? domega_aer[x + (size_t)nAer * k] : 0.0, dft_aer ? dft_aer[x + (size_t)nAer * k] : 0.0,
-                           &da[ax + 2 * AZ * k], &da[AZ + ax + 2 * AZ * k]);
-        }
+      for (int b = 0; b < nB; ++b)
+        for (int z = 0; z < Nz; ++z)
+          for (int x = 0; x < nAer; ++x) {
+            const size_t ax = x + (size_t)nAer * z, xb = x + (size_t)nAer * b, blk = 2 * AZ * (b + (size_t)nB * k);
+            create_aero_dual(h->h_tau_aer[ax + AZ * b], h->h_omega_aer[xb], h->h_ft_aer[xb],
+                             dtau_aer ? dtau_aer[ax + AZ * (b + (size_t)nB * k)] : 0.0,
+                             domega_aer ? domega_aer[xb + (size_t)nAer * nB * k] : 0.0, dft_aer ? dft_aer[xb + (size_t)nAer * nB * k] : 0.0,
+                             &da[blk + ax], &da[blk + AZ + ax]);
+          }
   }
   HIPCHK(h, h->d_optics_prm.reserve(prm.size(), h->stream));
   HIPCHK(h, hipMemcpyAsync(h->d_optics_prm, prm.data(), prm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, h->d_dual_in[0].renew(SZ * P));
   HIPCHK(h, h->d_dual_in[1].renew(SZ * P));
   // the weights depend on the Rayleigh and aerosol ingredients only: without a partial of those dzw stays absent and the sweep skips it
-  if (nAer > 0 && (w_rayl || dtau_aer || domega_aer || dft_aer)) HIPCHK(h, h->d_dual_in[2].renew((size_t)K * SZ * P));
+  if (nAer > 0 && (w_rayl || dtau_aer || domega_aer || dft_aer)) {
+    HIPCHK(h, h->d_dual_in[2].renew((size_t)K * SZ * P));
+    // band-resolved: the entries outside a point's own band are exact zeros, and k_optics_bands_dual stores the live ones only
+    if (banded) HIPCHK(h, hipMemsetAsync(h->d_dual_in[2], 0, (size_t)K * SZ * P * sizeof(double), h->stream));
+  }
   OpticsDualArgs a{};
   a.S = h->S; a.Nz = Nz; a.nAer = nAer;
-  a.varpi_rayl = h->optics_varpi_rayl;
+  a.varpi_rayl = h->h_varpi_rayl[0];
   a.tau_rayl = h->d_tau_rayl; a.tau_abs = h->d_tau_abs; a.dtau_abs = h->d_dtau_abs; a.aer = h->d_aer; a.aer_mode = h->d_aer_mode;
   a.w_abs = h->d_optics_prm; a.w_rayl = h->d_optics_prm + n_abs; a.daer = h->d_optics_prm + n_abs + n_rayl;
   a.dtau = h->d_dual_in[0]; a.dvarpi = h->d_dual_in[1]; a.dzw = h->d_dual_in[2];
+  a.nBand = h->optics_nBand; a.band_start = h->d_band_start; a.varpi_band = h->d_varpi_band;
   // the launch between the handle's timing events: mom_timers right after this call gives the kernel's time as its total
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-  hipLaunchKernelGGL(k_optics_dual, dim3((unsigned)((S + 255) / 256), (unsigned)Nz, (unsigned)P), dim3(256), 0, h->stream, a);
+  const dim3 grid((unsigned)((S + 255) / 256), (unsigned)Nz, (unsigned)P);
+  if (banded) hipLaunchKernelGGL(k_optics_bands_dual, grid, dim3(256), 0, h->stream, a);
+  else hipLaunchKernelGGL(k_optics_dual, grid, dim3(256), 0, h->stream, a);
   HIPCHK(h, hipGetLastError());
   for (int k = 1; k < 4; ++k) HIPCHK(h, hipEventRecord(h->ev[k], h->stream));
   h->launches = 1; h->launches_full = 0; h->launches_red = 0;
   HIPCHK(h, hipStreamSynchronize(h->stream));  // prm is a host temporary
   return mom_partials_rest(h, dZpp, dZmp, dalbedo, dRsurf, dalbedo_spec);
+}
+}  // namespace
+
+extern "C" int mom_scene_set_optics_partials(mom_t *h, int P, const double *w_abs, const double *w_rayl, const double *dtau_aer,
+                                             const double *domega_aer, const double *dft_aer, const double *dZpp, const double *dZmp,
+                                             const double *dalbedo, const double *dRsurf, const double *dalbedo_spec) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  F64_ONLY(h, "mom_scene_set_optics_partials");
+  return scene_set_optics_partials_run(h, "mom_scene_set_optics_partials", false, P, w_abs, w_rayl, dtau_aer, domega_aer, dft_aer, dZpp,
+                                       dZmp, dalbedo, dRsurf, dalbedo_spec);
+}
+
+extern "C" int mom_scene_set_optics_bands_partials(mom_t *h, int P, const double *w_abs, const double *w_rayl, const double *dtau_aer,
+                                                   const double *domega_aer, const double *dft_aer, const double *dZpp,
+                                                   const double *dZmp, const double *dalbedo, const double *dRsurf,
+                                                   const double *dalbedo_spec) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  F64_ONLY(h, "mom_scene_set_optics_bands_partials");
+  return scene_set_optics_partials_run(h, "mom_scene_set_optics_bands_partials", true, P, w_abs, w_rayl, dtau_aer, domega_aer, dft_aer,
+                                       dZpp, dZmp, dalbedo, dRsurf, dalbedo_spec);
 }
 
 extern "C" int mom_scene_get_partials(mom_t *h, double *dtau, double *dvarpi, double *dzw) {

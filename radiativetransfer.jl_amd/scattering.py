@@ -471,22 +471,82 @@ def truncate_phase(mod: δBGE, aero: rt.AerosolOptics, partials=None):
     return out, d_out
 
 
-def aerosol_optics_partial(model: rt.vSmartMOM_Model, i_aer: int, d_optics: rt.AerosolOptics, dτ_aer=None) -> rt.OpticsPartial:
+def aerosol_optics_partial(model: rt.vSmartMOM_Model, i_aer: int, d_optics: rt.AerosolOptics, dτ_aer=None, band: Optional[int] = None) -> rt.OpticsPartial:
     """The OpticsPartial of one parameter of aerosol i_aer (0-based) of the scene `model`, from ∂(aerosol optics)/∂θ as
     truncate_phase(..., partials=) returns it: dω̃ and dfᵗ at i_aer, dZpp / dZmp = compute_Z_moments of the derivative Greek
     coefficients (the moments are linear in them) at basis 1 + i_aer (basis 0 is Rayleigh), zeros elsewhere.  dτ_aer [nAer, Nz]
     is passed on (the scene's τ_aer is an input of its own; a caller that scales it with k supplies its partial).  The result goes
-    into rt_run_dual_device_optics."""
-    nAer = len(model.aerosol_optics)
+    into rt_run_dual_device_optics.
+    A model with bands: `band` (0-based) names the band whose aerosol i_aer the partial belongs to; dω̃ / dfᵗ [nBand, nAer] and
+    dZpp / dZmp [M, 1 + nAer nBand, N, N] are nonzero in that band's entries and basis 1 + i_aer + nAer band only, and dτ_aer
+    [nBand, nAer, Nz] is passed on.  A parameter shared by several bands is the sum of its per-band partials (sum_partials)."""
+    bands = model.bands
+    if (band is None) != (bands is None):
+        raise ValueError("`band` goes with a model that has bands, and only with one")
+    nAer = len(model.aerosol_optics) if bands is None else bands.nAer
     if not 0 <= i_aer < nAer:
         raise ValueError(f"i_aer = {i_aer} outside the model's {nAer} aerosols")
+    if bands is not None and not 0 <= band < bands.nBand:
+        raise ValueError(f"band = {band} outside the model's {bands.nBand} bands")
     pol, μ, M = model.params.polarization_type, model.quad_points.qp_μ, model.params.max_m
-    if len(d_optics.greek_coefs.β) != len(model.aerosol_optics[i_aer].greek_coefs.β):
+    aero = model.aerosol_optics[i_aer] if bands is None else bands.aerosol_optics[band][i_aer]
+    if len(d_optics.greek_coefs.β) != len(aero.greek_coefs.β):
         raise ValueError("the derivative Greek coefficients do not have the length of the aerosol's")
     N = pol.n * len(μ)
-    dZpp, dZmp = np.zeros((M, 1 + nAer, N, N)), np.zeros((M, 1 + nAer, N, N))
+    K, k = (1 + nAer, 1 + i_aer) if bands is None else (1 + nAer * bands.nBand, 1 + i_aer + nAer * band)
+    dZpp, dZmp = np.zeros((M, K, N, N)), np.zeros((M, K, N, N))
     for m in range(M):
-        dZpp[m, 1 + i_aer], dZmp[m, 1 + i_aer] = rt.compute_Z_moments(pol, μ, d_optics.greek_coefs, m)[:2]
-    dω̃, dfᵗ = np.zeros(nAer), np.zeros(nAer)
-    dω̃[i_aer], dfᵗ[i_aer] = d_optics.ω̃, d_optics.fᵗ
+        dZpp[m, k], dZmp[m, k] = rt.compute_Z_moments(pol, μ, d_optics.greek_coefs, m)[:2]
+    shape, at = ((nAer,), i_aer) if bands is None else ((bands.nBand, nAer), (band, i_aer))
+    dω̃, dfᵗ = np.zeros(shape), np.zeros(shape)
+    dω̃[at], dfᵗ[at] = d_optics.ω̃, d_optics.fᵗ
     return rt.OpticsPartial(dτ_aer=None if dτ_aer is None else np.asarray(dτ_aer, dtype=np.float64), dω̃=dω̃, dfᵗ=dfᵗ, dZpp=dZpp, dZmp=dZmp)
+
+
+def sum_partials(partials) -> rt.OpticsPartial:
+    """The OpticsPartial of ONE parameter that acts through several ingredients (a size parameter of an aerosol that every band
+    sees): the field-wise sum of the per-ingredient partials, None where none of them has the field."""
+    import dataclasses
+    out = rt.OpticsPartial()
+    for p in partials:
+        for f in dataclasses.fields(p):
+            v, acc = getattr(p, f.name), getattr(out, f.name)
+            if v is not None:
+                setattr(out, f.name, v if acc is None else acc + v)
+    return out
+
+
+def band_aerosol_optics(mie_model: MieModel, λ_bands, λ_ref: float, τ_ref: float, profile, nᵣ=None, nᵢ=None, n_ref=None,
+                        autodiff: bool = False, wrt=_SIZE_PARAMETERS):
+    """One aerosol type in every band of a band-resolved scene, as model_from_parameters.jl:117-165 sets it up: the Mie run at each
+    band centre λ_bands [nBand] and at λ_ref in ONE compute_spectral_aerosol_optical_properties call over [λ_bands..., λ_ref],
+    truncate_phase(mie_model.truncation_type) per band, and τ_aer[b] = τ_ref * (k_b / k_ref) * profile (profile [Nz]: the layers'
+    shares of the column, getAerosolLayerOptProp).  nᵣ, nᵢ [nBand]: the refractive index per band (default: the aerosol's), n_ref =
+    (nᵣ, nᵢ) at λ_ref (default: the aerosol's).  Returns (aerosol_optics [nBand], τ_aer [nBand, Nz]); with autodiff=True also
+    (d_optics [nBand][len(wrt)], dτ_aer [len(wrt), nBand, Nz]): the partials of each band's truncated optics and of τ_aer, which
+    depends on a parameter through k_b and k_ref.  An index parameter in `wrt` is the SAME change of every wavelength's index."""
+    λ_bands = np.atleast_1d(np.asarray(λ_bands, dtype=np.float64))
+    nB = λ_bands.size
+    profile = np.asarray(profile, dtype=np.float64).reshape(-1)
+    aer = mie_model.aerosol
+    nᵣ = np.full(nB, aer.nᵣ) if nᵣ is None else np.asarray(nᵣ, dtype=np.float64).reshape(nB)
+    nᵢ = np.full(nB, aer.nᵢ) if nᵢ is None else np.asarray(nᵢ, dtype=np.float64).reshape(nB)
+    n_ref = (aer.nᵣ, aer.nᵢ) if n_ref is None else n_ref
+    res = compute_spectral_aerosol_optical_properties(mie_model, np.append(λ_bands, λ_ref), np.append(nᵣ, n_ref[0]), np.append(nᵢ, n_ref[1]),
+                                                      autodiff=autodiff, wrt=wrt)
+    raw, parts = res if autodiff else (res, None)
+    k_ref = raw[nB].k
+    optics, d_optics = [], []
+    for b in range(nB):
+        if autodiff:
+            o, d = truncate_phase(mie_model.truncation_type, raw[b], parts[b])
+            d_optics.append(d)
+        else:
+            o = truncate_phase(mie_model.truncation_type, raw[b])
+        optics.append(o)
+    τ_aer = np.array([τ_ref * (o.k / k_ref) * profile for o in optics])
+    if not autodiff:
+        return optics, τ_aer
+    dτ_aer = np.array([[τ_ref * (d_optics[b][j].k / k_ref - optics[b].k * parts[nB][j].k / k_ref ** 2) * profile for b in range(nB)]
+                       for j in range(len(tuple(wrt)))]).reshape(len(tuple(wrt)), nB, profile.size)
+    return optics, τ_aer, d_optics, dτ_aer

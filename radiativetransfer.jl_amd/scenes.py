@@ -121,6 +121,48 @@ def scene_C3(S: int = 29_944, Nz: int = 40, **kw):
     return m
 
 
+def c3_band_start(S: int) -> np.ndarray:
+    """the offsets of scene_C3's three bands on its spectral axis"""
+    n1, n2 = 13_672 * S // 29_944, 6_402 * S // 29_944
+    return np.array([0, n1, n1 + n2, S], dtype=np.int32)
+
+
+# per band of scene_C3_bands: asymmetry g of hg_like_greek, ω̃, fᵗ, τ_aer relative to the O2 A-band's
+C3_BAND_AEROSOL = ((0.70, 0.95, 0.00), (0.62, 0.92, 0.05), (0.55, 0.90, 0.10))
+C3_BAND_τ_SCALE = (1.0, 0.45, 0.30)
+
+
+def scene_C3_bands(S: int = 29_944, Nz: int = 40, **kw):
+    """scene_C3 with the aerosol resolved per band (rt.Bands): the O2 A-band's aerosol as in scene_C3, a synthetic one of its own
+    (hg_like_greek with its own g, ω̃, fᵗ and τ scaling: C3_BAND_AEROSOL, C3_BAND_τ_SCALE) at 1.6 µm and 2.06 µm.  K = 4 bases."""
+    m = scene_C3(S, Nz, **kw)
+    if not m.aerosol_optics:
+        raise ValueError("scene_C3_bands needs aerosol_total > 0")
+    l_trunc = m.params.l_trunc
+    optics = [[rt.AerosolOptics(hg_like_greek(g, l_trunc), ω̃, fᵗ)] for g, ω̃, fᵗ in C3_BAND_AEROSOL]
+    τ_aer = np.array([s * m.τ_aer for s in C3_BAND_τ_SCALE])
+    return rt.with_bands(m, rt.Bands(c3_band_start(S), τ_aer, optics, np.full(3, float(m.ϖ_Cabannes))))
+
+
+def make_mie_band_scene(nStokes: int, l_trunc: int, Nz: int, band_start, λ_bands, λ_ref: float = 0.76, r_m: float = 0.3, σ_g: float = 1.6,
+                        nᵣ: float = 1.3, nᵢ: float = 0.001, r_max: float = 1.0, nquad_radius: int = 37, truncation=None,
+                        computation_type=None, **kw) -> rt.vSmartMOM_Model:
+    """make_mie_scene for a band-resolved scene: one Mie aerosol (log-normal r_m, σ_g, index nᵣ + i nᵢ) whose optics are computed
+    at every band centre λ_bands and at λ_ref in one device call (scattering.band_aerosol_optics), truncated per band, with
+    τ_aer[b] = τ_ref k_b / k_ref profile; τ_ref and the profile are make_scene's aerosol column (aerosol_total and its shape)."""
+    from . import scattering as sc
+    band_start = np.asarray(band_start, dtype=np.int32)
+    m = make_scene(nStokes, l_trunc, Nz, int(band_start[-1]), **kw)
+    if not m.aerosol_optics:
+        raise ValueError("make_mie_band_scene needs aerosol_total > 0")
+    aerosol = sc.Aerosol(sc.LogNormal(math.log(r_m), math.log(σ_g)), nᵣ, nᵢ)
+    mie = sc.make_mie_model(computation_type or sc.NAI2(), aerosol, λ_ref, m.params.polarization_type, truncation or sc.δBGE(l_trunc, 2.0), r_max,
+                            nquad_radius)
+    τ_ref = float(m.τ_aer.sum())
+    optics, τ_aer = sc.band_aerosol_optics(mie, λ_bands, λ_ref, τ_ref, m.τ_aer[0] / τ_ref)
+    return rt.with_bands(m, rt.Bands(band_start, τ_aer[:, None, :], [[o] for o in optics], np.full(len(optics), float(m.ϖ_Cabannes))))
+
+
 def scene_C4(S: int = 2_000, Nz: int = 40, **kw):
     """aerosol + cloud, IQUV, 61 Gauss nodes (incl. 0.5 = cos 60°) + {1, cos 30°, μ₀ = cos 50°} = 64 streams, N = 256."""
     kw.setdefault("aerosol_total", 5.0)

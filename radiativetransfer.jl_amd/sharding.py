@@ -6,7 +6,9 @@ into contiguous slices, one per rank (one process per GPU).  The only quantities
 WHOLE axis (rt_kernel.jl:241-242, compEffectiveLayerProperties.jl:104) -- are computed by
 prepare_scene() on the global axis before slicing, so an N-way run reproduces the 1-way run bit
 for bit.  The single collective is an all-gather of the R/T spectra (RCCL over xGMI when the
-process group backend is "nccl"; gloo in the CPU tests).
+process group backend is "nccl"; gloo in the CPU tests).  A band-resolved model (corert.Bands) takes this route as it stands: its
+K = 1 + nAer nBand bases and per-point weights are ordinary SceneInputs, and a slice may begin or end inside a band.  The device
+assembly mom_scene_set_optics_bands is not for a handle with a communicator (MOM_EUNSUPPORTED).
 
 The rotational-Raman path couples spectral points at the offsets i_λ₁λ₀ (inelastic_helper.jl:13-21): element [.., n₁, Δn]
 of the inelastic operators takes radiation from n₀ = n₁ + i_λ₁λ₀[Δn].  A shard therefore carries a HALO of
