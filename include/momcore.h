@@ -880,6 +880,36 @@ int mom_pcw_pair_averages(int device, int nR, const double *r, const double *w, 
                           double *anam_re, double *anam_im, double *anbm_re, double *anbm_im, double *bnam_re, double *bnam_im,
                           double *bnbm_re, double *bnbm_im);
 
+/* ---- Phase-matrix Fourier moments ---------------------------------------------------------------
+ * Scattering.compute_Z_moments(mod, mu, greek_coefs, m) (src/Scattering/compute_Z_matrices.jl:5-84) for a batch of nG sets of Greek
+ * coefficients and the Fourier moments m_first .. m_first + M - 1 in one call: the generalised spherical functions P, R, T of
+ * compute_associated_legendre_PRT (legendre_functions.jl:17-178) at +mu and -mu for the requested m only, then
+ * A++ = sum_l Pi_l(mu_i) B_l Pi_l(mu_j) and A-+ = sum_l Pi_l(mu_i) B_l Pi_l(-mu_j), l = m .. l_max - 1 (construct_Pi_matrix,
+ * construct_B_matrix, mie_helper_functions.jl:287-348), as one product on v_mfma_f64_16x16x4 per (set, m, sign).  Float64,
+ * handle-free like the mom_mie_* calls, error text: mom_last_global_error().  The moments are linear in the coefficients, so a
+ * set may as well hold derivatives of coefficients (negative, all zero): the Z bases of a scene and those of its Jacobian are the
+ * same call.
+ *   nStokes                 1, 3 or 4; N = nStokes n_mu
+ *   mu [n_mu]               quadrature nodes, every one in ]0, 1] (the reference's @assert); mu = 1 is an ordinary node
+ *   l_max [nG]              length of each set, 1 <= l_max[g] <= l_pad; a set with l_max[g] <= m gives an all-zero matrix
+ *   greek [l_pad, 6, nG]    l fastest, rows in the reference's order alpha, beta, gamma, delta, epsilon, zeta; entries at
+ *                           l >= l_max[g] are not used
+ *   set_inner               0 (or nG): the matrices of (set g, moment m) are stored as [N, N, nG, M], i fastest -- what mom_scene_set*
+ *                           take as Zpp / Zmp with K = nG.  A divisor K of nG: the sets are read as g = k + K p and the matrices
+ *                           are stored as [N, N, K, M, P], P = nG / K -- what mom_scene_set_partials takes as dZpp / dZmp; no
+ *                           transpose is left to the host
+ * Outputs (host):
+ *   Zpp, Zmp                Z++ and Z-+ = 2 fact A, fact = 1/2 at m = 0 and 1 otherwise, Z-+ with the sign flipped on the blocks
+ *                           (i <= 2, j >= 3) and (i >= 3, j <= 2) of the Stokes index
+ *   gpu_ms or NULL          HIP-event time (ms) of the two kernels
+ * P, R, T are bitwise the reference's (same statements, same association, no contraction); the sum over l runs in the MFMA's
+ * k order with fused multiply-adds, so Z agrees with the host's to rounding, not bitwise.  Two calls are bitwise equal, and a
+ * set's matrices do not depend on what else is in the batch or on the (m_first, M) window.
+ * MOM_EINVAL, checked before the first HIP call: nStokes not 1, 3 or 4; n_mu, nG, M or l_pad < 1; m_first < 0; an l_max[g] outside
+ * 1..l_pad; a mu outside ]0, 1]; set_inner negative or not a divisor of nG; a null pointer (gpu_ms excepted). */
+int mom_z_moments(int device, int nStokes, int n_mu, const double *mu, int nG, int l_pad, const int *l_max, const double *greek,
+                  int m_first, int M, int set_inner, double *Zpp, double *Zmp, double *gpu_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,7 +61,8 @@ layer optics in the library's native input form (K phase-matrix bases + per-poin
 array of expandOpticalProperties, compEffectiveLayerProperties.jl:124-135), doubling numbers, interface codes,
 surface.  Returns the handle with everything resident in HBM.
 """
-function momcore_scene(RS_type, model::vSmartMOM_Model, iBand, arch::MI355X; strict_reference_indexing::Bool = true, split = nothing)
+function momcore_scene(RS_type, model::vSmartMOM_Model, iBand, arch::MI355X; strict_reference_indexing::Bool = true, split = nothing,
+                       z_moments_on_device::Bool = false)
     @unpack qp_μ, qp_μN, wt_μN, iμ₀, μ₀ = model.quad_points
     pol   = model.params.polarization_type
     max_m = model.params.max_m
@@ -71,7 +72,7 @@ function momcore_scene(RS_type, model::vSmartMOM_Model, iBand, arch::MI355X; str
     ifaces, τ_sum = extractEffectiveProps(props, model.quad_points)
     nd    = Cint[get_dtau_ndoubl(l, model.quad_points)[2] for l in props]                  # GLOBAL maxima (rt_kernel.jl:241)
     τ     = reduce(hcat, [l.τ for l in props]);  ϖ = reduce(hcat, [l.ϖ for l in props])   # [nSpec, Nz]
-    Zpp, Zmp, zw = z_bases_and_weights(RS_type, iBand, model)                              # [N,N,K,M] ×2, [K,nSpec,Nz]
+    Zpp, Zmp, zw = z_bases_and_weights(RS_type, iBand, model; z_moments_on_device)         # [N,N,K,M] ×2, [K,nSpec,Nz]
     node  = Cint[nearest_point(qp_μ, cosd(v)) for v in model.obs_geom.vza]
     cosm  = [cosd(m * a) for a in model.obs_geom.vaz, m in 0:max_m-1]
     sinm  = [sind(m * a) for a in model.obs_geom.vaz, m in 0:max_m-1]
@@ -200,12 +201,12 @@ function rt_run(RS_type::RRS, model::vSmartMOM_Model, iBand, arch::MI355X; rrs_s
     end
 end
 
-function momcore_scene_rrs(RS_type::RRS, model, iBand, arch::MI355X, strict::Bool; shard = nothing)
+function momcore_scene_rrs(RS_type::RRS, model, iBand, arch::MI355X, strict::Bool; shard = nothing, z_moments_on_device::Bool = false)
     pol, max_m = model.params.polarization_type, model.params.max_m
     qp_μ = model.quad_points.qp_μ
     # the elastic scene exactly as for noRS (the Rayleigh ϖ is RS_type.ϖ_Cabannes, compEffectiveLayerProperties.jl:27);
     # the Raman layers are allocated for the unpadded operator edge
-    h = momcore_scene(RS_type, model, iBand, arch)
+    h = momcore_scene(RS_type, model, iBand, arch; z_moments_on_device)
     MomCore.mom_set_option!(h.ptr, MomCore.MOM_OPT_STRIP_PAD, 0)
     MomCore.mom_rrs_set!(h.ptr, length(RS_type.i_λ₁λ₀), Cint.(RS_type.i_λ₁λ₀), RS_type.ϖ_λ₁λ₀, strict ? 1 : 0)
     if shard !== nothing            # (nSpec_global, wlo, lo, hi), 0-based owned slice [lo, hi) of the window starting at wlo
@@ -216,8 +217,13 @@ function momcore_scene_rrs(RS_type::RRS, model, iBand, arch::MI355X, strict::Boo
     # matrices of every Fourier moment (computeRamanZλ!, inelastic_helper.jl:457-464)
     fScattRayleigh = constructCoreOpticalProperties(RS_type, iBand, 0, model)[2]
     fsc  = reduce(hcat, [expandBandScalars(RS_type, f) for f in fScattRayleigh])
-    Zr   = [Scattering.compute_Z_moments(pol, Array(qp_μ), RS_type.greek_raman, m) for m in 0:max_m-1]
-    Zrpp = cat((z[1] for z in Zr)...; dims = 3);  Zrmp = cat((z[2] for z in Zr)...; dims = 3)
+    if z_moments_on_device          # all moments in one mom_z_moments call: [N, N, 1, M]
+        Zr4  = compute_Z_moments_batch(arch, pol, Array(qp_μ), [RS_type.greek_raman], max_m)
+        Zrpp = Zr4[1][:, :, 1, :];  Zrmp = Zr4[2][:, :, 1, :]
+    else
+        Zr   = [Scattering.compute_Z_moments(pol, Array(qp_μ), RS_type.greek_raman, m) for m in 0:max_m-1]
+        Zrpp = cat((z[1] for z in Zr)...; dims = 3);  Zrmp = cat((z[2] for z in Zr)...; dims = 3)
+    end
     MomCore.mom_scene_set_rrs!(h.ptr, fsc, Zrpp, Zrmp)
     return h
 end
@@ -577,3 +583,44 @@ function compute_wigner_values(arch::MI355X, m_max, n_max, l_max)
     return A, B
 end
 # <<< mie
+
+# >>> z_moments
+"""
+Scattering.compute_Z_moments(pol, μ, greek_coefs, m) (compute_Z_matrices.jl:5-84) for every set of `greeks` and the moments
+m_first : m_first + M - 1 in ONE device call: Z⁺⁺ and Z⁻⁺ as [N, N, nG, M], column-major as the ABI writes them, which is what
+mom_scene_set! takes as Zpp / Zmp with K = nG.  The sets may differ in length (Rayleigh has 3 coefficients, an aerosol l_max).
+`set_inner = K` with nG = K P sets ordered k fastest (the derivative sets of P parameters): [N, N, K, M, P], the dZpp / dZmp of
+mom_scene_set_partials!.  Off by default wherever the host layer forms Z: the keyword `z_moments_on_device` of its callers.
+"""
+function compute_Z_moments_batch(arch::MI355X, pol, μ, greeks, M; m_first = 0, set_inner = 0)
+    nG = length(greeks);  n_μ = length(μ);  N = pol.n * n_μ
+    l_max = Cint[length(g.β) for g in greeks];  l_pad = Int(maximum(l_max))
+    greek = zeros(Float64, l_pad, 6, nG)
+    for (k, g) in enumerate(greeks), (q, row) in enumerate((g.α, g.β, g.γ, g.δ, g.ϵ, g.ζ))
+        greek[1:l_max[k], q, k] .= row
+    end
+    K = set_inner == 0 ? nG : set_inner
+    dims = set_inner == 0 ? (N, N, nG, M) : (N, N, K, M, nG ÷ K)
+    Zpp = zeros(Float64, dims);  Zmp = zeros(Float64, dims);  ms = zeros(Float64, 1)
+    momcheck(MomCore.mom_z_moments(arch.device, pol.n, n_μ, collect(Float64, μ), nG, l_pad, l_max, greek, m_first, M, set_inner,
+                                   Zpp, Zmp, ms))
+    return Zpp, Zmp, ms[1]
+end
+
+"""The Z⁺⁺ / Z⁻⁺ bases of a scene, [N, N, K, M] with basis 1 = Rayleigh and then the aerosols of `aerosol_optics`: the host loop over
+(m, Greek set) of Scattering.compute_Z_moments, or with `z_moments_on_device` one compute_Z_moments_batch call."""
+function z_bases(arch::MI355X, pol, μ, greek_rayleigh, aerosol_optics, max_m; z_moments_on_device::Bool = false)
+    greeks = vcat([greek_rayleigh], [a.greek_coefs for a in aerosol_optics])
+    if z_moments_on_device
+        Zpp, Zmp, _ = compute_Z_moments_batch(arch, pol, μ, greeks, max_m)
+        return Zpp, Zmp
+    end
+    Z = [Scattering.compute_Z_moments(pol, Array(μ), g, m) for g in greeks, m in 0:max_m-1]
+    N = pol.n * length(μ)
+    Zpp = zeros(Float64, N, N, length(greeks), max_m);  Zmp = zeros(Float64, N, N, length(greeks), max_m)
+    for k in 1:length(greeks), m in 1:max_m
+        Zpp[:, :, k, m] .= Z[k, m][1];  Zmp[:, :, k, m] .= Z[k, m][2]
+    end
+    return Zpp, Zmp
+end
+# <<< z_moments

@@ -173,6 +173,7 @@ SIGNATURES = {
     "mom_mie_pcw": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, c_dp, c_dp, c_dp]),
     "mom_wigner_tables": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp]),
     "mom_pcw_pair_averages": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, C.c_double, C.c_double, C.c_double, C.c_int] + [c_dp] * 8),
+    "mom_z_moments": (C.c_int, [C.c_int, C.c_int, C.c_int, c_dp, C.c_int, C.c_int, c_ip, c_dp, C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp]),
 }
 
 _lib = None
@@ -1008,3 +1009,31 @@ def pcw_pair_averages(r, w, lam, n_r, n_i, N_max: int, device: int = 0):
     if rc != MOM_OK:
         raise MomError(rc, lib.mom_last_global_error().decode())
     return tuple(out[2 * q] + 1j * out[2 * q + 1] for q in range(4))
+
+
+def z_moments(nStokes: int, mu, greeks, M: int, m_first: int = 0, set_inner: int = 0, device: int = 0):
+    """mom_z_moments: Z⁺⁺, Z⁻⁺ of the Greek sets `greeks` (each a sequence of the six rows α, β, γ, δ, ϵ, ζ, of the set's own length)
+    at the nodes mu for the moments m_first .. m_first + M - 1.  Returns (Zpp, Zmp, gpu_ms): the ABI buffers as C arrays
+    [M, nG, N(j), N(i)] for set_inner = 0, and [P, M, K, N(j), N(i)] for set_inner = K (sets ordered g = k + K p, the dZpp / dZmp
+    layout of mom_scene_set_partials)."""
+    lib = load()
+    mu = f64(mu)
+    rows = [[f64(r) for r in g] for g in greeks]
+    nG, M, m_first, set_inner = len(rows), int(M), int(m_first), int(set_inner)
+    if mu.ndim != 1 or any(len(g) != 6 or any(r.ndim != 1 or r.shape != g[0].shape for r in g) for g in rows):
+        raise ValueError("z_moments: mu must be a vector and every Greek set six vectors of one length")
+    l_max = i32([len(g[0]) for g in rows])
+    l_pad = max(int(l_max.max()) if nG else 1, 1)
+    greek = np.zeros((max(nG, 1), 6, l_pad))
+    for k, g in enumerate(rows):
+        for q in range(6):
+            greek[k, q, :len(g[q])] = g[q]
+    N = int(nStokes) * len(mu)
+    ok = nG >= 1 and M >= 1 and N >= 1 and set_inner >= 0 and (set_inner == 0 or nG % set_inner == 0)
+    shape = ((M, nG, N, N) if set_inner == 0 else (nG // set_inner, M, set_inner, N, N)) if ok else (1,)   # a refused size is refused by the library
+    Zpp, Zmp, ms = np.empty(shape), np.empty(shape), np.zeros(1)
+    rc = lib.mom_z_moments(device, int(nStokes), len(mu), dp(mu), nG, l_pad, ip(l_max), dp(greek), m_first, M, set_inner, dp(Zpp), dp(Zmp),
+                           dp(ms))
+    if rc != MOM_OK:
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return Zpp, Zmp, float(ms[0])

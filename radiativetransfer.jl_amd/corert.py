@@ -360,6 +360,29 @@ def compute_Z_moments(pol_type: PolarizationType, μ: np.ndarray, greek: GreekCo
     return Zpp, Zmp
 
 
+def _greek_rows(greek: GreekCoefs):
+    return (greek.α, greek.β, greek.γ, greek.δ, greek.ϵ, greek.ζ)
+
+
+def compute_Z_moments_batch(pol_type: PolarizationType, μ: np.ndarray, greeks, M: int, m_first: int = 0, device: Optional[int] = None):
+    """compute_Z_moments for every Greek set of `greeks` (each of its own length) and the moments m_first .. m_first + M - 1:
+    (Zpp, Zmp), each [M, len(greeks), N, N].  device=None: the host function, call by call (the twin); an int: ONE
+    mom_z_moments call on that device."""
+    greeks = list(greeks)
+    if device is None:
+        Z = [[compute_Z_moments(pol_type, μ, g, m) for g in greeks] for m in range(m_first, m_first + M)]
+        N = pol_type.n * np.asarray(μ).size
+        return (np.array([[z[0] for z in row] for row in Z]).reshape(M, len(greeks), N, N),
+                np.array([[z[1] for z in row] for row in Z]).reshape(M, len(greeks), N, N))
+    Zpp, Zmp, _ = _lib.z_moments(pol_type.n, μ, [_greek_rows(g) for g in greeks], M, m_first=m_first, device=int(device))
+    return np.ascontiguousarray(np.swapaxes(Zpp, -1, -2)), np.ascontiguousarray(np.swapaxes(Zmp, -1, -2))
+
+
+def z_moments_device(params) -> Optional[int]:
+    """the device of compute_Z_moments_batch for a model's parameters: None (host) unless params.z_moments_on_device"""
+    return int(params.architecture.device) if params.z_moments_on_device else None
+
+
 # ------------------------------------------------------------------------------------------
 # Surface types (types.jl:300-344) and their Fourier-moment reflectance matrices
 # ------------------------------------------------------------------------------------------
@@ -501,6 +524,7 @@ class vSmartMOM_Parameters:
     brdf: Optional[object] = None  # any surface type above; None = LambertianSurfaceScalar(brdf_albedo)
     architecture: AbstractArchitecture = field(default_factory=default_architecture)
     strict_reference_indexing: bool = True
+    z_moments_on_device: bool = False  # z_bases / raman_z through mom_z_moments on architecture.device instead of the host loop
 
 
 @dataclass
@@ -707,12 +731,9 @@ def z_bases(model: vSmartMOM_Model):
     pol, μ = model.params.polarization_type, model.quad_points.qp_μ
     if model.bands is not None:
         greeks = [model.greek_rayleigh] + [a.greek_coefs for band in model.bands.aerosol_optics for a in band]
-        Z = [[compute_Z_moments(pol, μ, g, m) for g in greeks] for m in range(model.params.max_m)]
-        return np.array([[z[0] for z in row] for row in Z]), np.array([[z[1] for z in row] for row in Z])
-    greeks = [model.greek_rayleigh] + [a.greek_coefs for a in model.aerosol_optics]
-    Zpp = np.array([[compute_Z_moments(pol, μ, g, m)[0] for g in greeks] for m in range(model.params.max_m)])
-    Zmp = np.array([[compute_Z_moments(pol, μ, g, m)[1] for g in greeks] for m in range(model.params.max_m)])
-    return Zpp, Zmp
+    else:
+        greeks = [model.greek_rayleigh] + [a.greek_coefs for a in model.aerosol_optics]
+    return compute_Z_moments_batch(pol, μ, greeks, model.params.max_m, device=z_moments_device(model.params))
 
 
 def _abi_mats(Z: np.ndarray) -> np.ndarray:
@@ -1109,8 +1130,8 @@ def fscatt_rayleigh(model: vSmartMOM_Model) -> np.ndarray:
 def raman_z(RS_type: RRS, model: vSmartMOM_Model):
     """computeRamanZλ! (src/Inelastic/inelastic_helper.jl:457-464) for m = 0..max_m-1: Z⁺⁺_λ₁λ₀, Z⁻⁺_λ₁λ₀ [M, N, N]."""
     pol, μ = model.params.polarization_type, model.quad_points.qp_μ
-    Z = [compute_Z_moments(pol, μ, RS_type.greek_raman, m) for m in range(model.params.max_m)]
-    return np.array([z[0] for z in Z]), np.array([z[1] for z in Z])
+    Zpp, Zmp = compute_Z_moments_batch(pol, μ, [RS_type.greek_raman], model.params.max_m, device=z_moments_device(model.params))
+    return Zpp[:, 0], Zmp[:, 0]
 
 
 def _with_cabannes(RS_type: RRS, model: vSmartMOM_Model) -> vSmartMOM_Model:

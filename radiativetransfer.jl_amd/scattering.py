@@ -471,7 +471,8 @@ def truncate_phase(mod: δBGE, aero: rt.AerosolOptics, partials=None):
     return out, d_out
 
 
-def aerosol_optics_partial(model: rt.vSmartMOM_Model, i_aer: int, d_optics: rt.AerosolOptics, dτ_aer=None, band: Optional[int] = None) -> rt.OpticsPartial:
+def aerosol_optics_partial(model: rt.vSmartMOM_Model, i_aer: int, d_optics: rt.AerosolOptics, dτ_aer=None, band: Optional[int] = None,
+                           device: Optional[int] = None) -> rt.OpticsPartial:
     """The OpticsPartial of one parameter of aerosol i_aer (0-based) of the scene `model`, from ∂(aerosol optics)/∂θ as
     truncate_phase(..., partials=) returns it: dω̃ and dfᵗ at i_aer, dZpp / dZmp = compute_Z_moments of the derivative Greek
     coefficients (the moments are linear in them) at basis 1 + i_aer (basis 0 is Rayleigh), zeros elsewhere.  dτ_aer [nAer, Nz]
@@ -479,28 +480,44 @@ def aerosol_optics_partial(model: rt.vSmartMOM_Model, i_aer: int, d_optics: rt.A
     into rt_run_dual_device_optics.
     A model with bands: `band` (0-based) names the band whose aerosol i_aer the partial belongs to; dω̃ / dfᵗ [nBand, nAer] and
     dZpp / dZmp [M, 1 + nAer nBand, N, N] are nonzero in that band's entries and basis 1 + i_aer + nAer band only, and dτ_aer
-    [nBand, nAer, Nz] is passed on.  A parameter shared by several bands is the sum of its per-band partials (sum_partials)."""
+    [nBand, nAer, Nz] is passed on.  A parameter shared by several bands is the sum of its per-band partials (sum_partials).
+    device: None forms the M derivative matrices on the host, an int in one mom_z_moments call on that device."""
+    return aerosol_optics_partials(model, [(i_aer, d_optics, dτ_aer, band)], device=device)[0]
+
+
+def aerosol_optics_partials(model: rt.vSmartMOM_Model, items, device: Optional[int] = None):
+    """aerosol_optics_partial for every (i_aer, d_optics, dτ_aer, band) of `items`: the list of their OpticsPartials, with the
+    derivative sets of ALL items and all moments formed in one compute_Z_moments_batch call -- with an int `device`, one
+    mom_z_moments call; with None, the host function per (item, moment), bitwise what aerosol_optics_partial gives per item."""
+    items = list(items)
     bands = model.bands
-    if (band is None) != (bands is None):
-        raise ValueError("`band` goes with a model that has bands, and only with one")
     nAer = len(model.aerosol_optics) if bands is None else bands.nAer
-    if not 0 <= i_aer < nAer:
-        raise ValueError(f"i_aer = {i_aer} outside the model's {nAer} aerosols")
-    if bands is not None and not 0 <= band < bands.nBand:
-        raise ValueError(f"band = {band} outside the model's {bands.nBand} bands")
     pol, μ, M = model.params.polarization_type, model.quad_points.qp_μ, model.params.max_m
-    aero = model.aerosol_optics[i_aer] if bands is None else bands.aerosol_optics[band][i_aer]
-    if len(d_optics.greek_coefs.β) != len(aero.greek_coefs.β):
-        raise ValueError("the derivative Greek coefficients do not have the length of the aerosol's")
+    for i_aer, d_optics, _, band in items:
+        if (band is None) != (bands is None):
+            raise ValueError("`band` goes with a model that has bands, and only with one")
+        if not 0 <= i_aer < nAer:
+            raise ValueError(f"i_aer = {i_aer} outside the model's {nAer} aerosols")
+        if bands is not None and not 0 <= band < bands.nBand:
+            raise ValueError(f"band = {band} outside the model's {bands.nBand} bands")
+        aero = model.aerosol_optics[i_aer] if bands is None else bands.aerosol_optics[band][i_aer]
+        if len(d_optics.greek_coefs.β) != len(aero.greek_coefs.β):
+            raise ValueError("the derivative Greek coefficients do not have the length of the aerosol's")
+    if not items:
+        return []
+    Zp, Zm = rt.compute_Z_moments_batch(pol, μ, [it[1].greek_coefs for it in items], M, device=device)  # [M, len(items), N, N]
     N = pol.n * len(μ)
-    K, k = (1 + nAer, 1 + i_aer) if bands is None else (1 + nAer * bands.nBand, 1 + i_aer + nAer * band)
-    dZpp, dZmp = np.zeros((M, K, N, N)), np.zeros((M, K, N, N))
-    for m in range(M):
-        dZpp[m, k], dZmp[m, k] = rt.compute_Z_moments(pol, μ, d_optics.greek_coefs, m)[:2]
-    shape, at = ((nAer,), i_aer) if bands is None else ((bands.nBand, nAer), (band, i_aer))
-    dω̃, dfᵗ = np.zeros(shape), np.zeros(shape)
-    dω̃[at], dfᵗ[at] = d_optics.ω̃, d_optics.fᵗ
-    return rt.OpticsPartial(dτ_aer=None if dτ_aer is None else np.asarray(dτ_aer, dtype=np.float64), dω̃=dω̃, dfᵗ=dfᵗ, dZpp=dZpp, dZmp=dZmp)
+    out = []
+    for j, (i_aer, d_optics, dτ_aer, band) in enumerate(items):
+        K, k = (1 + nAer, 1 + i_aer) if bands is None else (1 + nAer * bands.nBand, 1 + i_aer + nAer * band)
+        dZpp, dZmp = np.zeros((M, K, N, N)), np.zeros((M, K, N, N))
+        dZpp[:, k], dZmp[:, k] = Zp[:, j], Zm[:, j]
+        shape, at = ((nAer,), i_aer) if bands is None else ((bands.nBand, nAer), (band, i_aer))
+        dω̃, dfᵗ = np.zeros(shape), np.zeros(shape)
+        dω̃[at], dfᵗ[at] = d_optics.ω̃, d_optics.fᵗ
+        out.append(rt.OpticsPartial(dτ_aer=None if dτ_aer is None else np.asarray(dτ_aer, dtype=np.float64), dω̃=dω̃, dfᵗ=dfᵗ, dZpp=dZpp,
+                                    dZmp=dZmp))
+    return out
 
 
 def sum_partials(partials) -> rt.OpticsPartial:
