@@ -8,7 +8,12 @@ derivative sets).  Per leg: the HIP-event time of the two kernels, the wall time
 host twin (device=None), both medians, and the contraction's share of the FP64 MFMA peak by its own operation count
 2 * 2 * N^2 * n * sum over (set, m) of max(l_max - m, 0) over the event time (which includes the recurrence kernel).  For the C2
 and C4 models also z_bases as the parent commit ran it (every (m, set) pair computed twice on the host) beside z_bases with
-z_moments_on_device, in the same process on the same machine."""
+z_moments_on_device, in the same process on the same machine.
+
+`--resident [OUT.json]` runs another leg instead and leaves the default output alone (committed as profiles/z_resident_bench.json):
+for the C2 and C4 models the wall time from Greek coefficients to a set scene -- z_bases plus mom_scene_set, ended by a mom_sync,
+median of 5, one handle, one process -- on three routes: Z on the host, Z by mom_z_moments and back through the host setter (the
+round trip), and the staged Greek sets with the bases formed in the handle's memory (params.z_resident)."""
 import dataclasses
 import json
 import statistics
@@ -79,6 +84,39 @@ def run_model(rtamd, model, host_repeats):
             "device_faster_than_parent": bool(dev_ms < par_ms)}
 
 
+def run_resident(repeats=5):
+    import rtamd
+    rt = rtamd.corert
+    out = {"metric": "Greek coefficients to a set scene at the C4 shape (n = 4, 64 nodes, l_max = 121, M = 3): wall time of the resident route",
+           "unit": "ms"}
+    for name, m in (("C2", rtamd.scenes.scene_C2(S=8, Nz=2)), ("C4", rtamd.scenes.scene_C4(S=4, Nz=2))):
+        sc = rt.prepare_scene(m)
+        md = dataclasses.replace(m, params=dataclasses.replace(m.params, z_moments_on_device=True))
+
+        def uploaded(h, model):
+            Zpp, Zmp = rt.z_bases(model)
+            rt.scene_set(h, dataclasses.replace(sc, Zpp=rt._abi_mats(Zpp), Zmp=rt._abi_mats(Zmp)))
+            h.sync()
+
+        def resident(h):
+            rt.scene_set(h, dataclasses.replace(sc, Zpp=None, Zmp=None, greeks=rt.z_greeks(m)))
+            h.sync()
+
+        leg = {"N": sc.N, "K": sc.K, "M": sc.M, "Z_MB_each_way": 2 * 8.0 * sc.N * sc.N * sc.K * sc.M / 1e6}
+        with rt.make_handle(m) as h:
+            routes = (("host_z_ms", lambda: uploaded(h, m)), ("round_trip_device_z_ms", lambda: uploaded(h, md)), ("resident_ms", lambda: resident(h)))
+            for key, f in routes:
+                f()   # the first call loads the code objects
+                med, runs = _median_ms(f, repeats)
+                leg[key] = {"median": med, "runs": runs}
+        leg["speedup_vs_round_trip"] = leg["round_trip_device_z_ms"]["median"] / leg["resident_ms"]["median"]
+        leg["resident_faster_than_round_trip"] = bool(leg["resident_ms"]["median"] < leg["round_trip_device_z_ms"]["median"])
+        out[name] = leg
+    out["value"] = out["C4"]["resident_ms"]["median"]
+    out["done"] = bool(out["C2"]["resident_faster_than_round_trip"] and out["C4"]["resident_faster_than_round_trip"])
+    return out
+
+
 def run(host_repeats=3):
     import rtamd
     rt = rtamd.corert
@@ -105,7 +143,11 @@ if __name__ == "__main__":
         i = argv.index("--host-repeats")
         repeats = int(argv[i + 1])
         del argv[i:i + 2]
-    res = run(repeats)
+    if "--resident" in argv:
+        argv.remove("--resident")
+        res = run_resident()
+    else:
+        res = run(repeats)
     if argv:
         Path(argv[0]).parent.mkdir(parents=True, exist_ok=True)
         Path(argv[0]).write_text(json.dumps(res, indent=1, ensure_ascii=False) + "\n")

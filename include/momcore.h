@@ -910,6 +910,32 @@ int mom_pcw_pair_averages(int device, int nR, const double *r, const double *w, 
 int mom_z_moments(int device, int nStokes, int n_mu, const double *mu, int nG, int l_pad, const int *l_max, const double *greek,
                   int m_first, int M, int set_inner, double *Zpp, double *Zmp, double *gpu_ms);
 
+/* ---- Scenes from Greek coefficients (Float64 handles) ----------------------------------------------
+ * The Z bases of a scene formed in the handle's own memory: no N x N matrix crosses the bus.  The staging calls do no GPU work;
+ * they check the arguments (mom_z_moments' checks, with the handle's nStokes and one mu per stream of mom_set_streams, each in
+ * ]0, 1]) and copy them, so the caller's arrays are free when they return.  greek [l_pad, 6, nG] and l_max [nG] as in mom_z_moments.
+ *   mom_scene_stage_greeks         which = 0: the nG = K phase-matrix bases, M moments, of the next mom_scene_set / _set_optics /
+ *                                  _set_optics_bands; which = 1: the one Raman set (nG = 1) of the next mom_scene_set_rrs.
+ *   mom_scene_stage_greek_partials nD derivative sets: set d is the partial of basis basis[d] (0-based) with respect to parameter
+ *                                  partial[d] (0-based, < P); every other (basis, partial) block of dZpp / dZmp is exactly zero.  A
+ *                                  pair named twice: MOM_EINVAL.  The moments are the scene's.
+ * A setter called with Zpp == Zmp == NULL (mom_scene_set_rrs: Zpp_l1l0 == Zmp_l1l0 == NULL) takes the stage: K and M have to agree
+ * with it (MOM_EINVAL, the text names both), the bases -- padded to the kernels' edge, and where the m = 0 reduction applies cut to
+ * the (I,Q) sub-problem as well, with the (I,Q) <-> (U,V) test of that reduction made on the device -- are written by the kernels
+ * of mom_z_moments with unchanged arithmetic, and the stage is gone.  Without a stage NULL is the MOM_EINVAL it always was.
+ * mom_scene_set_partials / _set_optics_partials / _set_optics_bands_partials with dZpp == dZmp == NULL take a staged partial set
+ * (P has to agree, and every basis[d] < K); without one NULL means "no dependence" as before.  A new scene drops a partial stage
+ * that is still pending; mom_set_streams drops every stage.
+ * Float32 handle: MOM_EUNSUPPORTED; before mom_set_streams: MOM_ESTATE.
+ *   mom_scene_get_bases            the resident arrays as the kernels read them, whichever route set them: which = 0 the bases
+ *                                  [edge, edge, K, M]; 1 the (I,Q) sub-problem's [edge, edge, K] (edge = 0: the scene is not reduced);
+ *                                  2 dZpp / dZmp [edge, edge, K, M, P] (blocks = 0: none resident); 3 the Raman set [N, N, M].
+ *                                  *blocks = the product of the trailing extents.  Zpp == Zmp == NULL: a size query. */
+int mom_scene_stage_greeks(mom_t *h, int which, int nG, int l_pad, const int *l_max, const double *greek, int M);
+int mom_scene_stage_greek_partials(mom_t *h, int P, int nD, const int *basis, const int *partial, int l_pad, const int *l_max,
+                                   const double *dgreek);
+int mom_scene_get_bases(mom_t *h, int which, int *edge, int *blocks, double *Zpp, double *Zmp);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,7 +62,7 @@ array of expandOpticalProperties, compEffectiveLayerProperties.jl:124-135), doub
 surface.  Returns the handle with everything resident in HBM.
 """
 function momcore_scene(RS_type, model::vSmartMOM_Model, iBand, arch::MI355X; strict_reference_indexing::Bool = true, split = nothing,
-                       z_moments_on_device::Bool = false)
+                       z_moments_on_device::Bool = false, z_resident::Bool = false)
     @unpack qp_μ, qp_μN, wt_μN, iμ₀, μ₀ = model.quad_points
     pol   = model.params.polarization_type
     max_m = model.params.max_m
@@ -72,7 +72,8 @@ function momcore_scene(RS_type, model::vSmartMOM_Model, iBand, arch::MI355X; str
     ifaces, τ_sum = extractEffectiveProps(props, model.quad_points)
     nd    = Cint[get_dtau_ndoubl(l, model.quad_points)[2] for l in props]                  # GLOBAL maxima (rt_kernel.jl:241)
     τ     = reduce(hcat, [l.τ for l in props]);  ϖ = reduce(hcat, [l.ϖ for l in props])   # [nSpec, Nz]
-    Zpp, Zmp, zw = z_bases_and_weights(RS_type, iBand, model; z_moments_on_device)         # [N,N,K,M] ×2, [K,nSpec,Nz]
+    # [N,N,K,M] ×2, [K,nSpec,Nz]; z_resident: Zpp = Zmp = nothing -- the handle forms the bases from the Greek sets (stage_greeks!)
+    Zpp, Zmp, zw = z_bases_and_weights(RS_type, iBand, model; z_moments_on_device, z_resident)
     node  = Cint[nearest_point(qp_μ, cosd(v)) for v in model.obs_geom.vza]
     cosm  = [cosd(m * a) for a in model.obs_geom.vaz, m in 0:max_m-1]
     sinm  = [sind(m * a) for a in model.obs_geom.vaz, m in 0:max_m-1]
@@ -83,8 +84,10 @@ function momcore_scene(RS_type, model::vSmartMOM_Model, iBand, arch::MI355X; str
     h = MomHandle(arch, N, pol.n, nSpec, max_m; float_type = model.params.float_type)
     MomCore.mom_set_streams!(h.ptr, qp_μN, wt_μN, N, iμ₀, μ₀, pol.I₀, pol.D, strict_reference_indexing ? 1 : 0)
     albedo = brdf isa LambertianSurfaceScalar ? brdf.albedo : zero(eltype(τ))
-    MomCore.mom_scene_set!(h.ptr, length(nd), size(zw, 1), max_m, val(τ), val(ϖ), val(zw), val(Zpp), val(Zmp), nd,
-                           iface_code.(ifaces), val(τ_sum), Float64(val([albedo])[1]), length(node), node, cosm, sinm)
+    z_resident && stage_greeks!(h, scene_greeks(model, iBand), max_m)      # then Zpp = Zmp = C_NULL below: "the staged bases"
+    MomCore.mom_scene_set!(h.ptr, length(nd), size(zw, 1), max_m, val(τ), val(ϖ), val(zw), z_resident ? C_NULL : val(Zpp),
+                           z_resident ? C_NULL : val(Zmp), nd, iface_code.(ifaces), val(τ_sum), Float64(val([albedo])[1]), length(node),
+                           node, cosm, sinm)
     dRsurf = dalb = nothing
     if brdf isa LambertianSurfaceLegendre                       # lambertian_surface.jl:90-96: spectral albedo
         alb = legendre_albedo(brdf, model, iBand)
@@ -94,7 +97,8 @@ function momcore_scene(RS_type, model::vSmartMOM_Model, iBand, arch::MI355X; str
         MomCore.mom_scene_set_surface!(h.ptr, 1, max_m, val(Rsurf), C_NULL);  dRsurf = part(Rsurf)
     end
     split === nothing && return h
-    return h, (dτ = part(τ), dϖ = part(ϖ), dzw = part(zw), dZpp = part(Zpp), dZmp = part(Zmp), dalbedo = part([albedo]),
+    return h, (dτ = part(τ), dϖ = part(ϖ), dzw = part(zw), dZpp = z_resident ? nothing : part(Zpp),
+               dZmp = z_resident ? nothing : part(Zmp), dalbedo = part([albedo]),
                dRsurf = dRsurf, dalbedo_spec = dalb)
 end
 # <<< scene
@@ -624,3 +628,37 @@ function z_bases(arch::MI355X, pol, μ, greek_rayleigh, aerosol_optics, max_m; z
     return Zpp, Zmp
 end
 # <<< z_moments
+
+# >>> z_resident
+"""
+Scenes from Greek coefficients: the staged call sequence.  The Greek sets of the K bases (Rayleigh, then the aerosols) go to the
+handle, which copies them; the setter that follows is called with Zpp = Zmp = C_NULL and forms the bases in its own memory with the
+kernels of mom_z_moments -- padded to the kernels' edge, cut to the (I,Q) sub-problem where moment 0 decouples, the decoupling test
+made on the device.  No N × N matrix is built on the host or crosses the bus.  `which = 1` stages the one Raman set that
+mom_scene_set_rrs!(h, fscatt, C_NULL, C_NULL) takes.  The keyword `z_resident` of momcore_scene selects the sequence.
+"""
+function stage_greeks!(h::MomHandle, greeks, M; which = 0)
+    nG = length(greeks)
+    l_max = Cint[length(g.β) for g in greeks];  l_pad = Int(maximum(l_max))
+    greek = zeros(Float64, l_pad, 6, nG)
+    for (k, g) in enumerate(greeks), (q, row) in enumerate((g.α, g.β, g.γ, g.δ, g.ϵ, g.ζ))
+        greek[1:l_max[k], q, k] .= row
+    end
+    MomCore.mom_scene_stage_greeks!(h.ptr, which, nG, l_pad, l_max, greek, M)
+end
+
+"""Derivative sets for the Dual run: `pairs` = [((k, p), dgreek), ...], 0-based basis k and parameter p < P; the partial setter that
+follows is called with dZpp = dZmp = C_NULL."""
+function stage_greek_partials!(h::MomHandle, P, pairs)
+    nD = length(pairs)
+    l_max = Cint[length(g.β) for (_, g) in pairs];  l_pad = Int(maximum(l_max))
+    dgreek = zeros(Float64, l_pad, 6, nD)
+    for (d, (_, g)) in enumerate(pairs), (q, row) in enumerate((g.α, g.β, g.γ, g.δ, g.ϵ, g.ζ))
+        dgreek[1:l_max[d], q, d] .= row
+    end
+    MomCore.mom_scene_stage_greek_partials!(h.ptr, P, nD, Cint[kp[1] for (kp, _) in pairs], Cint[kp[2] for (kp, _) in pairs], l_pad,
+                                            l_max, dgreek)
+end
+
+scene_greeks(model, iBand) = vcat([model.greek_rayleigh], [a.greek_coefs for a in model.aerosol_optics[iBand[1]]])
+# <<< z_resident

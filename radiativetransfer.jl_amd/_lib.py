@@ -174,6 +174,9 @@ SIGNATURES = {
     "mom_wigner_tables": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp]),
     "mom_pcw_pair_averages": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, C.c_double, C.c_double, C.c_double, C.c_int] + [c_dp] * 8),
     "mom_z_moments": (C.c_int, [C.c_int, C.c_int, C.c_int, c_dp, C.c_int, C.c_int, c_ip, c_dp, C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp]),
+    "mom_scene_stage_greeks": (C.c_int, [c_h, C.c_int, C.c_int, C.c_int, c_ip, c_dp, C.c_int]),
+    "mom_scene_stage_greek_partials": (C.c_int, [c_h, C.c_int, C.c_int, c_ip, c_ip, C.c_int, c_ip, c_dp]),
+    "mom_scene_get_bases": (C.c_int, [c_h, C.c_int, c_ip, c_ip, c_dp, c_dp]),
 }
 
 _lib = None
@@ -352,8 +355,8 @@ class Handle:
         return out
 
     def scene_set_rrs(self, fscatt, Zpp_l1l0, Zmp_l1l0):
-        a = [f64(x).reshape(-1) for x in (fscatt, Zpp_l1l0, Zmp_l1l0)]
-        self.check(self.lib.mom_scene_set_rrs(self._h, *[dp(x) for x in a]))
+        a = [None if x is None else f64(x).reshape(-1) for x in (fscatt, Zpp_l1l0, Zmp_l1l0)]   # Z None: the staged Raman set
+        self.check(self.lib.mom_scene_set_rrs(self._h, *[None if x is None else dp(x) for x in a]))
 
     def rt_run_rrs(self):
         self.check(self.lib.mom_rt_run_rrs(self._h))
@@ -424,12 +427,12 @@ class Handle:
         return Cm, dC
 
     def scene_set(self, Nz, K, M, tau, varpi, zw, Zpp, Zmp, nd, iface, tau_sum, albedo, node, cos_mphi, sin_mphi):
-        d = [f64(x).reshape(-1) for x in (tau, varpi, zw, Zpp, Zmp)]
+        d = [None if x is None else f64(x).reshape(-1) for x in (tau, varpi, zw, Zpp, Zmp)]   # Zpp, Zmp None: the staged bases
         nd, iface, node = i32(nd), i32(iface), i32(node)
         ts, cm, sm = f64(tau_sum).reshape(-1), f64(cos_mphi).reshape(-1), f64(sin_mphi).reshape(-1)
         self.nVza = len(node)
         self._Nz, self._K = int(Nz), int(K)
-        self.check(self.lib.mom_scene_set(self._h, int(Nz), int(K), int(M), *[dp(x) for x in d], ip(nd), ip(iface),
+        self.check(self.lib.mom_scene_set(self._h, int(Nz), int(K), int(M), *[None if x is None else dp(x) for x in d], ip(nd), ip(iface),
                                           dp(ts), float(albedo), len(node), ip(node), dp(cm), dp(sm)))
 
     # -- device-side layer optics --------------------------------------------------------------
@@ -615,13 +618,13 @@ class Handle:
         nAer = ta.shape[0] if ta.size else 0
         taf = np.ascontiguousarray(ta.T).reshape(-1) if nAer else np.zeros(1)  # [nAer, Nz] column-major
         om, ft = (f64(omega_aer), f64(ft_aer)) if nAer else (np.zeros(1), np.zeros(1))
-        zp, zm = f64(Zpp).reshape(-1), f64(Zmp).reshape(-1)
+        zp, zm = (None if z is None else dp(f64(z).reshape(-1)) for z in (Zpp, Zmp))   # None: the staged bases
         node = i32(node)
         cm, sm = f64(cos_mphi).reshape(-1), f64(sin_mphi).reshape(-1)
         self.nVza = len(node)
         self._Nz, self._K = int(Nz), 1 + nAer
         self.check(self.lib.mom_scene_set_optics(self._h, int(Nz), nAer, int(M), dp(tr), float(varpi_rayl), dp(taf), dp(om),
-                                                 dp(ft), dp(zp), dp(zm), float(albedo), len(node), ip(node), dp(cm), dp(sm)))
+                                                 dp(ft), zp, zm, float(albedo), len(node), ip(node), dp(cm), dp(sm)))
 
     def scene_set_optics_bands(self, Nz, M, band_start, tau_rayl, varpi_rayl, tau_aer, omega_aer, ft_aer, Zpp, Zmp, albedo, node,
                                cos_mphi, sin_mphi):
@@ -636,13 +639,39 @@ class Handle:
         taf = np.ascontiguousarray(ta.transpose(0, 2, 1)).reshape(-1) if nAer else np.zeros(1)  # [nAer, Nz, nBand], iAer fastest
         om, ft = (f64(omega_aer).reshape(-1), f64(ft_aer).reshape(-1)) if nAer else (np.zeros(1), np.zeros(1))
         assert vr.size == max(nBand, 1) and (not nAer or (ta.shape[0] == nBand and om.size == ft.size == nBand * nAer))
-        zp, zm = f64(Zpp).reshape(-1), f64(Zmp).reshape(-1)
+        zp, zm = (None if z is None else dp(f64(z).reshape(-1)) for z in (Zpp, Zmp))   # None: the staged bases
         node = i32(node)
         cm, sm = f64(cos_mphi).reshape(-1), f64(sin_mphi).reshape(-1)
         self.nVza = len(node)
         self._Nz, self._K = int(Nz), 1 + nAer * nBand
         self.check(self.lib.mom_scene_set_optics_bands(self._h, int(Nz), nAer, nBand, ip(bs), int(M), dp(tr), dp(vr), dp(taf), dp(om),
-                                                       dp(ft), dp(zp), dp(zm), float(albedo), len(node), ip(node), dp(cm), dp(sm)))
+                                                       dp(ft), zp, zm, float(albedo), len(node), ip(node), dp(cm), dp(sm)))
+
+    # -- scenes from Greek coefficients: the Z bases formed in the handle's memory ------------------------
+    def scene_stage_greeks(self, greeks, M, which=0):
+        """mom_scene_stage_greeks: `greeks` as in z_moments (each set the six rows α, β, γ, δ, ϵ, ζ of its own length).  which = 0: the
+        bases of the next scene setter called with Zpp = Zmp = None; 1: the one Raman set of the next scene_set_rrs."""
+        nG, l_pad, l_max, greek = pack_greeks(greeks, "scene_stage_greeks")
+        self.check(self.lib.mom_scene_stage_greeks(self._h, int(which), nG, l_pad, ip(l_max), dp(greek), int(M)))
+
+    def scene_stage_greek_partials(self, P, pairs):
+        """mom_scene_stage_greek_partials: `pairs` is a sequence of ((basis k, partial p), derivative Greek set); the next partial
+        setter called with dZpp = dZmp = None and this P takes them."""
+        nD, l_pad, l_max, greek = pack_greeks([g for _, g in pairs], "scene_stage_greek_partials")
+        basis, partial = i32([kp[0] for kp, _ in pairs]), i32([kp[1] for kp, _ in pairs])
+        self.check(self.lib.mom_scene_stage_greek_partials(self._h, int(P), nD, ip(basis), ip(partial), l_pad, ip(l_max), dp(greek)))
+
+    def scene_get_bases(self, which=0):
+        """mom_scene_get_bases: (edge, Zpp, Zmp) as the kernels read them, C arrays [blocks, edge(j), edge(i)] -- which = 0 the bases
+        (blocks = M K, k fastest), 1 the (I,Q) sub-problem's (blocks = K; edge 0 and empty arrays when the scene is not reduced), 2 the
+        resident dZ (blocks = P M K), 3 the Raman set (blocks = M)."""
+        e, b = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+        self.check(self.lib.mom_scene_get_bases(self._h, int(which), ip(e), ip(b), None, None))
+        edge, blocks = int(e[0]), int(b[0])
+        Zpp, Zmp = np.empty((blocks, edge, edge)), np.empty((blocks, edge, edge))
+        if Zpp.size:
+            self.check(self.lib.mom_scene_get_bases(self._h, int(which), ip(e), ip(b), dp(Zpp), dp(Zmp)))
+        return edge, Zpp, Zmp
 
     def scene_get_layers(self, Nz, K, arrays=True):
         nd, iface = np.zeros(Nz, dtype=np.int32), np.zeros(Nz, dtype=np.int32)
@@ -1011,6 +1040,21 @@ def pcw_pair_averages(r, w, lam, n_r, n_i, N_max: int, device: int = 0):
     return tuple(out[2 * q] + 1j * out[2 * q + 1] for q in range(4))
 
 
+def pack_greeks(greeks, fn: str):
+    """Greek sets (each six vectors α, β, γ, δ, ϵ, ζ of the set's own length) as the ABI's (nG, l_pad, l_max [nG], greek [nG, 6, l_pad])."""
+    rows = [[f64(r) for r in g] for g in greeks]
+    if any(len(g) != 6 or any(r.ndim != 1 or r.shape != g[0].shape for r in g) for g in rows):
+        raise ValueError(f"{fn}: mu must be a vector and every Greek set six vectors of one length")
+    nG = len(rows)
+    l_max = i32([len(g[0]) for g in rows])
+    l_pad = max(int(l_max.max()) if nG else 1, 1)
+    greek = np.zeros((max(nG, 1), 6, l_pad))
+    for k, g in enumerate(rows):
+        for q in range(6):
+            greek[k, q, :len(g[q])] = g[q]
+    return nG, l_pad, l_max, greek
+
+
 def z_moments(nStokes: int, mu, greeks, M: int, m_first: int = 0, set_inner: int = 0, device: int = 0):
     """mom_z_moments: Z⁺⁺, Z⁻⁺ of the Greek sets `greeks` (each a sequence of the six rows α, β, γ, δ, ϵ, ζ, of the set's own length)
     at the nodes mu for the moments m_first .. m_first + M - 1.  Returns (Zpp, Zmp, gpu_ms): the ABI buffers as C arrays
@@ -1020,14 +1064,9 @@ def z_moments(nStokes: int, mu, greeks, M: int, m_first: int = 0, set_inner: int
     mu = f64(mu)
     rows = [[f64(r) for r in g] for g in greeks]
     nG, M, m_first, set_inner = len(rows), int(M), int(m_first), int(set_inner)
-    if mu.ndim != 1 or any(len(g) != 6 or any(r.ndim != 1 or r.shape != g[0].shape for r in g) for g in rows):
+    if mu.ndim != 1:
         raise ValueError("z_moments: mu must be a vector and every Greek set six vectors of one length")
-    l_max = i32([len(g[0]) for g in rows])
-    l_pad = max(int(l_max.max()) if nG else 1, 1)
-    greek = np.zeros((max(nG, 1), 6, l_pad))
-    for k, g in enumerate(rows):
-        for q in range(6):
-            greek[k, q, :len(g[q])] = g[q]
+    _, l_pad, l_max, greek = pack_greeks(rows, "z_moments")
     N = int(nStokes) * len(mu)
     ok = nG >= 1 and M >= 1 and N >= 1 and set_inner >= 0 and (set_inner == 0 or nG % set_inner == 0)
     shape = ((M, nG, N, N) if set_inner == 0 else (nG // set_inner, M, set_inner, N, N)) if ok else (1,)   # a refused size is refused by the library

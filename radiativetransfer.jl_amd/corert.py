@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -524,6 +524,8 @@ class vSmartMOM_Parameters:
     brdf: Optional[object] = None  # any surface type above; None = LambertianSurfaceScalar(brdf_albedo)
     architecture: AbstractArchitecture = field(default_factory=default_architecture)
     strict_reference_indexing: bool = True
+    z_resident: bool = False  # the Z bases are formed in the handle's memory from staged Greek sets (mom_scene_stage_greeks): no
+                              # matrix is built on the host or crosses the bus; prepare_scene leaves SceneInputs.Zpp / Zmp None
     z_moments_on_device: bool = False  # z_bases / raman_z through mom_z_moments on architecture.device instead of the host loop
 
 
@@ -725,15 +727,23 @@ def construct_layer_inputs(model: vSmartMOM_Model) -> LayerInputs:
     return LayerInputs(τ, ϖ, zw, nd, iface, τ_sum)
 
 
-def z_bases(model: vSmartMOM_Model):
-    """Z⁺⁺/Z⁻⁺ bases [M, K, N, N] (k = 0 Rayleigh, then aerosols) for m = 0..max_m-1.  With model.bands: K = 1 + nAer nBand,
-    basis 1 + x + nAer b = aerosol type x of band b, each (m, Greek set) computed once."""
-    pol, μ = model.params.polarization_type, model.quad_points.qp_μ
+def z_greeks(model: vSmartMOM_Model) -> List[GreekCoefs]:
+    """The Greek sets of the model's K phase-matrix bases (k = 0 Rayleigh, then aerosols).  With model.bands: K = 1 + nAer nBand,
+    basis 1 + x + nAer b = aerosol type x of band b."""
     if model.bands is not None:
-        greeks = [model.greek_rayleigh] + [a.greek_coefs for band in model.bands.aerosol_optics for a in band]
-    else:
-        greeks = [model.greek_rayleigh] + [a.greek_coefs for a in model.aerosol_optics]
-    return compute_Z_moments_batch(pol, μ, greeks, model.params.max_m, device=z_moments_device(model.params))
+        return [model.greek_rayleigh] + [a.greek_coefs for band in model.bands.aerosol_optics for a in band]
+    return [model.greek_rayleigh] + [a.greek_coefs for a in model.aerosol_optics]
+
+
+def z_bases(model: vSmartMOM_Model):
+    """Z⁺⁺/Z⁻⁺ bases [M, K, N, N] of z_greeks(model) for m = 0..max_m-1, each (m, Greek set) computed once."""
+    pol, μ = model.params.polarization_type, model.quad_points.qp_μ
+    return compute_Z_moments_batch(pol, μ, z_greeks(model), model.params.max_m, device=z_moments_device(model.params))
+
+
+def stage_bases(h: "_lib.Handle", greeks: Sequence[GreekCoefs], M: int, which: int = 0):
+    """mom_scene_stage_greeks: the next setter called with Zpp = Zmp = None forms the bases of `greeks` in the handle's memory"""
+    h.scene_stage_greeks([_greek_rows(g) for g in greeks], M, which=which)
 
 
 def _abi_mats(Z: np.ndarray) -> np.ndarray:
@@ -778,6 +788,7 @@ class SceneInputs:
     surf_kind: int = 0
     Rsurf: Optional[np.ndarray] = None        # ABI order [N, N, M]
     albedo_spec: Optional[np.ndarray] = None  # [S]
+    greeks: Optional[List[GreekCoefs]] = None  # params.z_resident: the K Greek sets in place of Zpp / Zmp (both None then)
 
     def spectral_slice(self, lo: int, hi: int) -> "SceneInputs":
         """Shard [lo, hi) of the spectral axis.  ndoubl / iface stay the GLOBAL ones
@@ -791,14 +802,14 @@ class SceneInputs:
                            self.Zpp, self.Zmp, self.ndoubl, self.iface,
                            np.ascontiguousarray(self.tau_sum.reshape(Nz + 1, S)[:, sl]).reshape(-1),
                            self.albedo, self.node, self.cos_mphi, self.sin_mphi, self.surf_kind, self.Rsurf,
-                           None if self.albedo_spec is None else np.ascontiguousarray(self.albedo_spec[sl]))
+                           None if self.albedo_spec is None else np.ascontiguousarray(self.albedo_spec[sl]), self.greeks)
 
 
 def prepare_scene(model: vSmartMOM_Model) -> SceneInputs:
     """Host preparation of rt_run.jl:43-138 for every Fourier moment at once (models with and without bands)."""
     p, qp = model.params, model.quad_points
     L = construct_layer_inputs(model)
-    Zpp, Zmp = z_bases(model)
+    Zpp, Zmp = (None, None) if p.z_resident else z_bases(model)
     M = p.max_m
     S, Nz = L.τ.shape
     cm = np.array([[cosd(m * a) for a in p.vaz] for m in range(M)])
@@ -810,7 +821,8 @@ def prepare_scene(model: vSmartMOM_Model) -> SceneInputs:
         N=len(qp.qp_μN), nStokes=p.polarization_type.n, S=S, Nz=Nz, K=L.zw.shape[0], M=M,
         tau=np.ascontiguousarray(L.τ.T).reshape(-1), varpi=np.ascontiguousarray(L.ϖ.T).reshape(-1),
         zw=np.ascontiguousarray(L.zw.transpose(2, 1, 0)).reshape(-1),  # [z][n][k]
-        Zpp=_abi_mats(Zpp), Zmp=_abi_mats(Zmp), ndoubl=L.ndoubl, iface=L.iface,
+        Zpp=None if Zpp is None else _abi_mats(Zpp), Zmp=None if Zmp is None else _abi_mats(Zmp),
+        greeks=z_greeks(model) if p.z_resident else None, ndoubl=L.ndoubl, iface=L.iface,
         tau_sum=np.ascontiguousarray(L.τ_sum.T).reshape(-1),
         albedo=float(brdf.albedo) if isinstance(brdf, LambertianSurfaceScalar) else 0.0, node=view_nodes(model),
         cos_mphi=cm.reshape(-1), sin_mphi=sm.reshape(-1))
@@ -829,10 +841,7 @@ def make_handle(model: vSmartMOM_Model, S: Optional[int] = None, float_type: str
 
 
 def run_scene(h: _lib.Handle, sc: SceneInputs):
-    h.scene_set(sc.Nz, sc.K, sc.M, sc.tau, sc.varpi, sc.zw, sc.Zpp, sc.Zmp, sc.ndoubl, sc.iface, sc.tau_sum,
-                sc.albedo, sc.node, sc.cos_mphi, sc.sin_mphi)
-    if sc.surf_kind != 0:
-        h.scene_set_surface(sc.surf_kind, sc.M, sc.Rsurf, sc.albedo_spec)
+    scene_set(h, sc)
     h.rt_run()
     return h.get_RT()
 
@@ -849,6 +858,19 @@ class ScenePartial:
     dalbedo: float = 0.0                        # LambertianSurfaceScalar
     dRsurf: Optional[np.ndarray] = None         # [M, N, N] BRDF surfaces (with the factor 2 of m = 0 like Rsurf)
     dalbedo_spec: Optional[np.ndarray] = None   # [nSpec] LambertianSurfaceLegendre
+    d_greeks: Optional[Sequence[Tuple[int, GreekCoefs]]] = None  # in place of dZpp / dZmp: (basis index k, derivative Greek set)
+                                                # pairs, the partials of those bases; the handle forms the matrices
+
+
+def stage_greek_partials(h: "_lib.Handle", partials) -> bool:
+    """The d_greeks of a sequence of ScenePartials / OpticsPartials staged on the handle (mom_scene_stage_greek_partials); False when
+    no partial carries any.  One call cannot mix them with dZpp / dZmp arrays."""
+    if not any(p.d_greeks for p in partials):
+        return False
+    if any(p.dZpp is not None or p.dZmp is not None for p in partials):
+        raise ValueError("partials carry both dZpp / dZmp arrays and d_greeks: one call takes the partials of the bases in one form")
+    h.scene_stage_greek_partials(len(partials), [((int(k), i), _greek_rows(g)) for i, p in enumerate(partials) for k, g in (p.d_greeks or ())])
+    return True
 
 
 def scene_set_partials(h: _lib.Handle, sc: SceneInputs, partials: Sequence[ScenePartial]):
@@ -863,6 +885,7 @@ def scene_set_partials(h: _lib.Handle, sc: SceneInputs, partials: Sequence[Scene
         return np.concatenate([conv(np.zeros_like(ref) if x is None else np.asarray(x, dtype=np.float64)) for x in xs])
 
     col = lambda a: np.ascontiguousarray(a.T).reshape(-1)
+    stage_greek_partials(h, partials)   # then dZpp / dZmp are None below, and the setter takes the stage
     h.scene_set_partials(
         P, dtau=pack(lambda p: p.dτ, col), dvarpi=pack(lambda p: p.dϖ, col),
         dzw=pack(lambda p: p.dzw, lambda a: np.ascontiguousarray(a.transpose(2, 1, 0)).reshape(-1)),
@@ -899,8 +922,12 @@ def scene_set_device_optics(h: _lib.Handle, model: vSmartMOM_Model, upload_tau_a
     """mom_scene_set_optics -- mom_scene_set_optics_bands for a model with bands -- (+ mom_scene_set_surface) from the model's
     ingredients: what run_scene_device_optics and its Dual twin share.  Returns the surface kind."""
     p, qp = model.params, model.quad_points
-    Zpp, Zmp = z_bases(model)
     M = p.max_m
+    if p.z_resident:   # the bases are formed in the handle's memory: the setter below gets None
+        stage_bases(h, z_greeks(model), M)
+        zp = zm = None
+    else:
+        zp, zm = (_abi_mats(Z) for Z in z_bases(model))
     S, Nz = model.τ_rayl.shape
     if upload_tau_abs:
         h.absorption_set(model.τ_abs)
@@ -913,10 +940,10 @@ def scene_set_device_optics(h: _lib.Handle, model: vSmartMOM_Model, upload_tau_a
         bd = model.bands
         h.scene_set_optics_bands(Nz, M, bd.band_start, model.τ_rayl, bd.ϖ_Cabannes, bd.τ_aer,
                                  [[a.ω̃ for a in band] for band in bd.aerosol_optics], [[a.fᵗ for a in band] for band in bd.aerosol_optics],
-                                 _abi_mats(Zpp), _abi_mats(Zmp), albedo, view_nodes(model), cm.reshape(-1), sm.reshape(-1))
+                                 zp, zm, albedo, view_nodes(model), cm.reshape(-1), sm.reshape(-1))
     else:
         h.scene_set_optics(Nz, M, model.τ_rayl, model.ϖ_Cabannes, model.τ_aer, [a.ω̃ for a in model.aerosol_optics],
-                           [a.fᵗ for a in model.aerosol_optics], _abi_mats(Zpp), _abi_mats(Zmp), albedo,
+                           [a.fᵗ for a in model.aerosol_optics], zp, zm, albedo,
                            view_nodes(model), cm.reshape(-1), sm.reshape(-1))
     if kind != 0:
         h.scene_set_surface(kind, M, None if Rs is None else _abi_mats(Rs), alb)
@@ -951,6 +978,7 @@ class OpticsPartial:
     dalbedo: float = 0.0
     dRsurf: Optional[np.ndarray] = None
     dalbedo_spec: Optional[np.ndarray] = None
+    d_greeks: Optional[Sequence[Tuple[int, GreekCoefs]]] = None   # as in ScenePartial
 
 
 def _pack_partials(partials, get, conv, shape=None):
@@ -987,6 +1015,7 @@ def scene_set_optics_partials(h: _lib.Handle, model: vSmartMOM_Model, partials: 
             for c, x in enumerate((p.w_p, p.w_T, p.w_gas)):
                 if x is not None:
                     w_abs[k, c] = np.asarray(x, dtype=np.float64).reshape(Nz)
+    stage_greek_partials(h, partials)
     setter(
         P, w_abs=w_abs, w_rayl=_pack_partials(partials, lambda p: p.w_rayl, flat, (Nz,)),
         dtau_aer=_pack_partials(partials, lambda p: p.dτ_aer, aer_conv, aer_shape + (Nz,)),
@@ -1032,6 +1061,9 @@ def rt_run(model: vSmartMOM_Model, i_band: int = 1):
 
 
 def scene_set(h: _lib.Handle, sc: SceneInputs):
+    """mom_scene_set (+ mom_scene_set_surface); a scene that carries Greek sets in place of Zpp / Zmp stages them first"""
+    if sc.Zpp is None:
+        stage_bases(h, sc.greeks, sc.M)
     h.scene_set(sc.Nz, sc.K, sc.M, sc.tau, sc.varpi, sc.zw, sc.Zpp, sc.Zmp, sc.ndoubl, sc.iface, sc.tau_sum,
                 sc.albedo, sc.node, sc.cos_mphi, sc.sin_mphi)
     if sc.surf_kind != 0:
@@ -1161,7 +1193,8 @@ def rt_run_rrs_window(RS_type: RRS, model: vSmartMOM_Model, lo: int, hi: int, wi
         window = (max(0, lo - H), min(S, hi + H))
     wlo, whi = window
     sc = sc_full if (wlo, whi) == (0, S) else sc_full.spectral_slice(wlo, whi)
-    Zr_pp, Zr_mp = raman_z(RS_type, model)
+    resident = model.params.z_resident
+    Zr = (None, None) if resident else tuple(_abi_mats(Z) for Z in raman_z(RS_type, model))
     fs = fscatt_rayleigh(model)[wlo:whi]
     with make_handle(model, S=whi - wlo) as h:
         h.set_option(_lib.MOM_OPT_STRIP_PAD, 0)
@@ -1170,7 +1203,9 @@ def rt_run_rrs_window(RS_type: RRS, model: vSmartMOM_Model, lo: int, hi: int, wi
         h.rrs_set(RS_type.i_λ1λ0, RS_type.ϖ_λ1λ0, RS_type.rrs_strict_reference)
         h.rrs_set_shard(S, wlo, lo - wlo, hi - wlo)
         scene_set(h, sc)
-        h.scene_set_rrs(np.ascontiguousarray(fs.T), _abi_mats(Zr_pp), _abi_mats(Zr_mp))
+        if resident:
+            stage_bases(h, [RS_type.greek_raman], sc.M, which=1)
+        h.scene_set_rrs(np.ascontiguousarray(fs.T), *Zr)
         h.rt_run_rrs()
         R, T, ieR, ieT = h.get_RT_rrs()[:4]
         hdr, up, dw = h.get_hdr_rrs()

@@ -29,6 +29,16 @@ struct MomLut {
   MomDevBuf<double> d_nu;           // the model's nu grid [nNu] (mom_lut_build's spectral grid)
 };
 
+// Greek sets [nG][6][l_pad] (rows α, β, γ, δ, ϵ, ζ; mom_z_moments' layout) waiting for a setter.  Derivative sets: set d is the
+// partial of basis `basis[d]` with respect to parameter `partial[d]` of P
+struct MomGreekStage {
+  bool live = false;
+  int nG = 0, l_pad = 0, M = 0, P = 0;
+  std::vector<int> l_max, basis, partial;
+  std::vector<double> greek;
+  void drop() { *this = MomGreekStage{}; }
+};
+
 // The resident scene's arrays and counts (d_mu ... d_scratch, Nz, K, nVza, scene_M, surf_kind, albedo, nd, iface) are the base:
 // MomSceneBufs, mom_host.hpp -- the declaration the Float32 scene shares
 struct mom_handle : MomSceneBufs<double> {
@@ -77,6 +87,9 @@ struct mom_handle : MomSceneBufs<double> {
   MomDevBuf<double> d_Zop[2];
   // scene
   bool scene_set = false;
+  // Greek coefficients staged for the next setter (mom_scene_stage_greeks / _greek_partials): host copies, no device memory.  The
+  // setter that takes a stage forms the Z bases in the handle's own buffers (mom_zmom.hip) and the stage is gone
+  MomGreekStage stage_z, stage_r, stage_d;  // the elastic bases, the Raman set, the derivative sets
   // m = 0 reduction (see mom_scene_set)
   int opt_m0 = 1;
   int opt_w4 = 1;
@@ -190,6 +203,10 @@ hipError_t mom_launch_combine(const mom::InterArgs &a, bool lds, int grid, size_
 // geometry, output buffers, the m = 0 reduction
 int scene_common(mom_t *h, int Nz, int K, int M, const double *Zpp, const double *Zmp, double albedo, int nVza,
                  const int *node_1based, const double *cos_mphi, const double *sin_mphi);
+// mom_scene.hip: a setter `fn` of K bases and M moments was given Zpp == Zmp == NULL.  MOM_OK when staged Greek sets of that shape
+// wait (scene_common takes them when its Zpp is null); MOM_EINVAL otherwise: without a stage the setter's "bad argument", with one
+// of another shape a text that names both
+int mom_stage_claim(mom_t *h, const char *fn, int K, int M);
 // mom_comm.hip: set once RCCL is loaded (mom_comm_init); the maximum over the ranks of `count` doubles on the device, in place
 extern void (*g_rccl_destroy)(void *);
 int mom_comm_allreduce_max(mom_t *h, double *d_buf, size_t count);

@@ -358,6 +358,32 @@ struct MomDualScene {
 size_t momd_bytes_per_unit(int N, int P);
 int momd_run(const MomDualScene &sc, std::string *err);   // 0 ok, 1 unsupported, 2 HIP error (text in *err)
 
+// mom_zmom.hip: the phase-matrix Fourier moments as a plan and a launch.  The plan holds what does not depend on the destination:
+// the host scalars of the recurrences and their uploads, the Greek rows [nG][6][l_pad], the (set, moment) -> block table
+// slot [nG, M] and the planes of the generalised spherical functions.  The launch writes block slot[g + nG mi] of Zpp / Zmp, blocks of
+// row pitch `pitch` >= N = n n_mu (the entries behind N are left as they are: zero them in front), and with Zpp0 the (I,Q) cut of
+// the moment-0 block of set g into block g of [pitch0, pitch0, nG].  Everything is asynchronous on `st`, so the plan, the stage it
+// was made from and the destinations outlive the stream's work.
+struct MomZmomPlan {
+  int n = 0, n_mu = 0, L = 0, l_pad = 0, nG = 0, m_first = 0, M = 0, ldSeed = 0;
+  std::vector<double> mu, smu, coef, seed;  // the host side of the asynchronous uploads
+  std::vector<int> slot;
+  MomDevBuf<double> d_mu, d_smu, d_coef, d_seed, d_greek, d_tab;
+  MomDevBuf<int> d_lmax, d_slot, d_flag;
+};
+#pragma GCC visibility push(hidden)
+// the argument checks mom_z_moments makes before its first HIP call: the text of the first that fails, or null
+const char *mom_zmom_check(int n, int n_mu, const double *mu, int nG, int l_pad, const int *l_max, const double *greek, int m_first,
+                           int M);
+hipError_t mom_zmom_plan(MomZmomPlan &pl, int n, int n_mu, const double *mu, int nG, int l_pad, const int *l_max, const double *greek,
+                         int m_first, int M, const int *slot, hipStream_t st);
+hipError_t mom_zmom_launch(const MomZmomPlan &pl, hipStream_t st, double *Zpp, double *Zmp, int pitch, double *Zpp0, double *Zmp0,
+                           int pitch0);
+// the data half of mom_m0_reducible on the device: *coupled = 1 when a moment-0 block (blocks 0 .. K - 1) of Zpp or Zmp has an
+// (I,Q) <-> (U,V) entry != 0.0.  Drains `st`: the int is the only transfer
+hipError_t mom_zmom_couples(MomZmomPlan &pl, hipStream_t st, int K, const double *Zpp, const double *Zmp, int pitch, int *coupled);
+#pragma GCC visibility pop
+
 // mom_scene.hip: what the two setters of the scene's partials share (mom_scene_set_partials there, mom_scene_set_optics_partials in
 // mom_optics.hip).  _check: 0 <= P <= 64 and dZpp / dZmp both or neither, else MOM_EINVAL with `fn` in the text; _reset: the partials,
 // outputs and workspaces of the previous call go and P becomes the scene's; _rest: everything but dtau / dvarpi / dzw (d_dual_in[0..2])

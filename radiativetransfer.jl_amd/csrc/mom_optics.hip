@@ -576,9 +576,13 @@ int scene_set_optics_run(mom_t *h, const char *fn, int Nz, int nAer, int nBand, 
                          const double *sin_mphi) {
   const std::string f(fn);
   if (!h->streams_set) return fail(h, MOM_ESTATE, (f + ": call mom_set_streams first").c_str());
-  if (Nz <= 0 || nAer < 0 || nAer > 7 || M <= 0 || M > h->M || nVza <= 0 || !tau_rayl || !varpi_rayl || !Zpp || !Zmp || !node_1based ||
-      !cos_mphi || !sin_mphi || (nAer > 0 && (!tau_aer || !omega_aer || !ft_aer)))
+  if (Nz <= 0 || nAer < 0 || nAer > 7 || M <= 0 || M > h->M || nVza <= 0 || !tau_rayl || !varpi_rayl || (Zpp == nullptr) != (Zmp == nullptr) ||
+      !node_1based || !cos_mphi || !sin_mphi || (nAer > 0 && (!tau_aer || !omega_aer || !ft_aer)))
     return fail(h, MOM_EINVAL, (f + ": bad argument").c_str());
+  if (!Zpp) {  // the staged bases (mom_scene_stage_greeks), if any: one per (aerosol type, band) behind Rayleigh's
+    const int rc_stage = mom_stage_claim(h, fn, 1 + nAer * std::max(nBand, 1), M);
+    if (rc_stage) return rc_stage;
+  }
   if (!h->d_tau_abs || h->abs_Nz != Nz)
     return fail(h, MOM_ESTATE, (f + ": no resident tau_abs table of this Nz (mom_absorption_begin / _set)").c_str());
   HIPCHK(h, hipSetDevice(h->device));

@@ -16,9 +16,14 @@ inline int mom_m0_edge(int N, int nS) { return kMomM0Stokes * (N / nS); }
 
 // Moment 0 decouples into (I,Q) and (U,V) when the source has no U, V (I0[k] == 0 for k >= 2; I0 holds 4 entries) and no basis
 // of Zpp / Zmp [N,N,K,M] has an (I,Q) <-> (U,V) entry in its moment-0 block; checked on the data, bitwise
-inline bool mom_m0_reducible(const double *I0, int N, int nS, int K, const double *Zpp, const double *Zmp) {
+// (mom_m0_source: the source's half alone, for bases whose entries are tested where they are formed, mom_zmom.hip)
+inline bool mom_m0_source(const double *I0, int nS) {
   for (int k = 2; k < nS; ++k)
     if (I0[k] != 0.0) return false;
+  return true;
+}
+inline bool mom_m0_reducible(const double *I0, int N, int nS, int K, const double *Zpp, const double *Zmp) {
+  if (!mom_m0_source(I0, nS)) return false;
   for (int kb = 0; kb < K; ++kb)
     for (int j = 0; j < N; ++j)
       for (int i = 0; i < N; ++i) {
@@ -34,11 +39,18 @@ inline bool mom_m0_reducible(const double *I0, int N, int nS, int K, const doubl
 struct MomM0Cut {
   std::vector<double> mu, wt, sg, Zpp, Zmp;
 };
+// the streams alone (Zpp, Zmp empty): for bases that are cut on the device (mom_zmom.hip)
+inline MomM0Cut mom_m0_cut_streams(const double *mu, const double *wt, int N, int nS, int N0) {
+  const int N0r = mom_m0_edge(N, nS);
+  MomM0Cut c{std::vector<double>(N0, 1.0), std::vector<double>(N0, 0.0), std::vector<double>(N0, 1.0), {}, {}};
+  for (int i = 0; i < N0r; ++i) { c.mu[i] = mu[mom_m0_full(i, nS)]; c.wt[i] = wt[mom_m0_full(i, nS)]; }
+  return c;
+}
 inline MomM0Cut mom_m0_cut(const double *mu, const double *wt, int N, int nS, int K, int N0, const double *Zpp, const double *Zmp) {
   const int N0r = mom_m0_edge(N, nS);
-  const std::vector<double> zero((size_t)N0 * N0 * K, 0.0);
-  MomM0Cut c{std::vector<double>(N0, 1.0), std::vector<double>(N0, 0.0), std::vector<double>(N0, 1.0), zero, zero};
-  for (int i = 0; i < N0r; ++i) { c.mu[i] = mu[mom_m0_full(i, nS)]; c.wt[i] = wt[mom_m0_full(i, nS)]; }
+  MomM0Cut c = mom_m0_cut_streams(mu, wt, N, nS, N0);
+  c.Zpp.assign((size_t)N0 * N0 * K, 0.0);
+  c.Zmp = c.Zpp;
   for (int kb = 0; kb < K; ++kb)
     for (int j = 0; j < N0r; ++j)
       for (int i = 0; i < N0r; ++i) {

@@ -334,10 +334,35 @@ extern "C" int mom_scene_set_rrs(mom_t *h, const double *fscattRayl, const doubl
   int rc = rrs_ready(h, "mom_scene_set_rrs");
   if (rc) return rc;
   if (!h->scene_set) return fail(h, MOM_ESTATE, "mom_scene_set_rrs: call mom_scene_set / mom_scene_set_optics first");
-  if (!fscattRayl || !Zpp_l1l0 || !Zmp_l1l0) return fail(h, MOM_EINVAL, "mom_scene_set_rrs: bad argument");
+  // Zpp_l1l0 == Zmp_l1l0 == NULL: the staged Raman set (mom_scene_stage_greeks, which = 1), if any
+  const bool staged = !Zpp_l1l0 && !Zmp_l1l0 && h->stage_r.live;
+  if (!fscattRayl || (!staged && (!Zpp_l1l0 || !Zmp_l1l0))) return fail(h, MOM_EINVAL, "mom_scene_set_rrs: bad argument");
+  if (staged && h->stage_r.M != h->scene_M) {
+    char buf[200];
+    snprintf(buf, sizeof buf, "mom_scene_set_rrs: the scene has M = %d, but the staged Raman set (mom_scene_stage_greeks) is M = %d",
+             h->scene_M, h->stage_r.M);
+    return fail(h, MOM_EINVAL, buf);
+  }
   if (h->Nk != h->N) return fail(h, MOM_ESTATE, "mom_scene_set_rrs: the scene was set with a padded operator edge (MOM_OPT_STRIP_PAD)");
   const size_t NN = (size_t)h->N * h->N;
   HIPCHK(h, mom_upload(h->d_fscatt, fscattRayl, (size_t)h->S * h->Nz, h->stream));
+  if (staged) {  // [N, N, M] formed in d_Zr on the handle's stream: one set, block m
+    MomGreekStage st = std::move(h->stage_r);
+    h->stage_r.drop();
+    const int M = h->scene_M, n_mu = h->N / h->nS;
+    std::vector<double> mu((size_t)n_mu);
+    for (int i = 0; i < n_mu; ++i) mu[i] = h->h_mu[(size_t)i * h->nS];
+    std::vector<int> slot((size_t)M);
+    for (int m = 0; m < M; ++m) slot[m] = m;
+    MomZmomPlan pl;
+    HIPCHK(h, mom_zmom_plan(pl, h->nS, n_mu, mu.data(), 1, st.l_pad, st.l_max.data(), st.greek.data(), 0, M, slot.data(), h->stream));
+    HIPCHK(h, h->d_Zr[0].renew(NN * M));
+    HIPCHK(h, h->d_Zr[1].renew(NN * M));
+    HIPCHK(h, mom_zmom_launch(pl, h->stream, h->d_Zr[0], h->d_Zr[1], h->N, nullptr, nullptr, 0));
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // the plan and the stage go out of scope
+    h->rrs_scene = true;
+    return MOM_OK;
+  }
   HIPCHK(h, mom_upload(h->d_Zr[0], Zpp_l1l0, NN * h->scene_M, h->stream));
   HIPCHK(h, mom_upload(h->d_Zr[1], Zmp_l1l0, NN * h->scene_M, h->stream));
   h->rrs_scene = true;

@@ -82,15 +82,124 @@ static int stream_tables(mom_t *h, const DevStreams &q, MomDevBuf<double> &buf) 
 static bool strip_size(int N) { return mom_find_image(MOM_IMG_STRIP4, N) || mom_find_image(MOM_IMG_STRIP8, N); }
 static int strip_pad(int N) { return mom_strip_pad(strip_size, N); }
 
+// ---- Greek coefficients staged on the handle: the Z bases are formed where the kernels read them (mom_zmom.hip) -------------
+// one mu per stream of the handle's quadrature (mom_set_streams): entry i nS of h_mu
+static std::vector<double> stream_mu(const mom_t *h) {
+  std::vector<double> mu((size_t)(h->N / h->nS));
+  for (size_t i = 0; i < mu.size(); ++i) mu[i] = h->h_mu[i * h->nS];
+  return mu;
+}
+// what both staging calls check and copy: the handle's state, the Greek sets against the handle's streams (mom_z_moments' checks)
+static int stage_greeks(mom_t *h, const char *fn, MomGreekStage &st, int nG, int l_pad, const int *l_max, const double *greek, int M) {
+  const std::string f(fn);
+  if (h->dtype != 0) return fail(h, MOM_EUNSUPPORTED, (f + ": Greek coefficients are staged on Float64 handles only").c_str());
+  if (!h->streams_set) return fail(h, MOM_ESTATE, (f + ": call mom_set_streams first").c_str());
+  if (h->N % h->nS != 0) return fail(h, MOM_EINVAL, (f + ": the operator edge is not a whole number of streams").c_str());
+  if (M > h->M) return fail(h, MOM_EINVAL, (f + ": more moments than the handle was created for").c_str());
+  const std::vector<double> mu = stream_mu(h);
+  if (const char *bad = mom_zmom_check(h->nS, (int)mu.size(), mu.data(), nG, l_pad, l_max, greek, 0, M))
+    return fail(h, MOM_EINVAL, (f + ": " + bad).c_str());
+  st.drop();
+  st.nG = nG; st.l_pad = l_pad; st.M = M;
+  st.l_max.assign(l_max, l_max + nG);
+  st.greek.assign(greek, greek + (size_t)nG * 6 * l_pad);
+  st.live = true;
+  return MOM_OK;
+}
+
+extern "C" int mom_scene_stage_greeks(mom_t *h, int which, int nG, int l_pad, const int *l_max, const double *greek, int M) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  if (which != 0 && which != 1) return fail(h, MOM_EINVAL, "mom_scene_stage_greeks: which must be 0 (elastic bases) or 1 (the Raman set)");
+  if (which == 0 && nG > 64) return fail(h, MOM_EINVAL, "mom_scene_stage_greeks: at most 64 phase-matrix bases");
+  if (which == 1 && nG != 1) return fail(h, MOM_EINVAL, "mom_scene_stage_greeks: the Raman stage is one Greek set (nG = 1)");
+  return stage_greeks(h, "mom_scene_stage_greeks", which ? h->stage_r : h->stage_z, nG, l_pad, l_max, greek, M);
+}
+
+extern "C" int mom_scene_stage_greek_partials(mom_t *h, int P, int nD, const int *basis, const int *partial, int l_pad,
+                                              const int *l_max, const double *dgreek) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  const char *fn = "mom_scene_stage_greek_partials";
+  if (P < 1 || P > 64 || nD < 1 || !basis || !partial) return fail(h, MOM_EINVAL, "mom_scene_stage_greek_partials: 1 <= P <= 64, nD >= 1, basis and partial given");
+  for (int d = 0; d < nD; ++d) {
+    if (basis[d] < 0 || basis[d] >= 64 || partial[d] < 0 || partial[d] >= P)
+      return fail(h, MOM_EINVAL, "mom_scene_stage_greek_partials: basis within 0..63 and partial within 0..P-1");
+    for (int e = 0; e < d; ++e)
+      if (basis[e] == basis[d] && partial[e] == partial[d]) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "%s: the pair (basis %d, partial %d) is named twice", fn, basis[d], partial[d]);
+        return fail(h, MOM_EINVAL, buf);
+      }
+  }
+  MomGreekStage st;
+  const int rc = stage_greeks(h, fn, st, nD, l_pad, l_max, dgreek, 1);  // the moments are the scene's, known at the setter
+  if (rc) return rc;
+  st.P = P;
+  st.basis.assign(basis, basis + nD);
+  st.partial.assign(partial, partial + nD);
+  h->stage_d = std::move(st);
+  return MOM_OK;
+}
+
+int mom_stage_claim(mom_t *h, const char *fn, int K, int M) {
+  const MomGreekStage &st = h->stage_z;
+  char buf[256];
+  if (!st.live) {
+    snprintf(buf, sizeof buf, "%s: bad argument", fn);
+    return fail(h, MOM_EINVAL, buf);
+  }
+  if (st.nG == K && st.M == M) return MOM_OK;
+  snprintf(buf, sizeof buf, "%s: K = %d, M = %d, but the staged Greek sets (mom_scene_stage_greeks) are K = %d, M = %d", fn, K, M, st.nG, st.M);
+  return fail(h, MOM_EINVAL, buf);
+}
+
+// scene_common's staged case: d_Zpp / d_Zmp [Nk, Nk, K, M] and, for N0 > 0 (the host half of the m = 0 condition holds), d_Zpp0 /
+// d_Zmp0 [N0, N0, K], zeroed and written on the handle's stream; *red_ok ends up false when a moment-0 block couples (I,Q) with (U,V)
+static int stage_bases(mom_t *h, int K, int M, int Nk, int N0, bool *red_ok) {
+  MomGreekStage st = std::move(h->stage_z);
+  h->stage_z.drop();
+  if (!st.live || st.nG != K || st.M != M) return fail(h, MOM_EINVAL, "the scene's setter: no staged Greek sets of this K and M");
+  const std::vector<double> mu = stream_mu(h);
+  std::vector<int> slot((size_t)K * M);
+  for (size_t e = 0; e < slot.size(); ++e) slot[e] = (int)e;  // [Nk, Nk, K, M]: block k + K m
+  const size_t nZ = (size_t)Nk * Nk * K * M, nZ0 = (size_t)N0 * N0 * K;
+  MomZmomPlan pl;
+  HIPCHK(h, mom_zmom_plan(pl, h->nS, (int)mu.size(), mu.data(), K, st.l_pad, st.l_max.data(), st.greek.data(), 0, M, slot.data(), h->stream));
+  HIPCHK(h, h->d_Zpp.renew(nZ));
+  HIPCHK(h, h->d_Zmp.renew(nZ));
+  if (Nk != h->N) {  // strip_pad's dummy entries: exact zeros
+    HIPCHK(h, hipMemsetAsync(h->d_Zpp, 0, nZ * sizeof(double), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_Zmp, 0, nZ * sizeof(double), h->stream));
+  }
+  if (N0 > 0) {
+    HIPCHK(h, h->d_Zpp0.renew(nZ0));
+    HIPCHK(h, h->d_Zmp0.renew(nZ0));
+    HIPCHK(h, hipMemsetAsync(h->d_Zpp0, 0, nZ0 * sizeof(double), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_Zmp0, 0, nZ0 * sizeof(double), h->stream));
+  }
+  HIPCHK(h, mom_zmom_launch(pl, h->stream, h->d_Zpp, h->d_Zmp, Nk, N0 > 0 ? h->d_Zpp0.get() : nullptr, N0 > 0 ? h->d_Zmp0.get() : nullptr, N0));
+  int coupled = 0;
+  if (N0 > 0) HIPCHK(h, mom_zmom_couples(pl, h->stream, K, h->d_Zpp, h->d_Zmp, Nk, &coupled));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // the plan and the stage go out of scope
+  if (coupled) {
+    *red_ok = false;
+    h->d_Zpp0.reset(); h->d_Zmp0.reset();
+  }
+  return MOM_OK;
+}
+
 extern "C" int mom_scene_set(mom_t *h, int Nz, int K, int M, const double *tau, const double *varpi, const double *zw,
                              const double *Zpp, const double *Zmp, const int *ndoubl, const int *iface,
                              const double *tau_sum, double albedo, int nVza, const int *node_1based,
                              const double *cos_mphi, const double *sin_mphi) {
   if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
   if (!h->streams_set) return fail(h, MOM_ESTATE, "mom_scene_set: call mom_set_streams first");
-  if (Nz <= 0 || K <= 0 || M <= 0 || M > h->M || nVza <= 0 || !tau || !varpi || !zw || !Zpp || !Zmp || !ndoubl ||
+  if (Nz <= 0 || K <= 0 || M <= 0 || M > h->M || nVza <= 0 || !tau || !varpi || !zw || (Zpp == nullptr) != (Zmp == nullptr) || !ndoubl ||
       !iface || !tau_sum || !node_1based || !cos_mphi || !sin_mphi)
     return fail(h, MOM_EINVAL, "mom_scene_set: bad argument");
+  if (!Zpp) {  // the staged bases (mom_scene_stage_greeks), if any
+    const int rc = mom_stage_claim(h, "mom_scene_set", K, M);
+    if (rc) return rc;
+  }
   if (K > 64) return fail(h, MOM_EINVAL, "mom_scene_set: at most 64 phase-matrix bases (Rayleigh + aerosol types)");
   for (int z = 0; z < Nz; ++z)
     if (ndoubl[z] < 0 || ndoubl[z] > 60 || iface[z] < 0 || iface[z] > 3)
@@ -128,16 +237,35 @@ int scene_common(mom_t *h, int Nz, int K, int M, const double *Zpp, const double
   for (int v = 0; v < nVza; ++v)
     if (node_1based[v] < 1 || node_1based[v] * h->nS > h->N) return fail(h, MOM_EINVAL, "mom_scene_set: bad view node");
   const size_t S = h->S, NN = (size_t)h->N * h->N;
-  // a new scene: the partials of the previous one (mom_scene_set_partials) do not belong to it
+  // a new scene: the partials of the previous one (mom_scene_set_partials) do not belong to it, nor does a staged partial set
   for (auto &b : h->d_dual_in) b.reset();
   h->dual_P = 0; h->dual_ran = false;
+  h->stage_d.drop();
   // (edges up to 32 belong to the wave-per-point kernel, which takes the operators as they are)
   const int Nk = (h->opt_pad && !(h->N <= 32 && h->opt_small)) ? strip_pad(h->N) : h->N;
   h->Nk = Nk;
   h->qk = h->q;
   h->qk.N = Nk;
   h->nbw_0 = 0;
-  if (Nk == h->N) {
+  // ---- m = 0 reduction (include/momcore.h): conditions checked on the data, bitwise.  The options, the source and the N <= 4 route
+  // are decided here; the data are the host's arrays, or for staged bases (Zpp == nullptr) what the device formed (stage_bases)
+  const bool staged = !Zpp;
+  bool red_ok = h->opt_m0 && h->nS >= 3 && h->q.regular && !(h->N <= 4 && h->opt_small && nVza <= 4 && K <= 4) &&
+                (staged ? mom_m0_source(h->q.I0, h->nS) : mom_m0_reducible(h->q.I0, h->N, h->nS, K, Zpp, Zmp));
+  int N0 = 0;
+  if (red_ok) {
+    // N0r real entries; the kernels run on N0 >= N0r (dummy entries of strip_pad at the end: mu = 1, weight 0, Z = 0)
+    const int N0r = mom_m0_edge(h->N, h->nS);
+    N0 = h->opt_pad ? strip_pad(N0r) : N0r;
+    // r6: sub-problems of edge 18 .. 30 that are not a multiple of 4 take ONE dummy stream (two entries) to reach a quad-block
+    // size (20, 24, 28, 32: mom_q4.hpp; IQUV scenes of 9 .. 15 streams)
+    if (h->opt_pad && h->opt_lean >= 3 && N0 == N0r && N0r > 16 && N0r < 32 && (N0r % 4) != 0) N0 = N0r + 2;
+  }
+  for (MomDevBuf<double> *b : {&h->d_mu0, &h->d_wt0, &h->d_sg0, &h->d_Zpp0, &h->d_Zmp0, &h->d_hdrJ0, &h->d_scratch0}) b->reset();
+  if (staged) {
+    const int rc = stage_bases(h, K, M, Nk, N0, &red_ok);
+    if (rc) return rc;
+  } else if (Nk == h->N) {
     HIPCHK(h, mom_upload(h->d_Zpp, Zpp, NN * K * M, h->stream));
     HIPCHK(h, mom_upload(h->d_Zmp, Zmp, NN * K * M, h->stream));
   } else {
@@ -159,29 +287,24 @@ int scene_common(mom_t *h, int Nz, int K, int M, const double *Zpp, const double
     HIPCHK(h, h->d_bhr_uw.renew((size_t)h->nS * S));
     HIPCHK(h, h->d_bhr_dw.renew((size_t)h->nS * S));
   }
-  // ---- m = 0 reduction (include/momcore.h): conditions checked on the data, bitwise
-  {
+  {  // the (I,Q) sub-problem of a reducible scene: its streams, composite state and scratch (its bases: above)
     const int N = h->N, nS = h->nS;
-    const bool ok = h->opt_m0 && nS >= 3 && h->q.regular && !(N <= 4 && h->opt_small && nVza <= 4 && K <= 4) &&
-                    mom_m0_reducible(h->q.I0, N, nS, K, Zpp, Zmp);
-    for (MomDevBuf<double> *b : {&h->d_mu0, &h->d_wt0, &h->d_sg0, &h->d_Zpp0, &h->d_Zmp0, &h->d_hdrJ0, &h->d_scratch0}) b->reset();
+    const bool ok = red_ok;
     for (auto &b : h->comp0) b.reset();
     h->red0 = ok;
     if (ok) {
-      // N0r real entries; the kernels run on N0 >= N0r (dummy entries of strip_pad at the end: mu = 1, weight 0, Z = 0)
-      const int nS0 = kMomM0Stokes, N0r = mom_m0_edge(N, nS);
-      int N0 = h->opt_pad ? strip_pad(N0r) : N0r;
-      // r6: sub-problems of edge 18 .. 30 that are not a multiple of 4 take ONE dummy stream (two entries) to reach a quad-block
-      // size (20, 24, 28, 32: mom_q4.hpp; IQUV scenes of 9 .. 15 streams)
-      if (h->opt_pad && h->opt_lean >= 3 && N0 == N0r && N0r > 16 && N0r < 32 && (N0r % 4) != 0) N0 = N0r + 2;
+      const int nS0 = kMomM0Stokes;
       h->N0 = N0; h->nS0 = nS0;
-      const MomM0Cut cut = mom_m0_cut(h->h_mu.data(), h->h_wt.data(), N, nS, K, N0, Zpp, Zmp);
+      const MomM0Cut cut = staged ? mom_m0_cut_streams(h->h_mu.data(), h->h_wt.data(), N, nS, N0)
+                                  : mom_m0_cut(h->h_mu.data(), h->h_wt.data(), N, nS, K, N0, Zpp, Zmp);
       h->nbw_0 = mom_q4_nbw(cut.wt.data(), N0);  // after the reduction to (I,Q) and the padding
       HIPCHK(h, mom_upload(h->d_mu0, cut.mu.data(), (size_t)N0, h->stream));
       HIPCHK(h, mom_upload(h->d_wt0, cut.wt.data(), (size_t)N0, h->stream));
       HIPCHK(h, mom_upload(h->d_sg0, cut.sg.data(), (size_t)N0, h->stream));
-      HIPCHK(h, mom_upload(h->d_Zpp0, cut.Zpp.data(), cut.Zpp.size(), h->stream));
-      HIPCHK(h, mom_upload(h->d_Zmp0, cut.Zmp.data(), cut.Zmp.size(), h->stream));
+      if (!staged) {
+        HIPCHK(h, mom_upload(h->d_Zpp0, cut.Zpp.data(), cut.Zpp.size(), h->stream));
+        HIPCHK(h, mom_upload(h->d_Zmp0, cut.Zmp.data(), cut.Zmp.size(), h->stream));
+      }
       for (int k = 0; k < 6; ++k) {
         const size_t cnt = ((k < 4) ? (size_t)comp_pitch(N0) * N0 : (size_t)N0) * S;
         HIPCHK(h, h->comp0[k].renew(cnt));
@@ -744,10 +867,44 @@ extern "C" int mom_rt_run_multisensor(mom_t *h, int nSensors, const int *sensor_
 // ---- ForwardDiff.Dual through rt_run (mom_dual.hip) ---------------------------------------------------------------
 // What mom_scene_set_partials and mom_scene_set_optics_partials (mom_optics.hip) share: mom_host.hpp
 int mom_partials_check(mom_t *h, const char *fn, int P, const double *dZpp, const double *dZmp) {
-  if (P >= 0 && P <= 64 && ((dZpp == nullptr) == (dZmp == nullptr))) return MOM_OK;
-  char buf[160];
-  snprintf(buf, sizeof buf, "%s: 0 <= P <= 64; dZpp and dZmp come together", fn);
-  return fail(h, MOM_EINVAL, buf);
+  char buf[200];
+  if (!(P >= 0 && P <= 64 && ((dZpp == nullptr) == (dZmp == nullptr)))) {
+    snprintf(buf, sizeof buf, "%s: 0 <= P <= 64; dZpp and dZmp come together", fn);
+    return fail(h, MOM_EINVAL, buf);
+  }
+  // dZpp == dZmp == NULL with a staged partial set (mom_scene_stage_greek_partials): mom_partials_rest forms it, for this P
+  const MomGreekStage &st = h->stage_d;
+  if (dZpp || !st.live) return MOM_OK;
+  if (st.P != P) {
+    snprintf(buf, sizeof buf, "%s: P = %d, but the staged Greek partials (mom_scene_stage_greek_partials) are P = %d", fn, P, st.P);
+    return fail(h, MOM_EINVAL, buf);
+  }
+  for (int b : st.basis)
+    if (b >= h->K) {
+      snprintf(buf, sizeof buf, "%s: the staged Greek partials name basis %d, the scene has K = %d", fn, b, h->K);
+      return fail(h, MOM_EINVAL, buf);
+    }
+  return MOM_OK;
+}
+// mom_partials_rest's staged case: d_dual_in[3] / [4] [Nk, Nk, K, M, P], zero but for the blocks of the staged (basis, partial) pairs
+static int stage_partials(mom_t *h) {
+  MomGreekStage st = std::move(h->stage_d);
+  h->stage_d.drop();
+  const int K = h->K, M = h->scene_M, Nk = h->Nk, nD = st.nG;
+  const size_t nZ = (size_t)Nk * Nk * K * M * h->dual_P;
+  const std::vector<double> mu = stream_mu(h);
+  std::vector<int> slot((size_t)nD * M);
+  for (int mi = 0; mi < M; ++mi)
+    for (int d = 0; d < nD; ++d) slot[d + (size_t)nD * mi] = st.basis[d] + K * (mi + M * st.partial[d]);
+  MomZmomPlan pl;
+  HIPCHK(h, mom_zmom_plan(pl, h->nS, (int)mu.size(), mu.data(), nD, st.l_pad, st.l_max.data(), st.greek.data(), 0, M, slot.data(), h->stream));
+  HIPCHK(h, h->d_dual_in[3].renew(nZ));
+  HIPCHK(h, h->d_dual_in[4].renew(nZ));
+  HIPCHK(h, hipMemsetAsync(h->d_dual_in[3], 0, nZ * sizeof(double), h->stream));
+  HIPCHK(h, hipMemsetAsync(h->d_dual_in[4], 0, nZ * sizeof(double), h->stream));
+  HIPCHK(h, mom_zmom_launch(pl, h->stream, h->d_dual_in[3], h->d_dual_in[4], Nk, nullptr, nullptr, 0));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // the plan and the stage go out of scope
+  return MOM_OK;
 }
 void mom_partials_reset(mom_t *h, int P) {
   for (auto &b : h->d_dual_in) b.reset();
@@ -768,6 +925,9 @@ int mom_partials_rest(mom_t *h, const double *dZpp, const double *dZmp, const do
       HIPCHK(h, mom_upload(h->d_dual_in[4], zm.data(), zm.size(), h->stream));
       HIPCHK(h, hipStreamSynchronize(h->stream));
     }
+  } else if (h->stage_d.live) {  // (mom_partials_check has compared P and the bases with the scene)
+    const int rc = stage_partials(h);
+    if (rc) return rc;
   }
   if (dalbedo) HIPCHK(h, mom_upload(h->d_dual_in[5], dalbedo, (size_t)P, h->stream));
   if (dRsurf && h->surf_kind == 1) {
@@ -903,4 +1063,29 @@ extern "C" int mom_get_RT_device(mom_t *h, void *dR, void *dT) {
   HIPCHK(h, hipMemcpyAsync(dR, h->d_R, bytes, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(dT, h->d_T, bytes, hipMemcpyDeviceToDevice, h->stream));
   return MOM_OK;  // asynchronous: a singular-operator report surfaces at mom_get_RT / mom_check
+}
+
+// The resident phase-matrix arrays as the kernels read them (include/momcore.h), whichever route put them there
+extern "C" int mom_scene_get_bases(mom_t *h, int which, int *edge, int *blocks, double *Zpp, double *Zmp) {
+  if (!h) return fail(nullptr, MOM_EINVAL, "null handle");
+  F64_ONLY(h, "mom_scene_get_bases");
+  if (!h->scene_set) return fail(h, MOM_ESTATE, "mom_scene_get_bases: no scene");
+  if (which < 0 || which > 3 || (Zpp == nullptr) != (Zmp == nullptr))
+    return fail(h, MOM_EINVAL, "mom_scene_get_bases: which within 0..3; Zpp and Zmp come together");
+  if (which == 3 && !h->rrs_scene) return fail(h, MOM_ESTATE, "mom_scene_get_bases: no Raman set (mom_scene_set_rrs)");
+  int e = 0, b = 0;
+  const double *src[2] = {nullptr, nullptr};
+  if (which == 0) { e = h->Nk; b = h->K * h->scene_M; src[0] = h->d_Zpp; src[1] = h->d_Zmp; }
+  else if (which == 1 && h->red0) { e = h->N0; b = h->K; src[0] = h->d_Zpp0; src[1] = h->d_Zmp0; }
+  else if (which == 2 && h->d_dual_in[3]) { e = h->Nk; b = h->K * h->scene_M * h->dual_P; src[0] = h->d_dual_in[3]; src[1] = h->d_dual_in[4]; }
+  else if (which == 3) { e = h->N; b = h->scene_M; src[0] = h->d_Zr[0]; src[1] = h->d_Zr[1]; }
+  if (edge) *edge = e;
+  if (blocks) *blocks = b;
+  if (!Zpp || e == 0 || b == 0) return MOM_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t bytes = (size_t)e * e * b * sizeof(double);
+  HIPCHK(h, hipMemcpyAsync(Zpp, src[0], bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(Zmp, src[1], bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MOM_OK;
 }

@@ -14,6 +14,10 @@
 // roots, integer quotients) come from the host, formed as the host text forms them: the planes are bitwise those of
 // corert._prt_for_moment.  The products of (b) are summed in another order than the reference's loop over l (k-steps of the
 // MFMA, fused multiply-adds); DESIGN section 4 states what that is allowed to cost.
+// The host part is a plan and a launch (MomZmomPlan, mom_host.hpp): mom_z_moments launches into a buffer of its own and downloads it,
+// the handle's scene setters launch into the buffers their kernels read (staged Greek sets, mom_scene.hip) -- the same kernels and
+// the same arithmetic per entry, so the two leave the same bits.  (c) k_zmom_couples is the data half of the m = 0 reducibility
+// test for bases that never reach the host.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -145,13 +149,15 @@ __device__ __forceinline__ int left_sel(int a, int b, int &q, double &sgn) {
 
 // grid: (output tiles, (set, m), {++, -+}).  The MFMA's row index runs over the columns (j, c) of Z and its column index, the one
 // on the lanes, over the rows (i, a): Z is stored with i fastest, so a wavefront's stores are runs of 16 doubles.
-// out slot of (set g, moment mi): (g % Kin) + Kin (mi + M (g / Kin)) with Kin = set_inner -- [N, N, nG, M] for Kin = nG and
-// [N, N, K, M, P] for nG = K P sets ordered k fastest and Kin = K.
+// The block of (set g, moment mi) is slot[g + nG mi] of the destination, whose blocks have the row pitch `pitch` >= N (strip_pad's
+// edge: the entries behind N are not written).  With Zpp0 the moment-0 block of set g also goes, cut to its (I,Q) entries at the
+// mom_m0_full mapping (mom_reduce.hpp), to block g of the (I,Q) sub-problem's [pitch0, pitch0, nG] arrays.
 template <int n>
-__global__ void __launch_bounds__(kThreads) k_zmom_gemm(int n_mu, int L, int l_pad, int nG, int m_first, int M, int set_inner,
-                                                        const int *__restrict__ l_max, const double *__restrict__ greek,
-                                                        const double *__restrict__ tab, double *__restrict__ Zpp,
-                                                        double *__restrict__ Zmp) {
+__global__ void __launch_bounds__(kThreads) k_zmom_gemm(int n_mu, int L, int l_pad, int nG, int m_first, int M, int pitch,
+                                                        const int *__restrict__ slot, const int *__restrict__ l_max,
+                                                        const double *__restrict__ greek, const double *__restrict__ tab,
+                                                        double *__restrict__ Zpp, double *__restrict__ Zmp, int pitch0,
+                                                        double *__restrict__ Zpp0, double *__restrict__ Zmp0) {
   __shared__ double Xs[kKStep][kLd];  // Pi_l(+-mu_j)[b][c] at [k][(j, c) of the tile]
   __shared__ double Ys[kKStep][kLd];  // (Pi_l(mu_i) B_l)[a][b] at [k][(i, a) of the tile]
   const int N = n * n_mu, tiles = (N + kTile - 1) / kTile;
@@ -202,8 +208,8 @@ __global__ void __launch_bounds__(kThreads) k_zmom_gemm(int n_mu, int L, int l_p
   }
   // epilogue: Z = 2 fact A, fact = 1/2 at m = 0; Z-+ flips the blocks (a <= 1, c >= 2) and (a >= 2, c <= 1)
   const double scale = m == 0 ? 1.0 : 2.0;
-  const size_t slot = (size_t)(g % set_inner) + (size_t)set_inner * ((size_t)mi + (size_t)M * (g / set_inner));
-  double *out = (sg ? Zmp : Zpp) + slot * N * N;
+  double *out = (sg ? Zmp : Zpp) + (size_t)slot[g + nG * mi] * pitch * pitch;
+  double *out0 = (n >= 3 && m == 0 && Zpp0) ? (sg ? Zmp0 : Zpp0) + (size_t)g * pitch0 * pitch0 : nullptr;
 #pragma unroll
   for (int p = 0; p < 2; ++p)
 #pragma unroll
@@ -214,8 +220,21 @@ __global__ void __launch_bounds__(kThreads) k_zmom_gemm(int n_mu, int L, int l_p
         if (cj >= N || ri >= N) continue;
         double z = scale * acc[p][r][v];
         if (sg && ((ri % n <= 1) != (cj % n <= 1))) z = -z;
-        out[(size_t)cj * N + ri] = z;
+        out[(size_t)cj * pitch + ri] = z;
+        if (out0 && ri % n <= 1 && cj % n <= 1) out0[(size_t)((cj / n) * 2 + cj % n) * pitch0 + (ri / n) * 2 + ri % n] = z;
       }
+}
+
+// The device half of mom_m0_reducible (mom_reduce.hpp): *flag becomes 1 when an (I,Q) <-> (U,V) entry of a moment-0 block (blocks
+// 0 .. K - 1 of [pitch, pitch, K, M]) of either array is != 0.0 (a NaN counts).  *flag is zeroed on the stream in front.
+__global__ void __launch_bounds__(256) k_zmom_couples(int N, int n, int pitch, int K, const double *__restrict__ Zpp,
+                                                      const double *__restrict__ Zmp, int *flag) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x, NN = (size_t)N * N;
+  if (e >= NN * K) return;
+  const int k = (int)(e / NN), j = (int)((e - k * NN) / N), i = (int)(e - k * NN - (size_t)j * N);
+  if (((i % n) < 2) == ((j % n) < 2)) return;
+  const size_t o = i + (size_t)pitch * (j + (size_t)pitch * k);
+  if (Zpp[o] != 0.0 || Zmp[o] != 0.0) atomicOr(flag, 1);
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
@@ -282,69 +301,51 @@ void zmom_scalars(int L, int m_first, int M, int ldSeed, std::vector<double> &co
   }
 }
 
+// argument checks of a plan, before any HIP call: the text of the first one that fails, or null
+const char *zmom_check(int n, int n_mu, const double *mu, int nG, int l_pad, const int *l_max, const double *greek, int m_first, int M) {
+  if (n != 1 && n != 3 && n != 4) return "nStokes must be 1, 3 or 4";
+  if (n_mu < 1) return "n_mu must be at least 1";
+  if (nG < 1) return "nG must be at least 1";
+  if (M < 1) return "M must be at least 1";
+  if (m_first < 0) return "m_first must not be negative";
+  if (l_pad < 1) return "l_pad must be at least 1";
+  if (!mu || !l_max || !greek) return "null pointer";
+  for (int g = 0; g < nG; ++g)
+    if (l_max[g] < 1 || l_max[g] > l_pad) return "every l_max must be within 1..l_pad";
+  for (int i = 0; i < n_mu; ++i)
+    if (!(mu[i] > 0.0 && mu[i] <= 1.0)) return "all mu within compute_Z_moments have to be in ]0,1]";
+  if ((long long)n * n_mu > 46340 || (long long)nG * M > 65535 || (long long)m_first + M > 46340)
+    return "size out of range (N <= 46340, nG M <= 65535, m_first + M <= 46340)";
+  return nullptr;
+}
+
 int zmom_run(const char *fn, int device, int n, int n_mu, const double *mu, int nG, int l_pad, const int *l_max, const double *greek,
              int m_first, int M, int set_inner, double *Zpp, double *Zmp, double *gpu_ms) {
-  if (n != 1 && n != 3 && n != 4) return zmom_fail(fn, "nStokes must be 1, 3 or 4");
-  if (n_mu < 1) return zmom_fail(fn, "n_mu must be at least 1");
-  if (nG < 1) return zmom_fail(fn, "nG must be at least 1");
-  if (M < 1) return zmom_fail(fn, "M must be at least 1");
-  if (m_first < 0) return zmom_fail(fn, "m_first must not be negative");
-  if (l_pad < 1) return zmom_fail(fn, "l_pad must be at least 1");
-  if (!mu || !l_max || !greek || !Zpp || !Zmp) return zmom_fail(fn, "null pointer");
+  if (const char *bad = zmom_check(n, n_mu, mu, nG, l_pad, l_max, greek, m_first, M)) return zmom_fail(fn, bad);
+  if (!Zpp || !Zmp) return zmom_fail(fn, "null pointer");
   if (set_inner < 0 || (set_inner > 0 && nG % set_inner != 0)) return zmom_fail(fn, "set_inner must be 0 or a divisor of nG");
   if (set_inner == 0) set_inner = nG;
-  int L = 0;
-  for (int g = 0; g < nG; ++g) {
-    if (l_max[g] < 1 || l_max[g] > l_pad) return zmom_fail(fn, "every l_max must be within 1..l_pad");
-    L = std::max(L, l_max[g]);
-  }
-  for (int i = 0; i < n_mu; ++i)
-    if (!(mu[i] > 0.0 && mu[i] <= 1.0)) return zmom_fail(fn, "all mu within compute_Z_moments have to be in ]0,1]");
-  if ((long long)n * n_mu > 46340 || (long long)nG * M > 65535 || (long long)m_first + M > 46340)
-    return zmom_fail(fn, "size out of range (N <= 46340, nG M <= 65535, m_first + M <= 46340)");
   int rc = zmom_device(fn, device);
   if (rc != MOM_OK) return rc;
 
-  const int N = n * n_mu, ldSeed = m_first + M, tiles = (N + kTile - 1) / kTile;
-  const size_t nTab = (size_t)M * 2 * 3 * L * n_mu, nZ = (size_t)N * N * nG * M, nGreek = (size_t)l_pad * 6 * nG;
-  std::vector<double> coef, seed, smu((size_t)n_mu);
-  zmom_scalars(L, m_first, M, ldSeed, coef, seed);
-  for (int i = 0; i < n_mu; ++i) smu[i] = std::sqrt(1.0 - mu[i] * mu[i]);
-  MomDevBuf<double> d_mu, d_smu, d_coef, d_seed, d_greek, d_tab, d_Z;
-  MomDevBuf<int> d_lmax;
+  const int N = n * n_mu;
+  const size_t nZ = (size_t)N * N * nG * M;
+  // [N, N, nG, M] for set_inner = nG; [N, N, K, M, P] for nG = K P sets ordered k fastest and set_inner = K
+  std::vector<int> slot((size_t)nG * M);
+  for (int mi = 0; mi < M; ++mi)
+    for (int g = 0; g < nG; ++g) slot[g + (size_t)nG * mi] = (g % set_inner) + set_inner * (mi + M * (g / set_inner));
+  MomZmomPlan pl;
+  MomDevBuf<double> d_Z;
   hipStream_t st = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
   ZCHK(hipSetDevice(device));
   ZCHK(hipStreamCreate(&st));
   ZCHK(hipEventCreate(&ev[0]));
   ZCHK(hipEventCreate(&ev[1]));
-  ZCHK(mom_upload(d_mu, mu, (size_t)n_mu, st));
-  ZCHK(mom_upload(d_smu, smu.data(), smu.size(), st));
-  ZCHK(mom_upload(d_coef, coef.data(), coef.size(), st));
-  ZCHK(mom_upload(d_seed, seed.data(), seed.size(), st));
-  ZCHK(mom_upload(d_greek, greek, nGreek, st));
-  ZCHK(mom_upload(d_lmax, l_max, (size_t)nG, st));
-  ZCHK(d_tab.renew(nTab));
+  ZCHK(mom_zmom_plan(pl, n, n_mu, mu, nG, l_pad, l_max, greek, m_first, M, slot.data(), st));
   ZCHK(d_Z.renew(2 * nZ));
   ZCHK(hipEventRecord(ev[0], st));
-  hipLaunchKernelGGL(k_zmom_prt, dim3((unsigned)((M * 2 * n_mu + 63) / 64)), dim3(64), 0, st, n_mu, L, m_first, M, ldSeed, d_mu.get(),
-                     d_smu.get(), d_coef.get(), d_seed.get(), std::sqrt(1.5), std::sqrt(0.5), std::sqrt(1.0 / 6.0),
-                     0.5 * std::sqrt(1.5), d_tab.get());
-  ZCHK(hipGetLastError());
-  {
-    const dim3 grid((unsigned)(tiles * tiles), (unsigned)(nG * M), 2);
-    double *zp = d_Z.get(), *zm = d_Z.get() + nZ;
-    if (n == 1)
-      hipLaunchKernelGGL(k_zmom_gemm<1>, grid, dim3(kThreads), 0, st, n_mu, L, l_pad, nG, m_first, M, set_inner, d_lmax.get(),
-                         d_greek.get(), d_tab.get(), zp, zm);
-    else if (n == 3)
-      hipLaunchKernelGGL(k_zmom_gemm<3>, grid, dim3(kThreads), 0, st, n_mu, L, l_pad, nG, m_first, M, set_inner, d_lmax.get(),
-                         d_greek.get(), d_tab.get(), zp, zm);
-    else
-      hipLaunchKernelGGL(k_zmom_gemm<4>, grid, dim3(kThreads), 0, st, n_mu, L, l_pad, nG, m_first, M, set_inner, d_lmax.get(),
-                         d_greek.get(), d_tab.get(), zp, zm);
-  }
-  ZCHK(hipGetLastError());
+  ZCHK(mom_zmom_launch(pl, st, d_Z.get(), d_Z.get() + nZ, N, nullptr, nullptr, 0));
   ZCHK(hipEventRecord(ev[1], st));
   ZCHK(hipMemcpyAsync(Zpp, d_Z.get(), nZ * sizeof(double), hipMemcpyDeviceToHost, st));
   ZCHK(hipMemcpyAsync(Zmp, d_Z.get() + nZ, nZ * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -367,4 +368,66 @@ done:
 extern "C" int mom_z_moments(int device, int nStokes, int n_mu, const double *mu, int nG, int l_pad, const int *l_max,
                              const double *greek, int m_first, int M, int set_inner, double *Zpp, double *Zmp, double *gpu_ms) {
   return zmom_run("mom_z_moments", device, nStokes, n_mu, mu, nG, l_pad, l_max, greek, m_first, M, set_inner, Zpp, Zmp, gpu_ms);
+}
+
+// ---- plan and launch (mom_host.hpp): what mom_z_moments and the handle's staged scene setters (mom_scene.hip) share ---------
+const char *mom_zmom_check(int n, int n_mu, const double *mu, int nG, int l_pad, const int *l_max, const double *greek, int m_first,
+                           int M) {
+  return zmom_check(n, n_mu, mu, nG, l_pad, l_max, greek, m_first, M);
+}
+
+#define PCHK(call)                          \
+  do {                                      \
+    const hipError_t e__ = (call);          \
+    if (e__ != hipSuccess) return e__;      \
+  } while (0)
+
+hipError_t mom_zmom_plan(MomZmomPlan &pl, int n, int n_mu, const double *mu, int nG, int l_pad, const int *l_max, const double *greek,
+                         int m_first, int M, const int *slot, hipStream_t st) {
+  int L = 0;
+  for (int g = 0; g < nG; ++g) L = std::max(L, l_max[g]);
+  pl.n = n; pl.n_mu = n_mu; pl.L = L; pl.l_pad = l_pad; pl.nG = nG; pl.m_first = m_first; pl.M = M; pl.ldSeed = m_first + M;
+  zmom_scalars(L, m_first, M, pl.ldSeed, pl.coef, pl.seed);
+  pl.mu.assign(mu, mu + n_mu);
+  pl.smu.resize((size_t)n_mu);
+  for (int i = 0; i < n_mu; ++i) pl.smu[i] = std::sqrt(1.0 - mu[i] * mu[i]);
+  pl.slot.assign(slot, slot + (size_t)nG * M);
+  PCHK(mom_upload(pl.d_mu, pl.mu.data(), pl.mu.size(), st));
+  PCHK(mom_upload(pl.d_smu, pl.smu.data(), pl.smu.size(), st));
+  PCHK(mom_upload(pl.d_coef, pl.coef.data(), pl.coef.size(), st));
+  PCHK(mom_upload(pl.d_seed, pl.seed.data(), pl.seed.size(), st));
+  PCHK(mom_upload(pl.d_greek, greek, (size_t)l_pad * 6 * nG, st));
+  PCHK(mom_upload(pl.d_lmax, l_max, (size_t)nG, st));
+  PCHK(mom_upload(pl.d_slot, pl.slot.data(), pl.slot.size(), st));
+  return pl.d_tab.renew((size_t)M * 2 * 3 * L * n_mu);
+}
+
+hipError_t mom_zmom_launch(const MomZmomPlan &pl, hipStream_t st, double *Zpp, double *Zmp, int pitch, double *Zpp0, double *Zmp0,
+                           int pitch0) {
+  const int N = pl.n * pl.n_mu, tiles = (N + kTile - 1) / kTile;
+  if (pitch < N || (Zpp0 && (!Zmp0 || pitch0 < 2 * pl.n_mu))) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_zmom_prt, dim3((unsigned)((pl.M * 2 * pl.n_mu + 63) / 64)), dim3(64), 0, st, pl.n_mu, pl.L, pl.m_first, pl.M,
+                     pl.ldSeed, pl.d_mu.get(), pl.d_smu.get(), pl.d_coef.get(), pl.d_seed.get(), std::sqrt(1.5), std::sqrt(0.5),
+                     std::sqrt(1.0 / 6.0), 0.5 * std::sqrt(1.5), pl.d_tab.get());
+  PCHK(hipGetLastError());
+  const dim3 grid((unsigned)(tiles * tiles), (unsigned)(pl.nG * pl.M), 2);
+#define ZMOM_GEMM(NS)                                                                                                              \
+  hipLaunchKernelGGL(k_zmom_gemm<NS>, grid, dim3(kThreads), 0, st, pl.n_mu, pl.L, pl.l_pad, pl.nG, pl.m_first, pl.M, pitch,        \
+                     pl.d_slot.get(), pl.d_lmax.get(), pl.d_greek.get(), pl.d_tab.get(), Zpp, Zmp, pitch0, Zpp0, Zmp0)
+  if (pl.n == 1) ZMOM_GEMM(1);
+  else if (pl.n == 3) ZMOM_GEMM(3);
+  else ZMOM_GEMM(4);
+#undef ZMOM_GEMM
+  return hipGetLastError();
+}
+
+hipError_t mom_zmom_couples(MomZmomPlan &pl, hipStream_t st, int K, const double *Zpp, const double *Zmp, int pitch, int *coupled) {
+  const int N = pl.n * pl.n_mu;
+  const size_t total = (size_t)N * N * K;
+  if (!pl.d_flag) PCHK(pl.d_flag.renew(1));
+  PCHK(hipMemsetAsync(pl.d_flag, 0, sizeof(int), st));
+  hipLaunchKernelGGL(k_zmom_couples, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, N, pl.n, pitch, K, Zpp, Zmp, pl.d_flag.get());
+  PCHK(hipGetLastError());
+  PCHK(hipMemcpyAsync(coupled, pl.d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  return hipStreamSynchronize(st);
 }

@@ -291,6 +291,7 @@ extern "C" int mom_set_streams(mom_t *h, const double *qp_muN, const double *wt_
   h->h_mu.assign(qp_muN, qp_muN + N);
   h->h_wt.assign(wt_muN, wt_muN + N);
   h->strict = strict;
+  h->stage_z.drop(); h->stage_r.drop(); h->stage_d.drop();  // Greek sets staged for the previous nodes
   std::vector<double> sg(N);
   for (int i = 0; i < N; ++i) {
     const int comp = strict ? ((i + 1) % h->nS) : (i % h->nS) + 1;

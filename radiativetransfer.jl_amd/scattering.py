@@ -485,10 +485,12 @@ def aerosol_optics_partial(model: rt.vSmartMOM_Model, i_aer: int, d_optics: rt.A
     return aerosol_optics_partials(model, [(i_aer, d_optics, dτ_aer, band)], device=device)[0]
 
 
-def aerosol_optics_partials(model: rt.vSmartMOM_Model, items, device: Optional[int] = None):
+def aerosol_optics_partials(model: rt.vSmartMOM_Model, items, device: Optional[int] = None, resident: bool = False):
     """aerosol_optics_partial for every (i_aer, d_optics, dτ_aer, band) of `items`: the list of their OpticsPartials, with the
     derivative sets of ALL items and all moments formed in one compute_Z_moments_batch call -- with an int `device`, one
-    mom_z_moments call; with None, the host function per (item, moment), bitwise what aerosol_optics_partial gives per item."""
+    mom_z_moments call; with None, the host function per (item, moment), bitwise what aerosol_optics_partial gives per item.
+    resident = True: no matrix is formed; each partial carries its derivative Greek set as d_greeks = [(basis, set)] and the
+    handle forms dZpp / dZmp in its own memory (mom_scene_stage_greek_partials)."""
     items = list(items)
     bands = model.bands
     nAer = len(model.aerosol_optics) if bands is None else bands.nAer
@@ -505,18 +507,23 @@ def aerosol_optics_partials(model: rt.vSmartMOM_Model, items, device: Optional[i
             raise ValueError("the derivative Greek coefficients do not have the length of the aerosol's")
     if not items:
         return []
-    Zp, Zm = rt.compute_Z_moments_batch(pol, μ, [it[1].greek_coefs for it in items], M, device=device)  # [M, len(items), N, N]
+    if not resident:
+        Zp, Zm = rt.compute_Z_moments_batch(pol, μ, [it[1].greek_coefs for it in items], M, device=device)  # [M, len(items), N, N]
     N = pol.n * len(μ)
     out = []
     for j, (i_aer, d_optics, dτ_aer, band) in enumerate(items):
         K, k = (1 + nAer, 1 + i_aer) if bands is None else (1 + nAer * bands.nBand, 1 + i_aer + nAer * band)
-        dZpp, dZmp = np.zeros((M, K, N, N)), np.zeros((M, K, N, N))
-        dZpp[:, k], dZmp[:, k] = Zp[:, j], Zm[:, j]
+        dZpp = dZmp = d_greeks = None
+        if resident:
+            d_greeks = [(k, d_optics.greek_coefs)]
+        else:
+            dZpp, dZmp = np.zeros((M, K, N, N)), np.zeros((M, K, N, N))
+            dZpp[:, k], dZmp[:, k] = Zp[:, j], Zm[:, j]
         shape, at = ((nAer,), i_aer) if bands is None else ((bands.nBand, nAer), (band, i_aer))
         dω̃, dfᵗ = np.zeros(shape), np.zeros(shape)
         dω̃[at], dfᵗ[at] = d_optics.ω̃, d_optics.fᵗ
         out.append(rt.OpticsPartial(dτ_aer=None if dτ_aer is None else np.asarray(dτ_aer, dtype=np.float64), dω̃=dω̃, dfᵗ=dfᵗ, dZpp=dZpp,
-                                    dZmp=dZmp))
+                                    dZmp=dZmp, d_greeks=d_greeks))
     return out
 
 

@@ -62,7 +62,7 @@ def make_scene(nStokes: int, l_trunc: int, Nz: int, S: int, ν_lo: float = 12903
                sza: Optional[float] = None, vza=(0.0, 30.0, 60.0), vaz=(0.0, 45.0, 120.0), aerosol_total: float = 0.2,
                aerosol_p0: float = 800.0, aerosol_σp: float = 50.0, g: float = 0.7, albedo: float = 0.2,
                depol: float = 0.03, max_m: int = 3, seed: int = 1234, absorption: bool = True,
-               architecture=None, z_moments_on_device: bool = False) -> rt.vSmartMOM_Model:
+               architecture=None, z_moments_on_device: bool = False, z_resident: bool = False) -> rt.vSmartMOM_Model:
     pol = {1: rt.Stokes_I, 3: rt.Stokes_IQU, 4: rt.Stokes_IQUV}[nStokes]()
     if sza is None:
         # Sun at 60 deg -- unless the Gauss rule itself has a node at cosd(60) = 0.5 (odd number of nodes on [0, 1]):
@@ -72,7 +72,8 @@ def make_scene(nStokes: int, l_trunc: int, Nz: int, S: int, ν_lo: float = 12903
     params = rt.vSmartMOM_Parameters(
         polarization_type=pol, quadrature_type="GaussQuadHemisphere", max_m=max_m, l_trunc=l_trunc, depol=depol,
         sza=sza, vza=np.asarray(vza, dtype=np.float64), vaz=np.asarray(vaz, dtype=np.float64), brdf_albedo=albedo,
-        architecture=architecture or rt.default_architecture(), z_moments_on_device=z_moments_on_device)
+        architecture=architecture or rt.default_architecture(), z_moments_on_device=z_moments_on_device,
+        z_resident=z_resident)
     p_half = pressure_grid(Nz)
     ν = np.linspace(ν_lo, ν_hi, S)
     τ_rayl = rayleigh_tau(ν, p_half, depol)
