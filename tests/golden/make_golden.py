@@ -10,6 +10,7 @@ the C oracle and the HIP library can be checked against stored numbers too.
   cef.npz         Re/Im w(z) of the HW32SD approximation on a 64x64 (x, y) grid
   voigt_co2.npz   Voigt spectrum of the 16 lines of the reference's test file testCO2.data
                   (copied as data to tests/golden/) at two (p, T)
+  pcw_n300.npz, pcw_n112.npz   the PCW oracle (tests/pcw_oracle.py) at N_max = 300 and 112: see pcw_mid
 """
 import sys
 from pathlib import Path
@@ -104,10 +105,46 @@ def voigt_co2():
     print("voigt_co2: lines", len(out["nu_a"]), "max sigma", out["sigma_a"].max())
 
 
+def pcw_mid():
+    """The two middle PCW cases whose long-double oracle is too slow for a test (tests/pcw_oracle.py: MID_CASES), from
+    pcw_oracle.pcw_sums only: the inputs r, wx, the Float64 run's greek [6, 2 N - 1] and C, and their Float64-minus-long-double
+    differences (as Float64), which the GPU tests build their bounds from.
+      pcw_n300.npz  n300_r40; also sens_greek [6], sens_C: by how much of each array's largest magnitude the Float64 run moves when
+                    the Mie coefficients of the orders n > 256 are set to zero (the sensitivity condition of test_oracle_pcw.py)
+      pcw_n112.npz  n112_r650; also d_pairs [4]: max |Float64 - long double| of the four pair averages, and big_pairs [4], the
+                    largest magnitude of each (the matrices themselves are recomputed in Float64 where they are needed)"""
+    import pcw_oracle as po
+
+    def zero_above_256(a, b):
+        a, b = a.copy(), b.copy()
+        a[256:], b[256:] = 0, 0
+        return a, b
+
+    for case in ("n300_r40", "n112_r650"):
+        args = po.MID_CASES[case]
+        r_max, _, lam, n_r, n_i, _, _ = args
+        r, wx, N = po.case_inputs(case)
+        o64 = po.pcw_sums(r, wx, lam, n_r, n_i, r_max)
+        o80 = po.pcw_sums(r.astype(np.longdouble), wx.astype(np.longdouble), lam, n_r, n_i, r_max)
+        out = dict(r=r, wx=wx, greek=o64["greek"], C=o64["C"], d_greek=(o64["greek"] - o80["greek"]).astype(np.float64),
+                   d_C=(o64["C"] - o80["C"]).astype(np.float64), params=np.array(args + (N,)))
+        if case == "n300_r40":
+            cut = po.pcw_sums(r, wx, lam, n_r, n_i, r_max, ab_edit=zero_above_256)
+            out["sens_greek"] = np.abs(cut["greek"] - o64["greek"]).max(axis=1) / np.abs(o64["greek"]).max(axis=1)
+            out["sens_C"] = np.float64(np.abs(cut["C"] - o64["C"]).max() / np.abs(o64["C"]).max())
+        else:
+            out["d_pairs"] = np.array([float(np.abs(a - b).max()) for a, b in zip(o64["pairs"], o80["pairs"])])
+            out["big_pairs"] = np.array([float(np.abs(a).max()) for a in o64["pairs"]])
+        name = "pcw_" + case.split("_")[0] + ".npz"
+        np.savez_compressed(OUT / name, **out)
+        print(name, "N", N, "radii", len(r), {k: (v if v.size < 7 else v.shape) for k, v in out.items() if k.startswith(("sens", "d_p", "d_C"))})
+
+
 if __name__ == "__main__":
     small_iqu()
     natraj()
     cef()
     voigt_co2()
+    pcw_mid()
     for f in sorted(OUT.glob("*")):
         print(f.name, f.stat().st_size)

@@ -13,10 +13,13 @@ Nothing here is imported by the product."""
 import math
 from fractions import Fraction
 from functools import lru_cache
+from pathlib import Path
 
 import numpy as np
 
 import mie_oracle as mo
+
+GOLDEN_DIR = Path(__file__).resolve().parent / "golden"
 
 
 # ---- exact symbols ------------------------------------------------------------------------------------------------------------
@@ -171,9 +174,10 @@ def pair_averages(a, b, w, n_max_i):
     return tuple(out)
 
 
-def pcw_sums(r, wx, lam, n_r, n_i, r_max):
+def pcw_sums(r, wx, lam, n_r, n_i, r_max, ab_edit=None, pair_edit=None):
     """The sums of the PCW route in the dtype of r, none divided by C_sca: greek [6, 2 N - 1] (alpha .. zeta), C (C_sca, C_ext), the
-    four pair averages, N = get_n_max(2 pi r_max / lam)."""
+    four pair averages, N = get_n_max(2 pi r_max / lam).  ab_edit and pair_edit, (a, b) -> (a, b), are for the sensitivity tests
+    only: the first alters the Mie coefficients every sum reads, the second only those the pair averages read."""
     dt = r.dtype.type
     cdt = np.result_type(dt, np.complex64)
     pi = mo.pi_of(dt)
@@ -182,11 +186,13 @@ def pcw_sums(r, wx, lam, n_r, n_i, r_max):
     N = int(mo.n_max_of(np.float64(2 * np.pi * float(r_max) / float(lam))))
     ar, ai, br, bi, n_max_i = mo.mie_ab(x, n_r, n_i, dt, n_rows=N)
     a, b = (ar + 1j * ai).astype(cdt), (br + 1j * bi).astype(cdt)
+    if ab_edit is not None:
+        a, b = ab_edit(a, b)
     order = np.arange(1, N + 1)
     w2 = (2 * order + 1).astype(dt)
     C_sca = np.sum((2 * pi / k ** 2 * w2) * ((np.abs(a) ** 2 + np.abs(b) ** 2) @ wx))
     C_ext = np.sum((2 * pi / k ** 2 * w2) * ((a + b).real @ wx))
-    anam, anbm, bnam, bnbm = pair_averages(a, b, wx, n_max_i)
+    anam, anbm, bnam, bnbm = pair_averages(*((a, b) if pair_edit is None else pair_edit(a, b)), wx, n_max_i)
     an_m_bn, an_p_bn = (np.abs(a - b) ** 2) @ wx, (np.abs(a + b) ** 2) @ wx
     L = 2 * N - 1
     A, B = compute_wigner_values(N, N, L, dt)                       # [m, n, l]
@@ -244,3 +250,136 @@ SMALL_CASES = {
     "n32": (1.07, 49, 0.55, 1.5, 0.1, 0.3, 2.0),
     "nquad1": (0.12, 1, 0.55, 1.33, 0.0, 0.3, 2.0),
 }
+
+
+# the five middle cases, the same fields: (r_max, nquad, lam, n_r, n_i, r_m, sigma_g), the last two the size distribution
+# LogNormal(log r_m, log sigma_g), and the N_max each r_max is chosen for (MID_N_MAX; tests/test_oracle_pcw.py asserts it).  By what
+# they reach in csrc/mom_pcw.hip, Np = N_max rounded up to 16:
+#   n33_r64    Np = 48: macro tiles of 32 rows hold rows of two planes, a plane's last tile has one live row; 64 radii: no padding
+#   n48_r100   Np = 48 = N_max: the same with full planes; 100 radii: the second trip of k_pcw_diag's loop over the radii
+#   n49_r7     Np = 64; fewer radii than one chunk of 16; n_i = 0
+#   n112_r650  Np = 112 = 7 x 16, 105 macro tiles, G = 39 < 41 chunks: two chunk groups take a second chunk, the largest radii
+#   n300_r40   Np = 304 = 19 x 16; a lane of k_pcw_sums takes a second order n = tid + 257 (stored: tests/golden/pcw_n300.npz)
+# The distributions sit at 0.6 .. 0.75 r_max and are narrow, so that the largest radii and the highest orders carry weight.
+MID_CASES = {
+    "n33_r64": (1.1716, 64, 0.55, 1.45, 0.01, 0.6 * 1.1716, 1.5),
+    "n48_r100": (2.2761, 100, 0.55, 1.33, 0.005, 0.6 * 2.2761, 1.3),
+    "n49_r7": (2.352, 7, 0.55, 1.5, 0.0, 0.6 * 2.352, 1.5),
+    "n112_r650": (7.3745, 650, 0.55, 1.4, 0.002, 0.75 * 7.3745, 1.2),
+    "n300_r40": (23.1109, 40, 0.55, 1.33, 0.005, 0.75 * 23.1109, 1.2),
+}
+MID_N_MAX = {"n33_r64": 33, "n48_r100": 48, "n49_r7": 49, "n112_r650": 112, "n300_r40": 300}
+COMPUTED_MID_CASES = ("n33_r64", "n48_r100", "n49_r7")   # both oracle runs are made inside the tests; the other two are stored
+PAIR_MID_CASES = COMPUTED_MID_CASES + ("n112_r650",)       # the cases whose pair averages are compared
+
+# The rule of the device comparisons (PCW accuracy; section 4): relative to the array's largest magnitude, 8 x the
+# distance of the Float64 oracle to its long-double run, and not below 2^-46: for a short sum that distance is a chance value (0.3 ulp
+# on C at n48_r100).
+BOUND_FLOOR = 2.0 ** -46
+
+
+def rule_bound(x64, diff):
+    """x64: the Float64 oracle's array, diff: it minus the long-double run's -> the bound, relative to max |x64|"""
+    return max(8 * float(np.abs(diff).max()) / float(np.abs(x64).max()), BOUND_FLOOR)
+
+
+def case_inputs(case, dtype=np.float64):
+    """-> r, wx, N_max of a case: what the device calls take (mom_mie_pcw, mom_pcw_pair_averages)"""
+    r_max, nquad, lam, _, _, r_m, sigma_g = {**SMALL_CASES, **MID_CASES}[case]
+    r, wr = mo.gauleg_norm(nquad, 0, r_max, dtype)
+    return r, mo.weights_wx(r, wr, r_m, sigma_g), int(mo.n_max_of(np.float64(2 * np.pi * float(r_max) / float(lam))))
+
+
+def stored_case(case):
+    """-> the arrays of tests/golden/pcw_n300.npz or pcw_n112.npz (make_golden.pcw_mid)"""
+    return np.load(GOLDEN_DIR / ("pcw_" + case.split("_")[0] + ".npz"))
+
+
+@lru_cache(maxsize=None)
+def mid_reference(case):
+    """What the device is compared with, once per process and to be left unchanged: r, wx, N; the Float64 oracle's greek, C and
+    pairs on these inputs; d_greek [6, 2 N - 1] and d_C [2], its differences to the long-double oracle on the same (Float64) inputs;
+    d_pairs [4], the largest such difference of each pair matrix.  Both runs are made here for the three cases where they take
+    under a second.  n112_r650: the long-double run (7 s) is stored, the Float64 pair averages are formed here.  n300_r40 (23 s and
+    97 s): both are stored, pairs is None."""
+    r_max, _, lam, n_r, n_i, _, _ = MID_CASES[case]
+    r, wx, N = case_inputs(case)
+    if case in COMPUTED_MID_CASES:
+        o64 = pcw_sums(r, wx, lam, n_r, n_i, r_max)
+        o80 = pcw_sums(r.astype(np.longdouble), wx.astype(np.longdouble), lam, n_r, n_i, r_max)
+        assert o64["N"] == o80["N"] == N
+        return dict(r=r, wx=wx, N=N, greek=o64["greek"], C=o64["C"], pairs=o64["pairs"],
+                    d_greek=(o64["greek"] - o80["greek"]).astype(np.float64), d_C=(o64["C"] - o80["C"]).astype(np.float64),
+                    d_pairs=np.array([float(np.abs(a - b).max()) for a, b in zip(o64["pairs"], o80["pairs"])]))
+    z = stored_case(case)
+    assert np.array_equal(z["r"], r) and np.array_equal(z["wx"], wx) and int(z["params"][-1]) == N
+    out = dict(r=r, wx=wx, N=N, greek=z["greek"], C=z["C"], pairs=None, d_greek=z["d_greek"], d_C=z["d_C"], d_pairs=None)
+    if case == "n112_r650":
+        ar, ai, br, bi, n_max_i = mo.mie_ab(2 * np.pi / np.float64(lam) * r, n_r, n_i, np.float64, n_rows=N)
+        out.update(pairs=pair_averages(ar + 1j * ai, br + 1j * bi, wx, n_max_i), d_pairs=z["d_pairs"])
+    return out
+
+
+# ---- the symbols at the limit of mom_wigner_tables (n_max + l_max = 1900) --------------------------------------------------------
+
+def wigner_column(n, l):
+    """One (n, l) column of compute_wigner_values above, l the degree (the tables' third index minus one), as a scalar Float64
+    walk: the same statements on numpy scalars, the integers Python's.  -> {m: (A, B)} for max(|n - l|, 1) <= m <= n + l.  The array
+    form at (12, 950, 950) is 1900 steps on 950 x 950 arrays, minutes; tests/test_oracle_pcw.py holds the two forms bitwise equal."""
+    f, sq = np.float64, np.sqrt
+    s = f((-1) ** (l % 2)) * sq(f((l + 1) * (l + 2)) / f((2 * l + 1) * (2 * l + 2) * (2 * l + 3)))
+    for nn in range(2, n + 1):
+        s = -s * sq(f(nn * (2 * nn - 1) * ((nn + l) ** 2 - 1)) / f((nn + l) * (2 * (nn + l) + 1) * (nn * nn - 1)))
+
+    def D(k):
+        return (1 / f(k)) * sq(f((k * k - 1) * (k * k - (l - n) ** 2) * ((n + l + 1) ** 2 - k * k)))
+
+    m, lo = n + l, max(abs(n - l), 1)
+    a_cur, a_up, d_up = s, f(0), D(m + 1)
+    w_same = (a_cur * 2) * sq(f((n + l) * (n + l + 1) * n * (n + 1))) / f(l * (l + 1) - (l + n) * (l + n + 1) - n * (n + 1))
+    fac = np.power(np.array([f(max((l - 1) * l * (l + 1) * (l + 2), 1))]), f(-0.5))[0] if l >= 2 else f(0)
+    out = {}
+    for t in range(n + l - lo + 1):
+        if t > 0:
+            k = m + 1
+            d_k = D(k)
+            M_k = 1 - f(n * (n + 1) - l * (l + 1)) / f(k * (k + 1))
+            a_new = (1 / d_k) * (M_k * f(2 * m + 3) * a_cur - d_up * a_up)
+            a_up, a_cur, d_up = a_cur, a_new, d_k
+            if t % 2 == 0:
+                w_same = -w_same * sq(f((m + 2) ** 2 - (n - l) ** 2) / f((m + 1) ** 2 - (n - l) ** 2)) * \
+                    sq((1 - (1 / f(n + l - m))) * (1 + (1 / f(m + n + l + 2))))
+        w = w_same if t % 2 == 0 else f(0)
+        sg = 1 - 2 * ((m + n + l) % 2)
+        b = (f(sg) * fac) * (f(m * (m + 1) + sg * n * (n + 1)) * a_cur + (2 * sq(f(m * (m + 1) * n * (n + 1)))) * w)
+        out[m] = (float(a_cur), float(b) if l >= 2 else 0.0)
+        m -= 1
+    return out
+
+
+LIMIT_TABLE = (12, 950, 950)
+
+
+def limit_samples(count=60, seed=19570104):
+    """(m, n, l), 1-based as the tables are indexed, of the table LIMIT_TABLE: `count` seeded entries inside the triangle with
+    n + (l - 1) >= 1700, then every entry of the eight columns next to n = l = 950 (the 3 x 3 corner without (948, 948))"""
+    m_max, n_max, l_max = LIMIT_TABLE
+    rng = np.random.default_rng(seed)
+    out = []
+    while len(out) < count:
+        n, d = int(rng.integers(n_max - 99, n_max + 1)), int(rng.integers(-m_max, m_max + 1))
+        m, l = int(rng.integers(max(abs(d), 1), m_max + 1)), n - d + 1
+        if 1 <= l <= l_max and n + l - 1 >= 1700 and (m, n, l) not in out:
+            out.append((m, n, l))
+    for n in range(n_max - 2, n_max + 1):
+        for l in range(l_max - 2, l_max + 1):
+            if (n, l) != (n_max - 2, l_max - 2):
+                out += [(m, n, l) for m in range(max(abs(n - (l - 1)), 1), m_max + 1)]
+    return out
+
+
+@lru_cache(maxsize=None)
+def limit_exact():
+    """-> the samples and their exact symbols, arrays [len(samples)]"""
+    s = limit_samples()
+    return s, np.array([wigner_A_exact(*e) for e in s]), np.array([wigner_B_exact(*e) for e in s])
