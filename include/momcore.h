@@ -936,6 +936,33 @@ int mom_scene_stage_greek_partials(mom_t *h, int P, int nD, const int *basis, co
                                    const double *dgreek);
 int mom_scene_get_bases(mom_t *h, int which, int *edge, int *blocks, double *Zpp, double *Zmp);
 
+/* ---- delta-BGE truncation of Greek coefficients ---------------------------------------------------
+ * truncate_phase(mod::dBGE, aero) (src/Scattering/truncate_phase.jl:95-220) with the forward-mode partials of that function, for a
+ * batch of nG Greek sets of one length l_full, each with nP derivative sets, in one call.  The phase functions f11 = P beta,
+ * f12 = P2 (fac gamma), f34 = P2 (fac epsilon) are rebuilt from all l_full terms at the n_mu nodes; the three weighted fits (beta on
+ * P[:, 0:l_tr], gamma and epsilon on fac P2[:, 2:l_tr]) run over ALL nodes (the reference reads D_angle and does not use it).  Every
+ * normal matrix and right-hand side, of the value run and of each partial, is one product B^T diag(d) B with one more column B^T d'
+ * on v_mfma_f64_16x16x4; A c = b and A dc = db - dA c are solved by one Cholesky factor per (set, fit) held in LDS.  Float64,
+ * handle-free like mom_z_moments, error text: mom_last_global_error().
+ *   mu, w_mu [n_mu]           nodes in [-1, 1] and weights; the reference takes gausslegendre(l_full), the call keeps n_mu free
+ *   greek [l_full, 6, 1 + nP, nG]  l fastest, rows alpha, beta, gamma, delta, epsilon, zeta; row 0 of the third axis is the set,
+ *                             rows 1 .. nP are its derivative sets (any direction: the map is differentiated along what it is given)
+ *   l_tr                      the truncation order, 1 <= l_tr <= min(l_full, 128); above 128: MOM_EUNSUPPORTED
+ * Outputs (host):
+ *   greek_t [l_tr, 6, 1 + nP, nG]  beta^t = cl / c0, (alpha, delta, zeta)^t = (a - (beta - cl)) / c0, gamma^t and epsilon^t the fits
+ *                             themselves with exact zeros at l < 2, and the partials of all of them by the quotient rules
+ *   c0 [1 + nP, nG]           c0 = cl[0] and its partials: f^t = 1 - c0, df^t = -dc0.  (omega and k do not enter.)
+ *   status [nG]               0, or bit q set when fit q (0 beta, 1 gamma, 2 epsilon) met a divisor f or a Cholesky pivot (for
+ *                             fit 0 also c0) that is zero, negative (pivot) or not finite
+ *   gpu_ms or NULL            HIP-event time (ms) of the kernels
+ * Two calls are bitwise equal, and a set's rows do not depend on what else is in the batch.
+ * MOM_EINVAL, checked before the first HIP call: n_mu, nG, l_full or l_tr < 1; nP < 0; l_tr > l_full; a null pointer (gpu_ms
+ * excepted); a mu outside [-1, 1]; a weight or coefficient that is not finite; nG > 65535 or nP > 16383.
+ * MOM_ESINGULAR when a status word is not zero: the text names the first such set and its first fit, every row of such a set (and
+ * its c0 row) is NaN, every other set of the batch is as it would be alone. */
+int mom_truncate_phase(int device, int n_mu, const double *mu, const double *w_mu, int nG, int nP, int l_full, int l_tr,
+                       const double *greek, double *greek_t, double *c0, int *status, double *gpu_ms);
+
 #ifdef __cplusplus
 }
 #endif

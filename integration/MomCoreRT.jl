@@ -629,6 +629,37 @@ function z_bases(arch::MI355X, pol, μ, greek_rayleigh, aerosol_optics, max_m; z
 end
 # <<< z_moments
 
+# >>> truncate
+"""
+Scattering.truncate_phase(mod::δBGE, aero) (truncate_phase.jl:95-220) for every AerosolOptics of `optics` (one l_max for all) in
+ONE device call, with the forward-mode partials of the function along `partials[k]` (AerosolOptics holding ∂aero/∂θ, the same
+number per set; `nothing`: values only).  The nodes are gausslegendre(l_max) as in the reference; ω̃ and k pass through on the host,
+fᵗ = 1 - c₀ and ∂fᵗ = -∂c₀.  Returns the truncated sets and, per set, its partials.  `mod.l_max` above 128 is not built
+(MOM_EUNSUPPORTED): keep the host function there.  A set whose fits are singular is named by the error (MOM_ESINGULAR).
+"""
+function truncate_phase_batch(arch::MI355X, mod::δBGE, optics, partials = nothing)
+    nG = length(optics);  nP = partials === nothing ? 0 : length(partials[1])
+    l_full = length(optics[1].greek_coefs.β);  l_tr = mod.l_max
+    μ, w_μ = gausslegendre(l_full)
+    greek = zeros(Float64, l_full, 6, 1 + nP, nG)
+    for k in 1:nG, (r, a) in enumerate(vcat([optics[k]], nP == 0 ? [] : partials[k]))
+        g = a.greek_coefs
+        for (q, row) in enumerate((g.α, g.β, g.γ, g.δ, g.ϵ, g.ζ))
+            greek[:, q, r, k] .= row
+        end
+    end
+    greek_t = zeros(Float64, l_tr, 6, 1 + nP, nG);  c₀ = zeros(Float64, 1 + nP, nG)
+    status = zeros(Cint, nG);  ms = zeros(Float64, 1)
+    momcheck(MomCore.mom_truncate_phase(arch.device, l_full, collect(Float64, μ), collect(Float64, w_μ), nG, nP, l_full, l_tr, greek,
+                                        greek_t, c₀, status, ms))
+    coefs(r, k) = GreekCoefs((greek_t[:, q, r, k] for q in 1:6)...)
+    out = [AerosolOptics(greek_coefs = coefs(1, k), ω̃ = optics[k].ω̃, k = optics[k].k, fᵗ = 1 - c₀[1, k]) for k in 1:nG]
+    d_out = [[AerosolOptics(greek_coefs = coefs(1 + j, k), ω̃ = partials[k][j].ω̃, k = partials[k][j].k, fᵗ = -c₀[1 + j, k])
+              for j in 1:nP] for k in 1:nG]
+    return out, d_out
+end
+# <<< truncate
+
 # >>> z_resident
 """
 Scenes from Greek coefficients: the staged call sequence.  The Greek sets of the K bases (Rayleigh, then the aerosols) go to the

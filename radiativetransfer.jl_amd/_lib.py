@@ -177,6 +177,7 @@ SIGNATURES = {
     "mom_scene_stage_greeks": (C.c_int, [c_h, C.c_int, C.c_int, C.c_int, c_ip, c_dp, C.c_int]),
     "mom_scene_stage_greek_partials": (C.c_int, [c_h, C.c_int, C.c_int, c_ip, c_ip, C.c_int, c_ip, c_dp]),
     "mom_scene_get_bases": (C.c_int, [c_h, C.c_int, c_ip, c_ip, c_dp, c_dp]),
+    "mom_truncate_phase": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_ip, c_dp]),
 }
 
 _lib = None
@@ -1076,3 +1077,27 @@ def z_moments(nStokes: int, mu, greeks, M: int, m_first: int = 0, set_inner: int
     if rc != MOM_OK:
         raise MomError(rc, lib.mom_last_global_error().decode())
     return Zpp, Zmp, float(ms[0])
+
+
+TRUNCATE_MAX = 128   # the largest truncation order of mom_truncate_phase
+
+
+def truncate_phase(mu, w_mu, greek, l_tr: int, device: int = 0):
+    """mom_truncate_phase: greek [nG, 1 + nP, 6, l_full] (the ABI's array as a C array: sets, then the set and its nP derivative sets,
+    then the rows α, β, γ, δ, ϵ, ζ) truncated to l_tr terms at the nodes mu with weights w_mu.  Returns (greek_t [nG, 1 + nP, 6, l_tr],
+    c0 [nG, 1 + nP], status [nG], gpu_ms).  A set whose status word is not zero has NaN rows and is not an error of this wrapper:
+    MOM_ESINGULAR comes back as the status array, every other code raises MomError."""
+    lib = load()
+    mu, w_mu, greek = f64(mu), f64(w_mu), f64(greek)
+    if mu.ndim != 1 or w_mu.shape != mu.shape or greek.ndim != 4 or greek.shape[2] != 6:
+        raise ValueError("truncate_phase: mu and w_mu must be vectors of one length and greek [nG, 1 + nP, 6, l_full]")
+    nG, R, _, l_full = greek.shape
+    l_tr = int(l_tr)
+    ok = nG >= 1 and R >= 1 and 1 <= l_tr <= l_full
+    greek_t = np.empty((nG, R, 6, l_tr) if ok else (1,))   # a refused size is refused by the library
+    c0, status, ms = np.empty((max(nG, 1), max(R, 1))), np.zeros(max(nG, 1), dtype=np.int32), np.zeros(1)
+    rc = lib.mom_truncate_phase(device, len(mu), dp(mu), dp(w_mu), nG, R - 1, l_full, l_tr, dp(greek), dp(greek_t), dp(c0), ip(status),
+                                dp(ms))
+    if rc not in (MOM_OK, MOM_ESINGULAR):
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return greek_t, c0, status, float(ms[0])

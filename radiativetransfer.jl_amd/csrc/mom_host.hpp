@@ -384,6 +384,33 @@ hipError_t mom_zmom_launch(const MomZmomPlan &pl, hipStream_t st, double *Zpp, d
 hipError_t mom_zmom_couples(MomZmomPlan &pl, hipStream_t st, int K, const double *Zpp, const double *Zmp, int pitch, int *coupled);
 #pragma GCC visibility pop
 
+// mom_mie.hip: the tables P, P2, R2, T2 [l_max, n_mu] (mu fastest) of compute_legendre_poly from device nodes mu, by the kernel of
+// the spectral Mie call (k_mie_tables), bitwise the host's.  coef: mom_legendre_table_coef(l_max) on the device; pitau [2 n_mu]:
+// room for the first row of the kernel's pi / tau tables; leg: the four destinations.  Asynchronous on `st`.
+#pragma GCC visibility push(hidden)
+std::vector<double> mom_legendre_table_coef(int l_max);
+hipError_t mom_legendre_tables_launch(hipStream_t st, int n_mu, int l_max, const double *mu, const double *coef, double *pitau,
+                                      double *const *leg);
+#pragma GCC visibility pop
+
+// mom_trunc.hip: the delta-BGE truncation of a batch of Greek sets as a plan and a launch.  The plan holds what does not depend on the
+// destination: the nodes, the Greek rows [l_full, 6, 1 + nP, nG], the per-degree scalars, and the workspaces (tables, diagonal
+// weights, Gram products of one sub-batch of sets).  The launch writes greek_t [l_tr, 6, 1 + nP, nG], c0 [1 + nP, nG] and
+// status [nG] on the device; everything is asynchronous on `st`, so the plan and the destinations outlive the stream's work.
+constexpr int kMomTruncMax = 128;  // the largest l_tr: the edge of the normal matrix the solve keeps in LDS
+struct MomTruncPlan {
+  int n_mu = 0, nG = 0, nP = 0, l_full = 0, l_tr = 0, chunk = 0;  // chunk: sets per pass over the Gram workspace
+  std::vector<double> coef, fac;  // the host side of the asynchronous uploads
+  MomDevBuf<double> d_mu, d_w, d_coef, d_fac, d_greek, d_tab, d_D, d_G;
+};
+#pragma GCC visibility push(hidden)
+// the argument checks mom_truncate_phase makes before its first HIP call: the text of the first that fails, or null
+const char *mom_trunc_check(int n_mu, const double *mu, const double *w_mu, int nG, int nP, int l_full, int l_tr, const double *greek);
+hipError_t mom_trunc_plan(MomTruncPlan &pl, int n_mu, const double *mu, const double *w_mu, int nG, int nP, int l_full, int l_tr,
+                          const double *greek, hipStream_t st);
+hipError_t mom_trunc_launch(const MomTruncPlan &pl, hipStream_t st, double *greek_t, double *c0, int *status);
+#pragma GCC visibility pop
+
 // mom_scene.hip: what the two setters of the scene's partials share (mom_scene_set_partials there, mom_scene_set_optics_partials in
 // mom_optics.hip).  _check: 0 <= P <= 64 and dZpp / dZmp both or neither, else MOM_EINVAL with `fn` in the text; _reset: the partials,
 // outputs and workspaces of the previous call go and P becomes the scene's; _rest: everything but dtau / dvarpi / dzw (d_dual_in[0..2])

@@ -944,3 +944,12 @@ extern "C" int mom_mie_coefficients_dual(int device, int nX, const double *x, do
   double *const out[8] = {a_re, a_im, b_re, b_im, da_re, da_im, db_re, db_im};
   return mie_coefficients_run("mom_mie_coefficients_dual", true, device, nX, x, n_r, n_i, n_max, out);
 }
+
+// ---- the Legendre tables for other units (mom_host.hpp): k_mie_tables with the pi / tau part cut to its first row ------------
+std::vector<double> mom_legendre_table_coef(int l_max) { return mie_table_coef(l_max); }
+
+hipError_t mom_legendre_tables_launch(hipStream_t st, int n_mu, int l_max, const double *mu, const double *coef, double *pitau,
+                                      double *const *leg) {
+  launch_tables(st, n_mu, n_mu, 1, l_max, mu, coef, pitau, pitau + n_mu, leg);
+  return hipGetLastError();
+}

@@ -426,12 +426,15 @@ def _weighted_fit(w_μ, B, f, first, dfs=()):
     return c, dcs
 
 
-def truncate_phase(mod: δBGE, aero: rt.AerosolOptics, partials=None):
+def truncate_phase(mod: δBGE, aero: rt.AerosolOptics, partials=None, device: Optional[int] = None):
     """truncate_phase(mod::δBGE, aero) as the reference writes it: three weighted least-squares fits over ALL Gauss nodes
     (Δ_angle is read, the index set it selects is never used), β, δ, α, ζ rescaled by c₀ = cl[1], γᵗ and ϵᵗ the fits themselves,
     ω̃ and k unchanged, fᵗ = 1 - c₀.
     With `partials` (AerosolOptics holding ∂aero/∂θ, as compute_aerosol_optical_properties(autodiff=True) returns them) the result
-    is (truncated, [∂truncated/∂θ]): the forward-mode derivative of the fits and of the quotients, ∂fᵗ = -∂c₀, ∂ω̃ and ∂k passed on."""
+    is (truncated, [∂truncated/∂θ]): the forward-mode derivative of the fits and of the quotients, ∂fᵗ = -∂c₀, ∂ω̃ and ∂k passed on.
+    device: None is the numpy text below; an int runs a batch of one on that device (truncate_phase_batch)."""
+    if device is not None:
+        return truncate_phase_batch(mod, [aero], None if partials is None else [partials], device=device)[0]
     g = aero.greek_coefs
     l_tr = int(mod.l_max)
     μ, w_μ = gausslegendre(len(g.β))
@@ -469,6 +472,86 @@ def truncate_phase(mod: δBGE, aero: rt.AerosolOptics, partials=None):
             greek_coefs=rt.GreekCoefs(α=rescaled(g.α, dg.α), β=dc / c0 - cl * dc0 / c0 ** 2, γ=dγᵗ[j], δ=rescaled(g.δ, dg.δ), ϵ=dϵᵗ[j],
                                       ζ=rescaled(g.ζ, dg.ζ)), ω̃=p.ω̃, fᵗ=float(-dc0), k=p.k))
     return out, d_out
+
+
+_warned_host_truncation = False
+
+
+def _six(g: rt.GreekCoefs):
+    return (g.α, g.β, g.γ, g.δ, g.ϵ, g.ζ)
+
+
+def _device_truncation_built(mod: δBGE, optics, partials) -> bool:
+    """What mom_truncate_phase covers: l_tr <= 128 and Float64 coefficients.  Anything else takes the host text, with ONE warning per
+    process."""
+    global _warned_host_truncation
+    sets = list(optics) + [p for ps in (partials or []) for p in ps]
+    f32 = any(np.asarray(r).dtype == np.float32 for o in sets for r in _six(o.greek_coefs))
+    if int(mod.l_max) <= _lib.TRUNCATE_MAX and not f32:
+        return True
+    if not _warned_host_truncation:
+        import warnings
+        _warned_host_truncation = True
+        warnings.warn(f"truncate_phase on the device covers l_max <= {_lib.TRUNCATE_MAX} in Float64; this and every later request "
+                      "outside that takes the host path", RuntimeWarning, stacklevel=3)
+    return False
+
+
+def truncate_phase_batch(mod: δBGE, optics, partials=None, device: Optional[int] = 0):
+    """[truncate_phase(mod, o) for o in optics], or with `partials` (one list of AerosolOptics per set)
+    [truncate_phase(mod, o, p) for o, p in zip(optics, partials)], in ONE mom_truncate_phase call on `device`: the sets have one
+    length l_full, the nodes are gausslegendre(l_full) as in truncate_phase, ω̃ and k pass through on the host.  Sets with fewer
+    partials than the longest list are filled with zero derivative sets, whose rows are dropped again.
+    A set whose fits met a zero or non-finite divisor or pivot raises np.linalg.LinAlgError naming it.  device = None, l_max > 128
+    or Float32 coefficients: the host loop."""
+    optics = list(optics)
+    partials = None if partials is None else [list(p) for p in partials]
+    if partials is not None and len(partials) != len(optics):
+        raise ValueError("truncate_phase_batch: one list of partials per set")
+    if not optics:
+        return []
+    if device is None or not _device_truncation_built(mod, optics, partials):
+        return [truncate_phase(mod, o) if partials is None else truncate_phase(mod, o, partials[i]) for i, o in enumerate(optics)]
+    l_full, l_tr = len(optics[0].greek_coefs.β), int(mod.l_max)
+    nP = max((len(p) for p in partials), default=0) if partials is not None else 0
+    greek = np.zeros((len(optics), 1 + nP, 6, l_full))
+    for i, o in enumerate(optics):
+        for j, a in enumerate([o] + (partials[i] if partials is not None else [])):
+            rows = [np.asarray(r, dtype=np.float64) for r in _six(a.greek_coefs)]
+            if any(r.shape != (l_full,) for r in rows):
+                raise ValueError("truncate_phase_batch: every Greek set and derivative set of a batch has one length")
+            greek[i, j] = rows
+    μ, w_μ = gausslegendre(l_full)
+    greek_t, c0, status, _ = _lib.truncate_phase(μ, w_μ, greek, l_tr, device=device)
+    if status.any():
+        i = int(np.flatnonzero(status)[0])
+        fit = next(q for q in range(3) if (int(status[i]) >> q) & 1)
+        raise np.linalg.LinAlgError(f"truncate_phase_batch: set {i}, fit {fit} ({'βγϵ'[fit]}): singular weighted fit "
+                                    "(a zero or non-finite divisor or pivot)")
+    out = []
+    for i, o in enumerate(optics):
+        sets = [rt.GreekCoefs(*(greek_t[i, j, q].copy() for q in range(6))) for j in range(1 + nP)]
+        val = rt.AerosolOptics(greek_coefs=sets[0], ω̃=o.ω̃, fᵗ=float(1.0 - c0[i, 0]), k=o.k)
+        if partials is None:
+            out.append(val)
+        else:
+            out.append((val, [rt.AerosolOptics(greek_coefs=sets[1 + j], ω̃=p.ω̃, fᵗ=float(-c0[i, 1 + j]), k=p.k)
+                              for j, p in enumerate(partials[i])]))
+    return out
+
+
+def _truncate_grouped(mod: δBGE, optics, partials, device: Optional[int]):
+    """truncate_phase_batch for sets of several lengths: one call per distinct length, the results in the order of `optics`.  The
+    spectral Mie call cuts each wavelength's set to its own 2 n_max(λ) - 1 terms and the Gauss nodes of the fits follow the length,
+    so only sets of one length share a device call.  device = None: the host loop in the order of `optics`."""
+    out = [None] * len(optics)
+    lengths = [len(o.greek_coefs.β) for o in optics]
+    for L in (sorted(set(lengths)) if device is not None else [None]):
+        idx = [i for i in range(len(optics)) if L is None or lengths[i] == L]
+        res = truncate_phase_batch(mod, [optics[i] for i in idx], None if partials is None else [partials[i] for i in idx], device=device)
+        for i, r in zip(idx, res):
+            out[i] = r
+    return out
 
 
 def aerosol_optics_partial(model: rt.vSmartMOM_Model, i_aer: int, d_optics: rt.AerosolOptics, dτ_aer=None, band: Optional[int] = None,
@@ -541,14 +624,17 @@ def sum_partials(partials) -> rt.OpticsPartial:
 
 
 def band_aerosol_optics(mie_model: MieModel, λ_bands, λ_ref: float, τ_ref: float, profile, nᵣ=None, nᵢ=None, n_ref=None,
-                        autodiff: bool = False, wrt=_SIZE_PARAMETERS):
+                        autodiff: bool = False, wrt=_SIZE_PARAMETERS, device: Optional[int] = None):
     """One aerosol type in every band of a band-resolved scene, as model_from_parameters.jl:117-165 sets it up: the Mie run at each
     band centre λ_bands [nBand] and at λ_ref in ONE compute_spectral_aerosol_optical_properties call over [λ_bands..., λ_ref],
     truncate_phase(mie_model.truncation_type) per band, and τ_aer[b] = τ_ref * (k_b / k_ref) * profile (profile [Nz]: the layers'
     shares of the column, getAerosolLayerOptProp).  nᵣ, nᵢ [nBand]: the refractive index per band (default: the aerosol's), n_ref =
     (nᵣ, nᵢ) at λ_ref (default: the aerosol's).  Returns (aerosol_optics [nBand], τ_aer [nBand, Nz]); with autodiff=True also
     (d_optics [nBand][len(wrt)], dτ_aer [len(wrt), nBand, Nz]): the partials of each band's truncated optics and of τ_aer, which
-    depends on a parameter through k_b and k_ref.  An index parameter in `wrt` is the SAME change of every wavelength's index."""
+    depends on a parameter through k_b and k_ref.  An index parameter in `wrt` is the SAME change of every wavelength's index.
+    device: None truncates band by band on the host; an int truncates all bands with all their partials in one truncate_phase_batch
+    call on that device per distinct length of the bands' Greek sets (the spectral call cuts each to 2 n_max(λ) - 1 terms and the
+    Gauss nodes of the fits follow that length, so only bands of one length share a call)."""
     λ_bands = np.atleast_1d(np.asarray(λ_bands, dtype=np.float64))
     nB = λ_bands.size
     profile = np.asarray(profile, dtype=np.float64).reshape(-1)
@@ -560,14 +646,9 @@ def band_aerosol_optics(mie_model: MieModel, λ_bands, λ_ref: float, τ_ref: fl
                                                       autodiff=autodiff, wrt=wrt)
     raw, parts = res if autodiff else (res, None)
     k_ref = raw[nB].k
-    optics, d_optics = [], []
-    for b in range(nB):
-        if autodiff:
-            o, d = truncate_phase(mie_model.truncation_type, raw[b], parts[b])
-            d_optics.append(d)
-        else:
-            o = truncate_phase(mie_model.truncation_type, raw[b])
-        optics.append(o)
+    res_t = _truncate_grouped(mie_model.truncation_type, raw[:nB], parts[:nB] if autodiff else None, device)
+    optics = [r[0] for r in res_t] if autodiff else res_t
+    d_optics = [r[1] for r in res_t] if autodiff else []
     τ_aer = np.array([τ_ref * (o.k / k_ref) * profile for o in optics])
     if not autodiff:
         return optics, τ_aer
