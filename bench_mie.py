@@ -4,7 +4,9 @@
 parameters beside the value call in the same process (committed as profiles/mie_dual_bench.json).  `bench_mie.py --spectral
 OUT.json`: 16 wavelengths in one call (mom_mie_nai2_spectral) beside 16 single calls (committed as
 profiles/mie_spectral_bench.json).  `bench_mie.py --pcw OUT.json`: the Domke-PCW route (csrc/mom_pcw.hip, mom_mie_pcw) beside the
-NAI-2 call at the reference's test point (committed as profiles/mie_pcw_bench.json).
+NAI-2 call at the reference's test point (committed as profiles/mie_pcw_bench.json).  `bench_mie.py --pcw-dual OUT.json`: the PCW
+call with the Jacobian rows of all four aerosol parameters (mom_mie_pcw_dual) beside the value call in the same process (committed
+as profiles/mie_pcw_dual_bench.json).
 
 Two points: the reference's own test point (test/test_Scattering.jl: λ = 0.55 µm, r_max = 30 µm, nquad_radius = 2500,
 m = 1.3 + 0.001i, LogNormal(log 0.3, log 6.82): x_max = 342.7, n_max = 381, n_μ = 761) and a small one (r_max = 1 µm, 37 radii:
@@ -220,6 +222,71 @@ def run_pcw():
     return out
 
 
+def run_pcw_dual_point(p, repeats=7):
+    """mom_mie_pcw_dual with the (r_m, σ_g) weight rows and the index rows (five output rows) beside mom_mie_pcw, alternating in one
+    process: the HIP-event times of the three kernel groups (median and minimum over `repeats` calls after one that loads the code
+    objects), their ratio, and the two conditions the shared work is held to -- the four-parameter call under five value calls (what
+    one-sided finite differences cost), symbols_and_sums under twice the value call's (all rows share one walk over the symbols).
+    Two more legs, the size rows alone and the index rows alone (three output rows each), show what a row costs in each stage.
+    Flop model of the Gram products, as run: three weight rows on the lower triangle of 32 x 32 macro tiles and the index rows'
+    non-symmetric product on the full square, each over the radii rounded up to 16; the rate divides by the whole radius_averages
+    group (diagonal sums, products, chunk sums)."""
+    import rtamd
+    sc = rtamd.scattering
+    aer = sc.Aerosol(sc.LogNormal(math.log(p["r_m"]), math.log(p["sigma_g"])), p["n_r"], p["n_i"])
+    model = sc.make_mie_model(sc.PCW(), aer, p["lam"], None, None, p["r_max"], p["nquad_radius"])
+    r, w, N, index_rows, _ = sc.pcw_jacobian_inputs(model, sc.ALL_AEROSOL_PARAMETERS)
+    dual = lambda rows, index: rtamd._lib.mie_pcw_dual(r, rows, p["lam"], p["n_r"], p["n_i"], N, index_rows=index)[2]
+    calls = {"value": lambda: rtamd._lib.mie_pcw(r, w[0], p["lam"], p["n_r"], p["n_i"], N)[2],
+             "four_parameters": lambda: dual(w, index_rows),
+             "size_rows_only": lambda: dual(w, False),         # three output rows: w_x and its (r_m, σ_g) rows
+             "index_rows_only": lambda: dual(w[:1], True)}     # three output rows: w_x and its (nᵣ, nᵢ) rows
+    groups = ("coefficients", "radius_averages", "symbols_and_sums")
+    ms, wall = {k: [] for k in calls}, {k: [] for k in calls}
+    for c in calls.values():
+        c()
+    for _ in range(repeats):
+        for k, c in calls.items():
+            t0 = time.perf_counter()
+            ms[k].append(c())
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+    legs = {}
+    for k in calls:
+        m = np.array(ms[k])
+        legs[k] = {"repeats": repeats,
+                   "kernels_ms_median": {**{g: float(v) for g, v in zip(groups, np.median(m, axis=0))}, "sum": float(np.median(m.sum(axis=1)))},
+                   "kernels_ms_min": {**{g: float(v) for g, v in zip(groups, m.min(axis=0))}, "sum": float(m.sum(axis=1).min())},
+                   "device_call_wall_ms_median": float(np.median(wall[k]))}
+    whole = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        sc.aerosol_optics_jacobian(model)
+        whole.append((time.perf_counter() - t0) * 1e3)
+    v, d = legs["value"]["kernels_ms_median"], legs["four_parameters"]["kernels_ms_median"]
+    ratio = {g: d[g] / v[g] for g in groups + ("sum",)}
+    Np, ld = -(-N // 16) * 16, -(-r.size // 16) * 16
+    mrows = 4 * Np // 32
+    flop_run = 2.0 * (3 * (mrows * (mrows + 1) // 2) + mrows * mrows) * 32 * 32 * ld
+    t = d["radius_averages"] * 1e-3
+    conditions = {"four_parameters_under_five_value_calls": bool(d["sum"] < 5 * v["sum"]),
+                  "symbols_and_sums_under_twice_the_value_calls": bool(d["symbols_and_sums"] < 2 * v["symbols_and_sums"])}
+    over = [g for g in groups if d[g] >= (2 if g == "symbols_and_sums" else 5) * v[g]]
+    return {"n_radii": int(r.size), "N_max": int(N), "degrees": int(2 * N - 1), "output_rows": int(w.shape[0] + 2), **legs,
+            "aerosol_optics_jacobian_wall_ms_median": float(np.median(whole)),
+            "four_parameters_over_value": ratio, "conditions": conditions, "stages_over": over,
+            "radius_averages": {"flop_run": flop_run,
+                                "roofline": {"bound": "mfma", "achieved": flop_run / t / 1e12, "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s",
+                                             "frac": flop_run / t / 1e12 / PEAK_FP64_MFMA_TFLOPS}}}
+
+
+def run_pcw_dual():
+    out = {"metric": "Mie Domke-PCW aerosol optics with the Jacobian rows of (r_m, σ_g, nᵣ, nᵢ) at the reference's test point: kernels "
+                     "of one call", "unit": "ms"}
+    out["reference_test_point"] = run_pcw_dual_point(POINTS["reference_test_point"])
+    out["value"] = out["reference_test_point"]["four_parameters"]["kernels_ms_median"]["sum"]
+    return out
+
+
 def run_spectral():
     out = {"metric": "Mie NAI-2 aerosol optics, 16 wavelengths (0.4 .. 2.2 µm) in one spectral call: wall time of the public call",
            "unit": "ms"}
@@ -245,8 +312,10 @@ def run_dual():
 
 
 if __name__ == "__main__":
-    argv = [a for a in sys.argv[1:] if a not in ("--dual", "--spectral", "--pcw")]
-    if "--pcw" in sys.argv[1:]:
+    argv = [a for a in sys.argv[1:] if a not in ("--dual", "--spectral", "--pcw", "--pcw-dual")]
+    if "--pcw-dual" in sys.argv[1:]:
+        res = run_pcw_dual()
+    elif "--pcw" in sys.argv[1:]:
         res = run_pcw()
     else:
         res = run_dual() if "--dual" in sys.argv[1:] else (run_spectral() if "--spectral" in sys.argv[1:] else run())

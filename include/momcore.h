@@ -880,6 +880,29 @@ int mom_pcw_pair_averages(int device, int nR, const double *r, const double *w, 
                           double *anam_re, double *anam_im, double *anbm_re, double *anbm_im, double *bnam_re, double *bnam_im,
                           double *bnbm_re, double *bnbm_im);
 
+/* mom_mie_pcw with Jacobian rows: the partials of every sum with respect to (r_m, sigma_g, n_r, n_i), PCW's own second route to what
+ * mom_mie_nai2_dual gives.
+ *   w [nW, nR]              row-major, 1 <= nW <= MOM_PCW_MAX_WEIGHT_ROWS: row 0 is w_x, a further row is d w_x / d theta of a
+ *                           size-distribution parameter (every sum is linear in w; a row may be negative)
+ *   flags                   0 or MOM_PCW_INDEX_ROWS: two more output rows; nO = nW + 2 (flag set)
+ * Outputs (host), everything else as for mom_mie_pcw:
+ *   greek [nO, 6, 2 N_max - 1], C [nO, 2]
+ * Row k < nW holds the sums of weight row k, bitwise what mom_mie_pcw writes when handed w[k], with or without the flag and whatever
+ * else is in the call.  Row nW is d/dn_r and row nW + 1 is d/dn_i of row 0's sums: the coefficient kernel carries d/dm (as for
+ * mom_mie_nai2_dual; n_max,i, the start of the downward recurrence and the strict mask of the pair averages are integers, taken on
+ * the values), the sums over the radii that keep order n_max,i take one complex sum each, and the pair averages take ONE
+ * non-symmetric product Y~ diag(w_0) X~^T on v_mfma_f64_16x16x4, Y = [Re a'; Im a'; Re b'; Im b'], from which both parameters follow
+ * by a row map.  All nO rows share one walk over the Wigner symbols.  Two calls are bitwise equal.
+ * MOM_EINVAL: the list of mom_mie_pcw, nW outside 1..3, a flag other than MOM_PCW_INDEX_ROWS. */
+enum { MOM_PCW_MAX_WEIGHT_ROWS = 3, MOM_PCW_INDEX_ROWS = 1 /* flag */ };
+int mom_mie_pcw_dual(int device, int nR, const double *r, int nW, const double *w, double lambda, double n_r, double n_i,
+                     int N_max, int flags, double *greek, double *C, double *gpu_ms);
+
+/* Test access: mom_pcw_pair_averages for the arguments of mom_mie_pcw_dual: pairs [nO, 8, N_max, N_max], per row the eight arrays
+ * in the order and entry convention of mom_pcw_pair_averages; rows nW and nW + 1 their partials.  MOM_EINVAL as mom_mie_pcw_dual. */
+int mom_pcw_pair_averages_dual(int device, int nR, const double *r, int nW, const double *w, double lambda, double n_r,
+                               double n_i, int N_max, int flags, double *pairs);
+
 /* ---- Phase-matrix Fourier moments ---------------------------------------------------------------
  * Scattering.compute_Z_moments(mod, mu, greek_coefs, m) (src/Scattering/compute_Z_matrices.jl:5-84) for a batch of nG sets of Greek
  * coefficients and the Fourier moments m_first .. m_first + M - 1 in one call: the generalised spherical functions P, R, T of

@@ -13,4 +13,4 @@ from .corert import (MI355X, rt_run, rt_run_dual, ScenePartial, OpticsPartial, r
 from .scattering import (LogNormal, Aerosol, NAI2, PCW, δBGE, make_mie_model, compute_wigner_values, compute_aerosol_optical_properties,  # noqa: F401,E402
                          compute_spectral_aerosol_optical_properties, spectral_mie_inputs,
                          compute_ref_aerosol_extinction, truncate_phase, truncate_phase_batch, ALL_AEROSOL_PARAMETERS, aerosol_derivs,
-                         aerosol_optics_partial, aerosol_optics_partials, band_aerosol_optics)
+                         aerosol_optics_partial, aerosol_optics_partials, band_aerosol_optics, aerosol_optics_jacobian)

@@ -51,6 +51,7 @@ CEF_HW32SD, CEF_HW32VOIGT = 0, 1
 MOM_MIE_FULL_K = 1   # mom_mie_nai2 flag: every radius tile sums l to the global n_max (test access; bitwise the same result)
 MOM_PCW_MAX_ORDER, MOM_WIGNER_MAX_TABLE_BYTES = 640, 1 << 30   # mom_mie_pcw: largest N_max; mom_wigner_tables: largest table
 MOM_MIE_DUAL_MAX_WEIGHT_ROWS, MOM_MIE_INDEX_ROWS = 3, 2   # mom_mie_nai2_dual: at most 3 weight rows; 2 more output rows (n_r, n_i)
+MOM_PCW_MAX_WEIGHT_ROWS, MOM_PCW_INDEX_ROWS = 3, 1   # mom_mie_pcw_dual: at most 3 weight rows; the flag that asks for the (n_r, n_i) rows
 
 
 class MomError(RuntimeError):
@@ -173,6 +174,10 @@ SIGNATURES = {
     "mom_mie_pcw": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, c_dp, c_dp, c_dp]),
     "mom_wigner_tables": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp]),
     "mom_pcw_pair_averages": (C.c_int, [C.c_int, C.c_int, c_dp, c_dp, C.c_double, C.c_double, C.c_double, C.c_int] + [c_dp] * 8),
+    "mom_mie_pcw_dual": (C.c_int, [C.c_int, C.c_int, c_dp, C.c_int, c_dp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, c_dp, c_dp,
+                                   c_dp]),
+    "mom_pcw_pair_averages_dual": (C.c_int, [C.c_int, C.c_int, c_dp, C.c_int, c_dp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                                             c_dp]),
     "mom_z_moments": (C.c_int, [C.c_int, C.c_int, C.c_int, c_dp, C.c_int, C.c_int, c_ip, c_dp, C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp]),
     "mom_scene_stage_greeks": (C.c_int, [c_h, C.c_int, C.c_int, C.c_int, c_ip, c_dp, C.c_int]),
     "mom_scene_stage_greek_partials": (C.c_int, [c_h, C.c_int, C.c_int, c_ip, c_ip, C.c_int, c_ip, c_dp]),
@@ -1039,6 +1044,43 @@ def pcw_pair_averages(r, w, lam, n_r, n_i, N_max: int, device: int = 0):
     if rc != MOM_OK:
         raise MomError(rc, lib.mom_last_global_error().decode())
     return tuple(out[2 * q] + 1j * out[2 * q + 1] for q in range(4))
+
+
+def _pcw_dual_args(fn: str, r, w, index_rows: bool):
+    r, w = f64(r), f64(w)
+    if w.ndim == 1:
+        w = w[None, :]
+    if r.ndim != 1 or w.ndim != 2 or w.shape[1] != r.shape[0]:
+        raise ValueError(f"{fn}: r [nR] must be a vector and w [nW, nR] its weight rows")
+    nO = w.shape[0] + (2 if index_rows else 0)
+    return r, np.ascontiguousarray(w), nO, MOM_PCW_INDEX_ROWS if index_rows else 0
+
+
+def mie_pcw_dual(r, w, lam, n_r, n_i, N_max: int, index_rows: bool = False, device: int = 0, flags=None):
+    """mom_mie_pcw_dual: r [nR] ascending, w [nW, nR], row 0 = w_x, further rows its partials.  Returns (greek [nO, 6, 2 N_max - 1]
+    not divided by C_sca, C [nO, 2], gpu_ms [3]), nO = nW + 2 with index_rows: then the last two rows are d/dn_r and d/dn_i of row
+    0.  flags (test access) replaces the flag word index_rows stands for."""
+    lib = load()
+    r, w, nO, fl = _pcw_dual_args("mie_pcw_dual", r, w, index_rows)
+    N_max = int(N_max)
+    greek, Cx, ms = np.empty((nO, 6, max(2 * N_max - 1, 1))), np.empty((nO, 2)), np.zeros(3)
+    rc = lib.mom_mie_pcw_dual(device, len(r), dp(r), w.shape[0], dp(w), float(lam), float(n_r), float(n_i), N_max,
+                              fl if flags is None else int(flags), dp(greek), dp(Cx), dp(ms))
+    if rc != MOM_OK:
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return greek, Cx, ms
+
+
+def pcw_pair_averages_dual(r, w, lam, n_r, n_i, N_max: int, index_rows: bool = False, device: int = 0):
+    """mom_pcw_pair_averages_dual: complex [nO, 4, N_max, N_max]: per row (anam, anbm, bnam, bnbm), entry [m - 1, n - 1] for m >= n."""
+    lib = load()
+    r, w, nO, fl = _pcw_dual_args("pcw_pair_averages_dual", r, w, index_rows)
+    N_max = int(N_max)
+    out = np.empty((nO, 8, max(N_max, 1), max(N_max, 1)))
+    rc = lib.mom_pcw_pair_averages_dual(device, len(r), dp(r), w.shape[0], dp(w), float(lam), float(n_r), float(n_i), N_max, fl, dp(out))
+    if rc != MOM_OK:
+        raise MomError(rc, lib.mom_last_global_error().decode())
+    return out[:, 0::2] + 1j * out[:, 1::2]
 
 
 def pack_greeks(greeks, fn: str):

@@ -17,6 +17,9 @@
 //   (e) k_pcw_sums     one workgroup per degree l, lanes over n: each lane walks its (n, l) column of symbols downward in m from
 //                      m = n + l and accumulates the five sums of compute_Sl; fixed-order reduction; writes the six Greek rows
 // Nothing is added with floating-point atomics: two calls are bitwise equal.
+// mom_mie_pcw_dual runs the same five kernels with Jacobian rows: up to three weight rows (w_x and its partials in a size
+// parameter: every sum is linear in w) and, with MOM_PCW_INDEX_ROWS, d / dn_r and d / dn_i of row 0 from the Dual form of (a).  The
+// kernels are templates over the row counts; a row's statements do not depend on them, so a weight row is bitwise the value call's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -106,24 +109,55 @@ __global__ void __launch_bounds__(64) k_wigner_tables(int m_max, int n_max, int 
 }
 
 // ---- (b) the sums over the radii that keep order n = n_max,i ---------------------------------------------------------------
-// planes: Re a, Im a, Re b, Im b at stride ps; diag [4, Np]: |a + b|^2, |a - b|^2, |a|^2 + |b|^2, Re(a + b), each weighted
+// planes: Re a, Im a, Re b, Im b at stride ps; diag [nO, 4, Np]: |a + b|^2, |a - b|^2, |a|^2 + |b|^2, Re(a + b), weighted, one row
+// per weight row w [NW, ld]: a row's statements do not depend on NW.  IDX: planes 4 .. 7 hold a' = da / dm, b' = db / dm, and two
+// more rows follow, d / dn_r and d / dn_i of row 0.  Each quantity takes ONE complex sum, z = sum w_0 conj(u) u' for |u|^2 and
+// sum w_0 u' for Re u: d / dn_r u = u' and d / dn_i u = i u' (Cauchy-Riemann), so the rows are (2 Re z, -2 Im z) and (Re z, -Im z).
+template <int NW, bool IDX>
 __global__ void __launch_bounds__(64) k_pcw_diag(int nR, int ld, int Np, size_t ps, const double *__restrict__ pl, const double *__restrict__ w,
                                                  double *__restrict__ diag) {
   const int p = blockIdx.x, lane = threadIdx.x;
   const double *aR = pl + (size_t)p * ld, *aI = aR + ps, *bR = aI + ps, *bI = bR + ps;
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  double s[NW][4], zr[4] = {0.0, 0.0, 0.0, 0.0}, zi[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int k = 0; k < NW; ++k)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[k][q] = 0.0;
   for (int i = lane; i < nR; i += 64) {
-    const double ar = aR[i], ai = aI[i], br = bR[i], bi = bI[i], wi = w[i];
-    s[0] += wi * ((ar + br) * (ar + br) + (ai + bi) * (ai + bi));
-    s[1] += wi * ((ar - br) * (ar - br) + (ai - bi) * (ai - bi));
-    s[2] += wi * ((ar * ar + ai * ai) + (br * br + bi * bi));
-    s[3] += wi * (ar + br);
+    const double ar = aR[i], ai = aI[i], br = bR[i], bi = bI[i];
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+      const double wi = w[(size_t)k * ld + i];
+      s[k][0] += wi * ((ar + br) * (ar + br) + (ai + bi) * (ai + bi));
+      s[k][1] += wi * ((ar - br) * (ar - br) + (ai - bi) * (ai - bi));
+      s[k][2] += wi * ((ar * ar + ai * ai) + (br * br + bi * bi));
+      s[k][3] += wi * (ar + br);
+    }
+    if constexpr (IDX) {
+      const double dar = aR[4 * ps + i], dai = aI[4 * ps + i], dbr = bR[4 * ps + i], dbi = bI[4 * ps + i], wi = w[i];
+      const double pr = ar + br, pi = ai + bi, mr = ar - br, mi = ai - bi, dpr = dar + dbr, dpi = dai + dbi, dmr = dar - dbr, dmi = dai - dbi;
+      zr[0] += wi * (pr * dpr + pi * dpi), zi[0] += wi * (pr * dpi - pi * dpr);
+      zr[1] += wi * (mr * dmr + mi * dmi), zi[1] += wi * (mr * dmi - mi * dmr);
+      zr[2] += wi * ((ar * dar + ai * dai) + (br * dbr + bi * dbi)), zi[2] += wi * ((ar * dai - ai * dar) + (br * dbi - bi * dbr));
+      zr[3] += wi * dpr, zi[3] += wi * dpi;
+    }
   }
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
+  for (int k = 0; k < NW; ++k)
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) s[q] += __shfl_xor(s[q], off);
-    if (lane == 0) diag[(size_t)q * Np + p] = s[q];
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) s[k][q] += __shfl_xor(s[k][q], off);
+      if (lane == 0) diag[((size_t)k * 4 + q) * Np + p] = s[k][q];
+    }
+  if constexpr (IDX) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) zr[q] += __shfl_xor(zr[q], off), zi[q] += __shfl_xor(zi[q], off);
+      const double two = q < 3 ? 2.0 : 1.0;
+      if (lane == 0) diag[((size_t)NW * 4 + q) * Np + p] = two * zr[q], diag[((size_t)(NW + 1) * 4 + q) * Np + p] = -two * zi[q];
+    }
   }
 }
 
@@ -133,56 +167,78 @@ __global__ void __launch_bounds__(64) k_pcw_diag(int nR, int ld, int Np, size_t 
 // of v_mfma_f64_16x16x4: A lane = A[row lane & 15][k lane >> 4], B lane = B[k lane >> 4][column lane & 15].  K is the contiguous axis,
 // so a lane loads FOUR consecutive radii of its row (16 c + 4 (lane >> 4) ..) and step j of the chunk multiplies the j-th of them:
 // the four k of a step are 16 c + 4 q + j, q = 0..3, the same in A and B, which permutes the sum over k and nothing else.
-// part [G, 4 Np, 4 Np]; the upper macro tiles are never written and never read.
+// part [NW, G, 4 Np, 4 Np]; the upper macro tiles are never written and never read.  NW weight rows w [NW, ld] share the loads of X
+// and the A operand; only b = w_k x differs, so a row's product does not depend on NW.
+// SQ: the non-symmetric product Y~ diag(w) X~^T of the index rows, Y the four d / dm planes that follow X (row + 4 Np), masked by the
+// same rule: blockIdx.x walks the full square of macro tiles, part [G, 4 Np, 4 Np] is written everywhere.
+template <int NW, bool SQ>
 __global__ void __launch_bounds__(64) k_pcw_gram(int Np, int ld, int nChunks, int G, const double *__restrict__ X, const double *__restrict__ w,
                                                  const int *__restrict__ nmax, double *__restrict__ part) {
   const int lane = threadIdx.x, lr = lane & 15, lq = lane >> 4;
-  int R = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
-  while ((R + 1) * (R + 2) / 2 <= (int)blockIdx.x) ++R;
-  while (R * (R + 1) / 2 > (int)blockIdx.x) --R;
-  const int C = (int)blockIdx.x - R * (R + 1) / 2;
   const int M = 4 * Np;
+  int R, C;
+  if constexpr (SQ) {
+    R = (int)blockIdx.x / (M / kMacro), C = (int)blockIdx.x % (M / kMacro);
+  } else {
+    R = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
+    while ((R + 1) * (R + 2) / 2 <= (int)blockIdx.x) ++R;
+    while (R * (R + 1) / 2 > (int)blockIdx.x) --R;
+    C = (int)blockIdx.x - R * (R + 1) / 2;
+  }
+  const double *XA = SQ ? X + (size_t)M * ld : X;  // the A operand's planes
   int row[2], col[2], prow[2], pcol[2];  // X rows of the lane in the two row tiles and the two column tiles; their order index
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     row[t] = kMacro * R + 16 * t + lr, col[t] = kMacro * C + 16 * t + lr;
     prow[t] = row[t] % Np, pcol[t] = col[t] % Np;
   }
-  d4 acc[2][2];
+  d4 acc[NW][2][2];
 #pragma unroll
-  for (int s = 0; s < 2; ++s)
+  for (int k = 0; k < NW; ++k)
 #pragma unroll
-    for (int t = 0; t < 2; ++t) acc[s][t] = (d4){0.0, 0.0, 0.0, 0.0};
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) acc[k][s][t] = (d4){0.0, 0.0, 0.0, 0.0};
   for (int c = blockIdx.y; c < nChunks; c += G) {
     const int i0 = kChunk * c + 4 * lq;
-    double wk[4];
+    double wk[NW][4];
     int keep[4];  // order index p stays where p + 1 < n_max,i
 #pragma unroll
-    for (int j = 0; j < 4; ++j) wk[j] = w[i0 + j], keep[j] = nmax[i0 + j] - 1;
-    double a[2][4], b[2][4];
+    for (int j = 0; j < 4; ++j) {
+      keep[j] = nmax[i0 + j] - 1;
+#pragma unroll
+      for (int k = 0; k < NW; ++k) wk[k][j] = w[(size_t)k * ld + i0 + j];
+    }
+    double a[2][4], b[NW][2][4];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const double va = X[(size_t)row[t] * ld + i0 + j], vb = X[(size_t)col[t] * ld + i0 + j];
+        const double va = XA[(size_t)row[t] * ld + i0 + j], vb = X[(size_t)col[t] * ld + i0 + j];
         a[t][j] = prow[t] < keep[j] ? va : 0.0;
-        b[t][j] = pcol[t] < keep[j] ? wk[j] * vb : 0.0;
+#pragma unroll
+        for (int k = 0; k < NW; ++k) b[k][t][j] = pcol[t] < keep[j] ? wk[k][j] * vb : 0.0;
       }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int s = 0; s < 2; ++s)
+      for (int k = 0; k < NW; ++k)
 #pragma unroll
-        for (int t = 0; t < 2; ++t) acc[s][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][j], b[t][j], acc[s][t], 0, 0, 0);
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int t = 0; t < 2; ++t) acc[k][s][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][j], b[k][t][j], acc[k][s][t], 0, 0, 0);
   }
-  double *out = part + (size_t)blockIdx.y * M * M;
 #pragma unroll
-  for (int s = 0; s < 2; ++s)
+  for (int k = 0; k < NW; ++k) {
+    double *out = part + ((size_t)k * G + blockIdx.y) * M * M;
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+    for (int s = 0; s < 2; ++s)
 #pragma unroll
-      for (int r = 0; r < 4; ++r)  // C lane, register r = C[row (lane >> 4) + 4 r][column lane & 15]
-        out[(size_t)(kMacro * R + 16 * s + lq + 4 * r) * M + kMacro * C + 16 * t + lr] = acc[s][t][r];
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)  // C lane, register r = C[row (lane >> 4) + 4 r][column lane & 15]
+          out[(size_t)(kMacro * R + 16 * s + lq + 4 * r) * M + kMacro * C + 16 * t + lr] = acc[k][s][t][r];
+  }
 }
 
 // ---- (d) chunk sum and the planes of (e) -----------------------------------------------------------------------------------
@@ -191,10 +247,15 @@ __global__ void __launch_bounds__(64) k_pcw_gram(int Np, int ld, int nChunks, in
 //   2, 3: anam + bnam - anbm - bnbm    4, 5: anam' - bnam' + anbm' - bnbm'           (:151; ' the conjugate)
 // each added in the order written there.  diag2 [2, Np]: anan - anbn + bnan - bnbn (:159).  pairs, when given: the four complex
 // averages themselves as eight arrays [N, N], entry [m - 1][n - 1] (test access).
+// MODE 0: part is the symmetric product of one weight row.  MODE 1 (d / dn_r) and 2 (d / dn_i): part is H = Y~ diag(w_0) X~^T of
+// k_pcw_gram<1, true>, and what stands for the product is its derivative dG[(q1, n), (q2, m)] = Hd[(q1, n), (q2, m)] + Hd[(q2, m),
+// (q1, n)], Hd the rows of H mapped to the parameter: d / dn_r of a plane pair (Re, Im) is (Re y, Im y), d / dn_i is (-Im y, Re y).
+// Everything after g is the same text, so the derivative planes are added in the order of the value planes.
 struct PcwPairsOut {
   double *p[8];
 };
 
+template <int MODE>
 __global__ void __launch_bounds__(256) k_pcw_combine(int N, int Np, int G, const double *__restrict__ part, double *__restrict__ Q,
                                                      double *__restrict__ diag2, PcwPairsOut po) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -203,16 +264,26 @@ __global__ void __launch_bounds__(256) k_pcw_combine(int N, int Np, int G, const
   const int M = 4 * Np;
   const size_t MM = (size_t)M * M;
   // sum_i w_i X~[qa Np + pn, i] X~[qb Np + pm, i]: the product is symmetric, stored where the row's macro tile is not above the column's
-  auto g = [&](int qa, int qb) {
-    int r1 = qa * Np + pn, r2 = qb * Np + pm;
-    if (r1 / kMacro < r2 / kMacro) {
-      const int t = r1;
-      r1 = r2, r2 = t;
-    }
+  auto chunk_sum = [&](int r1, int r2) {
     const double *p = part + (size_t)r1 * M + r2;
     double v = 0.0;
     for (int c = 0; c < G; ++c) v += p[c * MM];
     return v;
+  };
+  // row (q, p) of Hd against X row r2: plane q of dX / dn_r is plane q of Y, of dX / dn_i plane q ^ 1 with the sign of i y
+  auto hd = [&](int q, int p, int r2) {
+    if constexpr (MODE == 1) return chunk_sum(q * Np + p, r2);
+    const double v = chunk_sum((q ^ 1) * Np + p, r2);
+    return (q & 1) ? v : -v;
+  };
+  auto g = [&](int qa, int qb) {
+    int r1 = qa * Np + pn, r2 = qb * Np + pm;
+    if constexpr (MODE != 0) return hd(qa, pn, r2) + hd(qb, pm, r1);
+    if (r1 / kMacro < r2 / kMacro) {
+      const int t = r1;
+      r1 = r2, r2 = t;
+    }
+    return chunk_sum(r1, r2);
   };
   // conj(u_n) v_m = (ur_n vr_m + ui_n vi_m) + i (ur_n vi_m - ui_n vr_m); planes: 0 Re a, 1 Im a, 2 Re b, 3 Im b
   double re[4], im[4];  // anam, anbm, bnam, bnbm
@@ -242,20 +313,30 @@ __global__ void __launch_bounds__(256) k_pcw_combine(int N, int Np, int G, const
 }
 
 // ---- (e) the symbols and the sums S_l, fused --------------------------------------------------------------------------------
-// Workgroup blockIdx.x is the degree l = 0 .. 2 N - 2 (the reference's l - 1), thread t takes n = t + 1, t + 1 + 256, ...  A lane
+// A workgroup is one degree l = 0 .. 2 N - 2 (the reference's l - 1), the highest first: a column's walk is min(2 n, l) steps long, so
+// the long workgroups start first and the short ones fill the device behind them.  Thread t takes n = t + 1, t + 1 + 256, ...  A lane
 // walks its column from m = n + l down to max(l - n, n): steps with m > N only advance the recursion and read nothing; the terms
 // with max(l - n, n + 1) <= m <= min(l + n, N) go into the first sums of compute_Sl, m = n into the second.  diag as k_pcw_diag
 // writes it, Q and diag2 as k_pcw_combine.  greek [6, 2 N - 1] in the order alpha, beta, gamma, delta, epsilon, zeta, not divided by
 // C_sca.  The 12 sums (first and second of S00, S0-0, S22, S2-2, Re S02, Im S02) are reduced over the workgroup by a fixed tree.
+// NO output rows share ONE walk: a lane produces each symbol once and accumulates every row from that row's Q [NO, 6, Np, Np], diag
+// [NO, 4, Np] and diag2 [NO, 2, Np] into 12 NO registers; greek [NO, 6, 2 N - 1].  A row's statements and its reduction tree are
+// those of NO = 1, so a row does not depend on what else is in the call.  The rows are reduced one after the other through the
+// same 24 KiB of LDS.
+template <int NO>
 __global__ void __launch_bounds__(kSumThreads) k_pcw_sums(int N, int Np, const double *__restrict__ Q, const double *__restrict__ diag,
                                                           const double *__restrict__ diag2, const double *__restrict__ fac, double pi,
                                                           double k2, double *__restrict__ greek) {
 #pragma clang fp contract(off)
   __shared__ double red[12][kSumThreads];
-  const int l = blockIdx.x, tid = threadIdx.x;
+  const int l = 2 * N - 2 - (int)blockIdx.x, tid = threadIdx.x;
   const size_t QQ = (size_t)Np * Np;
   const double fl = fac[l];
-  double f[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double f[NO][6], s[NO][6];
+#pragma unroll
+  for (int r = 0; r < NO; ++r)
+#pragma unroll
+    for (int q = 0; q < 6; ++q) f[r][q] = 0.0, s[r][q] = 0.0;
   for (int n = tid + 1; n <= N; n += kSumThreads) {
     const int lo = max(l - n, n), m_star = max(l - n, n + 1);
     if (lo > N) continue;
@@ -269,50 +350,63 @@ __global__ void __launch_bounds__(kSumThreads) k_pcw_sums(int N, int Np, const d
         if (m >= m_star) {
           const size_t o = (size_t)(m - n) * Np + (n - 1);
           const long long sg = ((l + n + m) & 1) ? -1 : 1, c2 = 2 * (2 * (long long)m + 1) * c1;
-          const double p1 = Q[o], p2 = Q[QQ + o];
-          f[0] += (p1 * (A * A)) * (double)c2;
-          f[1] += (p2 * (A * A)) * (double)(c2 * sg);
-          f[2] += (p1 * (B * B)) * (double)c2;
-          f[3] += (p2 * (B * B)) * (double)(c2 * sg);
-          const double ar = (double)sg * Q[2 * QQ + o] + Q[4 * QQ + o], ai = (double)sg * Q[3 * QQ + o] + Q[5 * QQ + o];
-          f[4] += ar * 2.0 * (double)c1 * (double)(2 * m + 1) * A * B;
-          f[5] += ai * 2.0 * (double)c1 * (double)(2 * m + 1) * A * B;
+#pragma unroll
+          for (int r = 0; r < NO; ++r) {
+            const double *Qr = Q + (size_t)r * 6 * QQ;
+            const double p1 = Qr[o], p2 = Qr[QQ + o];
+            f[r][0] += (p1 * (A * A)) * (double)c2;
+            f[r][1] += (p2 * (A * A)) * (double)(c2 * sg);
+            f[r][2] += (p1 * (B * B)) * (double)c2;
+            f[r][3] += (p2 * (B * B)) * (double)(c2 * sg);
+            const double ar = (double)sg * Qr[2 * QQ + o] + Qr[4 * QQ + o], ai = (double)sg * Qr[3 * QQ + o] + Qr[5 * QQ + o];
+            f[r][4] += ar * 2.0 * (double)c1 * (double)(2 * m + 1) * A * B;
+            f[r][5] += ai * 2.0 * (double)c1 * (double)(2 * m + 1) * A * B;
+          }
         }
         if (m == n) {
           const long long sgl = (l & 1) ? -1 : 1;
-          s[0] += (diag[n - 1] * (A * A)) * (double)(c1 * c1);
-          s[1] += (diag[Np + n - 1] * (A * A)) * (double)(c1 * c1 * sgl);
-          s[2] += (diag[n - 1] * (B * B)) * (double)(c1 * c1);
-          s[3] += (diag[Np + n - 1] * (B * B)) * (double)(c1 * c1 * sgl);
-          s[4] += diag2[n - 1] * 2.0 * (double)c1 * (double)c1 * A * B;
-          s[5] += diag2[Np + n - 1] * 2.0 * (double)c1 * (double)c1 * A * B;
+#pragma unroll
+          for (int r = 0; r < NO; ++r) {
+            const double *dr = diag + (size_t)r * 4 * Np, *d2 = diag2 + (size_t)r * 2 * Np;
+            s[r][0] += (dr[n - 1] * (A * A)) * (double)(c1 * c1);
+            s[r][1] += (dr[Np + n - 1] * (A * A)) * (double)(c1 * c1 * sgl);
+            s[r][2] += (dr[n - 1] * (B * B)) * (double)(c1 * c1);
+            s[r][3] += (dr[Np + n - 1] * (B * B)) * (double)(c1 * c1 * sgl);
+            s[r][4] += d2[n - 1] * 2.0 * (double)c1 * (double)c1 * A * B;
+            s[r][5] += d2[Np + n - 1] * 2.0 * (double)c1 * (double)c1 * A * B;
+          }
         }
       }
       if (m == lo) break;
       c.step();
     }
   }
+  const size_t L = (size_t)2 * N - 1;
 #pragma unroll
-  for (int q = 0; q < 6; ++q) red[q][tid] = f[q], red[6 + q][tid] = s[q];
-  __syncthreads();
-  for (int h = kSumThreads / 2; h > 0; h >>= 1) {
-    if (tid < h)
+  for (int r = 0; r < NO; ++r) {
+    // the tree below ends with a barrier, and thread 0 reads only its own slots after it: the next row may be written at once
 #pragma unroll
-      for (int q = 0; q < 12; ++q) red[q][tid] += red[q][tid + h];
+    for (int q = 0; q < 6; ++q) red[q][tid] = f[r][q], red[6 + q][tid] = s[r][q];
     __syncthreads();
-  }
-  if (tid == 0) {
-    const double coef = (double)(2 * l + 1) * pi / k2;
-    double S[6];  // S00, S0-0, S22, S2-2, Re S02, Im S02
+    for (int h = kSumThreads / 2; h > 0; h >>= 1) {
+      if (tid < h)
 #pragma unroll
-    for (int q = 0; q < 6; ++q) S[q] = coef * (red[q][0] + red[6 + q][0]);
-    const size_t L = (size_t)2 * N - 1;
-    greek[l] = S[2] + S[3];
-    greek[L + l] = S[0] + S[1];
-    greek[2 * L + l] = S[4];
-    greek[3 * L + l] = S[0] - S[1];
-    greek[4 * L + l] = S[5];
-    greek[5 * L + l] = S[2] - S[3];
+        for (int q = 0; q < 12; ++q) red[q][tid] += red[q][tid + h];
+      __syncthreads();
+    }
+    if (tid == 0) {
+      const double coef = (double)(2 * l + 1) * pi / k2;
+      double S[6];  // S00, S0-0, S22, S2-2, Re S02, Im S02
+#pragma unroll
+      for (int q = 0; q < 6; ++q) S[q] = coef * (red[q][0] + red[6 + q][0]);
+      double *gr = greek + (size_t)r * 6 * L;
+      gr[l] = S[2] + S[3];
+      gr[L + l] = S[0] + S[1];
+      gr[2 * L + l] = S[4];
+      gr[3 * L + l] = S[0] - S[1];
+      gr[4 * L + l] = S[5];
+      gr[5 * L + l] = S[2] - S[3];
+    }
   }
 }
 
@@ -358,17 +452,61 @@ std::vector<double> pcw_fac(int n) {
   return f;
 }
 
-// mom_mie_pcw (pairs null) and mom_pcw_pair_averages (pairs given: stops after (d))
-int pcw_run(const char *fn, int device, int nR, const double *r, const double *w, double lambda, double n_r, double n_i, int N, int flags,
-            double *const *pairs, double *greek, double *C, double *gpu_ms) {
+// The launches of (b), (c) and (e) by their template arguments
+void launch_diag(hipStream_t st, int nW, bool index, int N, int nR, int ld, int Np, size_t ps, const double *pl, const double *w, double *diag) {
+#define PCW_DIAG(NW, IDX) hipLaunchKernelGGL((k_pcw_diag<NW, IDX>), dim3(N), dim3(64), 0, st, nR, ld, Np, ps, pl, w, diag)
+  switch (2 * nW + (index ? 1 : 0)) {
+    case 2: PCW_DIAG(1, false); break;
+    case 3: PCW_DIAG(1, true); break;
+    case 4: PCW_DIAG(2, false); break;
+    case 5: PCW_DIAG(2, true); break;
+    case 6: PCW_DIAG(3, false); break;
+    default: PCW_DIAG(3, true); break;
+  }
+#undef PCW_DIAG
+}
+
+void launch_gram(hipStream_t st, int nW, int nMacro, int G, int Np, int ld, int nChunks, const double *X, const double *w, const int *nmax,
+                 double *part) {
+#define PCW_GRAM(NW) hipLaunchKernelGGL((k_pcw_gram<NW, false>), dim3(nMacro, G), dim3(64), 0, st, Np, ld, nChunks, G, X, w, nmax, part)
+  switch (nW) {
+    case 1: PCW_GRAM(1); break;
+    case 2: PCW_GRAM(2); break;
+    default: PCW_GRAM(3); break;
+  }
+#undef PCW_GRAM
+}
+
+void launch_sums(hipStream_t st, int nO, int L, int N, int Np, const double *Q, const double *diag, const double *diag2, const double *fac,
+                 double k2, double *greek) {
+#define PCW_SUMS(NO) hipLaunchKernelGGL((k_pcw_sums<NO>), dim3((unsigned)L), dim3(kSumThreads), 0, st, N, Np, Q, diag, diag2, fac, M_PI, k2, greek)
+  switch (nO) {
+    case 1: PCW_SUMS(1); break;
+    case 2: PCW_SUMS(2); break;
+    case 3: PCW_SUMS(3); break;
+    case 4: PCW_SUMS(4); break;
+    default: PCW_SUMS(5); break;
+  }
+#undef PCW_SUMS
+}
+
+// All four entry points.  w [nW, nR]; index: two more output rows, d / dn_r and d / dn_i of row 0 (nO = nW + 2).  pairs null: greek
+// [nO, 6, L] and C [nO, 2]; pairs given, nO x 8 arrays [N, N]: stops after (d).  A weight row k takes the launches, the chunk groups
+// (G) and the statements of the single-row call, so its results are bitwise those of mom_mie_pcw(w[k]); the index rows' product has
+// a chunk group count of its own (GH), sized for the full square of macro tiles.
+int pcw_run(const char *fn, int device, int nR, const double *r, int nW, const double *w, double lambda, double n_r, double n_i, int N, int flags,
+            int known_flags, double *const *pairs, double *greek, double *C, double *gpu_ms) {
   if (nR < 1) return pcw_fail(fn, "nR must be at least 1");
+  if (nW < 1 || nW > MOM_PCW_MAX_WEIGHT_ROWS) return pcw_fail(fn, "nW must be 1..3");
   if (!(lambda > 0.0)) return pcw_fail(fn, "lambda must be positive");
   if (!(n_i >= 0.0) || !std::isfinite(n_r) || !std::isfinite(n_i)) return pcw_fail(fn, "n_i must be >= 0 (m = n_r + i n_i)");
   if (N < 1 || N > kMaxOrder) return pcw_fail(fn, "N_max must be 1..640 (MOM_PCW_MAX_ORDER)");
-  if (flags != 0) return pcw_fail(fn, "unknown flag");
+  if (flags & ~known_flags) return pcw_fail(fn, "unknown flag");
+  const bool index = (flags & MOM_PCW_INDEX_ROWS) != 0;
+  const int nO = nW + (index ? 2 : 0);
   if (!r || !w || (!pairs && (!greek || !C))) return pcw_fail(fn, "null pointer");
   if (pairs)
-    for (int q = 0; q < 8; ++q)
+    for (int q = 0; q < 8 * nO; ++q)
       if (!pairs[q]) return pcw_fail(fn, "null pointer");
   if (!(r[0] > 0.0) || !std::isfinite(r[nR - 1])) return pcw_fail(fn, "r[0] must be positive and r finite");
   for (int i = 1; i < nR; ++i)
@@ -386,13 +524,17 @@ int pcw_run(const char *fn, int device, int nR, const double *r, const double *w
   const int nChunks = (int)(ld / kChunk), nRows = (int)(M / kMacro), nMacro = nRows * (nRows + 1) / 2;
   int G = 4096 / nMacro;  // about four wavefronts per SIMD of the device
   G = G < 1 ? 1 : (G > nChunks ? nChunks : G);
-  // one allocation, carved in doubles: planes | w | diag [4, Np] | diag2 [2, Np] | fac [L] | Q [6, Np, Np] | greek [6, L] |
-  // part [G, M, M] | pairs [8, N, N] | the workspace of the coefficient kernel
-  const size_t nQ = 6 * Np * Np, nPart = (size_t)G * M * M, nPairs = pairs ? 8 * (size_t)N * N : 0;
-  const size_t nDbl = 4 * ps + ld + 6 * Np + L + nQ + 6 * L + nPart + nPairs;
-  const size_t bytes = nDbl * sizeof(double) + mom_mie_ab::workspace_bytes(N, ld);
+  int GH = 4096 / (nRows * nRows);  // the same for the square of the index rows' product
+  GH = GH < 1 ? 1 : (GH > nChunks ? nChunks : GH);
+  // one allocation, carved in doubles: planes (index: eight) | w [nW, ld] | diag [nO, 4, Np] | diag2 [nO, 2, Np] | fac [L] |
+  // Q [nO, 6, Np, Np] | greek [nO, 6, L] | part [nW, G, M, M] | partH [GH, M, M] | pairs [nO, 8, N, N] | the workspace of the
+  // coefficient kernel
+  const size_t nPl = (index ? 8 : 4) * ps, nQ = 6 * Np * Np, nPart = (size_t)nW * G * M * M, nPartH = index ? (size_t)GH * M * M : 0;
+  const size_t nPairs = pairs ? 8 * (size_t)N * N : 0;
+  const size_t nDbl = nPl + nW * ld + nO * 6 * Np + L + nO * nQ + nO * 6 * L + nPart + nPartH + nO * nPairs;
+  const size_t bytes = nDbl * sizeof(double) + mom_mie_ab::workspace_bytes(N, ld, index);
   const std::vector<double> hfac = pcw_fac((int)L);
-  std::vector<double> hdiag(4 * Np);
+  std::vector<double> hdiag((size_t)nO * 4 * Np);
   char *base = nullptr;
   hipStream_t st = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -401,57 +543,73 @@ int pcw_run(const char *fn, int device, int nR, const double *r, const double *w
   PCHK(hipMalloc((void **)&base, bytes));
   {
     double *p = (double *)base;
-    double *d_pl = p; p += 4 * ps;
-    double *d_w = p; p += ld;
-    double *d_diag = p; p += 4 * Np;
-    double *d_diag2 = p; p += 2 * Np;
+    double *d_pl = p; p += nPl;
+    double *d_w = p; p += nW * ld;
+    double *d_diag = p; p += nO * 4 * Np;
+    double *d_diag2 = p; p += nO * 2 * Np;
     double *d_fac = p; p += L;
-    double *d_Q = p; p += nQ;
-    double *d_greek = p; p += 6 * L;
+    double *d_Q = p; p += nO * nQ;
+    double *d_greek = p; p += nO * 6 * L;
     double *d_part = p; p += nPart;
-    double *d_pairs = p; p += nPairs;
+    double *d_partH = p; p += nPartH;
+    double *d_pairs = p; p += nO * nPairs;
     const size_t nZero = (size_t)((char *)d_part - base);  // planes (rows above n_max,i, padding), w padding, Q; part is written where read
     const int *d_nmax = nullptr;
     PCHK(hipMemsetAsync(base, 0, nZero, st));
-    if (nPairs) PCHK(hipMemsetAsync(d_pairs, 0, nPairs * sizeof(double), st));
-    PCHK(hipMemcpyAsync(d_w, w, (size_t)nR * sizeof(double), hipMemcpyHostToDevice, st));
+    if (nPairs) PCHK(hipMemsetAsync(d_pairs, 0, nO * nPairs * sizeof(double), st));
+    for (int k = 0; k < nW; ++k)
+      PCHK(hipMemcpyAsync(d_w + k * ld, w + (size_t)k * nR, (size_t)nR * sizeof(double), hipMemcpyHostToDevice, st));
     PCHK(hipMemcpyAsync(d_fac, hfac.data(), L * sizeof(double), hipMemcpyHostToDevice, st));
     for (int q = 0; q < 4; ++q) PCHK(hipEventCreate(&ev[q]));
-    rc = mom_mie_ab::launch(fn, st, nR, ld, hx.data(), n_r, n_i, N, ps, d_pl, (char *)p, nullptr, &d_nmax, ev[0], ev[1]);
+    rc = mom_mie_ab::launch(fn, st, nR, ld, hx.data(), n_r, n_i, N, ps, d_pl, (char *)p, nullptr, &d_nmax, ev[0], ev[1], index);
     if (rc != MOM_OK) goto done;
-    hipLaunchKernelGGL(k_pcw_diag, dim3(N), dim3(64), 0, st, nR, (int)ld, (int)Np, ps, d_pl, d_w, d_diag);
+    launch_diag(st, nW, index, N, nR, (int)ld, (int)Np, ps, d_pl, d_w, d_diag);
     PCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_pcw_gram, dim3(nMacro, G), dim3(64), 0, st, (int)Np, (int)ld, nChunks, G, d_pl, d_w, d_nmax, d_part);
+    launch_gram(st, nW, nMacro, G, (int)Np, (int)ld, nChunks, d_pl, d_w, d_nmax, d_part);
     PCHK(hipGetLastError());
-    {
+    if (index) {
+      hipLaunchKernelGGL((k_pcw_gram<1, true>), dim3(nRows * nRows, GH), dim3(64), 0, st, (int)Np, (int)ld, nChunks, GH, d_pl, d_w, d_nmax, d_partH);
+      PCHK(hipGetLastError());
+    }
+    for (int k = 0; k < nO; ++k) {
       PcwPairsOut po;
-      for (int q = 0; q < 8; ++q) po.p[q] = pairs ? d_pairs + (size_t)q * N * N : nullptr;
-      hipLaunchKernelGGL(k_pcw_combine, dim3((unsigned)((Np * Np + 255) / 256)), dim3(256), 0, st, N, (int)Np, G, d_part, d_Q, d_diag2, po);
+      for (int q = 0; q < 8; ++q) po.p[q] = pairs ? d_pairs + ((size_t)k * 8 + q) * N * N : nullptr;
+      const dim3 grid((unsigned)((Np * Np + 255) / 256));
+      double *Qk = d_Q + k * nQ, *d2k = d_diag2 + k * 2 * Np;
+      if (k < nW)
+        hipLaunchKernelGGL(k_pcw_combine<0>, grid, dim3(256), 0, st, N, (int)Np, G, d_part + (size_t)k * G * M * M, Qk, d2k, po);
+      else if (k == nW)
+        hipLaunchKernelGGL(k_pcw_combine<1>, grid, dim3(256), 0, st, N, (int)Np, GH, d_partH, Qk, d2k, po);
+      else
+        hipLaunchKernelGGL(k_pcw_combine<2>, grid, dim3(256), 0, st, N, (int)Np, GH, d_partH, Qk, d2k, po);
       PCHK(hipGetLastError());
     }
     PCHK(hipEventRecord(ev[2], st));
     if (!pairs) {
-      hipLaunchKernelGGL(k_pcw_sums, dim3((unsigned)L), dim3(kSumThreads), 0, st, N, (int)Np, d_Q, d_diag, d_diag2, d_fac, M_PI, kw * kw, d_greek);
+      launch_sums(st, nO, (int)L, N, (int)Np, d_Q, d_diag, d_diag2, d_fac, kw * kw, d_greek);
       PCHK(hipGetLastError());
     }
     PCHK(hipEventRecord(ev[3], st));
     if (pairs) {
-      for (int q = 0; q < 8; ++q)
+      for (int q = 0; q < 8 * nO; ++q)
         PCHK(hipMemcpyAsync(pairs[q], d_pairs + (size_t)q * N * N, (size_t)N * N * sizeof(double), hipMemcpyDeviceToHost, st));
     } else {
-      PCHK(hipMemcpyAsync(greek, d_greek, 6 * L * sizeof(double), hipMemcpyDeviceToHost, st));
-      PCHK(hipMemcpyAsync(hdiag.data(), d_diag, 4 * Np * sizeof(double), hipMemcpyDeviceToHost, st));
+      PCHK(hipMemcpyAsync(greek, d_greek, nO * 6 * L * sizeof(double), hipMemcpyDeviceToHost, st));
+      PCHK(hipMemcpyAsync(hdiag.data(), d_diag, hdiag.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     PCHK(hipStreamSynchronize(st));
     if (!pairs) {
-      // compute_avg_C_scatt_ext: 2 pi / k^2 (2 n + 1) times the weighted sums of k_pcw_diag, added in the order of n
-      double cs = 0.0, ce = 0.0;
-      for (int n = 1; n <= N; ++n) {
-        const double coef = 2.0 * M_PI / (kw * kw) * (double)(2 * n + 1);
-        cs += coef * hdiag[2 * Np + n - 1];
-        ce += coef * hdiag[3 * Np + n - 1];
+      // compute_avg_C_scatt_ext: 2 pi / k^2 (2 n + 1) times the weighted sums of k_pcw_diag, added in the order of n, per row
+      for (int k = 0; k < nO; ++k) {
+        const double *hd = hdiag.data() + (size_t)k * 4 * Np;
+        double cs = 0.0, ce = 0.0;
+        for (int n = 1; n <= N; ++n) {
+          const double coef = 2.0 * M_PI / (kw * kw) * (double)(2 * n + 1);
+          cs += coef * hd[2 * Np + n - 1];
+          ce += coef * hd[3 * Np + n - 1];
+        }
+        C[2 * k] = cs, C[2 * k + 1] = ce;
       }
-      C[0] = cs, C[1] = ce;
     }
     if (gpu_ms)
       for (int q = 0; q < 3; ++q) {
@@ -505,14 +663,29 @@ done:
 
 extern "C" int mom_mie_pcw(int device, int nR, const double *r, const double *w, double lambda, double n_r, double n_i, int N_max, int flags,
                            double *greek, double *C, double *gpu_ms) {
-  return pcw_run("mom_mie_pcw", device, nR, r, w, lambda, n_r, n_i, N_max, flags, nullptr, greek, C, gpu_ms);
+  return pcw_run("mom_mie_pcw", device, nR, r, 1, w, lambda, n_r, n_i, N_max, flags, 0, nullptr, greek, C, gpu_ms);
+}
+
+extern "C" int mom_mie_pcw_dual(int device, int nR, const double *r, int nW, const double *w, double lambda, double n_r, double n_i, int N_max,
+                                int flags, double *greek, double *C, double *gpu_ms) {
+  return pcw_run("mom_mie_pcw_dual", device, nR, r, nW, w, lambda, n_r, n_i, N_max, flags, MOM_PCW_INDEX_ROWS, nullptr, greek, C, gpu_ms);
 }
 
 extern "C" int mom_pcw_pair_averages(int device, int nR, const double *r, const double *w, double lambda, double n_r, double n_i, int N_max,
                                      double *anam_re, double *anam_im, double *anbm_re, double *anbm_im, double *bnam_re, double *bnam_im,
                                      double *bnbm_re, double *bnbm_im) {
   double *const pairs[8] = {anam_re, anam_im, anbm_re, anbm_im, bnam_re, bnam_im, bnbm_re, bnbm_im};
-  return pcw_run("mom_pcw_pair_averages", device, nR, r, w, lambda, n_r, n_i, N_max, 0, pairs, nullptr, nullptr, nullptr);
+  return pcw_run("mom_pcw_pair_averages", device, nR, r, 1, w, lambda, n_r, n_i, N_max, 0, 0, pairs, nullptr, nullptr, nullptr);
+}
+
+extern "C" int mom_pcw_pair_averages_dual(int device, int nR, const double *r, int nW, const double *w, double lambda, double n_r, double n_i,
+                                          int N_max, int flags, double *pairs) {
+  const char *fn = "mom_pcw_pair_averages_dual";
+  if (!pairs) return pcw_fail(fn, "null pointer");
+  if (N_max < 1 || N_max > kMaxOrder) return pcw_fail(fn, "N_max must be 1..640 (MOM_PCW_MAX_ORDER)");
+  double *out[8 * (MOM_PCW_MAX_WEIGHT_ROWS + 2)];
+  for (int q = 0; q < 8 * (MOM_PCW_MAX_WEIGHT_ROWS + 2); ++q) out[q] = pairs + (size_t)q * N_max * N_max;
+  return pcw_run(fn, device, nR, r, nW, w, lambda, n_r, n_i, N_max, flags, MOM_PCW_INDEX_ROWS, out, nullptr, nullptr, nullptr);
 }
 
 extern "C" int mom_wigner_tables(int device, int m_max, int n_max, int l_max, double *A, double *B) {

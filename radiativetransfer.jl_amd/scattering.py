@@ -11,7 +11,8 @@ angle grid, whose tables the device builds itself (mom_mie_tables): there the ho
 A PCW() model takes the Domke-PCW route (mom_mie_pcw, csrc/mom_pcw.hip): the Greek coefficients expanded directly in the Mie
 coefficients with Wigner 3j symbols, no angle quadrature -- the independent check of NAI-2.  The device produces the symbols in
 registers, so the model's wigner_A / wigner_B are accepted and not needed; compute_wigner_values returns the reference's two tables
-for whoever wants them (mom_wigner_tables).  The host brings the radii and w_x and divides by C_sca.  No partials on this route.
+for whoever wants them (mom_wigner_tables).  The host brings the radii and w_x and divides by C_sca.  aerosol_optics_jacobian
+returns the optics with their partials in (r_m, σ_g, nᵣ, nᵢ) on the model's own route: for PCW() one mom_mie_pcw_dual call.
 Float64 only.  There is no CPU fallback.
 """
 from __future__ import annotations
@@ -66,7 +67,7 @@ class NAI2:
 
 @dataclass
 class PCW:
-    """Domke's expansion in Wigner 3j symbols (Sanghavi 2014, eq. 22-24): values only."""
+    """Domke's expansion in Wigner 3j symbols (Sanghavi 2014, eq. 22-24); partials through aerosol_optics_jacobian."""
 
 
 @dataclass
@@ -201,8 +202,8 @@ class MieInputs:
     T2: np.ndarray
 
 
-def _radii_and_weight_rows(model: MieModel, autodiff: bool):
-    """(r, w [nW, nR]) of the model: the radius quadrature and 4π r² times wₓ (and, autodiff, its partials)"""
+def _radii_and_wx_rows(model: MieModel, autodiff: bool):
+    """(r, rows [nW, nR]) of the model: the radius quadrature, wₓ and (autodiff) ∂wₓ/∂(r_m, σ_g)"""
     aer = model.aerosol
     r, wᵣ = gauleg(model.nquad_radius, 0.0, model.r_max, norm=True)
     # compute_wₓ (mie_helper_functions.jl:266-276): wₓ = pdf wᵣ / Σ pdf wᵣ
@@ -211,7 +212,13 @@ def _radii_and_weight_rows(model: MieModel, autodiff: bool):
     if autodiff:
         for dp in aer.size_distribution.dpdf(r) * wᵣ:
             rows.append(dp / p.sum() - p * dp.sum() / p.sum() ** 2)
-    return r, 4 * math.pi * r ** 2 * np.stack(rows)
+    return r, np.stack(rows)
+
+
+def _radii_and_weight_rows(model: MieModel, autodiff: bool):
+    """(r, w [nW, nR]) of the model: the radius quadrature and 4π r² times wₓ (and, autodiff, its partials)"""
+    r, rows = _radii_and_wx_rows(model, autodiff)
+    return r, 4 * math.pi * r ** 2 * rows
 
 
 def mie_inputs(model: MieModel, autodiff: bool = False) -> MieInputs:
@@ -280,6 +287,46 @@ def _pcw_optics(model: MieModel):
     return rt.AerosolOptics(greek_coefs=_greek((1 / Cs) * greek), ω̃=float(Cs / Ce), fᵗ=1.0, k=float(Ce))
 
 
+def _checked_wrt(wrt):
+    wrt = tuple(wrt)
+    unknown = [p for p in wrt if p not in ALL_AEROSOL_PARAMETERS]
+    if unknown or len(set(wrt)) != len(wrt):
+        raise ValueError(f"wrt must be distinct names out of {ALL_AEROSOL_PARAMETERS}, got {wrt}")
+    return wrt
+
+
+def pcw_jacobian_inputs(model: MieModel, wrt):
+    """(r, w [nW, nR], N_max, index_rows, rows) of the mom_mie_pcw_dual call for `wrt`: the (r_m, σ_g) rows of wₓ only when `wrt` names
+    one of them, the index rows only when it names nᵣ or nᵢ; rows: the parameter of each output row after row 0"""
+    size_rows = any(p in _SIZE_PARAMETERS for p in wrt)
+    index_rows = any(p in _INDEX_PARAMETERS for p in wrt)
+    r, w = _radii_and_wx_rows(model, size_rows)
+    rows = (_SIZE_PARAMETERS if size_rows else ()) + (_INDEX_PARAMETERS if index_rows else ())
+    return r, w, int(get_n_max(2 * math.pi * model.r_max / model.λ)), index_rows, rows
+
+
+def aerosol_optics_jacobian(model: MieModel, wrt=ALL_AEROSOL_PARAMETERS):
+    """(optics, [∂optics/∂p for p in wrt]) on the model's own route, wrt a subset of ALL_AEROSOL_PARAMETERS = (r_m, σ_g, nᵣ, nᵢ): what
+    the reference's compute_aerosol_optical_properties(model; autodiff=true) returns "using either computation type".  A NAI2()
+    model: compute_aerosol_optical_properties(model, autodiff=True, wrt=wrt).  A PCW() model: ONE mom_mie_pcw_dual call -- the
+    size-distribution partials are further weight rows, the index partials the Dual run -- and the host's quotient rule; the value
+    is bitwise compute_aerosol_optical_properties(model).  The two routes share the radii and wₓ and nothing after them, so each
+    checks the other's Jacobian."""
+    wrt = _checked_wrt(wrt)
+    if not isinstance(model.computation_type, PCW):
+        return compute_aerosol_optical_properties(model, autodiff=True, wrt=wrt)
+    r, w, N_max, index_rows, rows = pcw_jacobian_inputs(model, wrt)
+    greek, C, _ = _lib.mie_pcw_dual(r, w, model.λ, model.aerosol.nᵣ, model.aerosol.nᵢ, N_max, index_rows=index_rows)
+    Cs, Ce = C[0]
+    aero = rt.AerosolOptics(greek_coefs=_greek((1 / Cs) * greek[0]), ω̃=float(Cs / Ce), fᵗ=1.0, k=float(Ce))
+    partials = []
+    for k in range(1, C.shape[0]):
+        dCs, dCe = C[k]
+        dg = (1 / Cs) * greek[k] - greek[0] * dCs / Cs ** 2
+        partials.append(rt.AerosolOptics(greek_coefs=_greek(dg), ω̃=float(dCs / Ce - Cs * dCe / Ce ** 2), fᵗ=0.0, k=float(dCe)))
+    return aero, [partials[rows.index(p)] for p in wrt]
+
+
 def compute_aerosol_optical_properties(model: MieModel, autodiff: bool = False, wrt=_SIZE_PARAMETERS):
     """AerosolOptics(greek_coefs, ω̃, k, fᵗ = 1) of the model; with autodiff=True also the partials of every field with respect to
     the parameters named in `wrt`, a subset of ALL_AEROSOL_PARAMETERS = (r_m, σ_g, nᵣ, nᵢ): the median radius and geometric width
@@ -288,18 +335,16 @@ def compute_aerosol_optical_properties(model: MieModel, autodiff: bool = False, 
     further weight rows of the same sums (mom_mie_nai2); an index parameter takes the Dual run of the Mie coefficients
     (mom_mie_nai2_dual).  The default, (r_m, σ_g), is the call without `wrt`.
     The model's computation type chooses the route: NAI2() the sums over scattering angles, PCW() the expansion in Wigner 3j symbols
-    (mom_mie_pcw), which has values only (autodiff=True raises NotImplementedError)."""
+    (mom_mie_pcw), whose values this call returns; its partials are aerosol_optics_jacobian's (autodiff=True raises
+    NotImplementedError here)."""
     if isinstance(model.computation_type, PCW):
         if autodiff:
-            raise NotImplementedError("autodiff=True is NAI-2's (as in the reference): make the model with NAI2()")
+            raise NotImplementedError("autodiff=True on a PCW() model: call aerosol_optics_jacobian(model, wrt), which takes either route")
         return _pcw_optics(model)
     if not autodiff:
         _, (_, C, greek, _) = _device_call(model, False)
         return optics_from_sums(C, greek)[0]
-    wrt = tuple(wrt)
-    unknown = [p for p in wrt if p not in ALL_AEROSOL_PARAMETERS]
-    if unknown or len(set(wrt)) != len(wrt):
-        raise ValueError(f"wrt must be distinct names out of {ALL_AEROSOL_PARAMETERS}, got {wrt}")
+    wrt = _checked_wrt(wrt)
     if not any(p in _INDEX_PARAMETERS for p in wrt):
         _, (_, C, greek, _) = _device_call(model, True)
         rows = _SIZE_PARAMETERS
@@ -354,10 +399,7 @@ def compute_spectral_aerosol_optical_properties(model: MieModel, λ, nᵣ=None, 
         raise ValueError("the imaginary part of the refractive index must be >= 0")
     rows, dual, size_rows = (), False, False
     if autodiff:
-        wrt = tuple(wrt)
-        unknown = [p for p in wrt if p not in ALL_AEROSOL_PARAMETERS]
-        if unknown or len(set(wrt)) != len(wrt):
-            raise ValueError(f"wrt must be distinct names out of {ALL_AEROSOL_PARAMETERS}, got {wrt}")
+        wrt = _checked_wrt(wrt)
         dual = any(p in _INDEX_PARAMETERS for p in wrt)
         size_rows = not dual or any(p in _SIZE_PARAMETERS for p in wrt)
         rows = (_SIZE_PARAMETERS if size_rows else ()) + (_INDEX_PARAMETERS if dual else ())
